@@ -8,9 +8,12 @@ model-input assembly, cond + uncond DiT forward (L = 14 x 22 x 40 = 12320 tokens
     python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1: starts its own N ranks (launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                   # ... or is started as one of them
+    python bench.py ... --dump-outputs DIR                       # + DIR/latents.npy: what the last timed step computed
+    python bench.py ... --full                                   # + everything beyond the headline (secondary numbers,
+                                                                 #   VAE / clip timings, roofline, CPU baseline)
 
-Prints ONE JSON line (rank 0).  N > 1 shards the SAME clip (strong scaling): CFG branches and/or token shards with a
-K/V all-gather over RCCL per attention layer (frameino_amd/parallel.py).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0).  N > 1 shards the SAME clip (strong
+scaling): CFG branches and/or token shards with a K/V all-gather over RCCL per attention layer (frameino_amd/parallel.py).
 """
 import argparse
 import json
@@ -290,7 +293,15 @@ def main():
                          "--gpus says, 1 included: one rank drives real RCCL communicators of size 1.  With --plan "
                          "interleave / --exchange heads the other plans' call sequences run the same way")
     ap.add_argument("--stall-s", type=float, default=240.0, help="N>1: seconds a phase may take before the watchdog acts")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: secondary numbers, VAE and clip timings, roofline, CPU "
+                         "baseline (N>1: the measured clip and the hipGraph replay after the line).  The --no-* options "
+                         "select within it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (the latents, float32) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if (a.gpus > 1 or a.force_shard) and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(a.gpus, sys.argv[1:]))
@@ -443,6 +454,15 @@ def main():
             elapsed = time.perf_counter() - t0
         return max_over_ranks(elapsed), timer
 
+    def dump_outputs():
+        """--dump-outputs: the latents the last timed step left behind -- what `pipe._step` hands its caller -- in float32
+        (rank 0: the latents are replicated over the ranks)"""
+        if a.dump_outputs is None or rank != 0:
+            return
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "latents.npy"), st.lat.float().cpu().numpy())
+
     def kv_gather_us(plan):
         """the K|V all-gather of one layer-call on this plan's communicator, alone on the wire (HIP events, rank 0)"""
         sh = plan.shard
@@ -565,6 +585,7 @@ def main():
         dog.arm(f"timed run ({first.desc})", a.stall_s + 2.0 * total)
         elapsed, _ = timed_run(a.warmup, a.steps)
         assert torch.isfinite(st.lat).all(), "non-finite latents"
+        dump_outputs()
         issued_flops(False)
         probe = {first.desc: elapsed / a.steps * 1e3}
         gather_us = {first.desc: wire_us(first)}
@@ -646,7 +667,7 @@ def main():
         # conditions (every rank: they are 0.25 s and nothing waits on a broadcast), the sharded loop, the VAE decode in `world`
         # slabs + one all-gather (round 6), post-processing.  The steps/s line above exists already: a stall or an error here costs
         # nothing but these keys.
-        if not a.no_clip and not a.layers and not a.mxfp8 and not a.fp8_attention:
+        if a.full and not a.no_clip and not a.layers and not a.mxfp8 and not a.fp8_attention:
             try:
                 dog.arm("measured clip", a.stall_s + 120.0, fallback=line)
                 vae = bench_vae(a.workload, dev)
@@ -669,7 +690,8 @@ def main():
         dog.disarm()
         if rank == 0:
             print(line, flush=True)
-        if backend == "nccl" and not a.graph_probe and not a.no_graph_probe and (world == 1 or a.graph_probe_after_line):
+        if (a.full and backend == "nccl" and not a.graph_probe and not a.no_graph_probe
+                and (world == 1 or a.graph_probe_after_line)):
             # Round 5: the best plan's step replayed from a hipGraph AFTER the line is out (default with one rank, opt-in with
             # more: --graph-probe-after-line).  The call patterns were probed through RCCL communicators of ONE rank
             # (frameino_amd/graph_step.py); with more ranks a capture has never run here, and a fault inside a capture cannot
@@ -694,9 +716,12 @@ def main():
         dog.disarm()
         return
 
-    # ================================================================ N = 1: the headline + its evidence
-    elapsed, timer = timed_run(a.warmup, a.steps, use_graph=a.graph, timer_names=() if a.graph else ("attn_self",))
+    # ================================================================ N = 1: the headline (+ its evidence with --full)
+    # (--full: HIP events around the attention launches of the timed steps feed `roofline`)
+    elapsed, timer = timed_run(a.warmup, a.steps, use_graph=a.graph,
+                               timer_names=("attn_self",) if a.full and not a.graph else ())
     assert torch.isfinite(st.lat).all(), "non-finite latents"
+    dump_outputs()
     issued_flops(getattr(model, "dedup_shared_prefix", False) and not a.cfg_streams)
     ms_step = elapsed / a.steps * 1e3
     extra = {}
@@ -704,7 +729,7 @@ def main():
 
     secondary = {}
     gemm_classes = None
-    if not a.no_secondary and a.workload == "wan2.2-5b-49f-704x1280" and not a.layers:
+    if a.full and not a.no_secondary and a.workload == "wan2.2-5b-49f-704x1280" and not a.layers:
         # (a) the same step replayed from a captured hipGraph (north_star: the sampler loop is graph-captured)
         if not a.graph:
             el_g, _ = timed_run(1, 5, use_graph=True)
@@ -737,7 +762,7 @@ def main():
 
     # ---- once-per-clip stages (outside the timed region): Wan VAE encode of the conditions + decode ----
     vae_times = None
-    if a.workload != "tiny" and not a.no_vae:
+    if a.full and a.workload != "tiny" and not a.no_vae:
         from frameino_amd.autoencoder_kl_wan import AutoencoderKLWan
         from frameino_amd.configs import WAN22_VAE_CFG
         vae = AutoencoderKLWan(**WAN22_VAE_CFG).random_init_(seed=2, device=dev)
@@ -803,7 +828,8 @@ def main():
         del vae
         torch.cuda.empty_cache()
 
-    if not a.no_secondary and a.workload == "wan2.2-5b-49f-704x1280" and not a.layers and not a.mxfp8 and not a.fp8_attention:
+    if (a.full and not a.no_secondary and a.workload == "wan2.2-5b-49f-704x1280" and not a.layers and not a.mxfp8
+            and not a.fp8_attention):
         # (c') the power-capped step's sensitivity to OPERAND BITS: the same step on all-zero weights (a floor: nothing
         # toggles) and on heavy-tailed weights, next to the N(0, 0.02^2) of the headline -- bounds how far the number can move
         # on a real checkpoint
@@ -841,7 +867,7 @@ def main():
                 extra[k] = secondary[src]["ms_per_step"]
 
     roofline = None
-    ks = timer.summary().get("attn_self") if not a.graph else None
+    ks = timer.summary().get("attn_self") if a.full and not a.graph else None
     if ks:
         traffic, traffic_src = profiled_traffic("attn_ppd_kernel<BF16, 128, 0>")
         # algorithmic FLOPs of the timed launches (4.Lq.Lk.H.Dh per batch element) / their summed duration
@@ -867,7 +893,7 @@ def main():
                                   "the branches) covers one: achieved = summed algorithmic FLOPs / summed durations"}
     if roofline is not None and gemm_classes:
         roofline["secondary"] = gemm_classes
-    cpu = None if a.no_cpu_baseline else cpu_baseline(cfg, L)
+    cpu = None if (a.no_cpu_baseline or not a.full) else cpu_baseline(cfg, L)
     if cpu is not None and a.workload != "tiny":
         try:
             cpu.update(cpu_config1())

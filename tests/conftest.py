@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -15,11 +16,35 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+def golden_arrays(name):
+    """the arrays of fixture `name` in their recorded order: tests/golden/<name>.npz, or a fixture too large for one committed
+    file spread over <name>.part<i>.npz, its largest arrays cut along axis 0 into `<key>#<j>` pieces
+    (tools/golden/make_golden.py::savez_parts)"""
+    path = os.path.join(GOLDEN, name + ".npz")
+    if os.path.exists(path):
+        with np.load(path) as z:
+            return {k: z[k] for k in z.files}
+    parts = sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz")),
+                   key=lambda p: int(p[:-len(".npz")].rsplit(".part", 1)[1]))
+    assert parts, f"no fixture {name} under {GOLDEN}"
+    out, pieces = {}, {}
+    for p in parts:
+        with np.load(p) as z:
+            for k in z.files:
+                base, cut, j = k.rpartition("#")
+                if cut:
+                    out.setdefault(base, None)
+                    pieces.setdefault(base, {})[int(j)] = z[k]
+                else:
+                    out[k] = z[k]
+    for k, d in pieces.items():
+        out[k] = np.concatenate([d[j] for j in range(len(d))])
+    return out
+
+
 def load_golden(name):
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
     cfg, sd, arr = {}, {}, {}
-    for k in z.files:
-        v = z[k]
+    for k, v in golden_arrays(name).items():
         if k.startswith("cfg/"):
             v = v.tolist()
             cfg[k[4:]] = tuple(v) if isinstance(v, list) and k.endswith("patch_size") and len(v) == 3 else v

@@ -53,8 +53,8 @@ def test_bare_command_eight_gloo_ranks_on_one_gpu():
     rehearsal of the launch, the groups and the probe protocol -- not of the links."""
     import time
     t0 = time.time()
-    p, lines = run_bench(["--gpus", "8", "--workload", "tiny", "--steps", "2", "--warmup", "1"], {"FINO_DIST_BACKEND": "gloo"},
-                         timeout=600)
+    p, lines = run_bench(["--gpus", "8", "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full"],
+                         {"FINO_DIST_BACKEND": "gloo"}, timeout=600)
     took = time.time() - t0
     assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stderr[-3000:])
     out = json.loads(lines[0])
@@ -74,9 +74,35 @@ def test_bare_command_eight_gloo_ranks_on_one_gpu():
 @pytest.mark.parametrize("plan,exchange", [("split", "kv"), ("interleave", "kv"), ("interleave", "heads"), ("split", "heads")])
 def test_forced_shard_path_through_rccl_of_one_rank(plan, exchange):
     p, lines = run_bench(["--gpus", "1", "--force-shard", "--plan", plan, "--exchange", exchange, "--workload", "tiny",
-                          "--steps", "2", "--warmup", "1"])
+                          "--steps", "2", "--warmup", "1", "--full"])
     assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stderr[-3000:])
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["config"]["ranks_seen"] == 1 and out["config"]["backend"] == "nccl"
     assert out["config"]["parallelism"] != "single"
     assert out["config"]["sec_per_clip_measured"] > 0 and "finite=True" in out["config"]["sec_per_clip_measured_what"]
+
+
+def test_steps_below_one_is_refused():
+    p, lines = run_bench(["--gpus", "1", "--workload", "tiny", "--steps", "0"])
+    assert p.returncode == 2 and not lines and "--steps" in p.stderr, (p.returncode, p.stderr[-2000:])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_ones_latents(tmp_path):
+    """a plain run: the line carries the headline keys and nothing that --full measures; --dump-outputs writes the latents
+    of the last timed step, and the same arguments give the same inputs (the two dumps agree)"""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        p, lines = run_bench(["--gpus", "1", "--workload", "tiny", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stderr[-3000:])
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] - 1e3) < 1e-3
+        assert out["unit"] == "denoise-steps/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+        assert "roofline" not in out and "cpu_baseline" not in out and "secondary" not in out["config"]
+        assert sorted(os.listdir(d)) == ["latents.npy"]
+        lat = np.load(d / "latents.npy")
+        assert lat.dtype == np.float32 and lat.shape == (4, 3, 8, 12) and np.isfinite(lat).all()
+        dumps.append(lat)
+    np.testing.assert_allclose(dumps[0], dumps[1], rtol=1e-2, atol=1e-2)

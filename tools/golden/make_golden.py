@@ -45,9 +45,49 @@ def save(name, cfg=None, sd=None, **arrays):
             d["sd/" + k] = to_np(v)
     for k, v in arrays.items():
         d[k] = to_np(v)
-    path = os.path.join(OUT, name + ".npz")
-    np.savez_compressed(path, **d)
-    print(f"wrote {path}  ({os.path.getsize(path) / 1024:.0f} KiB)")
+    for path in savez_parts(os.path.join(OUT, name), d):
+        print(f"wrote {path}  ({os.path.getsize(path) / 1024:.0f} KiB)")
+
+
+PART_BYTES = 900 * 1024          # a committed file stays under 1 MiB
+
+
+def _npz_bytes(d):
+    import io
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **d)
+    return buf.tell()
+
+
+def savez_parts(base, d):
+    """<base>.npz, or -- when that would exceed PART_BYTES -- the arrays in order over <base>.part<i>.npz, each at most PART_BYTES;
+    an array too large for one part is cut along axis 0 into `<key>#<j>` pieces.  tests/conftest.py::golden_arrays reads both
+    layouts back.  Returns the paths written."""
+    import glob
+    for old in glob.glob(base + ".npz") + glob.glob(base + ".part*.npz"):
+        os.remove(old)
+    if _npz_bytes(d) <= PART_BYTES:
+        np.savez_compressed(base + ".npz", **d)
+        return [base + ".npz"]
+    entries = []
+    for k, v in d.items():
+        n = -(-_npz_bytes({k: v}) // (PART_BYTES // 2))
+        if n > 1:
+            entries += [(f"{k}#{j}", piece) for j, piece in enumerate(np.array_split(v, n))]
+        else:
+            entries.append((k, v))
+    parts, cur = [], {}
+    for k, v in entries:
+        if cur and _npz_bytes(dict(cur, **{k: v})) > PART_BYTES:
+            parts.append(cur)
+            cur = {}
+        cur[k] = v
+    parts.append(cur)
+    paths = []
+    for i, part in enumerate(parts):
+        paths.append(f"{base}.part{i}.npz")
+        np.savez_compressed(paths[-1], **part)
+    return paths
 
 
 def randomize_(module, seed, std=0.2):
@@ -616,8 +656,67 @@ def gen_blend():
     save("vae_blend", **arrays)
 
 
+def gen_plugin():
+    """tests/test_reference_plugin_cpu.py: the reference's own `Attention` (architecture/attention_processor.py) with its own
+    WanAttnProcessor2_0 / CogVideoXAttnProcessor2_0 -- parameters (reference names), inputs, rotary tables, outputs -- and what
+    the reference's AutoencoderKLWan does with tiling switched on (architecture/autoencoder_kl_wan.py:1270-1397)."""
+    from architecture import attention_processor as A
+    from architecture import embeddings as emb
+    from architecture import transformer_wan as tw
+    from architecture.autoencoder_kl_wan import AutoencoderKLWan
+    arrays = {}
+    torch.manual_seed(0)
+    heads, dh = 2, 24
+    d = heads * dh
+    for cross in (False, True):
+        attn = A.Attention(query_dim=d, heads=heads, kv_heads=heads, dim_head=dh, qk_norm="rms_norm_across_heads", eps=1e-6,
+                           bias=True, cross_attention_dim=None, out_bias=True, processor=tw.WanAttnProcessor2_0()).eval()
+        for p in attn.parameters():
+            p.copy_(torch.randn_like(p) * (0.2 if p.ndim > 1 else 0.1))
+        x = torch.randn(2, 3 * 2 * 4, d)
+        ctx = torch.randn(2, 7, d) if cross else None
+        rot = None if cross else tw.WanRotaryPosEmbed(dh, (1, 2, 2), 64)(torch.zeros(1, 1, 3, 4, 8))
+        pre = f"wan{int(cross)}/"
+        arrays.update({pre + "sd/" + k: v for k, v in attn.state_dict().items()})
+        arrays[pre + "x"], arrays[pre + "out"] = x, attn(x, encoder_hidden_states=ctx, rotary_emb=rot)
+        if cross:
+            arrays[pre + "ctx"] = ctx
+        else:
+            arrays[pre + "rot_cos"], arrays[pre + "rot_sin"] = rot
+    torch.manual_seed(1)
+    heads, dh = 2, 16
+    d = heads * dh
+    attn = A.Attention(query_dim=d, dim_head=dh, heads=heads, qk_norm="layer_norm", eps=1e-6, bias=True, out_bias=True,
+                       processor=A.CogVideoXAttnProcessor2_0()).eval()
+    for p in attn.parameters():
+        p.copy_(torch.randn_like(p) * 0.2 + (1.0 if p.ndim == 1 and p.numel() == dh else 0.0))
+    txt, vid = torch.randn(2, 5, d), torch.randn(2, 3 * 4 * 4, d)
+    cos, sin = emb.get_3d_rotary_pos_embed(dh, ((0, 0), (4, 4)), (4, 4), 3)
+    rh, re = attn(vid, encoder_hidden_states=txt, image_rotary_emb=(cos, sin))
+    arrays.update({"cog/sd/" + k: v for k, v in attn.state_dict().items()})
+    arrays.update({"cog/txt": txt, "cog/vid": vid, "cog/cos": cos, "cog/sin": sin, "cog/out_hidden": rh, "cog/out_encoder": re})
+    # the tiled paths on the Wan2.2 VAE (patch_size=2, is_residual=True): the errors they raise, and the un-tiled decode
+    cfg = dict(base_dim=8, decoder_base_dim=16, z_dim=4, dim_mult=[1, 2, 4, 4], num_res_blocks=1, attn_scales=[],
+               temperal_downsample=[False, True, True], dropout=0.0, latents_mean=[0.0] * 4, latents_std=[1.0] * 4,
+               is_residual=True, in_channels=12, out_channels=12, patch_size=2, scale_factor_temporal=4, scale_factor_spatial=16)
+    torch.manual_seed(0)
+    vae = AutoencoderKLWan(**cfg).eval()
+    vae.enable_tiling(tile_sample_min_height=32, tile_sample_min_width=32, tile_sample_stride_height=24,
+                      tile_sample_stride_width=24)
+    for key, call in (("tiled_encode_error", lambda: vae.encode(torch.rand(1, 3, 5, 64, 96))),
+                      ("tiled_decode_error", lambda: vae.decode(torch.randn(1, 4, 2, 8, 12)))):
+        try:
+            call()
+            arrays[key] = np.array("")
+        except RuntimeError as ex:
+            arrays[key] = np.array(f"RuntimeError: {ex}")
+    vae.disable_tiling()
+    arrays["untiled_decode_shape"] = np.array(vae.decode(torch.randn(1, 4, 2, 4, 6), return_dict=False)[0].shape)
+    save("reference_plugin", **arrays)
+
+
 GENS = {"blend": gen_blend, "wan_dit": gen_wan_dit, "wan_pipe": gen_wan_pipe, "wan_vae": gen_wan_vae, "cog_dit": gen_cog_dit,
-        "cog_dit_s1": gen_cog_dit_s1, "cog_pipe": gen_cog_pipe, "traj_kernel": gen_traj_kernel}
+        "cog_dit_s1": gen_cog_dit_s1, "cog_pipe": gen_cog_pipe, "traj_kernel": gen_traj_kernel, "plugin": gen_plugin}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()

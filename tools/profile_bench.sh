@@ -2,7 +2,7 @@
 # GPU box: rocprofv3 kernel-trace stats + HBM traffic counters (separate passes) of the bench command -> gpurun_out/<tag>_*
 tag=${1:-r01}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-CMD="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-secondary"
+CMD="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-secondary"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_trace -- python3 $CMD > gpurun_out/${tag}_trace.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/${tag}_fetch -- python3 $CMD > gpurun_out/${tag}_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/${tag}_write -- python3 $CMD > gpurun_out/${tag}_write.log 2>&1
