@@ -66,6 +66,9 @@ def main():
                                                               "script switches it on)")
     ap.add_argument("--repeat", type=int, default=1, help="generate the clip this many times (the first call is cold)")
     ap.add_argument("--out", default=None, help="write the cropped uint8 frames [F, h, w, 3] as .npy")
+    ap.add_argument("--lora", default=None, metavar="PATH",
+                    help="a LoRA adapter (local folder or .safetensors file), merged into the transformer's weights")
+    ap.add_argument("--lora-scale", type=float, default=1.0, help="the adapter's scale (attention_kwargs['scale'])")
     a = ap.parse_args()
 
     from frameino_amd import _lib
@@ -111,6 +114,8 @@ def main():
             vae.enable_tiling()
         text_dim = cfg["text_embed_dim"]
         pipe = CogVideoXImageToVideoPipeline(vae=vae, transformer=transformer, scheduler=sched)
+    if a.lora:                                     # merged before the first step: the denoise step itself is unchanged
+        pipe.load_lora_weights(a.lora, adapter_name="lora")
     if a.mxfp8:
         transformer.enable_mxfp8_linears()
     if a.fp8_attention:
@@ -124,6 +129,8 @@ def main():
                   negative_prompt_embeds=torch.zeros(1, 226, text_dim, device=dev))
     else:
         kw = dict(prompt=a.prompt)
+    if a.lora:
+        kw["attention_kwargs"] = {"scale": a.lora_scale}
     torch.cuda.synchronize()
     tc = time.perf_counter()
     for rep in range(a.repeat):

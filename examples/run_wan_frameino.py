@@ -53,6 +53,9 @@ def main():
     ap.add_argument("--smoke", action="store_true", help="tiny random model + tiny VAE, 64x96, 5 frames")
     ap.add_argument("--repeat", type=int, default=1, help="generate the clip this many times (the first call is cold)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lora", default=None, metavar="PATH",
+                    help="a LoRA adapter (local folder or .safetensors file), merged into the transformer's weights")
+    ap.add_argument("--lora-scale", type=float, default=1.0, help="the adapter's scale (attention_kwargs['scale'])")
     ap.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16",
                     help="the DiT's dtype.  Default fp16 = what the reference app loads it in (app.py:156: "
                          "`WanTransformer3DModel.from_pretrained(..., torch_dtype=torch.float16)`, fp32 islands kept); bf16 is what "
@@ -118,6 +121,8 @@ def main():
         vae.set_compute_dtype(torch.float32, planes=a.vae_fp32)
     pipe = WanImageToVideoPipeline(tokenizer=tokenizer, text_encoder=text_encoder, vae=vae, scheduler=sched,
                                    transformer=transformer, expand_timesteps=True)
+    if a.lora:                                     # merged before the first step: the denoise step itself is unchanged
+        pipe.load_lora_weights(a.lora, adapter_name="lora")
     t0 = time.perf_counter()
     canvas, tracks, id_tensor, pads = synthetic_conditions(a.frames, a.height, a.width, dev)
     traj = prepare_traj_tensor(tracks, a.height, a.width, 6, a.width, a.height, device=dev)        # [F, 3, H, W]
@@ -129,6 +134,8 @@ def main():
         kw = dict(prompt_embeds=pe.to(dev), negative_prompt_embeds=torch.zeros(1, 512, text_dim, device=dev))
     else:
         kw = dict(prompt=a.prompt, negative_prompt="")
+    if a.lora:
+        kw["attention_kwargs"] = {"scale": a.lora_scale}
     torch.cuda.synchronize()
     tc = time.perf_counter()
     for rep in range(a.repeat):

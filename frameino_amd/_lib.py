@@ -100,6 +100,9 @@ SIGNATURES = {
     "fino_avg_down3d_add": [c_void_p] * 3 + [c_int] * 10 + [c_void_p],
     "fino_vae_unpatchify_clamp": [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p],
     "fino_vae_patchify": [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p],
+    "fino_lora_merge": [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_void_p),
+                        ctypes.POINTER(c_i64), ctypes.POINTER(c_void_p), ctypes.POINTER(c_i64), ctypes.POINTER(c_int),
+                        ctypes.POINTER(c_float), c_int, c_void_p],
 }
 _RESTYPES = {"fino_last_error": ctypes.c_char_p, "fino_attn_workspace_bytes": c_i64, "fino_mxfp8_scale_bytes": c_i64,
              "fino_groupnorm_workspace_bytes": c_i64,

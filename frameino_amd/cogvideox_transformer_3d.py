@@ -22,6 +22,7 @@ from torch import nn
 from . import ops
 from .attention_processor import Attention, MI355CogVideoXAttnProcessor, MI355FusedCogVideoXAttnProcessor
 from .loading import FromPretrainedMixin
+from .lora import LoraModelMixin
 from .transformer_wan import FeedForward, _Config, _MLP2
 
 
@@ -78,7 +79,7 @@ def cog_sincos_pos_embed(embed_dim, pw, ph, frames, spatial_scale, temporal_scal
     return torch.cat([temporal, spatial], dim=-1).flatten(0, 1)
 
 
-class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin):
+class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
     _loader_name = "load_cogvideox_transformer"
 
     def __init__(self, num_attention_heads=30, attention_head_dim=64, in_channels=16, out_channels=16,
@@ -315,7 +316,8 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin):
             raise NotImplementedError("timestep_cond is never passed on the FrameINO path")
         if attention_kwargs is not None:
             attention_kwargs = dict(attention_kwargs)
-            attention_kwargs.pop("scale", None)
+        # LoRA scale (:460-465): adapters are merged into the weights, a changed scale re-merges them here (frameino_amd/lora.py)
+        self._lora_apply(attention_kwargs.pop("scale", None) if attention_kwargs is not None else None)
         if self._fp8_pending:
             self.enable_mxfp8_linears()
         pk = self._packed or self._pack()

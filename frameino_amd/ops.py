@@ -913,3 +913,40 @@ def avg_pool_time2(x):
     out = torch.empty(((t & 1) + (t - (t & 1)) // 2, h, w, cp), dtype=x.dtype, device=x.device)
     _lib.check(_lib.lib().fino_avg_pool_time2(_p(x), _p(out), t, h, w, cp, _dt(x), _stream()), "fino_avg_pool_time2")
     return out
+
+
+LORA_MAX_ADAPTERS = 8                      # FINO_LORA_MAX_ADAPTERS
+
+
+def lora_merge_(w_base, adapters, out=None):
+    """LoRA merge on the GPU (fino_lora_merge): out = T( float(w_base) + sum_a s_a * B_a.float() @ A_a.float() ), the rank
+    products accumulated in fp32 and ONE rounding at the end.  `adapters`: (A [r, K], B [N, r], s) triples, A / B in the
+    weight's dtype (bf16 / fp16 / fp32), row-strided with a contiguous last dimension.  out=None merges in place; otherwise
+    `out` is a [N, K] row-strided buffer of the same dtype that does not overlap w_base.  Returns the written tensor."""
+    out = w_base if out is None else out
+    if not (w_base.is_cuda and out.is_cuda):
+        raise RuntimeError("frameino_amd ops need CUDA(HIP) tensors; there is no CPU path")
+    if w_base.dim() != 2 or out.shape != w_base.shape or out.dtype != w_base.dtype:
+        raise ValueError(f"lora_merge_: weight {tuple(w_base.shape)} {w_base.dtype} / out {tuple(out.shape)} {out.dtype}")
+    if w_base.stride(1) != 1 or out.stride(1) != 1:
+        raise ValueError("lora_merge_: the weight's last dimension must be contiguous")
+    if len(adapters) > LORA_MAX_ADAPTERS:
+        raise ValueError(f"lora_merge_: {len(adapters)} adapters in one call (at most {LORA_MAX_ADAPTERS})")
+    n, k = w_base.shape
+    na = len(adapters)
+    ptr_a, ptr_b = (_lib.c_void_p * max(na, 1))(), (_lib.c_void_p * max(na, 1))()
+    lda, ldb = (_lib.c_i64 * max(na, 1))(), (_lib.c_i64 * max(na, 1))()
+    rank, scale = (_lib.c_int * max(na, 1))(), (_lib.c_float * max(na, 1))()
+    for i, (a, b, s) in enumerate(adapters):
+        r = a.shape[0]
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != k or b.shape != (n, r):
+            raise ValueError(f"lora_merge_: adapter {i}: A {tuple(a.shape)} / B {tuple(b.shape)} for a weight {tuple(w_base.shape)}")
+        if a.dtype != w_base.dtype or b.dtype != w_base.dtype or not (a.is_cuda and b.is_cuda):
+            raise ValueError(f"lora_merge_: adapter {i}: factors must be {w_base.dtype} device tensors")
+        if a.stride(1) != 1 or b.stride(1) != 1:
+            raise ValueError(f"lora_merge_: adapter {i}: factors need a contiguous last dimension")
+        ptr_a[i], ptr_b[i] = a.data_ptr(), b.data_ptr()
+        lda[i], ldb[i], rank[i], scale[i] = a.stride(0), b.stride(0), r, float(s)
+    _lib.check(_lib.lib().fino_lora_merge(_p(w_base), w_base.stride(0), _p(out), out.stride(0), n, k, na, ptr_a, lda, ptr_b,
+                                          ldb, rank, scale, _dt3(w_base), _stream()), "fino_lora_merge")
+    return out

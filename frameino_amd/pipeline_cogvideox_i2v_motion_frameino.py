@@ -18,6 +18,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
+from .lora import LoraPipelineMixin, lora_denoise_loop
 from .schedulers import CogVideoXDDIMScheduler  # noqa: F401  (re-export)
 
 
@@ -81,7 +82,7 @@ def _one_generator(generator, batch_size=1):
     return generator
 
 
-class CogVideoXImageToVideoPipeline:
+class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
     extend_rope_by_first_frame = True             # :834-839 (the ID frame reuses the first frame's RoPE rows)
 
@@ -227,6 +228,7 @@ class CogVideoXImageToVideoPipeline:
         return cos.to(device), sin.to(device)
 
     @torch.no_grad()
+    @lora_denoise_loop
     def denoise(self, latents, image_latents, traj_latents, id_latent, prompt_embeds, negative_prompt_embeds,
                 guidance_scale=6.0, num_inference_steps=50, use_dynamic_cfg=False, image_rotary_emb=None,
                 attention_kwargs=None, callback_on_step_end=None, generator=None):

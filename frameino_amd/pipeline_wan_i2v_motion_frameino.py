@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .lora import LoraPipelineMixin, lora_denoise_loop
 
 
 def _basic_clean(text):
@@ -85,7 +86,7 @@ def tr_default_procs(transformer):
     return bool(f()) if callable(f) else True
 
 
-class WanImageToVideoPipeline:
+class WanImageToVideoPipeline(LoraPipelineMixin):
     model_cpu_offload_seq = "text_encoder->image_encoder->transformer->transformer_2->vae"
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
 
@@ -435,6 +436,7 @@ class WanImageToVideoPipeline:
         st.attention_kwargs = attention_kwargs
         return st
 
+    @lora_denoise_loop
     def denoise(self, latents, condition, traj_latents, id_latent, first_frame_mask, prompt_embeds,
                 negative_prompt_embeds, guidance_scale, num_inference_steps, attention_kwargs=None,
                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), timesteps_set=False):

@@ -25,6 +25,7 @@ from torch import nn
 from . import ops
 from .attention_processor import Attention, MI355WanAttnProcessor
 from .loading import FromPretrainedMixin
+from .lora import LoraModelMixin
 
 
 class _Config(dict):
@@ -110,9 +111,10 @@ class WanTransformerBlock(nn.Module):
         self.scale_shift_table = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
 
 
-class WanTransformer3DModel(nn.Module, FromPretrainedMixin):
+class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
     _loader_name = "load_wan_transformer"
     _keep_in_fp32_modules = ["time_embedder", "scale_shift_table", "norm1", "norm2", "norm3"]   # reference :393
+    _lora_wan_layout = True   # LoRA files in the original Wan-repo / kohya key layout map onto these names (frameino_amd/lora.py)
 
     def __init__(self, patch_size=(1, 2, 2), num_attention_heads=40, attention_head_dim=128, in_channels=16,
                  out_channels=16, text_dim=4096, freq_dim=256, ffn_dim=13824, num_layers=40, cross_attn_norm=True,
@@ -486,7 +488,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin):
             raise NotImplementedError("encoder_hidden_states_image: Wan2.1 branch, outside the TI2V-5B path")
         if attention_kwargs is not None:
             attention_kwargs = dict(attention_kwargs)
-            attention_kwargs.pop("scale", None)                                    # LoRA scale (:463-476): no PEFT here
+        # LoRA scale (:463-476): adapters are merged into the weights, a changed scale re-merges them here (frameino_amd/lora.py)
+        self._lora_apply(attention_kwargs.pop("scale", None) if attention_kwargs is not None else None)
         b = hidden_states.shape[0]
         if self._fp8_pending:
             self.enable_mxfp8_linears()

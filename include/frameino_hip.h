@@ -477,6 +477,24 @@ int fino_resize_area_pad_u8(const void* src, void* dst, int src_h, int src_w, in
                             int out_w, int off_y, int off_x, int fill, void* stream);
 int fino_u8_hwc_to_chw_unit(const void* src, float* dst, int height, int width, void* stream);
 
+/* ---- LoRA merge (HBM-bound: W read and written once) ------------------------------------------------------------------
+ * The reference's transformers inherit diffusers' PeftAdapterMixin and scale LoRA layers by attention_kwargs["scale"]
+ * (architecture/transformer_wan.py:23-24, :463-476, :545-547; architecture/cogvideox_transformer_3d.py:460-465); its pipelines
+ * load adapters through WanLoraLoaderMixin / CogVideoXLoraLoaderMixin (pipelines/pipeline_wan_i2v_motion_FrameINO.py:26, :134;
+ * pipelines/pipeline_cogvideox_i2v_motion_FrameINO.py:26, :166).  Here adapters are merged into the weights instead:
+ *   w_out[n, k] = T( float(w_base[n, k]) + sum_a scale[a] * sum_j b_a[n, j] * a_a[j, k] )
+ * for one weight [n, k] (row strides ldw_base / ldw_out >= k; w_out == w_base (same stride) merges in place, otherwise the two
+ * must not overlap).  Adapter a: a_a [rank[a], k] (row stride lda[a]), b_a [n, rank[a]] (row stride ldb[a]), both in the weight
+ * dtype; scale[a] fp32 (call scale x adapter weight x alpha / r).  The pointer / stride / rank / scale arrays are HOST arrays
+ * of n_adapters (0 .. FINO_LORA_MAX_ADAPTERS) entries, read during the call.  The rank product accumulates in fp32 (bf16 / fp16:
+ * v_mfma_f32_32x32x16, ranks in chunks of 16), scale[a] multiplies adapter a's fp32 partial product, and the one rounding is
+ * the final store (RNE; fp16 overflows to inf).  dtype FINO_BF16 | FINO_F16 | FINO_F32 (fp32: the fp32-island targets,
+ * plain FMA).  bf16 / fp16: the ranks of one call, each padded to 16, sum to at most FINO_LORA_MAX_TOTAL_RANK. */
+enum { FINO_LORA_MAX_ADAPTERS = 8, FINO_LORA_MAX_TOTAL_RANK = 1024 };
+int fino_lora_merge(const void* w_base, int64_t ldw_base, void* w_out, int64_t ldw_out, int64_t n, int64_t k,
+                    int n_adapters, const void* const* a, const int64_t* lda, const void* const* b, const int64_t* ldb,
+                    const int* rank, const float* scale, int dtype, void* stream);
+
 /* ---- diagnostics (tools/ only) --------------------------------------------------------------------------------
  * Dense MFMA rate with nothing else running: `iters` x 16 independent 32x32x16 (kind 0) / 32 independent 16x16x32
  * (kind 1) bf16 MFMAs per wave from registers -- or (kind 2) 16 block-scaled fp8 MFMAs 32x32x64 on e4m3 operands with unit scales,
