@@ -43,8 +43,13 @@ struct F16 {
     static constexpr int kId = FINO_F16;
     static __device__ __forceinline__ float to_f32(uint16_t u) { return (float)__builtin_bit_cast(_Float16, u); }
     static __device__ __forceinline__ uint16_t from_f32(float f) {
-        _Float16 h = (_Float16)f;
-        return __builtin_bit_cast(uint16_t, h);
+        // One rounding of the fp32 value to nearest even, as torch's .half() does.  Spelled as the instruction: the compiler's
+        // lowering of (_Float16)f differs on gfx950 -- pairs of conversions become v_cvt_pk_f16_f32, which rounds ties away
+        // from even; a conversion of a product or sum is fused into v_fma_mix*_f16 (one rounding of the exact result instead
+        // of the fp32 one); and a round trip (float)(_Float16)x is dropped, losing the reference's rounding point.
+        uint32_t r;
+        asm("v_cvt_f16_f32 %0, %1" : "=v"(r) : "v"(f));
+        return (uint16_t)r;
     }
     static __device__ __forceinline__ f32x16_t mfma32(vec8 a, vec8 b, f32x16_t c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);

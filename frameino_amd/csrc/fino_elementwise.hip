@@ -511,6 +511,20 @@ __global__ __launch_bounds__(256) void cfg_dpm_step_kernel(const uint16_t* __res
 //   x_c = use_corr ? Cx*last + C0*m0 + C1*m1 + Ct*m_t : x                    (multistep_uni_c_bh_update)
 //   x'  = Px*x_c + P0*m_t + P1*m0                                            (multistep_uni_p_bh_update)
 //   last <- x_c;  m1 <- m0;  m0 <- m_t;  x <- x'
+// `sigma_t * model_output` as torch evaluates it on this device: the exact product rounded ONCE to T.  For fp16 torch's
+// compiled elementwise product is one v_fma_mixlo_f16 (no fp32 rounding in between; tests/test_kernels_gpu.py::test_cfg_unipc_step),
+// for bf16 the fp32 product rounded to bf16.
+template <typename T>
+__device__ __forceinline__ float round_product(float a, float b) {
+    if constexpr (std::is_same<T, F16>::value) {
+        uint32_t r = 0;
+        asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "+v"(r) : "v"(a), "v"(b));
+        return F16::to_f32((uint16_t)r);
+    } else {
+        return round_to<T>(a * b);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void cfg_unipc_kernel(const uint16_t* __restrict__ pc, const uint16_t* __restrict__ pu,
                                                         float* __restrict__ x, float* __restrict__ last,
@@ -531,7 +545,7 @@ __global__ __launch_bounds__(256) void cfg_unipc_kernel(const uint16_t* __restri
             v = round_to<T>(u + round_to<T>(g * round_to<T>(v - u)));
         }
         const float xv = x[i], a0 = m0[i];
-        const float mt = xv - round_to<T>(sigma * v);
+        const float mt = xv - round_product<T>(sigma, v);
         const float xc = use_corr != 0.f ? Cx * last[i] + C0 * a0 + C1 * m1[i] + Ct * mt : xv;
         x[i] = Px * xc + P0 * mt + P1 * a0;
         last[i] = xc;

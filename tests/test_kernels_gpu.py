@@ -6,6 +6,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.kernel_check import check_close, check_exact
+from tests.test_elementwise_edges_gpu import headnorm_ref, ln_ref, rms_restate
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -44,13 +47,10 @@ def test_adaln_modulate(ops, dtype, rows, dim):
     sel = (torch.arange(rows) % 3 == 0).to(torch.int32).to(DEV)
     shift, scale = table[:, 0], table[:, 1]
     y = ops.adaln_modulate(x, shift, scale, sel, eps=1e-6)
-    n = F.layer_norm(x.float(), (dim,), None, None, 1e-6)
-    ref = (n * (1 + scale[sel.long()]) + shift[sel.long()]).to(dtype)
-    ulp_close(y, ref, dtype)
+    check_close(y, *ln_ref(0, x, None, None, shift[sel.long()], scale[sel.long()], 1e-6, dtype))
     # no selector -> row 0
     y0 = ops.adaln_modulate(x, shift[0], scale[0], None, eps=1e-6)
-    ref0 = (n * (1 + scale[0]) + shift[0]).to(dtype)
-    ulp_close(y0, ref0, dtype)
+    check_close(y0, *ln_ref(0, x, None, None, shift[0], scale[0], 1e-6, dtype))
 
 
 @pytest.mark.parametrize("affine", [True, False])
@@ -59,8 +59,7 @@ def test_layernorm(ops, affine):
     w = rnd(3072, dtype=torch.float32, seed=4) if affine else None
     b = rnd(3072, dtype=torch.float32, seed=5) if affine else None
     y = ops.layernorm(x, w, b, eps=1e-6)
-    ref = F.layer_norm(x.float(), (3072,), w, b, 1e-6).to(x.dtype)
-    ulp_close(y, ref, x.dtype)
+    check_close(y, *ln_ref(1, x, w, b, None, None, 1e-6, x.dtype))
 
 
 @pytest.mark.parametrize("gated", [True, False])
@@ -86,19 +85,10 @@ def test_rmsnorm_rope_inplace_on_fused_qkv(ops, dim, head_dim, rope):
     sin = torch.rand(rows, head_dim // 2).to(DEV) if rope else None
     ref_in = qkv[:, dim:2 * dim].clone()
     before = qkv.clone()
+    rrms = ops.row_rrms(ref_in, 1e-6)              # the kernel's own statistic (tests/test_elementwise_edges_gpu.py holds it to fp64)
     ops.rmsnorm_rope_(qkv[:, dim:2 * dim], w, 1e-6, cos, sin, head_dim)
-    # reference: diffusers RMSNorm semantics + transformer_wan.py:75-87
-    var = ref_in.float().pow(2).mean(-1, keepdim=True)
-    y = (ref_in * torch.rsqrt(var + 1e-6)).to(torch.bfloat16) * w
-    if rope:
-        yh = y.view(rows, dim // head_dim, head_dim // 2, 2)
-        x1, x2 = yh[..., 0], yh[..., 1]
-        c, s = cos[:, None, :], sin[:, None, :]
-        out = torch.empty_like(yh)
-        out[..., 0] = x1 * c - x2 * s
-        out[..., 1] = x1 * s + x2 * c
-        y = out.view(rows, dim)
-    ulp_close(qkv[:, dim:2 * dim], y, torch.bfloat16)
+    # reference: diffusers RMSNorm semantics + transformer_wan.py:75-87, at the kernel's rounding points
+    check_exact(qkv[:, dim:2 * dim], rms_restate(ref_in, rrms, w, cos, sin, head_dim, 1.0, torch.bfloat16))
     assert torch.equal(qkv[:, :dim], before[:, :dim]) and torch.equal(qkv[:, 2 * dim:], before[:, 2 * dim:])
 
 
@@ -108,14 +98,9 @@ def test_headnorm_rope_cog(ops):
     w = (1 + 0.1 * torch.randn(hd)).to(torch.bfloat16).to(DEV)
     bb = (0.1 * torch.randn(hd)).to(torch.bfloat16).to(DEV)
     cos, sin = torch.rand(lv, hd).to(DEV), torch.rand(lv, hd).to(DEV)
-    ref = x.view(b, lt + lv, heads, hd).transpose(1, 2)
-    ref = F.layer_norm(ref, (hd,), w, bb, 1e-6)
-    xr, xi = ref[:, :, lt:].reshape(b, heads, lv, hd // 2, 2).unbind(-1)
-    rot = torch.stack([-xi, xr], dim=-1).flatten(3)
-    ref[:, :, lt:] = (ref[:, :, lt:].float() * cos + rot.float() * sin).to(x.dtype)
-    ref = ref.transpose(1, 2).reshape(b, lt + lv, heads * hd)
+    ref, bound = headnorm_ref(x.view(b, lt + lv, heads, hd).clone(), w, bb, 1e-6, cos, sin, lt, 1.0, x.dtype)
     ops.headnorm_rope_(x, heads, hd, w, bb, 1e-6, cos, sin, rope_row0=lt)
-    ulp_close(x, ref, torch.bfloat16)
+    check_close(x.view(b, lt + lv, heads, hd), ref, bound)
 
 
 def sdpa_ref(q, k, v, heads):
@@ -339,15 +324,8 @@ def test_layernorm_zero_staged_rounding(ops):
     tab = rnd(2 * b, 3, d, seed=63, scale=0.3).float()            # bf16-representable values
     sel = (torch.arange(b * L, device=DEV) % 4).to(torch.int32)
     y = ops.layernorm_zero(x, w, bb, tab[:, 0], tab[:, 1], sel, 1e-5)
-    n = F.layer_norm(x, (d,), w.bfloat16(), bb.bfloat16(), 1e-5)
-    sc, sh = (1 + tab[:, 1].bfloat16())[sel.long()], tab[:, 0].bfloat16()[sel.long()]
-    ref = n * sc + sh
-    # a 1-ulp flip of the normalised value (reduction order) propagates through the product; with cancellation in
-    # "+ shift" the bound is 2 ulp of the LARGER intermediate, not of the result
-    mag = (n.float() * sc.float()).abs() + sh.float().abs()
-    bad = (y.float() - ref.float()).abs() > 2 * 2.0 ** -8 * mag + 1e-6
-    assert bad.float().mean().item() < 0.01
-    assert rel_rms(y, ref) < 2.0 ** -7
+    # a 1-ulp flip of the normalised value (reduction order) propagates through the product and "+ shift": ln_ref's bound
+    check_close(y, *ln_ref(2, x, w, bb, tab[:, 0][sel.long()], tab[:, 1][sel.long()], 1e-5, torch.bfloat16))
 
 
 def test_gated_residual_staged_and_gemm_epilogue(ops):
@@ -514,14 +492,9 @@ def test_rmsnorm_rope_out_scale_is_one_rounding():
     c = dh ** -0.5 * ops.LOG2E
     plain = ops.rmsnorm_rope_(x.clone(), w, 1e-6, cos, sin, dh)
     scaled = ops.rmsnorm_rope_(x.clone(), w, 1e-6, cos, sin, dh, out_scale=c)
-    # fp32 restatement of the kernel's arithmetic (same rounding points up to the RoPE, then x c, one rounding)
-    xf = x.float()
-    y = (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + 1e-6)).bfloat16().float() * w.float()
-    y = y.bfloat16().float().view(rows, heads, dh // 2, 2)
-    o = torch.stack((y[..., 0] * cos[:, None] - y[..., 1] * sin[:, None], y[..., 0] * sin[:, None] + y[..., 1] * cos[:, None]), -1)
-    want = (o.reshape(rows, d) * c).bfloat16()
-    assert (scaled.float() - want.float()).abs().max() <= 2.0 ** -8 * want.float().abs().max()
-    assert (scaled != want).float().mean() < 0.02                     # a few 1-ulp flips from rsqrt / fma contraction
+    # fp32 restatement of the kernel's arithmetic on its own statistic (same rounding points up to the RoPE, then x c, one
+    # rounding): bit-identical
+    check_exact(scaled, rms_restate(x, ops.row_rrms(x, 1e-6), w, cos, sin, dh, c, torch.bfloat16))
     assert rel_rms(scaled.float() / c, plain.float()) < 2.0 ** -8     # and it is the plain result, scaled
 
 

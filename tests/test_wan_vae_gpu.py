@@ -66,7 +66,7 @@ def test_conv3d_geometries_vs_torch(name, ci, co, k, stride, pad, up, thw):
     assert rel_rms(y2, (y.float() + r.float())) < 4e-3
 
 
-def _vae(golden, name, prefix=""):
+def _vae(golden, name, prefix="", dtype=torch.bfloat16):
     from frameino_amd.autoencoder_kl_wan import AutoencoderKLWan
     cfg, sd, a = golden(name)
     if prefix:
@@ -78,7 +78,7 @@ def _vae(golden, name, prefix=""):
     kw = {k: (list(cfg[k]) if isinstance(cfg[k], (list, tuple)) else cfg[k]) for k in keys}
     kw["is_residual"] = bool(kw["is_residual"])
     vae = AutoencoderKLWan(**kw).to(DEV)
-    vae.load_reference_state_dict(sd, dtype=torch.bfloat16)
+    vae.load_reference_state_dict(sd, dtype=dtype)
     return vae, a
 
 
@@ -144,6 +144,45 @@ def test_full_width_vae_vs_oracle_small_video():
     p = psnr(out, ref_v)
     print(f"full-width VAE: encode rel-RMS {r_enc:.4f}, decode PSNR {p:.1f} dB")
     assert r_enc < 3e-2 and p > 35.0
+
+
+def test_fp16_storage_and_compute_at_least_as_close_as_bf16(golden):
+    """fp16 storage and fp16 compute (the F16 instantiations of every VAE kernel): the tiny golden's decodes and encodes and the
+    full-width 9-frame 64x96 case, each held to what the bf16 mode measures on the same inputs and weights in this test (fp16
+    has 3 more mantissa bits), and never worse than the bf16 bar of the tests above"""
+    from frameino_amd.autoencoder_kl_wan import AutoencoderKLWan
+    from frameino_amd.configs import WAN22_VAE_CFG
+    from oracle import wan_vae as V
+    res = {}
+    for dt in (torch.bfloat16, torch.float16):
+        vae, a = _vae(golden, "wan_vae_tiny", dtype=dt)
+        vae.set_compute_dtype(dt)
+        assert vae.dtype == dt and vae.compute_dtype == dt
+        dec = [psnr(vae.decode(a[f"dec_in_{nl}"].to(DEV), return_dict=False)[0], a[f"dec_out_{nl}"]) for nl in (1, 2, 3)]
+        enc = [rel_rms(vae.encode(a[f"enc_in_{nf}"].to(DEV)).latent_dist.parameters, a[f"enc_out_{nf}"]) for nf in (1, 5, 9)]
+        res[dt] = (dec, enc)
+    full = {}
+    g = torch.Generator().manual_seed(6)
+    vid = torch.rand(1, 3, 9, 64, 96, generator=g) * 2 - 1
+    z = torch.randn(1, 48, 3, 4, 6, generator=g)
+    ref_z = ref_v = None
+    for dt in (torch.bfloat16, torch.float16):
+        vae = AutoencoderKLWan(**WAN22_VAE_CFG).random_init_(seed=5, device=DEV, dtype=dt)     # the same fp32 master weights
+        vae.set_compute_dtype(dt)
+        if ref_z is None:
+            sd = {k: v.float().cpu() for k, v in vae._sd.items()}
+            ref_z, ref_v = V.wan_vae_encode(sd, dict(WAN22_VAE_CFG), vid), V.wan_vae_decode(sd, dict(WAN22_VAE_CFG), z)
+        post = vae.encode(vid.to(DEV)).latent_dist.parameters
+        out = vae.decode(z.to(DEV), return_dict=False)[0]
+        assert torch.isfinite(post).all() and torch.isfinite(out).all(), dt
+        full[dt] = (psnr(out, ref_v), rel_rms(post, ref_z))
+    print("bf16 / fp16 tiny decode PSNR", res[torch.bfloat16][0], res[torch.float16][0], "encode rel-RMS", res[torch.bfloat16][1],
+          res[torch.float16][1], "full width (PSNR, rel-RMS)", full[torch.bfloat16], full[torch.float16])
+    for i in range(3):
+        assert res[torch.float16][0][i] >= max(res[torch.bfloat16][0][i], 35.0), (i, res)
+        assert res[torch.float16][1][i] <= min(res[torch.bfloat16][1][i], 3e-2), (i, res)
+    assert full[torch.float16][0] >= max(full[torch.bfloat16][0], 35.0), full
+    assert full[torch.float16][1] <= min(full[torch.bfloat16][1], 3e-2), full
 
 
 @pytest.mark.parametrize("chunk", [1, 2, 3, 5])
