@@ -56,6 +56,9 @@ def main():
     ap.add_argument("--lora", default=None, metavar="PATH",
                     help="a LoRA adapter (local folder or .safetensors file), merged into the transformer's weights")
     ap.add_argument("--lora-scale", type=float, default=1.0, help="the adapter's scale (attention_kwargs['scale'])")
+    ap.add_argument("--first-block-cache", type=float, default=None, metavar="THRESHOLD",
+                    help="diffusers' first-block caching (approximate; eager loop): skip blocks 1..N-1 of a step whose first-block "
+                         "residual changed by at most THRESHOLD (relative L1), e.g. 0.1")
     ap.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16",
                     help="the DiT's dtype.  Default fp16 = what the reference app loads it in (app.py:156: "
                          "`WanTransformer3DModel.from_pretrained(..., torch_dtype=torch.float16)`, fp32 islands kept); bf16 is what "
@@ -123,6 +126,9 @@ def main():
                                    transformer=transformer, expand_timesteps=True)
     if a.lora:                                     # merged before the first step: the denoise step itself is unchanged
         pipe.load_lora_weights(a.lora, adapter_name="lora")
+    if a.first_block_cache is not None:
+        from frameino_amd.step_cache import FirstBlockCacheConfig
+        transformer.enable_cache(FirstBlockCacheConfig(threshold=a.first_block_cache))
     t0 = time.perf_counter()
     canvas, tracks, id_tensor, pads = synthetic_conditions(a.frames, a.height, a.width, dev)
     traj = prepare_traj_tensor(tracks, a.height, a.width, 6, a.width, a.height, device=dev)        # [F, 3, H, W]

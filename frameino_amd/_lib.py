@@ -103,7 +103,15 @@ SIGNATURES = {
     "fino_lora_merge": [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_void_p),
                         ctypes.POINTER(c_i64), ctypes.POINTER(c_void_p), ctypes.POINTER(c_i64), ctypes.POINTER(c_int),
                         ctypes.POINTER(c_float), c_int, c_void_p],
+    "fino_step_cache_probe": [c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_void_p],
+    "fino_step_cache_residual": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_void_p],
 }
+
+
+class StepCacheSegment(ctypes.Structure):
+    """FinoStepCacheSegment (include/frameino_hip.h)"""
+    _fields_ = [("h0", c_void_p), ("h1", c_void_p), ("p", c_void_p), ("r", c_void_p), ("h1_copy", c_void_p),
+                ("rows", c_i64), ("ld_h0", c_i64), ("ld_h1", c_i64), ("ld_p", c_i64), ("ld_r", c_i64), ("ld_h1_copy", c_i64)]
 _RESTYPES = {"fino_last_error": ctypes.c_char_p, "fino_attn_workspace_bytes": c_i64, "fino_mxfp8_scale_bytes": c_i64,
              "fino_groupnorm_workspace_bytes": c_i64,
              "fino_attn_partial_bytes": c_i64, "fino_attn_fp8_kv_bytes": c_i64}

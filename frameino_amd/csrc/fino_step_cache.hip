@@ -1,0 +1,232 @@
+// First-block caching of the Wan DiT (diffusers' FirstBlockCache; frameino_amd/step_cache.py): the per-step probe of the
+// first block's residual and the two residual-stream updates around the skipped blocks.
+//
+// fino_step_cache_probe, per segment s (one CFG branch, or one joint batch):
+//   r = T(h1 - h0)                                           written to r (and h1 copied to h1_copy when given)
+//   sums[2 s]     = sum |T(r - p)|      sums[2 s + 1] = sum |p|        (fp32; p == NULL counts as zeros)
+// The host divides and compares (step_cache.decide).  Deterministic: every segment is cut into FINO_STEP_CACHE_BLOCKS row
+// ranges by its row count alone, each workgroup sums its range in a fixed order (per-thread sequential, xor-butterfly across
+// the wave, waves in index order) and stores one partial; a second launch adds the partials in index order.  No atomics: the
+// same inputs give the same bits on every run, whatever order the workgroups run in.
+//
+// fino_step_cache_residual: out = T(a - b) or T(a + b) -- bit-exact to torch's `a - b` / `a + b` in T (one fp32 operation,
+// one rounding).
+//
+// HBM-bound: 16-byte loads and stores, fp32 arithmetic, no contraction (the file is built with -ffp-contract=off).
+#include "fino_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kUnroll = 2;
+
+// 16-byte vectors of the storage type as fp32 lanes
+template <typename T>
+struct Io {
+    static constexpr int kElems = 8;
+    static constexpr int kBytes = 2;
+    static __device__ __forceinline__ void unpack(const uint4& v, float (&f)[8]) { unpack8<T>(v, f); }
+    static __device__ __forceinline__ uint4 pack(const float (&f)[8]) { return pack8<T>(f); }
+    static __device__ __forceinline__ float rnd(float x) { return round_to<T>(x); }
+};
+struct F32 {};
+template <>
+struct Io<F32> {
+    static constexpr int kElems = 4;
+    static constexpr int kBytes = 4;
+    static __device__ __forceinline__ void unpack(const uint4& v, float (&f)[4]) {
+        f[0] = __uint_as_float(v.x);
+        f[1] = __uint_as_float(v.y);
+        f[2] = __uint_as_float(v.z);
+        f[3] = __uint_as_float(v.w);
+    }
+    static __device__ __forceinline__ uint4 pack(const float (&f)[4]) {
+        return make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
+    }
+    static __device__ __forceinline__ float rnd(float x) { return x; }
+};
+
+struct ProbeArgs {
+    FinoStepCacheSegment seg[FINO_STEP_CACHE_MAX_SEGMENTS];
+    uint32_t vpr;                       // 16-byte vectors per row
+};
+
+__device__ __forceinline__ const uint4* at(const void* base, int64_t row, int64_t ld, uint32_t col, int esize) {
+    return (const uint4*)((const char*)base + (row * ld + col) * esize);
+}
+
+// (a, q) of the workgroup: thread 0 gets the sums, in a fixed order
+__device__ __forceinline__ void block_sum2(float& a, float& q) {
+    __shared__ float red[2][kThreads / 64];
+    a = wave_sum(a);
+    q = wave_sum(q);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[0][wave] = a;
+        red[1][wave] = q;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = red[0][0];
+        q = red[1][0];
+#pragma unroll
+        for (int w = 1; w < kThreads / 64; ++w) {
+            a += red[0][w];
+            q += red[1][w];
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void probe_kernel(ProbeArgs args, float* partial) {
+    using IO = Io<T>;
+    constexpr int E = IO::kElems;
+    const FinoStepCacheSegment& g = args.seg[blockIdx.y];
+    const int64_t r0 = g.rows * blockIdx.x / FINO_STEP_CACHE_BLOCKS, r1 = g.rows * (blockIdx.x + 1) / FINO_STEP_CACHE_BLOCKS;
+    const uint32_t vpr = args.vpr, nvec = (uint32_t)(r1 - r0) * vpr;
+    float sa = 0.f, sq = 0.f;
+    for (uint32_t i0 = threadIdx.x; i0 < nvec; i0 += kThreads * kUnroll) {
+        uint4 v0[kUnroll], v1[kUnroll], vp[kUnroll];
+        int64_t row[kUnroll];
+        uint32_t col[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const uint32_t i = i0 + u * kThreads;
+            if (i < nvec) {
+                row[u] = r0 + i / vpr;
+                col[u] = (i % vpr) * E;
+                v0[u] = *at(g.h0, row[u], g.ld_h0, col[u], IO::kBytes);
+                v1[u] = *at(g.h1, row[u], g.ld_h1, col[u], IO::kBytes);
+                vp[u] = g.p ? *at(g.p, row[u], g.ld_p, col[u], IO::kBytes) : make_uint4(0, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            if (i0 + u * kThreads >= nvec) break;
+            float f0[E], f1[E], fp[E], fr[E];
+            IO::unpack(v0[u], f0);
+            IO::unpack(v1[u], f1);
+            IO::unpack(vp[u], fp);
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                fr[e] = IO::rnd(f1[e] - f0[e]);
+                sa += fabsf(IO::rnd(fr[e] - fp[e]));
+                sq += fabsf(fp[e]);
+            }
+            *(uint4*)at(g.r, row[u], g.ld_r, col[u], IO::kBytes) = IO::pack(fr);
+            if (g.h1_copy) *(uint4*)at(g.h1_copy, row[u], g.ld_h1_copy, col[u], IO::kBytes) = v1[u];
+        }
+    }
+    block_sum2(sa, sq);
+    if (threadIdx.x == 0) {
+        float* dst = partial + 2 * ((int64_t)blockIdx.y * FINO_STEP_CACHE_BLOCKS + blockIdx.x);
+        dst[0] = sa;
+        dst[1] = sq;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void probe_finish_kernel(const float* partial, float* sums) {
+    const float* src = partial + 2 * (int64_t)blockIdx.x * FINO_STEP_CACHE_BLOCKS;
+    float sa = 0.f, sq = 0.f;
+    for (int j = threadIdx.x; j < FINO_STEP_CACHE_BLOCKS; j += kThreads) {
+        sa += src[2 * j];
+        sq += src[2 * j + 1];
+    }
+    block_sum2(sa, sq);
+    if (threadIdx.x == 0) {
+        sums[2 * blockIdx.x] = sa;
+        sums[2 * blockIdx.x + 1] = sq;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void residual_kernel(const void* a, int64_t lda, const void* b, int64_t ldb, void* out,
+                                                            int64_t ldo, uint32_t vpr, uint32_t nvec, int subtract) {
+    using IO = Io<T>;
+    constexpr int E = IO::kElems;
+    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < nvec; i += gridDim.x * kThreads) {
+        const int64_t row = i / vpr;
+        const uint32_t col = (i % vpr) * E;
+        float fa[E], fb[E], fo[E];
+        IO::unpack(*at(a, row, lda, col, IO::kBytes), fa);
+        IO::unpack(*at(b, row, ldb, col, IO::kBytes), fb);
+#pragma unroll
+        for (int e = 0; e < E; ++e) fo[e] = subtract ? fa[e] - fb[e] : fa[e] + fb[e];
+        *(uint4*)at(out, row, ldo, col, IO::kBytes) = IO::pack(fo);
+    }
+}
+
+int esize_of(int dtype) { return dtype == FINO_F32 ? 4 : 2; }
+
+bool rows_ok(const void* p, int64_t ld, int dtype) {
+    const int per16 = 16 / esize_of(dtype);
+    return fino_aligned16(p) && ld % per16 == 0;
+}
+
+}  // namespace
+
+extern "C" int fino_step_cache_probe(const FinoStepCacheSegment* segs, int nseg, int64_t dim, float* sums, float* workspace,
+                                     int dtype, void* stream) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16 || dtype == FINO_F32, FINO_ERR_ARG, "fino_step_cache_probe: dtype %d",
+               dtype);
+    FINO_CHECK(segs && nseg >= 1 && nseg <= FINO_STEP_CACHE_MAX_SEGMENTS, FINO_ERR_ARG,
+               "fino_step_cache_probe: %d segments (1 .. %d)", nseg, FINO_STEP_CACHE_MAX_SEGMENTS);
+    FINO_CHECK(sums && workspace && fino_aligned16(sums) && fino_aligned16(workspace), FINO_ERR_ARG,
+               "fino_step_cache_probe: sums / workspace missing or not 16-byte aligned");
+    const int per16 = 16 / esize_of(dtype);
+    FINO_CHECK(dim > 0 && dim % per16 == 0, FINO_ERR_ARG, "fino_step_cache_probe: dim=%lld must be a multiple of %d",
+               (long long)dim, per16);
+    ProbeArgs args = {};
+    args.vpr = (uint32_t)(dim / per16);
+    for (int s = 0; s < nseg; ++s) {
+        const FinoStepCacheSegment& g = segs[s];
+        FINO_CHECK(g.h0 && g.h1 && g.r, FINO_ERR_ARG, "fino_step_cache_probe: segment %d: null h0 / h1 / r", s);
+        FINO_CHECK(g.rows >= 0 && (g.rows + FINO_STEP_CACHE_BLOCKS - 1) / FINO_STEP_CACHE_BLOCKS * (dim / per16) < (1LL << 31),
+                   FINO_ERR_ARG, "fino_step_cache_probe: segment %d: rows=%lld out of range", s, (long long)g.rows);
+        FINO_CHECK(g.ld_h0 >= dim && g.ld_h1 >= dim && g.ld_r >= dim && (!g.p || g.ld_p >= dim) &&
+                       (!g.h1_copy || g.ld_h1_copy >= dim),
+                   FINO_ERR_ARG, "fino_step_cache_probe: segment %d: a row stride is below dim", s);
+        FINO_CHECK(rows_ok(g.h0, g.ld_h0, dtype) && rows_ok(g.h1, g.ld_h1, dtype) && rows_ok(g.r, g.ld_r, dtype) &&
+                       (!g.p || rows_ok(g.p, g.ld_p, dtype)) && (!g.h1_copy || rows_ok(g.h1_copy, g.ld_h1_copy, dtype)),
+                   FINO_ERR_ARG, "fino_step_cache_probe: segment %d: 16-byte alignment required", s);
+        args.seg[s] = g;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(FINO_STEP_CACHE_BLOCKS, nseg);
+    if (dtype == FINO_BF16)
+        probe_kernel<BF16><<<grid, kThreads, 0, st>>>(args, workspace);
+    else if (dtype == FINO_F16)
+        probe_kernel<F16><<<grid, kThreads, 0, st>>>(args, workspace);
+    else
+        probe_kernel<F32><<<grid, kThreads, 0, st>>>(args, workspace);
+    FINO_LAUNCH_CHECK();
+    probe_finish_kernel<<<nseg, kThreads, 0, st>>>(workspace, sums);
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
+}
+
+extern "C" int fino_step_cache_residual(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo,
+                                        int64_t rows, int64_t dim, int subtract, int dtype, void* stream) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16 || dtype == FINO_F32, FINO_ERR_ARG,
+               "fino_step_cache_residual: dtype %d", dtype);
+    const int per16 = 16 / esize_of(dtype);
+    FINO_CHECK(rows >= 0 && dim > 0 && dim % per16 == 0 && rows * (dim / per16) < (1LL << 31), FINO_ERR_ARG,
+               "fino_step_cache_residual: rows=%lld dim=%lld", (long long)rows, (long long)dim);
+    FINO_CHECK(a && b && out, FINO_ERR_ARG, "fino_step_cache_residual: null pointer");
+    FINO_CHECK(lda >= dim && ldb >= dim && ldo >= dim, FINO_ERR_ARG, "fino_step_cache_residual: a row stride is below dim");
+    FINO_CHECK(rows_ok(a, lda, dtype) && rows_ok(b, ldb, dtype) && rows_ok(out, ldo, dtype), FINO_ERR_ARG,
+               "fino_step_cache_residual: 16-byte alignment required");
+    if (rows == 0) return FINO_OK;
+    const uint32_t vpr = (uint32_t)(dim / per16), nvec = (uint32_t)(rows * vpr);
+    int64_t grid = (nvec + kThreads - 1) / kThreads;
+    if (grid > 256 * 8) grid = 256 * 8;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == FINO_BF16)
+        residual_kernel<BF16><<<(int)grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
+    else if (dtype == FINO_F16)
+        residual_kernel<F16><<<(int)grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
+    else
+        residual_kernel<F32><<<(int)grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
+}

@@ -950,3 +950,61 @@ def lora_merge_(w_base, adapters, out=None):
     _lib.check(_lib.lib().fino_lora_merge(_p(w_base), w_base.stride(0), _p(out), out.stride(0), n, k, na, ptr_a, lda, ptr_b,
                                           ldb, rank, scale, _dt3(w_base), _stream()), "fino_lora_merge")
     return out
+
+
+STEP_CACHE_MAX_SEGMENTS = 4                # FINO_STEP_CACHE_MAX_SEGMENTS
+_STEP_CACHE_WS = {}                        # (device, stream) -> (sums [MAX, 2], partial workspace) fp32
+
+
+def _rows_of(t, dtype, what):
+    if not t.is_cuda:
+        raise RuntimeError("frameino_amd ops need CUDA(HIP) tensors; there is no CPU path")
+    if t.dim() != 2 or t.stride(1) != 1 or t.dtype != dtype:
+        raise ValueError(f"{what}: need a row-strided [rows, D] {dtype} tensor, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+    return t
+
+
+def step_cache_probe(h0, h1, p, r, h1_copy=None):
+    """First-block-cache probe (fino_step_cache_probe) over S segments: r = T(h1 - h0) (and h1_copy = h1), and the fp32 sums
+    (sum |T(r - p)|, sum |p|) of every segment -- a device [S, 2] tensor (valid until the next probe on this device and stream: the host
+    reads it right away).  Every argument is a list of S row-strided [rows_s, D] tensors (or one tensor for S = 1); p[s] may be None
+    (read as zeros), h1_copy None or a list with None entries (no copy).  The sums are deterministic bit for bit."""
+    one = not isinstance(h0, (list, tuple))
+    h0, h1, p, r = ([t] for t in (h0, h1, p, r)) if one else (h0, h1, p, r)
+    n = len(h0)
+    h1_copy = ([h1_copy] if one else h1_copy) if h1_copy is not None else [None] * n
+    if not (1 <= n <= STEP_CACHE_MAX_SEGMENTS) or not (len(h1) == len(p) == len(r) == len(h1_copy) == n):
+        raise ValueError(f"step_cache_probe: {n} segments (1 .. {STEP_CACHE_MAX_SEGMENTS}), one entry per operand each")
+    dt, d, dev = h0[0].dtype, h0[0].shape[-1], h0[0].device
+    segs = (_lib.StepCacheSegment * n)()
+    for s in range(n):
+        rows = h0[s].shape[0]
+        for t, what in ((h0[s], "h0"), (h1[s], "h1"), (p[s], "p"), (r[s], "r"), (h1_copy[s], "h1_copy")):
+            if t is not None and (_rows_of(t, dt, f"step_cache_probe {what}").shape != (rows, d) or t.device != dev):
+                raise ValueError(f"step_cache_probe: segment {s}: {what} is {tuple(t.shape)} on {t.device}, want {(rows, d)} on {dev}")
+        g = segs[s]
+        g.h0, g.h1, g.p, g.r, g.h1_copy = _p(h0[s]), _p(h1[s]), _p(p[s]), _p(r[s]), _p(h1_copy[s])
+        g.rows, g.ld_h0, g.ld_h1, g.ld_r = rows, h0[s].stride(0), h1[s].stride(0), r[s].stride(0)
+        g.ld_p = p[s].stride(0) if p[s] is not None else 0
+        g.ld_h1_copy = h1_copy[s].stride(0) if h1_copy[s] is not None else 0
+    key = (str(dev), _stream())             # two CFG branches on two streams never share the sums
+    if key not in _STEP_CACHE_WS:
+        _STEP_CACHE_WS[key] = (torch.zeros((STEP_CACHE_MAX_SEGMENTS, 2), dtype=torch.float32, device=dev),
+                               torch.empty(2 * STEP_CACHE_MAX_SEGMENTS * 1024, dtype=torch.float32, device=dev))
+    sums, ws = _STEP_CACHE_WS[key]
+    _lib.check(_lib.lib().fino_step_cache_probe(segs, n, d, _p(sums), _p(ws), _dt3(h0[0]), _stream()), "fino_step_cache_probe")
+    return sums[:n]
+
+
+def step_cache_residual(a, b, out=None, subtract=True):
+    """out = T(a - b) (subtract) or T(a + b): torch's `a - b` / `a + b` in the storage dtype, bit for bit
+    (fino_step_cache_residual; bf16 / fp16 / fp32, row-strided [rows, D]; out may alias a or b)."""
+    _rows_of(a, a.dtype, "step_cache_residual a")
+    _rows_of(b, a.dtype, "step_cache_residual b")
+    out = torch.empty_like(a) if out is None else _rows_of(out, a.dtype, "step_cache_residual out")
+    if a.shape != b.shape or out.shape != a.shape:
+        raise ValueError(f"step_cache_residual: shapes {tuple(a.shape)} / {tuple(b.shape)} / {tuple(out.shape)}")
+    rows, d = a.shape
+    _lib.check(_lib.lib().fino_step_cache_residual(_p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), rows, d,
+                                                   int(bool(subtract)), _dt3(a), _stream()), "fino_step_cache_residual")
+    return out

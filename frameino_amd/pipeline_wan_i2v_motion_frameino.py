@@ -16,6 +16,12 @@ replays; timestep and dt live in device buffers that a device-to-device copy ref
 inside the loop) whenever the call has no per-step callback: on one GPU always, on token shards for the call patterns this
 image's runtime captures (graph_step.py lists them).  `use_hip_graph = False` keeps the eager loop, `True` makes a loop
 that cannot be captured an error.
+
+With first-block caching enabled on the transformer (`pipe.transformer.enable_cache(FirstBlockCacheConfig(threshold))`,
+frameino_amd/step_cache.py) the loop runs eagerly: every step decides on the host, between block 0 and block 1, whether the
+other blocks run.  The cache state starts fresh in every `denoise` and is dropped by `maybe_free_model_hooks()` at the end of
+`__call__`; `transformer.cache_log` keeps the call's decisions.  One sample, one GPU (a batch or a parallel plan with the cache
+raises NotImplementedError).
 """
 import html
 import re
@@ -145,7 +151,26 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
                    expand_timesteps=bool(index.get("expand_timesteps", True)))
 
     def maybe_free_model_hooks(self):
-        pass
+        # diffusers resets every component's stateful cache here, at the end of each call
+        reset = getattr(self.transformer, "_reset_stateful_cache", None)
+        if callable(reset):
+            reset()
+
+    def _step_cache_check(self, batch):
+        """the first-block cache's limits, checked before any work (and before any collective: a parallel plan and the cache
+        are configured by the same script on every rank, so every rank raises)"""
+        if not getattr(self.transformer, "is_cache_enabled", False):
+            return False
+        if getattr(self, "parallel", None) is not None:
+            raise NotImplementedError("first-block caching runs on one GPU; this pipeline has a parallel plan")
+        if batch > 1:
+            raise NotImplementedError("first-block caching with a batch (a list of prompts, num_videos_per_prompt > 1): diffusers "
+                                      "decides jointly over the batch, this pipeline runs the samples one at a time")
+        if self.use_hip_graph is True:
+            raise RuntimeError("use_hip_graph=True with first-block caching: every step decides on the host between block 0 and "
+                               "block 1 whether the other blocks run, which one captured step cannot contain (the loop runs "
+                               "eagerly; use_hip_graph=None or False)")
+        return True
 
     def to(self, device):
         for m in (self.transformer, self.vae, self.text_encoder):
@@ -313,6 +338,8 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
 
         live = {"live_rows": st.live_rows} if getattr(st, "live_rows", None) is not None else {}
 
+        cached = bool(getattr(tr, "is_cache_enabled", False))
+
         def fwd(name, emb):
             with tr.cache_context(name):
                 return tr(hidden_states=x, timestep=None, encoder_hidden_states=emb, return_dict=False,
@@ -380,10 +407,12 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
             main.wait_stream(s2)
         elif st.cfg and self.batch_cfg and st.pe_ne is not None and getattr(tr, "parallel", None) is None:
             # both CFG branches as ONE batch-2 forward (rows of the same GEMMs: identical per-row arithmetic, twice
-            # the tiles per launch, weights streamed once).  The reference makes two calls (:862-882).
+            # the tiles per launch, weights streamed once).  The reference makes two calls (:862-882); with the first-block
+            # cache each row block keeps the context of the call it stands for, and is decided as that call would be.
+            ctxs = {"_cache_contexts": ("cond", "uncond")} if cached else {}
             with tr.cache_context("cfg"):
                 both = tr(hidden_states=x.expand(2, -1, -1, -1, -1), timestep=None, encoder_hidden_states=st.pe_ne,
-                          return_dict=False, attention_kwargs=st.attention_kwargs, timestep_rows=rows, **live)[0]
+                          return_dict=False, attention_kwargs=st.attention_kwargs, timestep_rows=rows, **live, **ctxs)[0]
             pc, pu = both[0], both[1]
         else:
             pc = fwd("cond", st.pe)
@@ -442,7 +471,11 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
                 callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), timesteps_set=False):
         """reference :809-913.  Returns the final latents [B, C, F, h, w] fp32.  The loop state is one sample's (the app
         and the evaluation scripts run batch 1); a batch -- a list of prompts, num_videos_per_prompt > 1 -- runs sample by sample:
-        the samples of the reference's batched loop never meet, every one sees the noise row `prepare_latents` drew for it."""
+        the samples of the reference's batched loop never meet, every one sees the noise row `prepare_latents` drew for it.
+        With first-block caching every call starts from fresh cache state."""
+        cached = self._step_cache_check(latents.shape[0])
+        if cached:
+            self.transformer._reset_stateful_cache()
         if latents.shape[0] > 1:
             def row(t, i):
                 return t if t is None or t.shape[0] == 1 else t[i:i + 1]
@@ -472,7 +505,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
 
         from .graph_step import StepGraph, capture_error_mode, groups_capturable
         stepper = StepGraph(lambda: self._step(st), self.use_hip_graph,
-                            callback_on_step_end is None and st.lat.is_cuda
+                            callback_on_step_end is None and st.lat.is_cuda and not cached
                             and (self.use_hip_graph is True or tr_default_procs(self.transformer))
                             and groups_capturable(getattr(self, "parallel", None), self.use_hip_graph is True),
                             len(timesteps), capture_error_mode(getattr(self, "parallel", None)))
@@ -523,6 +556,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
             batch_size = len(prompt)
         else:
             batch_size = prompt_embeds.shape[0]
+        self._step_cache_check(batch_size * num_videos_per_prompt)
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(
             prompt, negative_prompt, self.do_classifier_free_guidance, num_videos_per_prompt, prompt_embeds,
             negative_prompt_embeds, max_sequence_length, device)

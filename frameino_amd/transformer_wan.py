@@ -13,6 +13,8 @@ What is different by design (results identical):
   * text K/V of the cross-attention (step-invariant) are cached per `cache_context` name;
   * Q/K/V are one fused GEMM; norm+RoPE run in place on the fused buffer; attention reads it in place;
     bias / GELU / gated-residual are GEMM epilogues.
+`enable_cache(FirstBlockCacheConfig(...))` (diffusers' CacheMixin, reference :28, :353) skips blocks 1 .. N-1 of a step whose
+first-block residual barely changed (frameino_amd/step_cache.py); off by default.
 """
 import contextlib
 import math
@@ -26,6 +28,7 @@ from . import ops
 from .attention_processor import Attention, MI355WanAttnProcessor
 from .loading import FromPretrainedMixin
 from .lora import LoraModelMixin
+from .step_cache import FirstBlockCacheMixin
 
 
 class _Config(dict):
@@ -111,7 +114,7 @@ class WanTransformerBlock(nn.Module):
         self.scale_shift_table = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
 
 
-class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
+class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, FirstBlockCacheMixin):
     _loader_name = "load_wan_transformer"
     _keep_in_fp32_modules = ["time_embedder", "scale_shift_table", "norm1", "norm2", "norm3"]   # reference :393
     _lora_wan_layout = True   # LoRA files in the original Wan-repo / kohya key layout map onto these names (frameino_amd/lora.py)
@@ -207,8 +210,9 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
     # ------------------------------------------------------------------ derived state
     def reset_caches(self):
         """Drop everything derived from the parameters or the prompt: packed/fused weight copies, MXFP8 weights, text
-        K/V, RoPE tables, workspaces.  Called whenever the parameters may have changed or moved."""
+        K/V, RoPE tables, workspaces, first-block-cache residuals.  Called whenever the parameters may have changed or moved."""
         had_fp8 = bool(self._fp8) or self._fp8_pending
+        self._reset_stateful_cache()
         self._packed = None
         self._fp8 = {}
         # the MXFP8 weights are re-quantised lazily, by the next forward, from wherever the parameters are then: a
@@ -460,7 +464,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None,
-                return_dict=True, attention_kwargs=None, timestep_rows=None, live_rows=None):
+                return_dict=True, attention_kwargs=None, timestep_rows=None, live_rows=None, _cache_contexts=None):
         """`timestep_rows=(values [R], selector int32 [L])` is the de-duplicated form of a per-token timestep; when a
         2-D `timestep` is given instead it is de-duplicated here (torch.unique: host sync, eager only).
         `live_rows=(lo, hi)` (round 6): the caller will only read the output of token rows [lo, hi) -- the FrameINO loop drops the
@@ -468,9 +472,13 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
         condition before every forward and at the end (:829, :913).  In the LAST block the other rows then only feed the
         self-attention as keys and values: their q projection's use, attention queries, out-projection, text branch, FFN and
         output head are skipped, and their part of the returned tensor is ZERO.  Every kept row is computed exactly as without it.
-        A bare `transformer(...)` call (None) keeps the full output."""
+        A bare `transformer(...)` call (None) keeps the full output.
+        `_cache_contexts` (private; first-block cache enabled): one cache-context name per batch element, each element then
+        decided on its own as if called alone under that context -- the pipeline's CFG-batched call passes ("cond", "uncond").
+        Without it a batch-B call under one `cache_context` makes one joint decision, as diffusers does."""
         gen = self.forward_steps(hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image,
-                                 return_dict, attention_kwargs, timestep_rows, live_rows=live_rows)
+                                 return_dict, attention_kwargs, timestep_rows, live_rows=live_rows,
+                                 _cache_contexts=_cache_contexts)
         while True:
             try:
                 next(gen)
@@ -478,7 +486,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
                 return done.value
 
     def forward_steps(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None,
-                      return_dict=True, attention_kwargs=None, timestep_rows=None, shard=None, live_rows=None):
+                      return_dict=True, attention_kwargs=None, timestep_rows=None, shard=None, live_rows=None,
+                      _cache_contexts=None):
         """The forward as a generator that yields after the embedding stage and after every block, so that a caller
         can interleave two independent forwards (the CFG branches) kernel-stream by kernel-stream
         (frameino_amd/parallel.py: one branch's K|V all-gather then flies under the other branch's compute).  Every
@@ -515,6 +524,9 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
             cos1, sin1 = cos1[lo:lo + n].contiguous(), sin1[lo:lo + n].contiguous()
         else:
             lo, n, lpad = 0, L, L
+        if self.is_cache_enabled and sh is not None:
+            raise NotImplementedError("first-block caching runs on one GPU: a token-sharded forward cannot take the cache")
+        fbc = self._step_cache_segments(b, n, _cache_contexts)     # None: no cache (nothing extra allocated or launched)
         # the shard's tile height for its GEMM calls (a per-call argument of the C ABI; {} = the library's planner)
         tk = {}
         if sh is not None and getattr(sh, "gemm_tile_m", 0):
@@ -577,6 +589,16 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
             a_rows = torch.cat([o.patchify(hidden_states[i], cfg.patch_size) for i in range(b)])
         x = ws.x[:nr]
         o.gemm(a_rows, pk.w_patch, self.patch_embedding.bias, out=x[:n] if shared else x, **tk)
+        if fbc is not None:
+            # first-block cache: keep h0 (block 0 updates x in place) and a buffer for the probe's copy of h1
+            if getattr(ws, "fbc_h0", None) is None:
+                ws.fbc_h0, ws.fbc_h1 = torch.empty_like(ws.x), torch.empty_like(ws.x)
+            h0, h1c = ws.fbc_h0[:nr], ws.fbc_h1[:nr]
+            if shared:                       # (the embedding of the shared latent sits in the first n rows only)
+                for bi in range(b):
+                    h0[bi * n:(bi + 1) * n].copy_(x[:n])
+            else:
+                h0.copy_(x)
         nrm, att, q2, ff = ws.n[:nr], ws.att[:nr], ws.q2[:nr], ws.ff[:nr]
         fold = self.fold_softmax_scale and hasattr(o, "SCALE_FOLDED")
         qfold = {"out_scale": dh ** -0.5 * o.LOG2E} if fold else {}
@@ -820,7 +842,19 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
                               out=ff[r0:r1], **tk)
                     self._lin(li, "ff2", ff[r0:r1], blk.ffn.net[2].weight, blk.ffn.net[2].bias, o.EPI_GATED_RESIDUAL,
                               residual=x[r0:r1], gate=m[:, 5], sel=None if sel is None else sel[r0:r1], out=x[r0:r1], **tk)
+            if fbc is not None and li == 0:
+                computes = self._step_cache_probe(fbc, h0, x, h1c)          # one host read: the rule's decision
             yield
+            if fbc is not None and not any(computes):
+                break                                                       # every segment skips blocks 1 .. N-1
+
+        if fbc is not None:
+            # tail residuals of the computed segments; T(tail + h1) for the skipped ones.  With `live_rows` the last block left
+            # the dead rows at block N-2's output, so a tail residual is meaningful on the live rows only -- the rows the caller
+            # reads; the head below runs on those rows alone whether or not the blocks ran.
+            self._step_cache_finish(fbc, computes, x, h1c)
+            if live is not None:
+                segs = [(bi * n + live[0], bi * n + live[1]) for bi in range(b)]
 
         # ---- output head (:519-543) ----
         for r0, r1 in segs:

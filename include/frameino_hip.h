@@ -495,6 +495,38 @@ int fino_lora_merge(const void* w_base, int64_t ldw_base, void* w_out, int64_t l
                     int n_adapters, const void* const* a, const int64_t* lda, const void* const* b, const int64_t* ldb,
                     const int* rank, const float* scale, int dtype, void* stream);
 
+/* ---- first-block caching (HBM-bound; frameino_amd/step_cache.py) ------------------------------------------------------
+ * The reference's WanTransformer3DModel inherits diffusers' CacheMixin (architecture/transformer_wan.py:28, :353) and its FrameINO
+ * loop runs the two CFG calls inside cache_context("cond") / ("uncond") (pipelines/pipeline_wan_i2v_motion_FrameINO.py:862,
+ * :873).  With diffusers' FirstBlockCache a step whose first-block residual barely changed skips blocks 1 .. N-1.
+ *
+ * fino_step_cache_probe, per segment s (one CFG branch or one jointly decided batch; h0 = input of block 0, h1 = its output,
+ * p = the head residual of the last computed step or NULL, read as zeros):
+ *   r = T(h1 - h0)                         written to r; h1 also copied to h1_copy unless that is NULL
+ *   sums[2 s] = sum |T(r - p)|,  sums[2 s + 1] = sum |p|      fp32 device floats
+ * Each segment: `rows` rows of `dim` elements, every operand row-strided (its own ld >= dim, 16-byte aligned rows; r and h1_copy
+ * must not overlap the inputs).  `segs` is a HOST array of nseg (1 .. FINO_STEP_CACHE_MAX_SEGMENTS) entries, read during the
+ * call.  `workspace`: FINO_STEP_CACHE_WORKSPACE_FLOATS device floats.  The sums are reproducible bit for bit: a fixed partition
+ * (FINO_STEP_CACHE_BLOCKS row ranges per segment) and fixed-order sums, no atomics.  inf / nan propagate as in torch.
+ * dtype FINO_BF16 | FINO_F16 | FINO_F32; dim a multiple of 8 (16-bit) or 4 (fp32).
+ *
+ * fino_step_cache_residual: out = T(a - b) (subtract != 0) or T(a + b), one fp32 operation and one rounding -- torch's
+ * `a - b` / `a + b` in T bit for bit.  The tail residual T(hN - h1) and the skipped step's T(tail + h1).  out may alias a or b. */
+typedef struct {
+    const void* h0;
+    const void* h1;
+    const void* p;
+    void* r;
+    void* h1_copy;
+    int64_t rows, ld_h0, ld_h1, ld_p, ld_r, ld_h1_copy;
+} FinoStepCacheSegment;
+enum { FINO_STEP_CACHE_MAX_SEGMENTS = 4, FINO_STEP_CACHE_BLOCKS = 1024,
+       FINO_STEP_CACHE_WORKSPACE_FLOATS = 2 * FINO_STEP_CACHE_MAX_SEGMENTS * FINO_STEP_CACHE_BLOCKS };
+int fino_step_cache_probe(const FinoStepCacheSegment* segs, int nseg, int64_t dim, float* sums, float* workspace, int dtype,
+                          void* stream);
+int fino_step_cache_residual(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int64_t rows,
+                             int64_t dim, int subtract, int dtype, void* stream);
+
 /* ---- diagnostics (tools/ only) --------------------------------------------------------------------------------
  * Dense MFMA rate with nothing else running: `iters` x 16 independent 32x32x16 (kind 0) / 32 independent 16x16x32
  * (kind 1) bf16 MFMAs per wave from registers -- or (kind 2) 16 block-scaled fp8 MFMAs 32x32x64 on e4m3 operands with unit scales,
