@@ -65,6 +65,10 @@ SIGNATURES = {
     "fino_quantize_mxfp8": [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p],
     "fino_gemm_mxfp8": [c_void_p] * 6 + [c_i64] * 4 + [c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p],
     "fino_gemm_mxfp8_q": [c_void_p] * 7 + [c_i64] * 3 + [c_int, c_int, c_void_p],
+    "fino_mxfp6_bytes": [c_i64, c_i64],
+    "fino_mxfp6_scale_bytes": [c_i64, c_i64],
+    "fino_quantize_mxfp6": [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p],
+    "fino_gemm_mxfp6": [c_void_p] * 6 + [c_i64] * 4 + [c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p],
     "fino_traj_paint": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "fino_traj_blur_quantize": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "fino_groupnorm_workspace_bytes": [c_int],
@@ -114,7 +118,8 @@ class StepCacheSegment(ctypes.Structure):
                 ("rows", c_i64), ("ld_h0", c_i64), ("ld_h1", c_i64), ("ld_p", c_i64), ("ld_r", c_i64), ("ld_h1_copy", c_i64)]
 _RESTYPES = {"fino_last_error": ctypes.c_char_p, "fino_attn_workspace_bytes": c_i64, "fino_mxfp8_scale_bytes": c_i64,
              "fino_groupnorm_workspace_bytes": c_i64,
-             "fino_attn_partial_bytes": c_i64, "fino_attn_fp8_kv_bytes": c_i64}
+             "fino_attn_partial_bytes": c_i64, "fino_attn_fp8_kv_bytes": c_i64, "fino_mxfp6_bytes": c_i64,
+             "fino_mxfp6_scale_bytes": c_i64}
 
 
 # the FINO_VERSION this table (argument lists, tune-knob meanings) was written for: a stale library found through

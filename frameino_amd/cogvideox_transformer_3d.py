@@ -128,6 +128,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         self._pos_cache = {}
         self._fp8 = {}
         self._fp8_pending = False
+        self._mx_fmt = 8          # element format of the `_fp8` entries: 8 = e4m3 (enable_mxfp8_linears), 6 = e2m3 (enable_mxfp6_linears)
         self.fp8_attention = False           # see enable_fp8_attention
         # q leaves its LayerNorm + RoPE kernel multiplied by head_dim**-0.5 * log2(e) and the attention kernels take q.k as
         # the exp2 argument (FINO_ATTN_SCALE_FOLDED): at head_dim 64 that selects the 4-wave kernel with the running maximum
@@ -212,15 +213,33 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         K-elements, fp32 accumulate; `fino_quantize_mxfp8` / `fino_gemm_mxfp8`); weights are quantised once here.
         Attention, norms, embeddings and the output head stay in the model dtype.  No reference counterpart (SURVEY
         F11): compared with this model's own bf16 forward."""
+        return self._enable_mx_linears(8, enabled)
+
+    def enable_mxfp6_linears(self, enabled=True):
+        """The same four linears on the MXFP6 path (OCP e2m3 + one e8m0 scale per 32 K-elements, fp32 accumulate, at the FP4
+        matrix rate; `fino_quantize_mxfp6` / `fino_gemm_mxfp6`).  Activations are quantised per call from the model dtype
+        (no fused producers).  One reduced precision at a time: raises ValueError while `enable_mxfp8_linears()` is on;
+        `enable_mxfp6_linears(False)` returns the model to its model-dtype output bit for bit."""
+        return self._enable_mx_linears(6, enabled)
+
+    def _enable_mx_linears(self, fmt, enabled):
+        on = bool(self._fp8) or self._fp8_pending
+        if on and self._mx_fmt != fmt:
+            if not enabled:
+                return self                                     # the other precision's switch: nothing of this one to drop
+            raise ValueError(f"enable_mxfp{fmt}_linears: enable_mxfp{self._mx_fmt}_linears() is on -- one reduced precision at a "
+                             f"time; call enable_mxfp{self._mx_fmt}_linears(False) first")
         self._fp8 = {}
         self._fp8_pending = False
         if not enabled:
             return self
+        self._mx_fmt = fmt
+        quantize = ops.quantize_mxfp6 if fmt == 6 else ops.quantize_mxfp8
         pk = self._packed or self._pack()
         for li, (blk, e) in enumerate(zip(self.transformer_blocks, pk.layers)):
             for key, w in (("qkv", e.wqkv), ("out", blk.attn1.to_out[0].weight), ("ff1", blk.ff.net[0].proj.weight),
                            ("ff2", blk.ff.net[2].weight)):
-                self._fp8[(li, key)] = ops.quantize_mxfp8(w.detach().contiguous())
+                self._fp8[(li, key)] = quantize(w.detach().contiguous())
         return self
 
     def enable_fp8_attention(self, enabled=True, p_mode=None):
@@ -239,6 +258,9 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         wq = self._fp8.get((li, key)) if self._fp8 else None
         if wq is None:
             return ops.gemm(x, w, b, epi, **kw)
+        if self._mx_fmt == 6:
+            xq, xs = ops.quantize_mxfp6(x)
+            return ops.gemm_mxfp6(xq, xs, wq[0], wq[1], b, epi, **kw)
         xq, xs = xq if xq is not None else ops.quantize_mxfp8(x)
         return ops.gemm_mxfp8(xq, xs, wq[0], wq[1], b, epi, **kw)
 
@@ -247,6 +269,8 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         (fino_ln_mxfp8 mode 2: one pass instead of norm -> bf16 -> quantise); None when the linear is not on the MXFP8 path"""
         if not self._fp8 or (li, key) not in self._fp8 or not hasattr(ops, "ln_mxfp8") or os.environ.get("FINO_NO_LN_MXFP8"):
             return None
+        if self._mx_fmt == 6:
+            return None                                         # MXFP6 takes the two-pass route: norm -> model dtype -> quantise
         return ops.ln_mxfp8(2, x2, weight=w, bias=b, shift=shift, scale=scale, sel=sel, eps=eps)
 
     def _default_processors(self):
@@ -319,7 +343,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         # LoRA scale (:460-465): adapters are merged into the weights, a changed scale re-merges them here (frameino_amd/lora.py)
         self._lora_apply(attention_kwargs.pop("scale", None) if attention_kwargs is not None else None)
         if self._fp8_pending:
-            self.enable_mxfp8_linears()
+            self._enable_mx_linears(self._mx_fmt, True)
         pk = self._packed or self._pack()
         default_procs = self._default_processors()
         c = self.config
@@ -421,7 +445,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
             xq2 = (self._lnz_q(li, "ff1", x2, e.n2w, e.n2b, t2[:, 0], t2[:, 1], sel, c.norm_eps)
                    if (w1q is not None and w2q is not None) else None)
             n = None if xq2 is not None else ops.layernorm_zero(x2, e.n2w, e.n2b, t2[:, 0], t2[:, 1], sel, c.norm_eps)
-            if w1q is not None and w2q is not None:
+            if w1q is not None and w2q is not None and self._mx_fmt == 8:
                 hq = ops.gemm_mxfp8_q(*(xq2 if xq2 is not None else ops.quantize_mxfp8(n)), w1q[0], w1q[1],
                                       blk.ff.net[0].proj.bias, ops.EPI_GELU_TANH)
                 ops.gemm_mxfp8(hq[0], hq[1], w2q[0], w2q[1], blk.ff.net[2].bias, ops.EPI_GATED_RESIDUAL_STAGED,

@@ -584,6 +584,58 @@ def gemm_mxfp8_q(aq, a_scales, wq, w_scales, bias, epilogue=EPI_NONE, out=None):
     return q, s
 
 
+def quantize_mxfp6(x, out=None):
+    """x [rows, cols] bf16|fp16 (cols % 128 == 0) -> (q uint8 [fino_mxfp6_bytes], scales uint8 [...]): OCP e2m3 elements packed
+    as the 16-row x 128-column fragments fino_gemm_mxfp6 reads (include/frameino_hip.h), one e8m0 scale per 32 K-elements."""
+    x2, rows, cols, ldx = _rows2d(x)
+    nbytes = _lib.lib().fino_mxfp6_scale_bytes(rows, cols)
+    if nbytes <= 0:
+        raise ValueError(f"quantize_mxfp6: cols={cols} must be a positive multiple of 128")
+    if out is None:
+        q = torch.empty(_lib.lib().fino_mxfp6_bytes(rows, cols), dtype=torch.uint8, device=x.device)
+        s = torch.zeros(nbytes, dtype=torch.uint8, device=x.device)
+    else:
+        q, s = out
+    _lib.check(_lib.lib().fino_quantize_mxfp6(_p(x2), _p(q), _p(s), rows, cols, ldx, _dt(x), _stream()),
+               "fino_quantize_mxfp6")
+    q.mx_shape = (rows, cols)
+    return q, s
+
+
+def gemm_mxfp6(aq, a_scales, wq, w_scales, bias=None, epilogue=EPI_NONE, residual=None, gate=None, sel=None, out=None,
+               out_dtype=torch.bfloat16, m=None, n=None, k=None):
+    """C = epilogue(dequant(aq).dequant(wq)^T + bias): aq / wq the packed images quantize_mxfp6 made of [M, K] / [N, K].  The
+    images are flat byte tensors; quantize_mxfp6 notes the matrix shape on them (`q.mx_shape`), and `m` / `n` / `k` say it for
+    images that came another way (a view, a copy)."""
+    assert aq.dtype == torch.uint8 and wq.dtype == torch.uint8 and aq.is_contiguous() and wq.is_contiguous()
+    sa_, sw_ = getattr(aq, "mx_shape", None), getattr(wq, "mx_shape", None)
+    m = m if m is not None else (sa_[0] if sa_ else None)
+    n = n if n is not None else (sw_[0] if sw_ else None)
+    k = k if k is not None else (sa_[1] if sa_ else (sw_[1] if sw_ else None))
+    if m is None or n is None or k is None:
+        raise ValueError("gemm_mxfp6: operands without mx_shape need m / n / k")
+    if sw_ and sw_[1] != k:
+        raise ValueError(f"gemm_mxfp6: K of A ({k}) and of W ({sw_[1]}) differ")
+    lib = _lib.lib()
+    if aq.numel() != lib.fino_mxfp6_bytes(m, k) or wq.numel() != lib.fino_mxfp6_bytes(n, k):
+        raise ValueError(f"gemm_mxfp6: operand sizes {aq.numel()} / {wq.numel()} do not match M={m} N={n} K={k}")
+    if out is None:
+        out = torch.empty((m, n), dtype=out_dtype, device=aq.device)
+    o2, _, _, ldc = _rows2d(out)
+    r2, ldr = (None, 0)
+    if residual is not None:
+        r2, _, _, ldr = _rows2d(residual)
+    ms = gate.stride(0) if (gate is not None and gate.dim() == 2) else 0
+    ev = _timed("gemm")
+    _lib.check(lib.fino_gemm_mxfp6(_p(aq), _p(a_scales), _p(wq), _p(w_scales), _p(bias), _p(o2), m, n, k, ldc,
+                                   epilogue, _p(r2), ldr, _p(gate), ms, _p(sel), _dt(out), _stream()),
+               "fino_gemm_mxfp6")
+    if ev is not None:
+        ev.record()
+        KernelTimer.active.flops["gemm"] = KernelTimer.active.flops.get("gemm", 0.0) + 2.0 * m * n * k
+    return out
+
+
 def skinny_linear(x, w, b=None, silu_input=False):
     """fp32 y = W.(silu?)(x) + b for M <= 16 rows; w fp32 or bf16/fp16."""
     assert x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and w.is_contiguous()

@@ -149,6 +149,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self.parallel = None      # frameino_amd.parallel.TokenShard or None
         self._fp8 = {}            # (layer, linear) -> (e4m3 weight bytes, MX scales); see enable_mxfp8_linears
         self._fp8_pending = False # MXFP8 was on when the parameters last moved / changed: re-quantise at the next forward
+        self._mx_fmt = 8          # element format of the `_fp8` entries: 8 = e4m3 (enable_mxfp8_linears), 6 = e2m3 (enable_mxfp6_linears)
         self.dedup_shared_prefix = True   # A/B knob: CFG-batched call computes the branch-invariant prefix once
         # True: q of the self-attention leaves its norm + RoPE kernel already multiplied by head_dim**-0.5 * log2(e) (fp32,
         # one rounding) and the attention kernels take q.k as the exp2 argument (FINO_ATTN_SCALE_FOLDED), which lets the
@@ -265,18 +266,40 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         accumulate): weights are quantised once here, activations per call.  Attention, norms, modulation, embeddings
         and the output head stay in the model dtype.  There is no reference counterpart: the result is
         compared with this model's own bf16 forward (tests/test_mxfp8_gpu.py)."""
+        return self._enable_mx_linears(8, enabled)
+
+    def enable_mxfp6_linears(self, enabled=True):
+        """The same six linears on the MXFP6 path (`fino_quantize_mxfp6` + `fino_gemm_mxfp6`: OCP e2m3 -- e4m3's three
+        mantissa bits, the block scale supplies the range -- with one e8m0 scale per 32 K-elements, fp32 accumulate, at the
+        FP4 matrix rate).  Weights are quantised once here, activations per call, from the model dtype (no fused producers:
+        LayerNorm and the FFN's GELU write the model dtype and `fino_quantize_mxfp6` follows).  One reduced precision at a
+        time: raises ValueError while `enable_mxfp8_linears()` is on.  Independent of `enable_fp8_attention()` and
+        `enable_cache()`; `enable_mxfp6_linears(False)` returns the model to its model-dtype output bit for bit."""
+        return self._enable_mx_linears(6, enabled)
+
+    def _enable_mx_linears(self, fmt, enabled):
+        on = bool(self._fp8) or self._fp8_pending
+        if on and self._mx_fmt != fmt:
+            if not enabled:
+                return self                                     # the other precision's switch: nothing of this one to drop
+            raise ValueError(f"enable_mxfp{fmt}_linears: enable_mxfp{self._mx_fmt}_linears() is on -- one reduced precision at a "
+                             f"time; call enable_mxfp{self._mx_fmt}_linears(False) first")
         self._fp8 = {}
         self._fp8_pending = False
         if not enabled:
             return self
+        self._mx_fmt = fmt
         pk = self._packed or self._pack()
-        o = self.ops
+        quantize = self._mx_quantize()
         for li, (blk, e) in enumerate(zip(self.blocks, pk.layers)):
             for key, w in (("qkv", e.wqkv), ("out", blk.attn1.to_out[0].weight), ("q2", blk.attn2.to_q.weight),
                            ("out2", blk.attn2.to_out[0].weight), ("ff1", blk.ffn.net[0].proj.weight),
                            ("ff2", blk.ffn.net[2].weight)):
-                self._fp8[(li, key)] = o.quantize_mxfp8(w.detach().contiguous())
+                self._fp8[(li, key)] = quantize(w.detach().contiguous())
         return self
+
+    def _mx_quantize(self):
+        return self.ops.quantize_mxfp6 if self._mx_fmt == 6 else self.ops.quantize_mxfp8
 
     def enable_fp8_attention(self, enabled=True, p_mode=None):
         """The 3-D self-attention (transformer_wan.py:108) with fp8 (e4m3) matrix operands -- q, k, v and P on the
@@ -294,6 +317,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         o = self.ops
         if not self._fp8 or (li, key) not in self._fp8 or not hasattr(o, "ln_mxfp8") or _NO_LN_MXFP8:
             return None
+        if self._mx_fmt == 6:
+            return None                                         # MXFP6 takes the two-pass route: norm -> model dtype -> quantise
         return o.ln_mxfp8(mode, x, **ln)
 
     def _lin(self, li, key, x, w, b, epi=0, xq=None, **kw):
@@ -304,10 +329,13 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         if wq is None and self._fp8 and key in ("kv", "q"):
             # token shards project K|V and Q separately: quantise those row blocks of the fused weight on first use
             # (MX scales are per output row, so this equals slicing the quantised fused weight)
-            wq = self._fp8[(li, key)] = o.quantize_mxfp8(w.detach().contiguous())
+            wq = self._fp8[(li, key)] = self._mx_quantize()(w.detach().contiguous())
         if wq is None:
             return o.gemm(x, w, b, epi, **kw)
-        kw.pop("tile_m", None)                                  # (the MXFP8 GEMM has one tile height)
+        kw.pop("tile_m", None)                                  # (the MX GEMMs have one tile height)
+        if self._mx_fmt == 6:
+            xq, xs = o.quantize_mxfp6(x)
+            return o.gemm_mxfp6(xq, xs, wq[0], wq[1], b, epi, **kw)
         xq, xs = xq if xq is not None else o.quantize_mxfp8(x)
         return o.gemm_mxfp8(xq, xs, wq[0], wq[1], b, epi, **kw)
 
@@ -501,7 +529,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._lora_apply(attention_kwargs.pop("scale", None) if attention_kwargs is not None else None)
         b = hidden_states.shape[0]
         if self._fp8_pending:
-            self.enable_mxfp8_linears()
+            self._enable_mx_linears(self._mx_fmt, True)
         pk = self._packed or self._pack()
         default_procs = self._default_processors()
         o = self.ops
@@ -829,7 +857,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             if xq3 is None:
                 for r0, r1 in segs:
                     o.adaln_modulate(x[r0:r1], m[:, 3], m[:, 4], None if sel is None else sel[r0:r1], cfg.eps, out=nrm[r0:r1])
-            if w1q is not None and w2q is not None:
+            if w1q is not None and w2q is not None and self._mx_fmt == 8:
                 # MXFP8: the adaLN emits the FFN input already quantised, and the GELU epilogue the hidden activations (no
                 # bf16 round trips)
                 hq = o.gemm_mxfp8_q(*(xq3 if xq3 is not None else o.quantize_mxfp8(nrm)), w1q[0], w1q[1],

@@ -430,6 +430,34 @@ int fino_gemm_mxfp8_q(const void* aq, const void* a_scales, const void* wq, cons
                       void* cq, void* c_scales, int64_t m, int64_t n, int64_t k, int epilogue, int bias_dtype,
                       void* stream);
 
+/* ---- MXFP6 linear layers: OCP e2m3 elements, one e8m0 scale per 32 consecutive K-elements -------------------------
+ * The e4m3 mantissa (3 bits) at the FP4 matrix rate (v_mfma_scale_f32_16x16x128_f8f6f4 with both operands e2m3: half the
+ * cycles of the MXFP8 form) and 3/4 of its operand bytes.  Same fused epilogues, output types and arguments as MXFP8.
+ * Element: 6 bits = sign (bit 5), exponent (bits 4:3, bias 1), mantissa (bits 2:0); exponent 0 = subnormal m/8, otherwise
+ *   (1 + m/8) * 2^(exponent - 1); largest magnitude 7.5; no inf / NaN.
+ * Block scale 2^e, e = the smallest integer with amax <= 7.5 * 2^e (amax / 2^e in (3.75, 7.5]), clamped to [-127, 127],
+ *   -127 for an all-zero block; element = round-to-nearest-even of v / 2^e onto the grid above, its sign bit that of v
+ *   (also for values that round to zero); stored scale byte e + 127.  A block holding inf or NaN quantises to unspecified
+ *   finite values.
+ * fino_quantize_mxfp6: x [rows, cols] bf16|fp16 (row stride ldx, cols % 128 == 0) -> q, fino_mxfp6_bytes(rows, cols) bytes,
+ *   and `scales`, fino_mxfp6_scale_bytes(rows, cols) bytes in the fino_quantize_mxfp8 scale layout
+ *   ([cols/128][rows_pad/256][1024], inside a KiB [K-block (4)][row & 15][row >> 4]); rows_pad = rows rounded up to 256.
+ *   q is the image the GEMM's wave reads, [cols/128][rows_pad/16] FRAGMENTS of 1536 bytes.  Fragment (kt, rg) holds rows
+ *   16 rg .. 16 rg + 15, columns 128 kt .. 128 kt + 127.  Lane l = 16 g + r (r = row & 15, g = (column & 127) / 32) owns the
+ *   32 elements of block g of row r as a 192-bit little-endian string, element j (column 128 kt + 32 g + j) in bits
+ *   [6j, 6j + 6): its bytes 0..15 are fragment bytes [16 l, 16 l + 16), its bytes 16..23 fragment bytes
+ *   [1024 + 8 l, 1024 + 8 l + 8).  Fragments of rows >= rows are not written (the last partly filled one repeats row
+ *   rows - 1).  Both q and scales must be 16-byte aligned.  Quantise weights once, activations per call.
+ * fino_gemm_mxfp6: C[M, N] = epilogue(dequant(Aq) . dequant(Wq)^T + bias); Aq / Wq as fino_quantize_mxfp6 writes them for
+ *   [M, K] / [N, K]; K % 128 == 0, N % 8 == 0; bias / residual / C in out_dtype, epilogue arguments as fino_gemm. */
+int64_t fino_mxfp6_bytes(int64_t rows, int64_t cols);
+int64_t fino_mxfp6_scale_bytes(int64_t rows, int64_t cols);
+int fino_quantize_mxfp6(const void* x, void* q, void* scales, int64_t rows, int64_t cols, int64_t ldx, int dtype,
+                        void* stream);
+int fino_gemm_mxfp6(const void* aq, const void* a_scales, const void* wq, const void* w_scales, const void* bias,
+                    void* c, int64_t m, int64_t n, int64_t k, int64_t ldc, int epilogue, const void* r, int64_t ldr,
+                    const float* gate, int64_t mod_stride, const int32_t* sel, int out_dtype, void* stream);
+
 /* ---- condition builders in front of the path ---------------------------------------------------------
  * Trajectory video of data_loader/video_dataset_motion.py:120-206 (`prepare_traj_tensor`, app.py:616-620).
  * fino_traj_paint: canvas fp32 [frames, 3, H, W] = 255, then for every frame its points, in order, paint the square
