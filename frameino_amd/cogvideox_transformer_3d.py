@@ -23,6 +23,7 @@ from . import ops
 from .attention_processor import Attention, MI355CogVideoXAttnProcessor, MI355FusedCogVideoXAttnProcessor
 from .loading import FromPretrainedMixin
 from .lora import LoraModelMixin
+from .mx_linears import MXLinearsMixin
 from .transformer_wan import FeedForward, _Config, _MLP2
 
 
@@ -79,7 +80,9 @@ def cog_sincos_pos_embed(embed_dim, pw, ph, frames, spatial_scale, temporal_scal
     return torch.cat([temporal, spatial], dim=-1).flatten(0, 1)
 
 
-class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin):
+class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, MXLinearsMixin):
+    """MX linears (enable_mxfp8_linears / enable_mxfp6_linears): four large linears of every block -- QKV, attention out, FFN
+    up / down; with `enable_fp8_attention()` MXFP8 is BASELINE config 5's "fp8 MFMA path" end to end."""
     _loader_name = "load_cogvideox_transformer"
 
     def __init__(self, num_attention_heads=30, attention_head_dim=64, in_channels=16, out_channels=16,
@@ -126,9 +129,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         self.proj_out = nn.Linear(inner, patch_size * patch_size * out_channels)
         self._packed = None
         self._pos_cache = {}
-        self._fp8 = {}
-        self._fp8_pending = False
-        self._mx_fmt = 8          # element format of the `_fp8` entries: 8 = e4m3 (enable_mxfp8_linears), 6 = e2m3 (enable_mxfp6_linears)
+        self.ops = ops            # kernel front end (tests inject a CPU stand-in)
         self.fp8_attention = False           # see enable_fp8_attention
         # q leaves its LayerNorm + RoPE kernel multiplied by head_dim**-0.5 * log2(e) and the attention kernels take q.k as
         # the exp2 argument (FINO_ATTN_SCALE_FOLDED): at head_dim 64 that selects the 4-wave kernel with the running maximum
@@ -186,12 +187,10 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         return self
 
     def reset_caches(self):
-        """Drop everything derived from the parameters (packed / fused copies, MXFP8 weights, positional tables);
-        called whenever the parameters may have changed or moved."""
-        had_fp8 = bool(self._fp8) or self._fp8_pending
+        """Drop everything derived from the parameters (packed / fused copies, MX weights, positional tables); called
+        whenever the parameters may have changed or moved.  Returns whether MX linears were on (the next forward re-quantises)."""
+        had_fp8 = self._mx_invalidate()
         self._packed = None
-        self._fp8 = {}
-        self._fp8_pending = had_fp8      # re-quantised lazily by the next forward, from wherever the parameters are then
         self._pos_cache.clear()
         return had_fp8
 
@@ -207,40 +206,11 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         return out
 
     # ---- packing ----
-    # ------------------------------------------------------------------ MXFP8 linears (BASELINE config 5)
-    def enable_mxfp8_linears(self, enabled=True):
-        """QKV, attention out, FFN up and FFN down of every block on the MXFP8 path (OCP e4m3 + one e8m0 scale per 32
-        K-elements, fp32 accumulate; `fino_quantize_mxfp8` / `fino_gemm_mxfp8`); weights are quantised once here.
-        Attention, norms, embeddings and the output head stay in the model dtype.  No reference counterpart (SURVEY
-        F11): compared with this model's own bf16 forward."""
-        return self._enable_mx_linears(8, enabled)
-
-    def enable_mxfp6_linears(self, enabled=True):
-        """The same four linears on the MXFP6 path (OCP e2m3 + one e8m0 scale per 32 K-elements, fp32 accumulate, at the FP4
-        matrix rate; `fino_quantize_mxfp6` / `fino_gemm_mxfp6`).  Activations are quantised per call from the model dtype
-        (no fused producers).  One reduced precision at a time: raises ValueError while `enable_mxfp8_linears()` is on;
-        `enable_mxfp6_linears(False)` returns the model to its model-dtype output bit for bit."""
-        return self._enable_mx_linears(6, enabled)
-
-    def _enable_mx_linears(self, fmt, enabled):
-        on = bool(self._fp8) or self._fp8_pending
-        if on and self._mx_fmt != fmt:
-            if not enabled:
-                return self                                     # the other precision's switch: nothing of this one to drop
-            raise ValueError(f"enable_mxfp{fmt}_linears: enable_mxfp{self._mx_fmt}_linears() is on -- one reduced precision at a "
-                             f"time; call enable_mxfp{self._mx_fmt}_linears(False) first")
-        self._fp8 = {}
-        self._fp8_pending = False
-        if not enabled:
-            return self
-        self._mx_fmt = fmt
-        quantize = ops.quantize_mxfp6 if fmt == 6 else ops.quantize_mxfp8
-        pk = self._packed or self._pack()
+    def _mx_linear_weights(self, pk):
         for li, (blk, e) in enumerate(zip(self.transformer_blocks, pk.layers)):
             for key, w in (("qkv", e.wqkv), ("out", blk.attn1.to_out[0].weight), ("ff1", blk.ff.net[0].proj.weight),
                            ("ff2", blk.ff.net[2].weight)):
-                self._fp8[(li, key)] = quantize(w.detach().contiguous())
-        return self
+                yield li, key, w
 
     def enable_fp8_attention(self, enabled=True, p_mode=None):
         """The joint text + video self-attention (attention_processor.py:2863 of the reference, head_dim 64: 55 % of the
@@ -253,25 +223,6 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         self.fp8_attention = bool(enabled)
         self.fp8_p_mode = p_mode
         return self
-
-    def _lin(self, li, key, x, w, b, epi=0, xq=None, **kw):
-        wq = self._fp8.get((li, key)) if self._fp8 else None
-        if wq is None:
-            return ops.gemm(x, w, b, epi, **kw)
-        if self._mx_fmt == 6:
-            xq, xs = ops.quantize_mxfp6(x)
-            return ops.gemm_mxfp6(xq, xs, wq[0], wq[1], b, epi, **kw)
-        xq, xs = xq if xq is not None else ops.quantize_mxfp8(x)
-        return ops.gemm_mxfp8(xq, xs, wq[0], wq[1], b, epi, **kw)
-
-    def _lnz_q(self, li, key, x2, w, b, shift, scale, sel, eps):
-        """CogVideoXLayerNormZero in front of linear (li, key) emitted directly as that linear's MXFP8 activations
-        (fino_ln_mxfp8 mode 2: one pass instead of norm -> bf16 -> quantise); None when the linear is not on the MXFP8 path"""
-        if not self._fp8 or (li, key) not in self._fp8 or not hasattr(ops, "ln_mxfp8") or os.environ.get("FINO_NO_LN_MXFP8"):
-            return None
-        if self._mx_fmt == 6:
-            return None                                         # MXFP6 takes the two-pass route: norm -> model dtype -> quantise
-        return ops.ln_mxfp8(2, x2, weight=w, bias=b, shift=shift, scale=scale, sel=sel, eps=eps)
 
     def _default_processors(self):
         return all(type(b.attn1.processor) in (MI355CogVideoXAttnProcessor, MI355FusedCogVideoXAttnProcessor)
@@ -336,14 +287,14 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         the other frames' tokens then serve as keys / values only, and so do the TEXT rows on every call (the model returns video
         rows only, :531-542): their attention queries, out-projection and feed-forward are skipped; dropped frames come back ZERO.
         Every returned row is computed exactly as without it."""
+        ops = self.ops
         if timestep_cond is not None:
             raise NotImplementedError("timestep_cond is never passed on the FrameINO path")
         if attention_kwargs is not None:
             attention_kwargs = dict(attention_kwargs)
         # LoRA scale (:460-465): adapters are merged into the weights, a changed scale re-merges them here (frameino_amd/lora.py)
         self._lora_apply(attention_kwargs.pop("scale", None) if attention_kwargs is not None else None)
-        if self._fp8_pending:
-            self._enable_mx_linears(self._mx_fmt, True)
+        self._mx_requantise_if_pending()
         pk = self._packed or self._pack()
         default_procs = self._default_processors()
         c = self.config
@@ -420,7 +371,9 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                     self._lin(li, "ff2", ff, blk.ff.net[2].weight, blk.ff.net[2].bias, ops.EPI_GATED_RESIDUAL_STAGED,
                               residual=xs, gate=t2[:, 2], sel=ss, out=xs)
                 continue
-            xq1 = self._lnz_q(li, "qkv", x2, e.n1w, e.n1b, t1[:, 0], t1[:, 1], sel, c.norm_eps) if default_procs else None
+            # CogVideoXLayerNormZero emitted directly as the linear's MXFP8 activations (None when it is not on that path)
+            xq1 = (self._ln_q(li, "qkv", 2, x2, weight=e.n1w, bias=e.n1b, shift=t1[:, 0], scale=t1[:, 1], sel=sel, eps=c.norm_eps)
+                   if default_procs else None)
             n = None if xq1 is not None else ops.layernorm_zero(x2, e.n1w, e.n1b, t1[:, 0], t1[:, 1], sel, c.norm_eps)
             if default_procs:
                 qkv = self._lin(li, "qkv", n, e.wqkv, e.bqkv, xq=xq1).view(b, L, 3 * d)
@@ -440,17 +393,11 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                                    image_rotary_emb=image_rotary_emb, **(attention_kwargs or {}))
                 y = torch.cat([ae, ah], dim=1).reshape(b * L, d)
                 ops.gated_residual(x2, y, t1[:, 2], sel, out=x2, staged=True)
-            fp8 = self._fp8
-            w1q, w2q = fp8.get((li, "ff1")), fp8.get((li, "ff2"))
-            xq2 = (self._lnz_q(li, "ff1", x2, e.n2w, e.n2b, t2[:, 0], t2[:, 1], sel, c.norm_eps)
-                   if (w1q is not None and w2q is not None) else None)
+            xq2 = (self._ln_q(li, "ff1", 2, x2, weight=e.n2w, bias=e.n2b, shift=t2[:, 0], scale=t2[:, 1], sel=sel, eps=c.norm_eps)
+                   if (li, "ff2") in self._fp8 else None)
             n = None if xq2 is not None else ops.layernorm_zero(x2, e.n2w, e.n2b, t2[:, 0], t2[:, 1], sel, c.norm_eps)
-            if w1q is not None and w2q is not None and self._mx_fmt == 8:
-                hq = ops.gemm_mxfp8_q(*(xq2 if xq2 is not None else ops.quantize_mxfp8(n)), w1q[0], w1q[1],
-                                      blk.ff.net[0].proj.bias, ops.EPI_GELU_TANH)
-                ops.gemm_mxfp8(hq[0], hq[1], w2q[0], w2q[1], blk.ff.net[2].bias, ops.EPI_GATED_RESIDUAL_STAGED,
-                               residual=x2, gate=t2[:, 2], sel=sel, out=x2)
-            else:
+            if self._ffn_mxfp8(li, n, xq2, blk.ff.net[0].proj.bias, blk.ff.net[2].bias, ops.EPI_GATED_RESIDUAL_STAGED,
+                               residual=x2, gate=t2[:, 2], sel=sel, out=x2) is None:
                 ff = self._lin(li, "ff1", n, blk.ff.net[0].proj.weight, blk.ff.net[0].proj.bias, ops.EPI_GELU_TANH)
                 self._lin(li, "ff2", ff, blk.ff.net[2].weight, blk.ff.net[2].bias, ops.EPI_GATED_RESIDUAL_STAGED,
                           residual=x2, gate=t2[:, 2], sel=sel, out=x2)

@@ -1,5 +1,7 @@
 // Shared definitions of the MFMA GEMM / implicit-GEMM conv kernels (fino_gemm.hip).
 #pragma once
+#include <type_traits>
+
 #include "fino_common.h"
 
 #ifdef FINO_GEMM_STAMP
@@ -334,6 +336,60 @@ __device__ __forceinline__ void gemm_epilogue(f32x4_t (&acc)[MI][4], const GemmP
         gemm_epilogue_f32<EPI, MI>(acc, p, m0, n0, lane, wm, wn);
     else
         gemm_epilogue_t<T, EPI, QOUT, MI>(acc, p, smem, m0, n0, tid, lane, wm, wn);
+}
+
+// ================= host side shared by the MX GEMMs (fino_gemm_fp8.hip, fino_gemm_fp6.hip) =================
+struct MxGemmParams {
+    GemmParams g;                  // a / w = the quantiser's element images (e4m3 bytes; e2m3 fragments); k in elements
+    const uint8_t* sa;             // [k/128][m_pad/256][1024]: inside a KiB [K-block g][row & 15][row >> 4]
+    const uint8_t* sw;             // [k/128][n_pad/256][1024]
+    int64_t m_pad, n_pad;
+};
+
+// Validates the arguments of an MX GEMM entry point `who` (its name, the prefix of every error text) and fills `fp`:
+// GemmParams, tiles, group_m, the scales and the padded sizes.  `qout`: the result leaves quantised (fino_gemm_mxfp8_q:
+// the caller checks and sets cq / cs), so there is no c / ldc.  What only one entry point asks for (the bounds on the
+// operand sizes, M = 0) stays with it.
+inline int mx_gemm_params(MxGemmParams& fp, const char* who, bool qout, const void* aq, const void* a_scales, const void* wq,
+                          const void* w_scales, const void* bias, void* c, int64_t m, int64_t n, int64_t k, int64_t ldc,
+                          int epilogue, const void* r, int64_t ldr, const float* gate, int64_t mod_stride,
+                          const int32_t* sel, int dtype) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "%s: dtype %d", who, dtype);
+    FINO_CHECK(aq && a_scales && wq && w_scales && (qout || c), FINO_ERR_ARG, "%s: null pointer", who);
+    FINO_CHECK(m >= 0 && n > 0 && k > 0 && k % 128 == 0 && n % 8 == 0, FINO_ERR_ARG,
+               "%s: K=%lld must be a multiple of 128, N=%lld of 8", who, (long long)k, (long long)n);
+    FINO_CHECK((qout || (ldc % 8 == 0 && ldc >= n && fino_aligned16(c))) && fino_aligned16(aq) && fino_aligned16(wq) &&
+                   fino_aligned16(a_scales) && fino_aligned16(w_scales),
+               FINO_ERR_ARG, "%s: alignment / leading dimension", who);
+    FINO_CHECK(epilogue >= FINO_EPI_NONE && epilogue <= FINO_EPI_GATED_RESIDUAL_STAGED, FINO_ERR_ARG, "%s: epilogue %d", who,
+               epilogue);
+    if (epilogue >= FINO_EPI_RESIDUAL)
+        FINO_CHECK(r && ldr % 8 == 0 && ldr >= n && fino_aligned16(r), FINO_ERR_ARG, "%s: residual operand", who);
+    if (epilogue == FINO_EPI_GATED_RESIDUAL || epilogue == FINO_EPI_GATED_RESIDUAL_STAGED)
+        FINO_CHECK(gate && fino_aligned16(gate) && mod_stride % 4 == 0, FINO_ERR_ARG, "%s: gate operand", who);
+    fp = {};
+    GemmParams& p = fp.g;
+    p.a = (const uint16_t*)aq; p.w = (const uint16_t*)wq; p.bias = (const uint16_t*)bias; p.c = (uint16_t*)c;
+    p.r = (const uint16_t*)r; p.gate = gate; p.sel = sel;
+    p.m = m; p.n = n; p.k = k; p.lda = k; p.ldw = k; p.ldc = ldc; p.ldr = ldr; p.mod_stride = mod_stride;
+    p.tiles_m = (int)((m + BM - 1) / BM);
+    p.tiles_n = (int)((n + BN - 1) / BN);
+    p.group_m = fino_tune_get(FINO_TUNE_GEMM_GROUP_M);
+    fp.sa = (const uint8_t*)a_scales; fp.sw = (const uint8_t*)w_scales;
+    fp.m_pad = (m + 255) / 256 * 256; fp.n_pad = (n + 255) / 256 * 256;
+    return FINO_OK;
+}
+
+// the epilogues an MX GEMM is instantiated for: `launch` is called with the epilogue as an integral constant
+template <typename F>
+int mx_dispatch_epilogue(int epi, F&& launch) {
+    switch (epi) {
+        case FINO_EPI_NONE: return launch(std::integral_constant<int, FINO_EPI_NONE>{});
+        case FINO_EPI_GELU_TANH: return launch(std::integral_constant<int, FINO_EPI_GELU_TANH>{});
+        case FINO_EPI_RESIDUAL: return launch(std::integral_constant<int, FINO_EPI_RESIDUAL>{});
+        case FINO_EPI_GATED_RESIDUAL_STAGED: return launch(std::integral_constant<int, FINO_EPI_GATED_RESIDUAL_STAGED>{});
+        default: return launch(std::integral_constant<int, FINO_EPI_GATED_RESIDUAL>{});
+    }
 }
 
 }  // namespace fino_gemm_ns

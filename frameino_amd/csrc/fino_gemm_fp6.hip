@@ -45,13 +45,6 @@ constexpr int kStages = 3;
 constexpr int kSmem6 = (kStages * kStage6 > BM * kCsStride) ? kStages * kStage6 : BM * kCsStride;
 static_assert(kSmem6 <= 160 * 1024, "LDS budget");
 
-struct Fp6Params {
-    GemmParams g;                  // a / w = fragment images (see the header comment); k in elements
-    const uint8_t* sa;             // [k/128][m_pad/256][1024]: inside a KiB [K-block g][row & 15][row >> 4] (the MXFP8 layout)
-    const uint8_t* sw;             // [k/128][n_pad/256][1024]
-    int64_t m_pad, n_pad;
-};
-
 // ---------------------------------------------------------------------------------------------------- quantize
 // One e2m3 code (sign, 2 exponent bits of bias 1, 3 mantissa bits) of y, |y| <= 7.5: round-to-nearest-even onto the grid
 // whose step is 1/8 below 2, 1/4 below 4 and 1/2 below 8.  Adding 2^(23 + s) makes the fp32 adder round to a multiple of 2^s.
@@ -141,7 +134,7 @@ __device__ __forceinline__ u32x4_t buffer_desc(const void* ptr, uint32_t bytes) 
 }
 
 template <typename T, int EPI>
-__global__ __launch_bounds__(kThreads, 2) void gemm_mxfp6_kernel(const Fp6Params fp) {
+__global__ __launch_bounds__(kThreads, 2) void gemm_mxfp6_kernel(const MxGemmParams fp) {   // g.a / w = fragment images
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const GemmParams& p = fp.g;
     const int tid = threadIdx.x;
@@ -305,7 +298,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_mxfp6_kernel(const Fp6Params
 }
 
 template <typename T, int EPI>
-int launch_mxfp6(const Fp6Params& fp, hipStream_t st) {
+int launch_mxfp6(const MxGemmParams& fp, hipStream_t st) {
     static FinoPerDeviceOnce once;
     if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&gemm_mxfp6_kernel<T, EPI>), kSmem6, "fino_gemm_mxfp6")) return rc;
     gemm_mxfp6_kernel<T, EPI><<<dim3((unsigned)(fp.g.tiles_m * fp.g.tiles_n)), kThreads, kSmem6, st>>>(fp);
@@ -314,14 +307,8 @@ int launch_mxfp6(const Fp6Params& fp, hipStream_t st) {
 }
 
 template <typename T>
-int launch_mxfp6_e(const Fp6Params& fp, int epi, hipStream_t st) {
-    switch (epi) {
-        case FINO_EPI_NONE: return launch_mxfp6<T, FINO_EPI_NONE>(fp, st);
-        case FINO_EPI_GELU_TANH: return launch_mxfp6<T, FINO_EPI_GELU_TANH>(fp, st);
-        case FINO_EPI_RESIDUAL: return launch_mxfp6<T, FINO_EPI_RESIDUAL>(fp, st);
-        case FINO_EPI_GATED_RESIDUAL_STAGED: return launch_mxfp6<T, FINO_EPI_GATED_RESIDUAL_STAGED>(fp, st);
-        default: return launch_mxfp6<T, FINO_EPI_GATED_RESIDUAL>(fp, st);
-    }
+int launch_mxfp6_e(const MxGemmParams& fp, int epi, hipStream_t st) {
+    return mx_dispatch_epilogue(epi, [&](auto e) { return launch_mxfp6<T, decltype(e)::value>(fp, st); });
 }
 
 }  // namespace
@@ -363,32 +350,13 @@ extern "C" int fino_gemm_mxfp6(const void* aq, const void* a_scales, const void*
                                const void* bias, void* c, int64_t m, int64_t n, int64_t k, int64_t ldc, int epilogue,
                                const void* r, int64_t ldr, const float* gate, int64_t mod_stride, const int32_t* sel,
                                int out_dtype, void* stream) {
-    FINO_CHECK(out_dtype == FINO_BF16 || out_dtype == FINO_F16, FINO_ERR_ARG, "fino_gemm_mxfp6: out dtype %d", out_dtype);
-    FINO_CHECK(aq && a_scales && wq && w_scales && c, FINO_ERR_ARG, "fino_gemm_mxfp6: null pointer");
-    FINO_CHECK(m >= 0 && n > 0 && k > 0 && k % 128 == 0 && n % 8 == 0, FINO_ERR_ARG,
-               "fino_gemm_mxfp6: K=%lld must be a multiple of 128, N=%lld of 8", (long long)k, (long long)n);
-    FINO_CHECK(ldc % 8 == 0 && ldc >= n && fino_aligned16(aq) && fino_aligned16(wq) && fino_aligned16(c) &&
-                   fino_aligned16(a_scales) && fino_aligned16(w_scales),
-               FINO_ERR_ARG, "fino_gemm_mxfp6: alignment / leading dimension");
-    FINO_CHECK(epilogue >= FINO_EPI_NONE && epilogue <= FINO_EPI_GATED_RESIDUAL_STAGED, FINO_ERR_ARG,
-               "fino_gemm_mxfp6: epilogue %d", epilogue);
-    if (epilogue >= FINO_EPI_RESIDUAL)
-        FINO_CHECK(r && ldr % 8 == 0 && ldr >= n && fino_aligned16(r), FINO_ERR_ARG, "fino_gemm_mxfp6: residual operand");
-    if (epilogue == FINO_EPI_GATED_RESIDUAL || epilogue == FINO_EPI_GATED_RESIDUAL_STAGED)
-        FINO_CHECK(gate && fino_aligned16(gate) && mod_stride % 4 == 0, FINO_ERR_ARG, "fino_gemm_mxfp6: gate operand");
+    MxGemmParams fp;
+    if (int rc = mx_gemm_params(fp, "fino_gemm_mxfp6", false, aq, a_scales, wq, w_scales, bias, c, m, n, k, ldc, epilogue, r,
+                                ldr, gate, mod_stride, sel, out_dtype))
+        return rc;
     if (m == 0) return FINO_OK;
-    Fp6Params fp = {};
-    fp.m_pad = (m + 255) / 256 * 256; fp.n_pad = (n + 255) / 256 * 256;
     FINO_CHECK(fp.m_pad * k < (1ll << 31) && fp.n_pad * k < (1ll << 31), FINO_ERR_UNSUPPORTED,
                "fino_gemm_mxfp6: operand > 2 GiB");
-    GemmParams& p = fp.g;
-    p.a = (const uint16_t*)aq; p.w = (const uint16_t*)wq; p.bias = (const uint16_t*)bias; p.c = (uint16_t*)c;
-    p.r = (const uint16_t*)r; p.gate = gate; p.sel = sel;
-    p.m = m; p.n = n; p.k = k; p.lda = k; p.ldw = k; p.ldc = ldc; p.ldr = ldr; p.mod_stride = mod_stride;
-    p.tiles_m = (int)((m + BM - 1) / BM);
-    p.tiles_n = (int)((n + BN - 1) / BN);
-    p.group_m = fino_tune_get(FINO_TUNE_GEMM_GROUP_M);
-    fp.sa = (const uint8_t*)a_scales; fp.sw = (const uint8_t*)w_scales;
     hipStream_t st = (hipStream_t)stream;
     return out_dtype == FINO_BF16 ? launch_mxfp6_e<BF16>(fp, epilogue, st) : launch_mxfp6_e<F16>(fp, epilogue, st);
 }

@@ -25,13 +25,6 @@ constexpr int kScaleBytes = 2048;                         // A scales 1 KiB + W 
 constexpr int kStageF8 = kStageBytes + kScaleBytes;       // 66 KiB
 constexpr int kSmemF8 = (2 * kStageF8 > BM * kCsStride) ? 2 * kStageF8 : BM * kCsStride;
 
-struct Fp8Params {
-    GemmParams g;                  // a / w = e4m3 bytes; lda / ldw in BYTES (= elements); k in elements
-    const uint8_t* sa;             // [k/128][m_pad/256][1024]: inside a KiB [K-block g][row & 15][row >> 4]
-    const uint8_t* sw;             // [k/128][n_pad/256][1024]
-    int64_t m_pad, n_pad;
-};
-
 // ---------------------------------------------------------------------------------------------------- quantize
 // lane: 8 consecutive elements; 4 lanes = one 32-element block; e = exponent with amax / 2^e in [224, 448]
 template <typename T>
@@ -56,7 +49,7 @@ __global__ __launch_bounds__(256) void mxfp8_quantize_kernel(const uint16_t* __r
 
 // ---------------------------------------------------------------------------------------------------- GEMM
 template <typename T, int EPI, bool QOUT>
-__global__ __launch_bounds__(kThreads, 2) void gemm_mxfp8_kernel(const Fp8Params fp) {
+__global__ __launch_bounds__(kThreads, 2) void gemm_mxfp8_kernel(const MxGemmParams fp) {   // g.lda / ldw in BYTES (= elements)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const GemmParams& p = fp.g;
     const int tid = threadIdx.x;
@@ -215,7 +208,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_mxfp8_kernel(const Fp8Params
 }
 
 template <typename T, int EPI, bool QOUT = false>
-int launch_mxfp8(const Fp8Params& fp, hipStream_t st) {
+int launch_mxfp8(const MxGemmParams& fp, hipStream_t st) {
     static FinoPerDeviceOnce once;
     if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&gemm_mxfp8_kernel<T, EPI, QOUT>), kSmemF8, "fino_gemm_mxfp8")) return rc;
     gemm_mxfp8_kernel<T, EPI, QOUT><<<dim3((unsigned)(fp.g.tiles_m * fp.g.tiles_n)), kThreads, kSmemF8, st>>>(fp);
@@ -224,14 +217,8 @@ int launch_mxfp8(const Fp8Params& fp, hipStream_t st) {
 }
 
 template <typename T>
-int launch_mxfp8_e(const Fp8Params& fp, int epi, hipStream_t st) {
-    switch (epi) {
-        case FINO_EPI_NONE: return launch_mxfp8<T, FINO_EPI_NONE>(fp, st);
-        case FINO_EPI_GELU_TANH: return launch_mxfp8<T, FINO_EPI_GELU_TANH>(fp, st);
-        case FINO_EPI_RESIDUAL: return launch_mxfp8<T, FINO_EPI_RESIDUAL>(fp, st);
-        case FINO_EPI_GATED_RESIDUAL_STAGED: return launch_mxfp8<T, FINO_EPI_GATED_RESIDUAL_STAGED>(fp, st);
-        default: return launch_mxfp8<T, FINO_EPI_GATED_RESIDUAL>(fp, st);
-    }
+int launch_mxfp8_e(const MxGemmParams& fp, int epi, hipStream_t st) {
+    return mx_dispatch_epilogue(epi, [&](auto e) { return launch_mxfp8<T, decltype(e)::value>(fp, st); });
 }
 
 }  // namespace
@@ -264,35 +251,21 @@ extern "C" int fino_quantize_mxfp8(const void* x, void* q, void* scales, int64_t
     return FINO_OK;
 }
 
-static int mxfp8_fill(Fp8Params& fp, const void* aq, const void* a_scales, const void* wq, const void* w_scales,
-                      const void* bias, int64_t m, int64_t n, int64_t k) {
-    GemmParams& p = fp.g;
-    p.a = (const uint16_t*)aq; p.w = (const uint16_t*)wq; p.bias = (const uint16_t*)bias;
-    p.m = m; p.n = n; p.k = k; p.lda = k; p.ldw = k;
-    p.tiles_m = (int)((m + BM - 1) / BM);
-    p.tiles_n = (int)((n + BN - 1) / BN);
-    p.group_m = fino_tune_get(FINO_TUNE_GEMM_GROUP_M);
-    fp.sa = (const uint8_t*)a_scales; fp.sw = (const uint8_t*)w_scales;
-    fp.m_pad = (m + 255) / 256 * 256; fp.n_pad = (n + 255) / 256 * 256;
-    return FINO_OK;
-}
-
 extern "C" int fino_gemm_mxfp8_q(const void* aq, const void* a_scales, const void* wq, const void* w_scales,
                                  const void* bias, void* cq, void* c_scales, int64_t m, int64_t n, int64_t k,
                                  int epilogue, int bias_dtype, void* stream) {
-    FINO_CHECK(bias_dtype == FINO_BF16 || bias_dtype == FINO_F16, FINO_ERR_ARG, "fino_gemm_mxfp8_q: dtype %d", bias_dtype);
-    FINO_CHECK(aq && a_scales && wq && w_scales && cq && c_scales, FINO_ERR_ARG, "fino_gemm_mxfp8_q: null pointer");
-    FINO_CHECK(m >= 0 && n > 0 && k > 0 && k % 128 == 0 && n % 128 == 0, FINO_ERR_ARG,
-               "fino_gemm_mxfp8_q: K=%lld and N=%lld must be multiples of 128", (long long)k, (long long)n);
+    MxGemmParams fp;
+    if (int rc = mx_gemm_params(fp, "fino_gemm_mxfp8_q", true, aq, a_scales, wq, w_scales, bias, nullptr, m, n, k, 0,
+                                epilogue, nullptr, 0, nullptr, 0, nullptr, bias_dtype))
+        return rc;
+    FINO_CHECK(cq && c_scales, FINO_ERR_ARG, "fino_gemm_mxfp8_q: null pointer");
+    FINO_CHECK(n % 128 == 0, FINO_ERR_ARG, "fino_gemm_mxfp8_q: K=%lld and N=%lld must be multiples of 128", (long long)k,
+               (long long)n);
     FINO_CHECK(epilogue == FINO_EPI_NONE || epilogue == FINO_EPI_GELU_TANH, FINO_ERR_ARG,
                "fino_gemm_mxfp8_q: epilogue %d (NONE or GELU_TANH)", epilogue);
-    FINO_CHECK(fino_aligned16(aq) && fino_aligned16(wq) && fino_aligned16(a_scales) && fino_aligned16(w_scales) &&
-                   ((uintptr_t)cq & 7) == 0,
-               FINO_ERR_ARG, "fino_gemm_mxfp8_q: alignment");
+    FINO_CHECK(((uintptr_t)cq & 7) == 0, FINO_ERR_ARG, "fino_gemm_mxfp8_q: alignment");
     FINO_CHECK(m * k < (1ll << 31) && n * k < (1ll << 31), FINO_ERR_UNSUPPORTED, "fino_gemm_mxfp8_q: operand > 2 GiB");
     if (m == 0) return FINO_OK;
-    Fp8Params fp = {};
-    mxfp8_fill(fp, aq, a_scales, wq, w_scales, bias, m, n, k);
     fp.g.cq = (uint8_t*)cq; fp.g.cs = (uint8_t*)c_scales; fp.g.cs_rows_pad = fp.m_pad;
     hipStream_t st = (hipStream_t)stream;
     if (bias_dtype == FINO_BF16)
@@ -306,31 +279,12 @@ extern "C" int fino_gemm_mxfp8(const void* aq, const void* a_scales, const void*
                                const void* bias, void* c, int64_t m, int64_t n, int64_t k, int64_t ldc, int epilogue,
                                const void* r, int64_t ldr, const float* gate, int64_t mod_stride, const int32_t* sel,
                                int out_dtype, void* stream) {
-    FINO_CHECK(out_dtype == FINO_BF16 || out_dtype == FINO_F16, FINO_ERR_ARG, "fino_gemm_mxfp8: out dtype %d", out_dtype);
-    FINO_CHECK(aq && a_scales && wq && w_scales && c, FINO_ERR_ARG, "fino_gemm_mxfp8: null pointer");
-    FINO_CHECK(m >= 0 && n > 0 && k > 0 && k % 128 == 0 && n % 8 == 0, FINO_ERR_ARG,
-               "fino_gemm_mxfp8: K=%lld must be a multiple of 128, N=%lld of 8", (long long)k, (long long)n);
-    FINO_CHECK(ldc % 8 == 0 && ldc >= n && fino_aligned16(aq) && fino_aligned16(wq) && fino_aligned16(c) &&
-                   fino_aligned16(a_scales) && fino_aligned16(w_scales),
-               FINO_ERR_ARG, "fino_gemm_mxfp8: alignment / leading dimension");
-    FINO_CHECK(epilogue >= FINO_EPI_NONE && epilogue <= FINO_EPI_GATED_RESIDUAL_STAGED, FINO_ERR_ARG,
-               "fino_gemm_mxfp8: epilogue %d", epilogue);
-    if (epilogue >= FINO_EPI_RESIDUAL)
-        FINO_CHECK(r && ldr % 8 == 0 && ldr >= n && fino_aligned16(r), FINO_ERR_ARG, "fino_gemm_mxfp8: residual operand");
-    if (epilogue == FINO_EPI_GATED_RESIDUAL || epilogue == FINO_EPI_GATED_RESIDUAL_STAGED)
-        FINO_CHECK(gate && fino_aligned16(gate) && mod_stride % 4 == 0, FINO_ERR_ARG, "fino_gemm_mxfp8: gate operand");
+    MxGemmParams fp;
+    if (int rc = mx_gemm_params(fp, "fino_gemm_mxfp8", false, aq, a_scales, wq, w_scales, bias, c, m, n, k, ldc, epilogue, r,
+                                ldr, gate, mod_stride, sel, out_dtype))
+        return rc;
     FINO_CHECK(m * k < (1ll << 31) && n * k < (1ll << 31), FINO_ERR_UNSUPPORTED, "fino_gemm_mxfp8: operand > 2 GiB");
     if (m == 0) return FINO_OK;
-    Fp8Params fp = {};
-    GemmParams& p = fp.g;
-    p.a = (const uint16_t*)aq; p.w = (const uint16_t*)wq; p.bias = (const uint16_t*)bias; p.c = (uint16_t*)c;
-    p.r = (const uint16_t*)r; p.gate = gate; p.sel = sel;
-    p.m = m; p.n = n; p.k = k; p.lda = k; p.ldw = k; p.ldc = ldc; p.ldr = ldr; p.mod_stride = mod_stride;
-    p.tiles_m = (int)((m + BM - 1) / BM);
-    p.tiles_n = (int)((n + BN - 1) / BN);
-    p.group_m = fino_tune_get(FINO_TUNE_GEMM_GROUP_M);
-    fp.sa = (const uint8_t*)a_scales; fp.sw = (const uint8_t*)w_scales;
-    fp.m_pad = (m + 255) / 256 * 256; fp.n_pad = (n + 255) / 256 * 256;
     hipStream_t st = (hipStream_t)stream;
     return out_dtype == FINO_BF16 ? launch_mxfp8_e<BF16>(fp, epilogue, st) : launch_mxfp8_e<F16>(fp, epilogue, st);
 }

@@ -56,11 +56,12 @@ def _timed(name):
 
 def _timed_gemm(epilogue, flops, nbytes=0.0):
     """a GEMM launch under KernelTimer: counted under "gemm_epi<epilogue>" (bench.py's roofline.secondary rows: one per epilogue
-    class of the block GEMMs) when that name is asked for, else under "gemm".  Returns a closure to call after the launch."""
+    class of the block GEMMs) when that name is asked for, else under "gemm"; `epilogue` None (the MX GEMMs, the two-output
+    split, the blocked-A GEMM): always under "gemm".  Returns a closure to call after the launch."""
     kt = KernelTimer.active
     if kt is None:
         return None
-    name = f"gemm_epi{int(epilogue)}"
+    name = "gemm" if epilogue is None else f"gemm_epi{int(epilogue)}"
     if name not in kt.names:
         name = "gemm"
         if name not in kt.names:
@@ -110,6 +111,21 @@ def _rows2d(t):
         else:
             raise ValueError("need a 2-D row-strided view")
     return t2, t2.shape[0], t2.shape[1], t2.stride(0)
+
+
+def _epi_operands(residual, gate):
+    """(residual as 2-D rows or None, its leading dimension, the gate's row stride) as the GEMM entry points take them"""
+    r2, ldr = (None, 0)
+    if residual is not None:
+        r2, _, _, ldr = _rows2d(residual)
+    return r2, ldr, gate.stride(0) if (gate is not None and gate.dim() == 2) else 0
+
+
+def _mx_pair(shape, scale_bytes, device, out):
+    """the (q, scales) pair an MX producer writes: `out`, or fresh element bytes + zeroed scale bytes"""
+    if out is not None:
+        return out
+    return (torch.empty(shape, dtype=torch.uint8, device=device), torch.zeros(scale_bytes, dtype=torch.uint8, device=device))
 
 
 def adaln_modulate(x, shift, scale, sel=None, eps=1e-6, out=None):
@@ -451,18 +467,14 @@ def gemm(a, w, bias=None, epilogue=EPI_NONE, residual=None, gate=None, sel=None,
     if out2 is not None:
         assert 0 < split < n and residual is None
         c2, _, _, ldc2 = _rows2d(out2)
-        ev = _timed("gemm")
+        done = _timed_gemm(None, 2.0 * m * n * k)
         _lib.check(_lib.lib().fino_gemm_split_n(_p(a2), _p(w), _p(bias), _p(o2), m, n, k, lda, w.stride(0), ldc, epilogue,
                                                0, 0, 0, 0, 0, _dt(a), _p(c2), ldc2, split, tile_m, _stream()),
                    "fino_gemm_split_n")
-        if ev is not None:
-            ev.record()
-            KernelTimer.active.flops["gemm"] = KernelTimer.active.flops.get("gemm", 0.0) + 2.0 * m * n * k
+        if done is not None:
+            done()
         return out, out2
-    r2, ldr = (None, 0)
-    if residual is not None:
-        r2, _, _, ldr = _rows2d(residual)
-    ms = gate.stride(0) if (gate is not None and gate.dim() == 2) else 0
+    r2, ldr, ms = _epi_operands(residual, gate)
     if bias is not None:
         assert bias.dtype == a.dtype and bias.is_contiguous()
     # algorithmic bytes: A [M, K] and W [N, K] read, C [M, N] written (+ the residual read), 2 bytes per element
@@ -493,14 +505,13 @@ def gemm_blocked_a(a_blocks, rows, w, bias, residual, gate, sel, out, tile_m=0):
     r2, _, _, ldr = _rows2d(residual)
     o2, _, _, ldc = _rows2d(out)
     ms = gate.stride(0) if gate.dim() == 2 else 0
-    ev = _timed("gemm")
+    done = _timed_gemm(None, 2.0 * rows * n * k)
     _lib.check(_lib.lib().fino_gemm_blocked_a(_p(a_blocks), _p(w), _p(bias), _p(o2), rows, n, k, bk, a_blocks.stride(1),
                                               groups, a_blocks.stride(0), a_blocks.stride(2), w.stride(0), ldc, _p(r2),
                                               ldr, _p(gate), ms, _p(sel), _dt(a_blocks), tile_m, _stream()),
                "fino_gemm_blocked_a")
-    if ev is not None:
-        ev.record()
-        KernelTimer.active.flops["gemm"] = KernelTimer.active.flops.get("gemm", 0.0) + 2.0 * rows * n * k
+    if done is not None:
+        done()
     return out
 
 
@@ -511,11 +522,7 @@ def quantize_mxfp8(x, out=None):
     nbytes = _lib.lib().fino_mxfp8_scale_bytes(rows, cols)
     if nbytes <= 0:
         raise ValueError(f"quantize_mxfp8: cols={cols} must be a positive multiple of 128")
-    if out is None:
-        q = torch.empty((rows, cols), dtype=torch.uint8, device=x.device)
-        s = torch.zeros(nbytes, dtype=torch.uint8, device=x.device)
-    else:
-        q, s = out
+    q, s = _mx_pair((rows, cols), nbytes, x.device, out)
     _lib.check(_lib.lib().fino_quantize_mxfp8(_p(x2), _p(q), _p(s), rows, cols, ldx, _dt(x), _stream()),
                "fino_quantize_mxfp8")
     return q, s
@@ -528,17 +535,27 @@ def ln_mxfp8(mode, x, weight=None, bias=None, shift=None, scale=None, sel=None, 
     nbytes = _lib.lib().fino_mxfp8_scale_bytes(rows, dim)
     if nbytes <= 0:
         raise ValueError(f"ln_mxfp8: dim={dim} must be a positive multiple of 128")
-    if out is None:
-        q = torch.empty((rows, dim), dtype=torch.uint8, device=x.device)
-        s = torch.zeros(nbytes, dtype=torch.uint8, device=x.device)
-    else:
-        q, s = out
+    q, s = _mx_pair((rows, dim), nbytes, x.device, out)
     for t in (weight, bias, shift, scale):
         assert t is None or t.dtype == torch.float32
     ms = shift.stride(0) if (shift is not None and shift.dim() == 2) else 0
     _lib.check(_lib.lib().fino_ln_mxfp8(mode, _p(x2), _p(q), _p(s), rows, dim, ldx, _p(weight), _p(bias), _p(shift),
                                        _p(scale), ms, _p(sel), eps, _dt(x), _stream()), "fino_ln_mxfp8")
     return q, s
+
+
+def _mx_gemm(entry, aq, a_scales, wq, w_scales, bias, epilogue, residual, gate, sel, out, out_dtype, m, n, k):
+    """what gemm_mxfp8 and gemm_mxfp6 share once the operands are checked: `entry` names the library's entry point"""
+    if out is None:
+        out = torch.empty((m, n), dtype=out_dtype, device=aq.device)
+    o2, _, _, ldc = _rows2d(out)
+    r2, ldr, ms = _epi_operands(residual, gate)
+    done = _timed_gemm(None, 2.0 * m * n * k)
+    _lib.check(getattr(_lib.lib(), entry)(_p(aq), _p(a_scales), _p(wq), _p(w_scales), _p(bias), _p(o2), m, n, k, ldc,
+                                          epilogue, _p(r2), ldr, _p(gate), ms, _p(sel), _dt(out), _stream()), entry)
+    if done is not None:
+        done()
+    return out
 
 
 def gemm_mxfp8(aq, a_scales, wq, w_scales, bias=None, epilogue=EPI_NONE, residual=None, gate=None, sel=None, out=None,
@@ -548,21 +565,7 @@ def gemm_mxfp8(aq, a_scales, wq, w_scales, bias=None, epilogue=EPI_NONE, residua
     n = wq.shape[0]
     assert wq.shape[1] == k and aq.dtype == torch.uint8 and wq.dtype == torch.uint8 and aq.is_contiguous() \
         and wq.is_contiguous()
-    if out is None:
-        out = torch.empty((m, n), dtype=out_dtype, device=aq.device)
-    o2, _, _, ldc = _rows2d(out)
-    r2, ldr = (None, 0)
-    if residual is not None:
-        r2, _, _, ldr = _rows2d(residual)
-    ms = gate.stride(0) if (gate is not None and gate.dim() == 2) else 0
-    ev = _timed("gemm")
-    _lib.check(_lib.lib().fino_gemm_mxfp8(_p(aq), _p(a_scales), _p(wq), _p(w_scales), _p(bias), _p(o2), m, n, k, ldc,
-                                         epilogue, _p(r2), ldr, _p(gate), ms, _p(sel), _dt(out), _stream()),
-               "fino_gemm_mxfp8")
-    if ev is not None:
-        ev.record()
-        KernelTimer.active.flops["gemm"] = KernelTimer.active.flops.get("gemm", 0.0) + 2.0 * m * n * k
-    return out
+    return _mx_gemm("fino_gemm_mxfp8", aq, a_scales, wq, w_scales, bias, epilogue, residual, gate, sel, out, out_dtype, m, n, k)
 
 
 def gemm_mxfp8_q(aq, a_scales, wq, w_scales, bias, epilogue=EPI_NONE, out=None):
@@ -570,17 +573,12 @@ def gemm_mxfp8_q(aq, a_scales, wq, w_scales, bias, epilogue=EPI_NONE, out=None):
     m, k = aq.shape
     n = wq.shape[0]
     assert bias is not None and wq.shape[1] == k
-    if out is None:
-        q = torch.empty((m, n), dtype=torch.uint8, device=aq.device)
-        s = torch.zeros(_lib.lib().fino_mxfp8_scale_bytes(m, n), dtype=torch.uint8, device=aq.device)
-    else:
-        q, s = out
-    ev = _timed("gemm")
+    q, s = _mx_pair((m, n), _lib.lib().fino_mxfp8_scale_bytes(m, n), aq.device, out)
+    done = _timed_gemm(None, 2.0 * m * n * k)
     _lib.check(_lib.lib().fino_gemm_mxfp8_q(_p(aq), _p(a_scales), _p(wq), _p(w_scales), _p(bias), _p(q), _p(s), m, n, k,
                                            epilogue, _dt(bias), _stream()), "fino_gemm_mxfp8_q")
-    if ev is not None:
-        ev.record()
-        KernelTimer.active.flops["gemm"] = KernelTimer.active.flops.get("gemm", 0.0) + 2.0 * m * n * k
+    if done is not None:
+        done()
     return q, s
 
 
@@ -591,11 +589,7 @@ def quantize_mxfp6(x, out=None):
     nbytes = _lib.lib().fino_mxfp6_scale_bytes(rows, cols)
     if nbytes <= 0:
         raise ValueError(f"quantize_mxfp6: cols={cols} must be a positive multiple of 128")
-    if out is None:
-        q = torch.empty(_lib.lib().fino_mxfp6_bytes(rows, cols), dtype=torch.uint8, device=x.device)
-        s = torch.zeros(nbytes, dtype=torch.uint8, device=x.device)
-    else:
-        q, s = out
+    q, s = _mx_pair(_lib.lib().fino_mxfp6_bytes(rows, cols), nbytes, x.device, out)
     _lib.check(_lib.lib().fino_quantize_mxfp6(_p(x2), _p(q), _p(s), rows, cols, ldx, _dt(x), _stream()),
                "fino_quantize_mxfp6")
     q.mx_shape = (rows, cols)
@@ -619,21 +613,7 @@ def gemm_mxfp6(aq, a_scales, wq, w_scales, bias=None, epilogue=EPI_NONE, residua
     lib = _lib.lib()
     if aq.numel() != lib.fino_mxfp6_bytes(m, k) or wq.numel() != lib.fino_mxfp6_bytes(n, k):
         raise ValueError(f"gemm_mxfp6: operand sizes {aq.numel()} / {wq.numel()} do not match M={m} N={n} K={k}")
-    if out is None:
-        out = torch.empty((m, n), dtype=out_dtype, device=aq.device)
-    o2, _, _, ldc = _rows2d(out)
-    r2, ldr = (None, 0)
-    if residual is not None:
-        r2, _, _, ldr = _rows2d(residual)
-    ms = gate.stride(0) if (gate is not None and gate.dim() == 2) else 0
-    ev = _timed("gemm")
-    _lib.check(lib.fino_gemm_mxfp6(_p(aq), _p(a_scales), _p(wq), _p(w_scales), _p(bias), _p(o2), m, n, k, ldc,
-                                   epilogue, _p(r2), ldr, _p(gate), ms, _p(sel), _dt(out), _stream()),
-               "fino_gemm_mxfp6")
-    if ev is not None:
-        ev.record()
-        KernelTimer.active.flops["gemm"] = KernelTimer.active.flops.get("gemm", 0.0) + 2.0 * m * n * k
-    return out
+    return _mx_gemm("fino_gemm_mxfp6", aq, a_scales, wq, w_scales, bias, epilogue, residual, gate, sel, out, out_dtype, m, n, k)
 
 
 def skinny_linear(x, w, b=None, silu_input=False):

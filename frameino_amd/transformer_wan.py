@@ -28,6 +28,7 @@ from . import ops
 from .attention_processor import Attention, MI355WanAttnProcessor
 from .loading import FromPretrainedMixin
 from .lora import LoraModelMixin
+from .mx_linears import MXLinearsMixin
 from .step_cache import FirstBlockCacheMixin
 
 
@@ -114,7 +115,9 @@ class WanTransformerBlock(nn.Module):
         self.scale_shift_table = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
 
 
-class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, FirstBlockCacheMixin):
+class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, FirstBlockCacheMixin, MXLinearsMixin):
+    """MX linears (enable_mxfp8_linears / enable_mxfp6_linears): the six large linears of every block -- QKV, attention out,
+    cross-attention q / out, FFN up / down."""
     _loader_name = "load_wan_transformer"
     _keep_in_fp32_modules = ["time_embedder", "scale_shift_table", "norm1", "norm2", "norm3"]   # reference :393
     _lora_wan_layout = True   # LoRA files in the original Wan-repo / kohya key layout map onto these names (frameino_amd/lora.py)
@@ -147,9 +150,6 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._ctx_name = None
         self.ops = ops            # kernel front end (tests of the sharding logic inject a CPU stand-in)
         self.parallel = None      # frameino_amd.parallel.TokenShard or None
-        self._fp8 = {}            # (layer, linear) -> (e4m3 weight bytes, MX scales); see enable_mxfp8_linears
-        self._fp8_pending = False # MXFP8 was on when the parameters last moved / changed: re-quantise at the next forward
-        self._mx_fmt = 8          # element format of the `_fp8` entries: 8 = e4m3 (enable_mxfp8_linears), 6 = e2m3 (enable_mxfp6_linears)
         self.dedup_shared_prefix = True   # A/B knob: CFG-batched call computes the branch-invariant prefix once
         # True: q of the self-attention leaves its norm + RoPE kernel already multiplied by head_dim**-0.5 * log2(e) (fp32,
         # one rounding) and the attention kernels take q.k as the exp2 argument (FINO_ATTN_SCALE_FOLDED), which lets the
@@ -210,15 +210,12 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
 
     # ------------------------------------------------------------------ derived state
     def reset_caches(self):
-        """Drop everything derived from the parameters or the prompt: packed/fused weight copies, MXFP8 weights, text
-        K/V, RoPE tables, workspaces, first-block-cache residuals.  Called whenever the parameters may have changed or moved."""
-        had_fp8 = bool(self._fp8) or self._fp8_pending
+        """Drop everything derived from the parameters or the prompt: packed/fused weight copies, MX weights, text
+        K/V, RoPE tables, workspaces, first-block-cache residuals.  Called whenever the parameters may have changed or moved.
+        Returns whether MX linears were on (they are re-quantised by the next forward)."""
+        had_fp8 = self._mx_invalidate()
         self._reset_stateful_cache()
         self._packed = None
-        self._fp8 = {}
-        # the MXFP8 weights are re-quantised lazily, by the next forward, from wherever the parameters are then: a
-        # `.to("cpu")` / `.float()` in between must not run the GPU quantiser on host tensors or leave the module half moved
-        self._fp8_pending = had_fp8
         self._text_cache.clear()
         self._rope_cache.clear()
         self._ws.clear()
@@ -259,47 +256,12 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._packed = pk
         return pk
 
-    # ------------------------------------------------------------------ MXFP8 linears (optional; BASELINE config 5)
-    def enable_mxfp8_linears(self, enabled=True):
-        """Run the six large linears of every block (QKV, attention out, cross-attention q / out, FFN up / down) on the
-        MXFP8 path (`fino_quantize_mxfp8` + `fino_gemm_mxfp8`: OCP e4m3 with one e8m0 scale per 32 K-elements, fp32
-        accumulate): weights are quantised once here, activations per call.  Attention, norms, modulation, embeddings
-        and the output head stay in the model dtype.  There is no reference counterpart: the result is
-        compared with this model's own bf16 forward (tests/test_mxfp8_gpu.py)."""
-        return self._enable_mx_linears(8, enabled)
-
-    def enable_mxfp6_linears(self, enabled=True):
-        """The same six linears on the MXFP6 path (`fino_quantize_mxfp6` + `fino_gemm_mxfp6`: OCP e2m3 -- e4m3's three
-        mantissa bits, the block scale supplies the range -- with one e8m0 scale per 32 K-elements, fp32 accumulate, at the
-        FP4 matrix rate).  Weights are quantised once here, activations per call, from the model dtype (no fused producers:
-        LayerNorm and the FFN's GELU write the model dtype and `fino_quantize_mxfp6` follows).  One reduced precision at a
-        time: raises ValueError while `enable_mxfp8_linears()` is on.  Independent of `enable_fp8_attention()` and
-        `enable_cache()`; `enable_mxfp6_linears(False)` returns the model to its model-dtype output bit for bit."""
-        return self._enable_mx_linears(6, enabled)
-
-    def _enable_mx_linears(self, fmt, enabled):
-        on = bool(self._fp8) or self._fp8_pending
-        if on and self._mx_fmt != fmt:
-            if not enabled:
-                return self                                     # the other precision's switch: nothing of this one to drop
-            raise ValueError(f"enable_mxfp{fmt}_linears: enable_mxfp{self._mx_fmt}_linears() is on -- one reduced precision at a "
-                             f"time; call enable_mxfp{self._mx_fmt}_linears(False) first")
-        self._fp8 = {}
-        self._fp8_pending = False
-        if not enabled:
-            return self
-        self._mx_fmt = fmt
-        pk = self._packed or self._pack()
-        quantize = self._mx_quantize()
+    def _mx_linear_weights(self, pk):
         for li, (blk, e) in enumerate(zip(self.blocks, pk.layers)):
             for key, w in (("qkv", e.wqkv), ("out", blk.attn1.to_out[0].weight), ("q2", blk.attn2.to_q.weight),
                            ("out2", blk.attn2.to_out[0].weight), ("ff1", blk.ffn.net[0].proj.weight),
                            ("ff2", blk.ffn.net[2].weight)):
-                self._fp8[(li, key)] = quantize(w.detach().contiguous())
-        return self
-
-    def _mx_quantize(self):
-        return self.ops.quantize_mxfp6 if self._mx_fmt == 6 else self.ops.quantize_mxfp8
+                yield li, key, w
 
     def enable_fp8_attention(self, enabled=True, p_mode=None):
         """The 3-D self-attention (transformer_wan.py:108) with fp8 (e4m3) matrix operands -- q, k, v and P on the
@@ -310,34 +272,6 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self.fp8_attention = bool(enabled)
         self.fp8_p_mode = p_mode
         return self
-
-    def _ln_q(self, li, key, mode, x, **ln):
-        """the LayerNorm in front of linear (li, key) emitted directly as that linear's MXFP8 activations (fino_ln_mxfp8: one
-        pass instead of norm -> bf16 -> quantise), or None when the linear is not on the MXFP8 path"""
-        o = self.ops
-        if not self._fp8 or (li, key) not in self._fp8 or not hasattr(o, "ln_mxfp8") or _NO_LN_MXFP8:
-            return None
-        if self._mx_fmt == 6:
-            return None                                         # MXFP6 takes the two-pass route: norm -> model dtype -> quantise
-        return o.ln_mxfp8(mode, x, **ln)
-
-    def _lin(self, li, key, x, w, b, epi=0, xq=None, **kw):
-        """one of a block's large linears: MXFP8 when enabled (and K is a multiple of 128), else the model-dtype GEMM.
-        xq: the activations already quantised (_ln_q)"""
-        wq = self._fp8.get((li, key)) if self._fp8 else None
-        o = self.ops
-        if wq is None and self._fp8 and key in ("kv", "q"):
-            # token shards project K|V and Q separately: quantise those row blocks of the fused weight on first use
-            # (MX scales are per output row, so this equals slicing the quantised fused weight)
-            wq = self._fp8[(li, key)] = self._mx_quantize()(w.detach().contiguous())
-        if wq is None:
-            return o.gemm(x, w, b, epi, **kw)
-        kw.pop("tile_m", None)                                  # (the MX GEMMs have one tile height)
-        if self._mx_fmt == 6:
-            xq, xs = o.quantize_mxfp6(x)
-            return o.gemm_mxfp6(xq, xs, wq[0], wq[1], b, epi, **kw)
-        xq, xs = xq if xq is not None else o.quantize_mxfp8(x)
-        return o.gemm_mxfp8(xq, xs, wq[0], wq[1], b, epi, **kw)
 
     def _workspace(self, L, dtype, device):
         # one workspace per (shape, cache_context name): the two CFG branches may run concurrently on two streams
@@ -456,7 +390,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         and projected (row-wise operations: the kept rows come out bit-identical) and `.tail` carries (key counts, multiplicities)."""
         hit = self._text_cache.get(self._ctx_name)
         if hit is not None and hit[0] is encoder_hidden_states and hit[1] == encoder_hidden_states._version \
-                and hit[3] == (bool(may_fold), int(lq) if may_fold else 0, bool(self._fp8) or self._fp8_pending, self.reassociate_text_out,
+                and hit[3] == (bool(may_fold), int(lq) if may_fold else 0, self._mx_on, self.reassociate_text_out,
                                self.dedup_text_padding):
             return hit[2]
         ce = self.condition_embedder
@@ -477,7 +411,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         # sample and 30 cached [D, heads x kp] matrices per sample (0.32 GB for a 64-token prompt, per cache context).  Longer prompts take the
         # folded attention + the ordinary out-projection.
         worth = tail is not None and self.config.num_attention_heads * (-(-max(tail[1]) // 8) * 8) <= 0.6 * d
-        if worth and self.reassociate_text_out and not self._fp8 and not self._fp8_pending \
+        if worth and self.reassociate_text_out and not self._mx_on \
                 and hasattr(self.ops, "attention_probs") \
                 and self.ops.attention_probs_supported(1, self.config.num_attention_heads, lq, kept.shape[1],
                                                        d // self.config.num_attention_heads):
@@ -485,7 +419,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         # the entry holds the prompt tensor itself: identity (`is`) + in-place version, never its address -- a freed
         # prompt's address is handed to the next same-shape prompt by the caching allocator
         self._text_cache[self._ctx_name] = (encoder_hidden_states, encoder_hidden_states._version, val,
-                                            (bool(may_fold), int(lq) if may_fold else 0, bool(self._fp8) or self._fp8_pending,
+                                            (bool(may_fold), int(lq) if may_fold else 0, self._mx_on,
                                              self.reassociate_text_out, self.dedup_text_padding))
         return val
 
@@ -528,8 +462,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         # LoRA scale (:463-476): adapters are merged into the weights, a changed scale re-merges them here (frameino_amd/lora.py)
         self._lora_apply(attention_kwargs.pop("scale", None) if attention_kwargs is not None else None)
         b = hidden_states.shape[0]
-        if self._fp8_pending:
-            self._enable_mx_linears(self._mx_fmt, True)
+        self._mx_requantise_if_pending()
         pk = self._packed or self._pack()
         default_procs = self._default_processors()
         o = self.ops
@@ -851,20 +784,14 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                               **(attention_kwargs or {}))
                 o.gated_residual(x, a.reshape(nr, d), out=x)
             # 3. feed-forward (:344-348)
-            w1q, w2q = self._fp8.get((li, "ff1")), self._fp8.get((li, "ff2"))
             xq3 = (self._ln_q(li, "ff1", 0, x, shift=m[:, 3], scale=m[:, 4], sel=sel, eps=cfg.eps)
-                   if (w1q is not None and w2q is not None) else None)
+                   if (li, "ff2") in self._fp8 else None)
             if xq3 is None:
                 for r0, r1 in segs:
                     o.adaln_modulate(x[r0:r1], m[:, 3], m[:, 4], None if sel is None else sel[r0:r1], cfg.eps, out=nrm[r0:r1])
-            if w1q is not None and w2q is not None and self._mx_fmt == 8:
-                # MXFP8: the adaLN emits the FFN input already quantised, and the GELU epilogue the hidden activations (no
-                # bf16 round trips)
-                hq = o.gemm_mxfp8_q(*(xq3 if xq3 is not None else o.quantize_mxfp8(nrm)), w1q[0], w1q[1],
-                                    blk.ffn.net[0].proj.bias, o.EPI_GELU_TANH)
-                o.gemm_mxfp8(hq[0], hq[1], w2q[0], w2q[1], blk.ffn.net[2].bias, o.EPI_GATED_RESIDUAL, residual=x,
-                             gate=m[:, 5], sel=sel, out=x)
-            else:
+            # MXFP8: the adaLN emits the FFN input already quantised, and the GELU epilogue the hidden activations
+            if self._ffn_mxfp8(li, nrm, xq3, blk.ffn.net[0].proj.bias, blk.ffn.net[2].bias, o.EPI_GATED_RESIDUAL, residual=x,
+                               gate=m[:, 5], sel=sel, out=x) is None:
                 for r0, r1 in segs:
                     self._lin(li, "ff1", nrm[r0:r1], blk.ffn.net[0].proj.weight, blk.ffn.net[0].proj.bias, o.EPI_GELU_TANH,
                               out=ff[r0:r1], **tk)
@@ -905,9 +832,6 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         if not return_dict:
             return (out,)
         return SimpleNamespace(sample=out)
-
-
-_NO_LN_MXFP8 = bool(os.environ.get("FINO_NO_LN_MXFP8"))       # A/B knob: LayerNorm -> bf16 -> quantise as two passes
 
 
 class _CompactRope(tuple):
