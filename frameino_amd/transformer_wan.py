@@ -233,8 +233,9 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         return out
 
     def _default_processors(self):
-        # exactly our processor (not a subclass): the fused path in forward_steps IS that processor's body; anything
-        # else the user installed (set_processor, at any time) is called through the plugin protocol instead.
+        # exactly our processor (not a subclass): the fused strategies behind `_self_attention` and the default arm of
+        # `_cross_attention` ARE that processor's body; anything else the user installed (set_processor, at any time) is called
+        # through the plugin protocol instead (`_sa_processors`, the other arm of `_cross_attention`).
         return all(type(b.attn1.processor) is MI355WanAttnProcessor and type(b.attn2.processor) is MI355WanAttnProcessor
                    for b in self.blocks)
 
@@ -320,16 +321,13 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         tproj = torch.cat([o[1] for o in outs]).unflatten(1, (6, -1))
         return temb, tproj
 
-    def _qk_norm_rope(self, blk, qkv, d, cos, sin, dh, qfold):
-        """norm_q / norm_k ("rms_norm_across_heads", :64-67) + RoPE (:73-90) on the q and k columns of the fused projection,
-        in place: one launch where the ops offer it (the arithmetic of the two rmsnorm_rope_ calls, bit for bit)"""
-        o, a = self.ops, blk.attn1
-        if hasattr(o, "qkv_rmsnorm_rope_"):
-            o.qkv_rmsnorm_rope_(qkv, d, a.norm_q.weight, a.norm_q.eps, a.norm_k.weight, a.norm_k.eps, cos, sin, dh,
-                                q_out_scale=qfold.get("out_scale", 1.0))
-        else:
-            o.rmsnorm_rope_(qkv[:, :d], a.norm_q.weight, a.norm_q.eps, cos, sin, dh, **qfold)
-            o.rmsnorm_rope_(qkv[:, d:2 * d], a.norm_k.weight, a.norm_k.eps, cos, sin, dh)
+    def _qk_norm_rope(self, blk, qkv, d, cos, sin, dh, qfold, **scatter):
+        """norm_q / norm_k ("rms_norm_across_heads", :64-67) + RoPE (:73-90) on the q and k columns of the fused projection in
+        ONE launch (the arithmetic of two rmsnorm_rope_ calls, bit for bit): in place, or -- `scatter`: out / head_off / head_ld
+        of the heads exchange -- q, k and v written by head into the send buffers"""
+        a = blk.attn1
+        self.ops.qkv_rmsnorm_rope_(qkv, d, a.norm_q.weight, a.norm_q.eps, a.norm_k.weight, a.norm_k.eps, cos, sin, dh,
+                                   q_out_scale=qfold.get("out_scale", 1.0), **scatter)
 
     def _text_tail(self, ehs, lq):
         """(rows to keep, per-sample key counts, per-sample multiplicities) when every sample of the prompt batch ends in a run of
@@ -389,9 +387,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         zero-padded tail of the prompt may be folded into one key (`dedup_text_padding`): then only the kept rows are embedded
         and projected (row-wise operations: the kept rows come out bit-identical) and `.tail` carries (key counts, multiplicities)."""
         hit = self._text_cache.get(self._ctx_name)
-        if hit is not None and hit[0] is encoder_hidden_states and hit[1] == encoder_hidden_states._version \
-                and hit[3] == (bool(may_fold), int(lq) if may_fold else 0, self._mx_on, self.reassociate_text_out,
-                               self.dedup_text_padding):
+        key = (bool(may_fold), int(lq) if may_fold else 0, self._mx_on, self.reassociate_text_out, self.dedup_text_padding)
+        if hit is not None and hit[0] is encoder_hidden_states and hit[1] == encoder_hidden_states._version and hit[3] == key:
             return hit[2]
         ce = self.condition_embedder
         d = self.inner_dim
@@ -418,9 +415,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             self._text_out_weights(val, kept.shape[0], lq, pk)
         # the entry holds the prompt tensor itself: identity (`is`) + in-place version, never its address -- a freed
         # prompt's address is handed to the next same-shape prompt by the caching allocator
-        self._text_cache[self._ctx_name] = (encoder_hidden_states, encoder_hidden_states._version, val,
-                                            (bool(may_fold), int(lq) if may_fold else 0, self._mx_on,
-                                             self.reassociate_text_out, self.dedup_text_padding))
+        self._text_cache[self._ctx_name] = (encoder_hidden_states, encoder_hidden_states._version, val, key)
         return val
 
     # ------------------------------------------------------------------ forward
@@ -453,21 +448,81 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         """The forward as a generator that yields after the embedding stage and after every block, so that a caller
         can interleave two independent forwards (the CFG branches) kernel-stream by kernel-stream
         (frameino_amd/parallel.py: one branch's K|V all-gather then flies under the other branch's compute).  Every
-        piece of per-call state (workspace, text K/V, shard) is bound at the first `next()`; `shard` overrides
-        `self.parallel` for this call.  Returns (StopIteration.value) what `forward` returns."""
+        piece of per-call state (workspace, text K/V, shard) is bound at the first `next()` (`_bind` -> `_Call`); `shard`
+        overrides `self.parallel` for this call.  Returns (StopIteration.value) what `forward` returns.
+        The stages are plain methods on that state; which self-attention strategy a call takes is `_self_attention`'s dispatch."""
         if encoder_hidden_states_image is not None:
             raise NotImplementedError("encoder_hidden_states_image: Wan2.1 branch, outside the TI2V-5B path")
         if attention_kwargs is not None:
             attention_kwargs = dict(attention_kwargs)
         # LoRA scale (:463-476): adapters are merged into the weights, a changed scale re-merges them here (frameino_amd/lora.py)
         self._lora_apply(attention_kwargs.pop("scale", None) if attention_kwargs is not None else None)
-        b = hidden_states.shape[0]
         self._mx_requantise_if_pending()
+        c = self._bind(hidden_states, timestep, encoder_hidden_states, attention_kwargs, timestep_rows, shard, live_rows,
+                       _cache_contexts)
+        self._embed(c, hidden_states)
+        yield
+
+        last = len(self.blocks) - 1
+        for li, (blk, e) in enumerate(zip(self.blocks, c.pk.layers)):
+            m = c.mod[:, li]                                                      # [R, 6, D] view, row stride = layers*6*D
+            if c.live is not None and li == last:
+                c.rows, c.segs = c.live, c.live_segs                              # dead rows: keys and values only
+            if not self._self_attention(c, li, blk, e, m):                        # 1. self-attention (:334-336)
+                self._self_attention_out(c, li, blk, m)
+            self._cross_attention(c, li, blk)                                     # 2. cross-attention (:339-341)
+            self._ffn(c, li, blk, m)                                              # 3. feed-forward (:344-348)
+            if c.fbc is not None and li == 0:
+                computes = self._step_cache_probe(c.fbc, c.h0, c.x, c.h1c)        # one host read: the rule's decision
+            yield
+            if c.fbc is not None and not any(computes):
+                break                                                             # every segment skips blocks 1 .. N-1
+
+        if c.fbc is not None:
+            # tail residuals of the computed segments; T(tail + h1) for the skipped ones.  With `live_rows` the last block left
+            # the dead rows at block N-2's output, so a tail residual is meaningful on the live rows only -- the rows the caller
+            # reads; the head below runs on those rows alone whether or not the blocks ran.
+            self._step_cache_finish(c.fbc, computes, c.x, c.h1c)
+            if c.live is not None:
+                c.segs = c.live_segs
+        out = self._output_head(c)
+        if not return_dict:
+            return (out,)
+        return SimpleNamespace(sample=out)
+
+    # ------------------------------------------------------------------ forward: per-call state
+    def _timestep_selector(self, timestep, timestep_rows, b, n, lo, sharded, dev):
+        """The three timestep forms -> (t_rows [R], selector int32 [b * n] or None, same_rows) (F7), cut to the shard's rows and
+        repeated over the batch.  `same_rows`: every batch element sees the same modulation rows BY CONSTRUCTION (the selector of
+        one element repeated, or one scalar timestep) -- the precondition of the shared prefix."""
+        if timestep_rows is not None:
+            t_rows, sel = timestep_rows
+            if sel is not None and sharded:
+                sel = sel[lo:lo + n].contiguous()
+            if sel is not None and b > 1:
+                sel = sel.repeat(b)
+            return t_rows, sel, True
+        if timestep.ndim == 2:
+            t_rows, inv = torch.unique(timestep.reshape(-1), return_inverse=True)
+            sel = inv.to(torch.int32).contiguous()
+            if sharded:
+                return t_rows, sel[lo:lo + n].contiguous(), False
+            if timestep.shape[0] == 1 and b > 1:                                   # one row of per-token values: broadcast
+                return t_rows, sel.repeat(b), True
+            return t_rows, sel, False
+        t_rows = timestep.reshape(-1)
+        if b == 1 or t_rows.numel() == 1:
+            return t_rows, None, b > 1
+        return t_rows, torch.arange(b, device=dev, dtype=torch.int32).repeat_interleave(n), False
+
+    def _bind(self, hidden_states, timestep, encoder_hidden_states, attention_kwargs, timestep_rows, shard, live_rows,
+              cache_contexts):
+        """Everything the stages of one call share, as a `_Call`: geometry, this rank's token shard, workspace views, RoPE
+        tables, modulation tables + selector, text K/V and the switches that pick a path."""
+        o, cfg = self.ops, self.config
         pk = self._packed or self._pack()
         default_procs = self._default_processors()
-        o = self.ops
-        cfg = self.config
-        _, c, nf, hh, ww = hidden_states.shape
+        b, _, nf, hh, ww = hidden_states.shape
         pt, ph, pw = cfg.patch_size
         ppf, pph, ppw = nf // pt, hh // ph, ww // pw
         L = ppf * pph * ppw
@@ -478,98 +533,47 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         # ---- token shard of this rank (frameino_amd/parallel.py); single GPU: the whole sequence ----
         sh = shard if shard is not None else self.parallel
         sh = sh if (sh is not None and sh.active) else None
+        lo, n, lpad = 0, L, L
+        tk = {}         # the shard's tile height for its GEMM calls (a per-call argument of the C ABI; {} = the library's planner)
         if sh is not None:
             if b != 1:
                 raise NotImplementedError("token-sharded execution runs one sample per call")
             lo, n, lpad = sh.rows(L)              # first row, valid rows, padded shard length (equal on all ranks)
             cos1, sin1 = cos1[lo:lo + n].contiguous(), sin1[lo:lo + n].contiguous()
-        else:
-            lo, n, lpad = 0, L, L
-        if self.is_cache_enabled and sh is not None:
-            raise NotImplementedError("first-block caching runs on one GPU: a token-sharded forward cannot take the cache")
-        fbc = self._step_cache_segments(b, n, _cache_contexts)     # None: no cache (nothing extra allocated or launched)
-        # the shard's tile height for its GEMM calls (a per-call argument of the C ABI; {} = the library's planner)
-        tk = {}
-        if sh is not None and getattr(sh, "gemm_tile_m", 0):
-            tk = {"tile_m": sh.tile_m_for(n) if hasattr(sh, "tile_m_for") else sh.gemm_tile_m}
+            if self.is_cache_enabled:
+                raise NotImplementedError("first-block caching runs on one GPU: a token-sharded forward cannot take the cache")
+            if sh.gemm_tile_m:
+                tk = {"tile_m": sh.tile_m_for(n)}
+        fbc = self._step_cache_segments(b, n, cache_contexts)      # None: no cache (nothing extra allocated or launched)
         # Batch elements are extra ROWS of the token-major buffers ([B*n, D]): every GEMM / norm is one launch over
         # both CFG branches (twice the tiles per launch, weights read once); attention and RoPE index rows per batch.
         nr = b * n
         ws = self._workspace(b * lpad, dt, dev)
-        if b == 1:
-            cos, sin = cos1, sin1
-        else:
+        cos, sin = cos1, sin1
+        if b > 1:
             key = ("rope_b", ppf, pph, ppw, b, str(dev))
             if key not in self._rope_cache:
                 self._rope_cache[key] = (cos1.repeat(b, 1).contiguous(), sin1.repeat(b, 1).contiguous())
             cos, sin = self._rope_cache[key]
 
-        # ---- timestep rows + selector (F7) ----
-        # `same_rows`: every batch element sees the same modulation rows BY CONSTRUCTION (the selector of one element
-        # repeated, or one scalar timestep) -- the precondition of the shared prefix below
-        same_rows = False
-        if timestep_rows is not None:
-            t_rows, sel = timestep_rows
-            same_rows = True
-            if sel is not None and sh is not None:
-                sel = sel[lo:lo + n].contiguous()
-            if sel is not None and b > 1:
-                sel = sel.repeat(b)
-        elif timestep.ndim == 2:
-            t_rows, inv = torch.unique(timestep.reshape(-1), return_inverse=True)
-            sel = inv.to(torch.int32).contiguous()
-            if sh is not None:
-                sel = sel[lo:lo + n].contiguous()
-            elif timestep.shape[0] == 1 and b > 1:                                 # one row of per-token values: broadcast
-                sel = sel.repeat(b)
-                same_rows = True
-        else:
-            t_rows = timestep.reshape(-1)
-            sel = None if b == 1 else torch.arange(b, device=dev, dtype=torch.int32).repeat_interleave(n)
-            if t_rows.numel() == 1 and b > 1:
-                sel = None
-                same_rows = True
+        t_rows, sel, same_rows = self._timestep_selector(timestep, timestep_rows, b, n, lo, sh is not None, dev)
         temb, tproj = self._time_rows(t_rows.to(dev), encoder_hidden_states.dtype)       # [R,D], [R,6,D]
         # per-layer modulation tables: scale_shift_table + temb.float()  (:317-319)  -> [R, layers, 6, D] fp32
         mod = (pk.sst[None] + tproj.float()[:, None]).contiguous()
         head = (self.scale_shift_table.float() + temb.float()[:, None]).contiguous()     # [R, 2, D]  (:522/:527)
+        text = self._text_kv(encoder_hidden_states, pk, lq=n, may_fold=default_procs)    # (token shards too: n = the shard's rows)
 
-        text = self._text_kv(encoder_hidden_states, pk, lq=n, may_fold=default_procs)      # (token shards too: n = the shard's rows)
-        lt = text.lt
-
-        # ---- patch embedding (:486-487): gather + GEMM (the gather is 9 MB; every rank builds it, keeps its rows) ----
         # `shared`: the batch elements are the SAME latent (the pipeline's CFG-batched call passes x.expand(2, ...)) under
         # the same timestep rows: everything up to the first text cross-attention is identical for them, so the patch
         # embedding and layer 0's self-attention branch run once and their result is copied (exactly what each element
         # would have computed).  A per-sample timestep ([b] or [b, L] values) takes the general path.
         shared = (self.dedup_shared_prefix and b > 1 and sh is None and hidden_states.stride(0) == 0 and default_procs
                   and same_rows)
-        if b == 1 or shared:
-            a_rows = o.patchify(hidden_states[0], cfg.patch_size)[lo:lo + n]
-        else:
-            a_rows = torch.cat([o.patchify(hidden_states[i], cfg.patch_size) for i in range(b)])
-        x = ws.x[:nr]
-        o.gemm(a_rows, pk.w_patch, self.patch_embedding.bias, out=x[:n] if shared else x, **tk)
-        if fbc is not None:
-            # first-block cache: keep h0 (block 0 updates x in place) and a buffer for the probe's copy of h1
-            if getattr(ws, "fbc_h0", None) is None:
-                ws.fbc_h0, ws.fbc_h1 = torch.empty_like(ws.x), torch.empty_like(ws.x)
-            h0, h1c = ws.fbc_h0[:nr], ws.fbc_h1[:nr]
-            if shared:                       # (the embedding of the shared latent sits in the first n rows only)
-                for bi in range(b):
-                    h0[bi * n:(bi + 1) * n].copy_(x[:n])
-            else:
-                h0.copy_(x)
-        nrm, att, q2, ff = ws.n[:nr], ws.att[:nr], ws.q2[:nr], ws.ff[:nr]
-        fold = self.fold_softmax_scale and hasattr(o, "SCALE_FOLDED")
-        qfold = {"out_scale": dh ** -0.5 * o.LOG2E} if fold else {}
-        afold = {"scale": o.SCALE_FOLDED} if fold else {}
+        fold = self.fold_softmax_scale
         attend = o.attention
         if self.fp8_attention and sh is None and hasattr(o, "attention_fp8"):
             def attend(q_, k_, v_, heads_, **kw_):
                 return o.attention_fp8(q_, k_, v_, heads_, p_mode=getattr(self, "fp8_p_mode", None), **kw_)
-        yield
-
         # rows whose output the caller reads (`live_rows`): honoured in the last block on the single-GPU default-processor path
         live = None
         if (live_rows is not None and self.skip_dead_rows and default_procs and sh is None and len(self.blocks) > 1
@@ -577,261 +581,305 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             l0, l1 = int(live_rows[0]), int(live_rows[1])
             if 0 <= l0 < l1 <= n and (l1 - l0) < n:
                 live = (l0, l1)
-        segs = [(0, nr)]                 # global row ranges the per-token operations of a block run on
-        for li, (blk, e) in enumerate(zip(self.blocks, pk.layers)):
-            m = mod[:, li]                                                        # [R, 6, D] view, row stride = layers*6*D
-            last_live = live is not None and li == len(self.blocks) - 1
-            if last_live:
-                segs = [(bi * n + live[0], bi * n + live[1]) for bi in range(b)]
-            # 1. self-attention (:334-336)
-            once = shared and li == 0
-            xq1 = None
-            if not once:
-                if default_procs and sh is None:
-                    xq1 = self._ln_q(li, "qkv", 0, x, shift=m[:, 0], scale=m[:, 1], sel=sel, eps=cfg.eps)
-                if xq1 is None:
-                    o.adaln_modulate(x, m[:, 0], m[:, 1], sel, cfg.eps, out=nrm)
-            if not default_procs:
-                if sh is not None:
-                    raise NotImplementedError("token-sharded execution needs the built-in MI355WanAttnProcessor")
-                rot = _CompactRope((cos1, sin1))
-                a = blk.attn1(nrm.view(b, n, d), rotary_emb=rot, **(attention_kwargs or {}))
-                o.gated_residual(x, a.reshape(nr, d), m[:, 2], sel, out=x)
-            elif sh is None and shared and li == 0:
-                n1, q1, sel1 = nrm[:n], ws.qkv[:n], (None if sel is None else sel[:n])
-                o.adaln_modulate(x[:n], m[:, 0], m[:, 1], sel1, cfg.eps, out=n1)
-                self._lin(li, "qkv", n1, e.wqkv, e.bqkv, out=q1)
-                self._qk_norm_rope(blk, q1, d, cos1, sin1, dh, qfold)
-                q3 = q1.view(1, n, 3 * d)
-                attend(q3[:, :, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], heads, out=att[:n].view(1, n, d), **afold)
-                self._lin(li, "out", att[:n], blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias, o.EPI_GATED_RESIDUAL,
-                          residual=x[:n], gate=m[:, 2], sel=sel1, out=x[:n])
-                for bi in range(1, b):
-                    x[bi * n:(bi + 1) * n].copy_(x[:n])
-            elif sh is None:
-                qkv = ws.qkv[:nr]
-                self._lin(li, "qkv", nrm, e.wqkv, e.bqkv, xq=xq1, out=qkv)
-                self._qk_norm_rope(blk, qkv, d, cos, sin, dh, qfold)
-                q3 = qkv.view(b, n, 3 * d)
-                if last_live:            # every row is a key; only the live rows are queries
-                    attend(q3[:, live[0]:live[1], :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], heads,
-                           out=att.view(b, n, d)[:, live[0]:live[1]], **afold)
-                else:
-                    attend(q3[:, :, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], heads, out=att.view(b, n, d), **afold)
-            elif sh.heads_exchange_ok(heads):
-                # heads exchange (frameino_amd/parallel.py): q | k | v of MY tokens -> all-to-all -> all tokens of MY
-                # heads -> one attention launch over the whole sequence -> all-to-all back to the token owners
-                ways = sh.ways
-                hp = heads // ways
-                dp = hp * dh
-                qkv = ws.qkv[:n]
-                self._lin(li, "qkv", nrm, e.wqkv, e.bqkv, out=qkv, **tk)
-                # the heads travel in groups, every group its own all-to-all on the communicator's stream: while group g
-                # is attended to, group g+1 arrives and group g-1's outputs leave
-                lay = sh.heads_send_layout(heads, dh, lpad, dt, dev) if hasattr(o, "qkv_rmsnorm_rope_") else None
-                if lay is not None:
-                    # ONE launch: RMSNorm + RoPE write q and k straight into the send buffers (slice j: heads of rank j) and
-                    # v follows as a scattering copy -- no permute copy of q | k | v afterwards
-                    o.qkv_rmsnorm_rope_(qkv, d, blk.attn1.norm_q.weight, blk.attn1.norm_q.eps, blk.attn1.norm_k.weight,
-                                        blk.attn1.norm_k.eps, cos, sin, dh, q_out_scale=qfold.get("out_scale", 1.0),
-                                        out=lay.flat, head_off=lay.off_qkv, head_ld=lay.ld)
-                else:
-                    o.rmsnorm_rope_(qkv[:, :d], blk.attn1.norm_q.weight, blk.attn1.norm_q.eps, cos, sin, dh, **qfold)
-                    o.rmsnorm_rope_(qkv[:, d:2 * d], blk.attn1.norm_k.weight, blk.attn1.norm_k.eps, cos, sin, dh)
-                    q4 = qkv.view(n, 3, ways, dp)
-                inflight = []
-                for gi, (h0, h1) in enumerate(sh.head_ranges(hp)):
-                    dg = (h1 - h0) * dh
-                    if lay is not None:
-                        send = lay.views[gi]
-                    else:
-                        send = sh.a2a_buffer(f"qkv_send{gi}", (ways, lpad, 3, dg), dt, dev)   # slice j: heads of rank j
-                        send[:, :n].copy_(q4[:, :, :, h0 * dh:h1 * dh].permute(2, 0, 1, 3))
-                    inflight.append((gi, h0, h1, dg) + sh.all_to_all(f"qkv_recv{gi}", send, async_op=True))
-                # the outputs return into ONE flat [group][rank j's heads][token] buffer when the groups are equal: the
-                # out-projection then reads it as K blocks (fino_gemm_blocked_a) instead of a permute copy into [token, D]
-                orl = (sh.heads_recv_layout(heads, dh, lpad, dt, dev)
-                       if (not self._fp8 and hasattr(o, "gemm_blocked_a") and hasattr(sh, "heads_recv_layout")) else None)
-                back = []
-                for gi, h0, h1, dg, recv, work in inflight:                                # slice j: tokens of rank j
-                    if work is not None:
-                        work.wait()
-                    r3 = recv.view(1, ways * lpad, 3 * dg)[:, :L]
-                    oh = sh.a2a_buffer(f"o_send{gi}", (ways, lpad, dg), dt, dev)
-                    o.attention(r3[:, :, :dg], r3[:, :, dg:2 * dg], r3[:, :, 2 * dg:], h1 - h0,
-                                out=oh.view(1, ways * lpad, dg)[:, :L], **afold)
-                    back.append((h0, h1) + sh.all_to_all(f"o_recv{gi}", oh, async_op=True))
-                if orl is not None and all(orv.data_ptr() == orl[gi].data_ptr() for gi, (_, _, orv, _) in enumerate(back)):
-                    for _, _, _, work in back:
-                        if work is not None:
-                            work.wait()
-                    o.gemm_blocked_a(orl, n, blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias, x, m[:, 2], sel, out=x,
-                                     **tk)
-                    once = True                                     # the common out-projection below is done
-                else:
-                    a3 = att.view(n, ways, dp)
-                    for h0, h1, orv, work in back:                                         # slice j: heads of rank j
-                        if work is not None:
-                            work.wait()
-                        a3[:, :, h0 * dh:h1 * dh].copy_(orv[:, :n].permute(1, 0, 2))
-            elif (hasattr(sh, "kv_groups") and sh.kv_groups(heads) > 1 and hasattr(o, "rmsnorm_rope_scatter")
-                  and hasattr(sh, "kv_group_layout")):
-                # K|V all-gather in HEAD GROUPS (TokenShard.kv_head_groups): the attention of group g runs while group g+1 is
-                # still on the wire.  k (norm_k + RoPE) is scattered by head into [group][token][k_g | v_g] send blocks, v
-                # follows as a scattering copy; per group one all-gather and one attention launch over that group's heads.
-                kv_loc = sh.kv_local(lpad, 2 * d, dt, dev)
-                lay = sh.kv_group_layout(heads, dh, lpad, dt, dev)
-                if sh.fused_qkv_ok() and not self._fp8:
-                    o.gemm(nrm, e.wqkv, e.bqkv, out=q2, out2=kv_loc[:n], split=d, **tk)
-                else:
-                    self._lin(li, "kv", nrm, e.wqkv[d:], e.bqkv[d:], out=kv_loc[:n], **tk)
-                o.rmsnorm_rope_scatter(kv_loc[:n, :d], blk.attn1.norm_k.weight, blk.attn1.norm_k.eps, cos, sin, dh, lay.flat,
-                                       lay.off_k, lay.ld)
-                o.rmsnorm_rope_scatter(kv_loc[:n, d:], None, 0.0, None, None, dh, lay.flat, lay.off_v, lay.ld)
-                flying = [sh._all_gather(f"kv_all_g{gi}", v_, True) for gi, v_ in enumerate(lay.views)]
-                if not (sh.fused_qkv_ok() and not self._fp8):
-                    self._lin(li, "q", nrm, e.wqkv[:d], e.bqkv[:d], out=q2, **tk)
-                o.rmsnorm_rope_(q2, blk.attn1.norm_q.weight, blk.attn1.norm_q.eps, cos, sin, dh, **qfold)
-                q3, a3 = q2.view(1, n, d), att.view(1, n, d)
-                for (h0, h1), (kv_all, work) in zip(lay.ranges, flying):
-                    if work is not None:
-                        work.wait()
-                    dg = (h1 - h0) * dh
-                    kv3 = kv_all.view(1, -1, 2 * dg)[:, :L]
-                    o.attention(q3[:, :, h0 * dh:h1 * dh], kv3[:, :, :dg], kv3[:, :, dg:], h1 - h0,
-                                out=a3[:, :, h0 * dh:h1 * dh], **afold)
-            else:
-                kv_loc = sh.kv_local(lpad, 2 * d, dt, dev)
-                if sh.fused_qkv_ok() and not self._fp8:
-                    # ONE q | k | v GEMM whose k | v columns land in the all-gather's send buffer (fino_gemm_split_n): the
-                    # interleaved plan, where the OTHER branch's compute is what the gather flies under
-                    o.gemm(nrm, e.wqkv, e.bqkv, out=q2, out2=kv_loc[:n], split=d, **tk)
-                    o.rmsnorm_rope_(kv_loc[:n, :d], blk.attn1.norm_k.weight, blk.attn1.norm_k.eps, cos, sin, dh)
-                    kv_all, work = sh.all_gather_kv(kv_loc)
-                else:
-                    # K|V of the local tokens first, so that their all-gather (RCCL over xGMI) overlaps the Q projection
-                    self._lin(li, "kv", nrm, e.wqkv[d:], e.bqkv[d:], out=kv_loc[:n], **tk)
-                    o.rmsnorm_rope_(kv_loc[:n, :d], blk.attn1.norm_k.weight, blk.attn1.norm_k.eps, cos, sin, dh)
-                    kv_all, work = sh.all_gather_kv(kv_loc)
-                    self._lin(li, "q", nrm, e.wqkv[:d], e.bqkv[:d], out=q2, **tk)
-                o.rmsnorm_rope_(q2, blk.attn1.norm_q.weight, blk.attn1.norm_q.eps, cos, sin, dh, **qfold)
-                if sh.local_first():
-                    # local keys first -- nothing of it waits for the wire -- then what the gather delivered before /
-                    # after the own chunk; the (O, m, l) partials are merged (same softmax up to fp32 summation order)
-                    qv = q2.view(1, n, d)
-                    pf = o.attention_partial_floats(1, heads, n, dh) if hasattr(o, "attention_partial_floats") else 0
-                    parts = [o.attention_partial(qv, kv_loc[:n, :d][None], kv_loc[:n, d:][None], heads,
-                                                 out=sh.partial_buf(0, pf, dev), **afold)]
-                    if work is not None:
-                        work.wait()
-                    kv3 = kv_all.view(1, -1, 2 * d)
-                    for pi, (k0, k1) in enumerate(((0, lo), (lo + lpad, L))):
-                        if k1 > k0:
-                            parts.append(o.attention_partial(qv, kv3[:, k0:k1, :d], kv3[:, k0:k1, d:], heads,
-                                                             out=sh.partial_buf(1 + pi, pf, dev), **afold))
-                    o.attention_merge(parts, 1, n, heads, dh, dt, out=att.view(1, n, d))
-                else:
-                    if work is not None:
-                        work.wait()
-                    kv3 = kv_all.view(1, -1, 2 * d)[:, :L]
-                    o.attention(q2.view(1, n, d), kv3[:, :, :d], kv3[:, :, d:], heads, out=att.view(1, n, d), **afold)
-            if default_procs and not once:
-                for r0, r1 in segs:
-                    self._lin(li, "out", att[r0:r1], blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias, o.EPI_GATED_RESIDUAL,
-                              residual=x[r0:r1], gate=m[:, 2], sel=None if sel is None else sel[r0:r1], out=x[r0:r1], **tk)
-            # 2. cross-attention (:339-341): text K/V are replicated, nothing to exchange
-            n2 = blk.norm2
-            xq2 = self._ln_q(li, "q2", 1, x, weight=n2.weight, bias=n2.bias, eps=cfg.eps) if (n2 is not None and
-                                                                                                default_procs) else None
-            if xq2 is not None:
-                pass
-            elif n2 is not None:
-                for r0, r1 in segs:
-                    o.layernorm(x[r0:r1], n2.weight, n2.bias, cfg.eps, out=nrm[r0:r1])
-            else:
-                nrm.copy_(x)
-            if default_procs:
-                for r0, r1 in segs:
-                    self._lin(li, "q2", nrm[r0:r1], blk.attn2.to_q.weight, blk.attn2.to_q.bias, xq=xq2, out=q2[r0:r1], **tk)
-                kv = text.kv[li].view(b, lt, 2 * d)
-                s0, s1 = (live if last_live else (0, n))                       # the rows of every batch element that run
-                if text.w2 is not None:
-                    # norm_q's statistic only (the probabilities kernel normalises q while it loads it: same rounding points, no
-                    # pass that rewrites q); probabilities per sample, then x += P.(V W_o^T) + b: K = heads x keys instead of D
-                    rr = text.rrms
-                    for r0, r1 in segs:
-                        o.row_rrms(q2[r0:r1], blk.attn2.norm_q.eps, out=rr[r0:r1])
-                    for i in range(b):
-                        r0, r1 = i * n + s0, i * n + s1
-                        pr = o.attention_probs(q2[r0:r1].view(1, s1 - s0, d), kv[i:i + 1, :, :d], heads, text.tail[0][i:i + 1],
-                                               text.tail[1][i:i + 1], text.kp[i], out=text.pbuf[i][:s1 - s0].view(1, s1 - s0, -1),
-                                               q_rrms=rr[r0:r1].view(1, s1 - s0), q_weight=blk.attn2.norm_q.weight)
-                        xi = x[r0:r1]
-                        o.gemm(pr.view(s1 - s0, -1), text.w2[li][i], blk.attn2.to_out[0].bias, o.EPI_RESIDUAL, residual=xi, out=xi, **tk)
-                else:
-                    for r0, r1 in segs:
-                        o.rmsnorm_rope_(q2[r0:r1], blk.attn2.norm_q.weight, blk.attn2.norm_q.eps)
-                    qv, av = q2.view(b, n, d)[:, s0:s1], att.view(b, n, d)[:, s0:s1]
-                    if text.tail is not None:
-                        o.attention_tail(qv, kv[:, :, :d], kv[:, :, d:], heads, text.tail[0], text.tail[1], out=av)
-                    else:
-                        o.attention(qv, kv[:, :, :d], kv[:, :, d:], heads, out=av)
-                    for r0, r1 in segs:
-                        self._lin(li, "out2", att[r0:r1], blk.attn2.to_out[0].weight, blk.attn2.to_out[0].bias, o.EPI_RESIDUAL,
-                                  residual=x[r0:r1], out=x[r0:r1], **tk)
-            else:
-                a = blk.attn2(nrm.view(b, n, d), encoder_hidden_states=text.txt.view(b, lt, d),
-                              **(attention_kwargs or {}))
-                o.gated_residual(x, a.reshape(nr, d), out=x)
-            # 3. feed-forward (:344-348)
-            xq3 = (self._ln_q(li, "ff1", 0, x, shift=m[:, 3], scale=m[:, 4], sel=sel, eps=cfg.eps)
-                   if (li, "ff2") in self._fp8 else None)
-            if xq3 is None:
-                for r0, r1 in segs:
-                    o.adaln_modulate(x[r0:r1], m[:, 3], m[:, 4], None if sel is None else sel[r0:r1], cfg.eps, out=nrm[r0:r1])
-            # MXFP8: the adaLN emits the FFN input already quantised, and the GELU epilogue the hidden activations
-            if self._ffn_mxfp8(li, nrm, xq3, blk.ffn.net[0].proj.bias, blk.ffn.net[2].bias, o.EPI_GATED_RESIDUAL, residual=x,
-                               gate=m[:, 5], sel=sel, out=x) is None:
-                for r0, r1 in segs:
-                    self._lin(li, "ff1", nrm[r0:r1], blk.ffn.net[0].proj.weight, blk.ffn.net[0].proj.bias, o.EPI_GELU_TANH,
-                              out=ff[r0:r1], **tk)
-                    self._lin(li, "ff2", ff[r0:r1], blk.ffn.net[2].weight, blk.ffn.net[2].bias, o.EPI_GATED_RESIDUAL,
-                              residual=x[r0:r1], gate=m[:, 5], sel=None if sel is None else sel[r0:r1], out=x[r0:r1], **tk)
-            if fbc is not None and li == 0:
-                computes = self._step_cache_probe(fbc, h0, x, h1c)          # one host read: the rule's decision
-            yield
-            if fbc is not None and not any(computes):
-                break                                                       # every segment skips blocks 1 .. N-1
+        return _Call(b=b, n=n, nr=nr, lo=lo, lpad=lpad, L=L, nf=nf, hh=hh, ww=ww, d=d, heads=heads, dh=dh, dev=dev, dt=dt,
+                     eps=cfg.eps, sh=sh, tk=tk, pk=pk, ws=ws, x=ws.x[:nr], nrm=ws.n[:nr], att=ws.att[:nr], q2=ws.q2[:nr],
+                     ff=ws.ff[:nr], qkv=ws.qkv[:nr], cos=cos, sin=sin, cos1=cos1, sin1=sin1, sel=sel, mod=mod, head=head,
+                     text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
+                     afold={"scale": o.SCALE_FOLDED} if fold else {}, attend=attend, default_procs=default_procs,
+                     shared=shared, fbc=fbc, h0=None, h1c=None, attention_kwargs=attention_kwargs, live=live,
+                     live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
+                     rows=(0, n),            # the rows of every batch element that run as queries / per-token rows ...
+                     segs=[(0, nr)])         # ... and the global row ranges the per-token operations of a block run on
 
-        if fbc is not None:
-            # tail residuals of the computed segments; T(tail + h1) for the skipped ones.  With `live_rows` the last block left
-            # the dead rows at block N-2's output, so a tail residual is meaningful on the live rows only -- the rows the caller
-            # reads; the head below runs on those rows alone whether or not the blocks ran.
-            self._step_cache_finish(fbc, computes, x, h1c)
-            if live is not None:
-                segs = [(bi * n + live[0], bi * n + live[1]) for bi in range(b)]
+    # ------------------------------------------------------------------ forward: stages
+    def _embed(self, c, hidden_states):
+        """patch embedding (:486-487): gather + GEMM (the gather is 9 MB; every rank builds it, keeps its rows); under the
+        shared prefix one element's rows only (x[:n]); with the first-block cache h0 is kept aside (block 0 updates x in place)."""
+        o, x, b, n = self.ops, c.x, c.b, c.n
+        patch = self.config.patch_size
+        if b == 1 or c.shared:
+            a_rows = o.patchify(hidden_states[0], patch)[c.lo:c.lo + n]
+        else:
+            a_rows = torch.cat([o.patchify(hidden_states[i], patch) for i in range(b)])
+        o.gemm(a_rows, c.pk.w_patch, self.patch_embedding.bias, out=x[:n] if c.shared else x, **c.tk)
+        if c.fbc is not None:
+            ws = c.ws                        # h0, and a buffer for the probe's copy of h1
+            if getattr(ws, "fbc_h0", None) is None:
+                ws.fbc_h0, ws.fbc_h1 = torch.empty_like(ws.x), torch.empty_like(ws.x)
+            c.h0, c.h1c = ws.fbc_h0[:c.nr], ws.fbc_h1[:c.nr]
+            if c.shared:                     # (the embedding of the shared latent sits in the first n rows only)
+                for bi in range(b):
+                    c.h0[bi * n:(bi + 1) * n].copy_(x[:n])
+            else:
+                c.h0.copy_(x)
 
-        # ---- output head (:519-543) ----
-        for r0, r1 in segs:
-            o.adaln_modulate(x[r0:r1], head[:, 0], head[:, 1], None if sel is None else sel[r0:r1], cfg.eps, out=nrm[r0:r1])
-        if sh is None:
-            po = ws.po[:nr]
-            if live is not None:
-                po.zero_()               # rows nobody computed: the caller asked not to read them -- zeros, not the last call's values
+    def _self_attention(self, c, li, blk, e, m):
+        """Block li's self-attention branch (:334-336) by the strategy this call takes.  -> True when the strategy has already
+        added the branch to x; False when its result waits in `att` for `_self_attention_out`."""
+        sh = c.sh
+        if not c.default_procs:                       # a processor the user installed, through the plugin protocol
+            if sh is not None:
+                raise NotImplementedError("token-sharded execution needs the built-in MI355WanAttnProcessor")
+            return self._sa_processors(c, blk, m)
+        if c.shared and li == 0:                      # CFG batch of one latent: block 0's branch once, copied
+            return self._sa_shared_prefix(c, li, blk, e, m)
+        if sh is None:                                # one GPU
+            return self._sa_single(c, li, blk, e, m)
+        self.ops.adaln_modulate(c.x, m[:, 0], m[:, 1], c.sel, c.eps, out=c.nrm)
+        if sh.heads_exchange_ok(c.heads):             # token shards <-> head shards by all-to-all
+            return self._sa_heads_exchange(c, li, blk, e, m)
+        if sh.kv_groups(c.heads) > 1:                 # K|V all-gather in head groups
+            return self._sa_kv_head_groups(c, li, blk, e)
+        return self._sa_kv_gather(c, li, blk, e)      # K|V all-gather, one attention pass or local-first partials
+
+    def _sa_processors(self, c, blk, m):
+        o = self.ops
+        o.adaln_modulate(c.x, m[:, 0], m[:, 1], c.sel, c.eps, out=c.nrm)
+        a = blk.attn1(c.nrm.view(c.b, c.n, c.d), rotary_emb=_CompactRope((c.cos1, c.sin1)), **(c.attention_kwargs or {}))
+        o.gated_residual(c.x, a.reshape(c.nr, c.d), m[:, 2], c.sel, out=c.x)
+        return True
+
+    def _sa_shared_prefix(self, c, li, blk, e, m):
+        """the whole branch, out-projection included, on the first element's rows; the other elements get a copy of x"""
+        o, n, d, x, to_out = self.ops, c.n, c.d, c.x, blk.attn1.to_out[0]
+        n1, q1, a1, sel1 = c.nrm[:n], c.qkv[:n], c.att[:n], _sel_rows(c.sel, 0, n)
+        o.adaln_modulate(x[:n], m[:, 0], m[:, 1], sel1, c.eps, out=n1)
+        self._lin(li, "qkv", n1, e.wqkv, e.bqkv, out=q1)
+        self._qk_norm_rope(blk, q1, d, c.cos1, c.sin1, c.dh, c.qfold)
+        q3 = q1.view(1, n, 3 * d)
+        c.attend(q3[:, :, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, out=a1.view(1, n, d), **c.afold)
+        self._lin(li, "out", a1, to_out.weight, to_out.bias, o.EPI_GATED_RESIDUAL, residual=x[:n], gate=m[:, 2], sel=sel1,
+                  out=x[:n])
+        for bi in range(1, c.b):
+            x[bi * n:(bi + 1) * n].copy_(x[:n])
+        return True
+
+    def _sa_single(self, c, li, blk, e, m):
+        o, b, n, d = self.ops, c.b, c.n, c.d
+        xq = self._ln_q(li, "qkv", 0, c.x, shift=m[:, 0], scale=m[:, 1], sel=c.sel, eps=c.eps)
+        if xq is None:
+            o.adaln_modulate(c.x, m[:, 0], m[:, 1], c.sel, c.eps, out=c.nrm)
+        self._lin(li, "qkv", c.nrm, e.wqkv, e.bqkv, xq=xq, out=c.qkv)
+        self._qk_norm_rope(blk, c.qkv, d, c.cos, c.sin, c.dh, c.qfold)
+        q3 = c.qkv.view(b, n, 3 * d)
+        s0, s1 = c.rows                  # every row is a key; under `live_rows` only the live rows of the last block are queries
+        c.attend(q3[:, s0:s1, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, out=c.att.view(b, n, d)[:, s0:s1], **c.afold)
+        return False
+
+    def _sa_heads_exchange(self, c, li, blk, e, m):
+        """heads exchange (frameino_amd/parallel.py): q | k | v of MY tokens -> all-to-all -> all tokens of MY heads -> one
+        attention launch over the whole sequence -> all-to-all back to the token owners.  -> whether the out-projection ran here."""
+        o, sh, n, L, lpad, heads, dh, dt, dev = self.ops, c.sh, c.n, c.L, c.lpad, c.heads, c.dh, c.dt, c.dev
+        ways = sh.ways
+        hp = heads // ways
+        self._lin(li, "qkv", c.nrm, e.wqkv, e.bqkv, out=c.qkv, **c.tk)
+        # the heads travel in groups, every group its own all-to-all on the communicator's stream: while group g is attended
+        # to, group g+1 arrives and group g-1's outputs leave.  ONE launch: RMSNorm + RoPE write q and k straight into the send
+        # buffers (slice j: heads of rank j) and v follows as a scattering copy -- no permute copy of q | k | v afterwards
+        lay = sh.heads_send_layout(heads, dh, lpad, dt, dev)
+        self._qk_norm_rope(blk, c.qkv, c.d, c.cos, c.sin, dh, c.qfold, out=lay.flat, head_off=lay.off_qkv, head_ld=lay.ld)
+        inflight = [(gi, h0, h1, (h1 - h0) * dh) + sh.all_to_all(f"qkv_recv{gi}", lay.views[gi], async_op=True)
+                    for gi, (h0, h1) in enumerate(sh.head_ranges(hp))]
+        # the outputs return into ONE flat [group][rank j's heads][token] buffer when the groups are equal: the
+        # out-projection then reads it as K blocks (fino_gemm_blocked_a) instead of a permute copy into [token, D]
+        orl = sh.heads_recv_layout(heads, dh, lpad, dt, dev) if not self._fp8 else None
+        back = []
+        for gi, h0, h1, dg, recv, work in inflight:                                # slice j: tokens of rank j
+            if work is not None:
+                work.wait()
+            r3 = recv.view(1, ways * lpad, 3 * dg)[:, :L]
+            oh = sh.a2a_buffer(f"o_send{gi}", (ways, lpad, dg), dt, dev)
+            o.attention(r3[:, :, :dg], r3[:, :, dg:2 * dg], r3[:, :, 2 * dg:], h1 - h0,
+                        out=oh.view(1, ways * lpad, dg)[:, :L], **c.afold)
+            back.append((h0, h1) + sh.all_to_all(f"o_recv{gi}", oh, async_op=True))
+        blocked = orl is not None and all(orv.data_ptr() == orl[gi].data_ptr() for gi, (_, _, orv, _) in enumerate(back))
+        a3 = c.att.view(n, ways, hp * dh)
+        for h0, h1, orv, work in back:                                             # slice j: heads of rank j
+            if work is not None:
+                work.wait()
+            if not blocked:              # MX linears, or unequal groups: the permute copy into [token, D]
+                a3[:, :, h0 * dh:h1 * dh].copy_(orv[:, :n].permute(1, 0, 2))
+        if blocked:
+            to_out = blk.attn1.to_out[0]
+            o.gemm_blocked_a(orl, n, to_out.weight, to_out.bias, c.x, m[:, 2], c.sel, out=c.x, **c.tk)
+        return blocked
+
+    def _project_kv(self, c, li, e, fused):
+        """k | v of the shard's rows into the all-gather's send buffer `kv_loc`.  `fused`: ONE q | k | v GEMM whose k | v
+        columns land there (fino_gemm_split_n) -- the interleaved plan, where the OTHER branch's compute is what the gather
+        flies under; else K|V alone first, so that their all-gather (RCCL over xGMI) overlaps the Q projection (`_project_q`)."""
+        kv_loc = c.sh.kv_local(c.lpad, 2 * c.d, c.dt, c.dev)
+        if fused:
+            self.ops.gemm(c.nrm, e.wqkv, e.bqkv, out=c.q2, out2=kv_loc[:c.n], split=c.d, **c.tk)
+        else:
+            self._lin(li, "kv", c.nrm, e.wqkv[c.d:], e.bqkv[c.d:], out=kv_loc[:c.n], **c.tk)
+        return kv_loc
+
+    def _project_q(self, c, li, blk, e, fused):
+        """q (its projection unless the fused GEMM made it) + norm_q + RoPE, in `q2`"""
+        if not fused:
+            self._lin(li, "q", c.nrm, e.wqkv[:c.d], e.bqkv[:c.d], out=c.q2, **c.tk)
+        self.ops.rmsnorm_rope_(c.q2, blk.attn1.norm_q.weight, blk.attn1.norm_q.eps, c.cos, c.sin, c.dh, **c.qfold)
+
+    def _sa_kv_head_groups(self, c, li, blk, e):
+        """K|V all-gather in HEAD GROUPS (TokenShard.kv_head_groups): the attention of group g runs while group g+1 is still on
+        the wire.  k (norm_k + RoPE) is scattered by head into [group][token][k_g | v_g] send blocks, v follows as a scattering
+        copy; per group one all-gather and one attention launch over that group's heads."""
+        o, sh, n, d, dh, nk = self.ops, c.sh, c.n, c.d, c.dh, blk.attn1.norm_k
+        fused = sh.fused_qkv_ok() and not self._fp8
+        kv_loc = self._project_kv(c, li, e, fused)
+        lay = sh.kv_group_layout(c.heads, dh, c.lpad, c.dt, c.dev)
+        o.rmsnorm_rope_scatter(kv_loc[:n, :d], nk.weight, nk.eps, c.cos, c.sin, dh, lay.flat, lay.off_k, lay.ld)
+        o.rmsnorm_rope_scatter(kv_loc[:n, d:], None, 0.0, None, None, dh, lay.flat, lay.off_v, lay.ld)
+        flying = [sh._all_gather(f"kv_all_g{gi}", v_, True) for gi, v_ in enumerate(lay.views)]
+        self._project_q(c, li, blk, e, fused)
+        q3, a3 = c.q2.view(1, n, d), c.att.view(1, n, d)
+        for (h0, h1), (kv_all, work) in zip(lay.ranges, flying):
+            if work is not None:
+                work.wait()
+            dg = (h1 - h0) * dh
+            kv3 = kv_all.view(1, -1, 2 * dg)[:, :c.L]
+            o.attention(q3[:, :, h0 * dh:h1 * dh], kv3[:, :, :dg], kv3[:, :, dg:], h1 - h0, out=a3[:, :, h0 * dh:h1 * dh],
+                        **c.afold)
+        return False
+
+    def _sa_kv_gather(self, c, li, blk, e):
+        """K|V all-gather: one attention launch over the gathered keys, or (TokenShard.local_first) the local keys first."""
+        o, sh, n, d, dh, heads, lo, L, nk = self.ops, c.sh, c.n, c.d, c.dh, c.heads, c.lo, c.L, blk.attn1.norm_k
+        fused = sh.fused_qkv_ok() and not self._fp8
+        kv_loc = self._project_kv(c, li, e, fused)
+        o.rmsnorm_rope_(kv_loc[:n, :d], nk.weight, nk.eps, c.cos, c.sin, dh)
+        kv_all, work = sh.all_gather_kv(kv_loc)
+        self._project_q(c, li, blk, e, fused)
+        qv, av = c.q2.view(1, n, d), c.att.view(1, n, d)
+        if not sh.local_first():
+            if work is not None:
+                work.wait()
+            kv3 = kv_all.view(1, -1, 2 * d)[:, :L]
+            o.attention(qv, kv3[:, :, :d], kv3[:, :, d:], heads, out=av, **c.afold)
+            return False
+        # local keys first -- nothing of it waits for the wire -- then what the gather delivered before / after the own
+        # chunk; the (O, m, l) partials are merged (same softmax up to fp32 summation order)
+        pf = o.attention_partial_floats(1, heads, n, dh) if hasattr(o, "attention_partial_floats") else 0
+        parts = [o.attention_partial(qv, kv_loc[:n, :d][None], kv_loc[:n, d:][None], heads, out=sh.partial_buf(0, pf, c.dev),
+                                     **c.afold)]
+        if work is not None:
+            work.wait()
+        kv3 = kv_all.view(1, -1, 2 * d)
+        for pi, (k0, k1) in enumerate(((0, lo), (lo + c.lpad, L))):
+            if k1 > k0:
+                parts.append(o.attention_partial(qv, kv3[:, k0:k1, :d], kv3[:, k0:k1, d:], heads,
+                                                 out=sh.partial_buf(1 + pi, pf, c.dev), **c.afold))
+        o.attention_merge(parts, 1, n, heads, dh, c.dt, out=av)
+        return False
+
+    def _self_attention_out(self, c, li, blk, m):
+        """x += gate * to_out(att) on the rows that run (:336, the gated residual as the GEMM's epilogue)"""
+        to_out = blk.attn1.to_out[0]
+        for r0, r1 in c.segs:
+            self._lin(li, "out", c.att[r0:r1], to_out.weight, to_out.bias, self.ops.EPI_GATED_RESIDUAL, residual=c.x[r0:r1],
+                      gate=m[:, 2], sel=_sel_rows(c.sel, r0, r1), out=c.x[r0:r1], **c.tk)
+
+    def _cross_attention(self, c, li, blk):
+        """text cross-attention (:339-341): text K/V are replicated, nothing to exchange"""
+        o, x, nrm, q2, att, segs, text = self.ops, c.x, c.nrm, c.q2, c.att, c.segs, c.text
+        b, n, d, heads, n2, a2 = c.b, c.n, c.d, c.heads, blk.norm2, blk.attn2
+        xq = self._ln_q(li, "q2", 1, x, weight=n2.weight, bias=n2.bias, eps=c.eps) if (n2 is not None
+                                                                                       and c.default_procs) else None
+        if xq is None and n2 is not None:
             for r0, r1 in segs:
+                o.layernorm(x[r0:r1], n2.weight, n2.bias, c.eps, out=nrm[r0:r1])
+        elif xq is None:
+            nrm.copy_(x)
+        if not c.default_procs:
+            a = a2(nrm.view(b, n, d), encoder_hidden_states=text.txt.view(b, text.lt, d), **(c.attention_kwargs or {}))
+            o.gated_residual(x, a.reshape(c.nr, d), out=x)
+            return
+        for r0, r1 in segs:
+            self._lin(li, "q2", nrm[r0:r1], a2.to_q.weight, a2.to_q.bias, xq=xq, out=q2[r0:r1], **c.tk)
+        kv = text.kv[li].view(b, text.lt, 2 * d)
+        s0, s1 = c.rows
+        if text.w2 is not None:
+            # norm_q's statistic only (the probabilities kernel normalises q while it loads it: same rounding points, no
+            # pass that rewrites q); probabilities per sample, then x += P.(V W_o^T) + b: K = heads x keys instead of D
+            rr = text.rrms
+            for r0, r1 in segs:
+                o.row_rrms(q2[r0:r1], a2.norm_q.eps, out=rr[r0:r1])
+            for i in range(b):
+                r0, r1 = i * n + s0, i * n + s1
+                pr = o.attention_probs(q2[r0:r1].view(1, s1 - s0, d), kv[i:i + 1, :, :d], heads, text.tail[0][i:i + 1],
+                                       text.tail[1][i:i + 1], text.kp[i], out=text.pbuf[i][:s1 - s0].view(1, s1 - s0, -1),
+                                       q_rrms=rr[r0:r1].view(1, s1 - s0), q_weight=a2.norm_q.weight)
+                xi = x[r0:r1]
+                o.gemm(pr.view(s1 - s0, -1), text.w2[li][i], a2.to_out[0].bias, o.EPI_RESIDUAL, residual=xi, out=xi, **c.tk)
+            return
+        for r0, r1 in segs:
+            o.rmsnorm_rope_(q2[r0:r1], a2.norm_q.weight, a2.norm_q.eps)
+        qv, av = q2.view(b, n, d)[:, s0:s1], att.view(b, n, d)[:, s0:s1]
+        if text.tail is not None:
+            o.attention_tail(qv, kv[:, :, :d], kv[:, :, d:], heads, text.tail[0], text.tail[1], out=av)
+        else:
+            o.attention(qv, kv[:, :, :d], kv[:, :, d:], heads, out=av)
+        for r0, r1 in segs:
+            self._lin(li, "out2", att[r0:r1], a2.to_out[0].weight, a2.to_out[0].bias, o.EPI_RESIDUAL, residual=x[r0:r1],
+                      out=x[r0:r1], **c.tk)
+
+    def _ffn(self, c, li, blk, m):
+        """feed-forward (:344-348)"""
+        o, x, nrm, ff, sel = self.ops, c.x, c.nrm, c.ff, c.sel
+        up, down = blk.ffn.net[0].proj, blk.ffn.net[2]
+        xq = self._ln_q(li, "ff1", 0, x, shift=m[:, 3], scale=m[:, 4], sel=sel, eps=c.eps) if (li, "ff2") in self._fp8 else None
+        if xq is None:
+            for r0, r1 in c.segs:
+                o.adaln_modulate(x[r0:r1], m[:, 3], m[:, 4], _sel_rows(sel, r0, r1), c.eps, out=nrm[r0:r1])
+        # MXFP8: the adaLN emits the FFN input already quantised, and the GELU epilogue the hidden activations
+        if self._ffn_mxfp8(li, nrm, xq, up.bias, down.bias, o.EPI_GATED_RESIDUAL, residual=x, gate=m[:, 5], sel=sel,
+                           out=x) is None:
+            for r0, r1 in c.segs:
+                self._lin(li, "ff1", nrm[r0:r1], up.weight, up.bias, o.EPI_GELU_TANH, out=ff[r0:r1], **c.tk)
+                self._lin(li, "ff2", ff[r0:r1], down.weight, down.bias, o.EPI_GATED_RESIDUAL, residual=x[r0:r1], gate=m[:, 5],
+                          sel=_sel_rows(sel, r0, r1), out=x[r0:r1], **c.tk)
+
+    def _output_head(self, c):
+        """output head (:519-543): modulated norm, proj_out, unpatchify -> [b, C_out, F, H, W]"""
+        o, cfg, nrm, sh = self.ops, self.config, c.nrm, c.sh
+        for r0, r1 in c.segs:
+            o.adaln_modulate(c.x[r0:r1], c.head[:, 0], c.head[:, 1], _sel_rows(c.sel, r0, r1), c.eps, out=nrm[r0:r1])
+        if sh is None:
+            po = c.ws.po[:c.nr]
+            if c.live is not None:
+                po.zero_()               # rows nobody computed: the caller asked not to read them -- zeros, not the last call's values
+            for r0, r1 in c.segs:
                 o.gemm(nrm[r0:r1], self.proj_out.weight, self.proj_out.bias, out=po[r0:r1])
         else:
-            po_loc = sh.out_local(lpad, ws.po.shape[1], dt, dev)
-            o.gemm(nrm, self.proj_out.weight, self.proj_out.bias, out=po_loc[:n], **tk)
-            po = sh.all_gather_out(po_loc)[:L]
-        if b == 1:
-            out = o.unpatchify(po, cfg.out_channels, nf, hh, ww, cfg.patch_size)[None]
-        else:
-            po3 = po.view(b, L, -1)
-            out = torch.stack([o.unpatchify(po3[i], cfg.out_channels, nf, hh, ww, cfg.patch_size) for i in range(b)])
-        if not return_dict:
-            return (out,)
-        return SimpleNamespace(sample=out)
+            po_loc = sh.out_local(c.lpad, c.ws.po.shape[1], c.dt, c.dev)
+            o.gemm(nrm, self.proj_out.weight, self.proj_out.bias, out=po_loc[:c.n], **c.tk)
+            po = sh.all_gather_out(po_loc)[:c.L]
+        unpatch = lambda rows: o.unpatchify(rows, cfg.out_channels, c.nf, c.hh, c.ww, cfg.patch_size)      # noqa: E731
+        if c.b == 1:
+            return unpatch(po)[None]
+        po3 = po.view(c.b, c.L, -1)
+        return torch.stack([unpatch(po3[i]) for i in range(c.b)])
+
+
+class _Call:
+    """What the stages of one `WanTransformer3DModel.forward_steps` call share (built by `_bind` at the first `next()`): sizes,
+    the token shard, views of the workspace, tables and the switches that pick a path.  References and views only: nothing on
+    the device the call would not hold anyway.  `rows` / `segs` (set for the last block under `live_rows`) and `h0` / `h1c`
+    (the first-block cache's buffers, set by the embedding stage) are the only fields written after `_bind`."""
+    __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
+                 "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
+                 "afold", "attend", "default_procs", "shared", "fbc", "h0", "h1c", "attention_kwargs", "live", "live_segs",
+                 "rows", "segs")
+
+    def __init__(self, **fields):
+        for k, v in fields.items():
+            setattr(self, k, v)
+
+
+def _sel_rows(sel, r0, r1):
+    """rows [r0, r1) of the per-token modulation selector (None: every row takes table row 0)"""
+    return None if sel is None else sel[r0:r1]
 
 
 class _CompactRope(tuple):

@@ -93,6 +93,67 @@ def test_shared_prefix_needs_identical_modulation_rows():
         assert torch.equal(run(ts, True, **kw), run(ts, False, **kw))
 
 
+def test_forward_steps_contract_of_the_interleaved_pipeline_step():
+    """What the pipeline's interleaved step relies on (pipeline_wan_i2v_motion_frameino.py: two generators, one per CFG branch,
+    advanced alternately): `forward_steps` yields once after the embedding stage and once after every block, its
+    StopIteration.value is what `forward` returns, and two generators advanced alternately under two `cache_context` names give
+    what two sequential forwards give -- every piece of per-call state is the call's own.  All bit for bit."""
+    from tests import cpu_ops
+    torch.manual_seed(7)
+    m = _tiny().float().eval()
+    with torch.no_grad():
+        for p_ in m.parameters():
+            p_.copy_(torch.randn(p_.shape) * (0.5 if p_.ndim == 1 else p_.shape[-1] ** -0.5))
+    m.reset_caches()
+    m.ops = cpu_ops
+    L = 2 * 2 * 2
+    sel = (torch.arange(L) >= 4).to(torch.int32)
+    rows = (torch.tensor([0.0, 700.0]), sel)
+    branches = {"cond": (torch.randn(1, 8, 2, 4, 4), torch.randn(1, 6, 16)),
+                "uncond": (torch.randn(1, 8, 2, 4, 4), torch.randn(1, 5, 16))}
+
+    def drain(gen):
+        yields = 0
+        while True:
+            try:
+                next(gen)
+                yields += 1
+            except StopIteration as done:
+                return yields, done.value
+
+    with torch.no_grad():
+        want = {}
+        for name, (x, txt) in branches.items():
+            with m.cache_context(name):
+                want[name] = m(x, None, txt, return_dict=False, timestep_rows=rows)[0]
+        assert (want["cond"] - want["uncond"]).abs().max() > 1e-3
+        # 1 + num_layers yields; the generator's value is forward's, as a tuple and as an object with `.sample`
+        x, txt = branches["cond"]
+        with m.cache_context("cond"):
+            yields, value = drain(m.forward_steps(x, None, txt, None, False, None, rows))
+            assert yields == 1 + len(m.blocks) and isinstance(value, tuple) and torch.equal(value[0], want["cond"])
+            yields, value = drain(m.forward_steps(hidden_states=x, timestep=torch.tensor([500.0]), encoder_hidden_states=txt))
+            assert yields == 1 + len(m.blocks)
+            assert torch.equal(value.sample, m(x, torch.tensor([500.0]), txt).sample)
+        # two generators bound under their own context names, then advanced alternately outside any context
+        gens, got, yields = {}, {}, {}
+        for name, (x, txt) in branches.items():
+            with m.cache_context(name):
+                gens[name] = m.forward_steps(x, None, txt, None, False, None, rows)
+                next(gens[name])
+            yields[name] = 1
+        while gens:
+            for name in list(gens):
+                try:
+                    next(gens[name])
+                    yields[name] += 1
+                except StopIteration as done:
+                    got[name] = done.value[0]
+                    del gens[name]
+    assert yields == {"cond": 1 + len(m.blocks), "uncond": 1 + len(m.blocks)}
+    assert torch.equal(got["cond"], want["cond"]) and torch.equal(got["uncond"], want["uncond"])
+
+
 def test_swapping_a_processor_after_the_first_forward_is_seen():
     from frameino_amd.attention_processor import MI355WanAttnProcessor
 
