@@ -59,6 +59,10 @@ def main():
     ap.add_argument("--first-block-cache", type=float, default=None, metavar="THRESHOLD",
                     help="diffusers' first-block caching (approximate; eager loop): skip blocks 1..N-1 of a step whose first-block "
                          "residual changed by at most THRESHOLD (relative L1), e.g. 0.1")
+    ap.add_argument("--pab", default=None, metavar="N[,M]",
+                    help="diffusers' Pyramid Attention Broadcast (approximate; eager loop): while the timestep is inside (100, 800) "
+                         "the self-attention branch is recomputed every N-th step and re-used in between, and with M the text "
+                         "cross-attention branch every M-th, e.g. 2 or 2,3.  Not together with --first-block-cache")
     ap.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16",
                     help="the DiT's dtype.  Default fp16 = what the reference app loads it in (app.py:156: "
                          "`WanTransformer3DModel.from_pretrained(..., torch_dtype=torch.float16)`, fp32 islands kept); bf16 is what "
@@ -129,6 +133,12 @@ def main():
     if a.first_block_cache is not None:
         from frameino_amd.step_cache import FirstBlockCacheConfig
         transformer.enable_cache(FirstBlockCacheConfig(threshold=a.first_block_cache))
+    if a.pab is not None:
+        from frameino_amd.step_cache import PyramidAttentionBroadcastConfig
+        n_m = [int(v) for v in a.pab.split(",")]
+        transformer.enable_cache(PyramidAttentionBroadcastConfig(
+            spatial_attention_block_skip_range=n_m[0], cross_attention_block_skip_range=n_m[1] if len(n_m) > 1 else None,
+            current_timestep_callback=lambda: pipe.current_timestep))
     t0 = time.perf_counter()
     canvas, tracks, id_tensor, pads = synthetic_conditions(a.frames, a.height, a.width, dev)
     traj = prepare_traj_tensor(tracks, a.height, a.width, 6, a.width, a.height, device=dev)        # [F, 3, H, W]

@@ -80,6 +80,8 @@ SIGNATURES = {
     "fino_gemm": [c_void_p] * 4 + [c_i64] * 6 + [c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p],
     "fino_gemm_split_n": [c_void_p] * 4 + [c_i64] * 6 + [c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p,
                           c_i64, c_i64, c_int, c_void_p],
+    "fino_gemm_keep": [c_void_p] * 4 + [c_i64] * 6 + [c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p,
+                       c_i64, c_int, c_void_p],
     "fino_ln_mxfp8": [c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
                       c_void_p, c_float, c_int, c_void_p],
     "fino_gemm_blocked_a": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_i64, c_i64, c_i64,
@@ -109,6 +111,8 @@ SIGNATURES = {
                         ctypes.POINTER(c_float), c_int, c_void_p],
     "fino_step_cache_probe": [c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_void_p],
     "fino_step_cache_residual": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_void_p],
+    "fino_pab_broadcast": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_int,
+                           c_void_p],
 }
 
 

@@ -27,7 +27,7 @@ extern "C" int fino_gemm_debug_read(unsigned long long* out) {
 
 namespace {
 
-template <typename T, int EPI, bool GENERIC, bool CONV>
+template <typename T, int EPI, bool GENERIC, bool CONV, bool KEEP = false>
 __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef typename T::vec8 vec8;
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
 #undef LOAD_FRAGS
 #undef MFMA_BLOCK
 
-    gemm_epilogue<T, EPI>(acc, p, smem, m0, n0, tid, lane, wm, wn);
+    gemm_epilogue<T, EPI, false, 8, KEEP>(acc, p, smem, m0, n0, tid, lane, wm, wn);
 }
 
 // ---- ping-pong main loop (aligned K, plain GEMM) ------------------------------------------------------------------
@@ -578,7 +578,7 @@ __device__ __forceinline__ void pp_mainloop(const GemmParams& p, char* smem, con
 // stages, the chained prologue waiting with a counted vmcnt so that the previous tile's stores stay in flight -- took 0.8 %
 // off the layer's GEMMs and nothing off the denoise step; an L2 warm-up touch of the next tile's A rows took nothing off
 // either.  What did pay is inside the epilogue (fino_gemm_common.h: order of issue).
-template <typename T, int EPI, bool CONV = false, int MI = 8, bool ABLK = false>
+template <typename T, int EPI, bool CONV = false, int MI = 8, bool ABLK = false, bool KEEP = false>
 __global__ __launch_bounds__(kThreads, 2) void gemm_pp_kernel(const GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -603,13 +603,13 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_pp_kernel(const GemmParams p
         if (rows <= 64) {
             f32x4_t acc2[2][4];
             pp_mainloop<T, false, 2, ABLK>(p, smem, m0, n0, 0, nk, acc2, tid, lane, wave, wm, wn);
-            gemm_epilogue<T, EPI, false, 2>(acc2, p, smem, m0, n0, tid, lane, wm, wn);
+            gemm_epilogue<T, EPI, false, 2, KEEP>(acc2, p, smem, m0, n0, tid, lane, wm, wn);
             return;
         }
         if (rows <= 128) {
             f32x4_t acc4[4][4];
             pp_mainloop<T, false, 4, ABLK>(p, smem, m0, n0, 0, nk, acc4, tid, lane, wave, wm, wn);
-            gemm_epilogue<T, EPI, false, 4>(acc4, p, smem, m0, n0, tid, lane, wm, wn);
+            gemm_epilogue<T, EPI, false, 4, KEEP>(acc4, p, smem, m0, n0, tid, lane, wm, wn);
             return;
         }
     }
@@ -623,23 +623,23 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_pp_kernel(const GemmParams p
     STAMP(ts1)
     if (blockIdx.x == 17 && lane == 0) fino_gemm_dbg[wave * 8 + 5] = ts1 - ts0;     // prologue + loop + re-sync
 #endif
-    gemm_epilogue<T, EPI, false, MI>(acc, p, smem, m0, n0, tid, lane, wm, wn);
+    gemm_epilogue<T, EPI, false, MI, KEEP>(acc, p, smem, m0, n0, tid, lane, wm, wn);
 }
 
-template <typename T, int EPI, bool GENERIC, bool CONV = false>
+template <typename T, int EPI, bool GENERIC, bool CONV = false, bool KEEP = false>
 int launch_gemm_t(const GemmParams& p, hipStream_t st) {
     static FinoPerDeviceOnce once;
-    if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&gemm_kernel<T, EPI, GENERIC, CONV>), kSmemBytes, "fino_gemm")) return rc;
-    gemm_kernel<T, EPI, GENERIC, CONV><<<dim3((unsigned)(p.tiles_m * p.tiles_n)), kThreads, kSmemBytes, st>>>(p);
+    if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&gemm_kernel<T, EPI, GENERIC, CONV, KEEP>), kSmemBytes, "fino_gemm")) return rc;
+    gemm_kernel<T, EPI, GENERIC, CONV, KEEP><<<dim3((unsigned)(p.tiles_m * p.tiles_n)), kThreads, kSmemBytes, st>>>(p);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }
 
-template <typename T, int EPI, bool CONV = false, int MI = 8, bool ABLK = false>
+template <typename T, int EPI, bool CONV = false, int MI = 8, bool ABLK = false, bool KEEP = false>
 int launch_gemm_pp(const GemmParams& p, hipStream_t st) {
     static FinoPerDeviceOnce once;
-    if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&gemm_pp_kernel<T, EPI, CONV, MI, ABLK>), kSmemBytes, "fino_gemm")) return rc;
-    gemm_pp_kernel<T, EPI, CONV, MI, ABLK><<<dim3((unsigned)(p.tiles_m * p.tiles_n)), kThreads, kSmemBytes, st>>>(p);
+    if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&gemm_pp_kernel<T, EPI, CONV, MI, ABLK, KEEP>), kSmemBytes, "fino_gemm")) return rc;
+    gemm_pp_kernel<T, EPI, CONV, MI, ABLK, KEEP><<<dim3((unsigned)(p.tiles_m * p.tiles_n)), kThreads, kSmemBytes, st>>>(p);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }
@@ -748,8 +748,19 @@ inline bool use_pingpong() {
     return v == 1;
 }
 
-template <typename T, int EPI>
+template <typename T, int EPI, bool KEEP = false>
 int launch_gemm_pp_mi(const GemmParams& p, int mi, hipStream_t st) {
+    if constexpr (KEEP) {  // fino_gemm_keep: y = T(acc + bias) also goes to p.c2 (the residual epilogues, every tile height)
+        switch (mi) {
+            case 2: return launch_gemm_pp<T, EPI, false, 2, false, true>(p, st);
+            case 3: return launch_gemm_pp<T, EPI, false, 3, false, true>(p, st);
+            case 4: return launch_gemm_pp<T, EPI, false, 4, false, true>(p, st);
+            case 5: return launch_gemm_pp<T, EPI, false, 5, false, true>(p, st);
+            case 6: return launch_gemm_pp<T, EPI, false, 6, false, true>(p, st);
+            case 7: return launch_gemm_pp<T, EPI, false, 7, false, true>(p, st);
+            default: return launch_gemm_pp<T, EPI, false, 8, false, true>(p, st);
+        }
+    }
     if (p.a_tpb > 0) {     // K-blocked A: built for the out-projection's epilogue only (fino_gemm_blocked_a checks)
         if constexpr (EPI == FINO_EPI_GATED_RESIDUAL) {
             switch (mi) {
@@ -778,7 +789,7 @@ int launch_gemm_pp_mi(const GemmParams& p, int mi, hipStream_t st) {
 }
 
 // rows [r0, r0 + rows) of the GEMM as one launch of 32 * mi-row tiles
-template <typename T>
+template <typename T, bool KEEP = false>
 int launch_gemm_rows(GemmParams p, int64_t r0, int64_t rows, int mi, int epi, hipStream_t st) {
     p.a += r0 * p.lda;
     p.c += r0 * p.ldc;
@@ -787,6 +798,13 @@ int launch_gemm_rows(GemmParams p, int64_t r0, int64_t rows, int mi, int epi, hi
     if (p.sel) p.sel += r0;
     p.m = rows;
     p.tiles_m = (int)((rows + 32 * mi - 1) / (32 * mi));
+    if constexpr (KEEP) {
+        switch (epi) {
+            case FINO_EPI_RESIDUAL: return launch_gemm_pp_mi<T, FINO_EPI_RESIDUAL, true>(p, mi, st);
+            case FINO_EPI_GATED_RESIDUAL_STAGED: return launch_gemm_pp_mi<T, FINO_EPI_GATED_RESIDUAL_STAGED, true>(p, mi, st);
+            default: return launch_gemm_pp_mi<T, FINO_EPI_GATED_RESIDUAL, true>(p, mi, st);
+        }
+    }
     switch (epi) {
         case FINO_EPI_NONE: return launch_gemm_pp_mi<T, FINO_EPI_NONE>(p, mi, st);
         case FINO_EPI_GELU_TANH: return launch_gemm_pp_mi<T, FINO_EPI_GELU_TANH>(p, mi, st);
@@ -796,7 +814,7 @@ int launch_gemm_rows(GemmParams p, int64_t r0, int64_t rows, int mi, int epi, hi
     }
 }
 
-template <typename T, bool GENERIC>
+template <typename T, bool GENERIC, bool KEEP = false>
 int launch_gemm_e(const GemmParams& p, int epi, int tile_m, hipStream_t st) {
     const bool fits32 = ((p.m - 1) * p.lda + p.k) * 2 < (1ll << 31) && ((p.n - 1) * p.ldw + p.k) * 2 < (1ll << 31);
     if (epi == FINO_EPI_F32 || epi == FINO_EPI_F32_RESIDUAL) {
@@ -812,9 +830,16 @@ int launch_gemm_e(const GemmParams& p, int epi, int tile_m, hipStream_t st) {
     if (!GENERIC && use_pingpong() && fits32) {
         const TilePlan tp = plan_tiles(p.m, p.tiles_n, gemm_device_cus(), tile_m);
         if (tp.rows1 > 0)
-            if (int rc = launch_gemm_rows<T>(p, 0, tp.rows1, 8, epi, st)) return rc;
-        if (tp.rows1 < p.m) return launch_gemm_rows<T>(p, tp.rows1, p.m - tp.rows1, tp.mi2, epi, st);
+            if (int rc = launch_gemm_rows<T, KEEP>(p, 0, tp.rows1, 8, epi, st)) return rc;
+        if (tp.rows1 < p.m) return launch_gemm_rows<T, KEEP>(p, tp.rows1, p.m - tp.rows1, tp.mi2, epi, st);
         return FINO_OK;
+    }
+    if constexpr (KEEP) {
+        switch (epi) {
+            case FINO_EPI_RESIDUAL: return launch_gemm_t<T, FINO_EPI_RESIDUAL, GENERIC, false, true>(p, st);
+            case FINO_EPI_GATED_RESIDUAL_STAGED: return launch_gemm_t<T, FINO_EPI_GATED_RESIDUAL_STAGED, GENERIC, false, true>(p, st);
+            default: return launch_gemm_t<T, FINO_EPI_GATED_RESIDUAL, GENERIC, false, true>(p, st);
+        }
     }
     switch (epi) {
         case FINO_EPI_NONE: return launch_gemm_t<T, FINO_EPI_NONE, GENERIC>(p, st);
@@ -882,10 +907,11 @@ extern "C" int fino_gemm(const void* a, const void* w, const void* bias, void* c
                              0, 0, 0, stream);
 }
 
-extern "C" int fino_gemm_split_n(const void* a, const void* w, const void* bias, void* c, int64_t m, int64_t n, int64_t k,
-                                 int64_t lda, int64_t ldw, int64_t ldc, int epilogue, const void* r, int64_t ldr,
-                                 const float* gate, int64_t mod_stride, const int32_t* sel, int dtype, void* c2,
-                                 int64_t ldc2, int64_t n_split, int tile_m, void* stream) {
+// fino_gemm / fino_gemm_split_n (keep == nullptr) and fino_gemm_keep (c2 == nullptr, n_split == 0): one body
+static int gemm_impl(const void* a, const void* w, const void* bias, void* c, int64_t m, int64_t n, int64_t k, int64_t lda,
+                     int64_t ldw, int64_t ldc, int epilogue, const void* r, int64_t ldr, const float* gate,
+                     int64_t mod_stride, const int32_t* sel, int dtype, void* c2, int64_t ldc2, int64_t n_split, void* keep,
+                     int64_t ldk, int tile_m, void* stream) {
     FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_gemm: dtype %d", dtype);
     FINO_CHECK(tile_m == 0 || (tile_m >= 2 && tile_m <= 8), FINO_ERR_ARG, "fino_gemm: tile_m=%d (0 = planned, 2 .. 8)", tile_m);
     if (c2 || n_split) {
@@ -917,6 +943,7 @@ extern "C" int fino_gemm_split_n(const void* a, const void* w, const void* bias,
     if (m == 0) return FINO_OK;
     GemmParams p = {};
     p.c2 = (uint16_t*)c2; p.ldc2 = ldc2; p.n_split = n_split;
+    if (keep) { p.c2 = (uint16_t*)keep; p.ldc2 = ldk; p.n_split = 0; }
     p.a = (const uint16_t*)a; p.w = (const uint16_t*)w; p.bias = (const uint16_t*)bias; p.c = (uint16_t*)c;
     p.r = (const uint16_t*)r; p.gate = gate; p.sel = sel;
     p.m = m; p.n = n; p.k = k; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.mod_stride = mod_stride;
@@ -934,9 +961,39 @@ extern "C" int fino_gemm_split_n(const void* a, const void* w, const void* bias,
         const int rk = fino_tune_get(FINO_TUNE_GEMM_RASTER);
         if (rk == 1 || (rk == 3 && (k >= 8192 || n >= 8192)) || (rk != 2 && rk != 3 && k >= 8192)) p.group_m |= 0x100;
     }
+    if (keep) {
+        if (dtype == FINO_BF16)
+            return generic ? launch_gemm_e<BF16, true, true>(p, epilogue, tile_m, st)
+                           : launch_gemm_e<BF16, false, true>(p, epilogue, tile_m, st);
+        return generic ? launch_gemm_e<F16, true, true>(p, epilogue, tile_m, st)
+                       : launch_gemm_e<F16, false, true>(p, epilogue, tile_m, st);
+    }
     if (dtype == FINO_BF16)
         return generic ? launch_gemm_e<BF16, true>(p, epilogue, tile_m, st) : launch_gemm_e<BF16, false>(p, epilogue, tile_m, st);
     return generic ? launch_gemm_e<F16, true>(p, epilogue, tile_m, st) : launch_gemm_e<F16, false>(p, epilogue, tile_m, st);
+}
+
+extern "C" int fino_gemm_split_n(const void* a, const void* w, const void* bias, void* c, int64_t m, int64_t n, int64_t k,
+                                 int64_t lda, int64_t ldw, int64_t ldc, int epilogue, const void* r, int64_t ldr,
+                                 const float* gate, int64_t mod_stride, const int32_t* sel, int dtype, void* c2,
+                                 int64_t ldc2, int64_t n_split, int tile_m, void* stream) {
+    return gemm_impl(a, w, bias, c, m, n, k, lda, ldw, ldc, epilogue, r, ldr, gate, mod_stride, sel, dtype, c2, ldc2, n_split,
+                     nullptr, 0, tile_m, stream);
+}
+
+extern "C" int fino_gemm_keep(const void* a, const void* w, const void* bias, void* c, int64_t m, int64_t n, int64_t k,
+                              int64_t lda, int64_t ldw, int64_t ldc, int epilogue, const void* r, int64_t ldr,
+                              const float* gate, int64_t mod_stride, const int32_t* sel, int dtype, void* keep, int64_t ldk,
+                              int tile_m, void* stream) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_gemm_keep: dtype %d", dtype);
+    FINO_CHECK(epilogue == FINO_EPI_RESIDUAL || epilogue == FINO_EPI_GATED_RESIDUAL ||
+                   epilogue == FINO_EPI_GATED_RESIDUAL_STAGED,
+               FINO_ERR_ARG, "fino_gemm_keep: epilogue %d (the residual epilogues %d, %d and %d keep y)", epilogue,
+               FINO_EPI_RESIDUAL, FINO_EPI_GATED_RESIDUAL, FINO_EPI_GATED_RESIDUAL_STAGED);
+    FINO_CHECK(keep && fino_aligned16(keep) && ldk % 8 == 0 && ldk >= n, FINO_ERR_ARG,
+               "fino_gemm_keep: needs a 16-byte aligned keep buffer with ldk >= N a multiple of 8");
+    return gemm_impl(a, w, bias, c, m, n, k, lda, ldw, ldc, epilogue, r, ldr, gate, mod_stride, sel, dtype, nullptr, 0, 0,
+                     keep, ldk, tile_m, stream);
 }
 
 extern "C" int fino_gemm_blocked_a(const void* a, const void* w, const void* bias, void* c, int64_t m, int64_t n, int64_t k,

@@ -33,7 +33,9 @@ struct GemmParams {
     int tiles_m, tiles_n;
     int group_m;                     // tile rows per raster group (tile_coords); 0 = default
     // column split of the output (fino_gemm_split_n): tile columns at n0 >= n_split go to c2 (leading dimension ldc2,
-    // column n_split = its column 0); n_split is a multiple of BN, 0 = one output
+    // column n_split = its column 0); n_split is a multiple of BN, 0 = one output.
+    // The KEEP epilogues (fino_gemm_keep) use the same two fields with n_split = 0: c2 / ldc2 are the keep buffer, which
+    // receives y = T(acc + bias) of EVERY tile beside the residual result in c.
     uint16_t* c2;
     int64_t ldc2, n_split;
     // K-blocked A (fino_gemm_blocked_a; the ABLK kernels): columns [j * 64 a_tpb, (j + 1) * 64 a_tpb) of a row live at
@@ -203,7 +205,10 @@ __device__ __forceinline__ void gemm_epilogue_f32(f32x4_t (&acc)[MI][4], const G
     }
 }
 
-template <typename T, int EPI, bool QOUT, int MI>
+// KEEP (residual epilogues only; fino_gemm_keep): the staged y = T(acc + bias) also leaves as it is -- the same 16-byte row
+// chunks, before the residual / gate arithmetic -- to p.c2 (leading dimension p.ldc2).  A template flag: the instantiations
+// without it are the code they were.
+template <typename T, int EPI, bool QOUT, int MI, bool KEEP = false>
 __device__ __forceinline__ void gemm_epilogue_t(f32x4_t (&acc)[MI][4], const GemmParams& p, char* smem, int64_t m0,
                                                 int64_t n0, int tid, int lane, int wm, int wn) {
     // ---- epilogue: y = T(acc + bias) [-> gelu] -> LDS tile -> whole-row global stores ----
@@ -281,6 +286,7 @@ __device__ __forceinline__ void gemm_epilogue_t(f32x4_t (&acc)[MI][4], const Gem
         const int64_t gm = m0 + row, gn = n0 + ch * 8;
         if (gm >= p.m || gn >= p.n) continue;
         uint4 yv = *reinterpret_cast<const uint4*>(smem + row * kCsStride + ch * 16);
+        if constexpr (KEEP) *reinterpret_cast<uint4*>(p.c2 + gm * p.ldc2 + gn) = yv;
         if (kHasRes) {
             float y[8], rv[8], o[8];
             unpack8<T>(yv, y);
@@ -329,13 +335,13 @@ __device__ __forceinline__ void gemm_epilogue_t(f32x4_t (&acc)[MI][4], const Gem
 #endif
 }
 
-template <typename T, int EPI, bool QOUT = false, int MI = 8>
+template <typename T, int EPI, bool QOUT = false, int MI = 8, bool KEEP = false>
 __device__ __forceinline__ void gemm_epilogue(f32x4_t (&acc)[MI][4], const GemmParams& p, char* smem, int64_t m0,
                                               int64_t n0, int tid, int lane, int wm, int wn) {
     if constexpr (EPI == FINO_EPI_F32 || EPI == FINO_EPI_F32_RESIDUAL)
         gemm_epilogue_f32<EPI, MI>(acc, p, m0, n0, lane, wm, wn);
     else
-        gemm_epilogue_t<T, EPI, QOUT, MI>(acc, p, smem, m0, n0, tid, lane, wm, wn);
+        gemm_epilogue_t<T, EPI, QOUT, MI, KEEP>(acc, p, smem, m0, n0, tid, lane, wm, wn);
 }
 
 // ================= host side shared by the MX GEMMs (fino_gemm_fp8.hip, fino_gemm_fp6.hip) =================

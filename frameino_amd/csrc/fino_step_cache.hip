@@ -12,6 +12,12 @@
 // fino_step_cache_residual: out = T(a - b) or T(a + b) -- bit-exact to torch's `a - b` / `a + b` in T (one fp32 operation,
 // one rounding).
 //
+// fino_pab_broadcast (Pyramid Attention Broadcast): out = T(fma(float(y), gate[sel[row]], float(x))), or T(x + y) without a
+// gate -- the arithmetic of the GEMM's FINO_EPI_GATED_RESIDUAL / FINO_EPI_RESIDUAL epilogue on a cached y = T(acc + bias).
+// That epilogue compiles to ONE fused multiply-add per element (v_pk_fma_f32 / v_fmac_f32: fino_gemm.hip is built with the
+// compiler's default contraction), so the fma is spelled out here: a step that re-uses y gives the bits of the step that
+// computed it.  (fino_gated_residual multiplies and adds with two roundings.)
+//
 // HBM-bound: 16-byte loads and stores, fp32 arithmetic, no contraction (the file is built with -ffp-contract=off).
 #include "fino_common.h"
 
@@ -156,6 +162,31 @@ __global__ __launch_bounds__(kThreads) void residual_kernel(const void* a, int64
     }
 }
 
+template <typename T>
+__global__ __launch_bounds__(kThreads) void pab_broadcast_kernel(const void* x, int64_t ldx, const void* y, int64_t ldy, void* out,
+                                                                 int64_t ldo, uint32_t vpr, uint32_t nvec, const float* gate,
+                                                                 int64_t mod_stride, const int32_t* sel) {
+    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < nvec; i += gridDim.x * kThreads) {
+        const int64_t row = i / vpr;
+        const uint32_t col = (i % vpr) * 8;
+        float fx[8], fy[8], fo[8];
+        unpack8<T>(*at(x, row, ldx, col, 2), fx);
+        unpack8<T>(*at(y, row, ldy, col, 2), fy);
+        if (gate) {
+            const float* g = gate + (sel ? (int64_t)sel[row] * mod_stride : 0) + col;
+            const float4 g0 = *reinterpret_cast<const float4*>(g);
+            const float4 g1 = *reinterpret_cast<const float4*>(g + 4);
+            const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) fo[e] = __builtin_fmaf(fy[e], gg[e], fx[e]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) fo[e] = fx[e] + fy[e];
+        }
+        *(uint4*)at(out, row, ldo, col, 2) = pack8<T>(fo);
+    }
+}
+
 int esize_of(int dtype) { return dtype == FINO_F32 ? 4 : 2; }
 
 bool rows_ok(const void* p, int64_t ld, int dtype) {
@@ -227,6 +258,30 @@ extern "C" int fino_step_cache_residual(const void* a, int64_t lda, const void* 
         residual_kernel<F16><<<(int)grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
     else
         residual_kernel<F32><<<(int)grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
+}
+
+extern "C" int fino_pab_broadcast(const void* x, int64_t ldx, const void* y, int64_t ldy, void* out, int64_t ldo, int64_t rows,
+                                  int64_t dim, const float* gate, int64_t mod_stride, const int32_t* sel, int dtype,
+                                  void* stream) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_pab_broadcast: dtype %d", dtype);
+    FINO_CHECK(rows >= 0 && dim > 0 && dim % 8 == 0 && rows * (dim / 8) < (1LL << 31), FINO_ERR_ARG,
+               "fino_pab_broadcast: rows=%lld dim=%lld", (long long)rows, (long long)dim);
+    FINO_CHECK(x && y && out, FINO_ERR_ARG, "fino_pab_broadcast: null pointer");
+    FINO_CHECK(ldx >= dim && ldy >= dim && ldo >= dim, FINO_ERR_ARG, "fino_pab_broadcast: a row stride is below dim");
+    FINO_CHECK(rows_ok(x, ldx, dtype) && rows_ok(y, ldy, dtype) && rows_ok(out, ldo, dtype) &&
+                   (!gate || (fino_aligned16(gate) && mod_stride % 4 == 0)),
+               FINO_ERR_ARG, "fino_pab_broadcast: 16-byte alignment required");
+    if (rows == 0) return FINO_OK;
+    const uint32_t vpr = (uint32_t)(dim / 8), nvec = (uint32_t)(rows * vpr);
+    int64_t grid = (nvec + kThreads - 1) / kThreads;
+    if (grid > 256 * 8) grid = 256 * 8;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == FINO_BF16)
+        pab_broadcast_kernel<BF16><<<(int)grid, kThreads, 0, st>>>(x, ldx, y, ldy, out, ldo, vpr, nvec, gate, mod_stride, sel);
+    else
+        pab_broadcast_kernel<F16><<<(int)grid, kThreads, 0, st>>>(x, ldx, y, ldy, out, ldo, vpr, nvec, gate, mod_stride, sel);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }

@@ -78,21 +78,31 @@ class MXLinearsMixin:
 
     def _lin(self, li, key, x, w, b, epi=0, xq=None, **kw):
         """one of a block's large linears: MX when enabled (and K is a multiple of 128), else the model-dtype GEMM.
-        xq: the activations already quantised (_ln_q); MXFP6 quantises `x` itself"""
+        xq: the activations already quantised (_ln_q); MXFP6 quantises `x` itself.
+        keep (residual epilogues): a [rows, N] buffer that also receives y = T(acc + bias), the linear's own output"""
         wq = self._fp8.get((li, key)) if self._fp8 else None
         o = self.ops
+        keep = kw.pop("keep", None)
         if wq is None and self._fp8 and key in ("kv", "q"):
             # token shards project K|V and Q separately: quantise those row blocks of the fused weight on first use
             # (MX scales are per output row, so this equals slicing the quantised fused weight)
             wq = self._fp8[(li, key)] = self._mx_quantize()(w.detach().contiguous())
         if wq is None:
+            if keep is not None:
+                kw["keep"] = keep                               # the GEMM's epilogue keeps y beside the residual result
             return o.gemm(x, w, b, epi, **kw)
         kw.pop("tile_m", None)                                  # (the MX GEMMs have one tile height)
         if self._mx_fmt == 6:
-            xq, xs = o.quantize_mxfp6(x)
-            return o.gemm_mxfp6(xq, xs, wq[0], wq[1], b, epi, **kw)
-        xq, xs = xq if xq is not None else o.quantize_mxfp8(x)
-        return o.gemm_mxfp8(xq, xs, wq[0], wq[1], b, epi, **kw)
+            mx_gemm, (xq, xs) = o.gemm_mxfp6, o.quantize_mxfp6(x)
+        else:
+            mx_gemm, (xq, xs) = o.gemm_mxfp8, (xq if xq is not None else o.quantize_mxfp8(x))
+        if keep is None:
+            return mx_gemm(xq, xs, wq[0], wq[1], b, epi, **kw)
+        # keep on an MX linear: two launches -- y = T(acc + bias) into the keep buffer, then the (gated) residual from it
+        if epi not in (o.EPI_RESIDUAL, o.EPI_GATED_RESIDUAL):
+            raise NotImplementedError(f"_lin(keep=...): epilogue {epi}")
+        mx_gemm(xq, xs, wq[0], wq[1], b, o.EPI_NONE, out=keep)
+        return o.pab_broadcast(kw["residual"], keep, kw.get("gate"), kw.get("sel"), out=kw["out"])
 
     def _ffn_mxfp8(self, li, x, xq, b1, b2, epi, **kw):
         """The FFN of block `li` as one MXFP8 pair: the up-projection's GELU epilogue emits the hidden activations already

@@ -452,12 +452,15 @@ def gemm_plan(m, n):
     return r.value, t.value
 
 
-def gemm(a, w, bias=None, epilogue=EPI_NONE, residual=None, gate=None, sel=None, out=None, out2=None, split=0, tile_m=0):
+def gemm(a, w, bias=None, epilogue=EPI_NONE, residual=None, gate=None, sel=None, out=None, out2=None, split=0, tile_m=0,
+         keep=None):
     """C = epilogue(A.W^T + bias).  a [M, K] row-strided, w [N, K] (nn.Linear weight).
     `out2`, `split`: columns [split, N) of the product go to out2 [M, N - split], columns [0, split) to out [M, split]
     (fino_gemm_split_n: the fused q | k | v projection of a token shard, k | v landing in the all-gather's send buffer).
     `tile_m`: this call's tile height (0 = planned, 8 = 256-row tiles only, 2 .. 7 = 32 x tile_m rows); results do not
-    depend on it."""
+    depend on it.
+    `keep` [M, N] row-strided (residual epilogues only; fino_gemm_keep): also receives y = T(A.W^T + bias), the value before
+    the gate multiply and the residual add -- what EPI_NONE would return; `out` is what the call without it returns."""
     a2, m, k, lda = _rows2d(a)
     assert w.dim() == 2 and w.stride(1) == 1 and w.shape[1] == k and w.dtype == a.dtype
     n = w.shape[0]
@@ -465,6 +468,8 @@ def gemm(a, w, bias=None, epilogue=EPI_NONE, residual=None, gate=None, sel=None,
         out = torch.empty((m, split or n), dtype=a.dtype, device=a.device)
     o2, _, _, ldc = _rows2d(out)
     if out2 is not None:
+        if keep is not None:
+            raise ValueError("gemm: keep= goes with a residual epilogue, out2= / split= with none: they do not combine")
         assert 0 < split < n and residual is None
         c2, _, _, ldc2 = _rows2d(out2)
         done = _timed_gemm(None, 2.0 * m * n * k)
@@ -479,7 +484,13 @@ def gemm(a, w, bias=None, epilogue=EPI_NONE, residual=None, gate=None, sel=None,
         assert bias.dtype == a.dtype and bias.is_contiguous()
     # algorithmic bytes: A [M, K] and W [N, K] read, C [M, N] written (+ the residual read), 2 bytes per element
     done = _timed_gemm(epilogue, 2.0 * m * n * k, 2.0 * (m * k + n * k + m * n * (2 if residual is not None else 1)))
-    if tile_m:
+    if keep is not None:
+        k2, km, kn, ldk = _rows2d(keep)
+        assert (km, kn) == (m, n) and keep.dtype == a.dtype and keep.is_cuda
+        _lib.check(_lib.lib().fino_gemm_keep(_p(a2), _p(w), _p(bias), _p(o2), m, n, k, lda, w.stride(0), ldc, epilogue,
+                                            _p(r2), ldr, _p(gate), ms, _p(sel), _dt(a), _p(k2), ldk, tile_m, _stream()),
+                   "fino_gemm_keep")
+    elif tile_m:
         _lib.check(_lib.lib().fino_gemm_split_n(_p(a2), _p(w), _p(bias), _p(o2), m, n, k, lda, w.stride(0), ldc, epilogue,
                                                _p(r2), ldr, _p(gate), ms, _p(sel), _dt(a), None, 0, 0, tile_m, _stream()),
                    "fino_gemm_split_n")
@@ -1039,4 +1050,22 @@ def step_cache_residual(a, b, out=None, subtract=True):
     rows, d = a.shape
     _lib.check(_lib.lib().fino_step_cache_residual(_p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), rows, d,
                                                    int(bool(subtract)), _dt3(a), _stream()), "fino_step_cache_residual")
+    return out
+
+
+def pab_broadcast(x, y, gate=None, sel=None, out=None):
+    """out = T(fma(float(y), gate[sel], float(x))) (gate None: T(x + y)): the gated-residual epilogue of `gemm` applied to a
+    cached y, bit for bit what the GEMM that produced y wrote (fino_pab_broadcast; `gated_residual` rounds y * gate first).
+    Row-strided [rows, D] bf16 / fp16; out may alias x."""
+    _rows_of(x, x.dtype, "pab_broadcast x")
+    _rows_of(y, x.dtype, "pab_broadcast y")
+    out = torch.empty_like(x) if out is None else _rows_of(out, x.dtype, "pab_broadcast out")
+    if x.shape != y.shape or out.shape != x.shape:
+        raise ValueError(f"pab_broadcast: shapes {tuple(x.shape)} / {tuple(y.shape)} / {tuple(out.shape)}")
+    if gate is not None:
+        assert gate.dtype == torch.float32 and gate.stride(-1) == 1 and gate.shape[-1] == x.shape[1]
+    rows, d = x.shape
+    ms = gate.stride(0) if (gate is not None and gate.dim() == 2) else 0
+    _lib.check(_lib.lib().fino_pab_broadcast(_p(x), x.stride(0), _p(y), y.stride(0), _p(out), out.stride(0), rows, d, _p(gate),
+                                             ms, _p(sel), _dt(x), _stream()), "fino_pab_broadcast")
     return out

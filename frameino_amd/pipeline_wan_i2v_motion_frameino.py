@@ -22,6 +22,11 @@ frameino_amd/step_cache.py) the loop runs eagerly: every step decides on the hos
 other blocks run.  The cache state starts fresh in every `denoise` and is dropped by `maybe_free_model_hooks()` at the end of
 `__call__`; `transformer.cache_log` keeps the call's decisions.  One sample, one GPU (a batch or a parallel plan with the cache
 raises NotImplementedError).
+
+Pyramid Attention Broadcast (`enable_cache(PyramidAttentionBroadcastConfig(spatial_attention_block_skip_range=2,
+current_timestep_callback=lambda: pipe.current_timestep))`) takes the same eager loop, one GPU, fresh state per `denoise`.  Its
+decisions depend on the step counter and the timestep only, so a batch is allowed: the samples run one at a time, each from
+fresh state, and decide as a joint run would.  Replaying its host-known schedule from captured graphs is not built.
 """
 import html
 import re
@@ -157,15 +162,23 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
             reset()
 
     def _step_cache_check(self, batch):
-        """the first-block cache's limits, checked before any work (and before any collective: a parallel plan and the cache
-        are configured by the same script on every rank, so every rank raises)"""
+        """the limits of the step caches (first-block caching, Pyramid Attention Broadcast), checked before any work (and before
+        any collective: a parallel plan and the cache are configured by the same script on every rank, so every rank raises)"""
         if not getattr(self.transformer, "is_cache_enabled", False):
             return False
+        pab = bool(getattr(self.transformer, "_pab_on", False))
+        what = "Pyramid Attention Broadcast" if pab else "first-block caching"
         if getattr(self, "parallel", None) is not None:
-            raise NotImplementedError("first-block caching runs on one GPU; this pipeline has a parallel plan")
-        if batch > 1:
+            raise NotImplementedError(f"{what} runs on one GPU; this pipeline has a parallel plan")
+        if batch > 1 and not pab:
+            # (Pyramid Attention Broadcast decides from the step counter and the timestep alone: the samples of a batch, run
+            # one at a time from fresh state, decide as diffusers' joint run does)
             raise NotImplementedError("first-block caching with a batch (a list of prompts, num_videos_per_prompt > 1): diffusers "
                                       "decides jointly over the batch, this pipeline runs the samples one at a time")
+        if self.use_hip_graph is True and pab:
+            raise RuntimeError("use_hip_graph=True with Pyramid Attention Broadcast: which attention branches a step runs "
+                               "changes from step to step on the host's schedule, which one captured step cannot contain (the "
+                               "loop runs eagerly; use_hip_graph=None or False)")
         if self.use_hip_graph is True:
             raise RuntimeError("use_hip_graph=True with first-block caching: every step decides on the host between block 0 and "
                                "block 1 whether the other blocks run, which one captured step cannot contain (the loop runs "
@@ -472,7 +485,8 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         """reference :809-913.  Returns the final latents [B, C, F, h, w] fp32.  The loop state is one sample's (the app
         and the evaluation scripts run batch 1); a batch -- a list of prompts, num_videos_per_prompt > 1 -- runs sample by sample:
         the samples of the reference's batched loop never meet, every one sees the noise row `prepare_latents` drew for it.
-        With first-block caching every call starts from fresh cache state."""
+        With a step cache (first-block caching, Pyramid Attention Broadcast) every call -- every sample -- starts from fresh
+        cache state."""
         cached = self._step_cache_check(latents.shape[0])
         if cached:
             self.transformer._reset_stateful_cache()

@@ -14,7 +14,9 @@ What is different by design (results identical):
   * Q/K/V are one fused GEMM; norm+RoPE run in place on the fused buffer; attention reads it in place;
     bias / GELU / gated-residual are GEMM epilogues.
 `enable_cache(FirstBlockCacheConfig(...))` (diffusers' CacheMixin, reference :28, :353) skips blocks 1 .. N-1 of a step whose
-first-block residual barely changed (frameino_amd/step_cache.py); off by default.
+first-block residual barely changed; `enable_cache(PyramidAttentionBroadcastConfig(...))` re-uses the self- and / or
+cross-attention branch outputs of the previous step on a schedule of the step counter and the timestep
+(frameino_amd/step_cache.py).  One at a time, both off by default.
 """
 import contextlib
 import math
@@ -402,6 +404,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             kv = self.ops.gemm(txt, e.wkv2, e.bkv2)                                     # [Lt, 2D]
             self.ops.rmsnorm_rope_(kv[:, :d], blk.attn2.norm_k.weight, blk.attn2.norm_k.eps)
             kvs.append(kv)
+        # (a field added to this namespace, here or in `_text_out_weights`, needs its one-sample view in `_text_element` below:
+        # Pyramid Attention Broadcast runs a batch's attention branches on it)
         val = SimpleNamespace(txt=txt, kv=kvs, lt=kept.shape[1], tail=None if tail is None else (tail[1], tail[2]), w2=None)
         # P.(V W_o^T) pays only while its K = heads x keys stays well under D (K = 1728 / 384 at 64 / 8 prompt tokens against
         # 3072): from ~77 kept keys on (24 heads) it costs the FLOPs it saves, plus the rrms / probabilities passes, a GEMM per
@@ -430,9 +434,11 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self-attention as keys and values: their q projection's use, attention queries, out-projection, text branch, FFN and
         output head are skipped, and their part of the returned tensor is ZERO.  Every kept row is computed exactly as without it.
         A bare `transformer(...)` call (None) keeps the full output.
-        `_cache_contexts` (private; first-block cache enabled): one cache-context name per batch element, each element then
-        decided on its own as if called alone under that context -- the pipeline's CFG-batched call passes ("cond", "uncond").
-        Without it a batch-B call under one `cache_context` makes one joint decision, as diffusers does."""
+        `_cache_contexts` (private; a step cache enabled -- first-block caching or Pyramid Attention Broadcast): one
+        cache-context name per batch element, each element then decided on its own as if called alone under that context -- the
+        pipeline's CFG-batched call passes ("cond", "uncond").  Without it a batch-B call under one `cache_context` makes one
+        joint decision, as diffusers does (first-block caching: over the means of all its rows; Pyramid Attention Broadcast:
+        one counter and one [B * L, D] buffer per layer and kind for the whole batch)."""
         gen = self.forward_steps(hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image,
                                  return_dict, attention_kwargs, timestep_rows, live_rows=live_rows,
                                  _cache_contexts=_cache_contexts)
@@ -468,9 +474,12 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             m = c.mod[:, li]                                                      # [R, 6, D] view, row stride = layers*6*D
             if c.live is not None and li == last:
                 c.rows, c.segs = c.live, c.live_segs                              # dead rows: keys and values only
-            if not self._self_attention(c, li, blk, e, m):                        # 1. self-attention (:334-336)
-                self._self_attention_out(c, li, blk, m)
-            self._cross_attention(c, li, blk)                                     # 2. cross-attention (:339-341)
+            if c.pab is not None:
+                self._pab_attention(c, li, blk, e, m)                             # 1. + 2., each computed or re-used
+            else:
+                if not self._self_attention(c, li, blk, e, m):                    # 1. self-attention (:334-336)
+                    self._self_attention_out(c, li, blk, m)
+                self._cross_attention(c, li, blk)                                 # 2. cross-attention (:339-341)
             self._ffn(c, li, blk, m)                                              # 3. feed-forward (:344-348)
             if c.fbc is not None and li == 0:
                 computes = self._step_cache_probe(c.fbc, c.h0, c.x, c.h1c)        # one host read: the rule's decision
@@ -541,10 +550,13 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             lo, n, lpad = sh.rows(L)              # first row, valid rows, padded shard length (equal on all ranks)
             cos1, sin1 = cos1[lo:lo + n].contiguous(), sin1[lo:lo + n].contiguous()
             if self.is_cache_enabled:
-                raise NotImplementedError("first-block caching runs on one GPU: a token-sharded forward cannot take the cache")
+                raise NotImplementedError("first-block caching and Pyramid Attention Broadcast run on one GPU: a token-sharded "
+                                          "forward cannot take the cache")
             if sh.gemm_tile_m:
                 tk = {"tile_m": sh.tile_m_for(n)}
         fbc = self._step_cache_segments(b, n, cache_contexts)      # None: no cache (nothing extra allocated or launched)
+        # Pyramid Attention Broadcast: this forward's decisions (the timestep callback is read here, once, before any launch)
+        pab = self._pab_begin(b, n, d, dt, dev, cache_contexts)
         # Batch elements are extra ROWS of the token-major buffers ([B*n, D]): every GEMM / norm is one launch over
         # both CFG branches (twice the tiles per launch, weights read once); attention and RoPE index rows per batch.
         nr = b * n
@@ -567,8 +579,9 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         # the same timestep rows: everything up to the first text cross-attention is identical for them, so the patch
         # embedding and layer 0's self-attention branch run once and their result is copied (exactly what each element
         # would have computed).  A per-sample timestep ([b] or [b, L] values) takes the general path.
+        # (Pyramid Attention Broadcast keeps one cache per context and layer: every element runs block 0's branch itself)
         shared = (self.dedup_shared_prefix and b > 1 and sh is None and hidden_states.stride(0) == 0 and default_procs
-                  and same_rows)
+                  and same_rows and pab is None)
         fold = self.fold_softmax_scale
         attend = o.attention
         if self.fp8_attention and sh is None and hasattr(o, "attention_fp8"):
@@ -576,17 +589,21 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                 return o.attention_fp8(q_, k_, v_, heads_, p_mode=getattr(self, "fp8_p_mode", None), **kw_)
         # rows whose output the caller reads (`live_rows`): honoured in the last block on the single-GPU default-processor path
         live = None
+        # (not under Pyramid Attention Broadcast: a cached branch output covers every row, so that any later step may use it)
         if (live_rows is not None and self.skip_dead_rows and default_procs and sh is None and len(self.blocks) > 1
-                and not self._fp8 and attend is o.attention):
+                and not self._fp8 and attend is o.attention and pab is None):
             l0, l1 = int(live_rows[0]), int(live_rows[1])
             if 0 <= l0 < l1 <= n and (l1 - l0) < n:
                 live = (l0, l1)
+        # (a per-row or per-batch field added here needs its one-element view in `_Call.element`: Pyramid Attention Broadcast
+        # runs a batch's attention branches through it)
         return _Call(b=b, n=n, nr=nr, lo=lo, lpad=lpad, L=L, nf=nf, hh=hh, ww=ww, d=d, heads=heads, dh=dh, dev=dev, dt=dt,
                      eps=cfg.eps, sh=sh, tk=tk, pk=pk, ws=ws, x=ws.x[:nr], nrm=ws.n[:nr], att=ws.att[:nr], q2=ws.q2[:nr],
                      ff=ws.ff[:nr], qkv=ws.qkv[:nr], cos=cos, sin=sin, cos1=cos1, sin1=sin1, sel=sel, mod=mod, head=head,
                      text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
                      afold={"scale": o.SCALE_FOLDED} if fold else {}, attend=attend, default_procs=default_procs,
-                     shared=shared, fbc=fbc, h0=None, h1c=None, attention_kwargs=attention_kwargs, live=live,
+                     shared=shared, fbc=fbc, pab=pab, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
+                     live=live,
                      live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
                      rows=(0, n),            # the rows of every batch element that run as queries / per-token rows ...
                      segs=[(0, nr)])         # ... and the global row ranges the per-token operations of a block run on
@@ -636,6 +653,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         o = self.ops
         o.adaln_modulate(c.x, m[:, 0], m[:, 1], c.sel, c.eps, out=c.nrm)
         a = blk.attn1(c.nrm.view(c.b, c.n, c.d), rotary_emb=_CompactRope((c.cos1, c.sin1)), **(c.attention_kwargs or {}))
+        _keep_copy(c, a.reshape(c.nr, c.d))
         o.gated_residual(c.x, a.reshape(c.nr, c.d), m[:, 2], c.sel, out=c.x)
         return True
 
@@ -778,7 +796,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         to_out = blk.attn1.to_out[0]
         for r0, r1 in c.segs:
             self._lin(li, "out", c.att[r0:r1], to_out.weight, to_out.bias, self.ops.EPI_GATED_RESIDUAL, residual=c.x[r0:r1],
-                      gate=m[:, 2], sel=_sel_rows(c.sel, r0, r1), out=c.x[r0:r1], **c.tk)
+                      gate=m[:, 2], sel=_sel_rows(c.sel, r0, r1), out=c.x[r0:r1], **c.tk, **_keep_kw(c, r0, r1))
 
     def _cross_attention(self, c, li, blk):
         """text cross-attention (:339-341): text K/V are replicated, nothing to exchange"""
@@ -793,6 +811,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             nrm.copy_(x)
         if not c.default_procs:
             a = a2(nrm.view(b, n, d), encoder_hidden_states=text.txt.view(b, text.lt, d), **(c.attention_kwargs or {}))
+            _keep_copy(c, a.reshape(c.nr, d))
             o.gated_residual(x, a.reshape(c.nr, d), out=x)
             return
         for r0, r1 in segs:
@@ -811,7 +830,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                                        text.tail[1][i:i + 1], text.kp[i], out=text.pbuf[i][:s1 - s0].view(1, s1 - s0, -1),
                                        q_rrms=rr[r0:r1].view(1, s1 - s0), q_weight=a2.norm_q.weight)
                 xi = x[r0:r1]
-                o.gemm(pr.view(s1 - s0, -1), text.w2[li][i], a2.to_out[0].bias, o.EPI_RESIDUAL, residual=xi, out=xi, **c.tk)
+                o.gemm(pr.view(s1 - s0, -1), text.w2[li][i], a2.to_out[0].bias, o.EPI_RESIDUAL, residual=xi, out=xi, **c.tk,
+                       **_keep_kw(c, r0, r1))
             return
         for r0, r1 in segs:
             o.rmsnorm_rope_(q2[r0:r1], a2.norm_q.weight, a2.norm_q.eps)
@@ -822,7 +842,47 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             o.attention(qv, kv[:, :, :d], kv[:, :, d:], heads, out=av)
         for r0, r1 in segs:
             self._lin(li, "out2", att[r0:r1], a2.to_out[0].weight, a2.to_out[0].bias, o.EPI_RESIDUAL, residual=x[r0:r1],
-                      out=x[r0:r1], **c.tk)
+                      out=x[r0:r1], **c.tk, **_keep_kw(c, r0, r1))
+
+    # ------------------------------------------------------------------ forward: Pyramid Attention Broadcast
+    def _pab_attention(self, c, li, blk, e, m):
+        """Block li's two attention branches under Pyramid Attention Broadcast (`c.pab`: this forward's decisions per row
+        segment = batch element and kind, frameino_amd/step_cache.py).
+        Compute: the launches of `_self_attention` / `_self_attention_out` / `_cross_attention`, the closing GEMM with `keep=`
+        into the segment's buffer of this layer (`c.keep`; a custom processor's return value is copied there).
+        Re-use: none of the branch runs; one launch adds the cached y to the residual stream with the closing GEMM's epilogue
+        arithmetic (`_pab_reuse`).  A kind that is not hooked runs as without the cache.  The elements of a batch (the CFG
+        branches of a batched call: one context and one buffer each, and counters that may differ) take a hooked branch one
+        by one, each on a one-element view of the call: per row the launches compute what the batched ones do."""
+        pab, n = c.pab, c.n
+        stages = (("self", lambda cc: self._self_attention(cc, li, blk, e, m) or self._self_attention_out(cc, li, blk, m)),
+                  ("cross", lambda cc: self._cross_attention(cc, li, blk)))
+        for kind, run in stages:
+            if not pab.hooked[kind]:
+                run(c)
+                continue
+            for i in range(c.b):
+                # the segment element i's rows lie in: its own (one context per element), or the joint one of a batch under one
+                # context -- one decision, one [b * n, D] buffer, of which the element takes its rows
+                seg = next(s_ for s_ in pab.segs if s_.r0 <= i * n < s_.r1)
+                if not seg.compute[kind]:
+                    self._pab_reuse(c, kind, seg, i, li, m)
+                    continue
+                cc = c if c.b == 1 else c.element(i)
+                cc.keep = {(0, n): self._pab_buffer(seg, kind, li, c.d, c.dt, c.dev)[i * n - seg.r0:(i + 1) * n - seg.r0]}
+                try:
+                    run(cc)
+                finally:
+                    cc.keep = None
+
+    def _pab_reuse(self, c, kind, seg, i, li, m):
+        """x += gate * y (self-attention) / x += y (cross-attention) on batch element i from the cached y, bit for bit what
+        the step that computed y wrote: the fused epilogues multiply-add once (`ops.pab_broadcast`), a custom processor's
+        result went through `ops.gated_residual`."""
+        o, r0, r1 = self.ops, i * c.n, (i + 1) * c.n
+        y, x = self._pab_buffer(seg, kind, li)[r0 - seg.r0:r1 - seg.r0], c.x[r0:r1]
+        gate, sel = (m[:, 2], _sel_rows(c.sel, r0, r1)) if kind == "self" else (None, None)
+        (o.pab_broadcast if c.default_procs else o.gated_residual)(x, y, gate, sel, out=x)
 
     def _ffn(self, c, li, blk, m):
         """feed-forward (:344-348)"""
@@ -865,21 +925,62 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
 class _Call:
     """What the stages of one `WanTransformer3DModel.forward_steps` call share (built by `_bind` at the first `next()`): sizes,
     the token shard, views of the workspace, tables and the switches that pick a path.  References and views only: nothing on
-    the device the call would not hold anyway.  `rows` / `segs` (set for the last block under `live_rows`) and `h0` / `h1c`
-    (the first-block cache's buffers, set by the embedding stage) are the only fields written after `_bind`."""
+    the device the call would not hold anyway.  `rows` / `segs` (set for the last block under `live_rows`), `h0` / `h1c`
+    (the first-block cache's buffers, set by the embedding stage) and `keep` around a branch that Pyramid Attention
+    Broadcast computes ({(first row, end row): the buffer that also receives the closing GEMM's y}; `elements`: the one-element
+    views it runs a batch through) are the only fields written after `_bind`."""
     __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
                  "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
-                 "afold", "attend", "default_procs", "shared", "fbc", "h0", "h1c", "attention_kwargs", "live", "live_segs",
-                 "rows", "segs")
+                 "afold", "attend", "default_procs", "shared", "fbc", "pab", "keep", "h0", "h1c", "attention_kwargs", "live",
+                 "live_segs", "rows", "segs", "elements")
 
     def __init__(self, **fields):
+        self.elements = None
         for k, v in fields.items():
             setattr(self, k, v)
+
+    def element(self, i):
+        """the same call seen as batch element i alone: views of its n rows, its text, b = 1 (Pyramid Attention Broadcast runs
+        a hooked attention branch element by element); built once per call and element"""
+        if self.elements is None:
+            self.elements = {}
+        if i in self.elements:
+            return self.elements[i]
+        r0, r1 = i * self.n, (i + 1) * self.n
+        f = {k: getattr(self, k) for k in self.__slots__ if k != "elements"}
+        for k in ("x", "nrm", "att", "q2", "ff", "qkv"):
+            f[k] = f[k][r0:r1]
+        f.update(b=1, nr=self.n, cos=self.cos1, sin=self.sin1, sel=_sel_rows(self.sel, r0, r1), segs=[(0, self.n)],
+                 text=_text_element(self.text, i, self.b, self.n, self.d), keep=None)
+        self.elements[i] = _Call(**f)
+        return self.elements[i]
 
 
 def _sel_rows(sel, r0, r1):
     """rows [r0, r1) of the per-token modulation selector (None: every row takes table row 0)"""
     return None if sel is None else sel[r0:r1]
+
+
+def _keep_kw(c, r0, r1):
+    """`keep=` of the closing GEMM over rows [r0, r1) while Pyramid Attention Broadcast computes a branch, else nothing"""
+    return {} if c.keep is None else {"keep": c.keep[(r0, r1)]}
+
+
+def _keep_copy(c, y):
+    """a custom processor's return value y [rows, D] into the buffers Pyramid Attention Broadcast keeps it in"""
+    if c.keep is not None:
+        for (r0, r1), buf in c.keep.items():
+            buf.copy_(y[r0:r1])
+
+
+def _text_element(text, i, b, n, d):
+    """the text K / V (`_text_kv`) of batch element i alone"""
+    lt = text.lt
+    t = SimpleNamespace(txt=text.txt.view(b, lt, d)[i], kv=[kv.view(b, lt, 2 * d)[i] for kv in text.kv], lt=lt, w2=None,
+                        tail=None if text.tail is None else (text.tail[0][i:i + 1], text.tail[1][i:i + 1]))
+    if text.w2 is not None:
+        t.w2, t.kp, t.pbuf, t.rrms = [[w[i]] for w in text.w2], text.kp[i:i + 1], text.pbuf[i:i + 1], text.rrms[i * n:(i + 1) * n]
+    return t
 
 
 class _CompactRope(tuple):

@@ -271,6 +271,15 @@ int fino_gemm_split_n(const void* a, const void* w, const void* bias, void* c, i
                       int64_t ldw, int64_t ldc, int epilogue, const void* r, int64_t ldr, const float* gate,
                       int64_t mod_stride, const int32_t* sel, int dtype, void* c2, int64_t ldc2, int64_t n_split,
                       int tile_m, void* stream);
+/* fino_gemm with a residual epilogue (FINO_EPI_RESIDUAL, FINO_EPI_GATED_RESIDUAL, FINO_EPI_GATED_RESIDUAL_STAGED) that ALSO
+ * keeps y = T(acc + bias), the Linear's own output before the gate multiply and the residual add: keep[i * ldk + j] = y[i][j]
+ * (ldk >= N a multiple of 8, keep 16-byte aligned, disjoint from c and r), written by the epilogue's store loop from the
+ * staged tile it already holds.  c is what fino_gemm gives, bit for bit; keep is what FINO_EPI_NONE gives.  Pyramid
+ * Attention Broadcast (frameino_amd/step_cache.py) caches an attention branch's output this way on the steps that compute
+ * it.  bf16 | fp16, every tile height; another epilogue or dtype -> FINO_ERR_ARG. */
+int fino_gemm_keep(const void* a, const void* w, const void* bias, void* c, int64_t m, int64_t n, int64_t k, int64_t lda,
+                   int64_t ldw, int64_t ldc, int epilogue, const void* r, int64_t ldr, const float* gate,
+                   int64_t mod_stride, const int32_t* sel, int dtype, void* keep, int64_t ldk, int tile_m, void* stream);
 /* c = r + gate[sel] * (A w^T + bias) (FINO_EPI_GATED_RESIDUAL) with a K-BLOCKED A: K block b (columns [b * a_block_k,
  * (b + 1) * a_block_k) of row i; a_block_k a multiple of 64 dividing K), b = j * a_groups + g, lives at
  * a + g * a_group_stride + j * a_block_stride + i * lda (elements).  That is the layout in which the heads all-to-all
@@ -554,6 +563,16 @@ int fino_step_cache_probe(const FinoStepCacheSegment* segs, int nseg, int64_t di
                           void* stream);
 int fino_step_cache_residual(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int64_t rows,
                              int64_t dim, int subtract, int dtype, void* stream);
+/* Pyramid Attention Broadcast (diffusers' hooks/pyramid_attention_broadcast.py; frameino_amd/step_cache.py): a step that
+ * re-uses an attention branch adds the cached y = T(acc + bias) of its out-projection (kept by fino_gemm_keep) to the residual
+ * stream without running the branch:
+ *   out = T(fma(float(y), gate[sel[row]], float(x)))     gate as in fino_adaln_modulate (fp32 rows of mod_stride floats)
+ *   out = T(float(x) + float(y))                         gate == NULL
+ * ONE fused multiply-add and one rounding per element: the bits of fino_gemm's FINO_EPI_GATED_RESIDUAL / FINO_EPI_RESIDUAL
+ * epilogue on the same y (fino_gated_residual rounds the product first).  Row-strided [rows, dim], dim a multiple of 8,
+ * 16-byte aligned rows, bf16 | fp16; out may alias x. */
+int fino_pab_broadcast(const void* x, int64_t ldx, const void* y, int64_t ldy, void* out, int64_t ldo, int64_t rows,
+                       int64_t dim, const float* gate, int64_t mod_stride, const int32_t* sel, int dtype, void* stream);
 
 /* ---- diagnostics (tools/ only) --------------------------------------------------------------------------------
  * Dense MFMA rate with nothing else running: `iters` x 16 independent 32x32x16 (kind 0) / 32 independent 16x16x32
