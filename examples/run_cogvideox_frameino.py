@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--frame-out", action="store_true", help="the FrameOut evaluation: no identity reference")
     ap.add_argument("--mxfp8", action="store_true", help="MXFP8 linears (reduced precision, opt-in)")
     ap.add_argument("--fp8-attention", action="store_true", help="fp8 (e4m3) attention operands (reduced precision, opt-in)")
+    ap.add_argument("--smooth-k", action="store_true",
+                    help="with --fp8-attention: subtract the key mean before K is quantised (exact for the softmax)")
     ap.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16",
                     help="dtype of transformer, VAE and text encoder.  Default fp16 = what the evaluation script loads all three in "
                          "(test_code/run_cogvideox_FrameIn_mass_evaluation.py:92-94,106)")
@@ -119,7 +121,7 @@ def main():
     if a.mxfp8:
         transformer.enable_mxfp8_linears()
     if a.fp8_attention:
-        transformer.enable_fp8_attention()
+        transformer.enable_fp8_attention(smooth_k=a.smooth_k)
 
     t0 = time.perf_counter()
     image, traj, id_tensor, pads = synthetic_conditions(a.frames, a.height, a.width, dev, a.frame_out)
@@ -144,7 +146,7 @@ def main():
         frames = np.stack([np.asarray(f) for f in video])
         assert frames.shape == (a.frames, a.height, a.width, 3) and frames.dtype == np.uint8
         cond_s = f"conditions {tc - t0:.2f} s, " if rep == 0 else ""
-        mode = ("mxfp8 linears" if a.mxfp8 else f"{a.dtype} linears") + (" + fp8 attention" if a.fp8_attention else "")
+        mode = ("mxfp8 linears" if a.mxfp8 else f"{a.dtype} linears") + ((" + fp8 attention" + (" (smooth K)" if a.smooth_k else "")) if a.fp8_attention else "")
         print(f"{cond_s}clip ({a.frames} frames {a.height}x{a.width}, {a.steps} steps, {a.scheduler}, {mode}) {t2 - t1:.2f} s"
               f"{' (cold)' if rep == 0 and a.repeat > 1 else ''}, frames in [{frames.min()}, {frames.max()}], peak device memory "
               f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")

@@ -212,16 +212,20 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                            ("ff2", blk.ff.net[2].weight)):
                 yield li, key, w
 
-    def enable_fp8_attention(self, enabled=True, p_mode=None):
+    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False):
         """The joint text + video self-attention (attention_processor.py:2863 of the reference, head_dim 64: 55 % of the
         CogVideoX-5B step) with fp8 e4m3 matrix operands -- K / V quantised per call with one scale per 32 elements, Q and
         P in registers, both products on the block-scaled fp8 MFMA, fp32 softmax and accumulation
         (`fino_attn_fwd_fp8`).  With `enable_mxfp8_linears()` this is BASELINE config 5's "fp8 MFMA path" end to end.
         No reference counterpart: tolerance stated in tests/test_attention_fp8_gpu.py and
         tests/test_fullsize_oracle_gpu.py against fp32 and against this model's own bf16 forward.
-        p_mode: "exp2" | "ramp" -- how a softmax weight becomes its e4m3 byte (ops.FP8_P_*; None = ops.FP8_P_DEFAULT)."""
+        p_mode: "exp2" | "ramp" -- how a softmax weight becomes its e4m3 byte (ops.FP8_P_*; None = ops.FP8_P_DEFAULT).
+        smooth_k: subtract the per-(batch element, head, channel) mean of K over the keys before K is quantised
+        (fino_attn_fwd_fp8_smooth): invisible to the softmax, and a channel offset that all keys share (a to_k bias, norm_k
+        weights, low-frequency RoPE channels) stops taking the mantissa bits.  Off by default."""
         self.fp8_attention = bool(enabled)
         self.fp8_p_mode = p_mode
+        self.fp8_smooth_k = bool(smooth_k)
         return self
 
     def _default_processors(self):
@@ -382,7 +386,8 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                 ops.headnorm_rope_(qkv[:, :, d:2 * d], heads, dh, nk.weight, nk.bias, nk.eps, cos, sin, rope_row0=lt)
                 if self.fp8_attention and dh == 64:
                     att = ops.attention_fp8(qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads,
-                                            p_mode=getattr(self, "fp8_p_mode", None), **afold)
+                                            p_mode=getattr(self, "fp8_p_mode", None),
+                                            smooth_k=getattr(self, "fp8_smooth_k", False), **afold)
                 else:
                     att = ops.attention(qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads, **afold)
                 self._lin(li, "out", att.view(b * L, d), blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias,

@@ -14,6 +14,8 @@
 //     key slots] -- V already TRANSPOSED and its keys in the order the S^T accumulators hold them (register j of lane
 //     group g = key (j & 3) + 8 (j >> 2) + 4 g of each 32-key half), so P never moves between lanes and the V^T fragment
 //     is two ds_read_b128 (the bf16 kernels need eight ds_read_b64_tr_b16) -- + one scale per (channel, 32-key block).
+//     fino_attn_fwd_fp8_smooth (opt-in) subtracts the mean of K over the keys first: two small launches in front of the
+//     quantiser (attn_kmean_*), nothing behind it changes -- see QuantParamsT below, DESIGN.md section 6e.
 //   * Q (bf16 / fp16, already multiplied by softmax_scale * log2 e in fp32) is quantised in registers at block start.
 //   * P = exp2(s - m + 6) is rounded to e4m3 with a fixed block scale 2^-6: between rescales p <= 2^kThr, so P8 <= 2^8 <
 //     448, and what underflows (p < 2^-15 of the running maximum) carries no weight.  l sums the ROUNDED P on the matrix
@@ -135,10 +137,75 @@ struct QuantParams {
     int64_t k_bs, k_rs, k_hs, v_bs, v_rs, v_hs;
 };
 
+// SMOOTH (fino_attn_fwd_fp8_smooth): the quantiser also takes the per-(batch, head, channel) mean of K over the keys and
+// quantises K - mean.  q.(k_j - mu) = q.k_j - q.mu and q.mu is one constant per query row, which the softmax drops: exact in
+// real arithmetic, no correction term, and the three mantissa bits of a block describe what differs from key to key instead
+// of an offset all keys share.  The plain quantiser's parameters stay the struct they were (an empty derived class).
+template <bool SMOOTH> struct QuantParamsT : QuantParams {};
+template <> struct QuantParamsT<true> : QuantParams {
+    const float* mean;      // [batch][heads * 64]: heads = the 64-channel sub-heads, as k_hs = 64 walks them
+};
+
+// ---- the key mean: two launches, a fixed partition and a fixed order (no atomics: the same inputs give the same bits) ----
+// K of one batch element is a [lk][channels] matrix with row stride k_rs (channels = sub-heads x 64, contiguous).  Workgroup
+// (chunk, 64-channel group, batch element) sums kMeanRows keys: thread (r = tid >> 3, c8 = tid & 7) adds rows r, r + 32, ...
+// of its 8 channels (one 16-byte load per row), the 32 row slices meet in LDS and are added in the order r = 0 .. 31.
+constexpr int kMeanRows = 256;               // keys per partial: the partition depends on lk alone
+struct MeanParams {
+    const uint16_t* k;
+    float* part;           // [batch][chunks][channels]
+    float* mean;           // [batch][channels]
+    int lk, chunks, channels;
+    int64_t k_bs, k_rs;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_kmean_partial_kernel(const MeanParams p) {
+    __shared__ float red[32][kD8 + 1];
+    const int tid = threadIdx.x, r = tid >> 3, c8 = tid & 7;
+    const int chunk = blockIdx.x, grp = blockIdx.y, bi = blockIdx.z;
+    const uint16_t* kp = p.k + bi * p.k_bs + grp * kD8 + c8 * 8;
+    const int key0 = chunk * kMeanRows + r;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    uint4 u[kMeanRows / 32];
+#pragma unroll
+    for (int i = 0; i < kMeanRows / 32; ++i) {
+        const int key = key0 + 32 * i;
+        u[i] = make_uint4(0, 0, 0, 0);                       // +0.0 in either dtype: keys past lk add nothing
+        if (key < p.lk) u[i] = *reinterpret_cast<const uint4*>(kp + (int64_t)key * p.k_rs);
+    }
+#pragma unroll
+    for (int i = 0; i < kMeanRows / 32; ++i) {
+        float f[8];
+        unpack8<T>(u[i], f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += f[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[r][c8 * 8 + e] = acc[e];
+    __syncthreads();
+    if (tid < kD8) {
+        float s = red[0][tid];
+#pragma unroll
+        for (int j = 1; j < 32; ++j) s += red[j][tid];
+        p.part[((int64_t)bi * p.chunks + chunk) * p.channels + grp * kD8 + tid] = s;
+    }
+}
+
+// one thread per (batch element, channel): the partials in chunk order, then / lk
+__global__ __launch_bounds__(256) void attn_kmean_finish_kernel(const MeanParams p) {
+    const int c = blockIdx.x * 256 + threadIdx.x, bi = blockIdx.y;
+    if (c >= p.channels) return;
+    const float* src = p.part + (int64_t)bi * p.chunks * p.channels + c;
+    float s = 0.f;
+    for (int j = 0; j < p.chunks; ++j) s += src[(int64_t)j * p.channels];
+    p.mean[(int64_t)bi * p.channels + c] = s / (float)p.lk;
+}
+
 // one workgroup per (batch * head, key tile): 256 threads; threads 0..127 own (key, channel block) of K, 128..255
 // (channel, key block) of V
-template <typename T>
-__global__ __launch_bounds__(256) void attn_quant_kv_fp8_kernel(const QuantParams p) {
+template <typename T, bool SMOOTH>
+__global__ __launch_bounds__(256) void attn_quant_kv_fp8_kernel(const QuantParamsT<SMOOTH> p) {
     __shared__ float kt[kKV][kD8 + 1];
     __shared__ float vt[kKV][kD8 + 1];
     const int tid = threadIdx.x;
@@ -159,6 +226,15 @@ __global__ __launch_bounds__(256) void attn_quant_kv_fp8_kernel(const QuantParam
         float kf[8], vf[8];
         unpack8<T>(ku, kf);
         unpack8<T>(vu, vf);
+        if constexpr (SMOOTH) {
+            // key slots past lk stay zero (masked with -inf by the main kernels, but the image must stay finite)
+            if (key < p.lk) {
+                const float* mp = p.mean + (int64_t)hb * kD8 + ch * 8;
+                const float4 m0 = *reinterpret_cast<const float4*>(mp), m1 = *reinterpret_cast<const float4*>(mp + 4);
+                kf[0] -= m0.x; kf[1] -= m0.y; kf[2] -= m0.z; kf[3] -= m0.w;
+                kf[4] -= m1.x; kf[5] -= m1.y; kf[6] -= m1.z; kf[7] -= m1.w;
+            }
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             kt[row][ch * 8 + e] = kf[e];
@@ -1120,22 +1196,35 @@ extern "C" int64_t fino_attn_fp8_kv_bytes(int batch, int heads, int64_t lk, int 
     return b;
 }
 
-extern "C" int fino_attn_fwd_fp8(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                                 int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
-                                 int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode,
-                                 void* kv_workspace, int64_t kv_workspace_bytes, void* stream) {
-    FINO_CHECK(p_mode == FINO_FP8_P_EXP2 || p_mode == FINO_FP8_P_RAMP, FINO_ERR_ARG, "fino_attn_fwd_fp8: p_mode %d", p_mode);
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_attn_fwd_fp8: dtype %d", dtype);
-    FINO_CHECK(head_dim == 64 || head_dim == 128, FINO_ERR_UNSUPPORTED, "fino_attn_fwd_fp8: head_dim %d not in {64, 128}", head_dim);
-    FINO_CHECK(q && k && v && o && kv_workspace, FINO_ERR_ARG, "fino_attn_fwd_fp8: null pointer");
-    FINO_CHECK(batch > 0 && heads > 0 && lq >= 0 && lk > 0, FINO_ERR_ARG, "fino_attn_fwd_fp8: bad shape");
+// fp32 partials of the key mean: one per (batch element, chunk of kMeanRows keys, channel)
+static int64_t kmean_chunks(int64_t lk) { return (lk + kMeanRows - 1) / kMeanRows; }
+
+// fino_attn_fp8_kv_bytes rounded up to 16 | mean fp32 [batch][heads * head_dim] | partials fp32 [batch][chunks][heads * head_dim]:
+// behind everything the plain layout places (head_dim 128's (O, m, l) partials included)
+extern "C" int64_t fino_attn_fp8_smooth_kv_bytes(int batch, int heads, int64_t lk, int head_dim) {
+    const int64_t base = fino_attn_fp8_kv_bytes(batch, heads, lk, head_dim);
+    if (base <= 0) return 0;
+    return ((base + 15) & ~(int64_t)15) + (int64_t)batch * heads * head_dim * 4 * (1 + kmean_chunks(lk));
+}
+
+// both entry points: `smooth` = mean -> smoothing quantiser, otherwise the plain quantiser; the main-kernel launch is the same
+static int attn_fwd_fp8_impl(const char* fn, bool smooth, const void* q, const void* k, const void* v, void* o, int batch, int heads,
+                             int64_t lq, int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
+                             int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode,
+                             void* kv_workspace, int64_t kv_workspace_bytes, void* stream) {
+    FINO_CHECK(p_mode == FINO_FP8_P_EXP2 || p_mode == FINO_FP8_P_RAMP, FINO_ERR_ARG, "%s: p_mode %d", fn, p_mode);
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "%s: dtype %d", fn, dtype);
+    FINO_CHECK(head_dim == 64 || head_dim == 128, FINO_ERR_UNSUPPORTED, "%s: head_dim %d not in {64, 128}", fn, head_dim);
+    FINO_CHECK(q && k && v && o && kv_workspace, FINO_ERR_ARG, "%s: null pointer", fn);
+    FINO_CHECK(batch > 0 && heads > 0 && lq >= 0 && lk > 0, FINO_ERR_ARG, "%s: bad shape", fn);
     FINO_CHECK(fino_aligned16(q) && fino_aligned16(k) && fino_aligned16(v) && fino_aligned16(o) &&
                    fino_aligned16(kv_workspace) && q_rs % 8 == 0 && k_rs % 8 == 0 && v_rs % 8 == 0 && o_rs % 8 == 0 &&
                    q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0 && o_bs % 8 == 0,
-               FINO_ERR_ARG, "fino_attn_fwd_fp8: pointers and strides must be 16-byte aligned");
-    FINO_CHECK(scale > 0.f || scale == FINO_ATTN_SCALE_FOLDED, FINO_ERR_ARG, "fino_attn_fwd_fp8: scale");
-    const int64_t need = fino_attn_fp8_kv_bytes(batch, heads, lk, head_dim);
-    FINO_CHECK(kv_workspace_bytes >= need, FINO_ERR_ARG, "fino_attn_fwd_fp8: workspace %lld B < %lld B",
+               FINO_ERR_ARG, "%s: pointers and strides must be 16-byte aligned", fn);
+    FINO_CHECK(scale > 0.f || scale == FINO_ATTN_SCALE_FOLDED, FINO_ERR_ARG, "%s: scale", fn);
+    const int64_t need = smooth ? fino_attn_fp8_smooth_kv_bytes(batch, heads, lk, head_dim)
+                                : fino_attn_fp8_kv_bytes(batch, heads, lk, head_dim);
+    FINO_CHECK(kv_workspace_bytes >= need, FINO_ERR_ARG, "%s: workspace %lld B < %lld B", fn,
                (long long)kv_workspace_bytes, (long long)need);
     if (lq == 0) return FINO_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -1143,13 +1232,34 @@ extern "C" int fino_attn_fwd_fp8(const void* q, const void* k, const void* v, vo
     const int sub = head_dim / 64;                            // 64-channel sub-heads per head: images of the pre-pass
     const int64_t bh = (int64_t)batch * heads * sub;
     uint8_t* w8 = (uint8_t*)kv_workspace;
-    QuantParams qp;
+    QuantParamsT<true> qp;                                    // (.mean: the smoothing quantiser alone reads it)
     qp.k = (const uint16_t*)k; qp.v = (const uint16_t*)v;
     qp.k8 = w8; qp.v8t = w8 + bh * nt * kTileK8; qp.ks = w8 + 2 * bh * nt * kTileK8; qp.vs = qp.ks + bh * nt * 128;
     qp.batch = batch; qp.heads = heads * sub; qp.lk = (int)lk; qp.nt = nt;
     qp.k_bs = k_bs; qp.k_rs = k_rs; qp.k_hs = 64; qp.v_bs = v_bs; qp.v_rs = v_rs; qp.v_hs = 64;
-    if (dtype == FINO_BF16) attn_quant_kv_fp8_kernel<BF16><<<dim3((unsigned)nt, (unsigned)bh), 256, 0, st>>>(qp);
-    else attn_quant_kv_fp8_kernel<F16><<<dim3((unsigned)nt, (unsigned)bh), 256, 0, st>>>(qp);
+    if (smooth) {
+        MeanParams mp;
+        mp.k = qp.k; mp.lk = (int)lk; mp.chunks = (int)kmean_chunks(lk); mp.channels = heads * head_dim;
+        mp.k_bs = k_bs; mp.k_rs = k_rs;
+        mp.mean = (float*)(w8 + ((fino_attn_fp8_kv_bytes(batch, heads, lk, head_dim) + 15) & ~(int64_t)15));
+        mp.part = mp.mean + (int64_t)batch * mp.channels;
+        qp.mean = mp.mean;
+        FINO_CHECK(mp.chunks <= 65535 && batch <= 65535, FINO_ERR_UNSUPPORTED, "%s: lk %lld / batch %d beyond the mean pass's grid",
+                   fn, (long long)lk, batch);
+        const dim3 gpart((unsigned)mp.chunks, (unsigned)(mp.channels / kD8), (unsigned)batch);
+        const dim3 gfin((unsigned)((mp.channels + 255) / 256), (unsigned)batch);
+        if (dtype == FINO_BF16) attn_kmean_partial_kernel<BF16><<<gpart, 256, 0, st>>>(mp);
+        else attn_kmean_partial_kernel<F16><<<gpart, 256, 0, st>>>(mp);
+        FINO_LAUNCH_CHECK();
+        attn_kmean_finish_kernel<<<gfin, 256, 0, st>>>(mp);
+        FINO_LAUNCH_CHECK();
+        if (dtype == FINO_BF16) attn_quant_kv_fp8_kernel<BF16, true><<<dim3((unsigned)nt, (unsigned)bh), 256, 0, st>>>(qp);
+        else attn_quant_kv_fp8_kernel<F16, true><<<dim3((unsigned)nt, (unsigned)bh), 256, 0, st>>>(qp);
+    } else {
+        const QuantParamsT<false> qpl{qp};
+        if (dtype == FINO_BF16) attn_quant_kv_fp8_kernel<BF16, false><<<dim3((unsigned)nt, (unsigned)bh), 256, 0, st>>>(qpl);
+        else attn_quant_kv_fp8_kernel<F16, false><<<dim3((unsigned)nt, (unsigned)bh), 256, 0, st>>>(qpl);
+    }
     FINO_LAUNCH_CHECK();
 
     Fp8AttnParams fp;
@@ -1181,7 +1291,7 @@ extern "C" int fino_attn_fwd_fp8(const void* q, const void* k, const void* v, vo
         static FinoPerDeviceOnce once_[4];                                                                                \
         const void* fn_ = dtype == FINO_BF16 ? (ramp ? (const void*)KERNEL_(BF16, 1) : (const void*)KERNEL_(BF16, 0))     \
                                              : (ramp ? (const void*)KERNEL_(F16, 1) : (const void*)KERNEL_(F16, 0));      \
-        const int rc_ = fino_max_smem_once(once_[(dtype == FINO_BF16 ? 0 : 2) + (ramp ? 1 : 0)], fn_, SMEM_, "fino_attn_fwd_fp8"); \
+        const int rc_ = fino_max_smem_once(once_[(dtype == FINO_BF16 ? 0 : 2) + (ramp ? 1 : 0)], fn_, SMEM_, fn); \
         if (rc_ != FINO_OK) return rc_;                                                                                   \
     }
 #define K_FR(T_, PX_) attn_fp8_fr_kernel<T_, PX_>
@@ -1211,4 +1321,20 @@ extern "C" int fino_attn_fwd_fp8(const void* q, const void* k, const void* v, vo
     F8_LAUNCH(K_PP, grid, kWaves * 64, smem)
     FINO_LAUNCH_CHECK();
     return FINO_OK;
+}
+
+extern "C" int fino_attn_fwd_fp8(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
+                                 int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
+                                 int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode,
+                                 void* kv_workspace, int64_t kv_workspace_bytes, void* stream) {
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8", false, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs,
+                             o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream);
+}
+
+extern "C" int fino_attn_fwd_fp8_smooth(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
+                                        int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
+                                        int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype,
+                                        int p_mode, void* kv_workspace, int64_t kv_workspace_bytes, void* stream) {
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smooth", true, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs, v_bs,
+                             v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream);
 }

@@ -377,10 +377,12 @@ if _p_env not in FP8_P_MODES:
 FP8_P_DEFAULT = FP8_P_MODES[_p_env]
 
 
-def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None):
+def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=False):
     """attention() with fp8 (e4m3) matrix operands, head_dim 64 or 128: K / V quantised per call (block-scaled, V transposed), Q
     and P in registers, both products on the block-scaled fp8 MFMA, softmax and accumulation in fp32 (fino_attn_fwd_fp8).
-    p_mode: "exp2" | "ramp" (or the FP8_P_* integers); None = FP8_P_DEFAULT."""
+    p_mode: "exp2" | "ramp" (or the FP8_P_* integers); None = FP8_P_DEFAULT.
+    smooth_k: subtract the mean of K over the keys (per batch element, head and channel) before K is quantised
+    (fino_attn_fwd_fp8_smooth): the softmax cannot see it, and a channel offset all keys share stops costing mantissa bits."""
     p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
     assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
     b, lq, hd = q.shape
@@ -391,7 +393,8 @@ def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None):
     if out is None:
         out = torch.empty((b, lq, hd), dtype=q.dtype, device=q.device)
     scale = dh ** -0.5 if scale is None else scale
-    need = _lib.lib().fino_attn_fp8_kv_bytes(b, heads, lk, dh)
+    fwd = "fino_attn_fwd_fp8_smooth" if smooth_k else "fino_attn_fwd_fp8"
+    need = (_lib.lib().fino_attn_fp8_smooth_kv_bytes if smooth_k else _lib.lib().fino_attn_fp8_kv_bytes)(b, heads, lk, dh)
     if need <= 0:
         raise RuntimeError(f"attention_fp8: head_dim {dh} is not supported (64 or 128)")
     key = (q.device.index, torch.cuda.current_stream().cuda_stream)
@@ -399,9 +402,9 @@ def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None):
     if ws is None or ws.numel() < need:
         ws = _attn_fp8_ws[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
     ev = _timed("attn_self" if lk > 1024 else "attn_cross")
-    _lib.check(_lib.lib().fino_attn_fwd_fp8(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
-                                           k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
-                                           float(scale), _dt(q), int(p_mode), _p(ws), need, _stream()), "fino_attn_fwd_fp8")
+    _lib.check(getattr(_lib.lib(), fwd)(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
+                                        k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
+                                        float(scale), _dt(q), int(p_mode), _p(ws), need, _stream()), fwd)
     if ev is not None:
         ev.record()
         kt_ = KernelTimer.active

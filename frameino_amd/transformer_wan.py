@@ -266,14 +266,18 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                            ("ff2", blk.ffn.net[2].weight)):
                 yield li, key, w
 
-    def enable_fp8_attention(self, enabled=True, p_mode=None):
+    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False):
         """The 3-D self-attention (transformer_wan.py:108) with fp8 (e4m3) matrix operands -- q, k, v and P on the
         block-scaled fp8 MFMA, softmax and accumulation fp32 (fino_attn_fwd_fp8, head_dim 128 as two 64-channel sub-heads).
         Opt-in, single-GPU forward only; no reference counterpart: rel-RMS ~5e-2 per attention output on N(0, 1) inputs
         (tests/test_attention_fp8_gpu.py).  The text cross-attention stays bf16.
-        p_mode: "exp2" | "ramp" -- how a softmax weight becomes its e4m3 byte (ops.FP8_P_*; None = ops.FP8_P_DEFAULT)."""
+        p_mode: "exp2" | "ramp" -- how a softmax weight becomes its e4m3 byte (ops.FP8_P_*; None = ops.FP8_P_DEFAULT).
+        smooth_k: subtract the per-(batch element, head, channel) mean of K over the keys before K is quantised
+        (fino_attn_fwd_fp8_smooth): invisible to the softmax, and a channel offset that all keys share (a to_k bias, norm_k
+        weights, low-frequency RoPE channels) stops taking the mantissa bits.  Off by default."""
         self.fp8_attention = bool(enabled)
         self.fp8_p_mode = p_mode
+        self.fp8_smooth_k = bool(smooth_k)
         return self
 
     def _workspace(self, L, dtype, device):
@@ -586,7 +590,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         attend = o.attention
         if self.fp8_attention and sh is None and hasattr(o, "attention_fp8"):
             def attend(q_, k_, v_, heads_, **kw_):
-                return o.attention_fp8(q_, k_, v_, heads_, p_mode=getattr(self, "fp8_p_mode", None), **kw_)
+                return o.attention_fp8(q_, k_, v_, heads_, p_mode=getattr(self, "fp8_p_mode", None),
+                                       smooth_k=getattr(self, "fp8_smooth_k", False), **kw_)
         # rows whose output the caller reads (`live_rows`): honoured in the last block on the single-GPU default-processor path
         live = None
         # (not under Pyramid Attention Broadcast: a cached branch output covers every row, so that any later step may use it)

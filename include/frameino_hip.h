@@ -180,6 +180,20 @@ int fino_attn_fwd_fp8(const void* q, const void* k, const void* v, void* o, int 
                       int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs,
                       int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode, void* kv_workspace,
                       int64_t kv_workspace_bytes, void* stream);
+/* fino_attn_fwd_fp8 with SMOOTH K: the mean of K over the keys, one fp32 per (batch element, head, head channel), is subtracted
+ * before K is quantised to e4m3.  The rule: q.(k_j - mu) = q.k_j - q.mu, and q.mu is ONE constant per query row, which the softmax
+ * drops -- exact in real arithmetic, no correction term; Q, V, the main kernels and the output are those of fino_attn_fwd_fp8.  What it
+ * buys: a channel offset shared by all keys (a to_k bias, norm_k weights, low-frequency RoPE channels) no longer takes the three
+ * mantissa bits of its 32-channel block.  mean = fp32 sum over the keys / (float)lk, summed in a fixed partition (256-key chunks)
+ * and a fixed order, no atomics: the same inputs give the same bits.  Same argument list; the workspace is larger
+ * (fino_attn_fp8_smooth_kv_bytes; 0 for unsupported arguments) and laid out as
+ *     [ everything fino_attn_fp8_kv_bytes covers, head_dim 128's (O, m, l) partials included | pad to 16 B |
+ *       mean fp32 [batch][heads * head_dim] | partial sums fp32 [batch][ceil(lk / 256)][heads * head_dim] ] */
+int64_t fino_attn_fp8_smooth_kv_bytes(int batch, int heads, int64_t lk, int head_dim);
+int fino_attn_fwd_fp8_smooth(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq, int64_t lk,
+                             int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs,
+                             int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode, void* kv_workspace,
+                             int64_t kv_workspace_bytes, void* stream);
 
 /* Cross-attention over key sequences whose TAIL is one row repeated -- the zero-padded prompt of
  * pipelines/pipeline_wan_i2v_motion_FrameINO.py:235-238: every padding token of the 512 the text cross-attention
