@@ -63,6 +63,10 @@ def main():
                     help="diffusers' Pyramid Attention Broadcast (approximate; eager loop): while the timestep is inside (100, 800) "
                          "the self-attention branch is recomputed every N-th step and re-used in between, and with M the text "
                          "cross-attention branch every M-th, e.g. 2 or 2,3.  Not together with --first-block-cache")
+    ap.add_argument("--window-frames", type=int, default=None, metavar="N",
+                    help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
+                         "every query attends its own frame +- N neighbours plus the first frame and the ID frame, e.g. 2.  Not "
+                         "together with --pab")
     ap.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16",
                     help="the DiT's dtype.  Default fp16 = what the reference app loads it in (app.py:156: "
                          "`WanTransformer3DModel.from_pretrained(..., torch_dtype=torch.float16)`, fp32 islands kept); bf16 is what "
@@ -139,6 +143,9 @@ def main():
         transformer.enable_cache(PyramidAttentionBroadcastConfig(
             spatial_attention_block_skip_range=n_m[0], cross_attention_block_skip_range=n_m[1] if len(n_m) > 1 else None,
             current_timestep_callback=lambda: pipe.current_timestep))
+    if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)
+        from frameino_amd.window_attention import WindowAttentionConfig
+        transformer.enable_window_attention(WindowAttentionConfig(window_frames=a.window_frames, sink_frames=(0,)))
     t0 = time.perf_counter()
     canvas, tracks, id_tensor, pads = synthetic_conditions(a.frames, a.height, a.width, dev)
     traj = prepare_traj_tensor(tracks, a.height, a.width, 6, a.width, a.height, device=dev)        # [F, 3, H, W]

@@ -43,7 +43,8 @@ using namespace fino_attn_ns;
 namespace {
 
 // VAR only names the launch site (0: long-KV self-attention, 1: short-KV text cross-attention) so that profilers
-// report the two call classes as separate kernel symbols; the code is identical.
+// report the two call classes as separate kernel symbols; the code is identical.  attn_ppd_kernel alone also has VAR 2:
+// the key tiles of a q-block come from a table of ranges (fino_attn_fwd_ranges).
 template <typename T, int D, int VAR>
 __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -528,7 +529,36 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
     const uint16_t* vp = p.v + bi * p.v_bs + head * p.v_hs + (int64_t)t_begin * kKV * p.v_rs;
     uint16_t* op = p.o + bi * p.o_bs + head * p.o_hs;
     const int lk = (t_end * kKV < p.lk ? t_end * kKV : p.lk) - t_begin * kKV;
-    const int nt = (lk + kKV - 1) / kKV;
+    int nt = (lk + kKV - 1) / kKV;
+    // VAR 2 (fino_attn_fwd_ranges; whole blocks: t_begin = 0, lk = p.lk): the block walks LOCAL tiles 0 .. nt - 1, which its
+    // row of p.ranges maps onto up to three runs of global key tiles.  Ring slots and every wait count below go by the local
+    // index; only the DMA's tile offset and the ragged mask see the global one, g(t) = t + rg_d(t).  The six integers are read
+    // once, here, clipped to [0, ntall] (a bad table cannot reach past K / V) and made wave-uniform: g stays scalar
+    // arithmetic, nothing of it lands on lgkmcnt inside the loop.  t >= nt maps to tile ntall (wholly past the last key: zeros).
+    int rg_c1 = 0, rg_c2 = 0, rg_d0 = 0, rg_d1 = 0, rg_d2 = 0, rg_rag = -1;
+    if constexpr (VAR == 2) {
+        const int* rg = p.ranges + (int64_t)qb * 6;
+        int b_[3], n_[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            int b = __builtin_amdgcn_readfirstlane(rg[2 * i]), e = __builtin_amdgcn_readfirstlane(rg[2 * i + 1]);
+            b = b < 0 ? 0 : (b > ntall ? ntall : b);
+            e = e < b ? b : (e > ntall ? ntall : e);
+            b_[i] = b;
+            n_[i] = e - b;
+        }
+        rg_c1 = n_[0];
+        rg_c2 = n_[0] + n_[1];
+        nt = rg_c2 + n_[2];
+        rg_d0 = b_[0];
+        rg_d1 = b_[1] - rg_c1;
+        rg_d2 = b_[2] - rg_c2;
+    }
+#define PD_GTILE(T_) ((T_) + ((T_) < rg_c1 ? rg_d0 : ((T_) < rg_c2 ? rg_d1 : ((T_) < nt ? rg_d2 : ntall - (T_)))))
+    if constexpr (VAR == 2) {
+        // the ragged tile is the LAST global tile; ranges ascend, so it can only be the last tile walked
+        if (nt > 0 && (lk & (kKV - 1)) && PD_GTILE(nt - 1) == ntall - 1) rg_rag = nt - 1;
+    }
 
     // ---- K / V staging by LDS-DMA: a tile is 16 pieces of 1 KiB (4 rows); wave w moves pieces w and w + 8 of K and of V.
     //      The lane's row inside the piece, its chunk position and the swizzle (row bits a step of 8 pieces leaves alone) are
@@ -550,7 +580,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
     // tile index clamped to nt: tile nt lies wholly past the last key (zeros), and the scalar offset stays inside 32 bits
 #define PD_DMA_K(TILE_)                                                                                      \
     {                                                                                                        \
-        const int tl_ = (TILE_) < nt ? (TILE_) : nt;                                                         \
+        const int tl_ = VAR == 2 ? PD_GTILE(TILE_) : ((TILE_) < nt ? (TILE_) : nt);                          \
         _Pragma("unroll") for (int i_ = 0; i_ < kPW; ++i_)                                                   \
             __builtin_amdgcn_raw_ptr_buffer_load_lds(                                                        \
                 k_rsrc, (FINO_LDS void*)(smem + ((TILE_) & (kPdSlots - 1)) * kTileBytes + (8 * i_ + wv) * 1024), 16, \
@@ -558,7 +588,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
     }
 #define PD_DMA_V(TILE_)                                                                                      \
     {                                                                                                        \
-        const int tl_ = (TILE_) < nt ? (TILE_) : nt;                                                         \
+        const int tl_ = VAR == 2 ? PD_GTILE(TILE_) : ((TILE_) < nt ? (TILE_) : nt);                          \
         _Pragma("unroll") for (int i_ = 0; i_ < kPW; ++i_)                                                   \
             __builtin_amdgcn_raw_ptr_buffer_load_lds(                                                        \
                 v_rsrc, (FINO_LDS void*)(smem + kVBase + ((TILE_) & (kPdSlots - 1)) * kTileBytes + (8 * i_ + wv) * 1024), \
@@ -609,8 +639,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
         }
     }
 #define MASK_RAGGED(T_)                                                                                     \
-    if ((T_) == nt - 1 && (lk & (kKV - 1))) {            /* key = (j&3) + 8*(j>>2) + 4*h (+32) */           \
-        const int kbase_ = (T_) * kKV + 4 * h;                                                              \
+    if (VAR == 2 ? (T_) == rg_rag : ((T_) == nt - 1 && (lk & (kKV - 1)))) { /* key = (j&3) + 8*(j>>2) + 4*h (+32) */ \
+        const int kbase_ = (VAR == 2 ? ntall - 1 : (T_)) * kKV + 4 * h;       /* VAR 2: keys of the GLOBAL last tile */ \
         _Pragma("unroll") for (int j_ = 0; j_ < 16; ++j_) {                                                 \
             const int key_ = kbase_ + (j_ & 3) + 8 * (j_ >> 2);                                             \
             if (key_ >= lk) sc0[j_] = -INFINITY;                                                            \
@@ -872,6 +902,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
     __builtin_amdgcn_s_barrier();                      // ... for EVERY wave: the epilogue stages its output rows in the rings
 #undef PD_DMA_K
 #undef PD_DMA_V
+#undef PD_GTILE
 #undef PD_KISSUE
 #undef PD_KWAIT
 #undef PD_SHADOW_MAX
@@ -903,7 +934,9 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
         wsp[kDT * 16 * (kWaves * 64) + kWaves * 64 + tid] = l_run;
         continue;
     }
-    const float inv = 1.0f / l_run;
+    float inv = 1.0f / l_run;
+    if constexpr (VAR == 2)
+        if (nt == 0) inv = 0.f;                        // a q-block without key tiles stores zeros (O = 0, l = 0), not NaN
     {
         // every wave is past its last matrix phase (the barrier above): the K ring's first 64 KiB take the output rows, 8 KiB per wave
         int le = lane;
@@ -1826,8 +1859,26 @@ int launch_attn_v(AttnParams p, int64_t ws_bytes, hipStream_t st) {
     return FINO_OK;
 }
 
+// fino_attn_fwd_ranges: always attn_ppd_kernel<T, D, 2>, whole blocks only (no tail split, no partials), whatever lk or
+// FINO_TUNE_ATTN_KERNEL say
+template <typename T, int D>
+int launch_attn_ranges(AttnParams p, hipStream_t st) {
+    constexpr int smem_d = 2 * kPdSlots * kKV * D * 2;
+    static FinoPerDeviceOnce once;
+    if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&attn_ppd_kernel<T, D, 2>), smem_d, "fino_attn_fwd_ranges"))
+        return rc;
+    attn_virtual_heads(p.batch, p.heads, p.nqb, p.vsplit, p.nqb_v);
+    const int groups = (p.batch * p.heads * p.vsplit + 7) / 8;
+    p.full_x = groups * p.nqb_v; p.rem_x = 0; p.nwg = 0; p.per = 1;
+    p.ws = nullptr; p.all_partial = 0;
+    attn_ppd_kernel<T, D, 2><<<dim3((unsigned)(8 * p.full_x)), kWaves * 64, smem_d, st>>>(p);
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
+}
+
 template <typename T, int D>
 int launch_attn(const AttnParams& p, int64_t ws_bytes, hipStream_t st) {
+    if (p.ranges) return launch_attn_ranges<T, D>(p, st);
     return p.lk > 1024 ? launch_attn_v<T, D, 0>(p, ws_bytes, st) : launch_attn_v<T, D, 1>(p, ws_bytes, st);
 }
 
@@ -1868,7 +1919,7 @@ static int attn_common(const void* q, const void* k, const void* v, void* o, int
                        int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs,
                        int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs,
                        int64_t o_rs, int64_t o_hs, float scale, int dtype, void* workspace,
-                       int64_t workspace_bytes, int all_partial, void* stream) {
+                       int64_t workspace_bytes, int all_partial, void* stream, const int* ranges = nullptr) {
     FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_attn_fwd: dtype %d", dtype);
     if (all_partial) {
         static const uint16_t dummy_o[8] __attribute__((aligned(16))) = {0};
@@ -1909,6 +1960,7 @@ static int attn_common(const void* q, const void* k, const void* v, void* o, int
     p.ws = (workspace && workspace_bytes > 0) ? (float*)workspace : nullptr;
     p.all_partial = all_partial;
     p.tail_n = 0;
+    p.ranges = ranges;
     FINO_CHECK(((uintptr_t)workspace & 15) == 0, FINO_ERR_ARG, "fino_attn_fwd_ws: workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int64_t wb = workspace_bytes;
@@ -1975,6 +2027,23 @@ extern "C" int fino_attn_fwd(const void* q, const void* k, const void* v, void* 
                             v_hs, o_bs, o_rs, o_hs, scale, dtype, nullptr, 0, stream);
 }
 
+// Attention over up to three ranges of key tiles per 256-row q-block (include/frameino_hip.h): fino_attn_fwd's arguments and
+// checks + the device table; always attn_ppd_kernel<T, D, 2>.
+extern "C" int fino_attn_ranges_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim) {
+    return (head_dim == 128 || head_dim == 64) && batch > 0 && heads > 0 && lq > 0 && lk > 0 && lq < (1ll << 31) - 256 &&
+           lk < (1ll << 31) - 64;
+}
+
+extern "C" int fino_attn_fwd_ranges(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
+                                    int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs,
+                                    int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs,
+                                    int64_t o_rs, int64_t o_hs, float scale, int dtype, const int* ranges, void* stream) {
+    FINO_CHECK(ranges, FINO_ERR_ARG, "fino_attn_fwd_ranges: null ranges table");
+    FINO_CHECK(((uintptr_t)ranges & 3) == 0, FINO_ERR_ARG, "fino_attn_fwd_ranges: the ranges table must be 4-byte aligned");
+    return attn_common(q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs, v_hs,
+                       o_bs, o_rs, o_hs, scale, dtype, nullptr, 0, 0, stream, ranges);
+}
+
 // Cross-attention over key sequences whose TAIL is one row repeated (a zero-padded prompt: every padding token yields the same
 // K and V row, transformer_wan.py:108 via attn2 with the 512-token text of pipeline_wan_i2v_motion_FrameINO.py:235-238): batch
 // element b attends to its first lk_b[b] rows of k / v, the last of which stands for tail_mult[b] identical keys; rows from
@@ -2010,7 +2079,7 @@ extern "C" int fino_attn_fwd_tail(const void* q, const void* k, const void* v, v
     p.scale_log2 = scale == FINO_ATTN_SCALE_FOLDED ? 1.0f : scale * 1.4426950408889634f;
     p.nqb = (int)((lq + kQBlock - 1) / kQBlock);
     p.vsplit = 1; p.nqb_v = p.nqb; p.full_x = 0; p.rem_x = 0; p.nwg = 0; p.per = 1;
-    p.ws = nullptr; p.all_partial = 0;
+    p.ws = nullptr; p.all_partial = 0; p.ranges = nullptr;
     // the walking kernel addresses each operand through ONE buffer resource over the whole tensor
     auto span = [&](int64_t bs, int64_t hs, int64_t rs, int64_t rows) {
         return (((int64_t)batch - 1) * bs + ((int64_t)heads - 1) * hs + (rows - 1 + 2 * kKV) * rs + 128) * 2;

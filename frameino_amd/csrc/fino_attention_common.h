@@ -44,6 +44,10 @@ struct AttnParams {
     int tail_n;
     int tail_lk[4];
     float tail_bias[4];
+    // fino_attn_fwd_ranges (attn_ppd_kernel<T, D, 2> only): int32 [nqb][3][2] device table, up to three ascending, disjoint
+    // [begin, end) ranges of key tiles per q-block ((0, 0): unused), shared by all heads and batch elements.  nullptr: off.
+    // Last member: the offsets of everything above, and with them the dense kernels' argument loads, stay as they were.
+    const int* ranges;
 };
 
 // (XCD, slot in that XCD's list of blocks) -> (head-batch, q-block); false: an empty slot.  The q-blocks of one head run on

@@ -281,6 +281,47 @@ def attention(q, k, v, heads, out=None, scale=None):
     return out
 
 
+def attention_ranges_supported(b, heads, lq, lk, dh):
+    return bool(_lib.lib().fino_attn_ranges_supported(int(b), int(heads), int(lq), int(lk), int(dh)))
+
+
+def attention_ranges(q, k, v, heads, ranges, out=None, scale=None):
+    """attention() over a subset of the key tiles, chosen per 256-row q-block: `ranges` is an int32 DEVICE tensor
+    [ceil(Lq / 256), 3, 2] of up to three ascending, disjoint [begin, end) ranges of 64-key tiles per q-block ((0, 0): unused),
+    shared by all heads and batch elements (fino_attn_fwd_ranges; frameino_amd/window_attention.py builds the tables of the
+    sliding window over frames).  A q-block without tiles gets zeros."""
+    assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
+    b, lq, hd = q.shape
+    lk = k.shape[1]
+    dh = hd // heads
+    for t in (q, k, v):
+        assert t.stride(2) == 1 and t.is_cuda
+    nqb = (lq + 255) // 256
+    assert ranges.dtype == torch.int32 and ranges.is_cuda and ranges.is_contiguous() and tuple(ranges.shape) == (nqb, 3, 2), \
+        f"ranges: an int32 device tensor [{nqb}, 3, 2] is needed, got {ranges.dtype} {tuple(ranges.shape)} on {ranges.device}"
+    if out is None:
+        out = torch.empty((b, lq, hd), dtype=q.dtype, device=q.device)
+    scale = dh ** -0.5 if scale is None else scale
+    ev = _timed("attn_self")
+    _lib.check(_lib.lib().fino_attn_fwd_ranges(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh,
+                                              q.stride(0), q.stride(1), dh, k.stride(0), k.stride(1), dh,
+                                              v.stride(0), v.stride(1), dh, out.stride(0), out.stride(1), dh,
+                                              float(scale), _dt(q), _p(ranges), _stream()), "fino_attn_fwd_ranges")
+    if ev is not None:
+        ev.record()
+        kt_ = KernelTimer.active
+        # FLOPs and bytes from the tiles walked (the table's host copy is read only here, under the timer: one sync per launch)
+        nta = (lk + 63) // 64
+        r = ranges.clamp(0, nta).tolist()
+        pairs = 0.0                                             # (query row, key) pairs of one head
+        for i, blk in enumerate(r):
+            keys = sum(max(0, min(e * 64, lk) - s * 64) for s, e in blk)
+            pairs += float(min(256, lq - 256 * i)) * keys
+        kt_.flops["attn_self"] = kt_.flops.get("attn_self", 0.0) + 4.0 * b * pairs * hd
+        kt_.bytes["attn_self"] = kt_.bytes.get("attn_self", 0.0) + 2.0 * b * hd * (2 * lq + 2 * lk)
+    return out
+
+
 def attention_tail_supported(b, heads, lq, lk, dh):
     return bool(_lib.lib().fino_attn_tail_supported(int(b), int(heads), int(lq), int(lk), int(dh)))
 

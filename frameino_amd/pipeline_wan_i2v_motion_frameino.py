@@ -185,6 +185,22 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
                                "eagerly; use_hip_graph=None or False)")
         return True
 
+    def _window_attention_check(self):
+        """the limits of window attention (WanTransformer3DModel.enable_window_attention), checked before any work.  -> whether
+        the loop must run eagerly: with a timestep range the host decides per step whether the windows apply."""
+        cfg = getattr(self.transformer, "_window", None)
+        if cfg is None:
+            return False
+        if getattr(self, "parallel", None) is not None:
+            raise NotImplementedError("window attention runs on one GPU; this pipeline has a parallel plan")
+        if cfg.timestep_range is None:
+            return False                      # the range table is a static device tensor: the step captures as it is
+        if self.use_hip_graph is True:
+            raise RuntimeError("use_hip_graph=True with window attention under a timestep range: whether a step's self-attention "
+                               "is windowed changes from step to step on the host's schedule, which one captured step cannot "
+                               "contain (the loop runs eagerly; use_hip_graph=None or False)")
+        return True
+
     def to(self, device):
         for m in (self.transformer, self.vae, self.text_encoder):
             if m is not None and hasattr(m, "to"):
@@ -350,6 +366,8 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         rows = (st.t_rows, st.sel)
 
         live = {"live_rows": st.live_rows} if getattr(st, "live_rows", None) is not None else {}
+        if getattr(tr, "is_window_attention_enabled", False):      # (this package's transformer only, like live_rows)
+            live["id_frames"] = st.id_frames
 
         cached = bool(getattr(tr, "is_cache_enabled", False))
 
@@ -463,6 +481,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         first_dead = bool((first_frame_mask[0, 0, 0] == 0).all()) if fg > 1 else False
         lo_live, hi_live = (tok_per_frame if first_dead else 0), fg * tok_per_frame
         st.live_rows = (lo_live, hi_live) if (hi_live - lo_live) < (fg + nid) * tok_per_frame else None
+        st.id_frames = nid               # window attention: the identity-reference frames are sinks
         st.t_rows = torch.zeros(2, dtype=torch.float32, device=dev)
         st.dt = torch.zeros(1, dtype=torch.float32, device=dev)
         # UniPC multistep history (last corrected sample, two x0 predictions) + this step's coefficient row
@@ -488,6 +507,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         With a step cache (first-block caching, Pyramid Attention Broadcast) every call -- every sample -- starts from fresh
         cache state."""
         cached = self._step_cache_check(latents.shape[0])
+        win_eager = self._window_attention_check()
         if cached:
             self.transformer._reset_stateful_cache()
         if latents.shape[0] > 1:
@@ -519,7 +539,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
 
         from .graph_step import StepGraph, capture_error_mode, groups_capturable
         stepper = StepGraph(lambda: self._step(st), self.use_hip_graph,
-                            callback_on_step_end is None and st.lat.is_cuda and not cached
+                            callback_on_step_end is None and st.lat.is_cuda and not cached and not win_eager
                             and (self.use_hip_graph is True or tr_default_procs(self.transformer))
                             and groups_capturable(getattr(self, "parallel", None), self.use_hip_graph is True),
                             len(timesteps), capture_error_mode(getattr(self, "parallel", None)))

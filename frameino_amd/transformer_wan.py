@@ -169,6 +169,9 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self.reassociate_text_out = os.environ.get("FINO_TEXT_REASSOC", "1") != "0"
         # honour `forward(live_rows=...)`: in the last block, rows the caller discards contribute K | V only (round 6)
         self.skip_dead_rows = os.environ.get("FINO_SKIP_DEAD_ROWS", "1") != "0"
+        self._window = None               # WindowAttentionConfig or None: see enable_window_attention
+        self._window_forwards = 0
+        self.window_attention_log = []    # (forward index, timestep or None, windowed) since enable_window_attention
 
     # ------------------------------------------------------------------ diffusers-style surface
     @property
@@ -219,7 +222,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._reset_stateful_cache()
         self._packed = None
         self._text_cache.clear()
-        self._rope_cache.clear()
+        self._rope_cache.clear()          # (the window-attention range tables live here too)
         self._ws.clear()
         return had_fp8
 
@@ -275,10 +278,100 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         smooth_k: subtract the per-(batch element, head, channel) mean of K over the keys before K is quantised
         (fino_attn_fwd_fp8_smooth): invisible to the softmax, and a channel offset that all keys share (a to_k bias, norm_k
         weights, low-frequency RoPE channels) stops taking the mantissa bits.  Off by default."""
+        if enabled and self._window is not None:
+            raise NotImplementedError("fp8 attention with window attention: the range walk exists in the bf16 / fp16 kernel "
+                                      "only; disable_window_attention() first")
         self.fp8_attention = bool(enabled)
         self.fp8_p_mode = p_mode
         self.fp8_smooth_k = bool(smooth_k)
         return self
+
+    # ------------------------------------------------------------------ sliding-window self-attention over frames
+    def enable_window_attention(self, config):
+        """Opt-in, approximate: in every block not in `config.skip_layers` a query attends its own latent frame +-
+        `config.window_frames` neighbours plus the sink frames (`config.sink_frames`, and the trailing `forward(id_frames=n)`
+        frames) instead of every token -- `ops.attention_ranges` over a per-q-block table of key-tile ranges
+        (frameino_amd/window_attention.py has the exact definition and the kernel's granularity).  A
+        window that covers the whole clip takes the dense call, bit for bit.  First-block caching, MX linears and LoRA work
+        with it; fp8 attention, Pyramid Attention Broadcast, a token-sharded plan and user-installed attention processors are
+        refused (here where they can be seen, else by the forward).  No reference counterpart."""
+        from .window_attention import WindowAttentionConfig
+        if not isinstance(config, WindowAttentionConfig):
+            raise TypeError(f"enable_window_attention takes a WindowAttentionConfig, got {type(config)}")
+        if any(li >= len(self.blocks) for li in config.skip_layers):
+            raise ValueError(f"skip_layers = {config.skip_layers}: this model has {len(self.blocks)} blocks")
+        self._window_refusals(config, self.parallel, self._pab_on, self._default_processors())
+        self._window = config
+        self._window_forwards = 0
+        self.window_attention_log = []
+        return self
+
+    def disable_window_attention(self):
+        self._window = None
+        return self
+
+    @property
+    def is_window_attention_enabled(self):
+        return self._window is not None
+
+    def _window_refusals(self, config, shard, pab_on, default_procs):
+        what = "window attention (enable_window_attention)"
+        if self.fp8_attention:
+            raise NotImplementedError(f"{what} with fp8 attention: the range walk exists in the bf16 / fp16 kernel only")
+        if pab_on:
+            raise NotImplementedError(f"{what} with Pyramid Attention Broadcast: not implemented in this version (first-block "
+                                      f"caching is)")
+        if shard is not None and getattr(shard, "active", True):
+            raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
+        if not default_procs:
+            raise NotImplementedError(f"{what} with a user-installed attention processor: the windows are applied by the "
+                                      f"built-in MI355WanAttnProcessor path only")
+
+    def enable_cache(self, config):
+        from .step_cache import _is_pab_config
+        if self._window is not None and _is_pab_config(config):
+            raise NotImplementedError("Pyramid Attention Broadcast with window attention (enable_window_attention): not "
+                                      "implemented in this version (first-block caching is)")
+        return super().enable_cache(config)
+
+    def _window_begin(self, ppf, tpf, id_frames, dev):
+        """This forward's window state, decided before anything is launched: None (off, or outside the timestep range), else
+        `.table(q_rows)` -> the device range table of those query rows, or None when it covers every key tile (the dense call)
+        -- and `.skip`, the blocks that stay dense.  Reads the timestep callback ONCE and appends to `window_attention_log`."""
+        cfg = self._window
+        if cfg is None:
+            return None
+        id_frames = int(id_frames or 0)
+        if not 0 <= id_frames < ppf:
+            raise ValueError(f"id_frames = {id_frames} of {ppf} latent frames")
+        t, on = None, True
+        if cfg.timestep_range is not None:
+            t = float(cfg.current_timestep_callback())
+            on = cfg.timestep_range[0] < t < cfg.timestep_range[1]
+        self.window_attention_log.append((self._window_forwards, t, on))
+        self._window_forwards += 1
+        if not on:
+            return None
+        from . import window_attention as wa
+        sinks = tuple(cfg.sink_frames) + tuple(range(ppf - id_frames, ppf))
+        L = ppf * tpf
+
+        def table(q_rows):
+            key = ("window", ppf, tpf, cfg.key(), id_frames, tuple(q_rows), str(dev))
+            if key not in self._rope_cache:
+                tab = wa.frame_window_ranges(ppf, tpf, cfg.window_frames, sinks, q_rows)
+                self._rope_cache[key] = None if wa.ranges_cover_all(tab, L) else tab.to(dev)
+            return self._rope_cache[key]
+
+        return SimpleNamespace(table=table, skip=frozenset(cfg.skip_layers))
+
+    @staticmethod
+    def _window_kw(c, li, q_rows):
+        """`ranges=` of block li's self-attention call over the query rows `q_rows`, or nothing (dense)"""
+        if c.win is None or li in c.win.skip:
+            return {}
+        tab = c.win.table(q_rows)
+        return {} if tab is None else {"ranges": tab}
 
     def _workspace(self, L, dtype, device):
         # one workspace per (shape, cache_context name): the two CFG branches may run concurrently on two streams
@@ -429,7 +522,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None,
-                return_dict=True, attention_kwargs=None, timestep_rows=None, live_rows=None, _cache_contexts=None):
+                return_dict=True, attention_kwargs=None, timestep_rows=None, live_rows=None, _cache_contexts=None,
+                id_frames=0):
         """`timestep_rows=(values [R], selector int32 [L])` is the de-duplicated form of a per-token timestep; when a
         2-D `timestep` is given instead it is de-duplicated here (torch.unique: host sync, eager only).
         `live_rows=(lo, hi)` (round 6): the caller will only read the output of token rows [lo, hi) -- the FrameINO loop drops the
@@ -442,10 +536,12 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         cache-context name per batch element, each element then decided on its own as if called alone under that context -- the
         pipeline's CFG-batched call passes ("cond", "uncond").  Without it a batch-B call under one `cache_context` makes one
         joint decision, as diffusers does (first-block caching: over the means of all its rows; Pyramid Attention Broadcast:
-        one counter and one [B * L, D] buffer per layer and kind for the whole batch)."""
+        one counter and one [B * L, D] buffer per layer and kind for the whole batch).
+        `id_frames` (window attention only, `enable_window_attention`): the trailing latent frames that are identity-reference
+        frames -- every query sees them, like the configured sink frames."""
         gen = self.forward_steps(hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image,
                                  return_dict, attention_kwargs, timestep_rows, live_rows=live_rows,
-                                 _cache_contexts=_cache_contexts)
+                                 _cache_contexts=_cache_contexts, id_frames=id_frames)
         while True:
             try:
                 next(gen)
@@ -454,7 +550,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
 
     def forward_steps(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None,
                       return_dict=True, attention_kwargs=None, timestep_rows=None, shard=None, live_rows=None,
-                      _cache_contexts=None):
+                      _cache_contexts=None, id_frames=0):
         """The forward as a generator that yields after the embedding stage and after every block, so that a caller
         can interleave two independent forwards (the CFG branches) kernel-stream by kernel-stream
         (frameino_amd/parallel.py: one branch's K|V all-gather then flies under the other branch's compute).  Every
@@ -469,7 +565,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._lora_apply(attention_kwargs.pop("scale", None) if attention_kwargs is not None else None)
         self._mx_requantise_if_pending()
         c = self._bind(hidden_states, timestep, encoder_hidden_states, attention_kwargs, timestep_rows, shard, live_rows,
-                       _cache_contexts)
+                       _cache_contexts, id_frames)
         self._embed(c, hidden_states)
         yield
 
@@ -529,7 +625,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         return t_rows, torch.arange(b, device=dev, dtype=torch.int32).repeat_interleave(n), False
 
     def _bind(self, hidden_states, timestep, encoder_hidden_states, attention_kwargs, timestep_rows, shard, live_rows,
-              cache_contexts):
+              cache_contexts, id_frames=0):
         """Everything the stages of one call share, as a `_Call`: geometry, this rank's token shard, workspace views, RoPE
         tables, modulation tables + selector, text K/V and the switches that pick a path."""
         o, cfg = self.ops, self.config
@@ -546,6 +642,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         # ---- token shard of this rank (frameino_amd/parallel.py); single GPU: the whole sequence ----
         sh = shard if shard is not None else self.parallel
         sh = sh if (sh is not None and sh.active) else None
+        if self._window is not None:             # what window attention refuses, before anything is launched
+            self._window_refusals(self._window, sh, self._pab_on, default_procs)
         lo, n, lpad = 0, L, L
         tk = {}         # the shard's tile height for its GEMM calls (a per-call argument of the C ABI; {} = the library's planner)
         if sh is not None:
@@ -592,11 +690,19 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             def attend(q_, k_, v_, heads_, **kw_):
                 return o.attention_fp8(q_, k_, v_, heads_, p_mode=getattr(self, "fp8_p_mode", None),
                                        smooth_k=getattr(self, "fp8_smooth_k", False), **kw_)
+        plain_attend = attend is o.attention
+        # sliding-window self-attention over frames: this forward's decision (the timestep callback is read here, once)
+        win = self._window_begin(ppf, pph * ppw, id_frames, dev)
+        if win is not None:
+            def attend(q_, k_, v_, heads_, ranges=None, **kw_):
+                if ranges is None:
+                    return o.attention(q_, k_, v_, heads_, **kw_)
+                return o.attention_ranges(q_, k_, v_, heads_, ranges, **kw_)
         # rows whose output the caller reads (`live_rows`): honoured in the last block on the single-GPU default-processor path
         live = None
         # (not under Pyramid Attention Broadcast: a cached branch output covers every row, so that any later step may use it)
         if (live_rows is not None and self.skip_dead_rows and default_procs and sh is None and len(self.blocks) > 1
-                and not self._fp8 and attend is o.attention and pab is None):
+                and not self._fp8 and plain_attend and pab is None):
             l0, l1 = int(live_rows[0]), int(live_rows[1])
             if 0 <= l0 < l1 <= n and (l1 - l0) < n:
                 live = (l0, l1)
@@ -608,7 +714,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                      text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
                      afold={"scale": o.SCALE_FOLDED} if fold else {}, attend=attend, default_procs=default_procs,
                      shared=shared, fbc=fbc, pab=pab, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
-                     live=live,
+                     live=live, win=win,
                      live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
                      rows=(0, n),            # the rows of every batch element that run as queries / per-token rows ...
                      segs=[(0, nr)])         # ... and the global row ranges the per-token operations of a block run on
@@ -670,7 +776,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._lin(li, "qkv", n1, e.wqkv, e.bqkv, out=q1)
         self._qk_norm_rope(blk, q1, d, c.cos1, c.sin1, c.dh, c.qfold)
         q3 = q1.view(1, n, 3 * d)
-        c.attend(q3[:, :, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, out=a1.view(1, n, d), **c.afold)
+        c.attend(q3[:, :, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, out=a1.view(1, n, d), **c.afold,
+                 **self._window_kw(c, li, (0, n)))
         self._lin(li, "out", a1, to_out.weight, to_out.bias, o.EPI_GATED_RESIDUAL, residual=x[:n], gate=m[:, 2], sel=sel1,
                   out=x[:n])
         for bi in range(1, c.b):
@@ -686,7 +793,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._qk_norm_rope(blk, c.qkv, d, c.cos, c.sin, c.dh, c.qfold)
         q3 = c.qkv.view(b, n, 3 * d)
         s0, s1 = c.rows                  # every row is a key; under `live_rows` only the live rows of the last block are queries
-        c.attend(q3[:, s0:s1, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, out=c.att.view(b, n, d)[:, s0:s1], **c.afold)
+        c.attend(q3[:, s0:s1, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, out=c.att.view(b, n, d)[:, s0:s1], **c.afold,
+                 **self._window_kw(c, li, (s0, s1)))
         return False
 
     def _sa_heads_exchange(self, c, li, blk, e, m):
@@ -937,7 +1045,7 @@ class _Call:
     __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
                  "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
                  "afold", "attend", "default_procs", "shared", "fbc", "pab", "keep", "h0", "h1c", "attention_kwargs", "live",
-                 "live_segs", "rows", "segs", "elements")
+                 "live_segs", "rows", "segs", "win", "elements")
 
     def __init__(self, **fields):
         self.elements = None

@@ -209,6 +209,22 @@ int fino_attn_fwd_tail(const void* q, const void* k, const void* v, void* o, int
                        int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs, int64_t o_rs, int64_t o_hs, float scale,
                        int dtype, const int* lk_b, const float* tail_mult, void* stream);
 
+/* fino_attn_fwd over a SUBSET of the key tiles, chosen per 256-row q-block: the sliding window over frames of a video DiT
+ * (every query sees its own latent frame +- a few neighbours and some sink frames; tokens are frame-major, so that is a few
+ * contiguous key ranges).  `ranges` is a DEVICE table int32 [ceil(lq / 256)][3][2], shared by all heads and batch elements:
+ * q-block i (query rows [256 i, 256 i + 256) of the q passed in) attends to the key tiles (64 keys each) of up to three
+ * ranges [begin, end), ascending and disjoint, an unused entry (0, 0).  Every range is clipped to [0, ceil(lk / 64)] by the
+ * kernel: a bad table gives a wrong answer, never a read outside k / v.  A q-block that walks the tiles T computes, in the same
+ * order and to the same bits, what fino_attn_fwd's LDS-DMA kernel computes over the keys of T gathered into one sequence; a
+ * q-block without tiles stores zeros.  Everything else -- arguments, strides, scale, the checks -- as fino_attn_fwd.  Always the
+ * LDS-DMA ping-pong kernel, whole blocks (no tail split, no workspace), head_dim 64 | 128, whatever lk or
+ * FINO_TUNE_ATTN_KERNEL say; the table is read by the launch, so it must stay alive until the stream has passed it. */
+int fino_attn_ranges_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim);
+int fino_attn_fwd_ranges(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq, int64_t lk,
+                         int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs, int64_t k_rs, int64_t k_hs,
+                         int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs, int64_t o_rs, int64_t o_hs, float scale,
+                         int dtype, const int* ranges, void* stream);
+
 /* Attention PROBABILITIES over a short key sequence (head_dim 128, lk <= 128 key rows allocated per sample, batch <= 4):
  * p[b][row][head][0 .. kp) = softmax(scale q.K^T) of that head's keys (kp a multiple of 8, >= every lk_b; columns from lk_b[b] on
  * are zeros; p_bs / p_rs in elements), lk_b / tail_mult as fino_attn_fwd_tail.  For the text cross-attention of
