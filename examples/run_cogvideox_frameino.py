@@ -60,6 +60,10 @@ def main():
     ap.add_argument("--fp8-attention", action="store_true", help="fp8 (e4m3) attention operands (reduced precision, opt-in)")
     ap.add_argument("--smooth-k", action="store_true",
                     help="with --fp8-attention: subtract the key mean before K is quantised (exact for the softmax)")
+    ap.add_argument("--window-frames", type=int, default=None, metavar="N",
+                    help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
+                         "a video query sees the text, its own latent frame +- N, the first frame and the identity frame; "
+                         "combines with --mxfp8 --fp8-attention --smooth-k")
     ap.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16",
                     help="dtype of transformer, VAE and text encoder.  Default fp16 = what the evaluation script loads all three in "
                          "(test_code/run_cogvideox_FrameIn_mass_evaluation.py:92-94,106)")
@@ -122,6 +126,9 @@ def main():
         transformer.enable_mxfp8_linears()
     if a.fp8_attention:
         transformer.enable_fp8_attention(smooth_k=a.smooth_k)
+    if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)
+        from frameino_amd.window_attention import WindowAttentionConfig
+        transformer.enable_window_attention(WindowAttentionConfig(window_frames=a.window_frames, sink_frames=(0,)))
 
     t0 = time.perf_counter()
     image, traj, id_tensor, pads = synthetic_conditions(a.frames, a.height, a.width, dev, a.frame_out)
@@ -147,6 +154,8 @@ def main():
         assert frames.shape == (a.frames, a.height, a.width, 3) and frames.dtype == np.uint8
         cond_s = f"conditions {tc - t0:.2f} s, " if rep == 0 else ""
         mode = ("mxfp8 linears" if a.mxfp8 else f"{a.dtype} linears") + ((" + fp8 attention" + (" (smooth K)" if a.smooth_k else "")) if a.fp8_attention else "")
+        if a.window_frames is not None:
+            mode += f" + window attention (+- {a.window_frames} frames)"
         print(f"{cond_s}clip ({a.frames} frames {a.height}x{a.width}, {a.steps} steps, {a.scheduler}, {mode}) {t2 - t1:.2f} s"
               f"{' (cold)' if rep == 0 and a.repeat > 1 else ''}, frames in [{frames.min()}, {frames.max()}], peak device memory "
               f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")

@@ -48,6 +48,9 @@ SIGNATURES = {
     "fino_attn_tail_supported": [c_int, c_int, c_i64, c_i64, c_int],
     "fino_attn_ranges_supported": [c_int, c_int, c_i64, c_i64, c_int],
     "fino_attn_fwd_ranges": [c_void_p] * 4 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 12 + [c_float, c_int, c_void_p, c_void_p],
+    "fino_attn_fp8_ranges_supported": [c_int, c_int, c_i64, c_i64, c_int],
+    "fino_attn_fwd_fp8_ranges": [c_void_p] * 4 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 8 + [c_float, c_int, c_int, c_void_p,
+                                                                                               c_i64, c_int, c_void_p, c_void_p],
     "fino_attn_fwd_tail": [c_void_p] * 4 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 12 + [c_float, c_int, c_void_p, c_void_p,
                                                                                             c_void_p],
     "fino_attn_probs_supported": [c_int, c_int, c_i64, c_i64, c_int],

@@ -139,6 +139,9 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         # in the last block, rows nobody reads afterwards (text rows; frames beyond forward(live_frames=)) are keys / values only
         self.skip_dead_rows = os.environ.get("FINO_SKIP_DEAD_ROWS", "1") != "0"
         self.original_attn_processors = None
+        self._window = None               # WindowAttentionConfig or None: see enable_window_attention
+        self._window_forwards = 0
+        self.window_attention_log = []    # (forward index, timestep or None, windowed) since enable_window_attention
 
     # ---- reference surface (:346-444) ----
     @property
@@ -191,7 +194,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         whenever the parameters may have changed or moved.  Returns whether MX linears were on (the next forward re-quantises)."""
         had_fp8 = self._mx_invalidate()
         self._packed = None
-        self._pos_cache.clear()
+        self._pos_cache.clear()           # (the window-attention range tables live here too)
         return had_fp8
 
     def _apply(self, fn, *args, **kwargs):          # .to() / .cuda() / .half()
@@ -227,6 +230,89 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         self.fp8_p_mode = p_mode
         self.fp8_smooth_k = bool(smooth_k)
         return self
+
+    # ---- sliding-window self-attention over frames ----
+    def enable_window_attention(self, config):
+        """Opt-in, approximate: in every block not in `config.skip_layers` a video query attends the text rows, its own latent
+        frame +- `config.window_frames` neighbours and the sink frames (`config.sink_frames`, and the trailing
+        `forward(id_frames=n)` frames) instead of every token; text queries and text keys stay dense.  `ops.attention_ranges`
+        -- or, with `enable_fp8_attention()`, `ops.attention_fp8_ranges` with the model's p_mode / smooth_k -- over a table of
+        key-tile ranges per 256 query rows (frameino_amd/window_attention.py, `prefix_rows` = the text rows; DESIGN.md section
+        6g).  A window that covers the whole clip takes the dense call, bit for bit.  MX linears and LoRA work with it; a
+        user-installed attention processor, and fp8 attention at a head_dim other than 64, are refused (here where they can be
+        seen, else by the forward before anything is launched).  No reference counterpart."""
+        from .window_attention import WindowAttentionConfig
+        if not isinstance(config, WindowAttentionConfig):
+            raise TypeError(f"enable_window_attention takes a WindowAttentionConfig, got {type(config)}")
+        if any(li >= len(self.transformer_blocks) for li in config.skip_layers):
+            raise ValueError(f"skip_layers = {config.skip_layers}: this model has {len(self.transformer_blocks)} blocks")
+        self._window_refusals(self._default_processors())
+        self._window = config
+        self._window_forwards = 0
+        self.window_attention_log = []
+        return self
+
+    def disable_window_attention(self):
+        self._window = None
+        return self
+
+    @property
+    def is_window_attention_enabled(self):
+        return self._window is not None
+
+    def _window_refusals(self, default_procs):
+        what = "window attention (enable_window_attention)"
+        if not default_procs:
+            raise NotImplementedError(f"{what} with a user-installed attention processor: the windows are applied by the "
+                                      f"built-in MI355CogVideoXAttnProcessor path only")
+        if self.fp8_attention and self.config.attention_head_dim != 64:
+            raise NotImplementedError(f"{what} with fp8 attention at head_dim {self.config.attention_head_dim}: the fp8 range "
+                                      f"walk (fino_attn_fwd_fp8_ranges) exists for head_dim 64 only")
+
+    def _window_begin(self, nf, tpf, lt, id_frames, dev):
+        """This forward's window state, decided before anything is launched: None (off, or outside the timestep range), else
+        `.table(q_rows)` -> the device range table of those rows of the joint sequence, or None when it covers every key tile
+        (the dense call) -- and `.skip`, the blocks that stay dense.  Reads the timestep callback ONCE and appends to
+        `window_attention_log`."""
+        cfg = self._window
+        if cfg is None:
+            return None
+        id_frames = int(id_frames or 0)
+        if not 0 <= id_frames < nf:
+            raise ValueError(f"id_frames = {id_frames} of {nf} latent frames")
+        t, on = None, True
+        if cfg.timestep_range is not None:
+            t = float(cfg.current_timestep_callback())
+            on = cfg.timestep_range[0] < t < cfg.timestep_range[1]
+        self.window_attention_log.append((self._window_forwards, t, on))
+        self._window_forwards += 1
+        if not on:
+            return None
+        from . import window_attention as wa
+        sinks = tuple(cfg.sink_frames) + tuple(range(nf - id_frames, nf))
+        L = lt + nf * tpf
+
+        def table(q_rows):
+            key = ("window", nf, tpf, lt, cfg.key(), id_frames, tuple(q_rows), str(dev))
+            if key not in self._pos_cache:
+                tab = wa.frame_window_ranges(nf, tpf, cfg.window_frames, sinks, q_rows, prefix_rows=lt)
+                self._pos_cache[key] = None if wa.ranges_cover_all(tab, L) else tab.to(dev)
+            return self._pos_cache[key]
+
+        return SimpleNamespace(table=table, skip=frozenset(cfg.skip_layers))
+
+    def _self_attention(self, ops, win, li, q_rows, q, k, v, heads, dh, afold):
+        """the joint self-attention of block li over the query rows `q_rows`: dense, or over this forward's range table"""
+        tab = None if win is None or li in win.skip else win.table(q_rows)
+        fp8 = self.fp8_attention and dh == 64
+        if fp8:
+            kw = dict(p_mode=getattr(self, "fp8_p_mode", None), smooth_k=getattr(self, "fp8_smooth_k", False), **afold)
+            if tab is not None:
+                return ops.attention_fp8_ranges(q, k, v, heads, tab, **kw)
+            return ops.attention_fp8(q, k, v, heads, **kw)
+        if tab is not None:
+            return ops.attention_ranges(q, k, v, heads, tab, **afold)
+        return ops.attention(q, k, v, heads, **afold)
 
     def _default_processors(self):
         return all(type(b.attn1.processor) in (MI355CogVideoXAttnProcessor, MI355FusedCogVideoXAttnProcessor)
@@ -285,12 +371,14 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
     # ---- forward (:446-562) ----
     @torch.no_grad()
     def forward(self, hidden_states, encoder_hidden_states, timestep, timestep_cond=None, ofs=None,
-                image_rotary_emb=None, attention_kwargs=None, return_dict=True, live_frames=None):
+                image_rotary_emb=None, attention_kwargs=None, return_dict=True, live_frames=None, id_frames=0):
         """`live_frames=k` (round 6): the caller reads the prediction of the first k latent frames only -- the FrameINO loop drops
         the identity frame appended on the frame axis (pipeline_cogvideox_i2v_motion_FrameINO.py:866-881, :896).  In the LAST block
         the other frames' tokens then serve as keys / values only, and so do the TEXT rows on every call (the model returns video
         rows only, :531-542): their attention queries, out-projection and feed-forward are skipped; dropped frames come back ZERO.
-        Every returned row is computed exactly as without it."""
+        Every returned row is computed exactly as without it.
+        `id_frames` (window attention only, `enable_window_attention`): the trailing latent frames that are identity-reference
+        frames; every query sees them, like `config.sink_frames`."""
         ops = self.ops
         if timestep_cond is not None:
             raise NotImplementedError("timestep_cond is never passed on the FrameINO path")
@@ -301,6 +389,8 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         self._mx_requantise_if_pending()
         pk = self._packed or self._pack()
         default_procs = self._default_processors()
+        if self._window is not None:             # what window attention refuses, before anything is launched
+            self._window_refusals(default_procs)
         c = self.config
         b, nf, ch, hh, ww = hidden_states.shape
         d, heads, dh, ps = self.inner_dim, c.num_attention_heads, c.attention_head_dim, c.patch_size
@@ -308,6 +398,8 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         lt = encoder_hidden_states.shape[1]
         lv = nf * (hh // ps) * (ww // ps)
         L = lt + lv
+        # sliding-window self-attention over frames: this forward's decision (the timestep callback is read here, once)
+        win = self._window_begin(nf, (hh // ps) * (ww // ps), lt, id_frames, dev)
 
         # 1. time embedding (:477-483): sinusoid fp32 -> T -> MLP in T
         half = d // 2
@@ -365,7 +457,8 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                 nq, nk = blk.attn1.norm_q, blk.attn1.norm_k
                 ops.headnorm_rope_(qkv[:, :, :d], heads, dh, nq.weight, nq.bias, nq.eps, cos, sin, rope_row0=lt, **qfold)
                 ops.headnorm_rope_(qkv[:, :, d:2 * d], heads, dh, nk.weight, nk.bias, nk.eps, cos, sin, rope_row0=lt)
-                att = ops.attention(qkv[:, r0:r1, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads, **afold)      # [B, r1 - r0, D]
+                att = self._self_attention(ops, win, li, (r0, r1), qkv[:, r0:r1, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:],
+                                           heads, dh, afold)                             # [B, r1 - r0, D]
                 for i in range(b):
                     xs, ss = x2[i * L + r0:i * L + r1], sel[i * L + r0:i * L + r1]
                     self._lin(li, "out", att[i], blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias,
@@ -384,12 +477,8 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                 nq, nk = blk.attn1.norm_q, blk.attn1.norm_k
                 ops.headnorm_rope_(qkv[:, :, :d], heads, dh, nq.weight, nq.bias, nq.eps, cos, sin, rope_row0=lt, **qfold)
                 ops.headnorm_rope_(qkv[:, :, d:2 * d], heads, dh, nk.weight, nk.bias, nk.eps, cos, sin, rope_row0=lt)
-                if self.fp8_attention and dh == 64:
-                    att = ops.attention_fp8(qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads,
-                                            p_mode=getattr(self, "fp8_p_mode", None),
-                                            smooth_k=getattr(self, "fp8_smooth_k", False), **afold)
-                else:
-                    att = ops.attention(qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads, **afold)
+                att = self._self_attention(ops, win, li, (0, L), qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads,
+                                           dh, afold)
                 self._lin(li, "out", att.view(b * L, d), blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias,
                           ops.EPI_GATED_RESIDUAL_STAGED, residual=x2, gate=t1[:, 2], sel=sel, out=x2)
             else:

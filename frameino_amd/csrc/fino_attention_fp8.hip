@@ -671,7 +671,14 @@ constexpr int kFrRing = 4;
 constexpr int kFrLdsK = 0, kFrLdsV = kFrRing * kTileK8, kFrLdsKS = 2 * kFrRing * kTileK8, kFrLdsVS = kFrLdsKS + kFrRing * 128;
 constexpr int kFrSmem = kFrLdsVS + kFrRing * 128;       // 33 KiB
 
-template <typename T, int PX>
+//
+// RG (fino_attn_fwd_fp8_ranges): the workgroup walks LOCAL tiles 0 .. nt - 1, which row qb >> 1 of p.ranges (one row per 256
+// query rows, as fino_attn_fwd_ranges: two of this kernel's 128-row blocks share a row) maps onto up to three runs of global
+// key tiles, g(t) = t + rg_d(t) -- PD_GTILE of fino_attention.hip.  Ring slots and the vmcnt counts go by the local index;
+// only the DMA's tile offset and the ragged mask see the global one.  The six integers are read once, clipped to [0, ntall]
+// and made wave-uniform, so g is scalar arithmetic; the buffer resources span the head's whole images either way (a bad table
+// can give a wrong answer, never a read outside them).  RG = false is the code it was.
+template <typename T, int PX, bool RG = false>
 __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8AttnParams fp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const AttnParams& p = fp.a;
@@ -691,26 +698,63 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
     const uint16_t* qp = p.q + bi * p.q_bs + head * p.q_hs;
     uint16_t* op = p.o + bi * p.o_bs + head * p.o_hs;
     const int64_t tile0 = (int64_t)hb * fp.nt;
-    const int nt = fp.nt;
+    const int ntall = fp.nt;
+    int nt = ntall;
     const int lk = p.lk;
 
     const int qrow = qb * kFrQBlock + wave * kQRowsPerWave + r;
+    int rg_c1 = 0, rg_c2 = 0, rg_d0 = 0, rg_d1 = 0, rg_d2 = 0, rg_rag = -1;
+    if constexpr (RG) {
+        const int* rg = p.ranges + (int64_t)(qb >> 1) * 6;
+        int b_[3], n_[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            int b = __builtin_amdgcn_readfirstlane(rg[2 * i]), e = __builtin_amdgcn_readfirstlane(rg[2 * i + 1]);
+            b = b < 0 ? 0 : (b > ntall ? ntall : b);
+            e = e < b ? b : (e > ntall ? ntall : e);
+            b_[i] = b;
+            n_[i] = e - b;
+        }
+        rg_c1 = n_[0];
+        rg_c2 = n_[0] + n_[1];
+        nt = rg_c2 + n_[2];
+        rg_d0 = b_[0];
+        rg_d1 = b_[1] - rg_c1;
+        rg_d2 = b_[2] - rg_c2;
+        if (nt == 0) {
+            // an empty q-block: zeros for its rows, no ring touched (the whole workgroup leaves: nt is uniform)
+            if (qrow < p.lq) {
+                uint16_t* orow = op + (int64_t)qrow * p.o_rs + 4 * g;
+#pragma unroll
+                for (int i = 0; i < kD8 / 8; ++i) *reinterpret_cast<uint2*>(orow + 8 * i) = make_uint2(0u, 0u);
+            }
+            return;
+        }
+    }
+    // local tile -> global tile; T_ < nt (the callers clamp: nt > 0 from here on)
+#define FR_GTILE(T_) ((T_) + ((T_) < rg_c1 ? rg_d0 : ((T_) < rg_c2 ? rg_d1 : rg_d2)))
+    if constexpr (RG) {
+        // the ragged tile is the LAST global tile; ranges ascend, so it can only be the last tile walked
+        if ((lk & (kKV - 1)) && FR_GTILE(nt - 1) == ntall - 1) rg_rag = nt - 1;
+    }
     i32x8_t qf;
     int q_scale;
     load_q_fp8<T>(p, qp, qrow, g, qf, q_scale);
 
     // ---- staging: wave w moves LDS positions 64 w .. 64 w + 63 (16-byte slots) of the K8 and of the V8T image, and (lanes
     //      0..31) the K scales (waves 0, 2) or the V scales (waves 1, 3): three vector-memory operations per wave and tile ----
-    const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(fp.k8 + tile0 * kTileK8), 0, nt * kTileK8, 0x00020000);
-    const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(fp.v8t + tile0 * kTileK8), 0, nt * kTileK8, 0x00020000);
+    const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(fp.k8 + tile0 * kTileK8), 0, ntall * kTileK8, 0x00020000);
+    const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(fp.v8t + tile0 * kTileK8), 0, ntall * kTileK8, 0x00020000);
     const bool sc_k = (wave & 1) == 0;
-    const __amdgpu_buffer_rsrc_t s_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((sc_k ? fp.ks : fp.vs) + tile0 * 128), 0, nt * 128, 0x00020000);
+    const __amdgpu_buffer_rsrc_t s_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((sc_k ? fp.ks : fp.vs) + tile0 * 128), 0, ntall * 128, 0x00020000);
     const int st_pos = wave * 64 + lane;
     const uint32_t st_voff = (uint32_t)((st_pos >> 2) * 64 + (((st_pos & 3) ^ swz8(st_pos >> 2)) << 4));
     const int st_slds = sc_k ? kFrLdsKS : kFrLdsVS;
+    // past the last tile walked: a harmless re-read of that tile (RG: of its global image)
 #define FR_DMA(U_)                                                                                           \
     {                                                                                                        \
-        const int tt_ = (U_) < nt ? (U_) : nt - 1;                                                           \
+        const int tc_ = (U_) < nt ? (U_) : nt - 1;                                                           \
+        const int tt_ = RG ? FR_GTILE(tc_) : tc_;                                                            \
         const int sl_ = (U_) & (kFrRing - 1);                                                                \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(k_rsrc, (FINO_LDS void*)(smem + kFrLdsK + sl_ * kTileK8 + wave * 1024), 16, \
                                                  st_voff, tt_ * kTileK8, 0, 0);                              \
@@ -763,8 +807,8 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
         S1_ = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k1_, qf, C1_, 0, 0, 0, ks1r, 0, q_scale);      \
     }
 #define FR_MASK(T_, S0_, S1_)                                                                                \
-    if (__builtin_expect((T_) == nt - 1 && (lk & (kKV - 1)), 0)) {                                           \
-        int rem_ = lk - (T_) * kKV - 4 * g;                                                                  \
+    if (__builtin_expect(RG ? (T_) == rg_rag : ((T_) == nt - 1 && (lk & (kKV - 1))), 0)) {                   \
+        int rem_ = lk - (RG ? ntall - 1 : (T_)) * kKV - 4 * g;                                               \
         asm volatile("" : "+v"(rem_));                                                                       \
         _Pragma("unroll") for (int j_ = 0; j_ < 16; ++j_) {                                                  \
             const int key_ = (j_ & 3) + 8 * (j_ >> 2);                                                       \
@@ -887,6 +931,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
 #undef FRX_BARRIER
 #undef FR_PV
 #undef FR_DMA
+#undef FR_GTILE
 #undef FR_KREAD
 #undef FR_QK
 #undef FR_MASK
@@ -1207,14 +1252,17 @@ extern "C" int64_t fino_attn_fp8_smooth_kv_bytes(int batch, int heads, int64_t l
     return ((base + 15) & ~(int64_t)15) + (int64_t)batch * heads * head_dim * 4 * (1 + kmean_chunks(lk));
 }
 
-// both entry points: `smooth` = mean -> smoothing quantiser, otherwise the plain quantiser; the main-kernel launch is the same
+// every entry point: `smooth` = mean -> smoothing quantiser, otherwise the plain quantiser; the main-kernel launch is the same.
+// `ranges` (fino_attn_fwd_fp8_ranges): head_dim 64 only, always attn_fp8_fr_kernel<T, PX, true>, whatever the tuning knob says.
 static int attn_fwd_fp8_impl(const char* fn, bool smooth, const void* q, const void* k, const void* v, void* o, int batch, int heads,
                              int64_t lq, int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
                              int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode,
-                             void* kv_workspace, int64_t kv_workspace_bytes, void* stream) {
+                             void* kv_workspace, int64_t kv_workspace_bytes, void* stream, const int* ranges = nullptr) {
     FINO_CHECK(p_mode == FINO_FP8_P_EXP2 || p_mode == FINO_FP8_P_RAMP, FINO_ERR_ARG, "%s: p_mode %d", fn, p_mode);
     FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "%s: dtype %d", fn, dtype);
     FINO_CHECK(head_dim == 64 || head_dim == 128, FINO_ERR_UNSUPPORTED, "%s: head_dim %d not in {64, 128}", fn, head_dim);
+    FINO_CHECK(!ranges || head_dim == 64, FINO_ERR_UNSUPPORTED, "%s: head_dim %d: the range walk exists for head_dim 64 only", fn,
+               head_dim);
     FINO_CHECK(q && k && v && o && kv_workspace, FINO_ERR_ARG, "%s: null pointer", fn);
     FINO_CHECK(batch > 0 && heads > 0 && lq >= 0 && lk > 0, FINO_ERR_ARG, "%s: bad shape", fn);
     FINO_CHECK(fino_aligned16(q) && fino_aligned16(k) && fino_aligned16(v) && fino_aligned16(o) &&
@@ -1271,10 +1319,10 @@ static int attn_fwd_fp8_impl(const char* fn, bool smooth, const void* q, const v
     p.scale_log2 = scale == FINO_ATTN_SCALE_FOLDED ? 1.0f : scale * 1.4426950408889634f;
     const bool ramp = p_mode == FINO_FP8_P_RAMP;
     if (ramp) p.scale_log2 *= 8.0f;          // logits in eighths of an octave: an exact shift of q's e8m0 block scales
-    const bool free_running = head_dim == 64 && fino_tune_get(FINO_TUNE_ATTN_FP8_KERNEL) != 1;   // default at head_dim 64
+    const bool free_running = head_dim == 64 && (ranges || fino_tune_get(FINO_TUNE_ATTN_FP8_KERNEL) != 1);   // default at head_dim 64
     const int qblock = free_running ? kFrQBlock : kQBlock;
     p.nqb = (int)((lq + qblock - 1) / qblock);
-    p.ws = nullptr; p.all_partial = 0; p.tail_n = 0; p.ranges = nullptr;
+    p.ws = nullptr; p.all_partial = 0; p.tail_n = 0; p.ranges = ranges;
     attn_virtual_heads(p.batch, p.heads, p.nqb, p.vsplit, p.nqb_v);
     const int groups = (p.batch * p.heads * p.vsplit + 7) / 8;
     p.full_x = groups * p.nqb_v; p.rem_x = 0; p.nwg = 0; p.per = 1;
@@ -1295,9 +1343,11 @@ static int attn_fwd_fp8_impl(const char* fn, bool smooth, const void* q, const v
         if (rc_ != FINO_OK) return rc_;                                                                                   \
     }
 #define K_FR(T_, PX_) attn_fp8_fr_kernel<T_, PX_>
+#define K_FR_RG(T_, PX_) attn_fp8_fr_kernel<T_, PX_, true>
 #define K_D128(T_, PX_) attn_fp8_d128_kernel<T_, PX_>
 #define K_PP(T_, PX_) attn_fp8_kernel<T_, 0, PX_>
-        F8_LAUNCH(K_FR, grid, kFrWaves * 64, kFrSmem)
+        if (ranges) F8_LAUNCH(K_FR_RG, grid, kFrWaves * 64, kFrSmem)
+        else F8_LAUNCH(K_FR, grid, kFrWaves * 64, kFrSmem)
         FINO_LAUNCH_CHECK();
         return FINO_OK;
     }
@@ -1337,4 +1387,21 @@ extern "C" int fino_attn_fwd_fp8_smooth(const void* q, const void* k, const void
                                         int p_mode, void* kv_workspace, int64_t kv_workspace_bytes, void* stream) {
     return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smooth", true, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs, v_bs,
                              v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream);
+}
+
+// fp8 attention over up to three ranges of key tiles per 256 query rows (include/frameino_hip.h): fino_attn_fwd_fp8's
+// arguments and checks + smooth_k + the device table; head_dim 64 only, always the free-running kernel's range walk.
+extern "C" int fino_attn_fp8_ranges_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim) {
+    return head_dim == 64 && batch > 0 && heads > 0 && lq > 0 && lk > 0 && lq < (1ll << 31) - 256 && lk < (1ll << 31) - 64;
+}
+
+extern "C" int fino_attn_fwd_fp8_ranges(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
+                                        int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
+                                        int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype,
+                                        int p_mode, void* kv_workspace, int64_t kv_workspace_bytes, int smooth_k,
+                                        const int* ranges, void* stream) {
+    FINO_CHECK(ranges, FINO_ERR_ARG, "fino_attn_fwd_fp8_ranges: null ranges table");
+    FINO_CHECK(((uintptr_t)ranges & 3) == 0, FINO_ERR_ARG, "fino_attn_fwd_fp8_ranges: the ranges table must be 4-byte aligned");
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_ranges", smooth_k != 0, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs,
+                             k_rs, v_bs, v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream, ranges);
 }

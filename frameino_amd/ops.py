@@ -281,6 +281,16 @@ def attention(q, k, v, heads, out=None, scale=None):
     return out
 
 
+def _ranges_pairs(ranges, lq, lk):
+    """(query row, key) pairs of one head that a ranges launch walks"""
+    nta = (lk + 63) // 64
+    pairs = 0.0
+    for i, blk in enumerate(ranges.clamp(0, nta).tolist()):
+        keys = sum(max(0, min(e * 64, lk) - s * 64) for s, e in blk)
+        pairs += float(min(256, lq - 256 * i)) * keys
+    return pairs
+
+
 def attention_ranges_supported(b, heads, lq, lk, dh):
     return bool(_lib.lib().fino_attn_ranges_supported(int(b), int(heads), int(lq), int(lk), int(dh)))
 
@@ -311,13 +321,7 @@ def attention_ranges(q, k, v, heads, ranges, out=None, scale=None):
         ev.record()
         kt_ = KernelTimer.active
         # FLOPs and bytes from the tiles walked (the table's host copy is read only here, under the timer: one sync per launch)
-        nta = (lk + 63) // 64
-        r = ranges.clamp(0, nta).tolist()
-        pairs = 0.0                                             # (query row, key) pairs of one head
-        for i, blk in enumerate(r):
-            keys = sum(max(0, min(e * 64, lk) - s * 64) for s, e in blk)
-            pairs += float(min(256, lq - 256 * i)) * keys
-        kt_.flops["attn_self"] = kt_.flops.get("attn_self", 0.0) + 4.0 * b * pairs * hd
+        kt_.flops["attn_self"] = kt_.flops.get("attn_self", 0.0) + 4.0 * b * _ranges_pairs(ranges, lq, lk) * hd
         kt_.bytes["attn_self"] = kt_.bytes.get("attn_self", 0.0) + 2.0 * b * hd * (2 * lq + 2 * lk)
     return out
 
@@ -451,6 +455,47 @@ def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=Fa
         kt_ = KernelTimer.active
         nm = "attn_self" if lk > 1024 else "attn_cross"
         kt_.flops[nm] = kt_.flops.get(nm, 0.0) + 4.0 * b * lq * lk * hd
+    return out
+
+
+def attention_fp8_ranges_supported(b, heads, lq, lk, dh):
+    return bool(_lib.lib().fino_attn_fp8_ranges_supported(int(b), int(heads), int(lq), int(lk), int(dh)))
+
+
+def attention_fp8_ranges(q, k, v, heads, ranges, out=None, scale=None, p_mode=None, smooth_k=False):
+    """attention_fp8() over the subset of key tiles attention_ranges() walks: the same int32 DEVICE table [ceil(Lq / 256), 3, 2]
+    per 256 query rows (fino_attn_fwd_fp8_ranges; head_dim 64 only).  K / V are quantised whole, and `smooth_k` subtracts the mean
+    over ALL keys: the softmax over any subset of them cannot see it either.  A q-block without tiles gets zeros."""
+    p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
+    assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
+    b, lq, hd = q.shape
+    lk = k.shape[1]
+    dh = hd // heads
+    for t in (q, k, v):
+        assert t.stride(2) == 1 and t.is_cuda
+    nqb = (lq + 255) // 256
+    assert ranges.dtype == torch.int32 and ranges.is_cuda and ranges.is_contiguous() and tuple(ranges.shape) == (nqb, 3, 2), \
+        f"ranges: an int32 device tensor [{nqb}, 3, 2] is needed, got {ranges.dtype} {tuple(ranges.shape)} on {ranges.device}"
+    if out is None:
+        out = torch.empty((b, lq, hd), dtype=q.dtype, device=q.device)
+    scale = dh ** -0.5 if scale is None else scale
+    if dh != 64:
+        raise RuntimeError(f"attention_fp8_ranges: head_dim {dh} is not supported (64 only)")
+    need = (_lib.lib().fino_attn_fp8_smooth_kv_bytes if smooth_k else _lib.lib().fino_attn_fp8_kv_bytes)(b, heads, lk, dh)
+    key = (q.device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _attn_fp8_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _attn_fp8_ws[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ev = _timed("attn_self")
+    _lib.check(_lib.lib().fino_attn_fwd_fp8_ranges(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
+                                                  k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0),
+                                                  out.stride(1), float(scale), _dt(q), int(p_mode), _p(ws), need,
+                                                  1 if smooth_k else 0, _p(ranges), _stream()), "fino_attn_fwd_fp8_ranges")
+    if ev is not None:
+        ev.record()
+        kt_ = KernelTimer.active
+        # FLOPs from the tiles walked (the table's host copy is read only here, under the timer: one sync per launch)
+        kt_.flops["attn_self"] = kt_.flops.get("attn_self", 0.0) + 4.0 * b * _ranges_pairs(ranges, lq, lk) * hd
     return out
 
 

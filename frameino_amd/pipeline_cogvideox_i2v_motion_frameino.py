@@ -93,6 +93,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         self.vae_scale_factor_temporal = 4
         self.vae_scaling_factor_image = getattr(getattr(vae, "config", None), "scaling_factor", 0.7)
         self._interrupt = False
+        self._current_timestep = None
         self.use_hip_graph = None            # None: replay the step from a captured hipGraph whenever the loop is
         #                                      capturable (no per-step callback); False: eager; True: capture or raise
 
@@ -214,6 +215,22 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
                              f"directly, but got: `prompt_embeds` {prompt_embeds.shape} != `negative_prompt_embeds` "
                              f"{negative_prompt_embeds.shape}.")
 
+    @property
+    def current_timestep(self):
+        return self._current_timestep
+
+    def _window_attention_check(self):
+        """the limits of window attention (CogVideoXTransformer3DModel.enable_window_attention), checked before any work.  ->
+        whether the loop must run eagerly: with a timestep range the host decides per step whether the windows apply."""
+        cfg = getattr(self.transformer, "_window", None)
+        if cfg is None or cfg.timestep_range is None:
+            return False                      # off, or the range table is a static device tensor: the step captures as it is
+        if self.use_hip_graph is True:
+            raise RuntimeError("use_hip_graph=True with window attention under a timestep range: whether a step's self-attention "
+                               "is windowed changes from step to step on the host's schedule, which one captured step cannot "
+                               "contain (the loop runs eagerly; use_hip_graph=None or False)")
+        return True
+
     def _prepare_rotary_positional_embeddings(self, height, width, num_frames, device):
         """reference :540-584 (patch_size_t None) + the FrameIn first-frame extension :834-839."""
         c = self.transformer.config
@@ -236,6 +253,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         None; returns the final latents [1, F, C, h, w] in the transformer dtype."""
         tr = self.transformer
         dev, dt = latents.device, tr.dtype
+        win_eager = self._window_attention_check()
         if latents.shape[0] != 1:
             # A batch (a list of prompts, batched `prompt_embeds` / `latents`) runs video by video: the loop state -- the static
             # model-input buffer, the sampler history, the captured graph -- is one video's.  The videos of a batched loop never
@@ -287,6 +305,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         nf_in = nlf + (0 if id_latent is None else id_latent.shape[1])
         st = SimpleNamespace(lat=lat, nlf=nlf, C=C, cfg_on=cfg_on, dpm=dpm, prompt=prompt, rot=image_rotary_emb,
                              attention_kwargs=attention_kwargs)
+        st.id_frames = nf_in - nlf            # window attention: the identity-reference frame is a sink (FrameOut: none)
         st.x = torch.zeros((nb, nf_in, 3 * C) + tuple(lat.shape[2:]), dtype=dt, device=dev)
         if id_latent is not None:
             st.x[:, nlf:, :C] = idl                                                             # :868 (img / trj pads stay 0)
@@ -299,11 +318,12 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         from .graph_step import StepGraph
         from .pipeline_wan_i2v_motion_frameino import tr_default_procs
         stepper = StepGraph(lambda: self._step(st), self.use_hip_graph,
-                            callback_on_step_end is None and lat.is_cuda
+                            callback_on_step_end is None and lat.is_cuda and not win_eager
                             and (self.use_hip_graph is True or tr_default_procs(tr)), len(ts))
         for i, t in enumerate(ts):
             if self._interrupt:
                 continue
+            self._current_timestep = t
             st.t.copy_(t.expand(nb))                          # device-to-device: no host sync
             st.coef.copy_(coefs[i])
             if dpm:
@@ -313,6 +333,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
                 out = callback_on_step_end(self, i, t, {"latents": lat[None]})
                 if "latents" in out and out["latents"] is not None:
                     lat.copy_(out["latents"][0])
+        self._current_timestep = None
         stepper.close()
         return lat[None]
 
@@ -322,6 +343,8 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         # (live_frames: the identity frame appended on the frame axis is dropped from the prediction, :896 -- the model may skip
         # what only that frame's output needs; only passed to the mirror's own transformer class)
         live = {"live_frames": st.nlf} if (st.x.shape[1] > st.nlf and getattr(self.transformer, "skip_dead_rows", False)) else {}
+        if getattr(self.transformer, "is_window_attention_enabled", False):      # (this package's transformer only, as above)
+            live["id_frames"] = st.id_frames
         pred = self.transformer(hidden_states=st.x, encoder_hidden_states=st.prompt, timestep=st.t,
                                 image_rotary_emb=st.rot, attention_kwargs=st.attention_kwargs, return_dict=False, **live)[0]
         if st.dpm:

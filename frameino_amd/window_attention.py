@@ -3,7 +3,12 @@
 Every query attends its own latent frame +- `window_frames` neighbours plus a few "sink" frames that every query always sees
 (the conditioning first frame, the identity-reference frames appended at the end).  Tokens are frame-major, so for one 256-row
 q-block "window + sinks" is at most three contiguous key ranges: the table `frame_window_ranges` builds is what
-`ops.attention_ranges` (fino_attn_fwd_ranges) walks -- per q-block up to three [begin, end) ranges of 64-key tiles.
+`ops.attention_ranges` (fino_attn_fwd_ranges) and `ops.attention_fp8_ranges` (fino_attn_fwd_fp8_ranges) walk -- per q-block up
+to three [begin, end) ranges of 64-key tiles.
+
+Both backbones use it.  The Wan DiT's sequence is the frames alone; the CogVideoX DiT's joint sequence is
+[text | frame 0 | ... | frame F - 1 (| ID frame)], which `prefix_rows` describes: the text rows are keys every query sees and
+queries that see every key.
 
 The granularity is the kernel's: a q-block's window is the union over its rows (a block that straddles two frames sees both
 frames' windows) and frame boundaries are rounded OUTWARD to key tiles, so a query may see up to 63 keys of a frame just outside
@@ -30,19 +35,26 @@ def _sink_frames(frames, sink_frames):
     return sorted(set(out))
 
 
-def frame_window_ranges(frames, tokens_per_frame, window_frames, sink_frames=(0,), q_rows=None):
+def frame_window_ranges(frames, tokens_per_frame, window_frames, sink_frames=(0,), q_rows=None, prefix_rows=0):
     """-> CPU int32 [nqb, 3, 2]: per q-block of the query rows `q_rows` = (s0, s1) (default: all L = frames x tokens_per_frame
     rows; q-blocks are counted from s0) up to three ascending, disjoint [begin, end) ranges of key tiles, unused entries (0, 0).
     For q-block rows [r0, r1): f0 = r0 // tpf, f1 = (r1 - 1) // tpf; the window is frames [max(0, f0 - w), min(F, f1 + w + 1)),
     every sink frame s (negatives count from the end) is [s, s + 1); a frame interval [a, b) becomes the tiles
     [a tpf // 64, min(ntall, ceil(b tpf / 64))); intervals that overlap or touch are merged.  ValueError if more than three
-    ranges remain (sinks in the middle of the clip)."""
+    ranges remain (sinks in the middle of the clip).
+    prefix_rows = p > 0: p rows (the text of a joint sequence) sit in front of frame 0, L = p + F tpf.  A q-block with any row < p is
+    dense, [0, ntall).  Any other has f0 = (r0 - p) // tpf, f1 = (r1 - 1 - p) // tpf and sees the ROW intervals [0, p) (the prefix),
+    [p + max(0, f0 - w) tpf, p + min(F, f1 + w + 1) tpf) (the window) and [p + s tpf, p + (s + 1) tpf) per sink frame s, each
+    rounded outward to tiles, merged as above."""
     frames, tpf, w = int(frames), int(tokens_per_frame), int(window_frames)
     if frames < 1 or tpf < 1:
         raise ValueError(f"frames = {frames}, tokens_per_frame = {tpf}: both must be >= 1")
     if w < 0:
         raise ValueError(f"window_frames = {w}: must be >= 0")
-    L = frames * tpf
+    p = int(prefix_rows)
+    if p < 0:
+        raise ValueError(f"prefix_rows = {p}: must be >= 0")
+    L = p + frames * tpf
     ntall = -(-L // KEY_TILE)
     s0, s1 = (0, L) if q_rows is None else (int(q_rows[0]), int(q_rows[1]))
     if not 0 <= s0 < s1 <= L:
@@ -53,9 +65,13 @@ def frame_window_ranges(frames, tokens_per_frame, window_frames, sink_frames=(0,
     for i in range(nqb):
         r0 = s0 + Q_BLOCK * i
         r1 = min(r0 + Q_BLOCK, s1)
-        f0, f1 = r0 // tpf, (r1 - 1) // tpf
+        if r0 < p:
+            table[i, 0, 1] = ntall
+            continue
+        f0, f1 = (r0 - p) // tpf, (r1 - 1 - p) // tpf
         spans = [(max(0, f0 - w), min(frames, f1 + w + 1))] + [(s, s + 1) for s in sinks]
-        tiles = sorted((a * tpf // KEY_TILE, min(ntall, -(-b * tpf // KEY_TILE))) for a, b in spans)
+        rows = [(p + a * tpf, p + b * tpf) for a, b in spans] + ([(0, p)] if p else [])
+        tiles = sorted((a // KEY_TILE, min(ntall, -(-b // KEY_TILE))) for a, b in rows)
         merged = [list(tiles[0])]
         for a, b in tiles[1:]:
             if a <= merged[-1][1]:
@@ -83,9 +99,12 @@ def ranges_cover_all(table, lk):
     return bool(((table[:, 0, 0] <= 0) & (table[:, 0, 1] >= ntall)).all())
 
 
-def block_mask(table, lq, lk):
+def block_mask(table, lq, lk, prefix_rows=0):
     """the boolean [lq, lk] mask of what `ops.attention_ranges` computes under `table` (query rows counted from the table's
-    first q-block)"""
+    first q-block).  `prefix_rows` is the one the table was built with: the table already carries the prefix (as a key range and
+    as dense q-blocks), so it changes nothing here beyond the check that the prefix fits into the keys."""
+    if not 0 <= int(prefix_rows) <= int(lk):
+        raise ValueError(f"prefix_rows = {prefix_rows} is outside the {lk} key rows")
     mask = torch.zeros((int(lq), int(lk)), dtype=torch.bool)
     for i, blk in enumerate(table.tolist()):
         for a, b in blk:
@@ -95,7 +114,8 @@ def block_mask(table, lq, lk):
 
 @dataclass
 class WindowAttentionConfig:
-    """`WanTransformer3DModel.enable_window_attention(config)`.
+    """`WanTransformer3DModel.enable_window_attention(config)` and `CogVideoXTransformer3DModel.enable_window_attention(config)`:
+    one class serves both models (the CogVideoX model adds its text rows as `prefix_rows` when it builds the table).
 
     window_frames: every query sees its own latent frame +- this many neighbours.
     sink_frames: latent frames every query sees (negatives count from the end); `forward(id_frames=n)` adds the trailing n.

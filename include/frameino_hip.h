@@ -224,6 +224,21 @@ int fino_attn_fwd_ranges(const void* q, const void* k, const void* v, void* o, i
                          int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs, int64_t k_rs, int64_t k_hs,
                          int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs, int64_t o_rs, int64_t o_hs, float scale,
                          int dtype, const int* ranges, void* stream);
+/* fino_attn_fwd_fp8 (smooth_k = 0) or fino_attn_fwd_fp8_smooth (smooth_k != 0) over the SUBSET of key tiles fino_attn_fwd_ranges
+ * walks: the same DEVICE table, int32 [ceil(lq / 256)][3][2] per 256 query rows (the kernel's workgroups hold 128 rows: two of them
+ * share a table row), clipped to [0, ceil(lk / 64)] by the kernel -- a bad table gives a wrong answer, never a read outside the
+ * workspace images -- non-null and 4-byte aligned.  Replaces what fino_attn_fwd_fp8 replaces (the SDPA at
+ * architecture/attention_processor.py:2863) under a block mask; no reference counterpart, like fino_attn_fwd_ranges.  The
+ * pre-pass quantises ALL keys (and the smooth-K mean is the mean over all keys: exact for a softmax over any subset, every logit
+ * of a query moves by the same q.mean), so the workspace is what fino_attn_fp8_kv_bytes / fino_attn_fp8_smooth_kv_bytes say.  A
+ * 256-row q-block that walks the tiles T computes, to the same bits, what fino_attn_fwd_fp8's default kernel computes for those
+ * query rows over the keys of T gathered into one sequence; a q-block without tiles stores zeros.  head_dim 64 only
+ * (FINO_ERR_UNSUPPORTED otherwise); always the free-running 4-wave kernel, whatever FINO_TUNE_ATTN_FP8_KERNEL says. */
+int fino_attn_fp8_ranges_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim);
+int fino_attn_fwd_fp8_ranges(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq, int64_t lk,
+                             int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs,
+                             int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode, void* kv_workspace,
+                             int64_t kv_workspace_bytes, int smooth_k, const int* ranges, void* stream);
 
 /* Attention PROBABILITIES over a short key sequence (head_dim 128, lk <= 128 key rows allocated per sample, batch <= 4):
  * p[b][row][head][0 .. kp) = softmax(scale q.K^T) of that head's keys (kp a multiple of 8, >= every lk_b; columns from lk_b[b] on
