@@ -64,6 +64,13 @@ def main():
                     help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
                          "a video query sees the text, its own latent frame +- N, the first frame and the identity frame; "
                          "combines with --mxfp8 --fp8-attention --smooth-k")
+    ap.add_argument("--pab", type=int, default=None, metavar="N",
+                    help="Pyramid Attention Broadcast (approximate; quality on real checkpoints unmeasured): inside --pab-range a "
+                         "step recomputes the joint self-attention branch on every N-th forward and re-uses its previous output "
+                         "otherwise (spatial_attention_block_skip_range=N); the loop runs eagerly; combines with --mxfp8 "
+                         "--fp8-attention --smooth-k --window-frames")
+    ap.add_argument("--pab-range", type=int, nargs=2, default=(100, 800), metavar=("LO", "HI"),
+                    help="with --pab: the timesteps (strictly between LO and HI) at which the branch may be re-used")
     ap.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16",
                     help="dtype of transformer, VAE and text encoder.  Default fp16 = what the evaluation script loads all three in "
                          "(test_code/run_cogvideox_FrameIn_mass_evaluation.py:92-94,106)")
@@ -129,6 +136,11 @@ def main():
     if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)
         from frameino_amd.window_attention import WindowAttentionConfig
         transformer.enable_window_attention(WindowAttentionConfig(window_frames=a.window_frames, sink_frames=(0,)))
+    if a.pab is not None:
+        from frameino_amd.step_cache import PyramidAttentionBroadcastConfig
+        transformer.enable_cache(PyramidAttentionBroadcastConfig(
+            spatial_attention_block_skip_range=a.pab, spatial_attention_timestep_skip_range=tuple(a.pab_range),
+            current_timestep_callback=lambda: pipe.current_timestep))
 
     t0 = time.perf_counter()
     image, traj, id_tensor, pads = synthetic_conditions(a.frames, a.height, a.width, dev, a.frame_out)
@@ -156,6 +168,10 @@ def main():
         mode = ("mxfp8 linears" if a.mxfp8 else f"{a.dtype} linears") + ((" + fp8 attention" + (" (smooth K)" if a.smooth_k else "")) if a.fp8_attention else "")
         if a.window_frames is not None:
             mode += f" + window attention (+- {a.window_frames} frames)"
+        if a.pab is not None:
+            computed = sum(1 for e in transformer.cache_log if e[3])
+            mode += (f" + Pyramid Attention Broadcast (every {a.pab}. forward in {tuple(a.pab_range)}: "
+                     f"{computed} of {len(transformer.cache_log)} steps computed the attention branch)")
         print(f"{cond_s}clip ({a.frames} frames {a.height}x{a.width}, {a.steps} steps, {a.scheduler}, {mode}) {t2 - t1:.2f} s"
               f"{' (cold)' if rep == 0 and a.repeat > 1 else ''}, frames in [{frames.min()}, {frames.max()}], peak device memory "
               f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")

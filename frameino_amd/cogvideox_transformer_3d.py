@@ -24,6 +24,7 @@ from .attention_processor import Attention, MI355CogVideoXAttnProcessor, MI355Fu
 from .loading import FromPretrainedMixin
 from .lora import LoraModelMixin
 from .mx_linears import MXLinearsMixin
+from .step_cache import PyramidAttentionBroadcastMixin
 from .transformer_wan import FeedForward, _Config, _MLP2
 
 
@@ -80,9 +81,22 @@ def cog_sincos_pos_embed(embed_dim, pw, ph, frames, spatial_scale, temporal_scal
     return torch.cat([temporal, spatial], dim=-1).flatten(0, 1)
 
 
-class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, MXLinearsMixin):
+class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, PyramidAttentionBroadcastMixin, MXLinearsMixin):
     """MX linears (enable_mxfp8_linears / enable_mxfp6_linears): four large linears of every block -- QKV, attention out, FFN
-    up / down; with `enable_fp8_attention()` MXFP8 is BASELINE config 5's "fp8 MFMA path" end to end."""
+    up / down; with `enable_fp8_attention()` MXFP8 is BASELINE config 5's "fp8 MFMA path" end to end.
+
+    Step caching (diffusers' CacheMixin surface: enable_cache / disable_cache / is_cache_enabled / cache_context /
+    _reset_stateful_cache, and `cache_log`; frameino_amd/step_cache.py): Pyramid Attention Broadcast,
+    `enable_cache(PyramidAttentionBroadcastConfig(spatial_attention_block_skip_range=2, current_timestep_callback=...))`.  Opt-in
+    and approximate.  Every block's joint attn1 is the "spatial" kind; per `cache_context` and layer one [B L, D] buffer in the
+    model dtype holds y = T(acc + bias) of `attn1.to_out[0]` over the joint [text | video] rows (the CFG batch of 2 is one
+    segment with one decision), written by the out-projection's own epilogue (`keep=`) on a computing forward.  A re-using forward
+    launches nothing of the branch -- no norm1, QKV, head norm + RoPE, attention, out-projection -- and adds the cached y with the
+    staged epilogue's arithmetic (`ops.gated_residual(staged=True)`).  With the cache enabled the LAST block runs all L rows
+    (`skip_dead_rows` is off: the cache must hold every row for the forwards that re-use it); the returned rows and the
+    `live_frames` zeros are what they are without it.  A user-installed processor is cached by its return value.  MX linears,
+    fp8 attention, LoRA and window attention combine with it: the cache stores whatever the branch produced.  At BASELINE
+    config 5 the buffers are 42 x 235 MB = 9.9 GB.  `FirstBlockCacheConfig` is refused."""
     _loader_name = "load_cogvideox_transformer"
 
     def __init__(self, num_attention_heads=30, attention_head_dim=64, in_channels=16, out_channels=16,
@@ -190,9 +204,11 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         return self
 
     def reset_caches(self):
-        """Drop everything derived from the parameters (packed / fused copies, MX weights, positional tables); called
-        whenever the parameters may have changed or moved.  Returns whether MX linears were on (the next forward re-quantises)."""
+        """Drop everything derived from the parameters (packed / fused copies, MX weights, positional tables, the step cache's
+        buffers); called whenever the parameters may have changed or moved.  Returns whether MX linears were on (the next forward
+        re-quantises)."""
         had_fp8 = self._mx_invalidate()
+        self._reset_stateful_cache()
         self._packed = None
         self._pos_cache.clear()           # (the window-attention range tables live here too)
         return had_fp8
@@ -314,6 +330,36 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
             return ops.attention_ranges(q, k, v, heads, tab, **afold)
         return ops.attention(q, k, v, heads, **afold)
 
+    def _attention_branch(self, ops, win, li, blk, e, x2, t1, sel, b, L, lt, cos, sin, qfold, afold, default_procs,
+                          image_rotary_emb, attention_kwargs, kept):
+        """the first half of block li over all rows: x2 += gate * attn1(norm1(x2)) in place.  `kept` (Pyramid Attention
+        Broadcast, a computing forward): the [B L, D] buffer that also receives the branch output y = T(acc + bias) -- from the
+        out-projection's epilogue, or a user-installed processor's return value"""
+        c = self.config
+        d, heads, dh = self.inner_dim, c.num_attention_heads, c.attention_head_dim
+        # CogVideoXLayerNormZero emitted directly as the linear's MXFP8 activations (None when it is not on that path)
+        xq1 = (self._ln_q(li, "qkv", 2, x2, weight=e.n1w, bias=e.n1b, shift=t1[:, 0], scale=t1[:, 1], sel=sel, eps=c.norm_eps)
+               if default_procs else None)
+        n = None if xq1 is not None else ops.layernorm_zero(x2, e.n1w, e.n1b, t1[:, 0], t1[:, 1], sel, c.norm_eps)
+        if default_procs:
+            qkv = self._lin(li, "qkv", n, e.wqkv, e.bqkv, xq=xq1).view(b, L, 3 * d)
+            nq, nk = blk.attn1.norm_q, blk.attn1.norm_k
+            ops.headnorm_rope_(qkv[:, :, :d], heads, dh, nq.weight, nq.bias, nq.eps, cos, sin, rope_row0=lt, **qfold)
+            ops.headnorm_rope_(qkv[:, :, d:2 * d], heads, dh, nk.weight, nk.bias, nk.eps, cos, sin, rope_row0=lt)
+            att = self._self_attention(ops, win, li, (0, L), qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads,
+                                       dh, afold)
+            keep = {} if kept is None else {"keep": kept}
+            self._lin(li, "out", att.view(b * L, d), blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias,
+                      ops.EPI_GATED_RESIDUAL_STAGED, residual=x2, gate=t1[:, 2], sel=sel, out=x2, **keep)
+        else:
+            n3 = n.view(b, L, d)
+            ah, ae = blk.attn1(hidden_states=n3[:, lt:], encoder_hidden_states=n3[:, :lt],
+                               image_rotary_emb=image_rotary_emb, **(attention_kwargs or {}))
+            y = torch.cat([ae, ah], dim=1).reshape(b * L, d)
+            if kept is not None:
+                y = kept.copy_(y)
+            ops.gated_residual(x2, y, t1[:, 2], sel, out=x2, staged=True)
+
     def _default_processors(self):
         return all(type(b.attn1.processor) in (MI355CogVideoXAttnProcessor, MI355FusedCogVideoXAttnProcessor)
                    for b in self.transformer_blocks)
@@ -376,7 +422,8 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         the identity frame appended on the frame axis (pipeline_cogvideox_i2v_motion_FrameINO.py:866-881, :896).  In the LAST block
         the other frames' tokens then serve as keys / values only, and so do the TEXT rows on every call (the model returns video
         rows only, :531-542): their attention queries, out-projection and feed-forward are skipped; dropped frames come back ZERO.
-        Every returned row is computed exactly as without it.
+        Every returned row is computed exactly as without it.  With a step cache enabled (`enable_cache`) the last block runs
+        all rows -- the cache holds every row's branch output -- and the same rows and zeros are returned.
         `id_frames` (window attention only, `enable_window_attention`): the trailing latent frames that are identity-reference
         frames; every query sees them, like `config.sink_frames`."""
         ops = self.ops
@@ -400,6 +447,11 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         L = lt + lv
         # sliding-window self-attention over frames: this forward's decision (the timestep callback is read here, once)
         win = self._window_begin(nf, (hh // ps) * (ww // ps), lt, id_frames, dev)
+        # Pyramid Attention Broadcast: this forward's decision for every block's attn1 (callback read once, nothing launched yet);
+        # the call's rows are ONE segment under the current cache_context
+        pab = self._pab_begin(b, L, d, dt, dev)
+        seg = pab.segs[0] if pab is not None and pab.hooked["self"] else None
+        reuse = seg is not None and not seg.compute["self"]
 
         # 1. time embedding (:477-483): sinusoid fp32 -> T -> MLP in T
         half = d // 2
@@ -447,10 +499,13 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                      and (r1 - r0) < L)
         if not skip_dead:
             kf, r0, r1 = nf, lt, L
+        # Pyramid Attention Broadcast: the cache holds every row of every block's branch, so the last block runs all L rows; what
+        # is returned (the live frames' rows, zeros for the others) stays
+        skip_dead_block = skip_dead and pab is None
         # 3. blocks (:503-529)
         for li, (blk, e) in enumerate(zip(self.transformer_blocks, pk.layers)):
             t1, t2 = tables[2 * li], tables[2 * li + 1]                              # [2B, 3, D]
-            if skip_dead and li == len(self.transformer_blocks) - 1:
+            if skip_dead_block and li == len(self.transformer_blocks) - 1:
                 # LAST block: every row is a key / value, only rows [r0, r1) of each sample are queries and go on
                 n = ops.layernorm_zero(x2, e.n1w, e.n1b, t1[:, 0], t1[:, 1], sel, c.norm_eps)
                 qkv = self._lin(li, "qkv", n, e.wqkv, e.bqkv).view(b, L, 3 * d)
@@ -468,25 +523,15 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                     self._lin(li, "ff2", ff, blk.ff.net[2].weight, blk.ff.net[2].bias, ops.EPI_GATED_RESIDUAL_STAGED,
                               residual=xs, gate=t2[:, 2], sel=ss, out=xs)
                 continue
-            # CogVideoXLayerNormZero emitted directly as the linear's MXFP8 activations (None when it is not on that path)
-            xq1 = (self._ln_q(li, "qkv", 2, x2, weight=e.n1w, bias=e.n1b, shift=t1[:, 0], scale=t1[:, 1], sel=sel, eps=c.norm_eps)
-                   if default_procs else None)
-            n = None if xq1 is not None else ops.layernorm_zero(x2, e.n1w, e.n1b, t1[:, 0], t1[:, 1], sel, c.norm_eps)
-            if default_procs:
-                qkv = self._lin(li, "qkv", n, e.wqkv, e.bqkv, xq=xq1).view(b, L, 3 * d)
-                nq, nk = blk.attn1.norm_q, blk.attn1.norm_k
-                ops.headnorm_rope_(qkv[:, :, :d], heads, dh, nq.weight, nq.bias, nq.eps, cos, sin, rope_row0=lt, **qfold)
-                ops.headnorm_rope_(qkv[:, :, d:2 * d], heads, dh, nk.weight, nk.bias, nk.eps, cos, sin, rope_row0=lt)
-                att = self._self_attention(ops, win, li, (0, L), qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads,
-                                           dh, afold)
-                self._lin(li, "out", att.view(b * L, d), blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias,
-                          ops.EPI_GATED_RESIDUAL_STAGED, residual=x2, gate=t1[:, 2], sel=sel, out=x2)
+            if reuse:
+                # Pyramid Attention Broadcast, a re-using forward: nothing of the attention branch runs; the y the last computing
+                # forward kept goes through the arithmetic of the out-projection's staged epilogue
+                ops.gated_residual(x2, self._pab_buffer(seg, "self", li), t1[:, 2], sel, out=x2, staged=True)
             else:
-                n3 = n.view(b, L, d)
-                ah, ae = blk.attn1(hidden_states=n3[:, lt:], encoder_hidden_states=n3[:, :lt],
-                                   image_rotary_emb=image_rotary_emb, **(attention_kwargs or {}))
-                y = torch.cat([ae, ah], dim=1).reshape(b * L, d)
-                ops.gated_residual(x2, y, t1[:, 2], sel, out=x2, staged=True)
+                # (... a computing forward: the out-projection also writes y = T(acc + bias) into this layer's buffer)
+                kept = None if seg is None else self._pab_buffer(seg, "self", li, d, dt, dev)
+                self._attention_branch(ops, win, li, blk, e, x2, t1, sel, b, L, lt, cos, sin, qfold, afold, default_procs,
+                                       image_rotary_emb, attention_kwargs, kept)
             xq2 = (self._ln_q(li, "ff1", 2, x2, weight=e.n2w, bias=e.n2b, shift=t2[:, 0], scale=t2[:, 1], sel=sel, eps=c.norm_eps)
                    if (li, "ff2") in self._fp8 else None)
             n = None if xq2 is not None else ops.layernorm_zero(x2, e.n2w, e.n2b, t2[:, 0], t2[:, 1], sel, c.norm_eps)

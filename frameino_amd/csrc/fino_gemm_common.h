@@ -398,4 +398,27 @@ int mx_dispatch_epilogue(int epi, F&& launch) {
     }
 }
 
+// the keep buffer of fino_gemm_mxfp8_keep / fino_gemm_mxfp6_keep (after mx_gemm_params): the residual epilogues only; the
+// buffer rides in c2 / ldc2 with n_split = 0, as in fino_gemm_keep
+inline int mx_gemm_keep_params(MxGemmParams& fp, const char* who, int epilogue, void* keep, int64_t ldk) {
+    FINO_CHECK(epilogue == FINO_EPI_RESIDUAL || epilogue == FINO_EPI_GATED_RESIDUAL ||
+                   epilogue == FINO_EPI_GATED_RESIDUAL_STAGED,
+               FINO_ERR_ARG, "%s: epilogue %d (the residual epilogues %d, %d and %d keep y)", who, epilogue,
+               FINO_EPI_RESIDUAL, FINO_EPI_GATED_RESIDUAL, FINO_EPI_GATED_RESIDUAL_STAGED);
+    FINO_CHECK(keep && fino_aligned16(keep) && ldk % 8 == 0 && ldk >= fp.g.n, FINO_ERR_ARG,
+               "%s: needs a 16-byte aligned keep buffer with ldk >= N a multiple of 8", who);
+    fp.g.c2 = (uint16_t*)keep; fp.g.ldc2 = ldk; fp.g.n_split = 0;
+    return FINO_OK;
+}
+
+// ... and the three epilogues the KEEP kernels are instantiated for (the caller has checked `epi`)
+template <typename F>
+int mx_dispatch_keep_epilogue(int epi, F&& launch) {
+    switch (epi) {
+        case FINO_EPI_RESIDUAL: return launch(std::integral_constant<int, FINO_EPI_RESIDUAL>{});
+        case FINO_EPI_GATED_RESIDUAL_STAGED: return launch(std::integral_constant<int, FINO_EPI_GATED_RESIDUAL_STAGED>{});
+        default: return launch(std::integral_constant<int, FINO_EPI_GATED_RESIDUAL>{});
+    }
+}
+
 }  // namespace fino_gemm_ns

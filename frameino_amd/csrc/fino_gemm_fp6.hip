@@ -133,7 +133,8 @@ __device__ __forceinline__ u32x4_t buffer_desc(const void* ptr, uint32_t bytes) 
                    (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(a >> 32) & 0xffffu)), bytes, 0x00020000u};
 }
 
-template <typename T, int EPI>
+// KEEP (fino_gemm_mxfp6_keep; residual epilogues): the shared epilogue also stores its staged y = T(acc + bias) to g.c2
+template <typename T, int EPI, bool KEEP = false>
 __global__ __launch_bounds__(kThreads, 2) void gemm_mxfp6_kernel(const MxGemmParams fp) {   // g.a / w = fragment images
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const GemmParams& p = fp.g;
@@ -294,14 +295,14 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_mxfp6_kernel(const MxGemmPar
 #undef F6_DMA_A
 #undef F6_DMA_W
 #undef F6_DMA_S
-    gemm_epilogue<T, EPI, false>(acc, p, smem, m0, n0, tid, lane, wm, wn);
+    gemm_epilogue<T, EPI, false, 8, KEEP>(acc, p, smem, m0, n0, tid, lane, wm, wn);
 }
 
-template <typename T, int EPI>
+template <typename T, int EPI, bool KEEP = false>
 int launch_mxfp6(const MxGemmParams& fp, hipStream_t st) {
     static FinoPerDeviceOnce once;
-    if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&gemm_mxfp6_kernel<T, EPI>), kSmem6, "fino_gemm_mxfp6")) return rc;
-    gemm_mxfp6_kernel<T, EPI><<<dim3((unsigned)(fp.g.tiles_m * fp.g.tiles_n)), kThreads, kSmem6, st>>>(fp);
+    if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&gemm_mxfp6_kernel<T, EPI, KEEP>), kSmem6, "fino_gemm_mxfp6")) return rc;
+    gemm_mxfp6_kernel<T, EPI, KEEP><<<dim3((unsigned)(fp.g.tiles_m * fp.g.tiles_n)), kThreads, kSmem6, st>>>(fp);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }
@@ -309,6 +310,11 @@ int launch_mxfp6(const MxGemmParams& fp, hipStream_t st) {
 template <typename T>
 int launch_mxfp6_e(const MxGemmParams& fp, int epi, hipStream_t st) {
     return mx_dispatch_epilogue(epi, [&](auto e) { return launch_mxfp6<T, decltype(e)::value>(fp, st); });
+}
+
+template <typename T>
+int launch_mxfp6_keep(const MxGemmParams& fp, int epi, hipStream_t st) {
+    return mx_dispatch_keep_epilogue(epi, [&](auto e) { return launch_mxfp6<T, decltype(e)::value, true>(fp, st); });
 }
 
 }  // namespace
@@ -359,4 +365,20 @@ extern "C" int fino_gemm_mxfp6(const void* aq, const void* a_scales, const void*
                "fino_gemm_mxfp6: operand > 2 GiB");
     hipStream_t st = (hipStream_t)stream;
     return out_dtype == FINO_BF16 ? launch_mxfp6_e<BF16>(fp, epilogue, st) : launch_mxfp6_e<F16>(fp, epilogue, st);
+}
+
+extern "C" int fino_gemm_mxfp6_keep(const void* aq, const void* a_scales, const void* wq, const void* w_scales,
+                                    const void* bias, void* c, int64_t m, int64_t n, int64_t k, int64_t ldc, int epilogue,
+                                    const void* r, int64_t ldr, const float* gate, int64_t mod_stride, const int32_t* sel,
+                                    int out_dtype, void* keep, int64_t ldk, void* stream) {
+    MxGemmParams fp;
+    if (int rc = mx_gemm_params(fp, "fino_gemm_mxfp6_keep", false, aq, a_scales, wq, w_scales, bias, c, m, n, k, ldc, epilogue,
+                                r, ldr, gate, mod_stride, sel, out_dtype))
+        return rc;
+    if (int rc = mx_gemm_keep_params(fp, "fino_gemm_mxfp6_keep", epilogue, keep, ldk)) return rc;
+    if (m == 0) return FINO_OK;
+    FINO_CHECK(fp.m_pad * k < (1ll << 31) && fp.n_pad * k < (1ll << 31), FINO_ERR_UNSUPPORTED,
+               "fino_gemm_mxfp6_keep: operand > 2 GiB");
+    hipStream_t st = (hipStream_t)stream;
+    return out_dtype == FINO_BF16 ? launch_mxfp6_keep<BF16>(fp, epilogue, st) : launch_mxfp6_keep<F16>(fp, epilogue, st);
 }

@@ -48,7 +48,8 @@ __global__ __launch_bounds__(256) void mxfp8_quantize_kernel(const uint16_t* __r
 }
 
 // ---------------------------------------------------------------------------------------------------- GEMM
-template <typename T, int EPI, bool QOUT>
+// KEEP (fino_gemm_mxfp8_keep; residual epilogues): the shared epilogue also stores its staged y = T(acc + bias) to g.c2
+template <typename T, int EPI, bool QOUT, bool KEEP = false>
 __global__ __launch_bounds__(kThreads, 2) void gemm_mxfp8_kernel(const MxGemmParams fp) {   // g.lda / ldw in BYTES (= elements)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const GemmParams& p = fp.g;
@@ -204,14 +205,22 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_mxfp8_kernel(const MxGemmPar
 #undef F8_DMA_A
 #undef F8_DMA_W
 #undef F8_DMA_S
-    gemm_epilogue<T, EPI, QOUT>(acc, p, smem, m0, n0, tid, lane, wm, wn);
+    if constexpr (KEEP) {
+        // opaque copies: what the epilogue derives from the thread index is computed here, not hoisted above the main loop,
+        // which has no register to spare for it
+        int tid_e = tid, lane_e = lane;
+        asm volatile("" : "+v"(tid_e), "+v"(lane_e));
+        gemm_epilogue<T, EPI, QOUT, 8, true>(acc, p, smem, m0, n0, tid_e, lane_e, wm, wn);
+    } else {
+        gemm_epilogue<T, EPI, QOUT>(acc, p, smem, m0, n0, tid, lane, wm, wn);
+    }
 }
 
-template <typename T, int EPI, bool QOUT = false>
+template <typename T, int EPI, bool QOUT = false, bool KEEP = false>
 int launch_mxfp8(const MxGemmParams& fp, hipStream_t st) {
     static FinoPerDeviceOnce once;
-    if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&gemm_mxfp8_kernel<T, EPI, QOUT>), kSmemF8, "fino_gemm_mxfp8")) return rc;
-    gemm_mxfp8_kernel<T, EPI, QOUT><<<dim3((unsigned)(fp.g.tiles_m * fp.g.tiles_n)), kThreads, kSmemF8, st>>>(fp);
+    if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&gemm_mxfp8_kernel<T, EPI, QOUT, KEEP>), kSmemF8, "fino_gemm_mxfp8")) return rc;
+    gemm_mxfp8_kernel<T, EPI, QOUT, KEEP><<<dim3((unsigned)(fp.g.tiles_m * fp.g.tiles_n)), kThreads, kSmemF8, st>>>(fp);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }
@@ -219,6 +228,11 @@ int launch_mxfp8(const MxGemmParams& fp, hipStream_t st) {
 template <typename T>
 int launch_mxfp8_e(const MxGemmParams& fp, int epi, hipStream_t st) {
     return mx_dispatch_epilogue(epi, [&](auto e) { return launch_mxfp8<T, decltype(e)::value>(fp, st); });
+}
+
+template <typename T>
+int launch_mxfp8_keep(const MxGemmParams& fp, int epi, hipStream_t st) {
+    return mx_dispatch_keep_epilogue(epi, [&](auto e) { return launch_mxfp8<T, decltype(e)::value, false, true>(fp, st); });
 }
 
 }  // namespace
@@ -287,4 +301,19 @@ extern "C" int fino_gemm_mxfp8(const void* aq, const void* a_scales, const void*
     if (m == 0) return FINO_OK;
     hipStream_t st = (hipStream_t)stream;
     return out_dtype == FINO_BF16 ? launch_mxfp8_e<BF16>(fp, epilogue, st) : launch_mxfp8_e<F16>(fp, epilogue, st);
+}
+
+extern "C" int fino_gemm_mxfp8_keep(const void* aq, const void* a_scales, const void* wq, const void* w_scales,
+                                    const void* bias, void* c, int64_t m, int64_t n, int64_t k, int64_t ldc, int epilogue,
+                                    const void* r, int64_t ldr, const float* gate, int64_t mod_stride, const int32_t* sel,
+                                    int out_dtype, void* keep, int64_t ldk, void* stream) {
+    MxGemmParams fp;
+    if (int rc = mx_gemm_params(fp, "fino_gemm_mxfp8_keep", false, aq, a_scales, wq, w_scales, bias, c, m, n, k, ldc, epilogue,
+                                r, ldr, gate, mod_stride, sel, out_dtype))
+        return rc;
+    if (int rc = mx_gemm_keep_params(fp, "fino_gemm_mxfp8_keep", epilogue, keep, ldk)) return rc;
+    FINO_CHECK(m * k < (1ll << 31) && n * k < (1ll << 31), FINO_ERR_UNSUPPORTED, "fino_gemm_mxfp8_keep: operand > 2 GiB");
+    if (m == 0) return FINO_OK;
+    hipStream_t st = (hipStream_t)stream;
+    return out_dtype == FINO_BF16 ? launch_mxfp8_keep<BF16>(fp, epilogue, st) : launch_mxfp8_keep<F16>(fp, epilogue, st);
 }

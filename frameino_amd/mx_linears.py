@@ -96,13 +96,9 @@ class MXLinearsMixin:
             mx_gemm, (xq, xs) = o.gemm_mxfp6, o.quantize_mxfp6(x)
         else:
             mx_gemm, (xq, xs) = o.gemm_mxfp8, (xq if xq is not None else o.quantize_mxfp8(x))
-        if keep is None:
-            return mx_gemm(xq, xs, wq[0], wq[1], b, epi, **kw)
-        # keep on an MX linear: two launches -- y = T(acc + bias) into the keep buffer, then the (gated) residual from it
-        if epi not in (o.EPI_RESIDUAL, o.EPI_GATED_RESIDUAL):
-            raise NotImplementedError(f"_lin(keep=...): epilogue {epi}")
-        mx_gemm(xq, xs, wq[0], wq[1], b, o.EPI_NONE, out=keep)
-        return o.pab_broadcast(kw["residual"], keep, kw.get("gate"), kw.get("sel"), out=kw["out"])
+        if keep is not None:
+            kw["keep"] = keep                                   # one launch: fino_gemm_mxfp8_keep / fino_gemm_mxfp6_keep
+        return mx_gemm(xq, xs, wq[0], wq[1], b, epi, **kw)
 
     def _ffn_mxfp8(self, li, x, xq, b1, b2, epi, **kw):
         """The FFN of block `li` as one MXFP8 pair: the up-projection's GELU epilogue emits the hidden activations already

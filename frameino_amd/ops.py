@@ -644,28 +644,40 @@ def ln_mxfp8(mode, x, weight=None, bias=None, shift=None, scale=None, sel=None, 
     return q, s
 
 
-def _mx_gemm(entry, aq, a_scales, wq, w_scales, bias, epilogue, residual, gate, sel, out, out_dtype, m, n, k):
-    """what gemm_mxfp8 and gemm_mxfp6 share once the operands are checked: `entry` names the library's entry point"""
+def _mx_gemm(entry, aq, a_scales, wq, w_scales, bias, epilogue, residual, gate, sel, out, out_dtype, m, n, k, keep=None):
+    """what gemm_mxfp8 and gemm_mxfp6 share once the operands are checked: `entry` names the library's entry point (with
+    `keep`, its `_keep` form)"""
     if out is None:
         out = torch.empty((m, n), dtype=out_dtype, device=aq.device)
     o2, _, _, ldc = _rows2d(out)
     r2, ldr, ms = _epi_operands(residual, gate)
     done = _timed_gemm(None, 2.0 * m * n * k)
-    _lib.check(getattr(_lib.lib(), entry)(_p(aq), _p(a_scales), _p(wq), _p(w_scales), _p(bias), _p(o2), m, n, k, ldc,
-                                          epilogue, _p(r2), ldr, _p(gate), ms, _p(sel), _dt(out), _stream()), entry)
+    if keep is not None:
+        k2, km, kn, ldk = _rows2d(keep)
+        assert (km, kn) == (m, n) and keep.dtype == out.dtype and keep.is_cuda
+        entry += "_keep"
+        _lib.check(getattr(_lib.lib(), entry)(_p(aq), _p(a_scales), _p(wq), _p(w_scales), _p(bias), _p(o2), m, n, k, ldc,
+                                              epilogue, _p(r2), ldr, _p(gate), ms, _p(sel), _dt(out), _p(k2), ldk, _stream()),
+                   entry)
+    else:
+        _lib.check(getattr(_lib.lib(), entry)(_p(aq), _p(a_scales), _p(wq), _p(w_scales), _p(bias), _p(o2), m, n, k, ldc,
+                                              epilogue, _p(r2), ldr, _p(gate), ms, _p(sel), _dt(out), _stream()), entry)
     if done is not None:
         done()
     return out
 
 
 def gemm_mxfp8(aq, a_scales, wq, w_scales, bias=None, epilogue=EPI_NONE, residual=None, gate=None, sel=None, out=None,
-               out_dtype=torch.bfloat16):
-    """C = epilogue(dequant(aq).dequant(wq)^T + bias): aq [M, K], wq [N, K] uint8 (e4m3) + their MX scales."""
+               out_dtype=torch.bfloat16, keep=None):
+    """C = epilogue(dequant(aq).dequant(wq)^T + bias): aq [M, K], wq [N, K] uint8 (e4m3) + their MX scales.
+    `keep` [M, N] row-strided (residual epilogues only; fino_gemm_mxfp8_keep): as in `gemm` -- also receives y = T(acc + bias),
+    what EPI_NONE would return; `out` is what the call without it returns."""
     m, k = aq.shape
     n = wq.shape[0]
     assert wq.shape[1] == k and aq.dtype == torch.uint8 and wq.dtype == torch.uint8 and aq.is_contiguous() \
         and wq.is_contiguous()
-    return _mx_gemm("fino_gemm_mxfp8", aq, a_scales, wq, w_scales, bias, epilogue, residual, gate, sel, out, out_dtype, m, n, k)
+    return _mx_gemm("fino_gemm_mxfp8", aq, a_scales, wq, w_scales, bias, epilogue, residual, gate, sel, out, out_dtype, m, n, k,
+                    keep)
 
 
 def gemm_mxfp8_q(aq, a_scales, wq, w_scales, bias, epilogue=EPI_NONE, out=None):
@@ -697,10 +709,10 @@ def quantize_mxfp6(x, out=None):
 
 
 def gemm_mxfp6(aq, a_scales, wq, w_scales, bias=None, epilogue=EPI_NONE, residual=None, gate=None, sel=None, out=None,
-               out_dtype=torch.bfloat16, m=None, n=None, k=None):
+               out_dtype=torch.bfloat16, m=None, n=None, k=None, keep=None):
     """C = epilogue(dequant(aq).dequant(wq)^T + bias): aq / wq the packed images quantize_mxfp6 made of [M, K] / [N, K].  The
     images are flat byte tensors; quantize_mxfp6 notes the matrix shape on them (`q.mx_shape`), and `m` / `n` / `k` say it for
-    images that came another way (a view, a copy)."""
+    images that came another way (a view, a copy).  `keep`: as in `gemm_mxfp8` (fino_gemm_mxfp6_keep)."""
     assert aq.dtype == torch.uint8 and wq.dtype == torch.uint8 and aq.is_contiguous() and wq.is_contiguous()
     sa_, sw_ = getattr(aq, "mx_shape", None), getattr(wq, "mx_shape", None)
     m = m if m is not None else (sa_[0] if sa_ else None)
@@ -713,7 +725,8 @@ def gemm_mxfp6(aq, a_scales, wq, w_scales, bias=None, epilogue=EPI_NONE, residua
     lib = _lib.lib()
     if aq.numel() != lib.fino_mxfp6_bytes(m, k) or wq.numel() != lib.fino_mxfp6_bytes(n, k):
         raise ValueError(f"gemm_mxfp6: operand sizes {aq.numel()} / {wq.numel()} do not match M={m} N={n} K={k}")
-    return _mx_gemm("fino_gemm_mxfp6", aq, a_scales, wq, w_scales, bias, epilogue, residual, gate, sel, out, out_dtype, m, n, k)
+    return _mx_gemm("fino_gemm_mxfp6", aq, a_scales, wq, w_scales, bias, epilogue, residual, gate, sel, out, out_dtype, m, n, k,
+                    keep)
 
 
 def skinny_linear(x, w, b=None, silu_input=False):

@@ -11,7 +11,15 @@ plus `_prepare_rotary_positional_embeddings` (:540-584) with the FrameIn extensi
 T5 objects, third-party on both sides, once per clip -- or pre-computed `prompt_embeds`; the condition encodes and the
 decode run on the `vae` handed in (frameino_amd.autoencoder_kl_cogvideox, or any object with the diffusers
 AutoencoderKLCogVideoX interface); `denoise()` works on latents alone.
+
+Pyramid Attention Broadcast (`pipe.transformer.enable_cache(PyramidAttentionBroadcastConfig(spatial_attention_block_skip_range=2,
+current_timestep_callback=lambda: pipe.current_timestep))`, frameino_amd/step_cache.py): every step's transformer call runs under
+`cache_context("cond_uncond")` as in diffusers' CogVideoX pipelines -- the CFG batch of 2 makes one joint decision -- and the loop
+runs eagerly (`use_hip_graph = True` raises; graph replay returns after `disable_cache()`).  The cache state starts fresh in every
+single-video loop and is dropped at its end and by `maybe_free_model_hooks()`; `transformer.cache_log` keeps the last loop's
+decisions.
 """
+import contextlib
 import math
 from types import SimpleNamespace
 
@@ -219,6 +227,23 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
     def current_timestep(self):
         return self._current_timestep
 
+    def maybe_free_model_hooks(self):
+        # diffusers resets every component's stateful cache here, at the end of each call
+        reset = getattr(self.transformer, "_reset_stateful_cache", None)
+        if callable(reset):
+            reset()
+
+    def _step_cache_check(self):
+        """the limits of Pyramid Attention Broadcast (CogVideoXTransformer3DModel.enable_cache), checked before any work.  ->
+        whether a step cache is enabled: the loop then runs eagerly."""
+        if not getattr(self.transformer, "is_cache_enabled", False):
+            return False
+        if self.use_hip_graph is True:
+            raise RuntimeError("use_hip_graph=True with Pyramid Attention Broadcast: which steps run the attention branch changes "
+                               "from step to step on the host's schedule, which one captured step cannot contain (the loop runs "
+                               "eagerly; use_hip_graph=None or False)")
+        return True
+
     def _window_attention_check(self):
         """the limits of window attention (CogVideoXTransformer3DModel.enable_window_attention), checked before any work.  ->
         whether the loop must run eagerly: with a timestep range the host decides per step whether the windows apply."""
@@ -254,6 +279,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         tr = self.transformer
         dev, dt = latents.device, tr.dtype
         win_eager = self._window_attention_check()
+        cached = self._step_cache_check()
         if latents.shape[0] != 1:
             # A batch (a list of prompts, batched `prompt_embeds` / `latents`) runs video by video: the loop state -- the static
             # model-input buffer, the sampler history, the captured graph -- is one video's.  The videos of a batched loop never
@@ -272,6 +298,8 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
                                          callback_on_step_end, gi))
             return torch.cat(outs, dim=0)
         generator = _one_generator(generator)
+        if cached:
+            tr._reset_stateful_cache()        # every video starts from fresh cache state
         cfg_on = guidance_scale > 1.0 and negative_prompt_embeds is not None
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
         ts = self.scheduler.timesteps
@@ -318,7 +346,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         from .graph_step import StepGraph
         from .pipeline_wan_i2v_motion_frameino import tr_default_procs
         stepper = StepGraph(lambda: self._step(st), self.use_hip_graph,
-                            callback_on_step_end is None and lat.is_cuda and not win_eager
+                            callback_on_step_end is None and lat.is_cuda and not win_eager and not cached
                             and (self.use_hip_graph is True or tr_default_procs(tr)), len(ts))
         for i, t in enumerate(ts):
             if self._interrupt:
@@ -335,6 +363,8 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
                     lat.copy_(out["latents"][0])
         self._current_timestep = None
         stepper.close()
+        if cached:
+            tr._reset_stateful_cache()        # (the buffers go; `cache_log` stays readable until the next forward)
         return lat[None]
 
     def _step(self, st):
@@ -345,8 +375,12 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         live = {"live_frames": st.nlf} if (st.x.shape[1] > st.nlf and getattr(self.transformer, "skip_dead_rows", False)) else {}
         if getattr(self.transformer, "is_window_attention_enabled", False):      # (this package's transformer only, as above)
             live["id_frames"] = st.id_frames
-        pred = self.transformer(hidden_states=st.x, encoder_hidden_states=st.prompt, timestep=st.t,
-                                image_rotary_emb=st.rot, attention_kwargs=st.attention_kwargs, return_dict=False, **live)[0]
+        # one cache context for the CFG batch, as diffusers' CogVideoX pipelines set it
+        ctx = self.transformer.cache_context("cond_uncond") if hasattr(self.transformer, "cache_context") \
+            else contextlib.nullcontext()
+        with ctx:
+            pred = self.transformer(hidden_states=st.x, encoder_hidden_states=st.prompt, timestep=st.t,
+                                    image_rotary_emb=st.rot, attention_kwargs=st.attention_kwargs, return_dict=False, **live)[0]
         if st.dpm:
             ops.cfg_dpm_step_(st.lat, pred.contiguous(), st.x0_old, st.noise, st.coef, has_uncond=st.cfg_on)
         else:
@@ -432,6 +466,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         width = width or c.sample_width * self.vae_scale_factor_spatial
         self.check_inputs(image, prompt, height, width, negative_prompt, callback_on_step_end_tensor_inputs, latents,
                           prompt_embeds, negative_prompt_embeds)
+        self._step_cache_check()
         # The reference overwrites `num_videos_per_prompt` with 1 (:723) and its loop breaks on more than one prompt (the
         # trajectory / identity latents are batch 1, :803-826 against torch.cat at :872-880); here a list of B prompts (or
         # B rows of `prompt_embeds`) makes B videos, run video by video in `denoise` (the Wan mirror does the same).
@@ -493,6 +528,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         out = self.denoise(latents, image_latents, traj_latents, id_latent, prompt_embeds, negative_prompt_embeds,
                            gscale, num_inference_steps, use_dynamic_cfg, None, attention_kwargs, callback_on_step_end,
                            generator)
+        self.maybe_free_model_hooks()
         if output_type == "latent":
             video = out
         else:

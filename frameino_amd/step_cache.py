@@ -30,7 +30,12 @@ residual add.  The decision is a function of the step counter and the timestep a
 so one counter per (context, kind) stands for them, the callback is read once per forward, and nothing on the device is read.
 A kind whose `*_block_skip_range` is None is never hooked and always computes.  The model asks `_pab_begin` for a forward's
 decisions and `_pab_buffer` for a layer's `[rows, D]` cache.
+
+The CogVideoX DiT (`PyramidAttentionBroadcastMixin`) takes Pyramid Attention Broadcast alone, with the same rule and state: its one
+attention layer per block, the joint text + video attn1, is the "spatial" kind, and a call's whole batch is one segment under one
+context (diffusers' CogVideoX pipelines run the CFG batch under `cache_context("cond_uncond")`).
 """
+import contextlib
 import dataclasses
 import warnings
 from types import SimpleNamespace
@@ -111,6 +116,7 @@ class FirstBlockCacheMixin:
     Pyramid Attention Broadcast: per context and kind a counter, per (kind, layer) a [rows, D] buffer in the model dtype,
     allocated by the first forward that computes; `cache_log` holds `(context, iteration, float(timestep),
     self_attention_computed, cross_attention_computed)` for every forward and context, with the same lifetime."""
+    _cache_configs_implemented = "FirstBlockCacheConfig and PyramidAttentionBroadcastConfig are"
     _step_cache_config = None
     _step_cache_states = None
     _step_cache_log_fresh = True
@@ -150,8 +156,7 @@ class FirstBlockCacheMixin:
                                       f"`current_timestep_callback` attributes of diffusers' config, so it cannot be applied")
         if name in _OTHER_DIFFUSERS_CONFIGS or (name.endswith("CacheConfig") and
                                                  type(config).__module__.split(".")[0] == "diffusers"):
-            raise NotImplementedError(f"{name} is not implemented on this model; FirstBlockCacheConfig and "
-                                      f"PyramidAttentionBroadcastConfig are")
+            raise NotImplementedError(f"{name} is not implemented on this model; {self._cache_configs_implemented}")
         raise ValueError(f"Cache config {type(config)} is not supported.")
 
     def disable_cache(self):
@@ -287,3 +292,31 @@ class FirstBlockCacheMixin:
                                f"context {seg.name!r}")
             buf = seg.state.buffers[(kind, layer)] = torch.empty((seg.r1 - seg.r0, d), dtype=dtype, device=device)
         return buf
+
+
+class PyramidAttentionBroadcastMixin(FirstBlockCacheMixin):
+    """The same surface for a model that implements Pyramid Attention Broadcast alone (CogVideoXTransformer3DModel), plus
+    diffusers' `cache_context(name)`.  `FirstBlockCacheConfig` is refused by name.  The model's only attention layer is each
+    block's joint text + video `attn1`, the "spatial" kind; `temporal_*` and `cross_*` ranges match no layer: a config that sets
+    only those is accepted, hooks nothing and says so once.  `_pab_begin` / `_pab_buffer` and the `cache_log` rows are the Wan
+    model's -- the last field, the cross-attention's decision, is always True here."""
+    _cache_configs_implemented = "PyramidAttentionBroadcastConfig is"
+    _ctx_name = None
+
+    @contextlib.contextmanager
+    def cache_context(self, name):
+        prev, self._ctx_name = self._ctx_name, name
+        try:
+            yield
+        finally:
+            self._ctx_name = prev
+
+    def enable_cache(self, config):
+        if not self.is_cache_enabled and _is_fbc_config(config):
+            raise NotImplementedError(f"FirstBlockCacheConfig is not implemented on {type(self).__name__}; "
+                                      f"{self._cache_configs_implemented}")
+        super().enable_cache(config)
+        if self._pab_on and config.spatial_attention_block_skip_range is None:
+            warnings.warn(f"Pyramid Attention Broadcast: `spatial_attention_block_skip_range` is None and the temporal / cross "
+                          f"ranges match no attention layer of {type(self).__name__} (its only one is the joint attn1 of every "
+                          f"block, the spatial kind): this config hooks nothing and every forward computes.", stacklevel=2)

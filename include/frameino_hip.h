@@ -477,6 +477,14 @@ int fino_quantize_mxfp8(const void* x, void* q, void* scales, int64_t rows, int6
 int fino_gemm_mxfp8(const void* aq, const void* a_scales, const void* wq, const void* w_scales, const void* bias,
                     void* c, int64_t m, int64_t n, int64_t k, int64_t ldc, int epilogue, const void* r, int64_t ldr,
                     const float* gate, int64_t mod_stride, const int32_t* sel, int out_dtype, void* stream);
+/* fino_gemm_mxfp8 for the residual epilogues (FINO_EPI_RESIDUAL, _GATED_RESIDUAL, _GATED_RESIDUAL_STAGED) that ALSO stores
+ * y = T(acc + bias), the value before the gate multiply and the residual add, to keep [M, N] (row stride ldk >= N, a multiple
+ * of 8; 16-byte aligned) -- from the staged tile the epilogue already holds, as fino_gemm_keep does.  c is what fino_gemm_mxfp8
+ * gives, bit for bit; keep is what FINO_EPI_NONE gives.  Another epilogue, a null or misaligned keep, ldk < N -> FINO_ERR_ARG. */
+int fino_gemm_mxfp8_keep(const void* aq, const void* a_scales, const void* wq, const void* w_scales, const void* bias,
+                         void* c, int64_t m, int64_t n, int64_t k, int64_t ldc, int epilogue, const void* r, int64_t ldr,
+                         const float* gate, int64_t mod_stride, const int32_t* sel, int out_dtype, void* keep, int64_t ldk,
+                         void* stream);
 /* Same product with the result QUANTISED in the epilogue (epilogue NONE or GELU_TANH): cq [M, N] e4m3 bytes + c_scales
  * in the fino_quantize_mxfp8 layout, byte-identical to fino_quantize_mxfp8 applied to the bias_dtype-rounded C.  Feeds
  * the next MXFP8 GEMM (FFN up -> FFN down) without the bf16 round trip through HBM.  N % 128 == 0. */
@@ -511,6 +519,11 @@ int fino_quantize_mxfp6(const void* x, void* q, void* scales, int64_t rows, int6
 int fino_gemm_mxfp6(const void* aq, const void* a_scales, const void* wq, const void* w_scales, const void* bias,
                     void* c, int64_t m, int64_t n, int64_t k, int64_t ldc, int epilogue, const void* r, int64_t ldr,
                     const float* gate, int64_t mod_stride, const int32_t* sel, int out_dtype, void* stream);
+/* fino_gemm_mxfp6 with the keep buffer of fino_gemm_mxfp8_keep: same arguments, same rules. */
+int fino_gemm_mxfp6_keep(const void* aq, const void* a_scales, const void* wq, const void* w_scales, const void* bias,
+                         void* c, int64_t m, int64_t n, int64_t k, int64_t ldc, int epilogue, const void* r, int64_t ldr,
+                         const float* gate, int64_t mod_stride, const int32_t* sel, int out_dtype, void* keep, int64_t ldk,
+                         void* stream);
 
 /* ---- condition builders in front of the path ---------------------------------------------------------
  * Trajectory video of data_loader/video_dataset_motion.py:120-206 (`prepare_traj_tensor`, app.py:616-620).
