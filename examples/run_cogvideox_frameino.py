@@ -60,6 +60,9 @@ def main():
     ap.add_argument("--fp8-attention", action="store_true", help="fp8 (e4m3) attention operands (reduced precision, opt-in)")
     ap.add_argument("--smooth-k", action="store_true",
                     help="with --fp8-attention: subtract the key mean before K is quantised (exact for the softmax)")
+    ap.add_argument("--smooth-v", action="store_true",
+                    help="with --fp8-attention: subtract the value mean before V is quantised and add it back to the output (exact: "
+                         "the softmax weights sum to one)")
     ap.add_argument("--window-frames", type=int, default=None, metavar="N",
                     help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
                          "a video query sees the text, its own latent frame +- N, the first frame and the identity frame; "
@@ -132,7 +135,7 @@ def main():
     if a.mxfp8:
         transformer.enable_mxfp8_linears()
     if a.fp8_attention:
-        transformer.enable_fp8_attention(smooth_k=a.smooth_k)
+        transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v)
     if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)
         from frameino_amd.window_attention import WindowAttentionConfig
         transformer.enable_window_attention(WindowAttentionConfig(window_frames=a.window_frames, sink_frames=(0,)))
@@ -165,7 +168,7 @@ def main():
         frames = np.stack([np.asarray(f) for f in video])
         assert frames.shape == (a.frames, a.height, a.width, 3) and frames.dtype == np.uint8
         cond_s = f"conditions {tc - t0:.2f} s, " if rep == 0 else ""
-        mode = ("mxfp8 linears" if a.mxfp8 else f"{a.dtype} linears") + ((" + fp8 attention" + (" (smooth K)" if a.smooth_k else "")) if a.fp8_attention else "")
+        mode = ("mxfp8 linears" if a.mxfp8 else f"{a.dtype} linears") + ((" + fp8 attention" + (" (smooth K)" if a.smooth_k else "") + (" (smooth V)" if a.smooth_v else "")) if a.fp8_attention else "")
         if a.window_frames is not None:
             mode += f" + window attention (+- {a.window_frames} frames)"
         if a.pab is not None:

@@ -67,6 +67,13 @@ def main():
                     help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
                          "every query attends its own frame +- N neighbours plus the first frame and the ID frame, e.g. 2.  Not "
                          "together with --pab")
+    ap.add_argument("--fp8-attention", action="store_true",
+                    help="fp8 (e4m3) operands in the 3-D self-attention (reduced precision, opt-in).  Not together with --window-frames")
+    ap.add_argument("--smooth-k", action="store_true",
+                    help="with --fp8-attention: subtract the key mean before K is quantised (exact for the softmax)")
+    ap.add_argument("--smooth-v", action="store_true",
+                    help="with --fp8-attention: subtract the value mean before V is quantised and add it back to the output (exact: "
+                         "the softmax weights sum to one)")
     ap.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16",
                     help="the DiT's dtype.  Default fp16 = what the reference app loads it in (app.py:156: "
                          "`WanTransformer3DModel.from_pretrained(..., torch_dtype=torch.float16)`, fp32 islands kept); bf16 is what "
@@ -143,6 +150,8 @@ def main():
         transformer.enable_cache(PyramidAttentionBroadcastConfig(
             spatial_attention_block_skip_range=n_m[0], cross_attention_block_skip_range=n_m[1] if len(n_m) > 1 else None,
             current_timestep_callback=lambda: pipe.current_timestep))
+    if a.fp8_attention:
+        transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v)
     if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)
         from frameino_amd.window_attention import WindowAttentionConfig
         transformer.enable_window_attention(WindowAttentionConfig(window_frames=a.window_frames, sink_frames=(0,)))

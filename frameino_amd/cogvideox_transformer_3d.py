@@ -231,7 +231,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                            ("ff2", blk.ff.net[2].weight)):
                 yield li, key, w
 
-    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False):
+    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False, smooth_v=False):
         """The joint text + video self-attention (attention_processor.py:2863 of the reference, head_dim 64: 55 % of the
         CogVideoX-5B step) with fp8 e4m3 matrix operands -- K / V quantised per call with one scale per 32 elements, Q and
         P in registers, both products on the block-scaled fp8 MFMA, fp32 softmax and accumulation
@@ -241,10 +241,15 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         p_mode: "exp2" | "ramp" -- how a softmax weight becomes its e4m3 byte (ops.FP8_P_*; None = ops.FP8_P_DEFAULT).
         smooth_k: subtract the per-(batch element, head, channel) mean of K over the keys before K is quantised
         (fino_attn_fwd_fp8_smooth): invisible to the softmax, and a channel offset that all keys share (a to_k bias, norm_k
-        weights, low-frequency RoPE channels) stops taking the mantissa bits.  Off by default."""
+        weights, low-frequency RoPE channels) stops taking the mantissa bits.  Off by default.
+        smooth_v: subtract the per-(batch element, head, channel) mean of V over the keys before V is quantised and add it back
+        to the normalised output in fp32 (fino_attn_fwd_fp8_smoothed): exact, the softmax weights sum to one, and an offset that
+        all keys of a channel share (attn1.to_v.bias, a DC component of the modulated input: V has no norm and no RoPE) stops
+        taking the mantissa bits.  Off by default."""
         self.fp8_attention = bool(enabled)
         self.fp8_p_mode = p_mode
         self.fp8_smooth_k = bool(smooth_k)
+        self.fp8_smooth_v = bool(smooth_v)
         return self
 
     # ---- sliding-window self-attention over frames ----
@@ -322,7 +327,8 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         tab = None if win is None or li in win.skip else win.table(q_rows)
         fp8 = self.fp8_attention and dh == 64
         if fp8:
-            kw = dict(p_mode=getattr(self, "fp8_p_mode", None), smooth_k=getattr(self, "fp8_smooth_k", False), **afold)
+            kw = dict(p_mode=getattr(self, "fp8_p_mode", None), smooth_k=getattr(self, "fp8_smooth_k", False),
+                      smooth_v=getattr(self, "fp8_smooth_v", False), **afold)
             if tab is not None:
                 return ops.attention_fp8_ranges(q, k, v, heads, tab, **kw)
             return ops.attention_fp8(q, k, v, heads, **kw)

@@ -1383,12 +1383,19 @@ __global__ __launch_bounds__(kWaves * 64) void attn_combine_kernel(const AttnPar
 #undef PART_PTR
     const float inv = 1.0f / l;
     uint16_t* orow = p.o + bi * p.o_bs + head * p.o_hs + (int64_t)qrow * p.o_rs;
+    // smooth V (the fp8 head_dim 128 tail split): the partials are mu-free; the mean of V joins here, after the normalisation
+    const float* mu = p.vmean ? p.vmean + (int64_t)hb * D : nullptr;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int d0 = dt * 32 + 8 * g + 4 * h;
         const float* a4 = acc + 4 * g;
-        uint32_t x0 = (uint32_t)T::from_f32(a4[0] * inv) | ((uint32_t)T::from_f32(a4[1] * inv) << 16);
-        uint32_t x1 = (uint32_t)T::from_f32(a4[2] * inv) | ((uint32_t)T::from_f32(a4[3] * inv) << 16);
+        float y[4] = {a4[0] * inv, a4[1] * inv, a4[2] * inv, a4[3] * inv};
+        if (mu) {
+            const float4 m4 = *reinterpret_cast<const float4*>(mu + d0);
+            y[0] += m4.x; y[1] += m4.y; y[2] += m4.z; y[3] += m4.w;
+        }
+        uint32_t x0 = (uint32_t)T::from_f32(y[0]) | ((uint32_t)T::from_f32(y[1]) << 16);
+        uint32_t x1 = (uint32_t)T::from_f32(y[2]) | ((uint32_t)T::from_f32(y[3]) << 16);
         *reinterpret_cast<uint2*>(orow + d0) = make_uint2(x0, x1);
     }
 }
@@ -1960,7 +1967,7 @@ static int attn_common(const void* q, const void* k, const void* v, void* o, int
     p.ws = (workspace && workspace_bytes > 0) ? (float*)workspace : nullptr;
     p.all_partial = all_partial;
     p.tail_n = 0;
-    p.ranges = ranges;
+    p.ranges = ranges; p.vmean = nullptr;
     FINO_CHECK(((uintptr_t)workspace & 15) == 0, FINO_ERR_ARG, "fino_attn_fwd_ws: workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int64_t wb = workspace_bytes;
@@ -2079,7 +2086,7 @@ extern "C" int fino_attn_fwd_tail(const void* q, const void* k, const void* v, v
     p.scale_log2 = scale == FINO_ATTN_SCALE_FOLDED ? 1.0f : scale * 1.4426950408889634f;
     p.nqb = (int)((lq + kQBlock - 1) / kQBlock);
     p.vsplit = 1; p.nqb_v = p.nqb; p.full_x = 0; p.rem_x = 0; p.nwg = 0; p.per = 1;
-    p.ws = nullptr; p.all_partial = 0; p.ranges = nullptr;
+    p.ws = nullptr; p.all_partial = 0; p.ranges = nullptr; p.vmean = nullptr;
     // the walking kernel addresses each operand through ONE buffer resource over the whole tensor
     auto span = [&](int64_t bs, int64_t hs, int64_t rs, int64_t rows) {
         return (((int64_t)batch - 1) * bs + ((int64_t)heads - 1) * hs + (rows - 1 + 2 * kKV) * rs + 128) * 2;

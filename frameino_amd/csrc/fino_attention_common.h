@@ -48,6 +48,11 @@ struct AttnParams {
     // [begin, end) ranges of key tiles per q-block ((0, 0): unused), shared by all heads and batch elements.  nullptr: off.
     // Last member: the offsets of everything above, and with them the dense kernels' argument loads, stay as they were.
     const int* ranges;
+    // smooth V (fino_attn_fwd_fp8_smoothed): fp32 [batch][heads * head_dim], the mean of V over the keys, which the fp8 quantiser
+    // subtracted.  O = P (V - mu) / l + mu exactly (the weights P / l sum to 1), so whoever normalises adds mu[channel] in fp32
+    // before the one rounding to T: the fp8 main kernels for the blocks they store, attn_combine_kernel for the tail split's
+    // (its partials stay mu-free).  nullptr: off -- every other caller.  Behind `ranges` for the same reason `ranges` is last.
+    const float* vmean;
 };
 
 // (XCD, slot in that XCD's list of blocks) -> (head-batch, q-block); false: an empty slot.  The q-blocks of one head run on
@@ -123,9 +128,10 @@ __device__ __forceinline__ int k_lds_off(int row, int ch) {
 // direct form -- 16 (8) stores of 8 bytes per lane -- touches 32 lines per instruction, and cost the short-key kernel 4.7 us per
 // q-block (profiles/r04_attn_ppw.txt).  All LDS traffic is inline asm (the compiler would drain vmcnt in front of LDS accesses
 // it can see while LDS-DMA is in flight); the wave reads only what it wrote.
-template <typename T, int D>
+// MU (smooth V): mu = the head's D means; o * inv + mu[channel] in fp32 is what gets rounded.
+template <typename T, int D, bool MU = false>
 __device__ __forceinline__ void attn_rows_through_lds(const f32x16_t (&o)[D / 32], float inv, uint32_t lds_base, int r, int h,
-                                                      int lane, u32x4_t (&rows)[D / 16]) {
+                                                      int lane, u32x4_t (&rows)[D / 16], const float* mu = nullptr) {
     typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
     constexpr int kC = D / 8;                         // 16-byte pieces per row
     const uint32_t wbase = lds_base + (uint32_t)(r * (2 * D) + (h << 3));
@@ -134,8 +140,14 @@ __device__ __forceinline__ void attn_rows_through_lds(const f32x16_t (&o)[D / 32
     for (int dt = 0; dt < D / 32; ++dt) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const uint32_t w0 = (uint32_t)T::from_f32(o[dt][4 * g + 0] * inv) | ((uint32_t)T::from_f32(o[dt][4 * g + 1] * inv) << 16);
-            const uint32_t w1 = (uint32_t)T::from_f32(o[dt][4 * g + 2] * inv) | ((uint32_t)T::from_f32(o[dt][4 * g + 3] * inv) << 16);
+            float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (MU) m4 = *reinterpret_cast<const float4*>(mu + dt * 32 + 8 * g + 4 * h);
+            const float x0 = MU ? o[dt][4 * g + 0] * inv + m4.x : o[dt][4 * g + 0] * inv;
+            const float x1 = MU ? o[dt][4 * g + 1] * inv + m4.y : o[dt][4 * g + 1] * inv;
+            const float x2 = MU ? o[dt][4 * g + 2] * inv + m4.z : o[dt][4 * g + 2] * inv;
+            const float x3 = MU ? o[dt][4 * g + 3] * inv + m4.w : o[dt][4 * g + 3] * inv;
+            const uint32_t w0 = (uint32_t)T::from_f32(x0) | ((uint32_t)T::from_f32(x1) << 16);
+            const uint32_t w1 = (uint32_t)T::from_f32(x2) | ((uint32_t)T::from_f32(x3) << 16);
             const uint32_t a = wbase + ((((uint32_t)(4 * dt + g)) ^ rsw) << 4);
             asm volatile("ds_write_b64 %0, %1" ::"v"(a), "v"(u32x2_t{w0, w1}) : "memory");
         }

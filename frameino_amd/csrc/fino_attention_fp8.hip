@@ -16,6 +16,8 @@
 //     is two ds_read_b128 (the bf16 kernels need eight ds_read_b64_tr_b16) -- + one scale per (channel, 32-key block).
 //     fino_attn_fwd_fp8_smooth (opt-in) subtracts the mean of K over the keys first: two small launches in front of the
 //     quantiser (attn_kmean_*), nothing behind it changes -- see QuantParamsT below, DESIGN.md section 6e.
+//     fino_attn_fwd_fp8_smoothed adds SMOOTH V: the same two launches also take the mean of V over the keys (one pass serves
+//     both operands), the quantiser subtracts it, and whoever normalises O adds it back in fp32 -- DESIGN.md section 6i.
 //   * Q (bf16 / fp16, already multiplied by softmax_scale * log2 e in fp32) is quantised in registers at block start.
 //   * P = exp2(s - m + 6) is rounded to e4m3 with a fixed block scale 2^-6: between rescales p <= 2^kThr, so P8 <= 2^8 <
 //     448, and what underflows (p < 2^-15 of the running maximum) carries no weight.  l sums the ROUNDED P on the matrix
@@ -141,9 +143,14 @@ struct QuantParams {
 // quantises K - mean.  q.(k_j - mu) = q.k_j - q.mu and q.mu is one constant per query row, which the softmax drops: exact in
 // real arithmetic, no correction term, and the three mantissa bits of a block describe what differs from key to key instead
 // of an offset all keys share.  The plain quantiser's parameters stay the struct they were (an empty derived class).
+//
+// SMOOTH V (bit FINO_FP8_SMOOTH_V of the quantiser's SM): the same for V with its own mean.  P.(V - mu) / l + mu = P.V / l when
+// the weights P / l sum to 1, and they do exactly: l sums the same rounded P bytes on the matrix pipe.  So V - mu is what gets
+// the e4m3 bits, and the kernel that normalises adds mu[channel] back in fp32 (AttnParams::vmean).
 template <bool SMOOTH> struct QuantParamsT : QuantParams {};
 template <> struct QuantParamsT<true> : QuantParams {
     const float* mean;      // [batch][heads * 64]: heads = the 64-channel sub-heads, as k_hs = 64 walks them
+    const float* vmean;     // the same for V (read with bit FINO_FP8_SMOOTH_V alone)
 };
 
 // ---- the key mean: two launches, a fixed partition and a fixed order (no atomics: the same inputs give the same bits) ----
@@ -151,20 +158,26 @@ template <> struct QuantParamsT<true> : QuantParams {
 // (chunk, 64-channel group, batch element) sums kMeanRows keys: thread (r = tid >> 3, c8 = tid & 7) adds rows r, r + 32, ...
 // of its 8 channels (one 16-byte load per row), the 32 row slices meet in LDS and are added in the order r = 0 .. 31.
 constexpr int kMeanRows = 256;               // keys per partial: the partition depends on lk alone
+// Up to two operands per launch (K, V, or both: `nsrc`), operand s in grid rows [s * channels / 64, (s + 1) * channels / 64) of
+// the partial kernel and grid.z = s of the finish: one pass, and each operand's partition, order and bits are those of a pass
+// of its own.
 struct MeanParams {
-    const uint16_t* k;
-    float* part;           // [batch][chunks][channels]
-    float* mean;           // [batch][channels]
-    int lk, chunks, channels;
-    int64_t k_bs, k_rs;
+    const uint16_t* k[2];
+    float* part[2];        // [batch][chunks][channels]
+    float* mean[2];        // [batch][channels]
+    int lk, chunks, channels, nsrc;
+    int64_t k_bs[2], k_rs[2];
 };
 
 template <typename T>
 __global__ __launch_bounds__(256) void attn_kmean_partial_kernel(const MeanParams p) {
     __shared__ float red[32][kD8 + 1];
     const int tid = threadIdx.x, r = tid >> 3, c8 = tid & 7;
-    const int chunk = blockIdx.x, grp = blockIdx.y, bi = blockIdx.z;
-    const uint16_t* kp = p.k + bi * p.k_bs + grp * kD8 + c8 * 8;
+    const int chunk = blockIdx.x, bi = blockIdx.z;
+    const int ngrp = p.channels / kD8;
+    const int src = (int)blockIdx.y >= ngrp ? 1 : 0, grp = (int)blockIdx.y - src * ngrp;      // uniform: scalar selects
+    const int64_t k_rs = src ? p.k_rs[1] : p.k_rs[0];
+    const uint16_t* kp = (src ? p.k[1] : p.k[0]) + bi * (src ? p.k_bs[1] : p.k_bs[0]) + grp * kD8 + c8 * 8;
     const int key0 = chunk * kMeanRows + r;
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     uint4 u[kMeanRows / 32];
@@ -172,7 +185,7 @@ __global__ __launch_bounds__(256) void attn_kmean_partial_kernel(const MeanParam
     for (int i = 0; i < kMeanRows / 32; ++i) {
         const int key = key0 + 32 * i;
         u[i] = make_uint4(0, 0, 0, 0);                       // +0.0 in either dtype: keys past lk add nothing
-        if (key < p.lk) u[i] = *reinterpret_cast<const uint4*>(kp + (int64_t)key * p.k_rs);
+        if (key < p.lk) u[i] = *reinterpret_cast<const uint4*>(kp + (int64_t)key * k_rs);
     }
 #pragma unroll
     for (int i = 0; i < kMeanRows / 32; ++i) {
@@ -188,24 +201,24 @@ __global__ __launch_bounds__(256) void attn_kmean_partial_kernel(const MeanParam
         float s = red[0][tid];
 #pragma unroll
         for (int j = 1; j < 32; ++j) s += red[j][tid];
-        p.part[((int64_t)bi * p.chunks + chunk) * p.channels + grp * kD8 + tid] = s;
+        (src ? p.part[1] : p.part[0])[((int64_t)bi * p.chunks + chunk) * p.channels + grp * kD8 + tid] = s;
     }
 }
 
 // one thread per (batch element, channel): the partials in chunk order, then / lk
 __global__ __launch_bounds__(256) void attn_kmean_finish_kernel(const MeanParams p) {
-    const int c = blockIdx.x * 256 + threadIdx.x, bi = blockIdx.y;
+    const int c = blockIdx.x * 256 + threadIdx.x, bi = blockIdx.y, op = blockIdx.z;
     if (c >= p.channels) return;
-    const float* src = p.part + (int64_t)bi * p.chunks * p.channels + c;
+    const float* src = (op ? p.part[1] : p.part[0]) + (int64_t)bi * p.chunks * p.channels + c;
     float s = 0.f;
     for (int j = 0; j < p.chunks; ++j) s += src[(int64_t)j * p.channels];
-    p.mean[(int64_t)bi * p.channels + c] = s / (float)p.lk;
+    (op ? p.mean[1] : p.mean[0])[(int64_t)bi * p.channels + c] = s / (float)p.lk;
 }
 
 // one workgroup per (batch * head, key tile): 256 threads; threads 0..127 own (key, channel block) of K, 128..255
 // (channel, key block) of V
-template <typename T, bool SMOOTH>
-__global__ __launch_bounds__(256) void attn_quant_kv_fp8_kernel(const QuantParamsT<SMOOTH> p) {
+template <typename T, int SM>               // SM: FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V
+__global__ __launch_bounds__(256) void attn_quant_kv_fp8_kernel(const QuantParamsT<SM != 0> p) {
     __shared__ float kt[kKV][kD8 + 1];
     __shared__ float vt[kKV][kD8 + 1];
     const int tid = threadIdx.x;
@@ -226,13 +239,22 @@ __global__ __launch_bounds__(256) void attn_quant_kv_fp8_kernel(const QuantParam
         float kf[8], vf[8];
         unpack8<T>(ku, kf);
         unpack8<T>(vu, vf);
-        if constexpr (SMOOTH) {
+        if constexpr ((SM & FINO_FP8_SMOOTH_K) != 0) {
             // key slots past lk stay zero (masked with -inf by the main kernels, but the image must stay finite)
             if (key < p.lk) {
                 const float* mp = p.mean + (int64_t)hb * kD8 + ch * 8;
                 const float4 m0 = *reinterpret_cast<const float4*>(mp), m1 = *reinterpret_cast<const float4*>(mp + 4);
                 kf[0] -= m0.x; kf[1] -= m0.y; kf[2] -= m0.z; kf[3] -= m0.w;
                 kf[4] -= m1.x; kf[5] -= m1.y; kf[6] -= m1.z; kf[7] -= m1.w;
+            }
+        }
+        if constexpr ((SM & FINO_FP8_SMOOTH_V) != 0) {
+            // V slots past lk stay zero too: their P is 0, and 0 x (-mu) must not become 0 x garbage
+            if (key < p.lk) {
+                const float* mp = p.vmean + (int64_t)hb * kD8 + ch * 8;
+                const float4 m0 = *reinterpret_cast<const float4*>(mp), m1 = *reinterpret_cast<const float4*>(mp + 4);
+                vf[0] -= m0.x; vf[1] -= m0.y; vf[2] -= m0.z; vf[3] -= m0.w;
+                vf[4] -= m1.x; vf[5] -= m1.y; vf[6] -= m1.z; vf[7] -= m1.w;
             }
         }
 #pragma unroll
@@ -264,6 +286,22 @@ __global__ __launch_bounds__(256) void attn_quant_kv_fp8_kernel(const QuantParam
     *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
     *reinterpret_cast<uint4*>(dst + 16) = make_uint4(w[4], w[5], w[6], w[7]);
     (tid < 128 ? p.ks : p.vs)[tbase * 128 + a * 2 + blk] = (uint8_t)sb;
+}
+
+// Smooth V in the main kernels: the pointer to the head's means (AttnParams::vmean + head-batch x head_dim, or null) is needed
+// by the epilogue alone.  Kept in scalar registers from the argument load to the epilogue it costs the free-running loop four
+// more SGPR spills per tile (v_writelane / v_readlane: all three kernels sit at the 100-SGPR ceiling), so it waits in LDS: thread 0
+// stores it into kMuSlot bytes behind the rings before the first DMA is issued, every lane reads it back after the loop (inline
+// asm, like the epilogue's other LDS traffic: invisible to the compiler, which therefore can neither hoist it nor drain vmcnt).
+constexpr int kMuSlot = 16;
+__device__ __forceinline__ void mu_park(char* slot, const float* vmean, int64_t head_off) {
+    if (threadIdx.x == 0) *reinterpret_cast<const float**>(slot) = vmean ? vmean + head_off : nullptr;
+}
+__device__ __forceinline__ const float* mu_fetch(int lds_off) {
+    unsigned long long bits;
+    asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(bits) : "v"(lds_off) : "memory");
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)bits), hi = __builtin_amdgcn_readfirstlane((uint32_t)(bits >> 32));
+    return reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
 }
 
 struct Fp8AttnParams {
@@ -440,6 +478,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_kernel(const Fp8AttnP
             __builtin_amdgcn_raw_ptr_buffer_load_lds(st_srsrc, (FINO_LDS void*)(smem + st_slds + sl_ * 128), 4, st_svoff, \
                                                      tt_ * 128, 0, 0);                                       \
     }
+    mu_park(smem + kSmem8, p.vmean, (int64_t)hb * kD8);       // smooth V: for the epilogue (visible after the barrier below)
     // ---- prologue: tiles 0 .. 3 by the same DMA (each group its halves); 0 and 1 must have landed before the loop ----
     { F8_DMA(0) }
     { F8_DMA(1) }
@@ -650,7 +689,10 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_kernel(const Fp8AttnP
         int le = lane;
         asm volatile("" : "+v"(le));       // opaque: or the epilogue's per-lane offsets are computed before the loop and spilled
         u32x4_t rows[kD8 / 16];
-        attn_rows_through_lds<T, kD8>(o, inv, (uint32_t)((tid >> 6) * 4096), le & 31, le >> 5, le, rows);
+        // smooth V: + mu[channel] in fp32 before the one rounding (a uniform branch)
+        const float* mu = mu_fetch(kSmem8);
+        if (mu) attn_rows_through_lds<T, kD8, true>(o, inv, (uint32_t)((tid >> 6) * 4096), le & 31, le >> 5, le, rows, mu);
+        else attn_rows_through_lds<T, kD8>(o, inv, (uint32_t)((tid >> 6) * 4096), le & 31, le >> 5, le, rows);
         attn_store_rows<kD8>(rows, op, p.o_rs, qrow - (lane & 31), p.lq, le);
     }
   }   // piece
@@ -767,6 +809,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
                                                      tt_ * 128, 0, 0);                                       \
         }                                                                                                    \
     }
+    mu_park(smem + kFrSmem, p.vmean, (int64_t)hb * kD8);      // smooth V: for the epilogue (visible after the barrier below)
     { FR_DMA(0) }
     { FR_DMA(1) }
     { FR_DMA(2) }
@@ -942,6 +985,29 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
     const float inv = 1.0f / lacc[0];
     if (qrow < p.lq) {
         uint16_t* orow = op + (int64_t)qrow * p.o_rs;
+        const float* mu_head = mu_fetch(kFrSmem);
+        if (mu_head) {
+            // smooth V: + mu[channel] in fp32 before the one rounding.  The pointer comes out of LDS and the lane's channel offset
+            // goes through an opaque copy of g made HERE, so the eight 16-byte loads of mu (and their addresses) start after the
+            // loop and hold no register in it.
+            int ge = g;
+            asm volatile("" : "+v"(ge));
+            const float* mu = mu_head + 4 * ge;
+#pragma unroll
+            for (int dt = 0; dt < kDT; ++dt) {
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    const int d0 = dt * 32 + 8 * gq;
+                    const float4 m4 = *reinterpret_cast<const float4*>(mu + d0);
+                    uint32_t w0 = (uint32_t)T::from_f32(o[dt][4 * gq + 0] * inv + m4.x) |
+                                  ((uint32_t)T::from_f32(o[dt][4 * gq + 1] * inv + m4.y) << 16);
+                    uint32_t w1 = (uint32_t)T::from_f32(o[dt][4 * gq + 2] * inv + m4.z) |
+                                  ((uint32_t)T::from_f32(o[dt][4 * gq + 3] * inv + m4.w) << 16);
+                    *reinterpret_cast<uint2*>(orow + d0 + 4 * ge) = make_uint2(w0, w1);
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int dt = 0; dt < kDT; ++dt) {
 #pragma unroll
@@ -1051,6 +1117,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
                                                      st_svoff, tt_ * 128, 0, 0);                             \
         }                                                                                                    \
     }
+    mu_park(smem + kSmem128, p.vmean, (int64_t)hb * 128);     // smooth V: for the epilogue (visible after the barrier below)
     { D8_DMA(0) }
     { D8_DMA(1) }
     { D8_DMA(2) }
@@ -1224,7 +1291,11 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
         int le = lane;
         asm volatile("" : "+v"(le));       // opaque: or the epilogue's per-lane offsets are computed before the loop and spilled
         u32x4_t rows[8];
-        attn_rows_through_lds<T, 128>(o, inv, (uint32_t)((tid >> 6) * 8192), le & 31, le >> 5, le, rows);
+        // smooth V: + mu[channel] in fp32 before the one rounding (a uniform branch); the partials above stay mu-free --
+        // attn_combine_kernel adds it after normalising
+        const float* mu = mu_fetch(kSmem128);
+        if (mu) attn_rows_through_lds<T, 128, true>(o, inv, (uint32_t)((tid >> 6) * 8192), le & 31, le >> 5, le, rows, mu);
+        else attn_rows_through_lds<T, 128>(o, inv, (uint32_t)((tid >> 6) * 8192), le & 31, le >> 5, le, rows);
         attn_store_rows<128>(rows, op, p.o_rs, qrow - r, p.lq, le);
     }
   }   // piece
@@ -1252,12 +1323,26 @@ extern "C" int64_t fino_attn_fp8_smooth_kv_bytes(int batch, int heads, int64_t l
     return ((base + 15) & ~(int64_t)15) + (int64_t)batch * heads * head_dim * 4 * (1 + kmean_chunks(lk));
 }
 
-// every entry point: `smooth` = mean -> smoothing quantiser, otherwise the plain quantiser; the main-kernel launch is the same.
+// the flag word's layout: [ fino_attn_fp8_kv_bytes | pad to 16 | K: mean, partials (bit FINO_FP8_SMOOTH_K) | pad to 16 |
+// V: mean, partials (bit FINO_FP8_SMOOTH_V) ] -- flags 0 and 1 are fino_attn_fp8_kv_bytes and fino_attn_fp8_smooth_kv_bytes
+extern "C" int64_t fino_attn_fp8_smoothed_kv_bytes(int batch, int heads, int64_t lk, int head_dim, int smooth) {
+    if (smooth < 0 || smooth > (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V)) return 0;
+    int64_t b = (smooth & FINO_FP8_SMOOTH_K) ? fino_attn_fp8_smooth_kv_bytes(batch, heads, lk, head_dim)
+                                             : fino_attn_fp8_kv_bytes(batch, heads, lk, head_dim);
+    if (b <= 0) return 0;
+    if (smooth & FINO_FP8_SMOOTH_V) b = ((b + 15) & ~(int64_t)15) + (int64_t)batch * heads * head_dim * 4 * (1 + kmean_chunks(lk));
+    return b;
+}
+
+// every entry point: `smooth` (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V) != 0 = means -> smoothing quantiser, otherwise the plain
+// quantiser; the main-kernel launch is the same, and with FINO_FP8_SMOOTH_V it gets the mean of V to add back (AttnParams::vmean).
 // `ranges` (fino_attn_fwd_fp8_ranges): head_dim 64 only, always attn_fp8_fr_kernel<T, PX, true>, whatever the tuning knob says.
-static int attn_fwd_fp8_impl(const char* fn, bool smooth, const void* q, const void* k, const void* v, void* o, int batch, int heads,
+static int attn_fwd_fp8_impl(const char* fn, int smooth, const void* q, const void* k, const void* v, void* o, int batch, int heads,
                              int64_t lq, int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
                              int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode,
                              void* kv_workspace, int64_t kv_workspace_bytes, void* stream, const int* ranges = nullptr) {
+    FINO_CHECK(smooth >= 0 && smooth <= (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V), FINO_ERR_ARG, "%s: smooth flags %d not in 0 .. 3", fn,
+               smooth);
     FINO_CHECK(p_mode == FINO_FP8_P_EXP2 || p_mode == FINO_FP8_P_RAMP, FINO_ERR_ARG, "%s: p_mode %d", fn, p_mode);
     FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "%s: dtype %d", fn, dtype);
     FINO_CHECK(head_dim == 64 || head_dim == 128, FINO_ERR_UNSUPPORTED, "%s: head_dim %d not in {64, 128}", fn, head_dim);
@@ -1270,8 +1355,7 @@ static int attn_fwd_fp8_impl(const char* fn, bool smooth, const void* q, const v
                    q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0 && o_bs % 8 == 0,
                FINO_ERR_ARG, "%s: pointers and strides must be 16-byte aligned", fn);
     FINO_CHECK(scale > 0.f || scale == FINO_ATTN_SCALE_FOLDED, FINO_ERR_ARG, "%s: scale", fn);
-    const int64_t need = smooth ? fino_attn_fp8_smooth_kv_bytes(batch, heads, lk, head_dim)
-                                : fino_attn_fp8_kv_bytes(batch, heads, lk, head_dim);
+    const int64_t need = fino_attn_fp8_smoothed_kv_bytes(batch, heads, lk, head_dim, smooth);
     FINO_CHECK(kv_workspace_bytes >= need, FINO_ERR_ARG, "%s: workspace %lld B < %lld B", fn,
                (long long)kv_workspace_bytes, (long long)need);
     if (lq == 0) return FINO_OK;
@@ -1285,28 +1369,47 @@ static int attn_fwd_fp8_impl(const char* fn, bool smooth, const void* q, const v
     qp.k8 = w8; qp.v8t = w8 + bh * nt * kTileK8; qp.ks = w8 + 2 * bh * nt * kTileK8; qp.vs = qp.ks + bh * nt * 128;
     qp.batch = batch; qp.heads = heads * sub; qp.lk = (int)lk; qp.nt = nt;
     qp.k_bs = k_bs; qp.k_rs = k_rs; qp.k_hs = 64; qp.v_bs = v_bs; qp.v_rs = v_rs; qp.v_hs = 64;
+    qp.mean = nullptr; qp.vmean = nullptr;
     if (smooth) {
+        // one mean pass for the operands the flags name: K first, then V (each behind a 16-byte boundary, as the size function lays
+        // them out); both = the same two launches with a grid twice as tall
         MeanParams mp;
-        mp.k = qp.k; mp.lk = (int)lk; mp.chunks = (int)kmean_chunks(lk); mp.channels = heads * head_dim;
-        mp.k_bs = k_bs; mp.k_rs = k_rs;
-        mp.mean = (float*)(w8 + ((fino_attn_fp8_kv_bytes(batch, heads, lk, head_dim) + 15) & ~(int64_t)15));
-        mp.part = mp.mean + (int64_t)batch * mp.channels;
-        qp.mean = mp.mean;
-        FINO_CHECK(mp.chunks <= 65535 && batch <= 65535, FINO_ERR_UNSUPPORTED, "%s: lk %lld / batch %d beyond the mean pass's grid",
-                   fn, (long long)lk, batch);
-        const dim3 gpart((unsigned)mp.chunks, (unsigned)(mp.channels / kD8), (unsigned)batch);
-        const dim3 gfin((unsigned)((mp.channels + 255) / 256), (unsigned)batch);
+        mp.lk = (int)lk; mp.chunks = (int)kmean_chunks(lk); mp.channels = heads * head_dim; mp.nsrc = 0;
+        const int64_t region = (int64_t)batch * mp.channels * 4 * (1 + mp.chunks);
+        int64_t off = (fino_attn_fp8_kv_bytes(batch, heads, lk, head_dim) + 15) & ~(int64_t)15;
+        for (int bit = FINO_FP8_SMOOTH_K; bit <= FINO_FP8_SMOOTH_V; bit <<= 1) {
+            if (!(smooth & bit)) continue;
+            const bool is_k = bit == FINO_FP8_SMOOTH_K;
+            const int s = mp.nsrc++;
+            mp.k[s] = is_k ? qp.k : qp.v; mp.k_bs[s] = is_k ? k_bs : v_bs; mp.k_rs[s] = is_k ? k_rs : v_rs;
+            mp.mean[s] = (float*)(w8 + off);
+            mp.part[s] = mp.mean[s] + (int64_t)batch * mp.channels;
+            (is_k ? qp.mean : qp.vmean) = mp.mean[s];
+            off = (off + region + 15) & ~(int64_t)15;
+        }
+        if (mp.nsrc == 1) { mp.k[1] = mp.k[0]; mp.k_bs[1] = mp.k_bs[0]; mp.k_rs[1] = mp.k_rs[0]; mp.mean[1] = mp.mean[0]; mp.part[1] = mp.part[0]; }
+        FINO_CHECK(mp.chunks <= 65535 && batch <= 65535 && mp.nsrc * (mp.channels / kD8) <= 65535, FINO_ERR_UNSUPPORTED,
+                   "%s: lk %lld / batch %d / %d channels beyond the mean pass's grid", fn, (long long)lk, batch, mp.channels);
+        const dim3 gpart((unsigned)mp.chunks, (unsigned)(mp.nsrc * (mp.channels / kD8)), (unsigned)batch);
+        const dim3 gfin((unsigned)((mp.channels + 255) / 256), (unsigned)batch, (unsigned)mp.nsrc);
         if (dtype == FINO_BF16) attn_kmean_partial_kernel<BF16><<<gpart, 256, 0, st>>>(mp);
         else attn_kmean_partial_kernel<F16><<<gpart, 256, 0, st>>>(mp);
         FINO_LAUNCH_CHECK();
         attn_kmean_finish_kernel<<<gfin, 256, 0, st>>>(mp);
         FINO_LAUNCH_CHECK();
-        if (dtype == FINO_BF16) attn_quant_kv_fp8_kernel<BF16, true><<<dim3((unsigned)nt, (unsigned)bh), 256, 0, st>>>(qp);
-        else attn_quant_kv_fp8_kernel<F16, true><<<dim3((unsigned)nt, (unsigned)bh), 256, 0, st>>>(qp);
-    } else {
+    }
+    {
+        const dim3 gq((unsigned)nt, (unsigned)bh);
         const QuantParamsT<false> qpl{qp};
-        if (dtype == FINO_BF16) attn_quant_kv_fp8_kernel<BF16, false><<<dim3((unsigned)nt, (unsigned)bh), 256, 0, st>>>(qpl);
-        else attn_quant_kv_fp8_kernel<F16, false><<<dim3((unsigned)nt, (unsigned)bh), 256, 0, st>>>(qpl);
+#define F8_QUANT(T_)                                                                                          \
+        switch (smooth) {                                                                                     \
+        case 0: attn_quant_kv_fp8_kernel<T_, 0><<<gq, 256, 0, st>>>(qpl); break;                              \
+        case 1: attn_quant_kv_fp8_kernel<T_, 1><<<gq, 256, 0, st>>>(qp); break;                               \
+        case 2: attn_quant_kv_fp8_kernel<T_, 2><<<gq, 256, 0, st>>>(qp); break;                               \
+        default: attn_quant_kv_fp8_kernel<T_, 3><<<gq, 256, 0, st>>>(qp); break;                              \
+        }
+        if (dtype == FINO_BF16) { F8_QUANT(BF16) } else { F8_QUANT(F16) }
+#undef F8_QUANT
     }
     FINO_LAUNCH_CHECK();
 
@@ -1322,7 +1425,7 @@ static int attn_fwd_fp8_impl(const char* fn, bool smooth, const void* q, const v
     const bool free_running = head_dim == 64 && (ranges || fino_tune_get(FINO_TUNE_ATTN_FP8_KERNEL) != 1);   // default at head_dim 64
     const int qblock = free_running ? kFrQBlock : kQBlock;
     p.nqb = (int)((lq + qblock - 1) / qblock);
-    p.ws = nullptr; p.all_partial = 0; p.tail_n = 0; p.ranges = ranges;
+    p.ws = nullptr; p.all_partial = 0; p.tail_n = 0; p.ranges = ranges; p.vmean = qp.vmean;
     attn_virtual_heads(p.batch, p.heads, p.nqb, p.vsplit, p.nqb_v);
     const int groups = (p.batch * p.heads * p.vsplit + 7) / 8;
     p.full_x = groups * p.nqb_v; p.rem_x = 0; p.nwg = 0; p.per = 1;
@@ -1346,8 +1449,8 @@ static int attn_fwd_fp8_impl(const char* fn, bool smooth, const void* q, const v
 #define K_FR_RG(T_, PX_) attn_fp8_fr_kernel<T_, PX_, true>
 #define K_D128(T_, PX_) attn_fp8_d128_kernel<T_, PX_>
 #define K_PP(T_, PX_) attn_fp8_kernel<T_, 0, PX_>
-        if (ranges) F8_LAUNCH(K_FR_RG, grid, kFrWaves * 64, kFrSmem)
-        else F8_LAUNCH(K_FR, grid, kFrWaves * 64, kFrSmem)
+        if (ranges) F8_LAUNCH(K_FR_RG, grid, kFrWaves * 64, kFrSmem + kMuSlot)
+        else F8_LAUNCH(K_FR, grid, kFrWaves * 64, kFrSmem + kMuSlot)
         FINO_LAUNCH_CHECK();
         return FINO_OK;
     }
@@ -1361,12 +1464,12 @@ static int attn_fwd_fp8_impl(const char* fn, bool smooth, const void* q, const v
             p.full_x = full_x; p.rem_x = rem_x; p.nwg = nwg; p.per = per;
         }
         const dim3 grid128((unsigned)(8 * (p.full_x + p.nwg)));
-        F8_SMEM_ONCE(K_D128, kSmem128)
-        F8_LAUNCH(K_D128, grid128, kWaves * 64, kSmem128)
+        F8_SMEM_ONCE(K_D128, kSmem128 + kMuSlot)
+        F8_LAUNCH(K_D128, grid128, kWaves * 64, kSmem128 + kMuSlot)
         FINO_LAUNCH_CHECK();
         return fino_attn_launch_combine(p, dtype, 128, st);
     }
-    constexpr int smem = kSmem8;
+    constexpr int smem = kSmem8 + kMuSlot;
     F8_SMEM_ONCE(K_PP, smem)        // 66 KiB of dynamic LDS: above the 64 KiB a kernel gets without asking
     F8_LAUNCH(K_PP, grid, kWaves * 64, smem)
     FINO_LAUNCH_CHECK();
@@ -1377,7 +1480,7 @@ extern "C" int fino_attn_fwd_fp8(const void* q, const void* k, const void* v, vo
                                  int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
                                  int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode,
                                  void* kv_workspace, int64_t kv_workspace_bytes, void* stream) {
-    return attn_fwd_fp8_impl("fino_attn_fwd_fp8", false, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs,
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8", 0, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs,
                              o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream);
 }
 
@@ -1385,7 +1488,16 @@ extern "C" int fino_attn_fwd_fp8_smooth(const void* q, const void* k, const void
                                         int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
                                         int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype,
                                         int p_mode, void* kv_workspace, int64_t kv_workspace_bytes, void* stream) {
-    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smooth", true, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs, v_bs,
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smooth", FINO_FP8_SMOOTH_K, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs,
+                             k_rs, v_bs, v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream);
+}
+
+// the flag word form: smooth = 0 is fino_attn_fwd_fp8, FINO_FP8_SMOOTH_K is fino_attn_fwd_fp8_smooth, bit FINO_FP8_SMOOTH_V adds smooth V
+extern "C" int fino_attn_fwd_fp8_smoothed(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
+                                          int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
+                                          int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype,
+                                          int p_mode, void* kv_workspace, int64_t kv_workspace_bytes, void* stream, int smooth) {
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smoothed", smooth, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs, v_bs,
                              v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream);
 }
 
@@ -1402,6 +1514,8 @@ extern "C" int fino_attn_fwd_fp8_ranges(const void* q, const void* k, const void
                                         const int* ranges, void* stream) {
     FINO_CHECK(ranges, FINO_ERR_ARG, "fino_attn_fwd_fp8_ranges: null ranges table");
     FINO_CHECK(((uintptr_t)ranges & 3) == 0, FINO_ERR_ARG, "fino_attn_fwd_fp8_ranges: the ranges table must be 4-byte aligned");
-    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_ranges", smooth_k != 0, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs,
+    // smooth_k: 0 / 1 as ever; 2 and 3 = the flag word of fino_attn_fwd_fp8_smoothed.  Any other non-zero value keeps meaning 1.
+    const int smooth = (smooth_k == 2 || smooth_k == 3) ? smooth_k : (smooth_k != 0 ? FINO_FP8_SMOOTH_K : 0);
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_ranges", smooth, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs,
                              k_rs, v_bs, v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream, ranges);
 }

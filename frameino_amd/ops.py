@@ -422,12 +422,20 @@ if _p_env not in FP8_P_MODES:
 FP8_P_DEFAULT = FP8_P_MODES[_p_env]
 
 
-def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=False):
+def _fp8_smooth_flags(smooth_k, smooth_v):
+    # include/frameino_hip.h: FINO_FP8_SMOOTH_K = 1, FINO_FP8_SMOOTH_V = 2
+    return (1 if smooth_k else 0) | (2 if smooth_v else 0)
+
+
+def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=False, smooth_v=False):
     """attention() with fp8 (e4m3) matrix operands, head_dim 64 or 128: K / V quantised per call (block-scaled, V transposed), Q
     and P in registers, both products on the block-scaled fp8 MFMA, softmax and accumulation in fp32 (fino_attn_fwd_fp8).
     p_mode: "exp2" | "ramp" (or the FP8_P_* integers); None = FP8_P_DEFAULT.
     smooth_k: subtract the mean of K over the keys (per batch element, head and channel) before K is quantised
-    (fino_attn_fwd_fp8_smooth): the softmax cannot see it, and a channel offset all keys share stops costing mantissa bits."""
+    (fino_attn_fwd_fp8_smooth): the softmax cannot see it, and a channel offset all keys share stops costing mantissa bits.
+    smooth_v: subtract the mean of V over the keys before V is quantised and add it back to the normalised output in fp32
+    (fino_attn_fwd_fp8_smoothed): exact, because the softmax weights sum to one; V has one scale per (channel, 32 keys), so an
+    offset all keys of a channel share (a to_v bias, a DC component) stops costing mantissa bits."""
     p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
     assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
     b, lq, hd = q.shape
@@ -438,8 +446,9 @@ def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=Fa
     if out is None:
         out = torch.empty((b, lq, hd), dtype=q.dtype, device=q.device)
     scale = dh ** -0.5 if scale is None else scale
-    fwd = "fino_attn_fwd_fp8_smooth" if smooth_k else "fino_attn_fwd_fp8"
-    need = (_lib.lib().fino_attn_fp8_smooth_kv_bytes if smooth_k else _lib.lib().fino_attn_fp8_kv_bytes)(b, heads, lk, dh)
+    flags = _fp8_smooth_flags(smooth_k, smooth_v)
+    fwd = "fino_attn_fwd_fp8_smoothed" if smooth_v else ("fino_attn_fwd_fp8_smooth" if smooth_k else "fino_attn_fwd_fp8")
+    need = _lib.lib().fino_attn_fp8_smoothed_kv_bytes(b, heads, lk, dh, flags)      # flags 0 / 1: the plain / smooth-K sizes
     if need <= 0:
         raise RuntimeError(f"attention_fp8: head_dim {dh} is not supported (64 or 128)")
     key = (q.device.index, torch.cuda.current_stream().cuda_stream)
@@ -449,7 +458,8 @@ def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=Fa
     ev = _timed("attn_self" if lk > 1024 else "attn_cross")
     _lib.check(getattr(_lib.lib(), fwd)(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
                                         k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
-                                        float(scale), _dt(q), int(p_mode), _p(ws), need, _stream()), fwd)
+                                        float(scale), _dt(q), int(p_mode), _p(ws), need, _stream(),
+                                        *((flags,) if smooth_v else ())), fwd)
     if ev is not None:
         ev.record()
         kt_ = KernelTimer.active
@@ -462,10 +472,11 @@ def attention_fp8_ranges_supported(b, heads, lq, lk, dh):
     return bool(_lib.lib().fino_attn_fp8_ranges_supported(int(b), int(heads), int(lq), int(lk), int(dh)))
 
 
-def attention_fp8_ranges(q, k, v, heads, ranges, out=None, scale=None, p_mode=None, smooth_k=False):
+def attention_fp8_ranges(q, k, v, heads, ranges, out=None, scale=None, p_mode=None, smooth_k=False, smooth_v=False):
     """attention_fp8() over the subset of key tiles attention_ranges() walks: the same int32 DEVICE table [ceil(Lq / 256), 3, 2]
     per 256 query rows (fino_attn_fwd_fp8_ranges; head_dim 64 only).  K / V are quantised whole, and `smooth_k` subtracts the mean
-    over ALL keys: the softmax over any subset of them cannot see it either.  A q-block without tiles gets zeros."""
+    over ALL keys: the softmax over any subset of them cannot see it either.  `smooth_v` likewise subtracts (and adds back) the
+    mean of V over ALL keys: the weights of any subset still sum to one.  A q-block without tiles gets zeros, not that mean."""
     p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
     assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
     b, lq, hd = q.shape
@@ -481,7 +492,8 @@ def attention_fp8_ranges(q, k, v, heads, ranges, out=None, scale=None, p_mode=No
     scale = dh ** -0.5 if scale is None else scale
     if dh != 64:
         raise RuntimeError(f"attention_fp8_ranges: head_dim {dh} is not supported (64 only)")
-    need = (_lib.lib().fino_attn_fp8_smooth_kv_bytes if smooth_k else _lib.lib().fino_attn_fp8_kv_bytes)(b, heads, lk, dh)
+    flags = _fp8_smooth_flags(smooth_k, smooth_v)
+    need = _lib.lib().fino_attn_fp8_smoothed_kv_bytes(b, heads, lk, dh, flags)
     key = (q.device.index, torch.cuda.current_stream().cuda_stream)
     ws = _attn_fp8_ws.get(key)
     if ws is None or ws.numel() < need:
@@ -490,7 +502,7 @@ def attention_fp8_ranges(q, k, v, heads, ranges, out=None, scale=None, p_mode=No
     _lib.check(_lib.lib().fino_attn_fwd_fp8_ranges(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
                                                   k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0),
                                                   out.stride(1), float(scale), _dt(q), int(p_mode), _p(ws), need,
-                                                  1 if smooth_k else 0, _p(ranges), _stream()), "fino_attn_fwd_fp8_ranges")
+                                                  flags, _p(ranges), _stream()), "fino_attn_fwd_fp8_ranges")
     if ev is not None:
         ev.record()
         kt_ = KernelTimer.active

@@ -269,7 +269,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                            ("ff2", blk.ffn.net[2].weight)):
                 yield li, key, w
 
-    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False):
+    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False, smooth_v=False):
         """The 3-D self-attention (transformer_wan.py:108) with fp8 (e4m3) matrix operands -- q, k, v and P on the
         block-scaled fp8 MFMA, softmax and accumulation fp32 (fino_attn_fwd_fp8, head_dim 128 as two 64-channel sub-heads).
         Opt-in, single-GPU forward only; no reference counterpart: rel-RMS ~5e-2 per attention output on N(0, 1) inputs
@@ -277,13 +277,18 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         p_mode: "exp2" | "ramp" -- how a softmax weight becomes its e4m3 byte (ops.FP8_P_*; None = ops.FP8_P_DEFAULT).
         smooth_k: subtract the per-(batch element, head, channel) mean of K over the keys before K is quantised
         (fino_attn_fwd_fp8_smooth): invisible to the softmax, and a channel offset that all keys share (a to_k bias, norm_k
-        weights, low-frequency RoPE channels) stops taking the mantissa bits.  Off by default."""
+        weights, low-frequency RoPE channels) stops taking the mantissa bits.  Off by default.
+        smooth_v: subtract the per-(batch element, head, channel) mean of V over the keys before V is quantised and add it back
+        to the normalised output in fp32 (fino_attn_fwd_fp8_smoothed): exact, the softmax weights sum to one, and an offset that
+        all keys of a channel share (attn1.to_v.bias, a DC component of the modulated input: V has no norm and no RoPE) stops
+        taking the mantissa bits.  Off by default."""
         if enabled and self._window is not None:
             raise NotImplementedError("fp8 attention with window attention: the range walk exists in the bf16 / fp16 kernel "
                                       "only; disable_window_attention() first")
         self.fp8_attention = bool(enabled)
         self.fp8_p_mode = p_mode
         self.fp8_smooth_k = bool(smooth_k)
+        self.fp8_smooth_v = bool(smooth_v)
         return self
 
     # ------------------------------------------------------------------ sliding-window self-attention over frames
@@ -689,7 +694,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         if self.fp8_attention and sh is None and hasattr(o, "attention_fp8"):
             def attend(q_, k_, v_, heads_, **kw_):
                 return o.attention_fp8(q_, k_, v_, heads_, p_mode=getattr(self, "fp8_p_mode", None),
-                                       smooth_k=getattr(self, "fp8_smooth_k", False), **kw_)
+                                       smooth_k=getattr(self, "fp8_smooth_k", False),
+                                       smooth_v=getattr(self, "fp8_smooth_v", False), **kw_)
         plain_attend = attend is o.attention
         # sliding-window self-attention over frames: this forward's decision (the timestep callback is read here, once)
         win = self._window_begin(ppf, pph * ppw, id_frames, dev)

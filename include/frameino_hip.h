@@ -194,6 +194,24 @@ int fino_attn_fwd_fp8_smooth(const void* q, const void* k, const void* v, void* 
                              int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs,
                              int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode, void* kv_workspace,
                              int64_t kv_workspace_bytes, void* stream);
+/* The flag-word form of the two calls above, and SMOOTH V.  smooth = 0 is fino_attn_fwd_fp8, FINO_FP8_SMOOTH_K is
+ * fino_attn_fwd_fp8_smooth (the same launches, sizes and bits); bit FINO_FP8_SMOOTH_V also subtracts the mean of V over the keys,
+ * one fp32 per (batch element, head, head channel), before V is quantised to e4m3, and adds it back to the normalised output in
+ * fp32 before the one rounding to bf16 / fp16.  The rule: O = P (V - mu) / l + mu, exact because the weights P / l sum to exactly 1
+ * (l sums the same rounded P bytes on the matrix pipe) -- no correction term, for any subset of the keys.  What it buys: V carries
+ * one scale per (channel, 32-key block), so an offset all keys of a channel share (a to_v bias, a DC component of the input: V has
+ * no norm and no RoPE) no longer takes the three mantissa bits.  The mean is computed as smooth K's (256-key chunks, fixed order, no
+ * atomics), in the same two launches when both bits are set.  head_dim 128's tail split keeps its partials mu-free and the
+ * combine adds mu.  Workspace (fino_attn_fp8_smoothed_kv_bytes; 0 for unsupported arguments or flags outside 0 .. 3):
+ *     [ smooth & FINO_FP8_SMOOTH_K ? fino_attn_fp8_smooth_kv_bytes : fino_attn_fp8_kv_bytes | with FINO_FP8_SMOOTH_V: pad to 16 B |
+ *       V mean fp32 [batch][heads * head_dim] | V partial sums fp32 [batch][ceil(lk / 256)][heads * head_dim] ] */
+#define FINO_FP8_SMOOTH_K 1
+#define FINO_FP8_SMOOTH_V 2
+int64_t fino_attn_fp8_smoothed_kv_bytes(int batch, int heads, int64_t lk, int head_dim, int smooth);
+int fino_attn_fwd_fp8_smoothed(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq, int64_t lk,
+                               int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs,
+                               int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode, void* kv_workspace,
+                               int64_t kv_workspace_bytes, void* stream, int smooth);
 
 /* Cross-attention over key sequences whose TAIL is one row repeated -- the zero-padded prompt of
  * pipelines/pipeline_wan_i2v_motion_FrameINO.py:235-238: every padding token of the 512 the text cross-attention
@@ -233,7 +251,10 @@ int fino_attn_fwd_ranges(const void* q, const void* k, const void* v, void* o, i
  * of a query moves by the same q.mean), so the workspace is what fino_attn_fp8_kv_bytes / fino_attn_fp8_smooth_kv_bytes say.  A
  * 256-row q-block that walks the tiles T computes, to the same bits, what fino_attn_fwd_fp8's default kernel computes for those
  * query rows over the keys of T gathered into one sequence; a q-block without tiles stores zeros.  head_dim 64 only
- * (FINO_ERR_UNSUPPORTED otherwise); always the free-running 4-wave kernel, whatever FINO_TUNE_ATTN_FP8_KERNEL says. */
+ * (FINO_ERR_UNSUPPORTED otherwise); always the free-running 4-wave kernel, whatever FINO_TUNE_ATTN_FP8_KERNEL says.
+ * smooth_k = 2 or 3 is the flag word of fino_attn_fwd_fp8_smoothed (FINO_FP8_SMOOTH_V alone, or both): the mean of V is the mean
+ * over all keys as well (the weights of any subset still sum to 1), the workspace is fino_attn_fp8_smoothed_kv_bytes of that word,
+ * and a q-block without tiles still stores zeros, not the mean. */
 int fino_attn_fp8_ranges_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim);
 int fino_attn_fwd_fp8_ranges(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq, int64_t lk,
                              int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs,
