@@ -26,6 +26,7 @@ from .lora import LoraModelMixin
 from .mx_linears import MXLinearsMixin
 from .step_cache import PyramidAttentionBroadcastMixin
 from .transformer_wan import FeedForward, _Config, _MLP2
+from .window_attention import SelfAttentionOptionsMixin
 
 
 class _LayerNormZero(nn.Module):
@@ -81,9 +82,20 @@ def cog_sincos_pos_embed(embed_dim, pw, ph, frames, spatial_scale, temporal_scal
     return torch.cat([temporal, spatial], dim=-1).flatten(0, 1)
 
 
-class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, PyramidAttentionBroadcastMixin, MXLinearsMixin):
+class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, PyramidAttentionBroadcastMixin, MXLinearsMixin,
+                                  SelfAttentionOptionsMixin):
     """MX linears (enable_mxfp8_linears / enable_mxfp6_linears): four large linears of every block -- QKV, attention out, FFN
     up / down; with `enable_fp8_attention()` MXFP8 is BASELINE config 5's "fp8 MFMA path" end to end.
+
+    fp8 attention (enable_fp8_attention): the joint text + video self-attention (attention_processor.py:2863 of the reference,
+    head_dim 64: 55 % of the CogVideoX-5B step) -- K / V quantised per call with one scale per 32 elements (`fino_attn_fwd_fp8`).
+    No reference counterpart: tolerance stated in tests/test_attention_fp8_gpu.py and
+    tests/test_fullsize_oracle_gpu.py against fp32 and against this model's own bf16 forward.
+
+    Window attention (enable_window_attention): a video query attends the text rows, its window and the
+    sink frames; text queries and text keys stay dense (`prefix_rows` of frameino_amd/window_attention.py = the text rows).  With
+    `enable_fp8_attention()` it takes `ops.attention_fp8_ranges` with the model's p_mode / smooth_k / smooth_v.  MX linears and
+    LoRA work with it; a user-installed attention processor, and fp8 attention at a head_dim other than 64, are refused.
 
     Step caching (diffusers' CacheMixin surface: enable_cache / disable_cache / is_cache_enabled / cache_context /
     _reset_stateful_cache, and `cache_log`; frameino_amd/step_cache.py): Pyramid Attention Broadcast,
@@ -98,6 +110,8 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
     fp8 attention, LoRA and window attention combine with it: the cache stores whatever the branch produced.  At BASELINE
     config 5 the buffers are 42 x 235 MB = 9.9 GB.  `FirstBlockCacheConfig` is refused."""
     _loader_name = "load_cogvideox_transformer"
+    _window_table_cache = "_pos_cache"
+    _fp8_window_walk = True       # fino_attn_fwd_fp8_ranges (head_dim 64; any other is refused by `_window_refusals`)
 
     def __init__(self, num_attention_heads=30, attention_head_dim=64, in_channels=16, out_channels=16,
                  flip_sin_to_cos=True, freq_shift=0, time_embed_dim=512, ofs_embed_dim=None, text_embed_dim=4096,
@@ -144,7 +158,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         self._packed = None
         self._pos_cache = {}
         self.ops = ops            # kernel front end (tests inject a CPU stand-in)
-        self.fp8_attention = False           # see enable_fp8_attention
+        self._init_self_attention_options()
         # q leaves its LayerNorm + RoPE kernel multiplied by head_dim**-0.5 * log2(e) and the attention kernels take q.k as
         # the exp2 argument (FINO_ATTN_SCALE_FOLDED): at head_dim 64 that selects the 4-wave kernel with the running maximum
         # folded into its MFMAs (-5 % per step).  Video rows: one rounding of q.c instead of q; the 226 text rows (LayerNorm
@@ -153,9 +167,6 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         # in the last block, rows nobody reads afterwards (text rows; frames beyond forward(live_frames=)) are keys / values only
         self.skip_dead_rows = os.environ.get("FINO_SKIP_DEAD_ROWS", "1") != "0"
         self.original_attn_processors = None
-        self._window = None               # WindowAttentionConfig or None: see enable_window_attention
-        self._window_forwards = 0
-        self.window_attention_log = []    # (forward index, timestep or None, windowed) since enable_window_attention
 
     # ---- reference surface (:346-444) ----
     @property
@@ -210,7 +221,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         had_fp8 = self._mx_invalidate()
         self._reset_stateful_cache()
         self._packed = None
-        self._pos_cache.clear()           # (the window-attention range tables live here too)
+        self._pos_cache.clear()           # (the window-attention range tables live here too: `_window_table_cache`)
         return had_fp8
 
     def _apply(self, fn, *args, **kwargs):          # .to() / .cuda() / .half()
@@ -231,134 +242,44 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                            ("ff2", blk.ff.net[2].weight)):
                 yield li, key, w
 
-    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False, smooth_v=False):
-        """The joint text + video self-attention (attention_processor.py:2863 of the reference, head_dim 64: 55 % of the
-        CogVideoX-5B step) with fp8 e4m3 matrix operands -- K / V quantised per call with one scale per 32 elements, Q and
-        P in registers, both products on the block-scaled fp8 MFMA, fp32 softmax and accumulation
-        (`fino_attn_fwd_fp8`).  With `enable_mxfp8_linears()` this is BASELINE config 5's "fp8 MFMA path" end to end.
-        No reference counterpart: tolerance stated in tests/test_attention_fp8_gpu.py and
-        tests/test_fullsize_oracle_gpu.py against fp32 and against this model's own bf16 forward.
-        p_mode: "exp2" | "ramp" -- how a softmax weight becomes its e4m3 byte (ops.FP8_P_*; None = ops.FP8_P_DEFAULT).
-        smooth_k: subtract the per-(batch element, head, channel) mean of K over the keys before K is quantised
-        (fino_attn_fwd_fp8_smooth): invisible to the softmax, and a channel offset that all keys share (a to_k bias, norm_k
-        weights, low-frequency RoPE channels) stops taking the mantissa bits.  Off by default.
-        smooth_v: subtract the per-(batch element, head, channel) mean of V over the keys before V is quantised and add it back
-        to the normalised output in fp32 (fino_attn_fwd_fp8_smoothed): exact, the softmax weights sum to one, and an offset that
-        all keys of a channel share (attn1.to_v.bias, a DC component of the modulated input: V has no norm and no RoPE) stops
-        taking the mantissa bits.  Off by default."""
-        self.fp8_attention = bool(enabled)
-        self.fp8_p_mode = p_mode
-        self.fp8_smooth_k = bool(smooth_k)
-        self.fp8_smooth_v = bool(smooth_v)
-        return self
-
-    # ---- sliding-window self-attention over frames ----
-    def enable_window_attention(self, config):
-        """Opt-in, approximate: in every block not in `config.skip_layers` a video query attends the text rows, its own latent
-        frame +- `config.window_frames` neighbours and the sink frames (`config.sink_frames`, and the trailing
-        `forward(id_frames=n)` frames) instead of every token; text queries and text keys stay dense.  `ops.attention_ranges`
-        -- or, with `enable_fp8_attention()`, `ops.attention_fp8_ranges` with the model's p_mode / smooth_k -- over a table of
-        key-tile ranges per 256 query rows (frameino_amd/window_attention.py, `prefix_rows` = the text rows; DESIGN.md section
-        6g).  A window that covers the whole clip takes the dense call, bit for bit.  MX linears and LoRA work with it; a
-        user-installed attention processor, and fp8 attention at a head_dim other than 64, are refused (here where they can be
-        seen, else by the forward before anything is launched).  No reference counterpart."""
-        from .window_attention import WindowAttentionConfig
-        if not isinstance(config, WindowAttentionConfig):
-            raise TypeError(f"enable_window_attention takes a WindowAttentionConfig, got {type(config)}")
-        if any(li >= len(self.transformer_blocks) for li in config.skip_layers):
-            raise ValueError(f"skip_layers = {config.skip_layers}: this model has {len(self.transformer_blocks)} blocks")
-        self._window_refusals(self._default_processors())
-        self._window = config
-        self._window_forwards = 0
-        self.window_attention_log = []
-        return self
-
-    def disable_window_attention(self):
-        self._window = None
-        return self
-
-    @property
-    def is_window_attention_enabled(self):
-        return self._window is not None
-
-    def _window_refusals(self, default_procs):
+    def _window_refusals(self, fp8, default_procs, shard=None):
         what = "window attention (enable_window_attention)"
         if not default_procs:
             raise NotImplementedError(f"{what} with a user-installed attention processor: the windows are applied by the "
                                       f"built-in MI355CogVideoXAttnProcessor path only")
-        if self.fp8_attention and self.config.attention_head_dim != 64:
+        if fp8 and self.config.attention_head_dim != 64:
             raise NotImplementedError(f"{what} with fp8 attention at head_dim {self.config.attention_head_dim}: the fp8 range "
                                       f"walk (fino_attn_fwd_fp8_ranges) exists for head_dim 64 only")
 
-    def _window_begin(self, nf, tpf, lt, id_frames, dev):
-        """This forward's window state, decided before anything is launched: None (off, or outside the timestep range), else
-        `.table(q_rows)` -> the device range table of those rows of the joint sequence, or None when it covers every key tile
-        (the dense call) -- and `.skip`, the blocks that stay dense.  Reads the timestep callback ONCE and appends to
-        `window_attention_log`."""
-        cfg = self._window
-        if cfg is None:
-            return None
-        id_frames = int(id_frames or 0)
-        if not 0 <= id_frames < nf:
-            raise ValueError(f"id_frames = {id_frames} of {nf} latent frames")
-        t, on = None, True
-        if cfg.timestep_range is not None:
-            t = float(cfg.current_timestep_callback())
-            on = cfg.timestep_range[0] < t < cfg.timestep_range[1]
-        self.window_attention_log.append((self._window_forwards, t, on))
-        self._window_forwards += 1
-        if not on:
-            return None
-        from . import window_attention as wa
-        sinks = tuple(cfg.sink_frames) + tuple(range(nf - id_frames, nf))
-        L = lt + nf * tpf
+    def _qkv_heads(self, ops, li, blk, e, x2, t1, sel, b, L, lt, cos, sin, qfold):
+        """the head of block li's attention branch over all rows: norm1 (CogVideoXLayerNormZero, or emitted directly as the
+        linear's MXFP8 activations), the fused QKV projection, per-head LayerNorm + RoPE on q and k -> q | k | v [B, L, 3D]"""
+        c = self.config
+        d, heads, dh = self.inner_dim, c.num_attention_heads, c.attention_head_dim
+        xq1 = self._ln_q(li, "qkv", 2, x2, weight=e.n1w, bias=e.n1b, shift=t1[:, 0], scale=t1[:, 1], sel=sel, eps=c.norm_eps)
+        n = None if xq1 is not None else ops.layernorm_zero(x2, e.n1w, e.n1b, t1[:, 0], t1[:, 1], sel, c.norm_eps)
+        qkv = self._lin(li, "qkv", n, e.wqkv, e.bqkv, xq=xq1).view(b, L, 3 * d)
+        nq, nk = blk.attn1.norm_q, blk.attn1.norm_k
+        ops.headnorm_rope_(qkv[:, :, :d], heads, dh, nq.weight, nq.bias, nq.eps, cos, sin, rope_row0=lt, **qfold)
+        ops.headnorm_rope_(qkv[:, :, d:2 * d], heads, dh, nk.weight, nk.bias, nk.eps, cos, sin, rope_row0=lt)
+        return qkv
 
-        def table(q_rows):
-            key = ("window", nf, tpf, lt, cfg.key(), id_frames, tuple(q_rows), str(dev))
-            if key not in self._pos_cache:
-                tab = wa.frame_window_ranges(nf, tpf, cfg.window_frames, sinks, q_rows, prefix_rows=lt)
-                self._pos_cache[key] = None if wa.ranges_cover_all(tab, L) else tab.to(dev)
-            return self._pos_cache[key]
-
-        return SimpleNamespace(table=table, skip=frozenset(cfg.skip_layers))
-
-    def _self_attention(self, ops, win, li, q_rows, q, k, v, heads, dh, afold):
-        """the joint self-attention of block li over the query rows `q_rows`: dense, or over this forward's range table"""
-        tab = None if win is None or li in win.skip else win.table(q_rows)
-        fp8 = self.fp8_attention and dh == 64
-        if fp8:
-            kw = dict(p_mode=getattr(self, "fp8_p_mode", None), smooth_k=getattr(self, "fp8_smooth_k", False),
-                      smooth_v=getattr(self, "fp8_smooth_v", False), **afold)
-            if tab is not None:
-                return ops.attention_fp8_ranges(q, k, v, heads, tab, **kw)
-            return ops.attention_fp8(q, k, v, heads, **kw)
-        if tab is not None:
-            return ops.attention_ranges(q, k, v, heads, tab, **afold)
-        return ops.attention(q, k, v, heads, **afold)
-
-    def _attention_branch(self, ops, win, li, blk, e, x2, t1, sel, b, L, lt, cos, sin, qfold, afold, default_procs,
+    def _attention_branch(self, ops, win, fp8, li, blk, e, x2, t1, sel, b, L, lt, cos, sin, qfold, afold, default_procs,
                           image_rotary_emb, attention_kwargs, kept):
         """the first half of block li over all rows: x2 += gate * attn1(norm1(x2)) in place.  `kept` (Pyramid Attention
         Broadcast, a computing forward): the [B L, D] buffer that also receives the branch output y = T(acc + bias) -- from the
         out-projection's epilogue, or a user-installed processor's return value"""
         c = self.config
-        d, heads, dh = self.inner_dim, c.num_attention_heads, c.attention_head_dim
-        # CogVideoXLayerNormZero emitted directly as the linear's MXFP8 activations (None when it is not on that path)
-        xq1 = (self._ln_q(li, "qkv", 2, x2, weight=e.n1w, bias=e.n1b, shift=t1[:, 0], scale=t1[:, 1], sel=sel, eps=c.norm_eps)
-               if default_procs else None)
-        n = None if xq1 is not None else ops.layernorm_zero(x2, e.n1w, e.n1b, t1[:, 0], t1[:, 1], sel, c.norm_eps)
+        d, heads = self.inner_dim, c.num_attention_heads
         if default_procs:
-            qkv = self._lin(li, "qkv", n, e.wqkv, e.bqkv, xq=xq1).view(b, L, 3 * d)
-            nq, nk = blk.attn1.norm_q, blk.attn1.norm_k
-            ops.headnorm_rope_(qkv[:, :, :d], heads, dh, nq.weight, nq.bias, nq.eps, cos, sin, rope_row0=lt, **qfold)
-            ops.headnorm_rope_(qkv[:, :, d:2 * d], heads, dh, nk.weight, nk.bias, nk.eps, cos, sin, rope_row0=lt)
-            att = self._self_attention(ops, win, li, (0, L), qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads,
-                                       dh, afold)
+            qkv = self._qkv_heads(ops, li, blk, e, x2, t1, sel, b, L, lt, cos, sin, qfold)
+            att = self._attend(ops, qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads, fp8=fp8,
+                               ranges=self._window_ranges(win, li, (0, L)), **afold)
             keep = {} if kept is None else {"keep": kept}
             self._lin(li, "out", att.view(b * L, d), blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias,
                       ops.EPI_GATED_RESIDUAL_STAGED, residual=x2, gate=t1[:, 2], sel=sel, out=x2, **keep)
         else:
-            n3 = n.view(b, L, d)
+            n3 = ops.layernorm_zero(x2, e.n1w, e.n1b, t1[:, 0], t1[:, 1], sel, c.norm_eps).view(b, L, d)
             ah, ae = blk.attn1(hidden_states=n3[:, lt:], encoder_hidden_states=n3[:, :lt],
                                image_rotary_emb=image_rotary_emb, **(attention_kwargs or {}))
             y = torch.cat([ae, ah], dim=1).reshape(b * L, d)
@@ -443,7 +364,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         pk = self._packed or self._pack()
         default_procs = self._default_processors()
         if self._window is not None:             # what window attention refuses, before anything is launched
-            self._window_refusals(default_procs)
+            self._window_refusals(self.fp8_attention, default_procs)
         c = self.config
         b, nf, ch, hh, ww = hidden_states.shape
         d, heads, dh, ps = self.inner_dim, c.num_attention_heads, c.attention_head_dim, c.patch_size
@@ -453,6 +374,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         L = lt + lv
         # sliding-window self-attention over frames: this forward's decision (the timestep callback is read here, once)
         win = self._window_begin(nf, (hh // ps) * (ww // ps), lt, id_frames, dev)
+        fp8 = self.fp8_attention and dh == 64     # this call's self-attention takes fp8 operands
         # Pyramid Attention Broadcast: this forward's decision for every block's attn1 (callback read once, nothing launched yet);
         # the call's rows are ONE segment under the current cache_context
         pab = self._pab_begin(b, L, d, dt, dev)
@@ -513,13 +435,10 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
             t1, t2 = tables[2 * li], tables[2 * li + 1]                              # [2B, 3, D]
             if skip_dead_block and li == len(self.transformer_blocks) - 1:
                 # LAST block: every row is a key / value, only rows [r0, r1) of each sample are queries and go on
-                n = ops.layernorm_zero(x2, e.n1w, e.n1b, t1[:, 0], t1[:, 1], sel, c.norm_eps)
-                qkv = self._lin(li, "qkv", n, e.wqkv, e.bqkv).view(b, L, 3 * d)
-                nq, nk = blk.attn1.norm_q, blk.attn1.norm_k
-                ops.headnorm_rope_(qkv[:, :, :d], heads, dh, nq.weight, nq.bias, nq.eps, cos, sin, rope_row0=lt, **qfold)
-                ops.headnorm_rope_(qkv[:, :, d:2 * d], heads, dh, nk.weight, nk.bias, nk.eps, cos, sin, rope_row0=lt)
-                att = self._self_attention(ops, win, li, (r0, r1), qkv[:, r0:r1, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:],
-                                           heads, dh, afold)                             # [B, r1 - r0, D]
+                # (MX linears are off here -- `skip_dead` -- so the shared head takes its model-dtype norm1 and GEMM)
+                qkv = self._qkv_heads(ops, li, blk, e, x2, t1, sel, b, L, lt, cos, sin, qfold)
+                att = self._attend(ops, qkv[:, r0:r1, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:], heads, fp8=fp8,
+                                   ranges=self._window_ranges(win, li, (r0, r1)), **afold)      # [B, r1 - r0, D]
                 for i in range(b):
                     xs, ss = x2[i * L + r0:i * L + r1], sel[i * L + r0:i * L + r1]
                     self._lin(li, "out", att[i], blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias,
@@ -536,7 +455,7 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
             else:
                 # (... a computing forward: the out-projection also writes y = T(acc + bias) into this layer's buffer)
                 kept = None if seg is None else self._pab_buffer(seg, "self", li, d, dt, dev)
-                self._attention_branch(ops, win, li, blk, e, x2, t1, sel, b, L, lt, cos, sin, qfold, afold, default_procs,
+                self._attention_branch(ops, win, fp8, li, blk, e, x2, t1, sel, b, L, lt, cos, sin, qfold, afold, default_procs,
                                        image_rotary_emb, attention_kwargs, kept)
             xq2 = (self._ln_q(li, "ff1", 2, x2, weight=e.n2w, bias=e.n2b, shift=t2[:, 0], scale=t2[:, 1], sel=sel, eps=c.norm_eps)
                    if (li, "ff2") in self._fp8 else None)

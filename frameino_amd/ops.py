@@ -254,8 +254,9 @@ def _attention_workspace(b, heads, lq, lk, dh, device):
     return ws, need
 
 
-def attention(q, k, v, heads, out=None, scale=None):
-    """q [B, Lq, H*Dh] (row-strided view), k/v [B, Lk, H*Dh] -> o [B, Lq, H*Dh].  Non-causal SDPA."""
+def _attn_args(q, k, v, heads, out, scale):
+    """what the attention front ends share before the launch: q [B, Lq, H*Dh], k / v [B, Lk, H*Dh] (row-strided views) checked,
+    `out` and `scale` defaulted -> (b, lq, lk, hd, dh, out, scale)"""
     assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
     b, lq, hd = q.shape
     lk = k.shape[1]
@@ -265,19 +266,46 @@ def attention(q, k, v, heads, out=None, scale=None):
     if out is None:
         out = torch.empty((b, lq, hd), dtype=q.dtype, device=q.device)
     scale = dh ** -0.5 if scale is None else scale
-    ev = _timed("attn_self" if lk > 1024 else "attn_cross")      # same rule as the kernel symbols (VAR 0 / 1)
+    return b, lq, lk, hd, dh, out, scale
+
+
+def _check_ranges(ranges, lq):
+    nqb = (lq + 255) // 256
+    assert ranges.dtype == torch.int32 and ranges.is_cuda and ranges.is_contiguous() and tuple(ranges.shape) == (nqb, 3, 2), \
+        f"ranges: an int32 device tensor [{nqb}, 3, 2] is needed, got {ranges.dtype} {tuple(ranges.shape)} on {ranges.device}"
+
+
+def _timed_attn(b, lq, lk, hd, ranges=None, nbytes=False):
+    """an attention launch under KernelTimer: "attn_self" / "attn_cross" by the rule of the kernel symbols (VAR 0 / 1; a range
+    walk is always "attn_self"), 4.Lq.Lk.(H.Dh) FLOPs per batch element -- a range walk: from the tiles walked, the table's host
+    copy read only here, under the timer (one sync per launch) -- and, `nbytes`, the algorithmic bytes: Q read + O written (Lq
+    rows), K and V read (Lk rows), 2 bytes per element.  Returns a closure to call after the launch, or None."""
+    name = "attn_self" if ranges is not None or lk > 1024 else "attn_cross"
+    ev = _timed(name)
+    if ev is None:
+        return None
+
+    def done():
+        ev.record()
+        kt_ = KernelTimer.active
+        pairs = lq * lk if ranges is None else _ranges_pairs(ranges, lq, lk)
+        kt_.flops[name] = kt_.flops.get(name, 0.0) + 4.0 * b * pairs * hd
+        if nbytes:
+            kt_.bytes[name] = kt_.bytes.get(name, 0.0) + 2.0 * b * hd * (2 * lq + 2 * lk)
+    return done
+
+
+def attention(q, k, v, heads, out=None, scale=None):
+    """q [B, Lq, H*Dh] (row-strided view), k/v [B, Lk, H*Dh] -> o [B, Lq, H*Dh].  Non-causal SDPA."""
+    b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
+    done = _timed_attn(b, lq, lk, hd, nbytes=True)
     ws, ws_bytes = _attention_workspace(b, heads, lq, lk, dh, q.device) if SPLIT_ATTENTION_TAIL else (None, 0)
     _lib.check(_lib.lib().fino_attn_fwd_ws(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh,
                                           q.stride(0), q.stride(1), dh, k.stride(0), k.stride(1), dh,
                                           v.stride(0), v.stride(1), dh, out.stride(0), out.stride(1), dh,
                                           float(scale), _dt(q), _p(ws), ws_bytes, _stream()), "fino_attn_fwd_ws")
-    if ev is not None:
-        ev.record()
-        kt_ = KernelTimer.active
-        nm = "attn_self" if lk > 1024 else "attn_cross"
-        kt_.flops[nm] = kt_.flops.get(nm, 0.0) + 4.0 * b * lq * lk * hd      # 4.Lq.Lk.(H.Dh) per batch element
-        # algorithmic bytes of the launch: Q read + O written (Lq rows), K and V read (Lk rows), 2 bytes per element
-        kt_.bytes[nm] = kt_.bytes.get(nm, 0.0) + 2.0 * b * hd * (2 * lq + 2 * lk)
+    if done is not None:
+        done()
     return out
 
 
@@ -300,29 +328,15 @@ def attention_ranges(q, k, v, heads, ranges, out=None, scale=None):
     [ceil(Lq / 256), 3, 2] of up to three ascending, disjoint [begin, end) ranges of 64-key tiles per q-block ((0, 0): unused),
     shared by all heads and batch elements (fino_attn_fwd_ranges; frameino_amd/window_attention.py builds the tables of the
     sliding window over frames).  A q-block without tiles gets zeros."""
-    assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
-    b, lq, hd = q.shape
-    lk = k.shape[1]
-    dh = hd // heads
-    for t in (q, k, v):
-        assert t.stride(2) == 1 and t.is_cuda
-    nqb = (lq + 255) // 256
-    assert ranges.dtype == torch.int32 and ranges.is_cuda and ranges.is_contiguous() and tuple(ranges.shape) == (nqb, 3, 2), \
-        f"ranges: an int32 device tensor [{nqb}, 3, 2] is needed, got {ranges.dtype} {tuple(ranges.shape)} on {ranges.device}"
-    if out is None:
-        out = torch.empty((b, lq, hd), dtype=q.dtype, device=q.device)
-    scale = dh ** -0.5 if scale is None else scale
-    ev = _timed("attn_self")
+    b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
+    _check_ranges(ranges, lq)
+    done = _timed_attn(b, lq, lk, hd, ranges, nbytes=True)
     _lib.check(_lib.lib().fino_attn_fwd_ranges(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh,
                                               q.stride(0), q.stride(1), dh, k.stride(0), k.stride(1), dh,
                                               v.stride(0), v.stride(1), dh, out.stride(0), out.stride(1), dh,
                                               float(scale), _dt(q), _p(ranges), _stream()), "fino_attn_fwd_ranges")
-    if ev is not None:
-        ev.record()
-        kt_ = KernelTimer.active
-        # FLOPs and bytes from the tiles walked (the table's host copy is read only here, under the timer: one sync per launch)
-        kt_.flops["attn_self"] = kt_.flops.get("attn_self", 0.0) + 4.0 * b * _ranges_pairs(ranges, lq, lk) * hd
-        kt_.bytes["attn_self"] = kt_.bytes.get("attn_self", 0.0) + 2.0 * b * hd * (2 * lq + 2 * lk)
+    if done is not None:
+        done()
     return out
 
 
@@ -336,16 +350,8 @@ def attention_tail(q, k, v, heads, lk_b, tail_mult, out=None, scale=None):
     from lk_b[i] on are ignored.  Equals attention() on the expanded sequences up to the rounding of one weight
     (fino_attn_fwd_tail: the walking kernel; head_dim 128, B <= 4, Lk > 64 -- attention_tail_supported)."""
     import ctypes
-    assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
-    b, lq, hd = q.shape
-    lk = k.shape[1]
-    dh = hd // heads
-    for t in (q, k, v):
-        assert t.stride(2) == 1 and t.is_cuda
+    b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
     assert len(lk_b) == b and len(tail_mult) == b
-    if out is None:
-        out = torch.empty((b, lq, hd), dtype=q.dtype, device=q.device)
-    scale = dh ** -0.5 if scale is None else scale
     lk_arr = (ctypes.c_int * b)(*[int(x) for x in lk_b])
     mult_arr = (ctypes.c_float * b)(*[float(x) for x in tail_mult])
     ev = _timed("attn_cross")
@@ -422,6 +428,15 @@ if _p_env not in FP8_P_MODES:
 FP8_P_DEFAULT = FP8_P_MODES[_p_env]
 
 
+def _attn_fp8_workspace(need, device):
+    """the byte workspace of the quantised K / V images, one per (device, stream), grown on demand"""
+    key = (device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _attn_fp8_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _attn_fp8_ws[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
 def _fp8_smooth_flags(smooth_k, smooth_v):
     # include/frameino_hip.h: FINO_FP8_SMOOTH_K = 1, FINO_FP8_SMOOTH_V = 2
     return (1 if smooth_k else 0) | (2 if smooth_v else 0)
@@ -437,34 +452,20 @@ def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=Fa
     (fino_attn_fwd_fp8_smoothed): exact, because the softmax weights sum to one; V has one scale per (channel, 32 keys), so an
     offset all keys of a channel share (a to_v bias, a DC component) stops costing mantissa bits."""
     p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
-    assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
-    b, lq, hd = q.shape
-    lk = k.shape[1]
-    dh = hd // heads
-    for t in (q, k, v):
-        assert t.stride(2) == 1 and t.is_cuda
-    if out is None:
-        out = torch.empty((b, lq, hd), dtype=q.dtype, device=q.device)
-    scale = dh ** -0.5 if scale is None else scale
+    b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
     flags = _fp8_smooth_flags(smooth_k, smooth_v)
     fwd = "fino_attn_fwd_fp8_smoothed" if smooth_v else ("fino_attn_fwd_fp8_smooth" if smooth_k else "fino_attn_fwd_fp8")
     need = _lib.lib().fino_attn_fp8_smoothed_kv_bytes(b, heads, lk, dh, flags)      # flags 0 / 1: the plain / smooth-K sizes
     if need <= 0:
         raise RuntimeError(f"attention_fp8: head_dim {dh} is not supported (64 or 128)")
-    key = (q.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _attn_fp8_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _attn_fp8_ws[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
-    ev = _timed("attn_self" if lk > 1024 else "attn_cross")
+    ws = _attn_fp8_workspace(need, q.device)
+    done = _timed_attn(b, lq, lk, hd)
     _lib.check(getattr(_lib.lib(), fwd)(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
                                         k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
                                         float(scale), _dt(q), int(p_mode), _p(ws), need, _stream(),
                                         *((flags,) if smooth_v else ())), fwd)
-    if ev is not None:
-        ev.record()
-        kt_ = KernelTimer.active
-        nm = "attn_self" if lk > 1024 else "attn_cross"
-        kt_.flops[nm] = kt_.flops.get(nm, 0.0) + 4.0 * b * lq * lk * hd
+    if done is not None:
+        done()
     return out
 
 
@@ -478,36 +479,20 @@ def attention_fp8_ranges(q, k, v, heads, ranges, out=None, scale=None, p_mode=No
     over ALL keys: the softmax over any subset of them cannot see it either.  `smooth_v` likewise subtracts (and adds back) the
     mean of V over ALL keys: the weights of any subset still sum to one.  A q-block without tiles gets zeros, not that mean."""
     p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
-    assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
-    b, lq, hd = q.shape
-    lk = k.shape[1]
-    dh = hd // heads
-    for t in (q, k, v):
-        assert t.stride(2) == 1 and t.is_cuda
-    nqb = (lq + 255) // 256
-    assert ranges.dtype == torch.int32 and ranges.is_cuda and ranges.is_contiguous() and tuple(ranges.shape) == (nqb, 3, 2), \
-        f"ranges: an int32 device tensor [{nqb}, 3, 2] is needed, got {ranges.dtype} {tuple(ranges.shape)} on {ranges.device}"
-    if out is None:
-        out = torch.empty((b, lq, hd), dtype=q.dtype, device=q.device)
-    scale = dh ** -0.5 if scale is None else scale
+    b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
+    _check_ranges(ranges, lq)
     if dh != 64:
         raise RuntimeError(f"attention_fp8_ranges: head_dim {dh} is not supported (64 only)")
     flags = _fp8_smooth_flags(smooth_k, smooth_v)
     need = _lib.lib().fino_attn_fp8_smoothed_kv_bytes(b, heads, lk, dh, flags)
-    key = (q.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _attn_fp8_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _attn_fp8_ws[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
-    ev = _timed("attn_self")
+    ws = _attn_fp8_workspace(need, q.device)
+    done = _timed_attn(b, lq, lk, hd, ranges)
     _lib.check(_lib.lib().fino_attn_fwd_fp8_ranges(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
                                                   k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0),
                                                   out.stride(1), float(scale), _dt(q), int(p_mode), _p(ws), need,
                                                   flags, _p(ranges), _stream()), "fino_attn_fwd_fp8_ranges")
-    if ev is not None:
-        ev.record()
-        kt_ = KernelTimer.active
-        # FLOPs from the tiles walked (the table's host copy is read only here, under the timer: one sync per launch)
-        kt_.flops["attn_self"] = kt_.flops.get("attn_self", 0.0) + 4.0 * b * _ranges_pairs(ranges, lq, lk) * hd
+    if done is not None:
+        done()
     return out
 
 

@@ -27,6 +27,7 @@ import torch
 
 from . import ops
 from .lora import LoraPipelineMixin, lora_denoise_loop
+from .window_attention import window_attention_runs_eagerly
 from .schedulers import CogVideoXDDIMScheduler  # noqa: F401  (re-export)
 
 
@@ -247,14 +248,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
     def _window_attention_check(self):
         """the limits of window attention (CogVideoXTransformer3DModel.enable_window_attention), checked before any work.  ->
         whether the loop must run eagerly: with a timestep range the host decides per step whether the windows apply."""
-        cfg = getattr(self.transformer, "_window", None)
-        if cfg is None or cfg.timestep_range is None:
-            return False                      # off, or the range table is a static device tensor: the step captures as it is
-        if self.use_hip_graph is True:
-            raise RuntimeError("use_hip_graph=True with window attention under a timestep range: whether a step's self-attention "
-                               "is windowed changes from step to step on the host's schedule, which one captured step cannot "
-                               "contain (the loop runs eagerly; use_hip_graph=None or False)")
-        return True
+        return window_attention_runs_eagerly(self.transformer, self.use_hip_graph)
 
     def _prepare_rotary_positional_embeddings(self, height, width, num_frames, device):
         """reference :540-584 (patch_size_t None) + the FrameIn first-frame extension :834-839."""

@@ -37,6 +37,7 @@ import torch
 
 from . import ops
 from .lora import LoraPipelineMixin, lora_denoise_loop
+from .window_attention import window_attention_runs_eagerly
 
 
 def _basic_clean(text):
@@ -188,18 +189,9 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
     def _window_attention_check(self):
         """the limits of window attention (WanTransformer3DModel.enable_window_attention), checked before any work.  -> whether
         the loop must run eagerly: with a timestep range the host decides per step whether the windows apply."""
-        cfg = getattr(self.transformer, "_window", None)
-        if cfg is None:
-            return False
-        if getattr(self, "parallel", None) is not None:
+        if getattr(self.transformer, "is_window_attention_enabled", False) and getattr(self, "parallel", None) is not None:
             raise NotImplementedError("window attention runs on one GPU; this pipeline has a parallel plan")
-        if cfg.timestep_range is None:
-            return False                      # the range table is a static device tensor: the step captures as it is
-        if self.use_hip_graph is True:
-            raise RuntimeError("use_hip_graph=True with window attention under a timestep range: whether a step's self-attention "
-                               "is windowed changes from step to step on the host's schedule, which one captured step cannot "
-                               "contain (the loop runs eagerly; use_hip_graph=None or False)")
-        return True
+        return window_attention_runs_eagerly(self.transformer, self.use_hip_graph)
 
     def to(self, device):
         for m in (self.transformer, self.vae, self.text_encoder):

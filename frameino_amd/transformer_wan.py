@@ -32,6 +32,7 @@ from .loading import FromPretrainedMixin
 from .lora import LoraModelMixin
 from .mx_linears import MXLinearsMixin
 from .step_cache import FirstBlockCacheMixin
+from .window_attention import SelfAttentionOptionsMixin
 
 
 class _Config(dict):
@@ -117,9 +118,19 @@ class WanTransformerBlock(nn.Module):
         self.scale_shift_table = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
 
 
-class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, FirstBlockCacheMixin, MXLinearsMixin):
+class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, FirstBlockCacheMixin, MXLinearsMixin,
+                            SelfAttentionOptionsMixin):
     """MX linears (enable_mxfp8_linears / enable_mxfp6_linears): the six large linears of every block -- QKV, attention out,
-    cross-attention q / out, FFN up / down."""
+    cross-attention q / out, FFN up / down.
+
+    fp8 attention (enable_fp8_attention): the 3-D self-attention (transformer_wan.py:108) -- fino_attn_fwd_fp8, head_dim 128 as
+    two 64-channel sub-heads.  Single-GPU forward only; rel-RMS ~5e-2 per attention output on N(0, 1) inputs
+    (tests/test_attention_fp8_gpu.py).  The text cross-attention stays bf16.
+
+    Window attention (enable_window_attention; frameino_amd/window_attention.py): first-block caching, MX
+    linears and LoRA work with it; fp8 attention (the range walk exists in the bf16 / fp16 kernel only), Pyramid Attention
+    Broadcast, a token-sharded plan and user-installed attention processors are refused."""
+    _window_table_cache = "_rope_cache"
     _loader_name = "load_wan_transformer"
     _keep_in_fp32_modules = ["time_embedder", "scale_shift_table", "norm1", "norm2", "norm3"]   # reference :393
     _lora_wan_layout = True   # LoRA files in the original Wan-repo / kohya key layout map onto these names (frameino_amd/lora.py)
@@ -158,7 +169,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         # 4-wave kernel fold the running maximum into its MFMAs.  False (default): q rounded where the reference rounds it,
         # scale applied to the logits -- inside the power-capped step the fold buys nothing.
         self.fold_softmax_scale = False
-        self.fp8_attention = False        # see enable_fp8_attention
+        self._init_self_attention_options()
         # The text cross-attention over a ZERO-PADDED prompt (pipeline_wan...FrameINO.py:235-238 pads every prompt to 512 tokens
         # with zero rows): all padding tokens yield the same K and V row, so the real tokens + ONE key that stands for the run
         # give the same softmax (ops.attention_tail: softmax(q.[K; k x M]) [V; v x M] = softmax(q.[K; k] + [0; ln M]) [V; v]).
@@ -169,9 +180,6 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self.reassociate_text_out = os.environ.get("FINO_TEXT_REASSOC", "1") != "0"
         # honour `forward(live_rows=...)`: in the last block, rows the caller discards contribute K | V only (round 6)
         self.skip_dead_rows = os.environ.get("FINO_SKIP_DEAD_ROWS", "1") != "0"
-        self._window = None               # WindowAttentionConfig or None: see enable_window_attention
-        self._window_forwards = 0
-        self.window_attention_log = []    # (forward index, timestep or None, windowed) since enable_window_attention
 
     # ------------------------------------------------------------------ diffusers-style surface
     @property
@@ -222,7 +230,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._reset_stateful_cache()
         self._packed = None
         self._text_cache.clear()
-        self._rope_cache.clear()          # (the window-attention range tables live here too)
+        self._rope_cache.clear()          # (the window-attention range tables live here too: `_window_table_cache`)
         self._ws.clear()
         return had_fp8
 
@@ -269,61 +277,12 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                            ("ff2", blk.ffn.net[2].weight)):
                 yield li, key, w
 
-    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False, smooth_v=False):
-        """The 3-D self-attention (transformer_wan.py:108) with fp8 (e4m3) matrix operands -- q, k, v and P on the
-        block-scaled fp8 MFMA, softmax and accumulation fp32 (fino_attn_fwd_fp8, head_dim 128 as two 64-channel sub-heads).
-        Opt-in, single-GPU forward only; no reference counterpart: rel-RMS ~5e-2 per attention output on N(0, 1) inputs
-        (tests/test_attention_fp8_gpu.py).  The text cross-attention stays bf16.
-        p_mode: "exp2" | "ramp" -- how a softmax weight becomes its e4m3 byte (ops.FP8_P_*; None = ops.FP8_P_DEFAULT).
-        smooth_k: subtract the per-(batch element, head, channel) mean of K over the keys before K is quantised
-        (fino_attn_fwd_fp8_smooth): invisible to the softmax, and a channel offset that all keys share (a to_k bias, norm_k
-        weights, low-frequency RoPE channels) stops taking the mantissa bits.  Off by default.
-        smooth_v: subtract the per-(batch element, head, channel) mean of V over the keys before V is quantised and add it back
-        to the normalised output in fp32 (fino_attn_fwd_fp8_smoothed): exact, the softmax weights sum to one, and an offset that
-        all keys of a channel share (attn1.to_v.bias, a DC component of the modulated input: V has no norm and no RoPE) stops
-        taking the mantissa bits.  Off by default."""
-        if enabled and self._window is not None:
-            raise NotImplementedError("fp8 attention with window attention: the range walk exists in the bf16 / fp16 kernel "
-                                      "only; disable_window_attention() first")
-        self.fp8_attention = bool(enabled)
-        self.fp8_p_mode = p_mode
-        self.fp8_smooth_k = bool(smooth_k)
-        self.fp8_smooth_v = bool(smooth_v)
-        return self
-
-    # ------------------------------------------------------------------ sliding-window self-attention over frames
-    def enable_window_attention(self, config):
-        """Opt-in, approximate: in every block not in `config.skip_layers` a query attends its own latent frame +-
-        `config.window_frames` neighbours plus the sink frames (`config.sink_frames`, and the trailing `forward(id_frames=n)`
-        frames) instead of every token -- `ops.attention_ranges` over a per-q-block table of key-tile ranges
-        (frameino_amd/window_attention.py has the exact definition and the kernel's granularity).  A
-        window that covers the whole clip takes the dense call, bit for bit.  First-block caching, MX linears and LoRA work
-        with it; fp8 attention, Pyramid Attention Broadcast, a token-sharded plan and user-installed attention processors are
-        refused (here where they can be seen, else by the forward).  No reference counterpart."""
-        from .window_attention import WindowAttentionConfig
-        if not isinstance(config, WindowAttentionConfig):
-            raise TypeError(f"enable_window_attention takes a WindowAttentionConfig, got {type(config)}")
-        if any(li >= len(self.blocks) for li in config.skip_layers):
-            raise ValueError(f"skip_layers = {config.skip_layers}: this model has {len(self.blocks)} blocks")
-        self._window_refusals(config, self.parallel, self._pab_on, self._default_processors())
-        self._window = config
-        self._window_forwards = 0
-        self.window_attention_log = []
-        return self
-
-    def disable_window_attention(self):
-        self._window = None
-        return self
-
-    @property
-    def is_window_attention_enabled(self):
-        return self._window is not None
-
-    def _window_refusals(self, config, shard, pab_on, default_procs):
+    def _window_refusals(self, fp8, default_procs, shard=None):
         what = "window attention (enable_window_attention)"
-        if self.fp8_attention:
-            raise NotImplementedError(f"{what} with fp8 attention: the range walk exists in the bf16 / fp16 kernel only")
-        if pab_on:
+        if fp8:
+            raise NotImplementedError(f"{what} with fp8 attention: the range walk exists in the bf16 / fp16 kernel only; switch "
+                                      f"one of them off first (disable_window_attention() / enable_fp8_attention(False))")
+        if self._pab_on:
             raise NotImplementedError(f"{what} with Pyramid Attention Broadcast: not implemented in this version (first-block "
                                       f"caching is)")
         if shard is not None and getattr(shard, "active", True):
@@ -338,45 +297,6 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             raise NotImplementedError("Pyramid Attention Broadcast with window attention (enable_window_attention): not "
                                       "implemented in this version (first-block caching is)")
         return super().enable_cache(config)
-
-    def _window_begin(self, ppf, tpf, id_frames, dev):
-        """This forward's window state, decided before anything is launched: None (off, or outside the timestep range), else
-        `.table(q_rows)` -> the device range table of those query rows, or None when it covers every key tile (the dense call)
-        -- and `.skip`, the blocks that stay dense.  Reads the timestep callback ONCE and appends to `window_attention_log`."""
-        cfg = self._window
-        if cfg is None:
-            return None
-        id_frames = int(id_frames or 0)
-        if not 0 <= id_frames < ppf:
-            raise ValueError(f"id_frames = {id_frames} of {ppf} latent frames")
-        t, on = None, True
-        if cfg.timestep_range is not None:
-            t = float(cfg.current_timestep_callback())
-            on = cfg.timestep_range[0] < t < cfg.timestep_range[1]
-        self.window_attention_log.append((self._window_forwards, t, on))
-        self._window_forwards += 1
-        if not on:
-            return None
-        from . import window_attention as wa
-        sinks = tuple(cfg.sink_frames) + tuple(range(ppf - id_frames, ppf))
-        L = ppf * tpf
-
-        def table(q_rows):
-            key = ("window", ppf, tpf, cfg.key(), id_frames, tuple(q_rows), str(dev))
-            if key not in self._rope_cache:
-                tab = wa.frame_window_ranges(ppf, tpf, cfg.window_frames, sinks, q_rows)
-                self._rope_cache[key] = None if wa.ranges_cover_all(tab, L) else tab.to(dev)
-            return self._rope_cache[key]
-
-        return SimpleNamespace(table=table, skip=frozenset(cfg.skip_layers))
-
-    @staticmethod
-    def _window_kw(c, li, q_rows):
-        """`ranges=` of block li's self-attention call over the query rows `q_rows`, or nothing (dense)"""
-        if c.win is None or li in c.win.skip:
-            return {}
-        tab = c.win.table(q_rows)
-        return {} if tab is None else {"ranges": tab}
 
     def _workspace(self, L, dtype, device):
         # one workspace per (shape, cache_context name): the two CFG branches may run concurrently on two streams
@@ -648,7 +568,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         sh = shard if shard is not None else self.parallel
         sh = sh if (sh is not None and sh.active) else None
         if self._window is not None:             # what window attention refuses, before anything is launched
-            self._window_refusals(self._window, sh, self._pab_on, default_procs)
+            self._window_refusals(self.fp8_attention, default_procs, sh)
         lo, n, lpad = 0, L, L
         tk = {}         # the shard's tile height for its GEMM calls (a per-call argument of the C ABI; {} = the library's planner)
         if sh is not None:
@@ -690,25 +610,14 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         shared = (self.dedup_shared_prefix and b > 1 and sh is None and hidden_states.stride(0) == 0 and default_procs
                   and same_rows and pab is None)
         fold = self.fold_softmax_scale
-        attend = o.attention
-        if self.fp8_attention and sh is None and hasattr(o, "attention_fp8"):
-            def attend(q_, k_, v_, heads_, **kw_):
-                return o.attention_fp8(q_, k_, v_, heads_, p_mode=getattr(self, "fp8_p_mode", None),
-                                       smooth_k=getattr(self, "fp8_smooth_k", False),
-                                       smooth_v=getattr(self, "fp8_smooth_v", False), **kw_)
-        plain_attend = attend is o.attention
+        fp8 = self.fp8_attention and sh is None and hasattr(o, "attention_fp8")     # this call's self-attention takes fp8 operands
         # sliding-window self-attention over frames: this forward's decision (the timestep callback is read here, once)
-        win = self._window_begin(ppf, pph * ppw, id_frames, dev)
-        if win is not None:
-            def attend(q_, k_, v_, heads_, ranges=None, **kw_):
-                if ranges is None:
-                    return o.attention(q_, k_, v_, heads_, **kw_)
-                return o.attention_ranges(q_, k_, v_, heads_, ranges, **kw_)
+        win = self._window_begin(ppf, pph * ppw, 0, id_frames, dev)
         # rows whose output the caller reads (`live_rows`): honoured in the last block on the single-GPU default-processor path
         live = None
         # (not under Pyramid Attention Broadcast: a cached branch output covers every row, so that any later step may use it)
         if (live_rows is not None and self.skip_dead_rows and default_procs and sh is None and len(self.blocks) > 1
-                and not self._fp8 and plain_attend and pab is None):
+                and not self._fp8 and not fp8 and pab is None):
             l0, l1 = int(live_rows[0]), int(live_rows[1])
             if 0 <= l0 < l1 <= n and (l1 - l0) < n:
                 live = (l0, l1)
@@ -718,7 +627,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                      eps=cfg.eps, sh=sh, tk=tk, pk=pk, ws=ws, x=ws.x[:nr], nrm=ws.n[:nr], att=ws.att[:nr], q2=ws.q2[:nr],
                      ff=ws.ff[:nr], qkv=ws.qkv[:nr], cos=cos, sin=sin, cos1=cos1, sin1=sin1, sel=sel, mod=mod, head=head,
                      text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
-                     afold={"scale": o.SCALE_FOLDED} if fold else {}, attend=attend, default_procs=default_procs,
+                     afold={"scale": o.SCALE_FOLDED} if fold else {}, fp8=fp8, default_procs=default_procs,
                      shared=shared, fbc=fbc, pab=pab, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
                      live=live, win=win,
                      live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
@@ -782,8 +691,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._lin(li, "qkv", n1, e.wqkv, e.bqkv, out=q1)
         self._qk_norm_rope(blk, q1, d, c.cos1, c.sin1, c.dh, c.qfold)
         q3 = q1.view(1, n, 3 * d)
-        c.attend(q3[:, :, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, out=a1.view(1, n, d), **c.afold,
-                 **self._window_kw(c, li, (0, n)))
+        self._attend(o, q3[:, :, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, fp8=c.fp8,
+                     ranges=self._window_ranges(c.win, li, (0, n)), out=a1.view(1, n, d), **c.afold)
         self._lin(li, "out", a1, to_out.weight, to_out.bias, o.EPI_GATED_RESIDUAL, residual=x[:n], gate=m[:, 2], sel=sel1,
                   out=x[:n])
         for bi in range(1, c.b):
@@ -799,8 +708,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._qk_norm_rope(blk, c.qkv, d, c.cos, c.sin, c.dh, c.qfold)
         q3 = c.qkv.view(b, n, 3 * d)
         s0, s1 = c.rows                  # every row is a key; under `live_rows` only the live rows of the last block are queries
-        c.attend(q3[:, s0:s1, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, out=c.att.view(b, n, d)[:, s0:s1], **c.afold,
-                 **self._window_kw(c, li, (s0, s1)))
+        self._attend(o, q3[:, s0:s1, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, fp8=c.fp8,
+                     ranges=self._window_ranges(c.win, li, (s0, s1)), out=c.att.view(b, n, d)[:, s0:s1], **c.afold)
         return False
 
     def _sa_heads_exchange(self, c, li, blk, e, m):
@@ -1050,7 +959,7 @@ class _Call:
     views it runs a batch through) are the only fields written after `_bind`."""
     __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
                  "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
-                 "afold", "attend", "default_procs", "shared", "fbc", "pab", "keep", "h0", "h1c", "attention_kwargs", "live",
+                 "afold", "fp8", "default_procs", "shared", "fbc", "pab", "keep", "h0", "h1c", "attention_kwargs", "live",
                  "live_segs", "rows", "segs", "win", "elements")
 
     def __init__(self, **fields):

@@ -13,8 +13,13 @@ queries that see every key.
 The granularity is the kernel's: a q-block's window is the union over its rows (a block that straddles two frames sees both
 frames' windows) and frame boundaries are rounded OUTWARD to key tiles, so a query may see up to 63 keys of a frame just outside
 its window on either side, never fewer keys than the definition says.  `block_mask` expands a table to the boolean mask of
-exactly what the kernel computes.  Pure Python + CPU torch: nothing here touches a GPU."""
+exactly what the kernel computes.  The tables are pure Python + CPU torch: nothing in them touches a GPU.
+
+`SelfAttentionOptionsMixin` is the host side both DiTs inherit: the fp8 and window switches with their state, the per-forward
+window decision and the one dispatch among the four `ops` self-attention front ends; `window_attention_runs_eagerly` is the rule
+both pipelines apply."""
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Any, Callable, Optional, Tuple
 
 import torch
@@ -153,3 +158,137 @@ class WindowAttentionConfig:
     def key(self):
         """what a range table depends on"""
         return (self.window_frames, self.sink_frames)
+
+
+def window_attention_runs_eagerly(transformer, use_hip_graph):
+    """The pipelines' rule, checked before any work.  -> whether the denoising loop must run eagerly: with a timestep range the
+    host decides per step whether the windows apply.  Off, or without a range (the table is a static device tensor), the step
+    captures as it is."""
+    if not getattr(transformer, "window_attention_is_timestep_gated", False):
+        return False
+    if use_hip_graph is True:
+        raise RuntimeError("use_hip_graph=True with window attention under a timestep range: whether a step's self-attention "
+                           "is windowed changes from step to step on the host's schedule, which one captured step cannot "
+                           "contain (the loop runs eagerly; use_hip_graph=None or False)")
+    return True
+
+
+class SelfAttentionOptionsMixin:
+    """The self-attention switches of a DiT -- fp8 operands (`enable_fp8_attention`) and the sliding window over frames
+    (`enable_window_attention`) -- with their state, and `_attend`, the one place that picks among `ops.attention`,
+    `ops.attention_ranges`, `ops.attention_fp8` and `ops.attention_fp8_ranges`.  The model calls `_init_self_attention_options()`
+    from its constructor, names the dict that holds its positional tables in `_window_table_cache` (the range tables are dropped
+    with them), says in `_window_refusals(fp8, default_procs, shard=None)` what it does not combine with the windows, calls
+    `_window_begin` once per forward and keeps its kernel front end in `self.ops`."""
+    _window_table_cache = None    # name of the model's dict of positional tables: `_window_begin` caches the range tables there
+    _fp8_window_walk = False      # whether the model has an fp8 range walk at all; without one fp8 is refused while windows are on
+
+    def _init_self_attention_options(self):
+        self.fp8_attention = False        # see enable_fp8_attention
+        self.fp8_p_mode = None
+        self.fp8_smooth_k = False
+        self.fp8_smooth_v = False
+        self._window = None               # WindowAttentionConfig or None: see enable_window_attention
+        self._window_forwards = 0
+        self.window_attention_log = []    # (forward index, timestep or None, windowed) since enable_window_attention
+
+    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False, smooth_v=False):
+        """The self-attention with fp8 (e4m3) matrix operands -- q, k, v and P on the block-scaled fp8 MFMA, softmax and
+        accumulation fp32 (`ops.attention_fp8`; the model's class docstring says where it applies).  Opt-in, no reference counterpart.
+        p_mode: "exp2" | "ramp" -- how a softmax weight becomes its e4m3 byte (ops.FP8_P_*; None = ops.FP8_P_DEFAULT).
+        smooth_k: subtract the per-(batch element, head, channel) mean of K over the keys before K is quantised
+        (fino_attn_fwd_fp8_smooth): invisible to the softmax, and a channel offset that all keys share (a to_k bias, norm_k
+        weights, low-frequency RoPE channels) stops taking the mantissa bits.  Off by default.
+        smooth_v: subtract the per-(batch element, head, channel) mean of V over the keys before V is quantised and add it back
+        to the normalised output in fp32 (fino_attn_fwd_fp8_smoothed): exact, the softmax weights sum to one, and an offset that
+        all keys of a channel share (attn1.to_v.bias, a DC component of the modulated input: V has no norm and no RoPE) stops
+        taking the mantissa bits.  Off by default."""
+        if enabled and self._window is not None and not self._fp8_window_walk:
+            # (such a model's hook refuses fp8 whatever else holds; one with an fp8 walk decides per head_dim, in its forward)
+            self._window_refusals(True, self._default_processors(), getattr(self, "parallel", None))
+        self.fp8_attention = bool(enabled)
+        self.fp8_p_mode = p_mode
+        self.fp8_smooth_k = bool(smooth_k)
+        self.fp8_smooth_v = bool(smooth_v)
+        return self
+
+    def enable_window_attention(self, config):
+        """Opt-in, approximate: in every block not in `config.skip_layers` a query attends its own latent frame +-
+        `config.window_frames` neighbours plus the sink frames (`config.sink_frames`, and the trailing `forward(id_frames=n)`
+        frames) instead of every token -- `ops.attention_ranges` (with fp8 attention, where the model has that walk,
+        `ops.attention_fp8_ranges`) over a per-q-block table of key-tile ranges (the module docstring has the exact definition and
+        the kernel's granularity; DESIGN.md sections 6f, 6g).  A window that covers the whole clip takes the dense call, bit for
+        bit.  In a joint sequence (CogVideoX: the text rows in front of frame 0, `prefix_rows`) only the video queries are windowed: the
+        prefix rows are keys every query sees and queries that see every key.  What the model does not combine with it (its class docstring) is refused here where it can be seen, else by the
+        forward before anything is launched.  No reference counterpart."""
+        if not isinstance(config, WindowAttentionConfig):
+            raise TypeError(f"enable_window_attention takes a WindowAttentionConfig, got {type(config)}")
+        if any(li >= self.config.num_layers for li in config.skip_layers):
+            raise ValueError(f"skip_layers = {config.skip_layers}: this model has {self.config.num_layers} blocks")
+        self._window_refusals(self.fp8_attention, self._default_processors(), getattr(self, "parallel", None))
+        self._window = config
+        self._window_forwards = 0
+        self.window_attention_log = []
+        return self
+
+    def disable_window_attention(self):
+        self._window = None
+        return self
+
+    @property
+    def is_window_attention_enabled(self):
+        return self._window is not None
+
+    @property
+    def window_attention_is_timestep_gated(self):
+        """on, and under a `timestep_range`: whether a forward is windowed is then decided on the host, forward by forward"""
+        return self._window is not None and self._window.timestep_range is not None
+
+    def _window_begin(self, frames, tokens_per_frame, prefix_rows, id_frames, dev):
+        """This forward's window state, decided before anything is launched: None (off, or outside the timestep range), else
+        `.table(q_rows)` -> the device range table of those query rows of the sequence [prefix_rows | frames], or None when it
+        covers every key tile (the dense call) -- and `.skip`, the blocks that stay dense.  Reads the timestep callback ONCE and
+        appends to `window_attention_log`."""
+        cfg = self._window
+        if cfg is None:
+            return None
+        id_frames = int(id_frames or 0)
+        if not 0 <= id_frames < frames:
+            raise ValueError(f"id_frames = {id_frames} of {frames} latent frames")
+        t, on = None, True
+        if cfg.timestep_range is not None:
+            t = float(cfg.current_timestep_callback())
+            on = cfg.timestep_range[0] < t < cfg.timestep_range[1]
+        self.window_attention_log.append((self._window_forwards, t, on))
+        self._window_forwards += 1
+        if not on:
+            return None
+        sinks = tuple(cfg.sink_frames) + tuple(range(frames - id_frames, frames))
+        L = prefix_rows + frames * tokens_per_frame
+        cache = getattr(self, self._window_table_cache)
+        # tests and tools read the keys by position (id_frames, q_rows), per model: a sequence without a prefix keeps the key
+        # it has always had, without the component
+        prefix = (prefix_rows,) if prefix_rows else ()
+
+        def table(q_rows):
+            key = ("window", frames, tokens_per_frame) + prefix + (cfg.key(), id_frames, tuple(q_rows), str(dev))
+            if key not in cache:
+                tab = frame_window_ranges(frames, tokens_per_frame, cfg.window_frames, sinks, q_rows, prefix_rows)
+                cache[key] = None if ranges_cover_all(tab, L) else tab.to(dev)
+            return cache[key]
+
+        return SimpleNamespace(table=table, skip=frozenset(cfg.skip_layers))
+
+    @staticmethod
+    def _window_ranges(win, li, q_rows):
+        """the range table of block li's self-attention over the query rows `q_rows`, or None (dense)"""
+        return None if win is None or li in win.skip else win.table(q_rows)
+
+    def _attend(self, ops, q, k, v, heads, *, fp8, ranges=None, **kw):
+        """one self-attention call: dense or over `ranges`, bf16 / fp16 or -- `fp8` -- with the model's fp8 options; `kw`: out=,
+        scale="""
+        if fp8:
+            kw.update(p_mode=self.fp8_p_mode, smooth_k=self.fp8_smooth_k, smooth_v=self.fp8_smooth_v)
+        if ranges is None:
+            return (ops.attention_fp8 if fp8 else ops.attention)(q, k, v, heads, **kw)
+        return (ops.attention_fp8_ranges if fp8 else ops.attention_ranges)(q, k, v, heads, ranges, **kw)
