@@ -67,6 +67,13 @@ def main():
                     help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
                          "every query attends its own frame +- N neighbours plus the first frame and the ID frame, e.g. 2.  Not "
                          "together with --pab")
+    ap.add_argument("--sparse-attention", type=float, default=None, metavar="TAU",
+                    help="dynamic block-sparse self-attention (approximate; quality on real checkpoints unmeasured): per head and "
+                         "q-block only the key tiles that a pooled predictor credits with a share TAU of the softmax mass, e.g. "
+                         "0.9, plus the own frame, the first frame and the ID frame.  Not together with --window-frames, --pab "
+                         "or --fp8-attention")
+    ap.add_argument("--sparse-window-frames", type=int, default=0, metavar="N",
+                    help="with --sparse-attention: the own frame +- N neighbours are always kept (default 0)")
     ap.add_argument("--fp8-attention", action="store_true",
                     help="fp8 (e4m3) operands in the 3-D self-attention (reduced precision, opt-in).  Not together with --window-frames")
     ap.add_argument("--smooth-k", action="store_true",
@@ -155,6 +162,10 @@ def main():
     if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)
         from frameino_amd.window_attention import WindowAttentionConfig
         transformer.enable_window_attention(WindowAttentionConfig(window_frames=a.window_frames, sink_frames=(0,)))
+    if a.sparse_attention is not None:             # forced tiles: own frame +- N, the first frame, the ID frame (id_frames)
+        from frameino_amd.window_attention import SparseAttentionConfig
+        transformer.enable_sparse_attention(SparseAttentionConfig(cdf_threshold=a.sparse_attention,
+                                                                  window_frames=a.sparse_window_frames, sink_frames=(0,)))
     t0 = time.perf_counter()
     canvas, tracks, id_tensor, pads = synthetic_conditions(a.frames, a.height, a.width, dev)
     traj = prepare_traj_tensor(tracks, a.height, a.width, 6, a.width, a.height, device=dev)        # [F, 3, H, W]

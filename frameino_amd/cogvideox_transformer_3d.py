@@ -242,6 +242,10 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                            ("ff2", blk.ff.net[2].weight)):
                 yield li, key, w
 
+    def enable_sparse_attention(self, config):
+        raise NotImplementedError("sparse attention (enable_sparse_attention) is not wired on this model: the joint text + video "
+                                  "sequence needs its own forced tiles (the Wan DiT has it)")
+
     def _window_refusals(self, fp8, default_procs, shard=None):
         what = "window attention (enable_window_attention)"
         if not default_procs:

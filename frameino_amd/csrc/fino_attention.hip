@@ -44,7 +44,8 @@ namespace {
 
 // VAR only names the launch site (0: long-KV self-attention, 1: short-KV text cross-attention) so that profilers
 // report the two call classes as separate kernel symbols; the code is identical.  attn_ppd_kernel alone also has VAR 2:
-// the key tiles of a q-block come from a table of ranges (fino_attn_fwd_ranges).
+// the key tiles of a q-block come from a table of ranges (fino_attn_fwd_ranges), and VAR 3: from a bitmask per (batch element,
+// head, q-block) (fino_attn_fwd_tiles).
 template <typename T, int D, int VAR>
 __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -477,7 +478,7 @@ constexpr int kPdSlots = 4;
 #define PD_MAX_SOFTMAX 1   /* 1: the row maxima of S(t) open softmax(t) instead of riding in the P.V shadow of matrix(t-1) */
 #endif
 template <typename T, int D, int VAR>
-__global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnParams p) {
+__global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnParams p, const AttnTileMask tm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int kTileBytes = kKV * D * 2;                  // 16 KiB (head_dim 128) / 8 KiB (64)
     constexpr int kC = D / 8;                                // 16-byte chunks per row
@@ -559,6 +560,60 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
         // the ragged tile is the LAST global tile; ranges ascend, so it can only be the last tile walked
         if (nt > 0 && (lk & (kKV - 1)) && PD_GTILE(nt - 1) == ntall - 1) rg_rag = nt - 1;
     }
+    // VAR 3 (fino_attn_fwd_tiles; whole blocks as VAR 2): the block walks the tiles whose bits are set in its row of tm.mask.
+    // The row is expanded ONCE, here, into a list g(0 .. nt - 1) of ascending global tile indices in LDS behind the rings,
+    // followed by kAttnTileListPad entries ntall (the tile wholly past the last key: what a look-ahead past nt fetches).
+    // Contract of VAR 2 otherwise: local loop index, ring slots and wait counts by it, only the DMA offset and the ragged mask
+    // see g.  Bits at or beyond ntall are dropped, so whatever the mask holds no DMA leaves the head's K / V.
+    // The loop needs g(w + 3) for K and g(w + 2) for V, w = t + grp: two scalars, g3_k and g3_v, shifted once per tile; the
+    // entry that comes in, g(w + 4), is read (inline asm, as every LDS read of the loop) at the TOP of the softmax phase, where
+    // lgkmcnt is 0 (the matrix phase ended on lgkmcnt(0)), and waited for with an lgkmcnt(0) of its own in front of the first
+    // PD_KISSUE, the only other LDS reads of that phase: the hand-counted waits of the matrix phase see what they saw.
+    constexpr uint32_t kListBase = 2 * kPdSlots * kTileBytes;
+    int g3_k = 0, g3_v = 0, g3_p0 = 0, g3_p1 = 0, g3_p2 = 0, g3_p3 = 0, g3_p4 = 0;
+    uint32_t g3_in = 0;
+#define PD_LIST_ISSUE(IDX_)                                                                                  \
+    {                                                                                                        \
+        const uint32_t a_ = kListBase + (uint32_t)(IDX_) * 4u;                                               \
+        asm volatile("ds_read_b32 %0, %1" : "=&v"(g3_in) : "v"(a_));                                         \
+    }
+#define PD_LIST_WAIT(OUT_)                                                                                   \
+    {                                                                                                        \
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(g3_in));                                                  \
+        OUT_ = __builtin_amdgcn_readfirstlane((int)g3_in);                                                   \
+    }
+    if constexpr (VAR == 3) {
+        const uint32_t* mrow = tm.mask + bi * tm.bs + head * tm.hs + (int64_t)qb * tm.words;
+        const int nw = (ntall + 31) >> 5;
+        uint32_t* list = reinterpret_cast<uint32_t*>(smem + kListBase);
+        // the clipped word wi: bits at or beyond ntall dropped
+        auto word = [&](int wi) -> uint32_t {
+            const int left = ntall - 32 * wi;
+            const uint32_t m = left >= 32 ? 0xffffffffu : ((1u << left) - 1u);
+            return mrow[wi] & m;
+        };
+        int total = 0;
+        for (int wi = 0; wi < nw; ++wi) total += __builtin_popcount(word(wi));
+        nt = __builtin_amdgcn_readfirstlane(total);
+        for (int tl = tid; tl < ntall; tl += kWaves * 64) {
+            const int wi = tl >> 5;
+            int before = 0;
+            for (int j = 0; j < wi; ++j) before += __builtin_popcount(word(j));
+            const uint32_t wd = word(wi);
+            if ((wd >> (tl & 31)) & 1u) list[before + __builtin_popcount(wd & ((1u << (tl & 31)) - 1u))] = (uint32_t)tl;
+        }
+        if (tid < kAttnTileListPad) list[nt + tid] = (uint32_t)ntall;
+        if (nt > 0 && (lk & (kKV - 1)) && ((word((ntall - 1) >> 5) >> ((ntall - 1) & 31)) & 1u)) rg_rag = nt - 1;
+        __syncthreads();
+        // g(0 .. 4): the prologue's tiles and what the first softmax phase issues (g(grp + 3), g(grp + 2)); plain LDS reads,
+        // nothing is in flight yet
+        const uint32_t g0_ = list[0], g1_ = list[1], g2_ = list[2], g3_ = list[3], g4_ = list[4];
+        g3_p0 = __builtin_amdgcn_readfirstlane((int)g0_);
+        g3_p1 = __builtin_amdgcn_readfirstlane((int)g1_);
+        g3_p2 = __builtin_amdgcn_readfirstlane((int)g2_);
+        g3_p3 = __builtin_amdgcn_readfirstlane((int)g3_);
+        g3_p4 = __builtin_amdgcn_readfirstlane((int)g4_);
+    }
 
     // ---- K / V staging by LDS-DMA: a tile is 16 pieces of 1 KiB (4 rows); wave w moves pieces w and w + 8 of K and of V.
     //      The lane's row inside the piece, its chunk position and the swizzle (row bits a step of 8 pieces leaves alone) are
@@ -578,17 +633,20 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
     const int k_piece_bytes = (int)(8 * kRPP * p.k_rs * 2), v_piece_bytes = (int)(8 * kRPP * p.v_rs * 2);
     const int k_tile_bytes = (int)(kKV * p.k_rs * 2), v_tile_bytes = (int)(kKV * p.v_rs * 2);
     // tile index clamped to nt: tile nt lies wholly past the last key (zeros), and the scalar offset stays inside 32 bits
-#define PD_DMA_K(TILE_)                                                                                      \
+    // (VAR 3, inside the loop only: the K stream's tile is g3_k, the V stream's g3_v; its prologue names its tiles itself)
+#define PD_DMA_K(TILE_) PD_DMA_K_G(TILE_, VAR == 3 ? g3_k : (VAR == 2 ? PD_GTILE(TILE_) : ((TILE_) < nt ? (TILE_) : nt)))
+#define PD_DMA_K_G(TILE_, G_)                                                                                \
     {                                                                                                        \
-        const int tl_ = VAR == 2 ? PD_GTILE(TILE_) : ((TILE_) < nt ? (TILE_) : nt);                          \
+        const int tl_ = (G_);                                                                                \
         _Pragma("unroll") for (int i_ = 0; i_ < kPW; ++i_)                                                   \
             __builtin_amdgcn_raw_ptr_buffer_load_lds(                                                        \
                 k_rsrc, (FINO_LDS void*)(smem + ((TILE_) & (kPdSlots - 1)) * kTileBytes + (8 * i_ + wv) * 1024), 16, \
                 k_voff, tl_ * k_tile_bytes + i_ * k_piece_bytes, 0, 0);                                      \
     }
-#define PD_DMA_V(TILE_)                                                                                      \
+#define PD_DMA_V(TILE_) PD_DMA_V_G(TILE_, VAR == 3 ? g3_v : (VAR == 2 ? PD_GTILE(TILE_) : ((TILE_) < nt ? (TILE_) : nt)))
+#define PD_DMA_V_G(TILE_, G_)                                                                                \
     {                                                                                                        \
-        const int tl_ = VAR == 2 ? PD_GTILE(TILE_) : ((TILE_) < nt ? (TILE_) : nt);                          \
+        const int tl_ = (G_);                                                                                \
         _Pragma("unroll") for (int i_ = 0; i_ < kPW; ++i_)                                                   \
             __builtin_amdgcn_raw_ptr_buffer_load_lds(                                                        \
                 v_rsrc, (FINO_LDS void*)(smem + kVBase + ((TILE_) & (kPdSlots - 1)) * kTileBytes + (8 * i_ + wv) * 1024), \
@@ -596,8 +654,15 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
     }
     // prologue: what the loop's schedule assumes was issued before it starts -- K(0..2), V(0..1) by everyone, and group 1
     // (whose softmax(0) issues K(4) / V(3)) also K(3) / V(2)
-    PD_DMA_K(0) PD_DMA_V(0) PD_DMA_K(1) PD_DMA_V(1) PD_DMA_K(2)
-    if (grp == 1) { PD_DMA_K(3) PD_DMA_V(2) }
+    if constexpr (VAR == 3) {
+        PD_DMA_K_G(0, g3_p0) PD_DMA_V_G(0, g3_p0) PD_DMA_K_G(1, g3_p1) PD_DMA_V_G(1, g3_p1) PD_DMA_K_G(2, g3_p2)
+        if (grp == 1) { PD_DMA_K_G(3, g3_p3) PD_DMA_V_G(2, g3_p2) }
+        g3_k = grp == 1 ? g3_p4 : g3_p3;
+        g3_v = grp == 1 ? g3_p3 : g3_p2;
+    } else {
+        PD_DMA_K(0) PD_DMA_V(0) PD_DMA_K(1) PD_DMA_V(1) PD_DMA_K(2)
+        if (grp == 1) { PD_DMA_K(3) PD_DMA_V(2) }
+    }
 
     // ---- Q fragments (B operand of S^T = K.Q^T): lane holds Q[q0 + r][16*ks + 8h .. +7] ----
     const int qrow = qb * kQBlock + wave * kQRowsPerWave + r;
@@ -639,8 +704,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
         }
     }
 #define MASK_RAGGED(T_)                                                                                     \
-    if (VAR == 2 ? (T_) == rg_rag : ((T_) == nt - 1 && (lk & (kKV - 1)))) { /* key = (j&3) + 8*(j>>2) + 4*h (+32) */ \
-        const int kbase_ = (VAR == 2 ? ntall - 1 : (T_)) * kKV + 4 * h;       /* VAR 2: keys of the GLOBAL last tile */ \
+    if (VAR >= 2 ? (T_) == rg_rag : ((T_) == nt - 1 && (lk & (kKV - 1)))) { /* key = (j&3) + 8*(j>>2) + 4*h (+32) */ \
+        const int kbase_ = (VAR >= 2 ? ntall - 1 : (T_)) * kKV + 4 * h;       /* VAR 2: keys of the GLOBAL last tile */ \
         _Pragma("unroll") for (int j_ = 0; j_ < 16; ++j_) {                                                 \
             const int key_ = kbase_ + (j_ & 3) + 8 * (j_ >> 2);                                             \
             if (key_ >= lk) sc0[j_] = -INFINITY;                                                            \
@@ -727,6 +792,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
     unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, tsm = 0, tse = 0, sa0 = 0, sa1 = 0, sa2 = 0, sa3 = 0, sa5 = 0, sa6 = 0;
 #endif
     for (int t = 0; t < nt; ++t) {
+        if constexpr (VAR == 3) PD_LIST_ISSUE(t + grp + 4)       // g(w + 4): lands during the softmax phase (PD_LIST_WAIT)
         ASTAMP(ts0)
         // ================= softmax phase =================
         const int w = t + grp;
@@ -782,6 +848,10 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
         }
         __builtin_amdgcn_sched_barrier(0);
         ASTAMP(tse)
+        if constexpr (VAR == 3) {                    // g(w + 4) has had the whole softmax phase to arrive
+            g3_v = g3_k;
+            PD_LIST_WAIT(g3_k)
+        }
 #if PD_PREK
         // K(t+1) was published a phase ago (vmcnt(4) below): the first two k-steps' fragments travel across the barrier
         if (t + 1 < nt) {
@@ -902,6 +972,10 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
     __builtin_amdgcn_s_barrier();                      // ... for EVERY wave: the epilogue stages its output rows in the rings
 #undef PD_DMA_K
 #undef PD_DMA_V
+#undef PD_DMA_K_G
+#undef PD_DMA_V_G
+#undef PD_LIST_ISSUE
+#undef PD_LIST_WAIT
 #undef PD_GTILE
 #undef PD_KISSUE
 #undef PD_KWAIT
@@ -935,7 +1009,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
         continue;
     }
     float inv = 1.0f / l_run;
-    if constexpr (VAR == 2)
+    if constexpr (VAR >= 2)
         if (nt == 0) inv = 0.f;                        // a q-block without key tiles stores zeros (O = 0, l = 0), not NaN
     {
         // every wave is past its last matrix phase (the barrier above): the K ring's first 64 KiB take the output rows, 8 KiB per wave
@@ -1855,7 +1929,7 @@ int launch_attn_v(AttnParams p, int64_t ws_bytes, hipStream_t st) {
         static FinoPerDeviceOnce once_d;
         if (int rc = fino_max_smem_once(once_d, reinterpret_cast<const void*>(&attn_ppd_kernel<T, D, VAR>), smem_d, "fino_attn_fwd"))
             return rc;
-        attn_ppd_kernel<T, D, VAR><<<grid, kWaves * 64, smem_d, st>>>(p);
+        attn_ppd_kernel<T, D, VAR><<<grid, kWaves * 64, smem_d, st>>>(p, AttnTileMask{});
     } else
         attn_pp_kernel<T, D, VAR><<<grid, kWaves * 64, smem, st>>>(p);
     FINO_LAUNCH_CHECK();
@@ -1878,13 +1952,30 @@ int launch_attn_ranges(AttnParams p, hipStream_t st) {
     const int groups = (p.batch * p.heads * p.vsplit + 7) / 8;
     p.full_x = groups * p.nqb_v; p.rem_x = 0; p.nwg = 0; p.per = 1;
     p.ws = nullptr; p.all_partial = 0;
-    attn_ppd_kernel<T, D, 2><<<dim3((unsigned)(8 * p.full_x)), kWaves * 64, smem_d, st>>>(p);
+    attn_ppd_kernel<T, D, 2><<<dim3((unsigned)(8 * p.full_x)), kWaves * 64, smem_d, st>>>(p, AttnTileMask{});
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
+}
+
+// fino_attn_fwd_tiles: always attn_ppd_kernel<T, D, 3>, whole blocks only; the tile list sits behind the rings
+template <typename T, int D>
+int launch_attn_tiles(AttnParams p, const AttnTileMask& tm, hipStream_t st) {
+    constexpr int smem_d = 2 * kPdSlots * kKV * D * 2 + (kAttnMaxTiles + kAttnTileListPad) * 4;
+    static FinoPerDeviceOnce once;
+    if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&attn_ppd_kernel<T, D, 3>), smem_d, "fino_attn_fwd_tiles"))
+        return rc;
+    attn_virtual_heads(p.batch, p.heads, p.nqb, p.vsplit, p.nqb_v);
+    const int groups = (p.batch * p.heads * p.vsplit + 7) / 8;
+    p.full_x = groups * p.nqb_v; p.rem_x = 0; p.nwg = 0; p.per = 1;
+    p.ws = nullptr; p.all_partial = 0;
+    attn_ppd_kernel<T, D, 3><<<dim3((unsigned)(8 * p.full_x)), kWaves * 64, smem_d, st>>>(p, tm);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }
 
 template <typename T, int D>
-int launch_attn(const AttnParams& p, int64_t ws_bytes, hipStream_t st) {
+int launch_attn(const AttnParams& p, const AttnTileMask& tm, int64_t ws_bytes, hipStream_t st) {
+    if (tm.mask) return launch_attn_tiles<T, D>(p, tm, st);
     if (p.ranges) return launch_attn_ranges<T, D>(p, st);
     return p.lk > 1024 ? launch_attn_v<T, D, 0>(p, ws_bytes, st) : launch_attn_v<T, D, 1>(p, ws_bytes, st);
 }
@@ -1926,7 +2017,8 @@ static int attn_common(const void* q, const void* k, const void* v, void* o, int
                        int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs,
                        int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs,
                        int64_t o_rs, int64_t o_hs, float scale, int dtype, void* workspace,
-                       int64_t workspace_bytes, int all_partial, void* stream, const int* ranges = nullptr) {
+                       int64_t workspace_bytes, int all_partial, void* stream, const int* ranges = nullptr,
+                       const uint32_t* mask = nullptr, int64_t mask_bs = 0, int64_t mask_hs = 0, int mask_words = 0) {
     FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_attn_fwd: dtype %d", dtype);
     if (all_partial) {
         static const uint16_t dummy_o[8] __attribute__((aligned(16))) = {0};
@@ -1968,12 +2060,13 @@ static int attn_common(const void* q, const void* k, const void* v, void* o, int
     p.all_partial = all_partial;
     p.tail_n = 0;
     p.ranges = ranges; p.vmean = nullptr;
+    const AttnTileMask tm{mask, mask_bs, mask_hs, mask_words};
     FINO_CHECK(((uintptr_t)workspace & 15) == 0, FINO_ERR_ARG, "fino_attn_fwd_ws: workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int64_t wb = workspace_bytes;
     if (dtype == FINO_BF16)
-        return head_dim == 128 ? launch_attn<BF16, 128>(p, wb, st) : launch_attn<BF16, 64>(p, wb, st);
-    return head_dim == 128 ? launch_attn<F16, 128>(p, wb, st) : launch_attn<F16, 64>(p, wb, st);
+        return head_dim == 128 ? launch_attn<BF16, 128>(p, tm, wb, st) : launch_attn<BF16, 64>(p, tm, wb, st);
+    return head_dim == 128 ? launch_attn<F16, 128>(p, tm, wb, st) : launch_attn<F16, 64>(p, tm, wb, st);
 }
 
 extern "C" int fino_attn_fwd_ws(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
@@ -2049,6 +2142,29 @@ extern "C" int fino_attn_fwd_ranges(const void* q, const void* k, const void* v,
     FINO_CHECK(((uintptr_t)ranges & 3) == 0, FINO_ERR_ARG, "fino_attn_fwd_ranges: the ranges table must be 4-byte aligned");
     return attn_common(q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs, v_hs,
                        o_bs, o_rs, o_hs, scale, dtype, nullptr, 0, 0, stream, ranges);
+}
+
+// Attention over the key tiles a bitmask names per (batch element, head, 256-row q-block) (include/frameino_hip.h):
+// fino_attn_fwd's arguments and checks + the device mask; always attn_ppd_kernel<T, D, 3>.
+extern "C" int fino_attn_tiles_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim) {
+    return fino_attn_ranges_supported(batch, heads, lq, lk, head_dim) && (lk + kKV - 1) / kKV <= kAttnMaxTiles;
+}
+
+extern "C" int fino_attn_fwd_tiles(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
+                                   int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs,
+                                   int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs,
+                                   int64_t o_rs, int64_t o_hs, float scale, int dtype, const uint32_t* mask,
+                                   int64_t mask_bs, int64_t mask_hs, int words, void* stream) {
+    FINO_CHECK(mask, FINO_ERR_ARG, "fino_attn_fwd_tiles: null mask");
+    FINO_CHECK(((uintptr_t)mask & 3) == 0, FINO_ERR_ARG, "fino_attn_fwd_tiles: the mask must be 4-byte aligned");
+    FINO_CHECK(lk > 0 && (lk + kKV - 1) / kKV <= kAttnMaxTiles, FINO_ERR_UNSUPPORTED,
+               "fino_attn_fwd_tiles: Lk=%lld is more than %d key tiles", (long long)lk, kAttnMaxTiles);
+    FINO_CHECK(words > 0 && (int64_t)words * 32 >= (lk + kKV - 1) / kKV, FINO_ERR_ARG,
+               "fino_attn_fwd_tiles: %d mask words per q-block do not hold %lld key tiles", words,
+               (long long)((lk + kKV - 1) / kKV));
+    FINO_CHECK(mask_bs >= 0 && mask_hs >= 0, FINO_ERR_ARG, "fino_attn_fwd_tiles: negative mask stride");
+    return attn_common(q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs, v_hs,
+                       o_bs, o_rs, o_hs, scale, dtype, nullptr, 0, 0, stream, nullptr, mask, mask_bs, mask_hs, words);
 }
 
 // Cross-attention over key sequences whose TAIL is one row repeated (a zero-padded prompt: every padding token yields the same

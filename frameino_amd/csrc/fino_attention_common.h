@@ -54,6 +54,16 @@ struct AttnParams {
     // (its partials stay mu-free).  nullptr: off -- every other caller.  Behind `ranges` for the same reason `ranges` is last.
     const float* vmean;
 };
+// fino_attn_fwd_tiles (attn_ppd_kernel<T, D, 3> only; a second kernel argument, so that AttnParams and with it every other
+// kernel's argument loads stay as they were): one bit per 64-key tile, bit t & 31 of word t >> 5, the row of (batch element b,
+// head h, q-block qb) at mask + b * bs + h * hs + qb * words (strides in words; 0 shares the rows across batch elements / heads).
+struct AttnTileMask {
+    const uint32_t* mask;
+    int64_t bs, hs;
+    int words;
+};
+constexpr int kAttnMaxTiles = 1024;          // key tiles a tile mask may name (fino_attn_tiles_supported): 65 536 keys
+constexpr int kAttnTileListPad = 8;          // list entries behind the last walked tile that the look-ahead may read
 
 // (XCD, slot in that XCD's list of blocks) -> (head-batch, q-block); false: an empty slot.  The q-blocks of one head run on
 // ONE XCD (hb = xcd + 8 g), so its K/V stream through that XCD's L2 only -- as long as batch*heads is a multiple of 8.

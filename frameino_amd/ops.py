@@ -340,6 +340,116 @@ def attention_ranges(q, k, v, heads, ranges, out=None, scale=None):
     return out
 
 
+def attention_tiles_supported(b, heads, lq, lk, dh):
+    return bool(_lib.lib().fino_attn_tiles_supported(int(b), int(heads), int(lq), int(lk), int(dh)))
+
+
+_MASK_DTYPES = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+
+
+def _check_tile_mask(mask, b, heads, lq, lk):
+    """a tile mask [B | 1, heads | 1, nqb, words] -> (words, batch stride, head stride) in words; size-1 dims share their rows"""
+    nqb, nta = (lq + 255) // 256, (lk + 63) // 64
+    ok = (isinstance(mask, torch.Tensor) and mask.dtype in _MASK_DTYPES and mask.is_cuda and mask.dim() == 4
+          and mask.is_contiguous() and mask.shape[0] in (1, b) and mask.shape[1] in (1, heads) and mask.shape[2] == nqb
+          and mask.shape[3] * 32 >= nta)
+    if not ok:
+        got = f"{mask.dtype} {tuple(mask.shape)} on {mask.device}" if isinstance(mask, torch.Tensor) else type(mask)
+        raise ValueError(f"mask: a contiguous int32 / uint32 device tensor [{b} | 1, {heads} | 1, {nqb}, >= {(nta + 31) // 32}] is "
+                         f"needed, got {got}")
+    words = mask.shape[3]
+    return words, (mask.shape[1] * nqb * words if mask.shape[0] == b and b > 1 else 0), (nqb * words if mask.shape[1] == heads and heads > 1 else 0)
+
+
+def _tile_mask_bits(mask, lk):
+    """host copy of a tile mask as bool [..., nqb, ceil(lk / 64)] (a host read: diagnostics only)"""
+    from .window_attention import unpack_tile_mask          # (the one unpacking of the layout; that module is pure torch)
+    return unpack_tile_mask(mask, lk)
+
+
+def tile_mask_density(mask, lk):
+    """fraction of the (q-block, key tile) pairs a tile mask keeps, over all its batch elements and heads.  A HOST read of the
+    mask (one sync): diagnostics only, never on the step's path."""
+    return float(_tile_mask_bits(mask, lk).float().mean())
+
+
+def attention_tile_plan_bytes(b, heads, lq, lk, dh):
+    """bytes of the fp32 workspace attention_tile_plan needs (0: shape not supported)"""
+    return int(_lib.lib().fino_attn_tile_plan_bytes(int(b), int(heads), int(lq), int(lk), int(dh)))
+
+
+_plan_ws = {}      # (device index, stream) -> fp32 workspace of attention_tile_plan (pooled q and k; grown on demand)
+
+
+def attention_tile_plan(q, k, heads, cdf, keep_ranges=None, scale=None, out=None, workspace=None):
+    """The tile mask of attention_tiles, predicted on the device from q [B, Lq, H*Dh] and k [B, Lk, H*Dh] as the attention call
+    gets them (fino_attn_tile_plan: mean-pooled q-blocks and key tiles, a softmax over the tiles, the smallest set of tiles by
+    descending mass that reaches `cdf` together with the always-kept tiles of `keep_ranges`, an int32 device table
+    [ceil(Lq / 256), 3, 2] in the format of attention_ranges, or None) -> int32 device tensor [B, heads, nqb, words].  `scale`
+    as attention(): SCALE_FOLDED when q carries it.  `out` / `workspace` (fp32, >= fino_attn_tile_plan_bytes): caller-owned
+    buffers, for a step that is captured.  No host read; deterministic."""
+    assert q.dim() == 3 and k.dim() == 3 and q.shape[0] == k.shape[0] and q.shape[2] == k.shape[2]
+    for t in (q, k):
+        assert t.stride(2) == 1 and t.is_cuda
+    b, lq, hd = q.shape
+    lk = k.shape[1]
+    dh = hd // heads
+    nqb, words = (lq + 255) // 256, ((lk + 63) // 64 + 31) // 32
+    if keep_ranges is not None:
+        _check_ranges(keep_ranges, lq)
+    if out is None:
+        out = torch.empty((b, heads, nqb, words), dtype=torch.int32, device=q.device)
+    assert out.dtype in _MASK_DTYPES and out.is_cuda and out.is_contiguous() and \
+        tuple(out.shape[:3]) == (b, heads, nqb) and out.dim() == 4 and out.shape[3] * 32 >= (lk + 63) // 64, \
+        f"out: a contiguous int32 device tensor [{b}, {heads}, {nqb}, >= {words}] is needed, got {out.dtype} {tuple(out.shape)}"
+    need = _lib.lib().fino_attn_tile_plan_bytes(b, heads, lq, lk, dh)
+    if need <= 0:
+        raise NotImplementedError(f"attention_tile_plan: B={b} H={heads} Lq={lq} Lk={lk} head_dim={dh} is not supported "
+                                  f"(head_dim 64 | 128, at most 65536 keys)")
+    if workspace is None:
+        key = (q.device.index, torch.cuda.current_stream().cuda_stream)
+        workspace = _plan_ws.get(key)
+        if workspace is None or workspace.numel() * 4 < need:
+            workspace = _plan_ws[key] = torch.empty(need // 4, dtype=torch.float32, device=q.device)
+    assert workspace.dtype == torch.float32 and workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * 4 >= need
+    scale = dh ** -0.5 if scale is None else scale
+    ev = _timed("attn_tile_plan")
+    _lib.check(_lib.lib().fino_attn_tile_plan(_p(q), _p(k), b, heads, lq, lk, dh, q.stride(0), q.stride(1), dh,
+                                             k.stride(0), k.stride(1), dh, float(scale), _dt(q), float(cdf),
+                                             _p(keep_ranges), _p(out), out.shape[3], _p(workspace), workspace.numel() * 4,
+                                             _stream()), "fino_attn_tile_plan")
+    if ev is not None:
+        ev.record()
+    return out
+
+
+def attention_tiles(q, k, v, heads, mask, out=None, scale=None):
+    """attention() over a subset of the key tiles, chosen per (batch element, head, 256-row q-block): `mask` is an int32 / uint32
+    DEVICE tensor [B | 1, heads | 1, ceil(Lq / 256), words], bit t & 31 of word t >> 5 of a row stands for the 64-key tile t; a
+    size-1 dimension shares its rows (fino_attn_fwd_tiles; attention_tile_plan predicts such a mask).  Bits at or beyond
+    ceil(Lk / 64) are ignored; an empty row gives zeros."""
+    b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
+    words, mask_bs, mask_hs = _check_tile_mask(mask, b, heads, lq, lk)
+    ev = _timed("attn_self")
+    _lib.check(_lib.lib().fino_attn_fwd_tiles(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh,
+                                             q.stride(0), q.stride(1), dh, k.stride(0), k.stride(1), dh,
+                                             v.stride(0), v.stride(1), dh, out.stride(0), out.stride(1), dh,
+                                             float(scale), _dt(q), _p(mask), mask_bs, mask_hs, words, _stream()),
+               "fino_attn_fwd_tiles")
+    if ev is not None:
+        # FLOPs from the tiles walked: the mask's host copy is read only here, under the timer (one sync per launch)
+        ev.record()
+        kt_ = KernelTimer.active
+        bits = _tile_mask_bits(mask, lk).expand(b, heads, -1, -1).to(torch.float64)
+        keys = torch.full((bits.shape[-1],), 64.0, dtype=torch.float64)
+        keys[-1] = lk - 64 * (bits.shape[-1] - 1)
+        rows = torch.tensor([min(256, lq - 256 * i) for i in range(bits.shape[2])], dtype=torch.float64)
+        pairs = float(((bits * keys).sum(-1) * rows).sum())
+        kt_.flops["attn_self"] = kt_.flops.get("attn_self", 0.0) + 4.0 * pairs * dh
+        kt_.bytes["attn_self"] = kt_.bytes.get("attn_self", 0.0) + 2.0 * b * hd * (2 * lq + 2 * lk)
+    return out
+
+
 def attention_tail_supported(b, heads, lq, lk, dh):
     return bool(_lib.lib().fino_attn_tail_supported(int(b), int(heads), int(lq), int(lk), int(dh)))
 

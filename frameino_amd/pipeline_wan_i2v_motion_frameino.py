@@ -191,6 +191,8 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         the loop must run eagerly: with a timestep range the host decides per step whether the windows apply."""
         if getattr(self.transformer, "is_window_attention_enabled", False) and getattr(self, "parallel", None) is not None:
             raise NotImplementedError("window attention runs on one GPU; this pipeline has a parallel plan")
+        if getattr(self.transformer, "is_sparse_attention_enabled", False) and getattr(self, "parallel", None) is not None:
+            raise NotImplementedError("sparse attention runs on one GPU; this pipeline has a parallel plan")
         return window_attention_runs_eagerly(self.transformer, self.use_hip_graph)
 
     def to(self, device):
@@ -358,7 +360,8 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         rows = (st.t_rows, st.sel)
 
         live = {"live_rows": st.live_rows} if getattr(st, "live_rows", None) is not None else {}
-        if getattr(tr, "is_window_attention_enabled", False):      # (this package's transformer only, like live_rows)
+        if getattr(tr, "is_window_attention_enabled", False) or getattr(tr, "is_sparse_attention_enabled", False):
+            # (this package's transformer only, like live_rows)
             live["id_frames"] = st.id_frames
 
         cached = bool(getattr(tr, "is_cache_enabled", False))
@@ -473,7 +476,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         first_dead = bool((first_frame_mask[0, 0, 0] == 0).all()) if fg > 1 else False
         lo_live, hi_live = (tok_per_frame if first_dead else 0), fg * tok_per_frame
         st.live_rows = (lo_live, hi_live) if (hi_live - lo_live) < (fg + nid) * tok_per_frame else None
-        st.id_frames = nid               # window attention: the identity-reference frames are sinks
+        st.id_frames = nid               # window / sparse attention: the identity-reference frames are sinks
         st.t_rows = torch.zeros(2, dtype=torch.float32, device=dev)
         st.dt = torch.zeros(1, dtype=torch.float32, device=dev)
         # UniPC multistep history (last corrected sample, two x0 predictions) + this step's coefficient row

@@ -129,7 +129,12 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
 
     Window attention (enable_window_attention; frameino_amd/window_attention.py): first-block caching, MX
     linears and LoRA work with it; fp8 attention (the range walk exists in the bf16 / fp16 kernel only), Pyramid Attention
-    Broadcast, a token-sharded plan and user-installed attention processors are refused."""
+    Broadcast, a token-sharded plan and user-installed attention processors are refused.
+
+    Sparse attention (enable_sparse_attention): per head and q-block only the key tiles a device-side
+    predictor picks, plus the own frame, the sink frames and the ID frame.  First-block caching, MX linears, LoRA and the
+    hipGraph loop work with it; window attention, fp8 attention, Pyramid Attention Broadcast, a token-sharded plan and
+    user-installed attention processors are refused."""
     _window_table_cache = "_rope_cache"
     _loader_name = "load_wan_transformer"
     _keep_in_fp32_modules = ["time_embedder", "scale_shift_table", "norm1", "norm2", "norm3"]   # reference :393
@@ -293,6 +298,9 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
 
     def enable_cache(self, config):
         from .step_cache import _is_pab_config
+        if self._sparse is not None and _is_pab_config(config):
+            raise NotImplementedError("Pyramid Attention Broadcast with sparse attention (enable_sparse_attention): not "
+                                      "implemented in this version (first-block caching is)")
         if self._window is not None and _is_pab_config(config):
             raise NotImplementedError("Pyramid Attention Broadcast with window attention (enable_window_attention): not "
                                       "implemented in this version (first-block caching is)")
@@ -462,7 +470,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         pipeline's CFG-batched call passes ("cond", "uncond").  Without it a batch-B call under one `cache_context` makes one
         joint decision, as diffusers does (first-block caching: over the means of all its rows; Pyramid Attention Broadcast:
         one counter and one [B * L, D] buffer per layer and kind for the whole batch).
-        `id_frames` (window attention only, `enable_window_attention`): the trailing latent frames that are identity-reference
+        `id_frames` (window and sparse attention only, `enable_window_attention` / `enable_sparse_attention`): the trailing latent frames that are identity-reference
         frames -- every query sees them, like the configured sink frames."""
         gen = self.forward_steps(hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image,
                                  return_dict, attention_kwargs, timestep_rows, live_rows=live_rows,
@@ -569,6 +577,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         sh = sh if (sh is not None and sh.active) else None
         if self._window is not None:             # what window attention refuses, before anything is launched
             self._window_refusals(self.fp8_attention, default_procs, sh)
+        if self._sparse is not None:             # ... and what sparse attention refuses
+            self._sparse_refusals(self.fp8_attention, default_procs, sh)
         lo, n, lpad = 0, L, L
         tk = {}         # the shard's tile height for its GEMM calls (a per-call argument of the C ABI; {} = the library's planner)
         if sh is not None:
@@ -613,6 +623,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         fp8 = self.fp8_attention and sh is None and hasattr(o, "attention_fp8")     # this call's self-attention takes fp8 operands
         # sliding-window self-attention over frames: this forward's decision (the timestep callback is read here, once)
         win = self._window_begin(ppf, pph * ppw, 0, id_frames, dev)
+        # dynamic block-sparse self-attention: the always-kept tiles, the mask buffer and the plan workspace of this forward
+        sp = self._sparse_begin(ppf, pph * ppw, id_frames, dev, ws, b, heads, dh)
         # rows whose output the caller reads (`live_rows`): honoured in the last block on the single-GPU default-processor path
         live = None
         # (not under Pyramid Attention Broadcast: a cached branch output covers every row, so that any later step may use it)
@@ -629,7 +641,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                      text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
                      afold={"scale": o.SCALE_FOLDED} if fold else {}, fp8=fp8, default_procs=default_procs,
                      shared=shared, fbc=fbc, pab=pab, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
-                     live=live, win=win,
+                     live=live, win=win, sp=sp,
                      live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
                      rows=(0, n),            # the rows of every batch element that run as queries / per-token rows ...
                      segs=[(0, nr)])         # ... and the global row ranges the per-token operations of a block run on
@@ -692,7 +704,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._qk_norm_rope(blk, q1, d, c.cos1, c.sin1, c.dh, c.qfold)
         q3 = q1.view(1, n, 3 * d)
         self._attend(o, q3[:, :, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, fp8=c.fp8,
-                     ranges=self._window_ranges(c.win, li, (0, n)), out=a1.view(1, n, d), **c.afold)
+                     ranges=self._window_ranges(c.win, li, (0, n)), tiles=self._sparse_tiles(c.sp, li, (0, n)),
+                     out=a1.view(1, n, d), **c.afold)
         self._lin(li, "out", a1, to_out.weight, to_out.bias, o.EPI_GATED_RESIDUAL, residual=x[:n], gate=m[:, 2], sel=sel1,
                   out=x[:n])
         for bi in range(1, c.b):
@@ -709,7 +722,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         q3 = c.qkv.view(b, n, 3 * d)
         s0, s1 = c.rows                  # every row is a key; under `live_rows` only the live rows of the last block are queries
         self._attend(o, q3[:, s0:s1, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, fp8=c.fp8,
-                     ranges=self._window_ranges(c.win, li, (s0, s1)), out=c.att.view(b, n, d)[:, s0:s1], **c.afold)
+                     ranges=self._window_ranges(c.win, li, (s0, s1)), tiles=self._sparse_tiles(c.sp, li, (s0, s1)),
+                     out=c.att.view(b, n, d)[:, s0:s1], **c.afold)
         return False
 
     def _sa_heads_exchange(self, c, li, blk, e, m):
@@ -960,7 +974,7 @@ class _Call:
     __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
                  "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
                  "afold", "fp8", "default_procs", "shared", "fbc", "pab", "keep", "h0", "h1c", "attention_kwargs", "live",
-                 "live_segs", "rows", "segs", "win", "elements")
+                 "live_segs", "rows", "segs", "win", "sp", "elements")
 
     def __init__(self, **fields):
         self.elements = None

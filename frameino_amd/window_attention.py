@@ -17,7 +17,12 @@ exactly what the kernel computes.  The tables are pure Python + CPU torch: nothi
 
 `SelfAttentionOptionsMixin` is the host side both DiTs inherit: the fp8 and window switches with their state, the per-forward
 window decision and the one dispatch among the four `ops` self-attention front ends; `window_attention_runs_eagerly` is the rule
-both pipelines apply."""
+both pipelines apply.
+
+Dynamic block-sparse self-attention (opt-in, approximate) lives here too: `SparseAttentionConfig`, the
+mixin's `enable_sparse_attention` and the `tiles=` route of `_attend` -- a device-side predictor (`ops.attention_tile_plan`) picks
+the key tiles per (batch element, head, q-block) right before each call, `ops.attention_tiles` walks them; the window tables
+above are its always-kept tiles.  Wired on the Wan DiT only."""
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Any, Callable, Optional, Tuple
@@ -173,13 +178,76 @@ def window_attention_runs_eagerly(transformer, use_hip_graph):
     return True
 
 
+@dataclass
+class SparseAttentionConfig:
+    """`WanTransformer3DModel.enable_sparse_attention(config)`: dynamic block-sparse self-attention.
+
+    cdf_threshold: per (batch element, head, q-block) the kept key tiles carry at least this share of the softmax mass that
+    the pooled predictor sees (`ops.attention_tile_plan`); >= 1: dense.
+    window_frames, sink_frames: the tiles that are ALWAYS kept -- `frame_window_ranges(frames, tpf, window_frames, sinks)`, the
+    own latent frame(s) +- window_frames neighbours and the sink frames (negatives count from the end; `forward(id_frames=n)`
+    adds the trailing n).
+    skip_layers: blocks whose self-attention stays dense.
+    keep_masks: copy every layer's mask into `model.sparse_attention_masks[layer]` (tests, `sparse_attention_density()`)."""
+    cdf_threshold: float = 0.9
+    window_frames: int = 0
+    sink_frames: Tuple[int, ...] = (0,)
+    skip_layers: Tuple[int, ...] = ()
+    keep_masks: bool = False
+
+    def __post_init__(self):
+        t = self.cdf_threshold
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not (t > 0) or t == float("inf"):
+            raise ValueError(f"cdf_threshold = {t!r}: a number in (0, inf) is needed (>= 1: dense)")
+        self.cdf_threshold = float(t)
+        if isinstance(self.window_frames, bool) or not isinstance(self.window_frames, int) or self.window_frames < 0:
+            raise ValueError(f"window_frames = {self.window_frames!r}: a non-negative int is needed")
+        try:
+            self.sink_frames = tuple(int(s) for s in self.sink_frames)
+            self.skip_layers = tuple(int(s) for s in self.skip_layers)
+        except TypeError as e:
+            raise ValueError(f"sink_frames / skip_layers must be sequences of ints: {e}") from None
+        if any(s < 0 for s in self.skip_layers):
+            raise ValueError(f"skip_layers = {self.skip_layers}: block indices are >= 0")
+        self.keep_masks = bool(self.keep_masks)
+
+    def key(self):
+        """what a forced-tile table depends on"""
+        return (self.window_frames, self.sink_frames)
+
+
+def tile_mask_words(lk):
+    """uint32 words per q-block row of a tile mask over lk keys"""
+    return (-(-int(lk) // KEY_TILE) + 31) // 32
+
+
+def pack_tile_mask(keep):
+    """bool [..., ntall] -> int32 [..., ceil(ntall / 32)]: bit t & 31 of word t >> 5 is tile t (the layout of `ops.attention_tiles`)"""
+    keep = torch.as_tensor(keep, dtype=torch.bool)
+    nt = keep.shape[-1]
+    words = (nt + 31) // 32
+    pad = torch.zeros(keep.shape[:-1] + (words * 32,), dtype=torch.int64)
+    pad[..., :nt] = keep
+    w = (pad.view(keep.shape[:-1] + (words, 32)) << torch.arange(32, dtype=torch.int64)).sum(-1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def unpack_tile_mask(mask, lk):
+    """int32 / uint32 [..., words] -> bool [..., ceil(lk / 64)] (bits at or beyond the last tile dropped)"""
+    ntall = -(-int(lk) // KEY_TILE)
+    w = mask.detach().cpu().view(torch.int32).to(torch.int64) & 0xffffffff
+    bits = (w.unsqueeze(-1) >> torch.arange(32, dtype=torch.int64)) & 1
+    return bits.reshape(w.shape[:-1] + (-1,))[..., :ntall].bool()
+
+
 class SelfAttentionOptionsMixin:
     """The self-attention switches of a DiT -- fp8 operands (`enable_fp8_attention`) and the sliding window over frames
     (`enable_window_attention`) -- with their state, and `_attend`, the one place that picks among `ops.attention`,
     `ops.attention_ranges`, `ops.attention_fp8` and `ops.attention_fp8_ranges`.  The model calls `_init_self_attention_options()`
     from its constructor, names the dict that holds its positional tables in `_window_table_cache` (the range tables are dropped
     with them), says in `_window_refusals(fp8, default_procs, shard=None)` what it does not combine with the windows, calls
-    `_window_begin` once per forward and keeps its kernel front end in `self.ops`."""
+    `_window_begin` once per forward and keeps its kernel front end in `self.ops`.  The sparse attention
+    (`enable_sparse_attention`, `_sparse_begin` once per forward, `_attend(tiles=)`) is a fifth route beside the four."""
     _window_table_cache = None    # name of the model's dict of positional tables: `_window_begin` caches the range tables there
     _fp8_window_walk = False      # whether the model has an fp8 range walk at all; without one fp8 is refused while windows are on
 
@@ -191,6 +259,9 @@ class SelfAttentionOptionsMixin:
         self._window = None               # WindowAttentionConfig or None: see enable_window_attention
         self._window_forwards = 0
         self.window_attention_log = []    # (forward index, timestep or None, windowed) since enable_window_attention
+        self._sparse = None               # SparseAttentionConfig or None: see enable_sparse_attention
+        self.sparse_attention_masks = {}  # layer -> that layer's last tile mask (device), with `keep_masks`
+        self._sparse_mask_keys = {}       # layer -> the key count of that mask
 
     def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False, smooth_v=False):
         """The self-attention with fp8 (e4m3) matrix operands -- q, k, v and P on the block-scaled fp8 MFMA, softmax and
@@ -203,6 +274,8 @@ class SelfAttentionOptionsMixin:
         to the normalised output in fp32 (fino_attn_fwd_fp8_smoothed): exact, the softmax weights sum to one, and an offset that
         all keys of a channel share (attn1.to_v.bias, a DC component of the modulated input: V has no norm and no RoPE) stops
         taking the mantissa bits.  Off by default."""
+        if enabled and self._sparse is not None:
+            self._sparse_refusals(True, self._default_processors(), getattr(self, "parallel", None))
         if enabled and self._window is not None and not self._fp8_window_walk:
             # (such a model's hook refuses fp8 whatever else holds; one with an fp8 walk decides per head_dim, in its forward)
             self._window_refusals(True, self._default_processors(), getattr(self, "parallel", None))
@@ -225,6 +298,10 @@ class SelfAttentionOptionsMixin:
             raise TypeError(f"enable_window_attention takes a WindowAttentionConfig, got {type(config)}")
         if any(li >= self.config.num_layers for li in config.skip_layers):
             raise ValueError(f"skip_layers = {config.skip_layers}: this model has {self.config.num_layers} blocks")
+        if self._sparse is not None:
+            raise NotImplementedError("window attention (enable_window_attention) with sparse attention "
+                                      "(enable_sparse_attention): switch one of them off first; the sparse attention's "
+                                      "`window_frames` keeps a window of frames always")
         self._window_refusals(self.fp8_attention, self._default_processors(), getattr(self, "parallel", None))
         self._window = config
         self._window_forwards = 0
@@ -284,9 +361,118 @@ class SelfAttentionOptionsMixin:
         """the range table of block li's self-attention over the query rows `q_rows`, or None (dense)"""
         return None if win is None or li in win.skip else win.table(q_rows)
 
-    def _attend(self, ops, q, k, v, heads, *, fp8, ranges=None, **kw):
+    # ------------------------------------------------------------------ dynamic block-sparse attention (DESIGN.md section 6j)
+    def _sparse_refusals(self, fp8, default_procs, shard=None):
+        what = "sparse attention (enable_sparse_attention)"
+        if self._window is not None:
+            raise NotImplementedError(f"{what} with window attention (enable_window_attention): switch one of them off first; "
+                                      f"`SparseAttentionConfig.window_frames` keeps a window of frames always")
+        if fp8:
+            raise NotImplementedError(f"{what} with fp8 attention: the tile walk exists in the bf16 / fp16 kernel only; switch "
+                                      f"one of them off first (disable_sparse_attention() / enable_fp8_attention(False))")
+        if getattr(self, "_pab_on", False):
+            raise NotImplementedError(f"{what} with Pyramid Attention Broadcast: not implemented in this version (first-block "
+                                      f"caching is)")
+        if shard is not None and getattr(shard, "active", True):
+            raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
+        if not default_procs:
+            raise NotImplementedError(f"{what} with a user-installed attention processor: the tile masks are applied by the "
+                                      f"built-in attention path only")
+
+    def enable_sparse_attention(self, config):
+        """Opt-in, approximate: in every block not in `config.skip_layers` each (batch element, head, 256-row q-block) attends
+        only the 64-key tiles that a device-side predictor picks right before the call, from that call's q and k
+        (`ops.attention_tile_plan`: mean-pooled q-blocks and key tiles, the smallest set of tiles by descending predicted
+        softmax mass that reaches `config.cdf_threshold`), plus the always-kept tiles of `frame_window_ranges(frames, tpf,
+        config.window_frames, sinks)` -- `ops.attention_tiles` over the mask.  `cdf_threshold >= 1`, or forced tiles that cover
+        everything, take the dense call, bit for bit.  No timestep gate and no host read: the step captures as it is.  What does
+        not combine with it (window attention, fp8 attention, Pyramid Attention Broadcast, a token-sharded plan, a
+        user-installed processor) is refused here where it can be seen, else by the forward before anything is launched.  No
+        reference counterpart; quality on real checkpoints is unmeasured."""
+        if not isinstance(config, SparseAttentionConfig):
+            raise TypeError(f"enable_sparse_attention takes a SparseAttentionConfig, got {type(config)}")
+        if any(li >= self.config.num_layers for li in config.skip_layers):
+            raise ValueError(f"skip_layers = {config.skip_layers}: this model has {self.config.num_layers} blocks")
+        self._sparse_refusals(self.fp8_attention, self._default_processors(), getattr(self, "parallel", None))
+        self._sparse = config
+        self.sparse_attention_masks, self._sparse_mask_keys = {}, {}
+        return self
+
+    def disable_sparse_attention(self):
+        self._sparse = None
+        self.sparse_attention_masks, self._sparse_mask_keys = {}, {}
+        return self
+
+    @property
+    def is_sparse_attention_enabled(self):
+        return self._sparse is not None
+
+    def sparse_attention_density(self):
+        """layer -> fraction of the (batch element, head, q-block, key tile) entries the last forward kept (needs `keep_masks`;
+        a host read)"""
+        return {li: float(unpack_tile_mask(m, self._sparse_mask_keys[li]).float().mean())
+                for li, m in sorted(self.sparse_attention_masks.items())}
+
+    def _sparse_begin(self, frames, tokens_per_frame, id_frames, dev, ws, batch, heads, head_dim):
+        """This forward's sparse state, decided before anything is launched: None (off, or `cdf_threshold >= 1`: dense), else
+        `.keep(q_rows)` -> the device table of the always-kept tiles of those query rows, or None when it covers every key tile
+        (the dense call); `.skip`; and the mask buffer and plan workspace, kept on the model workspace `ws` (allocated once per
+        workspace: a captured step replays them)."""
+        cfg = self._sparse
+        if cfg is None or cfg.cdf_threshold >= 1.0:
+            return None
+        id_frames = int(id_frames or 0)
+        if not 0 <= id_frames < frames:
+            raise ValueError(f"id_frames = {id_frames} of {frames} latent frames")
+        sinks = tuple(cfg.sink_frames) + tuple(range(frames - id_frames, frames))
+        L = frames * tokens_per_frame
+        cache = getattr(self, self._window_table_cache)
+
+        def keep(q_rows):
+            key = ("sparse", frames, tokens_per_frame, cfg.key(), id_frames, tuple(q_rows), str(dev))
+            if key not in cache:
+                tab = frame_window_ranges(frames, tokens_per_frame, cfg.window_frames, sinks, q_rows)
+                cache[key] = None if ranges_cover_all(tab, L) else tab.to(dev)
+            return cache[key]
+
+        words, nqb = tile_mask_words(L), -(-L // Q_BLOCK)
+        need_mask = batch * heads * nqb * words
+        need_plan = self.ops.attention_tile_plan_bytes(batch, heads, L, L, head_dim) // 4
+        if getattr(ws, "sparse_mask", None) is None or ws.sparse_mask.numel() < need_mask:
+            ws.sparse_mask = torch.zeros(need_mask, dtype=torch.int32, device=dev)
+        if getattr(ws, "sparse_plan", None) is None or ws.sparse_plan.numel() < need_plan:
+            ws.sparse_plan = torch.empty(need_plan, dtype=torch.float32, device=dev)
+        return SimpleNamespace(keep=keep, skip=frozenset(cfg.skip_layers), cdf=cfg.cdf_threshold, words=words, lk=L,
+                               mask=ws.sparse_mask, workspace=ws.sparse_plan, keep_masks=cfg.keep_masks)
+
+    @staticmethod
+    def _sparse_tiles(sp, li, q_rows):
+        """what `_attend(tiles=)` takes for block li's self-attention over the query rows `q_rows`, or None (dense)"""
+        if sp is None or li in sp.skip:
+            return None
+        table = sp.keep(q_rows)
+        return None if table is None else SimpleNamespace(sp=sp, layer=li, keep=table)
+
+    def _attend_tiles(self, ops, q, k, v, heads, tiles, **kw):
+        """the plan on this call's q and k, then the tile walk over its mask"""
+        sp = tiles.sp
+        b, nqb = q.shape[0], -(-q.shape[1] // Q_BLOCK)
+        mask = sp.mask[:b * heads * nqb * sp.words].view(b, heads, nqb, sp.words)
+        ops.attention_tile_plan(q, k, heads, sp.cdf, keep_ranges=tiles.keep, scale=kw.get("scale"), out=mask,
+                                workspace=sp.workspace)
+        if sp.keep_masks:
+            old = self.sparse_attention_masks.get(tiles.layer)
+            if old is None or old.shape != mask.shape:
+                old = self.sparse_attention_masks[tiles.layer] = torch.empty_like(mask)
+            old.copy_(mask)
+            self._sparse_mask_keys[tiles.layer] = k.shape[1]
+        return ops.attention_tiles(q, k, v, heads, mask, **kw)
+
+    def _attend(self, ops, q, k, v, heads, *, fp8, ranges=None, tiles=None, **kw):
         """one self-attention call: dense or over `ranges`, bf16 / fp16 or -- `fp8` -- with the model's fp8 options; `kw`: out=,
-        scale="""
+        scale=.  `tiles` (`_sparse_tiles`): the dynamic tile walk instead, bf16 / fp16 only."""
+        if tiles is not None:
+            return self._attend_tiles(ops, q, k, v, heads, tiles, **kw)
         if fp8:
             kw.update(p_mode=self.fp8_p_mode, smooth_k=self.fp8_smooth_k, smooth_v=self.fp8_smooth_v)
         if ranges is None:

@@ -242,6 +242,37 @@ int fino_attn_fwd_ranges(const void* q, const void* k, const void* v, void* o, i
                          int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs, int64_t k_rs, int64_t k_hs,
                          int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs, int64_t o_rs, int64_t o_hs, float scale,
                          int dtype, const int* ranges, void* stream);
+/* fino_attn_fwd over a SUBSET of the key tiles, chosen per (batch element, head, 256-row q-block) by a bitmask: the dynamic
+ * block-sparse self-attention (fino_attn_tile_plan predicts the mask from pooled q and k; any other producer will do).  `mask` is
+ * a DEVICE array of uint32; the row of (b, h, q-block qb) starts at mask + b * mask_bs + h * mask_hs + qb * words (strides in
+ * words; mask_bs = 0 and / or mask_hs = 0 shares the rows across batch elements and / or heads); bit t & 31 of word t >> 5 stands
+ * for key tile t (64 keys); words >= ceil(ceil(lk / 64) / 32); bits at or beyond ceil(lk / 64) are ignored, so a bad mask gives a
+ * wrong answer, never a read outside k / v.  A q-block that walks the tiles T computes, in the same order and to the same bits,
+ * what fino_attn_fwd's LDS-DMA kernel computes over the keys of T gathered into one sequence; a q-block whose row is empty stores
+ * zeros.  Everything else -- arguments, strides, scale, the checks -- as fino_attn_fwd.  Always the LDS-DMA ping-pong kernel, whole
+ * blocks (no tail split, no workspace), head_dim 64 | 128, at most 1024 key tiles (65 536 keys: fino_attn_tiles_supported(),
+ * FINO_ERR_UNSUPPORTED otherwise); the mask is read by the launch, so it must stay alive until the stream has passed it.  No
+ * reference counterpart, like fino_attn_fwd_ranges. */
+int fino_attn_tiles_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim);
+int fino_attn_fwd_tiles(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq, int64_t lk,
+                        int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs, int64_t k_rs, int64_t k_hs,
+                        int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs, int64_t o_rs, int64_t o_hs, float scale,
+                        int dtype, const uint32_t* mask, int64_t mask_bs, int64_t mask_hs, int words, void* stream);
+/* The mask of fino_attn_fwd_tiles from q and k as the attention call receives them (after norm and RoPE), on the device, in two
+ * launches, without a host read.  Pool: the fp32 mean of q over each 256-row q-block and of k over the real keys of each 64-key
+ * tile, into `workspace` (fp32, fino_attn_tile_plan_bytes(), 16-byte aligned).  Select, per (b, h, q-block i): s_t = scale
+ * <qbar_i, kbar_t> (FINO_ATTN_SCALE_FOLDED: the logits are in log2 units already), w_t = n_t exp(s_t - max s) with n_t the real
+ * keys of tile t, p_t = w_t / sum w.  F = row i of `keep_ranges`, a DEVICE table in the format of fino_attn_fwd_ranges, clipped
+ * the same way (NULL: empty); m_F = sum_{t in F} p_t.  m_F >= cdf keeps F; otherwise F and every t outside F with p_t >= theta,
+ * theta the largest p with m_F + sum_{t not in F, p_t >= theta} p_t >= cdf (none qualifies: every tile).  Ties at theta are all
+ * kept.  `mask` receives uint32 [batch][heads][ceil(lq / 256)][words], every word written.  Deterministic: no atomics, fixed
+ * summation order -- the same inputs give the same mask, bit for bit.  cdf > 0; head_dim 64 | 128, bf16 | fp16, shapes as
+ * fino_attn_tiles_supported(). */
+int64_t fino_attn_tile_plan_bytes(int batch, int heads, int64_t lq, int64_t lk, int head_dim);
+int fino_attn_tile_plan(const void* q, const void* k, int batch, int heads, int64_t lq, int64_t lk, int head_dim, int64_t q_bs,
+                        int64_t q_rs, int64_t q_hs, int64_t k_bs, int64_t k_rs, int64_t k_hs, float scale, int dtype, float cdf,
+                        const int* keep_ranges, uint32_t* mask, int words, void* workspace, int64_t workspace_bytes,
+                        void* stream);
 /* fino_attn_fwd_fp8 (smooth_k = 0) or fino_attn_fwd_fp8_smooth (smooth_k != 0) over the SUBSET of key tiles fino_attn_fwd_ranges
  * walks: the same DEVICE table, int32 [ceil(lq / 256)][3][2] per 256 query rows (the kernel's workgroups hold 128 rows: two of them
  * share a table row), clipped to [0, ceil(lk / 64)] by the kernel -- a bad table gives a wrong answer, never a read outside the
