@@ -74,6 +74,18 @@ def main():
                          "or --fp8-attention")
     ap.add_argument("--sparse-window-frames", type=int, default=0, metavar="N",
                     help="with --sparse-attention: the own frame +- N neighbours are always kept (default 0)")
+    ap.add_argument("--sparse-similarity", type=float, default=None, metavar="THETA",
+                    help="with --sparse-attention: never predict from a block whose tokens do not resemble each other (mean "
+                         "pairwise cosine below THETA, e.g. 0.3): such a q-block attends everything, such a key tile is always kept")
+    ap.add_argument("--sparse-calibrate", default=None, metavar="OUT.json",
+                    help="with --sparse-attention: before the clip, run a short dense clip that measures, per layer and head, the "
+                         "smallest threshold of a grid whose sparse output stays within --sparse-l1 of the dense one; write the "
+                         "thresholds to OUT.json and use them")
+    ap.add_argument("--sparse-l1", type=float, default=0.05, metavar="X",
+                    help="with --sparse-calibrate: the relative L1 error bound per layer and head (default 0.05)")
+    ap.add_argument("--sparse-thresholds", default=None, metavar="FILE",
+                    help="sparse attention with the configuration and per-head thresholds of FILE (written by --sparse-calibrate); "
+                         "instead of --sparse-attention")
     ap.add_argument("--fp8-attention", action="store_true",
                     help="fp8 (e4m3) operands in the 3-D self-attention (reduced precision, opt-in).  Not together with --window-frames")
     ap.add_argument("--smooth-k", action="store_true",
@@ -162,10 +174,20 @@ def main():
     if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)
         from frameino_amd.window_attention import WindowAttentionConfig
         transformer.enable_window_attention(WindowAttentionConfig(window_frames=a.window_frames, sink_frames=(0,)))
-    if a.sparse_attention is not None:             # forced tiles: own frame +- N, the first frame, the ID frame (id_frames)
+    sparse_cfg = None
+    if a.sparse_thresholds is not None:
+        if a.sparse_attention is not None or a.sparse_calibrate is not None:
+            ap.error("--sparse-thresholds FILE carries its own configuration: not together with --sparse-attention / --sparse-calibrate")
+        from frameino_amd.sparse_calibration import load_sparse_thresholds
+        sparse_cfg = load_sparse_thresholds(a.sparse_thresholds)
+    elif a.sparse_attention is not None:           # forced tiles: own frame +- N, the first frame, the ID frame (id_frames)
         from frameino_amd.window_attention import SparseAttentionConfig
-        transformer.enable_sparse_attention(SparseAttentionConfig(cdf_threshold=a.sparse_attention,
-                                                                  window_frames=a.sparse_window_frames, sink_frames=(0,)))
+        sparse_cfg = SparseAttentionConfig(cdf_threshold=a.sparse_attention, window_frames=a.sparse_window_frames,
+                                           sink_frames=(0,), similarity_threshold=a.sparse_similarity)
+    elif a.sparse_similarity is not None or a.sparse_calibrate is not None:
+        ap.error("--sparse-similarity / --sparse-calibrate need --sparse-attention TAU")
+    if sparse_cfg is not None and a.sparse_calibrate is None:
+        transformer.enable_sparse_attention(sparse_cfg)
     t0 = time.perf_counter()
     canvas, tracks, id_tensor, pads = synthetic_conditions(a.frames, a.height, a.width, dev)
     traj = prepare_traj_tensor(tracks, a.height, a.width, 6, a.width, a.height, device=dev)        # [F, 3, H, W]
@@ -179,6 +201,19 @@ def main():
         kw = dict(prompt=a.prompt, negative_prompt="")
     if a.lora:
         kw["attention_kwargs"] = {"scale": a.lora_scale}
+    if a.sparse_calibrate is not None:             # a short dense clip that measures the thresholds on this model's own weights
+        from frameino_amd.sparse_calibration import calibrate_sparse_attention, save_sparse_thresholds
+        sparse_cfg, report = calibrate_sparse_attention(
+            transformer, lambda: pipe(image=canvas, traj_tensor=traj, ID_tensor=id_tensor, height=a.height, width=a.width,
+                                      num_frames=a.frames, num_inference_steps=min(a.steps, 4), guidance_scale=a.guidance,
+                                      generator=torch.Generator().manual_seed(1234), **kw),
+            l1_bound=a.sparse_l1, base=sparse_cfg)
+        save_sparse_thresholds(a.sparse_calibrate, sparse_cfg)
+        flat = [t for row in sparse_cfg.head_thresholds.values() for t in row]
+        print(f"sparse calibration: {len(flat)} (layer, head) thresholds within L1 {a.sparse_l1} -> {a.sparse_calibrate}; "
+              f"{sum(t >= 1.0 for t in flat)} stay dense, mean threshold of the others "
+              f"{sum(t for t in flat if t < 1.0) / max(1, sum(t < 1.0 for t in flat)):.3f}")
+        transformer.enable_sparse_attention(sparse_cfg)
     torch.cuda.synchronize()
     tc = time.perf_counter()
     for rep in range(a.repeat):

@@ -54,6 +54,9 @@ SIGNATURES = {
     "fino_attn_tile_plan_bytes": [c_int, c_int, c_i64, c_i64, c_int],
     "fino_attn_tile_plan": [c_void_p] * 2 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 6 + [c_float, c_int, c_float, c_void_p,
                                                                                              c_void_p, c_int, c_void_p, c_i64, c_void_p],
+    "fino_attn_tile_plan_gated_bytes": [c_int, c_int, c_i64, c_i64, c_int],
+    "fino_attn_tile_plan_gated": [c_void_p] * 2 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 6 +
+                                 [c_float, c_int, c_float, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p],
     "fino_attn_fp8_ranges_supported": [c_int, c_int, c_i64, c_i64, c_int],
     "fino_attn_fwd_fp8_ranges": [c_void_p] * 4 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 8 + [c_float, c_int, c_int, c_void_p,
                                                                                                c_i64, c_int, c_void_p, c_void_p],
@@ -145,7 +148,8 @@ _RESTYPES = {"fino_last_error": ctypes.c_char_p, "fino_attn_workspace_bytes": c_
              "fino_groupnorm_workspace_bytes": c_i64,
              "fino_attn_partial_bytes": c_i64, "fino_attn_fp8_kv_bytes": c_i64, "fino_attn_fp8_smooth_kv_bytes": c_i64,
              "fino_attn_fp8_smoothed_kv_bytes": c_i64, "fino_mxfp6_bytes": c_i64,
-             "fino_mxfp6_scale_bytes": c_i64, "fino_attn_tile_plan_bytes": c_i64}
+             "fino_mxfp6_scale_bytes": c_i64, "fino_attn_tile_plan_bytes": c_i64,
+             "fino_attn_tile_plan_gated_bytes": c_i64}
 
 
 # the FINO_VERSION this table (argument lists, tune-knob meanings) was written for: a stale library found through

@@ -381,13 +381,25 @@ def attention_tile_plan_bytes(b, heads, lq, lk, dh):
 _plan_ws = {}      # (device index, stream) -> fp32 workspace of attention_tile_plan (pooled q and k; grown on demand)
 
 
-def attention_tile_plan(q, k, heads, cdf, keep_ranges=None, scale=None, out=None, workspace=None):
+def attention_tile_plan_gated_bytes(b, heads, lq, lk, dh):
+    """bytes of the fp32 workspace attention_tile_plan needs with `similarity_threshold`: the pooled means, then sim_q
+    [b, heads, nqb] and sim_k [b, heads, ntall] (0: shape not supported)"""
+    return int(_lib.lib().fino_attn_tile_plan_gated_bytes(int(b), int(heads), int(lq), int(lk), int(dh)))
+
+
+def attention_tile_plan(q, k, heads, cdf, keep_ranges=None, scale=None, out=None, workspace=None, cdf_heads=None,
+                        similarity_threshold=None, return_similarity=False):
     """The tile mask of attention_tiles, predicted on the device from q [B, Lq, H*Dh] and k [B, Lk, H*Dh] as the attention call
     gets them (fino_attn_tile_plan: mean-pooled q-blocks and key tiles, a softmax over the tiles, the smallest set of tiles by
     descending mass that reaches `cdf` together with the always-kept tiles of `keep_ranges`, an int32 device table
     [ceil(Lq / 256), 3, 2] in the format of attention_ranges, or None) -> int32 device tensor [B, heads, nqb, words].  `scale`
     as attention(): SCALE_FOLDED when q carries it.  `out` / `workspace` (fp32, >= fino_attn_tile_plan_bytes): caller-owned
-    buffers, for a step that is captured.  No host read; deterministic."""
+    buffers, for a step that is captured.  No host read; deterministic.
+    `cdf_heads` (fp32 device tensor [heads]): head h uses cdf_heads[h] instead of `cdf`, >= 1 keeps every tile of that head.
+    `similarity_threshold` (theta in (0, 1]): q-blocks whose rows do not resemble each other (mean pairwise cosine < theta) keep
+    every tile, such key tiles are always kept and take no part in the prediction (fino_attn_tile_plan_gated; the workspace is
+    then >= fino_attn_tile_plan_gated_bytes).  With both None the ungated entry is called, as ever.  `return_similarity` (needs
+    the threshold): -> (mask, (sim_q [B, heads, nqb], sim_k [B, heads, ntall])), copies of the workspace's tail."""
     assert q.dim() == 3 and k.dim() == 3 and q.shape[0] == k.shape[0] and q.shape[2] == k.shape[2]
     for t in (q, k):
         assert t.stride(2) == 1 and t.is_cuda
@@ -397,12 +409,23 @@ def attention_tile_plan(q, k, heads, cdf, keep_ranges=None, scale=None, out=None
     nqb, words = (lq + 255) // 256, ((lk + 63) // 64 + 31) // 32
     if keep_ranges is not None:
         _check_ranges(keep_ranges, lq)
+    if cdf_heads is not None:
+        assert isinstance(cdf_heads, torch.Tensor) and cdf_heads.dtype == torch.float32 and cdf_heads.is_cuda and \
+            cdf_heads.is_contiguous() and tuple(cdf_heads.shape) == (heads,), \
+            f"cdf_heads: a contiguous fp32 device tensor [{heads}] is needed, got {getattr(cdf_heads, 'dtype', type(cdf_heads))} " \
+            f"{tuple(getattr(cdf_heads, 'shape', ()))}"
+    gate = similarity_threshold is not None
+    if gate:
+        theta = float(similarity_threshold)
+        assert 0.0 < theta <= 1.0, f"similarity_threshold = {similarity_threshold!r}: a number in (0, 1] is needed"
+    assert gate or not return_similarity, "return_similarity needs similarity_threshold: the similarities are computed under the gate only"
     if out is None:
         out = torch.empty((b, heads, nqb, words), dtype=torch.int32, device=q.device)
     assert out.dtype in _MASK_DTYPES and out.is_cuda and out.is_contiguous() and \
         tuple(out.shape[:3]) == (b, heads, nqb) and out.dim() == 4 and out.shape[3] * 32 >= (lk + 63) // 64, \
         f"out: a contiguous int32 device tensor [{b}, {heads}, {nqb}, >= {words}] is needed, got {out.dtype} {tuple(out.shape)}"
-    need = _lib.lib().fino_attn_tile_plan_bytes(b, heads, lq, lk, dh)
+    plain = _lib.lib().fino_attn_tile_plan_bytes(b, heads, lq, lk, dh)
+    need = _lib.lib().fino_attn_tile_plan_gated_bytes(b, heads, lq, lk, dh) if gate else plain
     if need <= 0:
         raise NotImplementedError(f"attention_tile_plan: B={b} H={heads} Lq={lq} Lk={lk} head_dim={dh} is not supported "
                                   f"(head_dim 64 | 128, at most 65536 keys)")
@@ -414,12 +437,23 @@ def attention_tile_plan(q, k, heads, cdf, keep_ranges=None, scale=None, out=None
     assert workspace.dtype == torch.float32 and workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * 4 >= need
     scale = dh ** -0.5 if scale is None else scale
     ev = _timed("attn_tile_plan")
-    _lib.check(_lib.lib().fino_attn_tile_plan(_p(q), _p(k), b, heads, lq, lk, dh, q.stride(0), q.stride(1), dh,
-                                             k.stride(0), k.stride(1), dh, float(scale), _dt(q), float(cdf),
-                                             _p(keep_ranges), _p(out), out.shape[3], _p(workspace), workspace.numel() * 4,
-                                             _stream()), "fino_attn_tile_plan")
+    if cdf_heads is None and not gate:
+        _lib.check(_lib.lib().fino_attn_tile_plan(_p(q), _p(k), b, heads, lq, lk, dh, q.stride(0), q.stride(1), dh,
+                                                 k.stride(0), k.stride(1), dh, float(scale), _dt(q), float(cdf),
+                                                 _p(keep_ranges), _p(out), out.shape[3], _p(workspace), workspace.numel() * 4,
+                                                 _stream()), "fino_attn_tile_plan")
+    else:
+        _lib.check(_lib.lib().fino_attn_tile_plan_gated(_p(q), _p(k), b, heads, lq, lk, dh, q.stride(0), q.stride(1), dh,
+                                                       k.stride(0), k.stride(1), dh, float(scale), _dt(q), float(cdf),
+                                                       _p(cdf_heads), theta if gate else 0.0, _p(keep_ranges), _p(out),
+                                                       out.shape[3], _p(workspace), workspace.numel() * 4, _stream()),
+                   "fino_attn_tile_plan_gated")
     if ev is not None:
         ev.record()
+    if return_similarity:
+        nt = (lk + 63) // 64
+        tail = workspace[plain // 4:plain // 4 + b * heads * (nqb + nt)]
+        return out, (tail[:b * heads * nqb].view(b, heads, nqb).clone(), tail[b * heads * nqb:].view(b, heads, nt).clone())
     return out
 
 

@@ -22,10 +22,12 @@ both pipelines apply.
 Dynamic block-sparse self-attention (opt-in, approximate) lives here too: `SparseAttentionConfig`, the
 mixin's `enable_sparse_attention` and the `tiles=` route of `_attend` -- a device-side predictor (`ops.attention_tile_plan`) picks
 the key tiles per (batch element, head, q-block) right before each call, `ops.attention_tiles` walks them; the window tables
-above are its always-kept tiles.  Wired on the Wan DiT only."""
+above are its always-kept tiles.  Wired on the Wan DiT only.  Its two safeguards are fields of the same
+config: `similarity_threshold` (blocks whose tokens do not resemble each other are never predicted from) and `head_thresholds`
+(one cdf threshold per layer and head; frameino_amd/sparse_calibration.py measures them on the user's own weights)."""
 from dataclasses import dataclass
 from types import SimpleNamespace
-from typing import Any, Callable, Optional, Tuple
+from typing import Any, Callable, Mapping, Optional, Sequence, Tuple
 
 import torch
 
@@ -169,6 +171,13 @@ def window_attention_runs_eagerly(transformer, use_hip_graph):
     """The pipelines' rule, checked before any work.  -> whether the denoising loop must run eagerly: with a timestep range the
     host decides per step whether the windows apply.  Off, or without a range (the table is a static device tensor), the step
     captures as it is."""
+    if getattr(transformer, "is_sparse_calibrating", False):
+        # a calibration run (frameino_amd/sparse_calibration.py) accumulates per-call statistics on the host's schedule
+        if use_hip_graph is True:
+            raise RuntimeError("use_hip_graph=True while the sparse attention is being calibrated: every self-attention call "
+                               "runs the dense and the sparse kernels and adds to running sums, which one captured step "
+                               "replayed cannot contain (the loop runs eagerly; use_hip_graph=None or False)")
+        return True
     if not getattr(transformer, "window_attention_is_timestep_gated", False):
         return False
     if use_hip_graph is True:
@@ -188,12 +197,20 @@ class SparseAttentionConfig:
     own latent frame(s) +- window_frames neighbours and the sink frames (negatives count from the end; `forward(id_frames=n)`
     adds the trailing n).
     skip_layers: blocks whose self-attention stays dense.
-    keep_masks: copy every layer's mask into `model.sparse_attention_masks[layer]` (tests, `sparse_attention_density()`)."""
+    keep_masks: copy every layer's mask into `model.sparse_attention_masks[layer]` (tests, `sparse_attention_density()`).
+    similarity_threshold: theta in (0, 1], or None (off).  A mean-pooled block predicts its tokens only
+    when they resemble each other: a q-block whose mean pairwise cosine is below theta attends everything, such a key tile is
+    always kept and takes no part in the predicted softmax.
+    head_thresholds: layer -> one cdf threshold per head (each in (0, inf), >= 1: that head is dense), or None.  A layer that is
+    not named uses `cdf_threshold`; a layer whose heads are all >= 1 takes the dense call.
+    `frameino_amd.sparse_calibration.calibrate_sparse_attention` returns a config with this table filled."""
     cdf_threshold: float = 0.9
     window_frames: int = 0
     sink_frames: Tuple[int, ...] = (0,)
     skip_layers: Tuple[int, ...] = ()
     keep_masks: bool = False
+    similarity_threshold: Optional[float] = None
+    head_thresholds: Optional[Mapping[int, Sequence[float]]] = None
 
     def __post_init__(self):
         t = self.cdf_threshold
@@ -210,10 +227,43 @@ class SparseAttentionConfig:
         if any(s < 0 for s in self.skip_layers):
             raise ValueError(f"skip_layers = {self.skip_layers}: block indices are >= 0")
         self.keep_masks = bool(self.keep_masks)
+        th = self.similarity_threshold
+        if th is not None:
+            if isinstance(th, bool) or not isinstance(th, (int, float)) or not 0 < th <= 1:
+                raise ValueError(f"similarity_threshold = {th!r}: a number in (0, 1] is needed (None: off)")
+            self.similarity_threshold = float(th)
+        if self.head_thresholds is not None:
+            if not isinstance(self.head_thresholds, Mapping):
+                raise ValueError(f"head_thresholds = {self.head_thresholds!r}: a mapping layer -> thresholds per head is needed")
+            table = {}
+            for li, row in self.head_thresholds.items():
+                if isinstance(li, bool) or not isinstance(li, int) or li < 0:
+                    raise ValueError(f"head_thresholds: layer {li!r}: block indices are ints >= 0")
+                try:
+                    row = tuple(row)
+                except TypeError:
+                    raise ValueError(f"head_thresholds[{li}] = {row!r}: one threshold per head is needed") from None
+                for t in row:
+                    if isinstance(t, bool) or not isinstance(t, (int, float)) or not (t > 0) or t == float("inf"):
+                        raise ValueError(f"head_thresholds[{li}]: {t!r}: numbers in (0, inf) are needed (>= 1: dense)")
+                if not row:
+                    raise ValueError(f"head_thresholds[{li}] is empty: one threshold per head is needed")
+                table[li] = tuple(float(t) for t in row)
+            self.head_thresholds = table
 
     def key(self):
         """what a forced-tile table depends on"""
         return (self.window_frames, self.sink_frames)
+
+    def check_model(self, num_layers, num_heads):
+        """what can be checked only against a model: the layers exist, every `head_thresholds` row has one entry per head"""
+        if any(li >= num_layers for li in self.skip_layers):
+            raise ValueError(f"skip_layers = {self.skip_layers}: this model has {num_layers} blocks")
+        for li, row in (self.head_thresholds or {}).items():
+            if li >= num_layers:
+                raise ValueError(f"head_thresholds names layer {li}: this model has {num_layers} blocks")
+            if len(row) != num_heads:
+                raise ValueError(f"head_thresholds[{li}] has {len(row)} entries: this model has {num_heads} heads")
 
 
 def tile_mask_words(lk):
@@ -262,6 +312,8 @@ class SelfAttentionOptionsMixin:
         self._sparse = None               # SparseAttentionConfig or None: see enable_sparse_attention
         self.sparse_attention_masks = {}  # layer -> that layer's last tile mask (device), with `keep_masks`
         self._sparse_mask_keys = {}       # layer -> the key count of that mask
+        self._sparse_sims = {}            # layer -> (sim_q | sim_k of the last call (device), (b, heads, nqb, ntall)), gate + `keep_masks`
+        self._sparse_calib = None         # a running calibration (frameino_amd/sparse_calibration.py), else None
 
     def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False, smooth_v=False):
         """The self-attention with fp8 (e4m3) matrix operands -- q, k, v and P on the block-scaled fp8 MFMA, softmax and
@@ -388,20 +440,27 @@ class SelfAttentionOptionsMixin:
         everything, take the dense call, bit for bit.  No timestep gate and no host read: the step captures as it is.  What does
         not combine with it (window attention, fp8 attention, Pyramid Attention Broadcast, a token-sharded plan, a
         user-installed processor) is refused here where it can be seen, else by the forward before anything is launched.  No
-        reference counterpart; quality on real checkpoints is unmeasured."""
+        reference counterpart; quality on real checkpoints is unmeasured.
+        `config.similarity_threshold` and `config.head_thresholds` (both off by default): blocks whose tokens do
+        not resemble each other are never predicted from, and every (layer, head) gets its own threshold -- a head at >= 1 keeps
+        every tile, a layer whose heads are all >= 1 takes the dense call.  `head_thresholds` is checked against this model here."""
         if not isinstance(config, SparseAttentionConfig):
             raise TypeError(f"enable_sparse_attention takes a SparseAttentionConfig, got {type(config)}")
-        if any(li >= self.config.num_layers for li in config.skip_layers):
-            raise ValueError(f"skip_layers = {config.skip_layers}: this model has {self.config.num_layers} blocks")
+        config.check_model(self.config.num_layers, self.config.num_attention_heads)
         self._sparse_refusals(self.fp8_attention, self._default_processors(), getattr(self, "parallel", None))
         self._sparse = config
-        self.sparse_attention_masks, self._sparse_mask_keys = {}, {}
+        self.sparse_attention_masks, self._sparse_mask_keys, self._sparse_sims = {}, {}, {}
         return self
 
     def disable_sparse_attention(self):
         self._sparse = None
-        self.sparse_attention_masks, self._sparse_mask_keys = {}, {}
+        self.sparse_attention_masks, self._sparse_mask_keys, self._sparse_sims = {}, {}, {}
         return self
+
+    @property
+    def is_sparse_calibrating(self):
+        """inside `calibrate_sparse_attention`: every self-attention call runs dense and sparse and adds to running sums"""
+        return getattr(self, "_sparse_calib", None) is not None
 
     @property
     def is_sparse_attention_enabled(self):
@@ -413,13 +472,28 @@ class SelfAttentionOptionsMixin:
         return {li: float(unpack_tile_mask(m, self._sparse_mask_keys[li]).float().mean())
                 for li, m in sorted(self.sparse_attention_masks.items())}
 
+    def sparse_attention_similarity(self):
+        """layer -> (mean sim_q, mean sim_k, share of q-blocks under theta, share of key tiles under theta) of the last forward's
+        last call of that layer (needs `similarity_threshold` and `keep_masks`; a host read)"""
+        theta = getattr(self._sparse, "similarity_threshold", None) if self._sparse is not None else None
+        out = {}
+        for li, (sims, (b, heads, nqb, nt)) in sorted(self._sparse_sims.items()):
+            s = sims.detach().float().cpu()
+            sq, sk = s[:b * heads * nqb], s[b * heads * nqb:]
+            out[li] = (float(sq.mean()), float(sk.mean()), float((sq < theta).float().mean()), float((sk < theta).float().mean()))
+        return out
+
     def _sparse_begin(self, frames, tokens_per_frame, id_frames, dev, ws, batch, heads, head_dim):
-        """This forward's sparse state, decided before anything is launched: None (off, or `cdf_threshold >= 1`: dense), else
-        `.keep(q_rows)` -> the device table of the always-kept tiles of those query rows, or None when it covers every key tile
-        (the dense call); `.skip`; and the mask buffer and plan workspace, kept on the model workspace `ws` (allocated once per
-        workspace: a captured step replays them)."""
+        """This forward's sparse state, decided before anything is launched: None (off, or `cdf_threshold >= 1` without
+        `head_thresholds`: dense), else `.keep(q_rows)` -> the device table of the always-kept tiles of those query rows, or None
+        when it covers every key tile (the dense call); `.skip`; and the mask buffer and plan workspace, kept on the model
+        workspace `ws` (allocated once per workspace: a captured step replays them).  With `head_thresholds`: `.cdf_heads(layer)`
+        -> that layer's device table [heads] (None: the scalar) and `.dense`, the layers whose thresholds are all >= 1; with
+        `similarity_threshold`: `.similarity`, and the workspace holds the similarities too."""
         cfg = self._sparse
-        if cfg is None or cfg.cdf_threshold >= 1.0:
+        head_thr = getattr(cfg, "head_thresholds", None) or None
+        theta = getattr(cfg, "similarity_threshold", None)
+        if cfg is None or (cfg.cdf_threshold >= 1.0 and head_thr is None):
             return None
         id_frames = int(id_frames or 0)
         if not 0 <= id_frames < frames:
@@ -437,29 +511,73 @@ class SelfAttentionOptionsMixin:
 
         words, nqb = tile_mask_words(L), -(-L // Q_BLOCK)
         need_mask = batch * heads * nqb * words
-        need_plan = self.ops.attention_tile_plan_bytes(batch, heads, L, L, head_dim) // 4
+        plan_bytes = self.ops.attention_tile_plan_bytes if theta is None else self.ops.attention_tile_plan_gated_bytes
+        need_plan = plan_bytes(batch, heads, L, L, head_dim) // 4
         if getattr(ws, "sparse_mask", None) is None or ws.sparse_mask.numel() < need_mask:
             ws.sparse_mask = torch.zeros(need_mask, dtype=torch.int32, device=dev)
         if getattr(ws, "sparse_plan", None) is None or ws.sparse_plan.numel() < need_plan:
             ws.sparse_plan = torch.empty(need_plan, dtype=torch.float32, device=dev)
-        return SimpleNamespace(keep=keep, skip=frozenset(cfg.skip_layers), cdf=cfg.cdf_threshold, words=words, lk=L,
-                               mask=ws.sparse_mask, workspace=ws.sparse_plan, keep_masks=cfg.keep_masks)
+        sp = SimpleNamespace(keep=keep, skip=frozenset(cfg.skip_layers), cdf=cfg.cdf_threshold, words=words, lk=L,
+                             mask=ws.sparse_mask, workspace=ws.sparse_plan, keep_masks=cfg.keep_masks)
+        if theta is not None:
+            sp.similarity = theta
+        if head_thr is not None:
+            for li, row in head_thr.items():
+                if len(row) != heads:
+                    raise ValueError(f"head_thresholds[{li}] has {len(row)} entries: this forward has {heads} heads")
+            named_dense = {li for li, row in head_thr.items() if min(row) >= 1.0}
+            sp.dense = frozenset(named_dense if cfg.cdf_threshold < 1.0 else
+                                 named_dense | (set(range(self.config.num_layers)) - set(head_thr)))
+
+            def cdf_heads(li):
+                row = head_thr.get(li)
+                if row is None:
+                    return None
+                key = ("sparse_cdf", li, row, str(dev))
+                if key not in cache:
+                    cache[key] = torch.tensor(row, dtype=torch.float32).to(dev)
+                return cache[key]
+
+            sp.cdf_heads = cdf_heads
+        return sp
 
     @staticmethod
     def _sparse_tiles(sp, li, q_rows):
         """what `_attend(tiles=)` takes for block li's self-attention over the query rows `q_rows`, or None (dense)"""
-        if sp is None or li in sp.skip:
+        if sp is None or li in sp.skip or li in getattr(sp, "dense", ()):
             return None
         table = sp.keep(q_rows)
-        return None if table is None else SimpleNamespace(sp=sp, layer=li, keep=table)
+        if table is None:
+            return None
+        tiles = SimpleNamespace(sp=sp, layer=li, keep=table)
+        if getattr(sp, "cdf_heads", None) is not None:
+            tiles.cdf_heads = sp.cdf_heads(li)
+        return tiles
 
     def _attend_tiles(self, ops, q, k, v, heads, tiles, **kw):
         """the plan on this call's q and k, then the tile walk over its mask"""
+        if getattr(self, "_sparse_calib", None) is not None:
+            return self._sparse_calib.attend(self, ops, q, k, v, heads, tiles, **kw)
         sp = tiles.sp
         b, nqb = q.shape[0], -(-q.shape[1] // Q_BLOCK)
         mask = sp.mask[:b * heads * nqb * sp.words].view(b, heads, nqb, sp.words)
+        gate = {}                         # the safeguards of section 6k, named only when they are in use
+        if getattr(tiles, "cdf_heads", None) is not None:
+            gate["cdf_heads"] = tiles.cdf_heads
+        theta = getattr(sp, "similarity", None)
+        if theta is not None:
+            gate["similarity_threshold"] = theta
         ops.attention_tile_plan(q, k, heads, sp.cdf, keep_ranges=tiles.keep, scale=kw.get("scale"), out=mask,
-                                workspace=sp.workspace)
+                                workspace=sp.workspace, **gate)
+        if sp.keep_masks and theta is not None:
+            # the similarities sit in the workspace behind the pooled means (ops.attention_tile_plan)
+            nt = -(-k.shape[1] // KEY_TILE)
+            n, at = b * heads * (nqb + nt), b * heads * (nqb + nt) * (q.shape[2] // heads)
+            old = self._sparse_sims.get(tiles.layer)
+            sims = old[0] if old is not None and old[0].numel() == n else torch.empty(n, dtype=torch.float32,
+                                                                                     device=sp.workspace.device)
+            sims.copy_(sp.workspace[at:at + n])
+            self._sparse_sims[tiles.layer] = (sims, (b, heads, nqb, nt))
         if sp.keep_masks:
             old = self.sparse_attention_masks.get(tiles.layer)
             if old is None or old.shape != mask.shape:

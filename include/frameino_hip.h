@@ -273,6 +273,24 @@ int fino_attn_tile_plan(const void* q, const void* k, int batch, int heads, int6
                         int64_t q_rs, int64_t q_hs, int64_t k_bs, int64_t k_rs, int64_t k_hs, float scale, int dtype, float cdf,
                         const int* keep_ranges, uint32_t* mask, int words, void* workspace, int64_t workspace_bytes,
                         void* stream);
+/* fino_attn_tile_plan with the two safeguards of DESIGN.md section 6k, both opt-in: with cdf_heads == NULL and sim_threshold <= 0
+ * it launches what fino_attn_tile_plan launches and gives the same mask, bit for bit.
+ * cdf_heads: a DEVICE array of `heads` floats (or NULL): head h uses cdf_heads[h] instead of `cdf`; a value >= 1 keeps every tile
+ * of that head, explicitly (no bisection against a sum that is 1 +- rounding).
+ * sim_threshold = theta > 0 (at most 1): the pool pass also computes, per q-block and key tile, u = (1 / n) sum_r x_r / |x_r|_2
+ * over its n real rows (fp32; a zero row adds 0) and sim = |u|^2 -- the mean cosine over all ordered row pairs, in [0, 1] -- into
+ * the workspace behind the pooled means: sim_q [batch][heads][ceil(lq / 256)], then sim_k [batch][heads][ceil(lk / 64)].  U =
+ * {t : sim_k[t] < theta}.  A q-block with sim_q < theta keeps every tile.  Any other keeps U, and U takes no part in the
+ * prediction (not in the maximum, not in sum w: p_t = 0 there); the rule of fino_attn_tile_plan runs over the remaining tiles
+ * with the forced set F, m_F counting F \ U; kept = U + F + {p_t >= theta_p}.  Every tile in U: U and F alone.
+ * The workspace is fino_attn_tile_plan_gated_bytes() (= fino_attn_tile_plan_bytes() + 4 batch heads (nqb + ntall)) when
+ * sim_threshold > 0, fino_attn_tile_plan_bytes() otherwise.  Deterministic like fino_attn_tile_plan: no atomics, every sum in a
+ * fixed order. */
+int64_t fino_attn_tile_plan_gated_bytes(int batch, int heads, int64_t lq, int64_t lk, int head_dim);
+int fino_attn_tile_plan_gated(const void* q, const void* k, int batch, int heads, int64_t lq, int64_t lk, int head_dim,
+                              int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs, int64_t k_rs, int64_t k_hs, float scale,
+                              int dtype, float cdf, const float* cdf_heads, float sim_threshold, const int* keep_ranges,
+                              uint32_t* mask, int words, void* workspace, int64_t workspace_bytes, void* stream);
 /* fino_attn_fwd_fp8 (smooth_k = 0) or fino_attn_fwd_fp8_smooth (smooth_k != 0) over the SUBSET of key tiles fino_attn_fwd_ranges
  * walks: the same DEVICE table, int32 [ceil(lq / 256)][3][2] per 256 query rows (the kernel's workgroups hold 128 rows: two of them
  * share a table row), clipped to [0, ceil(lk / 64)] by the kernel -- a bad table gives a wrong answer, never a read outside the

@@ -14,8 +14,15 @@
   4. with --parent-lib PATH: the dense launch of this tree's library against another build's (the parent commit's), both loaded
      into this process, alternated.
 
+  5. with --gate (nothing of 1 - 4 is run): the PLAN per call at the bench shape through the old entry,
+     with the similarity gate (a theta nothing falls under, so that every q-block runs the whole select, and one everything
+     falls under), with a per-head table, and with both -- alternated in one run; with --parent-lib the old entry of this
+     tree's library against the parent commit's, masks compared; and the bench STEP dense / cdf_threshold 0.9 / cdf_threshold
+     0.9 + similarity_threshold, with the share of q-blocks and key tiles the gate fired on.
+
     python tools/sparse_attention_bench.py [--rounds 7] [--steps 3] [--skip-81f] [--parent-lib PATH]
                                            [--out profiles/sparse_attention.txt]
+    python tools/sparse_attention_bench.py --gate [--theta 0.3] [--parent-lib PATH] [--out profiles/sparse_attention_gate.txt]
 
 Quality on real checkpoints is NOT measured here or anywhere in this repository (random weights only)."""
 import argparse
@@ -129,7 +136,73 @@ def parent_ab(path, rounds, reps, frames=14, tpf=880, heads=24, dh=128):
     return {n: (statistics.median(v), min(v), max(v)) for n, v in t.items()}, torch.equal(outs["this tree"], outs["parent"])
 
 
-def step_times(workload, rounds, steps, cdf):
+def _median_us(runs, rounds, reps):
+    """{name: callable} -> {name: (median, min, max)} in us per call; alternated, device events"""
+    t = {n: [] for n in runs}
+    for f in runs.values():
+        f(), f()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for n, f in runs.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(reps):
+                f()
+            e.record()
+            torch.cuda.synchronize()
+            t[n].append(s.elapsed_time(e) / reps * 1e3)
+    return {n: (statistics.median(v), min(v), max(v)) for n, v in t.items()}
+
+
+def gate_plan_times(rounds, reps, theta, parent_lib=None, frames=14, tpf=880, heads=24, dh=128, cdf=0.9):
+    """the plan per call: old entry / gated / per-head table / both, and (parent_lib) the old entry of the parent's library"""
+    import ctypes
+    from frameino_amd import _lib
+    L, d, b = frames * tpf, heads * dh, 2
+    g = torch.Generator(device="cuda").manual_seed(0)
+    qkv = torch.randn(b, L, 3 * d, device="cuda", generator=g).bfloat16()
+    q, k = qkv[:, :, :d], qkv[:, :, d:2 * d]
+    keep_tab = frame_window_ranges(frames, tpf, 0, (0, -1)).cuda()
+    nqb, nt = -(-L // 256), -(-L // 64)
+    new_mask = lambda: torch.zeros(b, heads, nqb, (nt + 31) // 32, dtype=torch.int32, device="cuda")          # noqa: E731
+    ws = torch.empty(ops.attention_tile_plan_gated_bytes(b, heads, L, L, dh) // 4, dtype=torch.float32, device="cuda")
+    table = torch.full((heads,), cdf, dtype=torch.float32, device="cuda")
+    table[::2] = 0.5
+    never = 1e-6                # N(0, 1) rows: similarity ~ 1 / n = 0.004 (q-blocks), 0.016 (key tiles) -- nothing falls under this
+    names = {"ungated (old entry)": {}, f"gated, theta={never} (fires nowhere)": dict(similarity_threshold=never),
+             f"gated, theta={theta} (fires everywhere)": dict(similarity_threshold=theta),
+             "per-head table, no gate": dict(cdf_heads=table),
+             f"gated, theta={never} + per-head table": dict(similarity_threshold=never, cdf_heads=table)}
+    masks = {n: new_mask() for n in names}
+    runs = {n: (lambda kw=kw, m=masks[n]: ops.attention_tile_plan(q, k, heads, cdf, keep_ranges=keep_tab, out=m, workspace=ws, **kw))
+            for n, kw in names.items()}
+    same = None
+    if parent_lib:
+        other = ctypes.CDLL(parent_lib)
+        for name in ("fino_attn_tile_plan", "fino_last_error"):
+            getattr(other, name).argtypes = _lib.SIGNATURES.get(name)
+            getattr(other, name).restype = getattr(_lib.lib(), name).restype
+        st = torch.cuda.current_stream().cuda_stream
+
+        def raw(lib, m):                    # the C entry itself, for both libraries: no front-end work between the launches
+            rc = lib.fino_attn_tile_plan(q.data_ptr(), k.data_ptr(), b, heads, L, L, dh, q.stride(0), q.stride(1), dh, k.stride(0),
+                                         k.stride(1), dh, dh ** -0.5, 0, cdf, keep_tab.data_ptr(), m.data_ptr(), m.shape[3],
+                                         ws.data_ptr(), ws.numel() * 4, st)
+            assert rc == 0, lib.fino_last_error()
+
+        for n, lib in (("ungated, C entry, this tree's library", _lib.lib()), ("ungated, C entry, parent commit's library", other)):
+            masks[n] = new_mask()
+            runs[n] = (lambda lib=lib, m=masks[n]: raw(lib, m))
+    t = _median_us(runs, rounds, reps)
+    if parent_lib:
+        same = torch.equal(masks["ungated, C entry, this tree's library"], masks["ungated, C entry, parent commit's library"]) and \
+            torch.equal(masks["ungated (old entry)"], masks["ungated, C entry, parent commit's library"])
+    gate_off_same = torch.equal(masks["ungated (old entry)"], masks[f"gated, theta={never} (fires nowhere)"])
+    dens = {n: ops.tile_mask_density(m, L) for n, m in masks.items()}
+    return t, dens, same, gate_off_same
+
+
+def step_times(workload, rounds, steps, cdf, theta=None):
     import bench
     from frameino_amd.pipeline_wan_i2v_motion_frameino import WanImageToVideoPipeline
     from frameino_amd.schedulers import FlowMatchEulerDiscreteScheduler
@@ -152,11 +225,11 @@ def step_times(workload, rounds, steps, cdf):
                          ne.to(dev).bfloat16(), 5.0)
     ts, dts, lat0 = pipe.scheduler.timesteps.to(dev).float(), pipe.scheduler.dts.to(dev), st.lat.clone()
 
-    def run(sparse, n, keep_masks=False):
+    def run(sparse, n, keep_masks=False, similarity=None):
         model.disable_sparse_attention()
         if sparse:
             model.enable_sparse_attention(SparseAttentionConfig(cdf_threshold=cdf, window_frames=0, sink_frames=(0,),
-                                                                keep_masks=keep_masks))
+                                                                keep_masks=keep_masks, similarity_threshold=similarity))
         st.lat.copy_(lat0)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -172,15 +245,65 @@ def step_times(workload, rounds, steps, cdf):
     per_layer = model.sparse_attention_density()                          # ... and the density of the first step's masks
     dens = sum(per_layer.values()) / len(per_layer)
     t = {"dense": [], f"cdf_threshold={cdf}": []}
+    gate = None
+    if theta is not None:                                                 # the gate's first step: what it fired on, what was kept
+        run(True, 1, keep_masks=True, similarity=theta)
+        sims, gd = model.sparse_attention_similarity(), model.sparse_attention_density()
+        gate = {"density": sum(gd.values()) / len(gd), "sim_q": sum(v[0] for v in sims.values()) / len(sims),
+                "sim_k": sum(v[1] for v in sims.values()) / len(sims), "q_fired": sum(v[2] for v in sims.values()) / len(sims),
+                "k_fired": sum(v[3] for v in sims.values()) / len(sims)}
+        t[f"cdf_threshold={cdf}, similarity_threshold={theta}"] = []
     for _ in range(rounds):
         t["dense"].append(run(False, steps))
         t[f"cdf_threshold={cdf}"].append(run(True, steps))
+        if theta is not None:
+            t[f"cdf_threshold={cdf}, similarity_threshold={theta}"].append(run(True, steps, similarity=theta))
     frames, tpf = fg + nid, (lh // 2) * (lw // 2)
     forced = ranges_density(frame_window_ranges(frames, tpf, 0, (0, -1)), frames * tpf)
     del model, pipe, st
     torch.cuda.empty_cache()
-    return ({n: (statistics.median(v), min(v), max(v)) for n, v in t.items()}, dens, min(per_layer.values()),
-            max(per_layer.values()), forced, frames, tpf)
+    out = ({n: (statistics.median(v), min(v), max(v)) for n, v in t.items()}, dens, min(per_layer.values()),
+           max(per_layer.values()), forced, frames, tpf)
+    return out if theta is None else out + (gate,)
+
+
+def gate_report(a):
+    lines = [f"# tools/sparse_attention_bench.py --gate on {torch.cuda.get_device_name(0)}; bf16; one box, one run",
+             "# the similarity gate and the per-head thresholds of the sparse attention (DESIGN.md section 6k)",
+             "# quality on real checkpoints: NOT measured (random weights and N(0, 1) inputs only: what the gate fires on here says",
+             "# nothing about a real checkpoint)", ""]
+    t, dens, same, gate_off_same = gate_plan_times(a.rounds, a.reps, a.theta, a.parent_lib, cdf=a.cdf)
+    base = t["ungated (old entry)"]
+    lines.append(f"plan (pool + select) per call, [2, 12320, 24 x 128], cdf = {a.cdf}; alternated, {a.rounds} rounds x {a.reps} calls")
+    lines.append(f"{'':46s} {'median us':>10s} {'min':>9s} {'max':>9s} {'vs ungated':>11s} {'density':>8s}")
+    for n, (med, lo, hi) in t.items():
+        lines.append(f"{n:46s} {med:10.1f} {lo:9.1f} {hi:9.1f} {med / base[0]:11.3f} {dens[n]:8.3f}")
+    lines.append(f"run-to-run spread of the ungated plan in this run: {base[2] - base[1]:.1f} us ({(base[2] - base[1]) / base[0] * 100:.1f} % "
+                 f"of its median)")
+    lines.append(f"mask of the gated entry with a theta nothing falls under == mask of the old entry: {gate_off_same}")
+    if same is not None:
+        own, par = t["ungated, C entry, this tree's library"], t["ungated, C entry, parent commit's library"]
+        lines.append(f"ungated plan through the C entry, this tree against the parent commit's library: {own[0]:.1f} vs {par[0]:.1f} us "
+                     f"(difference {own[0] - par[0]:+.1f} us; spread of the two {own[2] - own[1]:.1f} / {par[2] - par[1]:.1f} us); masks "
+                     f"torch.equal: {same}")
+        lines.append("(the rows above it go through ops.attention_tile_plan, whose argument checks sit between the launches)")
+    worst = max(v[0] for n, v in t.items() if n.startswith("gated"))
+    lines.append(f"the tile walk saves 320 us per launch at density 0.9 (profiles/sparse_attention.txt: 3222.9 dense, density x "
+                 f"1.067 x dense walked); the costliest gated plan takes {worst:.1f} us of that, the ungated plan {base[0]:.1f} us")
+    if not a.skip_steps:
+        wl = "wan2.2-5b-49f-704x1280"
+        stt, d0, dlo, dhi, forced, frames, tpf, gate = step_times(wl, a.step_rounds, a.steps, a.cdf, a.theta)
+        b0 = stt["dense"][0]
+        lines.append("")
+        lines.append(f"denoise step, {wl} ({frames} latent frames x {tpf} tokens; eager, CFG batch); first step's mask density "
+                     f"{d0:.3f} without the gate, {gate['density']:.3f} with similarity_threshold = {a.theta}")
+        lines.append(f"the gate on that step: mean sim_q {gate['sim_q']:.3f}, mean sim_k {gate['sim_k']:.3f}; it fired on "
+                     f"{gate['q_fired'] * 100:.1f} % of the q-blocks and {gate['k_fired'] * 100:.1f} % of the key tiles (means over the layers)")
+        lines.append("(random weights: these shares and densities say nothing about real checkpoints)")
+        lines.append(f"{'':48s} {'median ms':>10s} {'min':>9s} {'max':>9s} {'ratio':>7s}")
+        for n, (med, lo, hi) in stt.items():
+            lines.append(f"{n:48s} {med:10.1f} {lo:9.1f} {hi:9.1f} {med / b0:7.3f}")
+    return lines
 
 
 def main():
@@ -193,10 +316,20 @@ def main():
     ap.add_argument("--skip-steps", action="store_true")
     ap.add_argument("--skip-81f", action="store_true")
     ap.add_argument("--parent-lib", default=None, help="another build of libframeino_hip.so to alternate the dense launch with")
+    ap.add_argument("--gate", action="store_true", help="measure the similarity gate and the per-head table only (section 6k)")
+    ap.add_argument("--theta", type=float, default=0.3, help="with --gate: the similarity threshold")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sparse_attention_bench: needs the GPU (no CPU path, nothing is estimated)")
+    if a.gate:
+        text = "\n".join(gate_report(a)) + "\n"
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     lines = [f"# tools/sparse_attention_bench.py on {torch.cuda.get_device_name(0)}; bf16; one box, one run",
              "# forced tiles: own frame(s), first frame, ID frame (window_frames = 0); extra tiles: random per (b, head, q-block)",
              "# quality on real checkpoints: NOT measured (random weights only)", ""]
