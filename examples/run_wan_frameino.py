@@ -63,6 +63,15 @@ def main():
                     help="diffusers' Pyramid Attention Broadcast (approximate; eager loop): while the timestep is inside (100, 800) "
                          "the self-attention branch is recomputed every N-th step and re-used in between, and with M the text "
                          "cross-attention branch every M-th, e.g. 2 or 2,3.  Not together with --first-block-cache")
+    ap.add_argument("--taylorseer", type=int, default=None, metavar="N",
+                    help="diffusers' TaylorSeer caching (approximate; eager loop; quality on real checkpoints unmeasured): after "
+                         "the warm-up steps every N-th step computes and the steps between extrapolate every attention branch's "
+                         "output from finite differences of the computed ones, e.g. 5.  Not together with --first-block-cache, "
+                         "--pab, --window-frames or --sparse-attention")
+    ap.add_argument("--taylorseer-order", type=int, default=1, metavar="K", help="order of the extrapolation, 0 to 3")
+    ap.add_argument("--taylorseer-warmup", type=int, default=3, metavar="W", help="the first W steps always compute")
+    ap.add_argument("--taylorseer-lite", action="store_true",
+                    help="lite mode: extrapolate the model's output itself; a predicted step runs no block at all")
     ap.add_argument("--window-frames", type=int, default=None, metavar="N",
                     help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
                          "every query attends its own frame +- N neighbours plus the first frame and the ID frame, e.g. 2.  Not "
@@ -169,6 +178,11 @@ def main():
         transformer.enable_cache(PyramidAttentionBroadcastConfig(
             spatial_attention_block_skip_range=n_m[0], cross_attention_block_skip_range=n_m[1] if len(n_m) > 1 else None,
             current_timestep_callback=lambda: pipe.current_timestep))
+    if a.taylorseer is not None:
+        from frameino_amd.step_cache import TaylorSeerCacheConfig
+        transformer.enable_cache(TaylorSeerCacheConfig(cache_interval=a.taylorseer, max_order=a.taylorseer_order,
+                                                       disable_cache_before_step=a.taylorseer_warmup,
+                                                       use_lite_mode=a.taylorseer_lite))
     if a.fp8_attention:
         transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v)
     if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)

@@ -137,6 +137,9 @@ SIGNATURES = {
     "fino_step_cache_residual": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_void_p],
     "fino_pab_broadcast": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_int,
                            c_void_p],
+    "fino_taylor_update": [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "fino_taylor_predict": [c_void_p, c_i64, c_i64, c_int, ctypes.POINTER(c_float), c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64,
+                            c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p],
 }
 
 

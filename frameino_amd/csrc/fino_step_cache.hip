@@ -18,6 +18,10 @@
 // compiler's default contraction), so the fma is spelled out here: a step that re-uses y gives the bits of the step that
 // computed it.  (fino_gated_residual multiplies and adds with two roundings.)
 //
+// fino_taylor_update / fino_taylor_predict (TaylorSeer): the finite-difference factors of a hooked tensor along the step axis,
+// updated in place on a computing step, and the Taylor extrapolation a predicting step writes or adds to the residual stream
+// with fino_pab_broadcast's arithmetic (include/frameino_hip.h spells out both).
+//
 // HBM-bound: 16-byte loads and stores, fp32 arithmetic, no contraction (the file is built with -ffp-contract=off).
 #include "fino_common.h"
 
@@ -187,7 +191,124 @@ __global__ __launch_bounds__(kThreads) void pab_broadcast_kernel(const void* x, 
     }
 }
 
+// ---- TaylorSeer: 8 consecutive elements of a factor plane (dtype F) as fp32 lanes: one 16-byte vector, two for fp32 planes
+template <typename F>
+struct Plane {
+    static __device__ __forceinline__ void load(const void* base, int64_t off, float (&f)[8]) {
+        unpack8<F>(*(const uint4*)((const char*)base + off * 2), f);
+    }
+    static __device__ __forceinline__ void store(void* base, int64_t off, const float (&f)[8]) {
+        *(uint4*)((char*)base + off * 2) = pack8<F>(f);
+    }
+    static __device__ __forceinline__ float rnd(float x) { return round_to<F>(x); }
+};
+template <>
+struct Plane<F32> {
+    static __device__ __forceinline__ void load(const void* base, int64_t off, float (&f)[8]) {
+        const float4* p = (const float4*)((const char*)base + off * 4);
+        const float4 a = p[0], b = p[1];
+        f[0] = a.x, f[1] = a.y, f[2] = a.z, f[3] = a.w, f[4] = b.x, f[5] = b.y, f[6] = b.z, f[7] = b.w;
+    }
+    static __device__ __forceinline__ void store(void* base, int64_t off, const float (&f)[8]) {
+        float4* p = (float4*)((char*)base + off * 4);
+        p[0] = make_float4(f[0], f[1], f[2], f[3]);
+        p[1] = make_float4(f[4], f[5], f[6], f[7]);
+    }
+    static __device__ __forceinline__ float rnd(float x) { return x; }
+};
+
+constexpr int kTaylorPlanes = FINO_TAYLOR_MAX_PLANES;
+
+// g_0 = F(y), g_{i+1} = F((g_i - f_i) / delta) for i + 1 < n_new; planes 0 .. n_new - 1 are rewritten in place.  Every old
+// plane a thread needs (0 .. n_new - 2) is in registers before its first store; no two threads share an element.
+template <typename T, typename F>
+__global__ __launch_bounds__(kThreads) void taylor_update_kernel(const void* y, int64_t ldy, void* fac, int64_t plane, int64_t ldf,
+                                                                 uint32_t vpr, uint32_t nvec, int n_new, float delta) {
+    using P = Plane<F>;
+    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < nvec; i += gridDim.x * kThreads) {
+        const int64_t row = i / vpr;
+        const uint32_t col = (i % vpr) * 8;
+        const int64_t off = row * ldf + col;
+        float g[8], old[kTaylorPlanes - 1][8];
+        unpack8<T>(*at(y, row, ldy, col, 2), g);
+#pragma unroll
+        for (int k = 0; k < kTaylorPlanes - 1; ++k)
+            if (k + 1 < n_new) P::load(fac, k * plane + off, old[k]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) g[e] = P::rnd(g[e]);
+        P::store(fac, off, g);
+#pragma unroll
+        for (int k = 0; k < kTaylorPlanes - 1; ++k) {
+            if (k + 1 >= n_new) break;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) g[e] = P::rnd((g[e] - old[k][e]) / delta);
+            P::store(fac, (k + 1) * plane + off, g);
+        }
+    }
+}
+
+struct TaylorCoef {
+    float c[kTaylorPlanes];
+};
+
+// p = f_0; p = p + f_i * c_i (i = 1 .. n - 1: the product rounded, then the sum: no contraction in this file); then
+// out = T(p) | T(p + x) | T(fma(p, gate[sel[row]], x)) -- the last two as pab_broadcast_kernel writes them
+template <typename T, typename F>
+__global__ __launch_bounds__(kThreads) void taylor_predict_kernel(const void* fac, int64_t plane, int64_t ldf, int n, TaylorCoef coef,
+                                                                  const void* x, int64_t ldx, void* out, int64_t ldo, uint32_t vpr,
+                                                                  uint32_t nvec, const float* gate, int64_t mod_stride,
+                                                                  const int32_t* sel) {
+    using P = Plane<F>;
+    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < nvec; i += gridDim.x * kThreads) {
+        const int64_t row = i / vpr;
+        const uint32_t col = (i % vpr) * 8;
+        const int64_t off = row * ldf + col;
+        float p[8], f[kTaylorPlanes - 1][8], fx[8], fo[8];
+        P::load(fac, off, p);
+#pragma unroll
+        for (int k = 1; k < kTaylorPlanes; ++k)
+            if (k < n) P::load(fac, k * plane + off, f[k - 1]);
+        if (x) unpack8<T>(*at(x, row, ldx, col, 2), fx);
+#pragma unroll
+        for (int k = 1; k < kTaylorPlanes; ++k) {
+            if (k >= n) break;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float t = f[k - 1][e] * coef.c[k];
+                p[e] = p[e] + t;
+            }
+        }
+        if (!x) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) fo[e] = p[e];
+        } else if (gate) {
+            const float* g = gate + (sel ? (int64_t)sel[row] * mod_stride : 0) + col;
+            const float4 g0 = *reinterpret_cast<const float4*>(g);
+            const float4 g1 = *reinterpret_cast<const float4*>(g + 4);
+            const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) fo[e] = __builtin_fmaf(p[e], gg[e], fx[e]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) fo[e] = fx[e] + p[e];
+        }
+        *(uint4*)at(out, row, ldo, col, 2) = pack8<T>(fo);
+    }
+}
+
 int esize_of(int dtype) { return dtype == FINO_F32 ? 4 : 2; }
+
+// the factor planes of a TaylorSeer call: [n planes][rows][dim] of dtype fdtype, 16-byte aligned rows, planes that do not overlap
+bool planes_ok(const void* fac, int64_t plane, int64_t ldf, int fdtype, int n, int64_t rows, int64_t dim) {
+    const int per16 = 16 / esize_of(fdtype);
+    if (!fac || !fino_aligned16(fac) || ldf < dim || ldf % per16 != 0) return false;
+    return n <= 1 || (plane % per16 == 0 && (rows == 0 || plane >= (rows - 1) * ldf + dim));
+}
+
+int taylor_grid(uint32_t nvec) {
+    const int64_t grid = ((int64_t)nvec + kThreads - 1) / kThreads;
+    return (int)(grid > 256 * 8 ? 256 * 8 : grid);
+}
 
 bool rows_ok(const void* p, int64_t ld, int dtype) {
     const int per16 = 16 / esize_of(dtype);
@@ -282,6 +403,72 @@ extern "C" int fino_pab_broadcast(const void* x, int64_t ldx, const void* y, int
         pab_broadcast_kernel<BF16><<<(int)grid, kThreads, 0, st>>>(x, ldx, y, ldy, out, ldo, vpr, nvec, gate, mod_stride, sel);
     else
         pab_broadcast_kernel<F16><<<(int)grid, kThreads, 0, st>>>(x, ldx, y, ldy, out, ldo, vpr, nvec, gate, mod_stride, sel);
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
+}
+
+#define FINO_TAYLOR_DISPATCH(KERNEL, ...)                                                          \
+    do {                                                                                           \
+        if (dtype == FINO_BF16 && fdtype == FINO_BF16)                                             \
+            KERNEL<BF16, BF16><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                            \
+        else if (dtype == FINO_BF16 && fdtype == FINO_F16)                                         \
+            KERNEL<BF16, F16><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                             \
+        else if (dtype == FINO_BF16)                                                               \
+            KERNEL<BF16, F32><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                             \
+        else if (fdtype == FINO_BF16)                                                              \
+            KERNEL<F16, BF16><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                             \
+        else if (fdtype == FINO_F16)                                                               \
+            KERNEL<F16, F16><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                              \
+        else                                                                                       \
+            KERNEL<F16, F32><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                              \
+    } while (0)
+
+extern "C" int fino_taylor_update(const void* y, int64_t ldy, void* factors, int64_t plane_stride, int64_t ldf, int64_t rows,
+                                  int64_t dim, int n_old, int n_new, int delta, int dtype, int fdtype, void* stream) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_taylor_update: dtype %d", dtype);
+    FINO_CHECK(fdtype == FINO_BF16 || fdtype == FINO_F16 || fdtype == FINO_F32, FINO_ERR_ARG, "fino_taylor_update: factor dtype %d",
+               fdtype);
+    FINO_CHECK(rows >= 0 && dim > 0 && dim % 8 == 0 && rows * (dim / 8) < (1LL << 31), FINO_ERR_ARG,
+               "fino_taylor_update: rows=%lld dim=%lld", (long long)rows, (long long)dim);
+    FINO_CHECK(n_old >= 0 && n_old <= FINO_TAYLOR_MAX_PLANES && n_new >= 1 && n_new <= FINO_TAYLOR_MAX_PLANES && n_new <= n_old + 1,
+               FINO_ERR_ARG, "fino_taylor_update: n_old=%d n_new=%d (n_new in 1 .. %d, at most n_old + 1)", n_old, n_new,
+               FINO_TAYLOR_MAX_PLANES);
+    FINO_CHECK(delta >= 1 || n_new == 1, FINO_ERR_ARG, "fino_taylor_update: delta=%d must be at least 1", delta);
+    FINO_CHECK(y && ldy >= dim, FINO_ERR_ARG, "fino_taylor_update: y missing or its row stride below dim");
+    FINO_CHECK(rows_ok(y, ldy, dtype) && planes_ok(factors, plane_stride, ldf, fdtype, n_new, rows, dim), FINO_ERR_ARG,
+               "fino_taylor_update: 16-byte aligned rows, row strides of at least dim and planes that do not overlap required");
+    if (rows == 0) return FINO_OK;
+    const uint32_t vpr = (uint32_t)(dim / 8), nvec = (uint32_t)(rows * vpr);
+    const int grid = taylor_grid(nvec);
+    hipStream_t st = (hipStream_t)stream;
+    FINO_TAYLOR_DISPATCH(taylor_update_kernel, y, ldy, factors, plane_stride, ldf, vpr, nvec, n_new, (float)delta);
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
+}
+
+extern "C" int fino_taylor_predict(const void* factors, int64_t plane_stride, int64_t ldf, int n, const float* coef, const void* x,
+                                   int64_t ldx, void* out, int64_t ldo, int64_t rows, int64_t dim, const float* gate,
+                                   int64_t mod_stride, const int32_t* sel, int dtype, int fdtype, void* stream) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_taylor_predict: dtype %d", dtype);
+    FINO_CHECK(fdtype == FINO_BF16 || fdtype == FINO_F16 || fdtype == FINO_F32, FINO_ERR_ARG, "fino_taylor_predict: factor dtype %d",
+               fdtype);
+    FINO_CHECK(rows >= 0 && dim > 0 && dim % 8 == 0 && rows * (dim / 8) < (1LL << 31), FINO_ERR_ARG,
+               "fino_taylor_predict: rows=%lld dim=%lld", (long long)rows, (long long)dim);
+    FINO_CHECK(n >= 1 && n <= FINO_TAYLOR_MAX_PLANES && coef, FINO_ERR_ARG, "fino_taylor_predict: n=%d planes (1 .. %d) with n "
+               "host coefficients", n, FINO_TAYLOR_MAX_PLANES);
+    FINO_CHECK(out && ldo >= dim && (!x || ldx >= dim), FINO_ERR_ARG, "fino_taylor_predict: out missing or a row stride below dim");
+    FINO_CHECK(x || !gate, FINO_ERR_ARG, "fino_taylor_predict: a gate needs x");
+    FINO_CHECK(planes_ok(factors, plane_stride, ldf, fdtype, n, rows, dim) && rows_ok(out, ldo, dtype) &&
+                   (!x || rows_ok(x, ldx, dtype)) && (!gate || (fino_aligned16(gate) && mod_stride % 4 == 0)),
+               FINO_ERR_ARG,
+               "fino_taylor_predict: 16-byte aligned rows, row strides of at least dim and planes that do not overlap required");
+    if (rows == 0) return FINO_OK;
+    TaylorCoef c = {};
+    for (int i = 0; i < n; ++i) c.c[i] = coef[i];
+    const uint32_t vpr = (uint32_t)(dim / 8), nvec = (uint32_t)(rows * vpr);
+    const int grid = taylor_grid(nvec);
+    hipStream_t st = (hipStream_t)stream;
+    FINO_TAYLOR_DISPATCH(taylor_predict_kernel, factors, plane_stride, ldf, n, c, x, ldx, out, ldo, vpr, nvec, gate, mod_stride, sel);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }

@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the HIP stream; every op bel
 pointers + strides to libframeino_hip.so on torch's *current* stream (so the calls are capturable in a
 torch.cuda.CUDAGraph == hipGraph).  No op has a torch/CPU fallback.
 """
+import math
 import os
 
 import torch
@@ -1311,4 +1312,96 @@ def pab_broadcast(x, y, gate=None, sel=None, out=None):
     ms = gate.stride(0) if (gate is not None and gate.dim() == 2) else 0
     _lib.check(_lib.lib().fino_pab_broadcast(_p(x), x.stride(0), _p(y), y.stride(0), _p(out), out.stride(0), rows, d, _p(gate),
                                              ms, _p(sel), _dt(x), _stream()), "fino_pab_broadcast")
+    return out
+
+
+TAYLOR_MAX_PLANES = 4                      # FINO_TAYLOR_MAX_PLANES
+_TAYLOR_FACTOR_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
+
+
+def _taylor_planes(factors, rows, d, what):
+    """the factor planes of a TaylorSeer buffer: [planes, rows, D] bf16 / fp16 / fp32 with a contiguous last dimension"""
+    if not factors.is_cuda:
+        raise RuntimeError("frameino_amd ops need CUDA(HIP) tensors; there is no CPU path")
+    if factors.dim() != 3 or factors.stride(2) != 1 or factors.dtype not in _TAYLOR_FACTOR_DTYPES:
+        raise ValueError(f"{what}: factors must be a [planes, rows, D] bf16 / fp16 / fp32 tensor with a contiguous last "
+                         f"dimension, got {tuple(factors.shape)} {factors.dtype} strides {factors.stride()}")
+    if tuple(factors.shape[1:]) != (rows, d):
+        raise ValueError(f"{what}: factor planes are {tuple(factors.shape[1:])}, want {(rows, d)}")
+    return factors
+
+
+def taylor_coefficients(k, n):
+    """c_i = float32(k**i / i!) for i < n, computed in double: the weights of a TaylorSeer prediction k steps after the last
+    computed step"""
+    return [_lib.c_float(float(k) ** i / math.factorial(i)).value for i in range(n)]      # (c_float rounds to nearest even)
+
+
+def _taylor_bytes(name, ev, nbytes):
+    if ev is not None:
+        ev.record()
+        kt_ = KernelTimer.active
+        kt_.bytes[name] = kt_.bytes.get(name, 0.0) + nbytes
+
+
+def taylor_update(y, factors, n_old, delta, n_new=None):
+    """TaylorSeer factor update on a step that computed y (fino_taylor_update), in place: g_0 = F(y),
+    g_{i+1} = F((g_i - f_i) / delta) for i + 1 < n_new, then f = g; every operation one fp32 operation, every factor rounded to
+    F once.  y row-strided [rows, D] bf16 / fp16; factors [planes, rows, D] of dtype F (bf16 / fp16 / fp32), of which the first
+    `n_old` are valid; `n_new` defaults to min(n_old + 1, planes).  Planes at and beyond n_new are not touched.  -> n_new"""
+    _rows_of(y, y.dtype, "taylor_update y")
+    rows, d = y.shape
+    _taylor_planes(factors, rows, d, "taylor_update")
+    planes = factors.shape[0]
+    n_old, delta = int(n_old), int(delta)
+    n_new = min(n_old + 1, planes) if n_new is None else int(n_new)
+    if not (0 <= n_old <= planes <= TAYLOR_MAX_PLANES and 1 <= n_new <= min(n_old + 1, planes)):
+        raise ValueError(f"taylor_update: n_old={n_old} n_new={n_new} with {planes} planes (at most {TAYLOR_MAX_PLANES}; "
+                         f"n_new in 1 .. min(n_old + 1, planes))")
+    if delta < 1 and n_new > 1:
+        raise ValueError(f"taylor_update: delta={delta} must be at least 1")
+    if factors.device != y.device:
+        raise ValueError(f"taylor_update: y on {y.device}, factors on {factors.device}")
+    ev = _timed("taylor_update")
+    _lib.check(_lib.lib().fino_taylor_update(_p(y), y.stride(0), _p(factors), factors.stride(0), factors.stride(1), rows, d, n_old,
+                                             n_new, delta, _dt(y), _dt3(factors), _stream()), "fino_taylor_update")
+    _taylor_bytes("taylor_update", ev, rows * d * (y.element_size() + (2 * n_new - 1) * factors.element_size()))
+    return n_new
+
+
+def taylor_predict(factors, n, k, x=None, gate=None, sel=None, out=None, dtype=None):
+    """TaylorSeer prediction k steps after the last update from the first n factor planes (fino_taylor_predict):
+    p = f_0 + sum_{i=1}^{n-1} f_i * float32(k**i / i!) in fp32 (the product and the sum each rounded, in that order), then
+    out = T(p) (x None), T(x + p) (gate None) or T(fma(p, gate[sel], x)) -- the last two are `pab_broadcast` on y = p.
+    factors [planes, rows, D] bf16 / fp16 / fp32; x / out row-strided [rows, D] bf16 / fp16 (`dtype` names T when neither is
+    given); out may alias x."""
+    if factors.dim() != 3:
+        raise ValueError(f"taylor_predict: factors must be [planes, rows, D], got {tuple(factors.shape)}")
+    rows, d = factors.shape[1:]
+    _taylor_planes(factors, rows, d, "taylor_predict")
+    n = int(n)
+    if not (1 <= n <= factors.shape[0] <= TAYLOR_MAX_PLANES):
+        raise ValueError(f"taylor_predict: n={n} of {factors.shape[0]} planes (1 .. planes, at most {TAYLOR_MAX_PLANES})")
+    t = x.dtype if x is not None else out.dtype if out is not None else dtype
+    if t not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"taylor_predict: the output dtype must be bf16 or fp16, got {t}")
+    if x is not None:
+        _rows_of(x, t, "taylor_predict x")
+    elif gate is not None or sel is not None:
+        raise ValueError("taylor_predict: a gate needs x")
+    out = torch.empty((rows, d), dtype=t, device=factors.device) if out is None else _rows_of(out, t, "taylor_predict out")
+    if tuple(out.shape) != (rows, d) or (x is not None and tuple(x.shape) != (rows, d)):
+        raise ValueError(f"taylor_predict: factor planes {(rows, d)} / x {None if x is None else tuple(x.shape)} / out "
+                         f"{tuple(out.shape)}")
+    if out.device != factors.device or (x is not None and x.device != factors.device):
+        raise ValueError("taylor_predict: operands on different devices")
+    if gate is not None:
+        assert gate.dtype == torch.float32 and gate.stride(-1) == 1 and gate.shape[-1] == d
+    ms = gate.stride(0) if (gate is not None and gate.dim() == 2) else 0
+    coef = (_lib.c_float * TAYLOR_MAX_PLANES)(*taylor_coefficients(k, n))
+    ev = _timed("taylor_predict")
+    _lib.check(_lib.lib().fino_taylor_predict(_p(factors), factors.stride(0), factors.stride(1), n, coef, _p(x),
+                                              0 if x is None else x.stride(0), _p(out), out.stride(0), rows, d, _p(gate), ms,
+                                              _p(sel), _dt(out), _dt3(factors), _stream()), "fino_taylor_predict")
+    _taylor_bytes("taylor_predict", ev, rows * d * (n * factors.element_size() + (2 if x is not None else 1) * out.element_size()))
     return out

@@ -27,6 +27,10 @@ Pyramid Attention Broadcast (`enable_cache(PyramidAttentionBroadcastConfig(spati
 current_timestep_callback=lambda: pipe.current_timestep))`) takes the same eager loop, one GPU, fresh state per `denoise`.  Its
 decisions depend on the step counter and the timestep only, so a batch is allowed: the samples run one at a time, each from
 fresh state, and decide as a joint run would.  Replaying its host-known schedule from captured graphs is not built.
+
+TaylorSeer caching (`enable_cache(TaylorSeerCacheConfig(cache_interval=5, disable_cache_before_step=3, max_order=1))`, with
+`use_lite_mode=True` for the mode that predicts the model's output) follows the same rules: the eager loop, one GPU, fresh state
+per `denoise`, a batch sample by sample; its decisions depend on the step counter alone.
 """
 import html
 import re
@@ -163,17 +167,22 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
             reset()
 
     def _step_cache_check(self, batch):
-        """the limits of the step caches (first-block caching, Pyramid Attention Broadcast), checked before any work (and before
+        """the limits of the step caches (first-block caching, Pyramid Attention Broadcast, TaylorSeer), checked before any work (and before
         any collective: a parallel plan and the cache are configured by the same script on every rank, so every rank raises)"""
         if not getattr(self.transformer, "is_cache_enabled", False):
             return False
         pab = bool(getattr(self.transformer, "_pab_on", False))
-        what = "Pyramid Attention Broadcast" if pab else "first-block caching"
+        taylor = bool(getattr(self.transformer, "_taylor_on", False))
+        what = "Pyramid Attention Broadcast" if pab else "TaylorSeer caching" if taylor else "first-block caching"
         if getattr(self, "parallel", None) is not None:
             raise NotImplementedError(f"{what} runs on one GPU; this pipeline has a parallel plan")
-        if batch > 1 and not pab:
-            # (Pyramid Attention Broadcast decides from the step counter and the timestep alone: the samples of a batch, run
-            # one at a time from fresh state, decide as diffusers' joint run does)
+        if self.use_hip_graph is True and taylor:
+            raise RuntimeError("use_hip_graph=True with TaylorSeer caching: whether a step computes or predicts changes from step "
+                               "to step on the host's schedule, which one captured step cannot contain (the loop runs eagerly; "
+                               "use_hip_graph=None or False)")
+        if batch > 1 and not pab and not taylor:
+            # (Pyramid Attention Broadcast decides from the step counter and the timestep alone, TaylorSeer from the step counter:
+            # the samples of a batch, run one at a time from fresh state, decide as diffusers' joint run does)
             raise NotImplementedError("first-block caching with a batch (a list of prompts, num_videos_per_prompt > 1): diffusers "
                                       "decides jointly over the batch, this pipeline runs the samples one at a time")
         if self.use_hip_graph is True and pab:

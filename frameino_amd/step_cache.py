@@ -1,8 +1,9 @@
 """Step caching of the Wan DiT: diffusers' `CacheMixin` (diffusers/models/cache_utils.py), which the reference's
 WanTransformer3DModel inherits (architecture/transformer_wan.py:28, :353) and whose state its FrameINO loop keys by
-`cache_context("cond")` / `("uncond")` (pipelines/pipeline_wan_i2v_motion_FrameINO.py:862, :873), with two of its configs:
-`FirstBlockCacheConfig` (diffusers/hooks/first_block_cache.py) and `PyramidAttentionBroadcastConfig`
-(diffusers/hooks/pyramid_attention_broadcast.py).  One at a time: a second `enable_cache` raises, as in diffusers.
+`cache_context("cond")` / `("uncond")` (pipelines/pipeline_wan_i2v_motion_FrameINO.py:862, :873), with three of its configs:
+`FirstBlockCacheConfig` (diffusers/hooks/first_block_cache.py), `PyramidAttentionBroadcastConfig`
+(diffusers/hooks/pyramid_attention_broadcast.py) and `TaylorSeerCacheConfig` (diffusers/hooks/taylorseer_cache.py).  One at a
+time: a second `enable_cache` raises, as in diffusers.
 
 First-block caching.  The rule, per forward under context c (T = the model dtype; h0 = input of block 0, h1 = its output, hN = the last block's):
 
@@ -30,6 +31,32 @@ residual add.  The decision is a function of the step counter and the timestep a
 so one counter per (context, kind) stands for them, the callback is read once per forward, and nothing on the device is read.
 A kind whose `*_block_skip_range` is None is never hooked and always computes.  The model asks `_pab_begin` for a forward's
 decisions and `_pab_buffer` for a layer's `[rows, D]` cache.
+
+TaylorSeer.  This project's restatement with diffusers' names (diffusers is not vendored by the reference): the rule below is the
+contract, and the decision sits in one pure function, `taylorseer_decide`, so that it can be aligned with diffusers in one place.
+Per context, s = the 0-based count of forwards since the last reset, W = disable_cache_before_step, N = cache_interval,
+A = disable_cache_after_step:
+
+    compute  if  no factor yet  or  s < W  or  (s - (W - 1)) % N == 0  or  (A is not None and s >= A)         else predict
+
+Per (context, hooked tensor) the state is up to max_order + 1 factor planes f_0 .. f_max [rows, D] in the factor dtype F
+(`taylor_factors_dtype`, None = the model dtype), the count n of valid planes and s_last, the last computing forward.
+A computing forward that sees y, delta = s - s_last forwards after the last one (ops.taylor_update):
+
+    g_0 = F(y);   g_{i+1} = F((float(g_i) - float(f_i)) / float(delta))  for i < min(n, max_order);   f = g, n = min(n + 1, max_order + 1)
+
+A predicting forward, k = s - s_last forwards after it, with c_i = float32(k**i / i!) (ops.taylor_predict):
+
+    p = float(f_0);   p = p + float(f_i) * c_i  for i = 1 .. n - 1        (every operation one fp32 operation)
+
+Default mode hooks what Pyramid Attention Broadcast keeps, the return value y = T(acc + bias) of every block's attn1 and attn2
+out-projection: a computing forward is the uncached forward plus one update launch per (layer, kind, segment); a predicting one
+runs neither attention branch and adds p to the residual stream with the closing GEMM's epilogue arithmetic,
+x = T(fma(p, gate, x)) / x = T(p + x).  Lite mode (`use_lite_mode`) hooks the output head's rows alone: a predicting forward
+runs no embedding, no block and no head, it writes T(p) and unpatchifies.  The decision reads the step counter alone -- no
+device data, no timestep callback.  `cache_log` gets `(context, s, computed)` per forward.  The model asks `_taylor_begin` for
+a forward's decisions and `_taylor_buffer` for a hooked tensor's factor planes; the state's lifetime is Pyramid Attention
+Broadcast's.  Selecting modules by `cache_identifiers` / `skip_predict_identifiers` is not implemented.
 
 The CogVideoX DiT (`PyramidAttentionBroadcastMixin`) takes Pyramid Attention Broadcast alone, with the same rule and state: its one
 attention layer per block, the joint text + video attn1, is the "spatial" kind, and a call's whole batch is one segment under one
@@ -69,8 +96,28 @@ class PyramidAttentionBroadcastConfig:
     current_timestep_callback: Optional[Callable[[], Any]] = None
 
 
+@dataclasses.dataclass
+class TaylorSeerCacheConfig:
+    """diffusers.TaylorSeerCacheConfig: after `disable_cache_before_step` warm-up forwards every `cache_interval`-th forward
+    computes and refreshes the finite-difference factors (up to `max_order` of them, kept in `taylor_factors_dtype`, None = the
+    model dtype); the forwards between extrapolate.  From `disable_cache_after_step` on every forward computes.
+    `use_lite_mode` predicts the model's output rows instead of every attention branch's.  Selection of modules by
+    `skip_predict_identifiers` / `cache_identifiers` is not implemented: anything but None is refused at `enable_cache`."""
+    cache_interval: int = 5
+    disable_cache_before_step: int = 3
+    disable_cache_after_step: Optional[int] = None
+    max_order: int = 1
+    taylor_factors_dtype: Optional[torch.dtype] = None
+    skip_predict_identifiers: Optional[Tuple[str, ...]] = None
+    cache_identifiers: Optional[Tuple[str, ...]] = None
+    use_lite_mode: bool = False
+
+
 # the other configs diffusers' CacheMixin applies: recognised, not implemented here
-_OTHER_DIFFUSERS_CONFIGS = ("FasterCacheConfig", "TaylorSeerCacheConfig", "MagCacheConfig", "TeaCacheConfig")
+_OTHER_DIFFUSERS_CONFIGS = ("FasterCacheConfig", "MagCacheConfig", "TeaCacheConfig")
+_TAYLOR_NAME = "TaylorSeerCacheConfig"
+_TAYLOR_REQUIRED = ("cache_interval", "disable_cache_before_step", "max_order")
+TAYLOR_MAX_ORDER = 3                     # ops.TAYLOR_MAX_PLANES - 1
 
 _PAB_NAME = "PyramidAttentionBroadcastConfig"
 _PAB_RANGES = ("spatial_attention_block_skip_range", "temporal_attention_block_skip_range", "cross_attention_block_skip_range")
@@ -85,6 +132,44 @@ def _is_fbc_config(config):
 
 def _is_pab_config(config):
     return type(config).__name__ == _PAB_NAME and all(hasattr(config, a) for a in _PAB_RANGES + ("current_timestep_callback",))
+
+
+def _is_taylorseer_config(config):
+    return type(config).__name__ == _TAYLOR_NAME and all(hasattr(config, a) for a in _TAYLOR_REQUIRED)
+
+
+def _taylorseer_validate(config):
+    """ValueError for a field outside its range, NotImplementedError for the module selection that is not built"""
+    def whole(name, lo, hi=None, optional=False):
+        v = getattr(config, name, None)
+        if v is None and optional:
+            return
+        if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+            raise ValueError(f"TaylorSeerCacheConfig.{name} = {v!r}: need an integer of at least {lo}"
+                             + (f" and at most {hi}" if hi is not None else "") + (" or None" if optional else ""))
+    whole("cache_interval", 1)
+    whole("disable_cache_before_step", 1)
+    whole("disable_cache_after_step", 0, optional=True)
+    whole("max_order", 0, TAYLOR_MAX_ORDER)
+    fdt = getattr(config, "taylor_factors_dtype", None)
+    if fdt is not None and fdt not in (torch.bfloat16, torch.float16, torch.float32):
+        raise ValueError(f"TaylorSeerCacheConfig.taylor_factors_dtype = {fdt!r}: torch.bfloat16, torch.float16, torch.float32 or "
+                         f"None (the model dtype)")
+    for name in ("skip_predict_identifiers", "cache_identifiers"):
+        if getattr(config, name, None) is not None:
+            raise NotImplementedError(f"TaylorSeerCacheConfig.{name}: selecting modules by identifier is not implemented; the "
+                                      f"hooked tensors are every block's attn1 / attn2 output, or the model's output rows in "
+                                      f"lite mode (pass None)")
+
+
+def taylorseer_decide(s, n_factors, cfg):
+    """True: forward `s` (0-based, per cache context, since the last reset) computes and refreshes the factors; False: it
+    predicts.  A function of the step counter alone.  With W = disable_cache_before_step, N = cache_interval and
+    A = disable_cache_after_step: compute if there is no factor yet, during the warm-up (s < W), on every N-th forward counted
+    from the last warm-up forward ((s - (W - 1)) % N == 0), and from A on."""
+    w, n = int(cfg.disable_cache_before_step), int(cfg.cache_interval)
+    after = getattr(cfg, "disable_cache_after_step", None)
+    return n_factors == 0 or s < w or (s - (w - 1)) % n == 0 or (after is not None and s >= after)
 
 
 def pab_decide(iteration, timestep, has_cache, block_skip_range, timestep_skip_range):
@@ -106,8 +191,9 @@ def decide(sum_abs_diff, sum_abs_prev, numel, dtype, threshold):
 
 class FirstBlockCacheMixin:
     """diffusers' CacheMixin surface (enable_cache / disable_cache / is_cache_enabled / _reset_stateful_cache) for
-    FirstBlockCache and Pyramid Attention Broadcast.  For the first the model calls `_step_cache_segments`, `_step_cache_probe`
-    and `_step_cache_finish` from its forward; for the second `_pab_begin` (once per forward) and `_pab_buffer`.
+    FirstBlockCache, Pyramid Attention Broadcast and TaylorSeer.  For the first the model calls `_step_cache_segments`,
+    `_step_cache_probe` and `_step_cache_finish` from its forward; for the second `_pab_begin` (once per forward) and
+    `_pab_buffer`; for the third `_taylor_begin` and `_taylor_buffer`.
 
     State per cache-context name: the head residual (plus a spare buffer the next probe writes into), the tail residual, and a
     step counter.  `cache_log` holds `(context, step, diff, computed)` for every forward since the last reset (diff None: no
@@ -115,8 +201,12 @@ class FirstBlockCacheMixin:
 
     Pyramid Attention Broadcast: per context and kind a counter, per (kind, layer) a [rows, D] buffer in the model dtype,
     allocated by the first forward that computes; `cache_log` holds `(context, iteration, float(timestep),
-    self_attention_computed, cross_attention_computed)` for every forward and context, with the same lifetime."""
-    _cache_configs_implemented = "FirstBlockCacheConfig and PyramidAttentionBroadcastConfig are"
+    self_attention_computed, cross_attention_computed)` for every forward and context, with the same lifetime.
+
+    TaylorSeer: per context a counter, the number of valid factor planes and the last computing forward, per hooked tensor
+    a [max_order + 1, rows, D] buffer in the factor dtype, allocated by the first forward that computes; `cache_log` holds
+    `(context, step, computed)`, with the same lifetime."""
+    _cache_configs_implemented = "FirstBlockCacheConfig, PyramidAttentionBroadcastConfig and TaylorSeerCacheConfig are"
     _step_cache_config = None
     _step_cache_states = None
     _step_cache_log_fresh = True
@@ -154,6 +244,16 @@ class FirstBlockCacheMixin:
         if name == _PAB_NAME:
             raise NotImplementedError(f"{name}: this object carries the name but not the `*_block_skip_range` and "
                                       f"`current_timestep_callback` attributes of diffusers' config, so it cannot be applied")
+        if _is_taylorseer_config(config):
+            _taylorseer_validate(config)
+            self._taylorseer_refusals(config)
+            self._step_cache_config = config
+            self._reset_stateful_cache()
+            return
+        if name == _TAYLOR_NAME:
+            raise NotImplementedError(f"{name}: this object carries the name but not the `cache_interval`, "
+                                      f"`disable_cache_before_step` and `max_order` attributes of diffusers' config, so it "
+                                      f"cannot be applied")
         if name in _OTHER_DIFFUSERS_CONFIGS or (name.endswith("CacheConfig") and
                                                  type(config).__module__.split(".")[0] == "diffusers"):
             raise NotImplementedError(f"{name} is not implemented on this model; {self._cache_configs_implemented}")
@@ -177,8 +277,8 @@ class FirstBlockCacheMixin:
         """None when no cache is enabled, else [(context, first row, end row)] of the call's [b * n, D] rows: one segment per
         batch element when `contexts` names one context each (the pipeline's CFG-batched call), else one joint segment under
         the current `cache_context`."""
-        if self._step_cache_config is None or self._pab_on:
-            return None                       # (Pyramid Attention Broadcast: the first-block code stays inert)
+        if self._step_cache_config is None or self._pab_on or self._taylor_on:
+            return None                       # (Pyramid Attention Broadcast, TaylorSeer: the first-block code stays inert)
         return self._context_segments(b, n, contexts)
 
     def _context_segments(self, b, n, contexts):
@@ -261,7 +361,7 @@ class FirstBlockCacheMixin:
         if self._step_cache_states is None:
             self._step_cache_states = {}
         hooked = {kind: getattr(cfg, rng) is not None for kind, rng, _ in PAB_KINDS}
-        plan = SimpleNamespace(segs=[], hooked=hooked, timestep=t)
+        plan = SimpleNamespace(segs=[], hooked=hooked, timestep=t, taylor=None)
         for name, r0, r1 in segs:
             key = (r1 - r0, d, dtype, str(device))
             st = self._step_cache_states.get(name)
@@ -293,6 +393,69 @@ class FirstBlockCacheMixin:
             buf = seg.state.buffers[(kind, layer)] = torch.empty((seg.r1 - seg.r0, d), dtype=dtype, device=device)
         return buf
 
+    # ---------------------------------------------------------------- TaylorSeer
+    @property
+    def _taylor_on(self):
+        return self._step_cache_config is not None and _is_taylorseer_config(self._step_cache_config)
+
+    @property
+    def _taylor_lite(self):
+        return self._taylor_on and bool(getattr(self._step_cache_config, "use_lite_mode", False))
+
+    def _taylorseer_refusals(self, config):
+        """what the model cannot combine with TaylorSeer, raised by `enable_cache` (the model overrides this)"""
+
+    def _taylor_begin(self, b, n, d, dtype, device, contexts=None):
+        """The decisions of one forward under TaylorSeer, taken before anything is launched: None when it is off, else a plan
+        shaped like `_pab_begin`'s -- `.segs` = one entry per row segment with `.name`, `.r0`, `.r1`, `.state`,
+        `.compute[kind]` (both kinds decide alike) -- plus, per segment, `.s` (this forward's number), `.k` (its distance to
+        the last computing forward: the `delta` of an update, the offset of a prediction) and `.n_old` / `.n_new` (the valid
+        factor planes before and after a computing forward; a predicting one reads `.n_old`).  `d` / `dtype`: width and dtype
+        of the hooked rows (lite mode: the output head's).  Advances every context's counter, moves `n` and `s_last` of a
+        computing context on, and appends `(context, s, computed)` to `cache_log`.  A context whose rows, width, dtype or
+        device changed starts over."""
+        if not self._taylor_on:
+            return None
+        cfg = self._step_cache_config
+        segs = self._context_segments(b, n, contexts)
+        if self._step_cache_log_fresh or not isinstance(self.cache_log, list):
+            self.cache_log = []
+            self._step_cache_log_fresh = False
+        if self._step_cache_states is None:
+            self._step_cache_states = {}
+        planes = int(cfg.max_order) + 1
+        fdt = getattr(cfg, "taylor_factors_dtype", None) or dtype
+        plan = SimpleNamespace(segs=[], hooked={"self": True, "cross": True}, taylor=cfg, planes=planes, factor_dtype=fdt,
+                               lite=self._taylor_lite)
+        for name, r0, r1 in segs:
+            key = (r1 - r0, d, dtype, str(device))
+            st = self._step_cache_states.get(name)
+            if st is None or st.key != key:
+                st = self._step_cache_states[name] = SimpleNamespace(key=key, steps=0, n=0, s_last=None, buffers={})
+            s = st.steps
+            compute = bool(taylorseer_decide(s, st.n, cfg))
+            k = 0 if st.s_last is None else s - st.s_last
+            seg = SimpleNamespace(name=name, r0=r0, r1=r1, state=st, compute={"self": compute, "cross": compute}, s=s, k=k,
+                                  n_old=st.n, n_new=min(st.n + 1, planes) if compute else st.n)
+            self.cache_log.append((name, s, compute))
+            st.steps += 1
+            if compute:
+                st.n, st.s_last = seg.n_new, s
+            plan.segs.append(seg)
+        return plan
+
+    @staticmethod
+    def _taylor_buffer(plan, seg, key, d=None, device=None):
+        """the factor planes of hooked tensor `key` ((kind, layer), or "out" in lite mode) under the segment's context:
+        [max_order + 1, rows, D] in the factor dtype, allocated by the first forward that computes (pass d / device); a
+        predicting step finds them there (KeyError: it never computed)"""
+        buf = seg.state.buffers.get(key)
+        if buf is None:
+            if d is None:
+                raise KeyError(f"TaylorSeer: no factors of {key!r} under context {seg.name!r}")
+            buf = seg.state.buffers[key] = torch.empty((plan.planes, seg.r1 - seg.r0, d), dtype=plan.factor_dtype, device=device)
+        return buf
+
 
 class PyramidAttentionBroadcastMixin(FirstBlockCacheMixin):
     """The same surface for a model that implements Pyramid Attention Broadcast alone (CogVideoXTransformer3DModel), plus
@@ -315,6 +478,8 @@ class PyramidAttentionBroadcastMixin(FirstBlockCacheMixin):
         if not self.is_cache_enabled and _is_fbc_config(config):
             raise NotImplementedError(f"FirstBlockCacheConfig is not implemented on {type(self).__name__}; "
                                       f"{self._cache_configs_implemented}")
+        if not self.is_cache_enabled and type(config).__name__ == _TAYLOR_NAME:       # with or without its attributes
+            raise NotImplementedError(f"{_TAYLOR_NAME} is not implemented on this model; {self._cache_configs_implemented}")
         super().enable_cache(config)
         if self._pab_on and config.spatial_attention_block_skip_range is None:
             warnings.warn(f"Pyramid Attention Broadcast: `spatial_attention_block_skip_range` is None and the temporal / cross "

@@ -291,6 +291,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         if self._pab_on:
             raise NotImplementedError(f"{what} with Pyramid Attention Broadcast: not implemented in this version (first-block "
                                       f"caching is)")
+        if self._taylor_on:
+            raise NotImplementedError(f"{what} with TaylorSeer caching: not implemented in this version (first-block caching is)")
         if shard is not None and getattr(shard, "active", True):
             raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
         if not default_procs:
@@ -306,6 +308,28 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             raise NotImplementedError("Pyramid Attention Broadcast with window attention (enable_window_attention): not "
                                       "implemented in this version (first-block caching is)")
         return super().enable_cache(config)
+
+    def _taylorseer_refusals(self, config):
+        """what TaylorSeer does not combine with, at `enable_cache` (the other order is refused where the other feature is
+        enabled, or by the forward before its first launch: `_window_refusals`, `_sparse_refusals`, `_bind`)"""
+        what = "TaylorSeer caching (TaylorSeerCacheConfig)"
+        if self._window is not None:
+            raise NotImplementedError(f"{what} with window attention (enable_window_attention): not implemented in this version "
+                                      f"(first-block caching is)")
+        if self._sparse is not None:
+            raise NotImplementedError(f"{what} with sparse attention (enable_sparse_attention): not implemented in this version "
+                                      f"(first-block caching is)")
+        if self.parallel is not None and getattr(self.parallel, "active", True):
+            raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
+        if not getattr(config, "use_lite_mode", False) and not self._default_processors():
+            raise NotImplementedError(f"{what} with a user-installed attention processor: the attention branches are predicted on "
+                                      f"the built-in MI355WanAttnProcessor path only (lite mode, `use_lite_mode=True`, predicts "
+                                      f"the model's output and takes any processor)")
+
+    def disable_cache(self):
+        super().disable_cache()
+        for ws in self._ws.values():          # TaylorSeer's [n, D] scratch for a computed branch's y
+            ws.taylor_y = None
 
     def _workspace(self, L, dtype, device):
         # one workspace per (shape, cache_context name): the two CFG branches may run concurrently on two streams
@@ -466,11 +490,11 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self-attention as keys and values: their q projection's use, attention queries, out-projection, text branch, FFN and
         output head are skipped, and their part of the returned tensor is ZERO.  Every kept row is computed exactly as without it.
         A bare `transformer(...)` call (None) keeps the full output.
-        `_cache_contexts` (private; a step cache enabled -- first-block caching or Pyramid Attention Broadcast): one
+        `_cache_contexts` (private; a step cache enabled -- first-block caching, Pyramid Attention Broadcast or TaylorSeer): one
         cache-context name per batch element, each element then decided on its own as if called alone under that context -- the
         pipeline's CFG-batched call passes ("cond", "uncond").  Without it a batch-B call under one `cache_context` makes one
         joint decision, as diffusers does (first-block caching: over the means of all its rows; Pyramid Attention Broadcast:
-        one counter and one [B * L, D] buffer per layer and kind for the whole batch).
+        one counter and one [B * L, D] buffer per layer and kind for the whole batch; TaylorSeer likewise, with its factor planes).
         `id_frames` (window and sparse attention only, `enable_window_attention` / `enable_sparse_attention`): the trailing latent frames that are identity-reference
         frames -- every query sees them, like the configured sink frames."""
         gen = self.forward_steps(hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image,
@@ -500,6 +524,9 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._mx_requantise_if_pending()
         c = self._bind(hidden_states, timestep, encoder_hidden_states, attention_kwargs, timestep_rows, shard, live_rows,
                        _cache_contexts, id_frames)
+        if c.lite is not None and not any(seg.compute["self"] for seg in c.lite.segs):
+            out = self._taylor_lite_rows(c, c.ws.po[:c.nr])                       # TaylorSeer, lite mode: the output rows predicted
+            return (out,) if not return_dict else SimpleNamespace(sample=out)
         self._embed(c, hidden_states)
         yield
 
@@ -588,13 +615,29 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             lo, n, lpad = sh.rows(L)              # first row, valid rows, padded shard length (equal on all ranks)
             cos1, sin1 = cos1[lo:lo + n].contiguous(), sin1[lo:lo + n].contiguous()
             if self.is_cache_enabled:
-                raise NotImplementedError("first-block caching and Pyramid Attention Broadcast run on one GPU: a token-sharded "
-                                          "forward cannot take the cache")
+                raise NotImplementedError("first-block caching, Pyramid Attention Broadcast and TaylorSeer caching run on one "
+                                          "GPU: a token-sharded forward cannot take the cache")
             if sh.gemm_tile_m:
                 tk = {"tile_m": sh.tile_m_for(n)}
         fbc = self._step_cache_segments(b, n, cache_contexts)      # None: no cache (nothing extra allocated or launched)
         # Pyramid Attention Broadcast: this forward's decisions (the timestep callback is read here, once, before any launch)
         pab = self._pab_begin(b, n, d, dt, dev, cache_contexts)
+        # TaylorSeer: this forward's decisions, from the step counters alone.  Default mode drives the attention branches through
+        # the same route as Pyramid Attention Broadcast (`pab`); lite mode sits around the block stack (`lite`)
+        lite = None
+        if self._taylor_on:
+            if not self._taylor_lite and not default_procs:
+                raise NotImplementedError("TaylorSeer caching (TaylorSeerCacheConfig) with a user-installed attention processor: "
+                                          "the attention branches are predicted on the built-in MI355WanAttnProcessor path only")
+            po_dim = cfg.out_channels * math.prod(cfg.patch_size)
+            if self._taylor_lite:
+                lite = self._taylor_begin(b, n, po_dim, dt, dev, cache_contexts)
+                if not any(seg.compute["self"] for seg in lite.segs):
+                    # every segment predicts: no embedding, no block, no head -- the call needs its geometry and the output rows
+                    return _Call(b=b, n=n, nr=b * n, L=L, nf=nf, hh=hh, ww=ww, d=d, dev=dev, dt=dt, sh=None,
+                                 ws=self._workspace(b * lpad, dt, dev), lite=lite, live=None, segs=[(0, b * n)])
+            else:
+                pab = self._taylor_begin(b, n, d, dt, dev, cache_contexts)
         # Batch elements are extra ROWS of the token-major buffers ([B*n, D]): every GEMM / norm is one launch over
         # both CFG branches (twice the tiles per launch, weights read once); attention and RoPE index rows per batch.
         nr = b * n
@@ -630,7 +673,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         live = None
         # (not under Pyramid Attention Broadcast: a cached branch output covers every row, so that any later step may use it)
         if (live_rows is not None and self.skip_dead_rows and default_procs and sh is None and len(self.blocks) > 1
-                and not self._fp8 and not fp8 and pab is None):
+                and not self._fp8 and not fp8 and pab is None and lite is None):
             l0, l1 = int(live_rows[0]), int(live_rows[1])
             if 0 <= l0 < l1 <= n and (l1 - l0) < n:
                 live = (l0, l1)
@@ -642,7 +685,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                      text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
                      afold={"scale": o.SCALE_FOLDED} if fold else {}, fp8=fp8, default_procs=default_procs,
                      shared=shared, fbc=fbc, pab=pab, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
-                     live=live, win=win, sp=sp,
+                     live=live, win=win, sp=sp, lite=lite,
                      live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
                      rows=(0, n),            # the rows of every batch element that run as queries / per-token rows ...
                      segs=[(0, nr)])         # ... and the global row ranges the per-token operations of a block run on
@@ -896,7 +939,10 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         Re-use: none of the branch runs; one launch adds the cached y to the residual stream with the closing GEMM's epilogue
         arithmetic (`_pab_reuse`).  A kind that is not hooked runs as without the cache.  The elements of a batch (the CFG
         branches of a batched call: one context and one buffer each, and counters that may differ) take a hooked branch one
-        by one, each on a one-element view of the call: per row the launches compute what the batched ones do."""
+        by one, each on a one-element view of the call: per row the launches compute what the batched ones do.
+        TaylorSeer in default mode (`pab.taylor`: its plan has the same shape, both kinds hooked and decided alike) takes the
+        same route: a computing branch keeps y in the workspace's one [n, D] scratch and `ops.taylor_update` folds it into the
+        factors of (kind, layer); a predicting one is `_taylor_predict`."""
         pab, n = c.pab, c.n
         stages = (("self", lambda cc: self._self_attention(cc, li, blk, e, m) or self._self_attention_out(cc, li, blk, m)),
                   ("cross", lambda cc: self._cross_attention(cc, li, blk)))
@@ -909,14 +955,21 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                 # context -- one decision, one [b * n, D] buffer, of which the element takes its rows
                 seg = next(s_ for s_ in pab.segs if s_.r0 <= i * n < s_.r1)
                 if not seg.compute[kind]:
-                    self._pab_reuse(c, kind, seg, i, li, m)
+                    (self._pab_reuse if pab.taylor is None else self._taylor_predict)(c, kind, seg, i, li, m)
                     continue
                 cc = c if c.b == 1 else c.element(i)
-                cc.keep = {(0, n): self._pab_buffer(seg, kind, li, c.d, c.dt, c.dev)[i * n - seg.r0:(i + 1) * n - seg.r0]}
+                if pab.taylor is None:
+                    y = self._pab_buffer(seg, kind, li, c.d, c.dt, c.dev)[i * n - seg.r0:(i + 1) * n - seg.r0]
+                else:
+                    y = self._taylor_scratch(c)
+                cc.keep = {(0, n): y}
                 try:
                     run(cc)
                 finally:
                     cc.keep = None
+                if pab.taylor is not None:                # the branch's y -> the factors of (kind, layer) under the segment
+                    f = self._taylor_buffer(pab, seg, (kind, li), c.d, c.dev)[:, i * n - seg.r0:(i + 1) * n - seg.r0]
+                    self.ops.taylor_update(y, f, seg.n_old, seg.k, seg.n_new)
 
     def _pab_reuse(self, c, kind, seg, i, li, m):
         """x += gate * y (self-attention) / x += y (cross-attention) on batch element i from the cached y, bit for bit what
@@ -926,6 +979,35 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         y, x = self._pab_buffer(seg, kind, li)[r0 - seg.r0:r1 - seg.r0], c.x[r0:r1]
         gate, sel = (m[:, 2], _sel_rows(c.sel, r0, r1)) if kind == "self" else (None, None)
         (o.pab_broadcast if c.default_procs else o.gated_residual)(x, y, gate, sel, out=x)
+
+    # ------------------------------------------------------------------ forward: TaylorSeer
+    def _taylor_scratch(self, c):
+        """the one [n, D] buffer of the workspace a computed branch's y = T(acc + bias) is kept in (`keep=` of its closing
+        GEMM) until the update launch that follows has read it"""
+        ws = c.ws
+        if getattr(ws, "taylor_y", None) is None:
+            ws.taylor_y = torch.empty((c.n, c.d), dtype=c.dt, device=c.dev)
+        return ws.taylor_y
+
+    def _taylor_predict(self, c, kind, seg, i, li, m):
+        """x += gate * p (self-attention) / x += p (cross-attention) on batch element i, p the Taylor extrapolation of the
+        branch's y from its factors: one launch with the closing GEMM's epilogue arithmetic, none of the branch runs"""
+        r0, r1 = i * c.n, (i + 1) * c.n
+        f, x = self._taylor_buffer(c.pab, seg, (kind, li))[:, r0 - seg.r0:r1 - seg.r0], c.x[r0:r1]
+        gate, sel = (m[:, 2], _sel_rows(c.sel, r0, r1)) if kind == "self" else (None, None)
+        self.ops.taylor_predict(f, seg.n_old, seg.k, x, gate, sel, out=x)
+
+    def _taylor_lite_rows(self, c, po):
+        """TaylorSeer in lite mode on the output head's rows `po` [b * n, C_out * prod(patch)]: a computing segment's rows
+        update its factors, a predicting segment's rows are overwritten by T(p); then unpatchify"""
+        o, lite = self.ops, c.lite
+        for seg in lite.segs:
+            if seg.compute["self"]:
+                o.taylor_update(po[seg.r0:seg.r1], self._taylor_buffer(lite, seg, "out", po.shape[1], c.dev), seg.n_old, seg.k,
+                                seg.n_new)
+            else:
+                o.taylor_predict(self._taylor_buffer(lite, seg, "out"), seg.n_old, seg.k, out=po[seg.r0:seg.r1])
+        return self._unpatchify(c, po)
 
     def _ffn(self, c, li, blk, m):
         """feed-forward (:344-348)"""
@@ -945,7 +1027,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
 
     def _output_head(self, c):
         """output head (:519-543): modulated norm, proj_out, unpatchify -> [b, C_out, F, H, W]"""
-        o, cfg, nrm, sh = self.ops, self.config, c.nrm, c.sh
+        o, nrm, sh = self.ops, c.nrm, c.sh
         for r0, r1 in c.segs:
             o.adaln_modulate(c.x[r0:r1], c.head[:, 0], c.head[:, 1], _sel_rows(c.sel, r0, r1), c.eps, out=nrm[r0:r1])
         if sh is None:
@@ -958,6 +1040,12 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             po_loc = sh.out_local(c.lpad, c.ws.po.shape[1], c.dt, c.dev)
             o.gemm(nrm, self.proj_out.weight, self.proj_out.bias, out=po_loc[:c.n], **c.tk)
             po = sh.all_gather_out(po_loc)[:c.L]
+        if c.lite is not None:
+            return self._taylor_lite_rows(c, po)
+        return self._unpatchify(c, po)
+
+    def _unpatchify(self, c, po):
+        o, cfg = self.ops, self.config
         unpatch = lambda rows: o.unpatchify(rows, cfg.out_channels, c.nf, c.hh, c.ww, cfg.patch_size)      # noqa: E731
         if c.b == 1:
             return unpatch(po)[None]
@@ -970,12 +1058,14 @@ class _Call:
     the token shard, views of the workspace, tables and the switches that pick a path.  References and views only: nothing on
     the device the call would not hold anyway.  `rows` / `segs` (set for the last block under `live_rows`), `h0` / `h1c`
     (the first-block cache's buffers, set by the embedding stage) and `keep` around a branch that Pyramid Attention
-    Broadcast computes ({(first row, end row): the buffer that also receives the closing GEMM's y}; `elements`: the one-element
-    views it runs a batch through) are the only fields written after `_bind`."""
+    Broadcast or TaylorSeer computes ({(first row, end row): the buffer that also receives the closing GEMM's y}; `elements`:
+    the one-element views it runs a batch through) are the only fields written after `_bind`.  `pab`: the plan of Pyramid
+    Attention Broadcast or of TaylorSeer's default mode; `lite`: the plan of TaylorSeer's lite mode -- when every segment of it
+    predicts, `_bind` returns a call with the geometry, the workspace and the plan alone."""
     __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
                  "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
                  "afold", "fp8", "default_procs", "shared", "fbc", "pab", "keep", "h0", "h1c", "attention_kwargs", "live",
-                 "live_segs", "rows", "segs", "win", "sp", "elements")
+                 "live_segs", "rows", "segs", "win", "sp", "lite", "elements")
 
     def __init__(self, **fields):
         self.elements = None

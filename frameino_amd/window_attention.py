@@ -425,6 +425,8 @@ class SelfAttentionOptionsMixin:
         if getattr(self, "_pab_on", False):
             raise NotImplementedError(f"{what} with Pyramid Attention Broadcast: not implemented in this version (first-block "
                                       f"caching is)")
+        if getattr(self, "_taylor_on", False):
+            raise NotImplementedError(f"{what} with TaylorSeer caching: not implemented in this version (first-block caching is)")
         if shard is not None and getattr(shard, "active", True):
             raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
         if not default_procs:

@@ -701,6 +701,34 @@ int fino_step_cache_residual(const void* a, int64_t lda, const void* b, int64_t 
  * 16-byte aligned rows, bf16 | fp16; out may alias x. */
 int fino_pab_broadcast(const void* x, int64_t ldx, const void* y, int64_t ldy, void* out, int64_t ldo, int64_t rows,
                        int64_t dim, const float* gate, int64_t mod_stride, const int32_t* sel, int dtype, void* stream);
+/* TaylorSeer (diffusers' hooks/taylorseer_cache.py; frameino_amd/step_cache.py): a hooked tensor y [rows, dim] of dtype T is
+ * followed along the step axis by its finite-difference factors f_0 .. f_{n-1}, planes of one buffer (plane i at
+ * factors + i * plane_stride elements, rows of ldf elements, dtype F = fdtype: FINO_BF16 | FINO_F16 | FINO_F32).
+ *
+ * fino_taylor_update, on a step that computed y, `delta` steps after the last one that did (in place; a thread reads every old
+ * plane of its elements before it writes any):
+ *   g_0     = F(y)
+ *   g_{i+1} = F((float(g_i) - float(f_i)) / float(delta))        for i + 1 < n_new   (n_new <= n_old + 1: only valid planes are read)
+ *   f_i     = g_i                                                 for i < n_new; planes at and beyond n_new are not touched
+ * Every subtraction and every division is one IEEE fp32 operation, every factor is rounded to F once and the rounded value
+ * feeds the next order.  n_new = 1 (the first update) stores F(y) alone and ignores delta.
+ *
+ * fino_taylor_predict, k steps after the last update, with the HOST array coef[i] = float(k^i / i!) of n entries (read during
+ * the call; coef[0] is not used: it is 1):
+ *   p   = float(f_0);   p = p + float(f_i) * coef[i]   for i = 1 .. n - 1 in that order, the product and the sum each rounded to fp32
+ *   out = T(p)                                          x == NULL (gate must be NULL too)
+ *   out = T(float(x) + p)                               gate == NULL
+ *   out = T(fma(p, gate[sel[row]], float(x)))           gate / mod_stride / sel as in fino_pab_broadcast
+ * With n = 1 and F = T the last two are fino_pab_broadcast on y = f_0 bit for bit.  out may alias x.
+ *
+ * Both: T = dtype FINO_BF16 | FINO_F16; dim a multiple of 8; every operand row-strided with 16-byte aligned rows; planes must
+ * not overlap (plane_stride >= (rows - 1) * ldf + dim, a multiple of 16 bytes).  HBM-bound: 16-byte loads and stores, no atomics. */
+enum { FINO_TAYLOR_MAX_PLANES = 4 };
+int fino_taylor_update(const void* y, int64_t ldy, void* factors, int64_t plane_stride, int64_t ldf, int64_t rows, int64_t dim,
+                       int n_old, int n_new, int delta, int dtype, int fdtype, void* stream);
+int fino_taylor_predict(const void* factors, int64_t plane_stride, int64_t ldf, int n, const float* coef, const void* x,
+                        int64_t ldx, void* out, int64_t ldo, int64_t rows, int64_t dim, const float* gate, int64_t mod_stride,
+                        const int32_t* sel, int dtype, int fdtype, void* stream);
 
 /* ---- diagnostics (tools/ only) --------------------------------------------------------------------------------
  * Dense MFMA rate with nothing else running: `iters` x 16 independent 32x32x16 (kind 0) / 32 independent 16x16x32
