@@ -79,8 +79,8 @@ def main():
     ap.add_argument("--sparse-attention", type=float, default=None, metavar="TAU",
                     help="dynamic block-sparse self-attention (approximate; quality on real checkpoints unmeasured): per head and "
                          "q-block only the key tiles that a pooled predictor credits with a share TAU of the softmax mass, e.g. "
-                         "0.9, plus the own frame, the first frame and the ID frame.  Not together with --window-frames, --pab "
-                         "or --fp8-attention")
+                         "0.9, plus the own frame, the first frame and the ID frame.  Combines with --fp8-attention (the fp8 tile "
+                         "walk, head_dim 128).  Not together with --window-frames or --pab")
     ap.add_argument("--sparse-window-frames", type=int, default=0, metavar="N",
                     help="with --sparse-attention: the own frame +- N neighbours are always kept (default 0)")
     ap.add_argument("--sparse-similarity", type=float, default=None, metavar="THETA",
@@ -89,14 +89,16 @@ def main():
     ap.add_argument("--sparse-calibrate", default=None, metavar="OUT.json",
                     help="with --sparse-attention: before the clip, run a short dense clip that measures, per layer and head, the "
                          "smallest threshold of a grid whose sparse output stays within --sparse-l1 of the dense one; write the "
-                         "thresholds to OUT.json and use them")
+                         "thresholds to OUT.json and use them (measured in the DiT's dtype: --fp8-attention is switched on "
+                         "after the calibration)")
     ap.add_argument("--sparse-l1", type=float, default=0.05, metavar="X",
                     help="with --sparse-calibrate: the relative L1 error bound per layer and head (default 0.05)")
     ap.add_argument("--sparse-thresholds", default=None, metavar="FILE",
                     help="sparse attention with the configuration and per-head thresholds of FILE (written by --sparse-calibrate); "
                          "instead of --sparse-attention")
     ap.add_argument("--fp8-attention", action="store_true",
-                    help="fp8 (e4m3) operands in the 3-D self-attention (reduced precision, opt-in).  Not together with --window-frames")
+                    help="fp8 (e4m3) operands in the 3-D self-attention (reduced precision, opt-in).  Combines with --sparse-attention; not "
+                         "together with --window-frames")
     ap.add_argument("--smooth-k", action="store_true",
                     help="with --fp8-attention: subtract the key mean before K is quantised (exact for the softmax)")
     ap.add_argument("--smooth-v", action="store_true",
@@ -217,6 +219,8 @@ def main():
         kw["attention_kwargs"] = {"scale": a.lora_scale}
     if a.sparse_calibrate is not None:             # a short dense clip that measures the thresholds on this model's own weights
         from frameino_amd.sparse_calibration import calibrate_sparse_attention, save_sparse_thresholds
+        if a.fp8_attention:                        # thresholds are calibrated in bf16 / fp16 and loaded
+            transformer.enable_fp8_attention(False)
         sparse_cfg, report = calibrate_sparse_attention(
             transformer, lambda: pipe(image=canvas, traj_tensor=traj, ID_tensor=id_tensor, height=a.height, width=a.width,
                                       num_frames=a.frames, num_inference_steps=min(a.steps, 4), guidance_scale=a.guidance,
@@ -228,6 +232,8 @@ def main():
               f"{sum(t >= 1.0 for t in flat)} stay dense, mean threshold of the others "
               f"{sum(t for t in flat if t < 1.0) / max(1, sum(t < 1.0 for t in flat)):.3f}")
         transformer.enable_sparse_attention(sparse_cfg)
+        if a.fp8_attention:
+            transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v)
     torch.cuda.synchronize()
     tc = time.perf_counter()
     for rep in range(a.repeat):

@@ -76,6 +76,10 @@ SIGNATURES = {
     "fino_attn_fp8_smoothed_kv_bytes": [c_int, c_int, c_i64, c_int, c_int],
     "fino_attn_fwd_fp8_smoothed": [c_void_p] * 4 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 8 + [c_float, c_int, c_int,
                                                                                                     c_void_p, c_i64, c_void_p, c_int],
+    "fino_attn_fp8_tiles_supported": [c_int, c_int, c_i64, c_i64, c_int],
+    "fino_attn_fwd_fp8_tiles": [c_void_p] * 4 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 8 + [c_float, c_int, c_int,
+                                                                                                 c_void_p, c_i64, c_int, c_void_p,
+                                                                                                 c_i64, c_i64, c_int, c_void_p],
     "fino_attn_partial_bytes": [c_int, c_int, c_i64, c_int],
     "fino_attn_partial": [c_void_p] * 3 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 9 + [c_float, c_int, c_void_p,
                                                                                                c_i64, c_void_p],

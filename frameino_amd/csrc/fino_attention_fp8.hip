@@ -1035,9 +1035,19 @@ constexpr int kRing128 = 8;
 constexpr int kTile128 = 2 * kTileK8;                        // K8 lo | K8 hi (and V8T lo | V8T hi) of one key tile: 8 KiB
 constexpr int kL128K = 0, kL128V = kRing128 * kTile128, kL128KS = 2 * kRing128 * kTile128, kL128VS = kL128KS + kRing128 * 256;
 constexpr int kSmem128 = kL128VS + kRing128 * 256;           // 132 KiB
+// TL (fino_attn_fwd_fp8_tiles; whole blocks only): the block walks the key tiles whose bits are set in its row of tm.mask, the
+// mask of fino_attn_fwd_tiles.  The row is expanded ONCE, before the prologue, into a list g(0 .. nt - 1) of ascending global tile
+// indices in LDS behind the rings and the kMuSlot (as attn_ppd_kernel VAR 3 does).  Contract of attn_fp8_fr_kernel's RG: the loop
+// index is local, ring slots and the hand-counted vmcnt waits go by it, only the DMA's tile offset and the ragged-key mask see
+// g(t); a look-ahead past nt re-reads the last tile walked; the buffer resources span the head's whole images (ntall tiles) and
+// bits at or beyond ntall are dropped, so whatever the mask holds no DMA leaves them.  nt = 0: zeros, before any ring is touched.
+// TL = false is the code it was: `tm` is not read.
+constexpr int kL128List = kSmem128 + kMuSlot;                // uint32 list, VAR 3's size (the pad is unused: the look-ahead clamps)
+constexpr int kSmem128Tiles = kL128List + (kAttnMaxTiles + kAttnTileListPad) * 4;
+static_assert(kSmem128Tiles <= 160 * 1024, "rings + mean slot + tile list must fit the CU's 160 KiB of LDS");
 
-template <typename T, int PX>
-__global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8AttnParams fp) {
+template <typename T, int PX, bool TL = false>
+__global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8AttnParams fp, const AttnTileMask tm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const AttnParams& p = fp.a;
     typedef typename T::vec8 vec8;
@@ -1077,8 +1087,41 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
     const int head = hb - bi * p.heads;
     const uint16_t* qp = p.q + bi * p.q_bs + head * p.q_hs;
     uint16_t* op = p.o + bi * p.o_bs + head * p.o_hs;
-    const int nt = t_end - t_begin;
-    const int lk = (t_end * kKV < p.lk ? t_end * kKV : p.lk) - t_begin * kKV;     // keys of this range, re-based to 0
+    int tl_nt = 0, tl_rag = -1;           // TL: tiles walked; the local index of the ragged global tile ntall - 1 (-1: not walked)
+    if constexpr (TL) {
+        const uint32_t* mrow = tm.mask + bi * tm.bs + head * tm.hs + (int64_t)qb * tm.words;
+        const int nw = (ntall + 31) >> 5;
+        uint32_t* list = reinterpret_cast<uint32_t*>(smem + kL128List);
+        // the clipped word wi: bits at or beyond ntall dropped
+        auto word = [&](int wi) -> uint32_t {
+            const int left = ntall - 32 * wi;
+            const uint32_t m = left >= 32 ? 0xffffffffu : ((1u << left) - 1u);
+            return mrow[wi] & m;
+        };
+        int total = 0;
+        for (int wi = 0; wi < nw; ++wi) total += __builtin_popcount(word(wi));
+        tl_nt = __builtin_amdgcn_readfirstlane(total);
+        if (tl_nt == 0) {
+            // an empty row: zeros for the block's rows (not the value mean), nothing staged
+            for (int i = tid; i < kQBlock * 16; i += kWaves * 64) {
+                const int qr = qb * kQBlock + (i >> 4);
+                if (qr < p.lq) *reinterpret_cast<uint4*>(op + (int64_t)qr * p.o_rs + (i & 15) * 8) = make_uint4(0u, 0u, 0u, 0u);
+            }
+            return;
+        }
+        for (int tl = tid; tl < ntall; tl += kWaves * 64) {
+            const int wi = tl >> 5;
+            int before = 0;
+            for (int j = 0; j < wi; ++j) before += __builtin_popcount(word(j));
+            const uint32_t wd = word(wi);
+            if ((wd >> (tl & 31)) & 1u) list[before + __builtin_popcount(wd & ((1u << (tl & 31)) - 1u))] = (uint32_t)tl;
+        }
+        // the ragged tile is the LAST global tile; set bits ascend, so it can only be the last tile walked
+        if ((p.lk & (kKV - 1)) && ((word((ntall - 1) >> 5) >> ((ntall - 1) & 31)) & 1u)) tl_rag = tl_nt - 1;
+        __syncthreads();
+    }
+    const int nt = TL ? tl_nt : t_end - t_begin;
+    const int lk = (t_end * kKV < p.lk ? t_end * kKV : p.lk) - t_begin * kKV;     // keys of this range, re-based to 0 (TL: all of them)
     const int64_t img0 = (int64_t)hb * 2 * ntall + t_begin;  // first tile of sub-head 0; sub-head 1: + ntall
 
     const int qrow = qb * kQBlock + wave * kQRowsPerWave + r;
@@ -1093,18 +1136,25 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
     const bool st_k = wl < 2;
     const uint8_t* timg = st_k ? fp.k8 : fp.v8t;
     const uint8_t* simg = st_k ? fp.ks : fp.vs;
-    const __amdgpu_buffer_rsrc_t st_r0 = __builtin_amdgcn_make_buffer_rsrc((void*)(timg + img0 * kTileK8), 0, nt * kTileK8, 0x00020000);
-    const __amdgpu_buffer_rsrc_t st_r1 = __builtin_amdgcn_make_buffer_rsrc((void*)(timg + (img0 + ntall) * kTileK8), 0, nt * kTileK8, 0x00020000);
-    const __amdgpu_buffer_rsrc_t st_s0 = __builtin_amdgcn_make_buffer_rsrc((void*)(simg + img0 * 128), 0, nt * 128, 0x00020000);
-    const __amdgpu_buffer_rsrc_t st_s1 = __builtin_amdgcn_make_buffer_rsrc((void*)(simg + (img0 + ntall) * 128), 0, nt * 128, 0x00020000);
+    const int st_nt = TL ? ntall : nt;                        // tiles the resources span (TL: the whole images, whatever is walked)
+    const __amdgpu_buffer_rsrc_t st_r0 = __builtin_amdgcn_make_buffer_rsrc((void*)(timg + img0 * kTileK8), 0, st_nt * kTileK8, 0x00020000);
+    const __amdgpu_buffer_rsrc_t st_r1 = __builtin_amdgcn_make_buffer_rsrc((void*)(timg + (img0 + ntall) * kTileK8), 0, st_nt * kTileK8, 0x00020000);
+    const __amdgpu_buffer_rsrc_t st_s0 = __builtin_amdgcn_make_buffer_rsrc((void*)(simg + img0 * 128), 0, st_nt * 128, 0x00020000);
+    const __amdgpu_buffer_rsrc_t st_s1 = __builtin_amdgcn_make_buffer_rsrc((void*)(simg + (img0 + ntall) * 128), 0, st_nt * 128, 0x00020000);
     const int st_pos = grp * 128 + (wl & 1) * 64 + lane;
     const uint32_t st_voff = (uint32_t)((st_pos >> 2) * 64 + (((st_pos & 3) ^ swz8(st_pos >> 2)) << 4));
     const uint32_t st_svoff = (uint32_t)((grp * 16 + (lane & 15)) * 4);
     const int st_lds = (st_k ? kL128K : kL128V) + (grp * 128 + (wl & 1) * 64) * 16;
     const int st_slds = (st_k ? kL128KS : kL128VS) + grp * 64;
-#define D8_DMA(U_)                                                                                           \
+    // TL: the global tile of local tile U_ -- one wave-uniform read of the list (D8_GLOAD), then v_readfirstlane.  The prologue
+    // reads g(0 .. 4) on the spot; the loop has g(t + 4) in tl_g already and reads g(t + 5) behind its DMAs, a whole softmax phase
+    // ahead of the v_readfirstlane at the top of the matrix phase (behind the phase's own lgkmcnt(0)): no wait in front of a DMA
+#define D8_CLAMP(U_) ((U_) < nt ? (U_) : nt - 1)
+#define D8_GLOAD(U_) reinterpret_cast<const uint32_t*>(smem + kL128List)[D8_CLAMP(U_)]
+#define D8_DMA(U_) D8_DMA_T(U_, TL ? __builtin_amdgcn_readfirstlane((int)D8_GLOAD(U_)) : D8_CLAMP(U_))
+#define D8_DMA_T(U_, TT_)                                                                                    \
     {                                                                                                        \
-        const int tt_ = (U_) < nt ? (U_) : nt - 1;                                                           \
+        const int tt_ = (TT_);                                                                               \
         const int sl_ = (U_) & (kRing128 - 1);                                                               \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(st_r0, (FINO_LDS void*)(smem + st_lds + sl_ * kTile128), 16, st_voff, \
                                                  tt_ * kTileK8, 0, 0);                                       \
@@ -1122,6 +1172,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
     { D8_DMA(1) }
     { D8_DMA(2) }
     { D8_DMA(3) }
+    int tl_g = 0;                                             // TL: g(t + 4) of the loop's next DMA
+    if constexpr (TL) tl_g = __builtin_amdgcn_readfirstlane((int)D8_GLOAD(4));
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");          // tiles 0 and 1
     __syncthreads();
 
@@ -1164,8 +1216,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
             __builtin_shufflevector(kA[1][1][0], kA[1][1][1], 0, 1, 2, 3, 4, 5, 6, 7), qf[1], S1_, 0, 0, 0, kS[1][1], 0, q_scale[1]); \
     }
 #define D8_MASK(T_, S0_, S1_)                                                                                \
-    if (__builtin_expect((T_) == nt - 1 && (lk & (kKV - 1)), 0)) {                                           \
-        int rem_ = lk - (T_) * kKV - 4 * g;                                                                  \
+    if (__builtin_expect(TL ? (T_) == tl_rag : ((T_) == nt - 1 && (lk & (kKV - 1))), 0)) {                   \
+        int rem_ = lk - (TL ? ntall - 1 : (T_)) * kKV - 4 * g;                                               \
         asm volatile("" : "+v"(rem_));                                                                       \
         _Pragma("unroll") for (int j_ = 0; j_ < 16; ++j_) {                                                  \
             const int key_ = (j_ & 3) + 8 * (j_ >> 2);                                                       \
@@ -1217,7 +1269,13 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
             pf[i] = (int)p_bytes4<PX>(s0[4 * i], s0[4 * i + 1], s0[4 * i + 2], s0[4 * i + 3]);
             pf[4 + i] = (int)p_bytes4<PX>(s1[4 * i], s1[4 * i + 1], s1[4 * i + 2], s1[4 * i + 3]);
         }
-        D8_DMA(t + 4)
+        uint32_t tl_gv = 0;
+        if constexpr (TL) {
+            D8_DMA_T(t + 4, tl_g)
+            tl_gv = D8_GLOAD(t + 5);
+        } else {
+            D8_DMA(t + 4)
+        }
         asm volatile("" : "+v"(pf));
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");     // tile t + 3 (issued a tile ago) has landed
@@ -1225,6 +1283,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
         __builtin_amdgcn_sched_barrier(0);
         // ================= matrix phase =================
         __builtin_amdgcn_s_setprio(1);
+        if constexpr (TL) tl_g = __builtin_amdgcn_readfirstlane((int)tl_gv);
         D8_KREAD((t + 1) & (kRing128 - 1))
         i32x4_t vA[4][2];                                      // [d-tile = 2 sub + dt][chunk]
         int vS[4];
@@ -1266,6 +1325,9 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
     }
     if (grp == 0) __builtin_amdgcn_s_barrier();
 #undef D8_DMA
+#undef D8_DMA_T
+#undef D8_GLOAD
+#undef D8_CLAMP
 #undef D8_KREAD
 #undef D8_QK
 #undef D8_MASK
@@ -1337,16 +1399,21 @@ extern "C" int64_t fino_attn_fp8_smoothed_kv_bytes(int batch, int heads, int64_t
 // every entry point: `smooth` (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V) != 0 = means -> smoothing quantiser, otherwise the plain
 // quantiser; the main-kernel launch is the same, and with FINO_FP8_SMOOTH_V it gets the mean of V to add back (AttnParams::vmean).
 // `ranges` (fino_attn_fwd_fp8_ranges): head_dim 64 only, always attn_fp8_fr_kernel<T, PX, true>, whatever the tuning knob says.
+// `tiles` (fino_attn_fwd_fp8_tiles): head_dim 128 only, always attn_fp8_d128_kernel<T, PX, true> over whole blocks (no tail split,
+// no partials, no combine launch).
 static int attn_fwd_fp8_impl(const char* fn, int smooth, const void* q, const void* k, const void* v, void* o, int batch, int heads,
                              int64_t lq, int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
                              int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode,
-                             void* kv_workspace, int64_t kv_workspace_bytes, void* stream, const int* ranges = nullptr) {
+                             void* kv_workspace, int64_t kv_workspace_bytes, void* stream, const int* ranges = nullptr,
+                             const AttnTileMask* tiles = nullptr) {
     FINO_CHECK(smooth >= 0 && smooth <= (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V), FINO_ERR_ARG, "%s: smooth flags %d not in 0 .. 3", fn,
                smooth);
     FINO_CHECK(p_mode == FINO_FP8_P_EXP2 || p_mode == FINO_FP8_P_RAMP, FINO_ERR_ARG, "%s: p_mode %d", fn, p_mode);
     FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "%s: dtype %d", fn, dtype);
     FINO_CHECK(head_dim == 64 || head_dim == 128, FINO_ERR_UNSUPPORTED, "%s: head_dim %d not in {64, 128}", fn, head_dim);
     FINO_CHECK(!ranges || head_dim == 64, FINO_ERR_UNSUPPORTED, "%s: head_dim %d: the range walk exists for head_dim 64 only", fn,
+               head_dim);
+    FINO_CHECK(!tiles || head_dim == 128, FINO_ERR_UNSUPPORTED, "%s: head_dim %d: the fp8 tile walk exists for head_dim 128 only", fn,
                head_dim);
     FINO_CHECK(q && k && v && o && kv_workspace, FINO_ERR_ARG, "%s: null pointer", fn);
     FINO_CHECK(batch > 0 && heads > 0 && lq >= 0 && lk > 0, FINO_ERR_ARG, "%s: bad shape", fn);
@@ -1437,6 +1504,11 @@ static int attn_fwd_fp8_impl(const char* fn, int smooth, const void* q, const vo
         if (dtype == FINO_BF16) { if (ramp) KERNEL_(BF16, 1)<<<GRID_, THREADS_, SMEM_, st>>>(fp); else KERNEL_(BF16, 0)<<<GRID_, THREADS_, SMEM_, st>>>(fp); } \
         else { if (ramp) KERNEL_(F16, 1)<<<GRID_, THREADS_, SMEM_, st>>>(fp); else KERNEL_(F16, 0)<<<GRID_, THREADS_, SMEM_, st>>>(fp); } \
     }
+#define F8_LAUNCH_TM(KERNEL_, GRID_, THREADS_, SMEM_, TM_)                                                                \
+    {                                                                                                                     \
+        if (dtype == FINO_BF16) { if (ramp) KERNEL_(BF16, 1)<<<GRID_, THREADS_, SMEM_, st>>>(fp, TM_); else KERNEL_(BF16, 0)<<<GRID_, THREADS_, SMEM_, st>>>(fp, TM_); } \
+        else { if (ramp) KERNEL_(F16, 1)<<<GRID_, THREADS_, SMEM_, st>>>(fp, TM_); else KERNEL_(F16, 0)<<<GRID_, THREADS_, SMEM_, st>>>(fp, TM_); } \
+    }
 #define F8_SMEM_ONCE(KERNEL_, SMEM_)                                                                                      \
     {                                                                                                                     \
         static FinoPerDeviceOnce once_[4];                                                                                \
@@ -1448,9 +1520,17 @@ static int attn_fwd_fp8_impl(const char* fn, int smooth, const void* q, const vo
 #define K_FR(T_, PX_) attn_fp8_fr_kernel<T_, PX_>
 #define K_FR_RG(T_, PX_) attn_fp8_fr_kernel<T_, PX_, true>
 #define K_D128(T_, PX_) attn_fp8_d128_kernel<T_, PX_>
+#define K_D128_TL(T_, PX_) attn_fp8_d128_kernel<T_, PX_, true>
 #define K_PP(T_, PX_) attn_fp8_kernel<T_, 0, PX_>
         if (ranges) F8_LAUNCH(K_FR_RG, grid, kFrWaves * 64, kFrSmem + kMuSlot)
         else F8_LAUNCH(K_FR, grid, kFrWaves * 64, kFrSmem + kMuSlot)
+        FINO_LAUNCH_CHECK();
+        return FINO_OK;
+    }
+    if (tiles) {
+        // whole blocks only (full_x covers every block, rem_x = 0 as set above); the tile list sits behind the rings and the mean slot
+        F8_SMEM_ONCE(K_D128_TL, kSmem128Tiles)
+        F8_LAUNCH_TM(K_D128_TL, grid, kWaves * 64, kSmem128Tiles, *tiles)
         FINO_LAUNCH_CHECK();
         return FINO_OK;
     }
@@ -1465,7 +1545,7 @@ static int attn_fwd_fp8_impl(const char* fn, int smooth, const void* q, const vo
         }
         const dim3 grid128((unsigned)(8 * (p.full_x + p.nwg)));
         F8_SMEM_ONCE(K_D128, kSmem128 + kMuSlot)
-        F8_LAUNCH(K_D128, grid128, kWaves * 64, kSmem128 + kMuSlot)
+        F8_LAUNCH_TM(K_D128, grid128, kWaves * 64, kSmem128 + kMuSlot, AttnTileMask{})
         FINO_LAUNCH_CHECK();
         return fino_attn_launch_combine(p, dtype, 128, st);
     }
@@ -1518,4 +1598,32 @@ extern "C" int fino_attn_fwd_fp8_ranges(const void* q, const void* k, const void
     const int smooth = (smooth_k == 2 || smooth_k == 3) ? smooth_k : (smooth_k != 0 ? FINO_FP8_SMOOTH_K : 0);
     return attn_fwd_fp8_impl("fino_attn_fwd_fp8_ranges", smooth, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs,
                              k_rs, v_bs, v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream, ranges);
+}
+
+// fp8 attention over the key tiles a bitmask names per (batch element, head, 256-row q-block) (include/frameino_hip.h):
+// fino_attn_fwd_fp8_smoothed's arguments and checks + the device mask of fino_attn_fwd_tiles; head_dim 128 only, always
+// attn_fp8_d128_kernel<T, PX, true>.
+extern "C" int fino_attn_fp8_tiles_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim) {
+    return head_dim == 128 && batch > 0 && heads > 0 && lq > 0 && lk > 0 && lq < (1ll << 31) - 256 && lk < (1ll << 31) - 64 &&
+           (lk + kKV - 1) / kKV <= kAttnMaxTiles;
+}
+
+extern "C" int fino_attn_fwd_fp8_tiles(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
+                                       int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
+                                       int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype,
+                                       int p_mode, void* kv_workspace, int64_t kv_workspace_bytes, int smooth,
+                                       const uint32_t* mask, int64_t mask_bs, int64_t mask_hs, int words, void* stream) {
+    FINO_CHECK(head_dim == 128, FINO_ERR_UNSUPPORTED,
+               "fino_attn_fwd_fp8_tiles: head_dim %d: the fp8 tile walk exists for head_dim 128 only", head_dim);
+    FINO_CHECK(mask, FINO_ERR_ARG, "fino_attn_fwd_fp8_tiles: null mask");
+    FINO_CHECK(((uintptr_t)mask & 3) == 0, FINO_ERR_ARG, "fino_attn_fwd_fp8_tiles: the mask must be 4-byte aligned");
+    FINO_CHECK(lk > 0 && (lk + kKV - 1) / kKV <= kAttnMaxTiles, FINO_ERR_UNSUPPORTED,
+               "fino_attn_fwd_fp8_tiles: Lk=%lld is more than %d key tiles", (long long)lk, kAttnMaxTiles);
+    FINO_CHECK(words > 0 && (int64_t)words * 32 >= (lk + kKV - 1) / kKV, FINO_ERR_ARG,
+               "fino_attn_fwd_fp8_tiles: %d mask words per q-block do not hold %lld key tiles", words,
+               (long long)((lk + kKV - 1) / kKV));
+    FINO_CHECK(mask_bs >= 0 && mask_hs >= 0, FINO_ERR_ARG, "fino_attn_fwd_fp8_tiles: negative mask stride");
+    const AttnTileMask tm{mask, mask_bs, mask_hs, words};
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_tiles", smooth, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs,
+                             v_bs, v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream, nullptr, &tm);
 }

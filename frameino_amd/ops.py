@@ -458,6 +458,20 @@ def attention_tile_plan(q, k, heads, cdf, keep_ranges=None, scale=None, out=None
     return out
 
 
+def _timed_tiles_done(ev, mask, b, heads, lq, lk, hd, dh):
+    """close the "attn_self" timing of a tile walk: FLOPs from the tiles walked -- the mask's host copy is read only here, under
+    the timer (one sync per launch)"""
+    ev.record()
+    kt_ = KernelTimer.active
+    bits = _tile_mask_bits(mask, lk).expand(b, heads, -1, -1).to(torch.float64)
+    keys = torch.full((bits.shape[-1],), 64.0, dtype=torch.float64)
+    keys[-1] = lk - 64 * (bits.shape[-1] - 1)
+    rows = torch.tensor([min(256, lq - 256 * i) for i in range(bits.shape[2])], dtype=torch.float64)
+    pairs = float(((bits * keys).sum(-1) * rows).sum())
+    kt_.flops["attn_self"] = kt_.flops.get("attn_self", 0.0) + 4.0 * pairs * dh
+    kt_.bytes["attn_self"] = kt_.bytes.get("attn_self", 0.0) + 2.0 * b * hd * (2 * lq + 2 * lk)
+
+
 def attention_tiles(q, k, v, heads, mask, out=None, scale=None):
     """attention() over a subset of the key tiles, chosen per (batch element, head, 256-row q-block): `mask` is an int32 / uint32
     DEVICE tensor [B | 1, heads | 1, ceil(Lq / 256), words], bit t & 31 of word t >> 5 of a row stands for the 64-key tile t; a
@@ -472,16 +486,7 @@ def attention_tiles(q, k, v, heads, mask, out=None, scale=None):
                                              float(scale), _dt(q), _p(mask), mask_bs, mask_hs, words, _stream()),
                "fino_attn_fwd_tiles")
     if ev is not None:
-        # FLOPs from the tiles walked: the mask's host copy is read only here, under the timer (one sync per launch)
-        ev.record()
-        kt_ = KernelTimer.active
-        bits = _tile_mask_bits(mask, lk).expand(b, heads, -1, -1).to(torch.float64)
-        keys = torch.full((bits.shape[-1],), 64.0, dtype=torch.float64)
-        keys[-1] = lk - 64 * (bits.shape[-1] - 1)
-        rows = torch.tensor([min(256, lq - 256 * i) for i in range(bits.shape[2])], dtype=torch.float64)
-        pairs = float(((bits * keys).sum(-1) * rows).sum())
-        kt_.flops["attn_self"] = kt_.flops.get("attn_self", 0.0) + 4.0 * pairs * dh
-        kt_.bytes["attn_self"] = kt_.bytes.get("attn_self", 0.0) + 2.0 * b * hd * (2 * lq + 2 * lk)
+        _timed_tiles_done(ev, mask, b, heads, lq, lk, hd, dh)
     return out
 
 
@@ -638,6 +643,34 @@ def attention_fp8_ranges(q, k, v, heads, ranges, out=None, scale=None, p_mode=No
                                                   flags, _p(ranges), _stream()), "fino_attn_fwd_fp8_ranges")
     if done is not None:
         done()
+    return out
+
+
+def attention_fp8_tiles_supported(b, heads, lq, lk, dh):
+    return bool(_lib.lib().fino_attn_fp8_tiles_supported(int(b), int(heads), int(lq), int(lk), int(dh)))
+
+
+def attention_fp8_tiles(q, k, v, heads, mask, out=None, scale=None, p_mode=None, smooth_k=False, smooth_v=False):
+    """attention_fp8() over the subset of key tiles attention_tiles() walks: the same int32 / uint32 DEVICE mask [B | 1, heads | 1,
+    ceil(Lq / 256), words] (fino_attn_fwd_fp8_tiles; head_dim 128 only, at most 1024 key tiles).  K / V are quantised whole, and
+    `smooth_k` / `smooth_v` take their means over ALL keys: exact for any subset (every logit of a query moves by the same amount;
+    the weights of the walked tiles sum to one).  Bits at or beyond ceil(Lk / 64) are ignored; an empty row gives zeros, not the
+    value mean."""
+    p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
+    b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
+    words, mask_bs, mask_hs = _check_tile_mask(mask, b, heads, lq, lk)
+    if dh != 128:
+        raise RuntimeError(f"attention_fp8_tiles: head_dim {dh} is not supported (the fp8 tile walk exists for head_dim 128 only)")
+    flags = _fp8_smooth_flags(smooth_k, smooth_v)
+    need = _lib.lib().fino_attn_fp8_smoothed_kv_bytes(b, heads, lk, dh, flags)
+    ws = _attn_fp8_workspace(need, q.device)
+    ev = _timed("attn_self")
+    _lib.check(_lib.lib().fino_attn_fwd_fp8_tiles(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
+                                                 k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0),
+                                                 out.stride(1), float(scale), _dt(q), int(p_mode), _p(ws), need, flags,
+                                                 _p(mask), mask_bs, mask_hs, words, _stream()), "fino_attn_fwd_fp8_tiles")
+    if ev is not None:
+        _timed_tiles_done(ev, mask, b, heads, lq, lk, hd, dh)
     return out
 
 

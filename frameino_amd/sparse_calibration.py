@@ -80,7 +80,10 @@ def calibrate_sparse_attention(model, run, *, l1_bound, grid=(0.5, 0.6, 0.7, 0.8
     for every layer outside `base.skip_layers` that made a sparse-eligible self-attention call during `run()`.  report: {"grid",
     "l1_bound", "error": {layer: [heads][len(grid)]}, "density": {layer: [heads][len(grid)]} (kept share of the (q-block, key
     tile) entries, from popcounts of the masks), "thresholds": {layer: [heads]}, "calls": {layer: n}}.  The model's sparse
-    attention setting is put back afterwards."""
+    attention setting is put back afterwards.
+    Thresholds are calibrated in bf16 / fp16 and loaded: with fp8 attention on (`enable_fp8_attention`) this raises
+    NotImplementedError before anything is launched -- the dense reference and the tile walks here are the bf16 / fp16 ones, and
+    the masks are predicted from the bf16 / fp16 q and k whatever the operands of the walk."""
     base = SparseAttentionConfig() if base is None else base
     if not isinstance(base, SparseAttentionConfig):
         raise TypeError(f"base: a SparseAttentionConfig is needed, got {type(base)}")
@@ -91,6 +94,9 @@ def calibrate_sparse_attention(model, run, *, l1_bound, grid=(0.5, 0.6, 0.7, 0.8
         raise ValueError(f"l1_bound = {l1_bound!r}: a number > 0 is needed")
     if getattr(model, "_sparse_calib", None) is not None:
         raise RuntimeError("a calibration of this model is already running")
+    if getattr(model, "fp8_attention", False):
+        raise NotImplementedError("calibrate_sparse_attention with fp8 attention: thresholds are calibrated in bf16 / fp16 and "
+                                  "loaded; enable_fp8_attention(False) first, calibrate, then switch fp8 attention back on")
     before = model._sparse
     state = _Calibration(grid, base.similarity_threshold)
     # the model's own host path builds the forced tiles, skips `skip_layers` and hands every other call to `state.attend`

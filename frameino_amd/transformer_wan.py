@@ -133,9 +133,11 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
 
     Sparse attention (enable_sparse_attention): per head and q-block only the key tiles a device-side
     predictor picks, plus the own frame, the sink frames and the ID frame.  First-block caching, MX linears, LoRA and the
-    hipGraph loop work with it; window attention, fp8 attention, Pyramid Attention Broadcast, a token-sharded plan and
-    user-installed attention processors are refused.  Its similarity gate, per-head thresholds and their calibration
-    (frameino_amd/sparse_calibration.py): DESIGN.md section 6k."""
+    hipGraph loop work with it, and so does fp8 attention at head_dim 128 (the fp8 tile walk, fino_attn_fwd_fp8_tiles, over the
+    mask predicted from the bf16 / fp16 q and k; DESIGN.md section 6m -- any other head_dim is refused); window attention,
+    Pyramid Attention Broadcast, TaylorSeer caching, a token-sharded plan and user-installed attention processors are refused.
+    Its similarity gate, per-head thresholds and their calibration (frameino_amd/sparse_calibration.py; bf16 / fp16 only):
+    DESIGN.md section 6k."""
     _window_table_cache = "_rope_cache"
     _loader_name = "load_wan_transformer"
     _keep_in_fp32_modules = ["time_embedder", "scale_shift_table", "norm1", "norm2", "norm3"]   # reference :393

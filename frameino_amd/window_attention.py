@@ -419,9 +419,10 @@ class SelfAttentionOptionsMixin:
         if self._window is not None:
             raise NotImplementedError(f"{what} with window attention (enable_window_attention): switch one of them off first; "
                                       f"`SparseAttentionConfig.window_frames` keeps a window of frames always")
-        if fp8:
-            raise NotImplementedError(f"{what} with fp8 attention: the tile walk exists in the bf16 / fp16 kernel only; switch "
-                                      f"one of them off first (disable_sparse_attention() / enable_fp8_attention(False))")
+        if fp8 and self.config.attention_head_dim != 128:
+            raise NotImplementedError(f"{what} with fp8 attention at head_dim {self.config.attention_head_dim}: the fp8 tile walk "
+                                      f"(fino_attn_fwd_fp8_tiles) exists for head_dim 128 only; switch one of them off first "
+                                      f"(disable_sparse_attention() / enable_fp8_attention(False))")
         if getattr(self, "_pab_on", False):
             raise NotImplementedError(f"{what} with Pyramid Attention Broadcast: not implemented in this version (first-block "
                                       f"caching is)")
@@ -438,10 +439,11 @@ class SelfAttentionOptionsMixin:
         only the 64-key tiles that a device-side predictor picks right before the call, from that call's q and k
         (`ops.attention_tile_plan`: mean-pooled q-blocks and key tiles, the smallest set of tiles by descending predicted
         softmax mass that reaches `config.cdf_threshold`), plus the always-kept tiles of `frame_window_ranges(frames, tpf,
-        config.window_frames, sinks)` -- `ops.attention_tiles` over the mask.  `cdf_threshold >= 1`, or forced tiles that cover
+        config.window_frames, sinks)` -- `ops.attention_tiles` over the mask (with fp8 attention, head_dim 128:
+        `ops.attention_fp8_tiles` over the same mask, predicted from the bf16 / fp16 q and k).  `cdf_threshold >= 1`, or forced tiles that cover
         everything, take the dense call, bit for bit.  No timestep gate and no host read: the step captures as it is.  What does
-        not combine with it (window attention, fp8 attention, Pyramid Attention Broadcast, a token-sharded plan, a
-        user-installed processor) is refused here where it can be seen, else by the forward before anything is launched.  No
+        not combine with it (window attention, fp8 attention at a head_dim other than 128, Pyramid Attention Broadcast, a
+        token-sharded plan, a user-installed processor) is refused here where it can be seen, else by the forward before anything is launched.  No
         reference counterpart; quality on real checkpoints is unmeasured.
         `config.similarity_threshold` and `config.head_thresholds` (both off by default): blocks whose tokens do
         not resemble each other are never predicted from, and every (layer, head) gets its own threshold -- a head at >= 1 keeps
@@ -556,9 +558,12 @@ class SelfAttentionOptionsMixin:
             tiles.cdf_heads = sp.cdf_heads(li)
         return tiles
 
-    def _attend_tiles(self, ops, q, k, v, heads, tiles, **kw):
-        """the plan on this call's q and k, then the tile walk over its mask"""
+    def _attend_tiles(self, ops, q, k, v, heads, tiles, fp8=False, **kw):
+        """the plan on this call's q and k, then the tile walk over its mask -- `fp8`: the fp8 walk with the model's fp8 options"""
         if getattr(self, "_sparse_calib", None) is not None:
+            if fp8:          # (switched on inside the calibration's run(): calibrate_sparse_attention has refused any other)
+                raise NotImplementedError("calibrate_sparse_attention with fp8 attention: thresholds are calibrated in "
+                                          "bf16 / fp16 and loaded; enable_fp8_attention(False) first")
             return self._sparse_calib.attend(self, ops, q, k, v, heads, tiles, **kw)
         sp = tiles.sp
         b, nqb = q.shape[0], -(-q.shape[1] // Q_BLOCK)
@@ -586,13 +591,16 @@ class SelfAttentionOptionsMixin:
                 old = self.sparse_attention_masks[tiles.layer] = torch.empty_like(mask)
             old.copy_(mask)
             self._sparse_mask_keys[tiles.layer] = k.shape[1]
+        if fp8:
+            return ops.attention_fp8_tiles(q, k, v, heads, mask, p_mode=self.fp8_p_mode, smooth_k=self.fp8_smooth_k,
+                                           smooth_v=self.fp8_smooth_v, **kw)
         return ops.attention_tiles(q, k, v, heads, mask, **kw)
 
     def _attend(self, ops, q, k, v, heads, *, fp8, ranges=None, tiles=None, **kw):
         """one self-attention call: dense or over `ranges`, bf16 / fp16 or -- `fp8` -- with the model's fp8 options; `kw`: out=,
-        scale=.  `tiles` (`_sparse_tiles`): the dynamic tile walk instead, bf16 / fp16 only."""
+        scale=.  `tiles` (`_sparse_tiles`): the dynamic tile walk instead (with `fp8`: head_dim 128 only, `_sparse_refusals`)."""
         if tiles is not None:
-            return self._attend_tiles(ops, q, k, v, heads, tiles, **kw)
+            return self._attend_tiles(ops, q, k, v, heads, tiles, fp8=fp8, **kw)
         if fp8:
             kw.update(p_mode=self.fp8_p_mode, smooth_k=self.fp8_smooth_k, smooth_v=self.fp8_smooth_v)
         if ranges is None:

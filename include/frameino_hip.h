@@ -309,6 +309,24 @@ int fino_attn_fwd_fp8_ranges(const void* q, const void* k, const void* v, void* 
                              int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs,
                              int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode, void* kv_workspace,
                              int64_t kv_workspace_bytes, int smooth_k, const int* ranges, void* stream);
+/* fino_attn_fwd_fp8_smoothed over the SUBSET of key tiles fino_attn_fwd_tiles walks: the same DEVICE mask (uint32 words, the row of
+ * (b, h, q-block qb) at mask + b * mask_bs + h * mask_hs + qb * words, strides in words and 0 shares the rows, bit t & 31 of word
+ * t >> 5 for key tile t, words >= ceil(ceil(lk / 64) / 32), bits at or beyond ceil(lk / 64) ignored) -- non-null and 4-byte aligned
+ * (FINO_ERR_ARG otherwise, as for too few words).  The dynamic block-sparse self-attention on the fp8 operands; no reference
+ * counterpart, like fino_attn_fwd_tiles.  The arguments are fino_attn_fwd_fp8_smoothed's, then the four of the mask, then the
+ * stream.  The pre-pass quantises ALL keys and the means of `smooth` (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V) are the means over all
+ * keys -- exact for any subset: every logit of a query moves by the same q.mean, and the weights of the walked tiles sum to 1 -- so
+ * the workspace is fino_attn_fp8_smoothed_kv_bytes (no partials are written).  A q-block that walks the tiles T computes, to the
+ * same bits, what fino_attn_fwd_fp8's whole-block kernel computes for those query rows over the keys of T gathered into one
+ * sequence; a q-block whose row is empty stores zeros, not the value mean.  A bad mask gives a wrong answer, never a read outside
+ * the workspace images.  head_dim 128 only (FINO_ERR_UNSUPPORTED otherwise), at most 1024 key tiles
+ * (fino_attn_fp8_tiles_supported()); whole blocks, one main launch, no combine. */
+int fino_attn_fp8_tiles_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim);
+int fino_attn_fwd_fp8_tiles(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq, int64_t lk,
+                            int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs,
+                            int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode, void* kv_workspace,
+                            int64_t kv_workspace_bytes, int smooth, const uint32_t* mask, int64_t mask_bs, int64_t mask_hs,
+                            int words, void* stream);
 
 /* Attention PROBABILITIES over a short key sequence (head_dim 128, lk <= 128 key rows allocated per sample, batch <= 4):
  * p[b][row][head][0 .. kp) = softmax(scale q.K^T) of that head's keys (kp a multiple of 8, >= every lk_b; columns from lk_b[b] on

@@ -20,9 +20,15 @@
      tree's library against the parent commit's, masks compared; and the bench STEP dense / cdf_threshold 0.9 / cdf_threshold
      0.9 + similarity_threshold, with the share of q-blocks and key tiles the gate fired on.
 
+  6. with --fp8 (nothing of 1 - 5 is run): the LAUNCH table of 1 on the fp8 operands -- ops.attention_fp8 dense
+     (tail split included) against ops.attention_fp8_tiles over the same scattered masks and the full mask, the same bar; with
+     --parent-lib the dense fp8 launch (fino_attn_fwd_fp8) of this tree's library against the parent commit's, outputs compared;
+     and the bench STEP with MXFP8 linears + fp8 attention, dense against cdf_threshold = 0.9 (random weights: no bar).
+
     python tools/sparse_attention_bench.py [--rounds 7] [--steps 3] [--skip-81f] [--parent-lib PATH]
                                            [--out profiles/sparse_attention.txt]
     python tools/sparse_attention_bench.py --gate [--theta 0.3] [--parent-lib PATH] [--out profiles/sparse_attention_gate.txt]
+    python tools/sparse_attention_bench.py --fp8 [--parent-lib PATH] [--out profiles/sparse_attention_fp8.txt]
 
 Quality on real checkpoints is NOT measured here or anywhere in this repository (random weights only)."""
 import argparse
@@ -45,6 +51,19 @@ def _forced_keep(frames, tpf, L):
     return block_mask(frame_window_ranges(frames, tpf, 0, (0, -1)), L, L)[::256, ::64]
 
 
+def _scattered_masks(forced, b, heads, densities):
+    """the masks of the launch tables: the forced set alone, the forced set + random extra tiles per (batch element, head, q-block)
+    up to each density, the full mask"""
+    cg = torch.Generator().manual_seed(1)
+    masks = {"tiles, forced set (window_frames=0)": forced.expand(b, heads, -1, -1)}
+    for want in densities:
+        f0 = float(forced.float().mean())
+        extra = torch.rand(b, heads, *forced.shape, generator=cg) < (want - f0) / (1.0 - f0)
+        masks[f"tiles, forced + random to {want}"] = forced | extra
+    masks["tiles, full mask"] = torch.ones(b, heads, *forced.shape, dtype=torch.bool)
+    return masks
+
+
 def launch_times(rounds, reps, frames=14, tpf=880, heads=24, dh=128, densities=(0.25, 0.5, 0.75)):
     L, d, b = frames * tpf, heads * dh, 2
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -56,13 +75,7 @@ def launch_times(rounds, reps, frames=14, tpf=880, heads=24, dh=128, densities=(
     dens["ranges, window_frames=2"] = ranges_density(tab, L)
     runs["ranges, window_frames=2"] = (lambda t=tab.cuda(): ops.attention_ranges(q, k, v, heads, t, out=o))
     forced = _forced_keep(frames, tpf, L)
-    cg = torch.Generator().manual_seed(1)
-    masks = {"tiles, forced set (window_frames=0)": forced.expand(b, heads, -1, -1)}
-    for want in densities:
-        f0 = float(forced.float().mean())
-        extra = torch.rand(b, heads, *forced.shape, generator=cg) < (want - f0) / (1.0 - f0)
-        masks[f"tiles, forced + random to {want}"] = forced | extra
-    masks["tiles, full mask"] = torch.ones(b, heads, *forced.shape, dtype=torch.bool)
+    masks = _scattered_masks(forced, b, heads, densities)
     for n, keep in masks.items():
         dens[n] = float(keep.float().mean())
         runs[n] = (lambda m=pack_tile_mask(keep).cuda(): ops.attention_tiles(q, k, v, heads, m, out=o))
@@ -136,6 +149,54 @@ def parent_ab(path, rounds, reps, frames=14, tpf=880, heads=24, dh=128):
     return {n: (statistics.median(v), min(v), max(v)) for n, v in t.items()}, torch.equal(outs["this tree"], outs["parent"])
 
 
+def fp8_launch_times(rounds, reps, frames=14, tpf=880, heads=24, dh=128, densities=(0.25, 0.5, 0.75)):
+    """the launch table on the fp8 operands: ops.attention_fp8 dense (as the model calls it: pre-pass, tail split and combine
+    included) and ops.attention_fp8_tiles (the same pre-pass, whole blocks) over the scattered masks of launch_times"""
+    L, d, b = frames * tpf, heads * dh, 2
+    g = torch.Generator(device="cuda").manual_seed(0)
+    qkv = torch.randn(b, L, 3 * d, device="cuda", generator=g).bfloat16()
+    q, k, v = qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:]
+    o = torch.empty(b, L, d, device="cuda", dtype=torch.bfloat16)
+    runs, dens = {"dense fp8": lambda: ops.attention_fp8(q, k, v, heads, out=o)}, {"dense fp8": 1.0}
+    for n, keep in _scattered_masks(_forced_keep(frames, tpf, L), b, heads, densities).items():
+        dens[n] = float(keep.float().mean())
+        runs[n] = (lambda m=pack_tile_mask(keep).cuda(): ops.attention_fp8_tiles(q, k, v, heads, m, out=o))
+    t = _median_us(runs, rounds, reps)
+    return {n: t[n] + (dens[n],) for n in runs}
+
+
+def fp8_parent_ab(path, rounds, reps, frames=14, tpf=880, heads=24, dh=128):
+    """the dense fp8 self-attention launch (fino_attn_fwd_fp8 with the default p_mode) through this tree's library and through the
+    one at `path` (the parent commit's build), both loaded into this process, alternated"""
+    import ctypes
+    from frameino_amd import _lib
+    L, d, b = frames * tpf, heads * dh, 2
+    g = torch.Generator(device="cuda").manual_seed(0)
+    qkv = torch.randn(b, L, 3 * d, device="cuda", generator=g).bfloat16()
+    q, k, v = qkv[:, :, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:]
+    outs = {"this tree": torch.empty(b, L, d, device="cuda", dtype=torch.bfloat16)}
+    outs["parent"] = torch.empty_like(outs["this tree"])
+    other = ctypes.CDLL(path)                               # (an older build lacks newer symbols: bind the three used here only)
+    for name in ("fino_attn_fp8_kv_bytes", "fino_attn_fwd_fp8", "fino_last_error"):
+        getattr(other, name).argtypes = _lib.SIGNATURES.get(name)
+        getattr(other, name).restype = getattr(_lib.lib(), name).restype
+    libs = {"this tree": _lib.lib(), "parent": other}
+    need = libs["this tree"].fino_attn_fp8_kv_bytes(b, heads, L, dh)
+    assert need == libs["parent"].fino_attn_fp8_kv_bytes(b, heads, L, dh)
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+
+    def call(n):
+        o = outs[n]
+        rc = libs[n].fino_attn_fwd_fp8(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), b, heads, L, L, dh, q.stride(0),
+                                       q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), o.stride(0), o.stride(1),
+                                       ctypes.c_float(dh ** -0.5), 0, ops.FP8_P_DEFAULT, ws.data_ptr(), need, st)
+        assert rc == 0, libs[n].fino_last_error()
+
+    t = _median_us({n: (lambda n=n: call(n)) for n in libs}, rounds, reps)
+    return t, torch.equal(outs["this tree"], outs["parent"])
+
+
 def _median_us(runs, rounds, reps):
     """{name: callable} -> {name: (median, min, max)} in us per call; alternated, device events"""
     t = {n: [] for n in runs}
@@ -202,7 +263,7 @@ def gate_plan_times(rounds, reps, theta, parent_lib=None, frames=14, tpf=880, he
     return t, dens, same, gate_off_same
 
 
-def step_times(workload, rounds, steps, cdf, theta=None):
+def step_times(workload, rounds, steps, cdf, theta=None, fp8=False):
     import bench
     from frameino_amd.pipeline_wan_i2v_motion_frameino import WanImageToVideoPipeline
     from frameino_amd.schedulers import FlowMatchEulerDiscreteScheduler
@@ -211,6 +272,9 @@ def step_times(workload, rounds, steps, cdf, theta=None):
     fg, lh, lw = bench.WORKLOADS[workload]
     C, nid = cfg["out_channels"], 1
     model = bench.build_model(cfg, dev)
+    if fp8:                                                               # the precision path: MXFP8 linears + fp8 attention operands
+        model.enable_mxfp8_linears()
+        model.enable_fp8_attention()
     pipe = WanImageToVideoPipeline(scheduler=FlowMatchEulerDiscreteScheduler(shift=5.0), transformer=model, expand_timesteps=True)
     g = torch.Generator().manual_seed(1234)
     rnd = lambda *s: torch.randn(*s, generator=g)          # noqa: E731
@@ -306,6 +370,42 @@ def gate_report(a):
     return lines
 
 
+def fp8_report(a):
+    lines = [f"# tools/sparse_attention_bench.py --fp8 on {torch.cuda.get_device_name(0)}; bf16 storage, fp8 (e4m3) attention "
+             f"operands; one box, one run",
+             "# block-sparse fp8 self-attention (DESIGN.md section 6m): ops.attention_fp8_tiles against ops.attention_fp8",
+             "# forced tiles: own frame(s), first frame, ID frame (window_frames = 0); extra tiles: random per (b, head, q-block)",
+             "# quality on real checkpoints: NOT measured (random weights and N(0, 1) inputs only)", ""]
+    lt = fp8_launch_times(a.rounds, a.reps)
+    base = lt["dense fp8"][0]
+    lines.append("fp8 self-attention launch (K / V pre-pass included in every row), [2, 12320, 24 x 128] (14 frames x 880 tokens, 49 "
+                 "q-blocks x 193 key tiles)")
+    lines.append(f"{'':40s} {'median us':>10s} {'min':>9s} {'max':>9s} {'ratio':>7s} {'density':>8s} {'(1+density)/2':>14s} {'bar':>5s}")
+    for n, (med, lo, hi, dens) in lt.items():
+        bar = "" if n == "dense fp8" else ("met" if med / base <= (1 + dens) / 2 else "MISS")
+        lines.append(f"{n:40s} {med:10.1f} {lo:9.1f} {hi:9.1f} {med / base:7.3f} {dens:8.3f} {(1 + dens) / 2:14.3f} {bar:>5s}")
+    if a.parent_lib:
+        ab, same = fp8_parent_ab(a.parent_lib, 9, a.reps)
+        lines.append("")
+        lines.append(f"dense fp8 launch (fino_attn_fwd_fp8), this tree's library against the parent commit's (one process, alternated, "
+                     f"9 rounds x {a.reps} launches); outputs torch.equal: {same}")
+        lines.append(f"{'':28s} {'median us':>10s} {'min':>9s} {'max':>9s}")
+        for n, (med, lo, hi) in ab.items():
+            lines.append(f"{n:28s} {med:10.1f} {lo:9.1f} {hi:9.1f}")
+    if not a.skip_steps:
+        wl = "wan2.2-5b-49f-704x1280"
+        stt, dens, dlo, dhi, forced, frames, tpf = step_times(wl, a.step_rounds, a.steps, a.cdf, fp8=True)
+        base = stt["dense"][0]
+        lines.append("")
+        lines.append(f"denoise step, {wl}, MXFP8 linears + fp8 attention ({frames} latent frames x {tpf} tokens; eager, CFG batch; mask "
+                     f"density of the first step: mean {dens:.3f}, layers {dlo:.3f} .. {dhi:.3f}; forced tiles alone {forced:.3f})")
+        lines.append("(random weights: a near-uniform pooled softmax -- this density says nothing about real checkpoints; no bar applies)")
+        lines.append(f"{'':28s} {'median ms':>10s} {'min':>9s} {'max':>9s} {'ratio':>7s}")
+        for n, (med, lo, hi) in stt.items():
+            lines.append(f"{n:28s} {med:10.1f} {lo:9.1f} {hi:9.1f} {med / base:7.3f}")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -318,12 +418,13 @@ def main():
     ap.add_argument("--parent-lib", default=None, help="another build of libframeino_hip.so to alternate the dense launch with")
     ap.add_argument("--gate", action="store_true", help="measure the similarity gate and the per-head table only (section 6k)")
     ap.add_argument("--theta", type=float, default=0.3, help="with --gate: the similarity threshold")
+    ap.add_argument("--fp8", action="store_true", help="measure the block-sparse fp8 self-attention only (section 6m)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sparse_attention_bench: needs the GPU (no CPU path, nothing is estimated)")
-    if a.gate:
-        text = "\n".join(gate_report(a)) + "\n"
+    if a.gate or a.fp8:
+        text = "\n".join(gate_report(a) if a.gate else fp8_report(a)) + "\n"
         print(text)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
