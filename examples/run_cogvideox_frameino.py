@@ -57,6 +57,10 @@ def main():
                     help="the released CogVideoX-5b-I2V folder ships CogVideoXDPMScheduler; the FrameINO training validation uses DDIM")
     ap.add_argument("--frame-out", action="store_true", help="the FrameOut evaluation: no identity reference")
     ap.add_argument("--mxfp8", action="store_true", help="MXFP8 linears (reduced precision, opt-in)")
+    ap.add_argument("--mxfp6", action="store_true", help="MXFP6 (e2m3) linears (reduced precision, opt-in); not together with --mxfp8")
+    ap.add_argument("--mxfp6-rotate", action="store_true",
+                    help="with --mxfp6: rotate every 32-element block of weights and activations by the Walsh-Hadamard matrix "
+                         "before it is quantised (exact algebra; spreads outliers over their block)")
     ap.add_argument("--fp8-attention", action="store_true", help="fp8 (e4m3) attention operands (reduced precision, opt-in)")
     ap.add_argument("--smooth-k", action="store_true",
                     help="with --fp8-attention: subtract the key mean before K is quantised (exact for the softmax)")
@@ -86,6 +90,10 @@ def main():
                     help="a LoRA adapter (local folder or .safetensors file), merged into the transformer's weights")
     ap.add_argument("--lora-scale", type=float, default=1.0, help="the adapter's scale (attention_kwargs['scale'])")
     a = ap.parse_args()
+    if a.mxfp6 and a.mxfp8:
+        ap.error("--mxfp6 and --mxfp8: one reduced precision of the linears at a time")
+    if a.mxfp6_rotate and not a.mxfp6:
+        ap.error("--mxfp6-rotate needs --mxfp6")
 
     from frameino_amd import _lib
     from frameino_amd.autoencoder_kl_cogvideox import AutoencoderKLCogVideoX
@@ -134,6 +142,8 @@ def main():
         pipe.load_lora_weights(a.lora, adapter_name="lora")
     if a.mxfp8:
         transformer.enable_mxfp8_linears()
+    if a.mxfp6:
+        transformer.enable_mxfp6_linears(rotate=a.mxfp6_rotate)
     if a.fp8_attention:
         transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v)
     if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)
@@ -168,7 +178,8 @@ def main():
         frames = np.stack([np.asarray(f) for f in video])
         assert frames.shape == (a.frames, a.height, a.width, 3) and frames.dtype == np.uint8
         cond_s = f"conditions {tc - t0:.2f} s, " if rep == 0 else ""
-        mode = ("mxfp8 linears" if a.mxfp8 else f"{a.dtype} linears") + ((" + fp8 attention" + (" (smooth K)" if a.smooth_k else "") + (" (smooth V)" if a.smooth_v else "")) if a.fp8_attention else "")
+        lin = "mxfp8" if a.mxfp8 else ("mxfp6, rotated blocks" if a.mxfp6_rotate else "mxfp6") if a.mxfp6 else a.dtype
+        mode = f"{lin} linears" + ((" + fp8 attention" + (" (smooth K)" if a.smooth_k else "") + (" (smooth V)" if a.smooth_v else "")) if a.fp8_attention else "")
         if a.window_frames is not None:
             mode += f" + window attention (+- {a.window_frames} frames)"
         if a.pab is not None:

@@ -104,6 +104,10 @@ def main():
     ap.add_argument("--smooth-v", action="store_true",
                     help="with --fp8-attention: subtract the value mean before V is quantised and add it back to the output (exact: "
                          "the softmax weights sum to one)")
+    ap.add_argument("--mxfp6", action="store_true", help="MXFP6 (e2m3) linears in the DiT (reduced precision, opt-in)")
+    ap.add_argument("--mxfp6-rotate", action="store_true",
+                    help="with --mxfp6: rotate every 32-element block of weights and activations by the Walsh-Hadamard matrix "
+                         "before it is quantised (exact algebra; spreads outliers over their block)")
     ap.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16",
                     help="the DiT's dtype.  Default fp16 = what the reference app loads it in (app.py:156: "
                          "`WanTransformer3DModel.from_pretrained(..., torch_dtype=torch.float16)`, fp32 islands kept); bf16 is what "
@@ -112,6 +116,8 @@ def main():
                     help="run the VAE like the reference app does (app.py:157 loads it in fp32): fp32-compute mode on split-bf16 "
                          "products, 3 (default) or 2 bf16 planes per fp32 operand -- `vae.set_compute_dtype(torch.float32)`")
     a = ap.parse_args()
+    if a.mxfp6_rotate and not a.mxfp6:
+        ap.error("--mxfp6-rotate needs --mxfp6")
 
     from frameino_amd import _lib
     from frameino_amd.autoencoder_kl_wan import AutoencoderKLWan
@@ -185,6 +191,8 @@ def main():
         transformer.enable_cache(TaylorSeerCacheConfig(cache_interval=a.taylorseer, max_order=a.taylorseer_order,
                                                        disable_cache_before_step=a.taylorseer_warmup,
                                                        use_lite_mode=a.taylorseer_lite))
+    if a.mxfp6:                                    # after the LoRA merge: the merged weights are what is quantised
+        transformer.enable_mxfp6_linears(rotate=a.mxfp6_rotate)
     if a.fp8_attention:
         transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v)
     if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)

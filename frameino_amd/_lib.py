@@ -94,6 +94,7 @@ SIGNATURES = {
     "fino_mxfp6_bytes": [c_i64, c_i64],
     "fino_mxfp6_scale_bytes": [c_i64, c_i64],
     "fino_quantize_mxfp6": [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p],
+    "fino_quantize_mxfp6_rot": [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_void_p],
     "fino_gemm_mxfp6": [c_void_p] * 6 + [c_i64] * 4 + [c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p],
     "fino_gemm_mxfp6_keep": [c_void_p] * 6 + [c_i64] * 4 + [c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_int, c_void_p,
                              c_i64, c_void_p],

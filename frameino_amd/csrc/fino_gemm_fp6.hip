@@ -2,6 +2,8 @@
 // ladder.  e2m3 keeps e4m3's three mantissa bits (the block scale supplies the range) and CDNA4 runs FP6 operands at the
 // FP4 matrix rate: v_mfma_scale_f32_16x16x128_f8f6f4 with cbsz = blgp = 2 takes 16 cycles where the e4m3 form takes 32.
 //   fino_quantize_mxfp6 : [rows, cols] bf16|fp16 -> packed e2m3 fragments + e8m0 block scales
+//   fino_quantize_mxfp6_rot : the same of the blocks rotated by the 32-point Walsh-Hadamard matrix (outlier-robust; the GEMM
+//                         of an ACT image and a WEIGHT image is the product of the unrotated operands)
 //   fino_gemm_mxfp6     : C = epilogue(dequant(A) . dequant(W)^T + bias), fp32 accumulate, the fused epilogues of fino_gemm
 //
 // Operand layout (probed on hardware, tools/fp6/mfma_scale_probe_fp6.hip, result in profiles/mxfp6_probe.txt): the FP6 form
@@ -66,8 +68,25 @@ __device__ __forceinline__ void pack16(const uint32_t* c, uint32_t& d0, uint32_t
     d2 = (c[10] >> 4) | (c[11] << 2) | (c[12] << 8) | (c[13] << 14) | (c[14] << 20) | (c[15] << 26);
 }
 
+// y = H v, H the 32-point Walsh-Hadamard matrix (symmetric, H H = 32 I): five butterfly stages, strides 1, 2, 4, 8, 16 in that
+// order, adds and subtracts only -- the order is the rule (include/frameino_hip.h), a plain fp32 restatement is bit-equal.
+// Constant indices throughout: the block stays in the registers it was loaded into.
+__device__ __forceinline__ void hadamard32(float* v) {
+#pragma unroll
+    for (int s = 1; s < 32; s <<= 1)
+#pragma unroll
+        for (int i = 0; i < 32; ++i)
+            if ((i & s) == 0) {
+                const float a = v[i], b = v[i + s];
+                v[i] = a + b;
+                v[i + s] = a - b;
+            }
+}
+
 // wave = one fragment (16 rows x 128 columns); lane (r, g) owns the whole 32-element block g of row r
-template <typename T>
+// ROT (fino_quantize_mxfp6_rot): 0 = none; FINO_MX_ROT_ACT: the block is rotated by H before the rule; FINO_MX_ROT_WEIGHT: the
+// same codes, and the stored exponent is e - 5 (the 1/32 of H H, so the GEMM needs no factor)
+template <typename T, int ROT = 0>
 __global__ __launch_bounds__(256) void mxfp6_quantize_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
                                                              uint8_t* __restrict__ scales, int64_t rows, int64_t cols,
                                                              int64_t ldx, int64_t rows_pad) {
@@ -90,6 +109,7 @@ __global__ __launch_bounds__(256) void mxfp6_quantize_kernel(const uint16_t* __r
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[c * 8 + j] = t[j];
         }
+        if constexpr (ROT != 0) hadamard32(v);
         float amax = 0.f;
 #pragma unroll
         for (int j = 0; j < 32; ++j) amax = fmaxf(amax, fabsf(v[j]));
@@ -110,6 +130,7 @@ __global__ __launch_bounds__(256) void mxfp6_quantize_kernel(const uint16_t* __r
         uint8_t* frag = q + (kt * (rows_pad >> 4) + rg) * kFragBytes;
         *reinterpret_cast<uint4*>(frag + lane * 16) = make_uint4(d[0], d[1], d[2], d[3]);
         *reinterpret_cast<uint2*>(frag + 1024 + lane * 8) = make_uint2(d[4], d[5]);
+        if constexpr (ROT == FINO_MX_ROT_WEIGHT) e = e < -122 ? -127 : e - 5;
         if (row < rows) scales[mx_scale_index(row, col, rows_pad)] = (uint8_t)(e + 127);
     }
 }
@@ -329,27 +350,48 @@ extern "C" int64_t fino_mxfp6_scale_bytes(int64_t rows, int64_t cols) {
     return (cols / 128) * ((rows + 255) / 256 * 256) * 4;
 }
 
-extern "C" int fino_quantize_mxfp6(const void* x, void* q, void* scales, int64_t rows, int64_t cols, int64_t ldx,
-                                   int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_quantize_mxfp6: dtype %d", dtype);
-    FINO_CHECK(x && q && scales, FINO_ERR_ARG, "fino_quantize_mxfp6: null pointer");
+namespace {
+
+// the two quantiser entries: `fn` names the caller in the messages, ROT is its rotation (0 for fino_quantize_mxfp6)
+template <int ROT>
+int quantize_mxfp6_launch(const char* fn, const void* x, void* q, void* scales, int64_t rows, int64_t cols, int64_t ldx,
+                          int dtype, void* stream) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "%s: dtype %d", fn, dtype);
+    FINO_CHECK(x && q && scales, FINO_ERR_ARG, "%s: null pointer", fn);
     FINO_CHECK(rows > 0 && cols > 0 && cols % 128 == 0 && ldx % 8 == 0 && ldx >= cols, FINO_ERR_ARG,
-               "fino_quantize_mxfp6: cols must be a multiple of 128 (rows=%lld cols=%lld)", (long long)rows,
-               (long long)cols);
-    FINO_CHECK(fino_aligned16(x) && fino_aligned16(q), FINO_ERR_ARG, "fino_quantize_mxfp6: alignment");
+               "%s: cols must be a multiple of 128 (rows=%lld cols=%lld)", fn, (long long)rows, (long long)cols);
+    FINO_CHECK(fino_aligned16(x) && fino_aligned16(q), FINO_ERR_ARG, "%s: alignment", fn);
     const int64_t rows_pad = (rows + 255) / 256 * 256;
     const int64_t total = ((rows + 15) / 16) * (cols / 128);      // fragments = waves
     int64_t grid = (total + 3) / 4;
     if (grid > 262144) grid = 262144;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == FINO_BF16)
-        mxfp6_quantize_kernel<BF16><<<(unsigned)grid, 256, 0, st>>>((const uint16_t*)x, (uint8_t*)q, (uint8_t*)scales,
-                                                                    rows, cols, ldx, rows_pad);
+        mxfp6_quantize_kernel<BF16, ROT><<<(unsigned)grid, 256, 0, st>>>((const uint16_t*)x, (uint8_t*)q, (uint8_t*)scales,
+                                                                         rows, cols, ldx, rows_pad);
     else
-        mxfp6_quantize_kernel<F16><<<(unsigned)grid, 256, 0, st>>>((const uint16_t*)x, (uint8_t*)q, (uint8_t*)scales,
-                                                                   rows, cols, ldx, rows_pad);
-    FINO_LAUNCH_CHECK();
+        mxfp6_quantize_kernel<F16, ROT><<<(unsigned)grid, 256, 0, st>>>((const uint16_t*)x, (uint8_t*)q, (uint8_t*)scales,
+                                                                        rows, cols, ldx, rows_pad);
+    const hipError_t err = hipGetLastError();
+    FINO_CHECK(err == hipSuccess, FINO_ERR_LAUNCH, "%s: launch failed: %s", fn, hipGetErrorString(err));
     return FINO_OK;
+}
+
+}  // namespace
+
+extern "C" int fino_quantize_mxfp6(const void* x, void* q, void* scales, int64_t rows, int64_t cols, int64_t ldx,
+                                   int dtype, void* stream) {
+    return quantize_mxfp6_launch<0>("fino_quantize_mxfp6", x, q, scales, rows, cols, ldx, dtype, stream);
+}
+
+extern "C" int fino_quantize_mxfp6_rot(const void* x, void* q, void* scales, int64_t rows, int64_t cols, int64_t ldx,
+                                       int dtype, int mode, void* stream) {
+    FINO_CHECK(mode == FINO_MX_ROT_ACT || mode == FINO_MX_ROT_WEIGHT, FINO_ERR_ARG,
+               "fino_quantize_mxfp6_rot: mode %d (FINO_MX_ROT_ACT = 1 | FINO_MX_ROT_WEIGHT = 2)", mode);
+    return mode == FINO_MX_ROT_ACT
+               ? quantize_mxfp6_launch<FINO_MX_ROT_ACT>("fino_quantize_mxfp6_rot", x, q, scales, rows, cols, ldx, dtype, stream)
+               : quantize_mxfp6_launch<FINO_MX_ROT_WEIGHT>("fino_quantize_mxfp6_rot", x, q, scales, rows, cols, ldx, dtype,
+                                                           stream);
 }
 
 extern "C" int fino_gemm_mxfp6(const void* aq, const void* a_scales, const void* wq, const void* w_scales,

@@ -2,7 +2,9 @@
 
 MXFP8 (`fino_quantize_mxfp8` + `fino_gemm_mxfp8`): OCP e4m3 elements with one e8m0 scale per 32 K-elements, fp32 accumulate.
 MXFP6 (`fino_quantize_mxfp6` + `fino_gemm_mxfp6`): OCP e2m3 -- e4m3's three mantissa bits, the block scale supplies the range --
-with the same scales, at the FP4 matrix rate.  Weights are quantised once when the switch is turned on, activations per call.
+with the same scales, at the FP4 matrix rate; with `rotate=True` every MX block of both operands is rotated by the 32-point
+Walsh-Hadamard matrix first (`fino_quantize_mxfp6_rot`), which keeps the product and spreads outliers over their block.
+Weights are quantised once when the switch is turned on, activations per call.
 Attention, norms, modulation, embeddings and the output head stay in the model dtype.  There is no reference counterpart (SURVEY
 F11): the result is compared with the model's own bf16 forward (tests/test_mxfp8_gpu.py, tests/test_mxfp6_gpu.py).
 """
@@ -16,25 +18,37 @@ class MXLinearsMixin:
     _fp8 = {}             # (layer, key) -> (element bytes, MX scales) of that weight (this shared default is never written to)
     _fp8_pending = False  # MX was on when the parameters last moved / changed: re-quantise at the next forward
     _mx_fmt = 8           # element format of the `_fp8` entries: 8 = e4m3 (enable_mxfp8_linears), 6 = e2m3 (enable_mxfp6_linears)
+    _mx_rotate = False    # MXFP6 only: block-Hadamard rotation of both operands (enable_mxfp6_linears(rotate=True))
 
     def enable_mxfp8_linears(self, enabled=True):
         """Run the model's large linears (see its class docstring) on the MXFP8 path.  The LayerNorm in front of a linear and
-        the FFN's GELU emit MXFP8 activations directly (`_ln_q`, `_ffn_mxfp8`)."""
+        the FFN's GELU emit MXFP8 activations directly (`_ln_q`, `_ffn_mxfp8`).  There is no `rotate=` here: e4m3's four
+        exponent bits already absorb a block's outliers and the rotation of `enable_mxfp6_linears` gains it nothing measurable
+        (GEMM rel-RMS 0.0375 -> 0.0373 on outlier channels)."""
         return self._enable_mx_linears(8, enabled)
 
-    def enable_mxfp6_linears(self, enabled=True):
+    def enable_mxfp6_linears(self, enabled=True, rotate=False):
         """The same linears on the MXFP6 path.  Activations are quantised from the model dtype (no fused producers: LayerNorm
         and the FFN's GELU write the model dtype and `fino_quantize_mxfp6` follows).  One reduced precision at a time: raises
         ValueError while `enable_mxfp8_linears()` is on.  Independent of `enable_fp8_attention()` and `enable_cache()`;
-        `enable_mxfp6_linears(False)` returns the model to its model-dtype output bit for bit."""
-        return self._enable_mx_linears(6, enabled)
+        `enable_mxfp6_linears(False)` returns the model to its model-dtype output bit for bit.
+        rotate: every 32-element MX block of the weights and of the activations is rotated by the Walsh-Hadamard matrix before
+        it is quantised (`fino_quantize_mxfp6_rot`; exact algebra, the GEMM is unchanged): an outlier no longer sets the
+        scale of its block alone, which brings e2m3 back to MXFP8-class error on operands with outlier channels or heavy tails.
+        Calling again with another `rotate` while on re-quantises the weights."""
+        return self._enable_mx_linears(6, enabled, bool(rotate))
+
+    @property
+    def mxfp6_rotate(self):
+        """whether the MXFP6 linears are on with the block-Hadamard rotation"""
+        return self._mx_on and self._mx_fmt == 6 and self._mx_rotate
 
     @property
     def _mx_on(self):
         """on, or on and waiting for the next forward to re-quantise"""
         return bool(self._fp8) or self._fp8_pending
 
-    def _enable_mx_linears(self, fmt, enabled):
+    def _enable_mx_linears(self, fmt, enabled, rotate=False):
         if self._mx_on and self._mx_fmt != fmt:
             if not enabled:
                 return self                                     # the other precision's switch: nothing of this one to drop
@@ -42,16 +56,23 @@ class MXLinearsMixin:
                              f"time; call enable_mxfp{self._mx_fmt}_linears(False) first")
         self._fp8 = {}
         self._fp8_pending = False
+        self._mx_rotate = False
         if not enabled:
             return self
         self._mx_fmt = fmt
+        self._mx_rotate = rotate
         quantize = self._mx_quantize()
         for li, key, w in self._mx_linear_weights(self._packed or self._pack()):
             self._fp8[(li, key)] = quantize(w.detach().contiguous())
         return self
 
     def _mx_quantize(self):
-        return self.ops.quantize_mxfp6 if self._mx_fmt == 6 else self.ops.quantize_mxfp8
+        """the weight quantiser of the format that is on"""
+        if self._mx_fmt != 6:
+            return self.ops.quantize_mxfp8
+        if self._mx_rotate:                                     # (the keyword only when on: the unrotated calls stay as they were)
+            return lambda w: self.ops.quantize_mxfp6(w, rotate="weight")
+        return self.ops.quantize_mxfp6
 
     def _mx_invalidate(self):
         """The parameters may have changed or moved: drop the quantised weights.  They are re-quantised lazily, by the next
@@ -64,7 +85,7 @@ class MXLinearsMixin:
 
     def _mx_requantise_if_pending(self):
         if self._fp8_pending:
-            self._enable_mx_linears(self._mx_fmt, True)
+            self._enable_mx_linears(self._mx_fmt, True, self._mx_rotate)
 
     def _ln_q(self, li, key, mode, x, **ln):
         """the LayerNorm in front of linear (li, key) emitted directly as that linear's MXFP8 activations (fino_ln_mxfp8: one
@@ -93,7 +114,7 @@ class MXLinearsMixin:
             return o.gemm(x, w, b, epi, **kw)
         kw.pop("tile_m", None)                                  # (the MX GEMMs have one tile height)
         if self._mx_fmt == 6:
-            mx_gemm, (xq, xs) = o.gemm_mxfp6, o.quantize_mxfp6(x)
+            mx_gemm, (xq, xs) = o.gemm_mxfp6, (o.quantize_mxfp6(x, rotate="act") if self._mx_rotate else o.quantize_mxfp6(x))
         else:
             mx_gemm, (xq, xs) = o.gemm_mxfp8, (xq if xq is not None else o.quantize_mxfp8(x))
         if keep is not None:

@@ -869,16 +869,28 @@ def gemm_mxfp8_q(aq, a_scales, wq, w_scales, bias, epilogue=EPI_NONE, out=None):
     return q, s
 
 
-def quantize_mxfp6(x, out=None):
+MX_ROTATE = {"act": 1, "weight": 2}        # FINO_MX_ROT_ACT, FINO_MX_ROT_WEIGHT
+
+
+def quantize_mxfp6(x, out=None, rotate=None):
     """x [rows, cols] bf16|fp16 (cols % 128 == 0) -> (q uint8 [fino_mxfp6_bytes], scales uint8 [...]): OCP e2m3 elements packed
-    as the 16-row x 128-column fragments fino_gemm_mxfp6 reads (include/frameino_hip.h), one e8m0 scale per 32 K-elements."""
+    as the 16-row x 128-column fragments fino_gemm_mxfp6 reads (include/frameino_hip.h), one e8m0 scale per 32 K-elements.
+    rotate: None, or "act" | "weight" (fino_quantize_mxfp6_rot): every 32-element block is rotated by the Walsh-Hadamard
+    matrix before the rule, which spreads a block's outliers; "weight" also folds the 1/32 into its scales, so gemm_mxfp6 of an
+    "act" image and a "weight" image is the product of the unrotated operands, up to quantisation."""
+    if rotate is not None and rotate not in MX_ROTATE:
+        raise ValueError(f"quantize_mxfp6: rotate={rotate!r} must be None, 'act' or 'weight'")
     x2, rows, cols, ldx = _rows2d(x)
     nbytes = _lib.lib().fino_mxfp6_scale_bytes(rows, cols)
     if nbytes <= 0:
         raise ValueError(f"quantize_mxfp6: cols={cols} must be a positive multiple of 128")
     q, s = _mx_pair(_lib.lib().fino_mxfp6_bytes(rows, cols), nbytes, x.device, out)
-    _lib.check(_lib.lib().fino_quantize_mxfp6(_p(x2), _p(q), _p(s), rows, cols, ldx, _dt(x), _stream()),
-               "fino_quantize_mxfp6")
+    if rotate is None:
+        _lib.check(_lib.lib().fino_quantize_mxfp6(_p(x2), _p(q), _p(s), rows, cols, ldx, _dt(x), _stream()),
+                   "fino_quantize_mxfp6")
+    else:
+        _lib.check(_lib.lib().fino_quantize_mxfp6_rot(_p(x2), _p(q), _p(s), rows, cols, ldx, _dt(x), MX_ROTATE[rotate],
+                                                     _stream()), "fino_quantize_mxfp6_rot")
     q.mx_shape = (rows, cols)
     return q, s
 

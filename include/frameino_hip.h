@@ -599,11 +599,28 @@ int fino_gemm_mxfp8_q(const void* aq, const void* a_scales, const void* wq, cons
  *   [1024 + 8 l, 1024 + 8 l + 8).  Fragments of rows >= rows are not written (the last partly filled one repeats row
  *   rows - 1).  Both q and scales must be 16-byte aligned.  Quantise weights once, activations per call.
  * fino_gemm_mxfp6: C[M, N] = epilogue(dequant(Aq) . dequant(Wq)^T + bias); Aq / Wq as fino_quantize_mxfp6 writes them for
- *   [M, K] / [N, K]; K % 128 == 0, N % 8 == 0; bias / residual / C in out_dtype, epilogue arguments as fino_gemm. */
+ *   [M, K] / [N, K]; K % 128 == 0, N % 8 == 0; bias / residual / C in out_dtype, epilogue arguments as fino_gemm.
+ * Block-Hadamard rotation (fino_quantize_mxfp6_rot; opt-in, for operands with outliers): one large element of a block sets
+ *   the block scale and e2m3's two exponent bits push everything 60 x smaller into the subnormals; rotating every block of
+ *   BOTH operands by the 32-point Walsh-Hadamard matrix H (symmetric, H H = 32 I) spreads it over the block, and the sum over
+ *   blocks of (H a).(H w) / 32 is a.w, so fino_gemm_mxfp6 and fino_gemm_mxfp6_keep take the rotated images unchanged.
+ *   Rule: each block of 32 consecutive K-elements v[0..31], widened to fp32, becomes y = H v by five in-place butterfly
+ *   stages with strides s = 1, 2, 4, 8, 16 in that order; in a stage, for every i with (i & s) == 0,
+ *   (v[i], v[i+s]) <- (v[i] + v[i+s], v[i] - v[i+s]): fp32 adds and subtracts only, no scaling (a restatement in plain fp32
+ *   is bit-equal; fp16 inputs cannot overflow, 32 x 65504 fits fp32).  The rule above then runs on y: amax, e, RNE codes
+ *   with the sign of y.  mode FINO_MX_ROT_ACT stores the scale byte e + 127; mode FINO_MX_ROT_WEIGHT stores
+ *   (e - 5) + 127, the 2^-5 being the 1/32 of H H, so dequant(Aq) . dequant(Wq)^T needs no factor anywhere else (one
+ *   operand in each mode).  e - 5 is clamped at -127 and an all-zero block stays -127; a WEIGHT block with e < -122 would
+ *   lose its value to the clamp: amax < 2^-119 does not occur.  The codes of the two modes are the same.  Blocks holding
+ *   inf or NaN stay unspecified.  Layouts, sizes and alignment as fino_quantize_mxfp6; another mode -> FINO_ERR_ARG. */
+#define FINO_MX_ROT_ACT 1
+#define FINO_MX_ROT_WEIGHT 2
 int64_t fino_mxfp6_bytes(int64_t rows, int64_t cols);
 int64_t fino_mxfp6_scale_bytes(int64_t rows, int64_t cols);
 int fino_quantize_mxfp6(const void* x, void* q, void* scales, int64_t rows, int64_t cols, int64_t ldx, int dtype,
                         void* stream);
+int fino_quantize_mxfp6_rot(const void* x, void* q, void* scales, int64_t rows, int64_t cols, int64_t ldx, int dtype,
+                            int mode, void* stream);
 int fino_gemm_mxfp6(const void* aq, const void* a_scales, const void* wq, const void* w_scales, const void* bias,
                     void* c, int64_t m, int64_t n, int64_t k, int64_t ldc, int epilogue, const void* r, int64_t ldr,
                     const float* gate, int64_t mod_stride, const int32_t* sel, int out_dtype, void* stream);

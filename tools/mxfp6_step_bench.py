@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """The full-size Wan2.2-5B denoise step (bench.py's workload: 49 frames 704 x 1280, batch-2 CFG, eager) in bf16, with MXFP8
-linears and with MXFP6 linears, in one process on one box: the three precisions alternated, the sequence run twice, device
-events around `steps` steps after `warmup`, plus the in-run matrix peak (fino_diag_mfma_peak) so boxes can be compared.
-Usage: mxfp6_step_bench.py [--steps 6] [--warmup 2] [--layers N] > profiles/mxfp6_step.txt"""
+linears, with MXFP6 linears and with MXFP6 linears on rotated blocks (`enable_mxfp6_linears(rotate=True)`), in one process on
+one box: the precisions alternated, the sequence run `--reps` times, device events around `steps` steps after `warmup`, plus the
+in-run matrix peak (fino_diag_mfma_peak) so boxes can be compared.  With --parent-lib PATH the unrotated MXFP6 step also runs on
+another build of the library (the parent commit's), alternated with the rest: the rotation must not have moved it.
+Usage: mxfp6_step_bench.py [--steps 6] [--warmup 2] [--layers N] [--parent-lib PATH] > profiles/mxfp6_step.txt"""
 import argparse
+import ctypes
 import os
+import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,8 +24,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--layers", type=int, default=None, help="fewer layers (a quick look; not the step)")
-    ap.add_argument("--only", default=None, choices=["bf16", "mxfp8", "mxfp6"], help="one precision (for a kernel trace)")
+    ap.add_argument("--only", default=None, choices=["bf16", "mxfp8", "mxfp6", "mxfp6-rot"], help="one precision (for a kernel trace)")
+    ap.add_argument("--parent-lib", default=None, help="another build of libframeino_hip.so: the unrotated MXFP6 step runs on it too")
     a = ap.parse_args()
+    from frameino_amd import _lib
     from frameino_amd.configs import WAN22_5B_CFG
     from frameino_amd.pipeline_wan_i2v_motion_frameino import WanImageToVideoPipeline
     from frameino_amd.schedulers import FlowMatchEulerDiscreteScheduler
@@ -67,15 +73,27 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.steps
 
+    own, parent = _lib.lib(), None
+    if a.parent_lib:                               # the same ABI version; entries it lacks (newer ones) are simply not bound
+        parent = ctypes.CDLL(a.parent_lib)
+        assert parent.fino_version() == _lib.ABI_VERSION
+        for name, argtypes in _lib.SIGNATURES.items():
+            fn = getattr(parent, name, None)
+            if fn is not None:
+                fn.argtypes, fn.restype = argtypes, _lib._RESTYPES.get(name, ctypes.c_int)
+
     def switch(name):
         model.enable_mxfp8_linears(False)
         model.enable_mxfp6_linears(False)
+        _lib._lib = parent if name == "mxfp6-parent" else own       # what every ops call of the step goes through
         if name == "mxfp8":
             model.enable_mxfp8_linears()
-        elif name == "mxfp6":
+        elif name in ("mxfp6", "mxfp6-parent"):
             model.enable_mxfp6_linears()
+        elif name == "mxfp6-rot":
+            model.enable_mxfp6_linears(rotate=True)
 
-    names = [a.only] if a.only else ["bf16", "mxfp8", "mxfp6"]
+    names = [a.only] if a.only else ["bf16", "mxfp8", "mxfp6", "mxfp6-rot"] + (["mxfp6-parent"] if parent else [])
     print(f"# {torch.cuda.get_device_name(0)}  layers {cfg['num_layers']}  L = {(fg + 1) * (lh // 2) * (lw // 2)} x 2 (CFG)  "
           f"{a.steps} steps after {a.warmup}, eager")
     res = {n: [] for n in names}
@@ -83,10 +101,11 @@ def main():
         for n in names:
             switch(n)
             res[n].append(run())
-            print(f"rep {r}: {n:6s} linears  {res[n][-1]:8.2f} ms per step")
+            print(f"rep {r}: {n:12s} linears  {res[n][-1]:8.2f} ms per step")
+    switch("bf16")
     if not a.only:
         for n in names:
-            print(f"{n:6s}: min {min(res[n]):8.2f}  max {max(res[n]):8.2f} ms per step")
+            print(f"{n:12s}: min {min(res[n]):8.2f}  median {statistics.median(res[n]):8.2f}  max {max(res[n]):8.2f} ms per step")
         peak = bench.measured_mfma_peak(dev, 0.0)
         print(f"matrix peak in this run (fino_diag_mfma_peak, bf16 32x32x16): {peak['power_capped_peak']} TFLOP/s")
     return 0
