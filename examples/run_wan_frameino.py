@@ -72,6 +72,15 @@ def main():
     ap.add_argument("--taylorseer-warmup", type=int, default=3, metavar="W", help="the first W steps always compute")
     ap.add_argument("--taylorseer-lite", action="store_true",
                     help="lite mode: extrapolate the model's output itself; a predicted step runs no block at all")
+    ap.add_argument("--fastercache", type=int, nargs="?", const=5, default=None, metavar="N",
+                    help="diffusers' FasterCache (approximate; eager loop; quality on real checkpoints unmeasured): while the "
+                         "timestep is inside (-1, 641) the unconditional CFG branch runs on every N-th step (default 5) and is "
+                         "rebuilt in between from the conditional prediction plus the frequency-split difference of the last "
+                         "step that ran both.  Not together with --first-block-cache, --pab or --taylorseer")
+    ap.add_argument("--fastercache-attention", type=int, default=None, metavar="M",
+                    help="with --fastercache: also recompute every block's self-attention on every M-th step only while the "
+                         "timestep is inside (-1, 681), e.g. 2, and extrapolate it from its last two outputs in between (weight "
+                         "0.5).  Not together with --window-frames or --sparse-attention")
     ap.add_argument("--window-frames", type=int, default=None, metavar="N",
                     help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
                          "every query attends its own frame +- N neighbours plus the first frame and the ID frame, e.g. 2.  Not "
@@ -118,6 +127,8 @@ def main():
     a = ap.parse_args()
     if a.mxfp6_rotate and not a.mxfp6:
         ap.error("--mxfp6-rotate needs --mxfp6")
+    if a.fastercache_attention is not None and a.fastercache is None:
+        ap.error("--fastercache-attention needs --fastercache")
 
     from frameino_amd import _lib
     from frameino_amd.autoencoder_kl_wan import AutoencoderKLWan
@@ -191,6 +202,12 @@ def main():
         transformer.enable_cache(TaylorSeerCacheConfig(cache_interval=a.taylorseer, max_order=a.taylorseer_order,
                                                        disable_cache_before_step=a.taylorseer_warmup,
                                                        use_lite_mode=a.taylorseer_lite))
+    if a.fastercache is not None:
+        from frameino_amd.step_cache import FasterCacheConfig
+        transformer.enable_cache(FasterCacheConfig(unconditional_batch_skip_range=a.fastercache,
+                                                   spatial_attention_block_skip_range=a.fastercache_attention,
+                                                   attention_weight_callback=lambda _module: 0.5,
+                                                   current_timestep_callback=lambda: pipe.current_timestep))
     if a.mxfp6:                                    # after the LoRA merge: the merged weights are what is quantised
         transformer.enable_mxfp6_linears(rotate=a.mxfp6_rotate)
     if a.fp8_attention:

@@ -145,6 +145,9 @@ SIGNATURES = {
     "fino_taylor_update": [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "fino_taylor_predict": [c_void_p, c_i64, c_i64, c_int, ctypes.POINTER(c_float), c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64,
                             c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p],
+    "fino_fastercache_supported": [c_i64, c_i64, c_i64],
+    "fino_fastercache_delta": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p],
+    "fino_fastercache_apply": [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_i64, c_int, c_void_p],
 }
 
 

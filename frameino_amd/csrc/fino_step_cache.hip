@@ -22,6 +22,11 @@
 // updated in place on a computing step, and the Taylor extrapolation a predicting step writes or adds to the residual stream
 // with fino_pab_broadcast's arithmetic (include/frameino_hip.h spells out both).
 //
+// fino_fastercache_delta / fino_fastercache_apply (FasterCache): the frequency-split difference D = u - c of the two CFG
+// predictions of a step that ran both, DL = LP(D) and DH = D - DL (LP: the radial low-pass of every [H, W] plane), and the
+// unconditional prediction a later step rebuilds from its conditional one, T((c + aL * DL) + aH * DH).  The low-pass is a
+// direct DFT over the half disk of kept bins, one workgroup per plane with the plane in LDS (below).
+//
 // HBM-bound: 16-byte loads and stores, fp32 arithmetic, no contraction (the file is built with -ffp-contract=off).
 #include "fino_common.h"
 
@@ -296,6 +301,179 @@ __global__ __launch_bounds__(kThreads) void taylor_predict_kernel(const void* fa
     }
 }
 
+// ---- FasterCache: the radial low-pass of one [H, W] plane of D = float(u) - float(c), one workgroup per plane.
+// The kept bins are the disk fy^2 + fx^2 <= r^2 of signed frequencies; r = min(H, W) / 5 < min(H, W) / 2, so a bin and its
+// mirror (-fy, -fx) are distinct residues on both axes and only the half disk (fy > 0, or fy == 0 and fx >= 0) is
+// transformed: row fy of it holds fx = -w[fy] .. w[fy] (fx = 0 .. w[0] in row 0), w[fy] = floor(sqrt(r^2 - fy^2)), and the
+// bins are numbered row by row (`off[fy]` = first bin of row fy; bin 0 is the mean).
+//   analysis   X[b] = sum_p D[p] (cos - i sin)(2 pi (fy y / H + fx x / W)): one wave per bin, lane l takes the pixels
+//              p = l, l + 64, ... in order, then the xor butterfly -- a fixed order, no atomics
+//   synthesis  DL[p] = (X[0] + 2 sum_{b > 0} Re(X[b] e^{+i ..})) / (H W): one thread per pixel over the bins in order
+// The twiddle of a pixel is the product of two table entries, cos / sin(2 pi k / H) at k = fy y mod H and cos / sin(2 pi k / W) at
+// k = fx x mod W, the residues advanced by integer additions: no sine of a large argument, no division in the loops.
+// D is fp32 (and DH = D - DL one fp32 subtraction); the tables, the bins and both sums are fp64, so DL is the exact low-pass
+// rounded to fp32 once -- a direct fp32 sum would sit a few 1e-8 of max |D| off, which is above what a butterfly leaves on a
+// plane whose spectrum is one line.
+constexpr int kFcThreads = 512;
+constexpr int kFcMaxRows = 32;          // r + 1 <= 26: H W <= 16384 bounds min(H, W) by 128
+
+struct FcDisk {
+    int off[kFcMaxRows + 1];
+    int w[kFcMaxRows];
+};
+
+template <typename T>
+__global__ __launch_bounds__(kFcThreads) void fastercache_delta_kernel(const uint16_t* u, const uint16_t* c, float* d_low,
+                                                                       float* d_high, int H, int W, int r, int nbins, FcDisk disk) {
+    // all LDS in the dynamic region, fp64 first: a static array in front of it would shift the base off 8-byte alignment
+    extern __shared__ __attribute__((aligned(16))) double fc_smem[];
+    const int HW = H * W, tid = threadIdx.x;
+    const int th = r > 0 ? H : 1, tw = r > 0 ? W : 1;      // r == 0: the mean alone, every residue is 0
+    double* cy = fc_smem;               // [th] each ...
+    double* sy = cy + th;
+    double* cx = sy + th;               // ... and [tw] each
+    double* sx = cx + tw;
+    double* bins = sx + tw;             // [nbins][re, im]
+    float* D = (float*)(bins + 2 * nbins);      // [HW]
+    int* off = (int*)(D + HW);                  // [kFcMaxRows + 1]: first bin of every row of the half disk
+    int* roww = off + kFcMaxRows + 1;           // [kFcMaxRows]: w[fy]
+    const int64_t base = (int64_t)blockIdx.x * HW;
+    if (tid <= r + 1) off[tid] = disk.off[tid];
+    if (tid <= r) roww[tid] = disk.w[tid];
+    if ((HW & 7) == 0) {                // every plane starts on a 16-byte boundary
+        const uint4* u4 = (const uint4*)(u + base);
+        const uint4* c4 = (const uint4*)(c + base);
+        for (int i = tid; i < HW / 8; i += kFcThreads) {
+            float fu[8], fc[8];
+            unpack8<T>(u4[i], fu);
+            unpack8<T>(c4[i], fc);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) D[i * 8 + e] = fu[e] - fc[e];
+        }
+    } else {
+        for (int p = tid; p < HW; p += kFcThreads) D[p] = T::to_f32(u[base + p]) - T::to_f32(c[base + p]);
+    }
+    for (int k = tid; k < th; k += kFcThreads) {
+        const double a = 2.0 * k / H;
+        cy[k] = cospi(a);
+        sy[k] = sinpi(a);
+    }
+    for (int k = tid; k < tw; k += kFcThreads) {
+        const double a = 2.0 * k / W;
+        cx[k] = cospi(a);
+        sx[k] = sinpi(a);
+    }
+    __syncthreads();
+
+    const int wave = tid >> 6, lane = tid & 63;
+    const int dx = 64 % W, dy = 64 / W;
+    for (int b = wave; b < nbins; b += kFcThreads / 64) {          // wave-uniform: every lane reaches the butterfly
+        int fy = 0;
+        while (off[fy + 1] <= b) ++fy;
+        const int fx = (fy == 0 ? 0 : -roww[fy]) + (b - off[fy]);
+        const int fxm = fx < 0 ? fx + W : fx;                      // residues in [0, W) / [0, H): |fx| <= r < W, fy <= r < H
+        int x = lane % W, y = lane / W;
+        int ix = (fxm * x) % W, iy = (fy * y) % H;                 // (y may pass H for the lanes beyond the plane: they do not loop)
+        const int six = (fxm * dx) % W, siy = (fy * dy) % H;
+        double re = 0., im = 0.;
+        for (int p = lane; p < HW; p += 64) {
+            const double v = (double)D[p];
+            const double cc = cy[iy] * cx[ix] - sy[iy] * sx[ix];
+            const double ss = sy[iy] * cx[ix] + cy[iy] * sx[ix];
+            re += v * cc;
+            im -= v * ss;
+            x += dx;
+            ix += six;
+            if (ix >= W) ix -= W;
+            iy += siy;
+            if (iy >= H) iy -= H;
+            if (x >= W) {               // the next pixel of this lane lies one row further down
+                x -= W;
+                iy += fy;
+                if (iy >= H) iy -= H;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {          // the xor butterfly in fp64
+            re += __shfl_xor(re, o, 64);
+            im += __shfl_xor(im, o, 64);
+        }
+        if (lane == 0) {
+            bins[2 * b] = re;
+            bins[2 * b + 1] = im;
+        }
+    }
+    __syncthreads();
+
+    const double norm = (double)HW;
+    for (int p = tid; p < HW; p += kFcThreads) {
+        const int y = p / W, x = p - y * W;
+        double acc = 0.;
+        int b = 1, iy = 0, ix = 0;
+        for (int fx = 1; fx <= roww[0]; ++fx, ++b) {               // row 0: fx = 1 .. w[0] (bin 0, the mean, is added last)
+            ix += x;
+            if (ix >= W) ix -= W;
+            acc += bins[2 * b] * cx[ix] - bins[2 * b + 1] * sx[ix];
+        }
+        for (int fy = 1; fy <= r; ++fy) {
+            iy += y;
+            if (iy >= H) iy -= H;
+            const int w = roww[fy];
+            ix = ((W - w) * x) % W;
+            const double cyv = cy[iy], syv = sy[iy];
+            for (int fx = -w; fx <= w; ++fx, ++b) {
+                const double cc = cyv * cx[ix] - syv * sx[ix];
+                const double ss = syv * cx[ix] + cyv * sx[ix];
+                acc += bins[2 * b] * cc - bins[2 * b + 1] * ss;
+                ix += x;
+                if (ix >= W) ix -= W;
+            }
+        }
+        const float dl = (float)((bins[0] + 2. * acc) / norm);
+        d_low[base + p] = dl;
+        d_high[base + p] = D[p] - dl;
+    }
+}
+
+// out = T((float(cond) + a_low * d_low) + a_high * d_high): 8 elements per thread, the last n % 8 by one thread
+template <typename T>
+__global__ __launch_bounds__(kThreads) void fastercache_apply_kernel(const uint16_t* cond, const float* d_low, const float* d_high,
+                                                                     float a_low, float a_high, uint16_t* out, int64_t n) {
+    const int64_t nvec = n / 8, stride = (int64_t)gridDim.x * kThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < nvec; i += stride) {
+        float fc[8], lo[8], hi[8], fo[8];
+        unpack8<T>(((const uint4*)cond)[i], fc);
+        Plane<F32>::load(d_low, i * 8, lo);
+        Plane<F32>::load(d_high, i * 8, hi);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float t0 = a_low * lo[e], t1 = a_high * hi[e];
+            fo[e] = (fc[e] + t0) + t1;
+        }
+        ((uint4*)out)[i] = pack8<T>(fo);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int64_t j = nvec * 8; j < n; ++j) {
+            const float t0 = a_low * d_low[j], t1 = a_high * d_high[j];
+            out[j] = T::from_f32((T::to_f32(cond[j]) + t0) + t1);
+        }
+    }
+}
+
+// the half disk of radius r: row widths and first bins; -> the number of bins
+int fc_disk(int r, FcDisk& disk) {
+    int n = 0;
+    for (int fy = 0; fy <= r; ++fy) {
+        int w = 0;
+        while ((w + 1) * (w + 1) + fy * fy <= r * r) ++w;
+        disk.off[fy] = n;
+        disk.w[fy] = w;
+        n += fy == 0 ? w + 1 : 2 * w + 1;
+    }
+    disk.off[r + 1] = n;
+    return n;
+}
+
 int esize_of(int dtype) { return dtype == FINO_F32 ? 4 : 2; }
 
 // the factor planes of a TaylorSeer call: [n planes][rows][dim] of dtype fdtype, 16-byte aligned rows, planes that do not overlap
@@ -469,6 +647,65 @@ extern "C" int fino_taylor_predict(const void* factors, int64_t plane_stride, in
     const int grid = taylor_grid(nvec);
     hipStream_t st = (hipStream_t)stream;
     FINO_TAYLOR_DISPATCH(taylor_predict_kernel, factors, plane_stride, ldf, n, c, x, ldx, out, ldo, vpr, nvec, gate, mod_stride, sel);
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
+}
+
+extern "C" int fino_fastercache_supported(int64_t planes, int64_t height, int64_t width) {
+    return planes >= 1 && height >= 1 && width >= 1 && height <= FINO_FASTERCACHE_MAX_PLANE && width <= FINO_FASTERCACHE_MAX_PLANE &&
+           height * width <= FINO_FASTERCACHE_MAX_PLANE;
+}
+
+extern "C" int fino_fastercache_delta(const void* uncond, const void* cond, float* d_low, float* d_high, int64_t planes,
+                                      int64_t height, int64_t width, int dtype, void* stream) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_fastercache_delta: dtype %d", dtype);
+    FINO_CHECK(uncond && cond && d_low && d_high, FINO_ERR_ARG, "fino_fastercache_delta: null pointer");
+    FINO_CHECK(fino_aligned16(uncond) && fino_aligned16(cond) && fino_aligned16(d_low) && fino_aligned16(d_high), FINO_ERR_ARG,
+               "fino_fastercache_delta: 16-byte alignment required");
+    FINO_CHECK(fino_fastercache_supported(planes, height, width) && planes < (1LL << 31), FINO_ERR_UNSUPPORTED,
+               "fino_fastercache_delta: planes=%lld height=%lld width=%lld (each at least 1, height * width at most %d)",
+               (long long)planes, (long long)height, (long long)width, (int)FINO_FASTERCACHE_MAX_PLANE);
+    const int H = (int)height, W = (int)width, r = (H < W ? H : W) / 5;
+    FcDisk disk = {};
+    const int nbins = fc_disk(r, disk);
+    const size_t smem = sizeof(double) * ((r > 0 ? 2 * (size_t)(H + W) : 4) + 2 * (size_t)nbins) + sizeof(float) * (size_t)H * W +
+                        sizeof(int) * (2 * kFcMaxRows + 1);
+    constexpr int kMaxSmem = 144 * 1024;        // (the largest supported plane: 64 KiB of D, 53 KiB of tables, 17 KiB of bins)
+    FINO_CHECK(r + 1 <= kFcMaxRows && smem <= (size_t)kMaxSmem, FINO_ERR_UNSUPPORTED,
+               "fino_fastercache_delta: height=%d width=%d needs %zu bytes of LDS", H, W, smem);
+    static FinoPerDeviceOnce once_bf16, once_f16;
+    hipStream_t st = (hipStream_t)stream;
+    const uint16_t* u = (const uint16_t*)uncond;
+    const uint16_t* c = (const uint16_t*)cond;
+    if (dtype == FINO_BF16) {
+        const int rc = fino_max_smem_once(once_bf16, (const void*)fastercache_delta_kernel<BF16>, kMaxSmem, "fino_fastercache_delta");
+        if (rc != FINO_OK) return rc;
+        fastercache_delta_kernel<BF16><<<(int)planes, kFcThreads, smem, st>>>(u, c, d_low, d_high, H, W, r, nbins, disk);
+    } else {
+        const int rc = fino_max_smem_once(once_f16, (const void*)fastercache_delta_kernel<F16>, kMaxSmem, "fino_fastercache_delta");
+        if (rc != FINO_OK) return rc;
+        fastercache_delta_kernel<F16><<<(int)planes, kFcThreads, smem, st>>>(u, c, d_low, d_high, H, W, r, nbins, disk);
+    }
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
+}
+
+extern "C" int fino_fastercache_apply(const void* cond, const float* d_low, const float* d_high, float a_low, float a_high,
+                                      void* out, int64_t n, int dtype, void* stream) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_fastercache_apply: dtype %d", dtype);
+    FINO_CHECK(cond && d_low && d_high && out, FINO_ERR_ARG, "fino_fastercache_apply: null pointer");
+    FINO_CHECK(fino_aligned16(cond) && fino_aligned16(d_low) && fino_aligned16(d_high) && fino_aligned16(out), FINO_ERR_ARG,
+               "fino_fastercache_apply: 16-byte alignment required");
+    FINO_CHECK(n >= 1, FINO_ERR_ARG, "fino_fastercache_apply: n=%lld must be at least 1", (long long)n);
+    int64_t grid = (n / 8 + kThreads - 1) / kThreads;
+    grid = grid < 1 ? 1 : grid > 256 * 8 ? 256 * 8 : grid;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == FINO_BF16)
+        fastercache_apply_kernel<BF16><<<(int)grid, kThreads, 0, st>>>((const uint16_t*)cond, d_low, d_high, a_low, a_high,
+                                                                       (uint16_t*)out, n);
+    else
+        fastercache_apply_kernel<F16><<<(int)grid, kThreads, 0, st>>>((const uint16_t*)cond, d_low, d_high, a_low, a_high,
+                                                                      (uint16_t*)out, n);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }

@@ -1414,12 +1414,13 @@ def taylor_update(y, factors, n_old, delta, n_new=None):
     return n_new
 
 
-def taylor_predict(factors, n, k, x=None, gate=None, sel=None, out=None, dtype=None):
+def taylor_predict(factors, n, k, x=None, gate=None, sel=None, out=None, dtype=None, coef=None):
     """TaylorSeer prediction k steps after the last update from the first n factor planes (fino_taylor_predict):
     p = f_0 + sum_{i=1}^{n-1} f_i * float32(k**i / i!) in fp32 (the product and the sum each rounded, in that order), then
     out = T(p) (x None), T(x + p) (gate None) or T(fma(p, gate[sel], x)) -- the last two are `pab_broadcast` on y = p.
     factors [planes, rows, D] bf16 / fp16 / fp32; x / out row-strided [rows, D] bf16 / fp16 (`dtype` names T when neither is
-    given); out may alias x."""
+    given); out may alias x.  `coef` (at least n host floats, coef[0] is not used) replaces the weights float32(k**i / i!) --
+    FasterCache's self-attention extrapolation passes [1, w]."""
     if factors.dim() != 3:
         raise ValueError(f"taylor_predict: factors must be [planes, rows, D], got {tuple(factors.shape)}")
     rows, d = factors.shape[1:]
@@ -1443,10 +1444,85 @@ def taylor_predict(factors, n, k, x=None, gate=None, sel=None, out=None, dtype=N
     if gate is not None:
         assert gate.dtype == torch.float32 and gate.stride(-1) == 1 and gate.shape[-1] == d
     ms = gate.stride(0) if (gate is not None and gate.dim() == 2) else 0
-    coef = (_lib.c_float * TAYLOR_MAX_PLANES)(*taylor_coefficients(k, n))
+    if coef is not None and len(coef) < n:
+        raise ValueError(f"taylor_predict: {len(coef)} coefficients for n={n} planes")
+    coef = (_lib.c_float * TAYLOR_MAX_PLANES)(*(taylor_coefficients(k, n) if coef is None else [float(v) for v in coef[:n]]))
     ev = _timed("taylor_predict")
     _lib.check(_lib.lib().fino_taylor_predict(_p(factors), factors.stride(0), factors.stride(1), n, coef, _p(x),
                                               0 if x is None else x.stride(0), _p(out), out.stride(0), rows, d, _p(gate), ms,
                                               _p(sel), _dt(out), _dt3(factors), _stream()), "fino_taylor_predict")
     _taylor_bytes("taylor_predict", ev, rows * d * (n * factors.element_size() + (2 if x is not None else 1) * out.element_size()))
+    return out
+
+
+FASTERCACHE_MAX_PLANE = 16384              # FINO_FASTERCACHE_MAX_PLANE
+
+
+def fastercache_supported(planes, height, width):
+    """whether `fastercache_delta` takes [planes, height, width] (fino_fastercache_supported): every size at least 1 and one
+    fp32 plane within 64 KiB of LDS (height * width <= 16384)"""
+    return bool(_lib.lib().fino_fastercache_supported(int(planes), int(height), int(width)))
+
+
+def _fastercache_planes(t, what):
+    if not t.is_cuda:
+        raise RuntimeError("frameino_amd ops need CUDA(HIP) tensors; there is no CPU path")
+    if t.dim() < 2 or not t.is_contiguous():
+        raise ValueError(f"{what}: need a contiguous [..., H, W] tensor, got {tuple(t.shape)} strides {t.stride()}")
+    return t
+
+
+def fastercache_delta(uncond, cond, d_low=None, d_high=None):
+    """FasterCache's frequency-split difference of the two CFG predictions of one step (fino_fastercache_delta):
+    D = float(uncond) - float(cond), d_low = LP(D) and d_high = D - d_low in fp32, LP the radial low-pass of every [H, W] plane
+    (the DFT bins with fy^2 + fx^2 <= (min(H, W) // 5)^2 kept).  uncond / cond: contiguous [..., H, W] bf16 / fp16 of one
+    shape; d_low / d_high: fp32 of that shape (allocated when None).  Deterministic bit for bit.  -> (d_low, d_high)"""
+    _fastercache_planes(uncond, "fastercache_delta uncond")
+    _fastercache_planes(cond, "fastercache_delta cond")
+    if uncond.dtype not in (torch.bfloat16, torch.float16) or cond.dtype != uncond.dtype or cond.shape != uncond.shape \
+            or cond.device != uncond.device:
+        raise ValueError(f"fastercache_delta: uncond {tuple(uncond.shape)} {uncond.dtype} on {uncond.device} / cond "
+                         f"{tuple(cond.shape)} {cond.dtype} on {cond.device}: need one bf16 / fp16 shape on one device")
+    h, w = uncond.shape[-2:]
+    planes = uncond.numel() // max(h * w, 1)
+    if not fastercache_supported(planes, h, w):
+        raise ValueError(f"fastercache_delta: {planes} planes of {h} x {w} are not supported (every size at least 1, "
+                         f"H * W at most {FASTERCACHE_MAX_PLANE})")
+    d_low = torch.empty(uncond.shape, dtype=torch.float32, device=uncond.device) if d_low is None else d_low
+    d_high = torch.empty(uncond.shape, dtype=torch.float32, device=uncond.device) if d_high is None else d_high
+    for t, what in ((d_low, "d_low"), (d_high, "d_high")):
+        _fastercache_planes(t, f"fastercache_delta {what}")
+        if t.dtype != torch.float32 or t.shape != uncond.shape or t.device != uncond.device:
+            raise ValueError(f"fastercache_delta: {what} must be fp32 {tuple(uncond.shape)} on {uncond.device}, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    ev = _timed("fastercache_delta")
+    _lib.check(_lib.lib().fino_fastercache_delta(_p(uncond), _p(cond), _p(d_low), _p(d_high), planes, h, w, _dt(uncond), _stream()),
+               "fino_fastercache_delta")
+    _taylor_bytes("fastercache_delta", ev, uncond.numel() * (2 * uncond.element_size() + 8))
+    return d_low, d_high
+
+
+def fastercache_apply(cond, d_low, d_high, a_low, a_high, out=None):
+    """FasterCache's rebuilt unconditional prediction (fino_fastercache_apply): out = T((float(cond) + a_low * d_low) +
+    a_high * d_high), every multiply and add one fp32 operation, one rounding to T.  cond / out contiguous bf16 / fp16, d_low /
+    d_high contiguous fp32 of the same number of elements; a_low / a_high host floats (rounded to fp32).  out may be cond."""
+    for t, what in ((cond, "cond"), (d_low, "d_low"), (d_high, "d_high")):
+        if not t.is_cuda:
+            raise RuntimeError("frameino_amd ops need CUDA(HIP) tensors; there is no CPU path")
+        if not t.is_contiguous():
+            raise ValueError(f"fastercache_apply: {what} must be contiguous, got strides {t.stride()}")
+    if cond.dtype not in (torch.bfloat16, torch.float16) or d_low.dtype != torch.float32 or d_high.dtype != torch.float32:
+        raise ValueError(f"fastercache_apply: cond {cond.dtype} (bf16 / fp16), d_low {d_low.dtype} / d_high {d_high.dtype} (fp32)")
+    n = cond.numel()
+    if n < 1 or d_low.numel() != n or d_high.numel() != n:
+        raise ValueError(f"fastercache_apply: {n} / {d_low.numel()} / {d_high.numel()} elements (one count, at least 1)")
+    out = torch.empty_like(cond) if out is None else out
+    if out.dtype != cond.dtype or out.numel() != n or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"fastercache_apply: out must be a contiguous {cond.dtype} device tensor of {n} elements")
+    if not (out.device == cond.device == d_low.device == d_high.device):
+        raise ValueError("fastercache_apply: operands on different devices")
+    ev = _timed("fastercache_apply")
+    _lib.check(_lib.lib().fino_fastercache_apply(_p(cond), _p(d_low), _p(d_high), float(a_low), float(a_high), _p(out), n,
+                                                 _dt(cond), _stream()), "fino_fastercache_apply")
+    _taylor_bytes("fastercache_apply", ev, n * (2 * cond.element_size() + 8))
     return out

@@ -167,21 +167,27 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
             reset()
 
     def _step_cache_check(self, batch):
-        """the limits of the step caches (first-block caching, Pyramid Attention Broadcast, TaylorSeer), checked before any work (and before
+        """the limits of the step caches (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache), checked before any work (and before
         any collective: a parallel plan and the cache are configured by the same script on every rank, so every rank raises)"""
         if not getattr(self.transformer, "is_cache_enabled", False):
             return False
         pab = bool(getattr(self.transformer, "_pab_on", False))
         taylor = bool(getattr(self.transformer, "_taylor_on", False))
-        what = "Pyramid Attention Broadcast" if pab else "TaylorSeer caching" if taylor else "first-block caching"
+        faster = bool(getattr(self.transformer, "_faster_on", False))
+        what = ("Pyramid Attention Broadcast" if pab else "TaylorSeer caching" if taylor else "FasterCache" if faster
+                else "first-block caching")
         if getattr(self, "parallel", None) is not None:
             raise NotImplementedError(f"{what} runs on one GPU; this pipeline has a parallel plan")
         if self.use_hip_graph is True and taylor:
             raise RuntimeError("use_hip_graph=True with TaylorSeer caching: whether a step computes or predicts changes from step "
                                "to step on the host's schedule, which one captured step cannot contain (the loop runs eagerly; "
                                "use_hip_graph=None or False)")
-        if batch > 1 and not pab and not taylor:
-            # (Pyramid Attention Broadcast decides from the step counter and the timestep alone, TaylorSeer from the step counter:
+        if self.use_hip_graph is True and faster:
+            raise RuntimeError("use_hip_graph=True with FasterCache: whether a step runs the unconditional branch and its "
+                               "self-attention branches changes from step to step on the host's schedule, which one captured "
+                               "step cannot contain (the loop runs eagerly; use_hip_graph=None or False)")
+        if batch > 1 and not pab and not taylor and not faster:
+            # (Pyramid Attention Broadcast and FasterCache decide from the step counter and the timestep alone, TaylorSeer from the step counter:
             # the samples of a batch, run one at a time from fresh state, decide as diffusers' joint run does)
             raise NotImplementedError("first-block caching with a batch (a list of prompts, num_videos_per_prompt > 1): diffusers "
                                       "decides jointly over the batch, this pipeline runs the samples one at a time")
@@ -432,14 +438,26 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
                 self._streams = (torch.cuda.Stream(), torch.cuda.Stream())
             main = torch.cuda.current_stream()
             s1, s2 = self._streams
-            s1.wait_stream(main)
-            s2.wait_stream(main)
-            with torch.cuda.stream(s1):
+            faster = bool(getattr(tr, "_faster_on", False))
+            if faster and tr._faster_will_skip():
+                # FasterCache, a skipping step: the cond forward alone, then the rebuild that reads its prediction -- one stream
                 pc = fwd("cond", st.pe)
-            with torch.cuda.stream(s2):
                 pu = fwd("uncond", st.ne)
-            main.wait_stream(s1)
-            main.wait_stream(s2)
+            else:
+                s1.wait_stream(main)
+                s2.wait_stream(main)
+                tr._faster_defer_delta = faster          # (the delta reads both predictions: taken after the streams join)
+                try:
+                    with torch.cuda.stream(s1):
+                        pc = fwd("cond", st.pe)
+                    with torch.cuda.stream(s2):
+                        pu = fwd("uncond", st.ne)
+                finally:
+                    tr._faster_defer_delta = False
+                main.wait_stream(s1)
+                main.wait_stream(s2)
+                if faster:
+                    tr._faster_delta_now()
         elif st.cfg and self.batch_cfg and st.pe_ne is not None and getattr(tr, "parallel", None) is None:
             # both CFG branches as ONE batch-2 forward (rows of the same GEMMs: identical per-row arithmetic, twice
             # the tiles per launch, weights streamed once).  The reference makes two calls (:862-882); with the first-block
@@ -508,7 +526,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         """reference :809-913.  Returns the final latents [B, C, F, h, w] fp32.  The loop state is one sample's (the app
         and the evaluation scripts run batch 1); a batch -- a list of prompts, num_videos_per_prompt > 1 -- runs sample by sample:
         the samples of the reference's batched loop never meet, every one sees the noise row `prepare_latents` drew for it.
-        With a step cache (first-block caching, Pyramid Attention Broadcast) every call -- every sample -- starts from fresh
+        With a step cache (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache) every call -- every sample -- starts from fresh
         cache state."""
         cached = self._step_cache_check(latents.shape[0])
         win_eager = self._window_attention_check()
@@ -540,6 +558,9 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
             dts = self.scheduler.dts.to(dev)
         ts_dev = timesteps.to(dev).float()
         self._num_timesteps = len(timesteps)
+        # FasterCache reads `current_timestep` on the host up to three times per step: a host copy of the schedule, taken once,
+        # keeps those reads from waiting for the device
+        ts_host = timesteps.cpu() if cached and getattr(self.transformer, "_faster_on", False) else None
 
         from .graph_step import StepGraph, capture_error_mode, groups_capturable
         stepper = StepGraph(lambda: self._step(st), self.use_hip_graph,
@@ -550,7 +571,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         for i in range(len(timesteps)):
             if self._interrupt:
                 continue
-            self._current_timestep = timesteps[i]
+            self._current_timestep = timesteps[i] if ts_host is None else ts_host[i]
             st.t_rows[1:2].copy_(ts_dev[i:i + 1])          # device-to-device: no host sync
             if st.unipc is not None:
                 st.coef.copy_(coefs[i])

@@ -1,8 +1,9 @@
 """Step caching of the Wan DiT: diffusers' `CacheMixin` (diffusers/models/cache_utils.py), which the reference's
 WanTransformer3DModel inherits (architecture/transformer_wan.py:28, :353) and whose state its FrameINO loop keys by
-`cache_context("cond")` / `("uncond")` (pipelines/pipeline_wan_i2v_motion_FrameINO.py:862, :873), with three of its configs:
+`cache_context("cond")` / `("uncond")` (pipelines/pipeline_wan_i2v_motion_FrameINO.py:862, :873), with four of its configs:
 `FirstBlockCacheConfig` (diffusers/hooks/first_block_cache.py), `PyramidAttentionBroadcastConfig`
-(diffusers/hooks/pyramid_attention_broadcast.py) and `TaylorSeerCacheConfig` (diffusers/hooks/taylorseer_cache.py).  One at a
+(diffusers/hooks/pyramid_attention_broadcast.py), `TaylorSeerCacheConfig` (diffusers/hooks/taylorseer_cache.py) and
+`FasterCacheConfig` (diffusers/hooks/faster_cache.py).  One at a
 time: a second `enable_cache` raises, as in diffusers.
 
 First-block caching.  The rule, per forward under context c (T = the model dtype; h0 = input of block 0, h1 = its output, hN = the last block's):
@@ -57,6 +58,37 @@ runs no embedding, no block and no head, it writes T(p) and unpatchifies.  The d
 device data, no timestep callback.  `cache_log` gets `(context, s, computed)` per forward.  The model asks `_taylor_begin` for
 a forward's decisions and `_taylor_buffer` for a hooked tensor's factor planes; the state's lifetime is Pyramid Attention
 Broadcast's.  Selecting modules by `cache_identifiers` / `skip_predict_identifiers` is not implemented.
+
+FasterCache.  This project's restatement with diffusers' names (`FasterCacheConfig`, diffusers/hooks/faster_cache.py; diffusers is
+not vendored by the reference): the rule below is the contract, and every decision sits in a pure function
+(`fastercache_uncond_decide`, `fastercache_weights`, `fastercache_attention_decide`).  State per context, "cond" and "uncond" as
+the loop names them; i = the 0-based count of forwards of that context since the last reset (for "uncond" a skipped forward
+counts too), t = float(current_timestep_callback()), read once per forward.
+
+  The unconditional branch.  "uncond" skips its stack iff  has_delta and i > 0 and lo < t < hi (unconditional_batch_timestep_skip_range)
+  and i % unconditional_batch_skip_range != 0 and not is_guidance_distilled (a skip range of None: never).  With c, u the model's
+  returned predictions [C, F, H, W] of one step under "cond" / "uncond" and LP the radial low-pass of every (c, f) plane (the
+  2-D DFT bins with fy^2 + fx^2 <= (min(H, W) // 5)^2 kept):
+    computing step (both ran):  D = float(u) - float(c), DL = LP(D), DH = D - DL (fp32; ops.fastercache_delta), aL = aH = 1
+    skipping step:              wL = low_frequency_weight_callback(model), or alpha_low_frequency while t lies strictly inside
+                                low_frequency_weight_update_timestep_range, else 1 (wH likewise); aL = f32(aL * wL),
+                                aH = f32(aH * wH) -- the weights compound over consecutive skips --, and
+                                u' = T((float(c) + aL * DL) + aH * DH)  (ops.fastercache_apply) on this step's c
+  The model's forward knows three call shapes: batch 2 with `_cache_contexts=("cond", "uncond")` (a skipping step launches the
+  stack for the "cond" element alone and row 1 of the result is u'); sequential calls under `cache_context("cond")` then
+  `("uncond")` (the "uncond" call of a skipping step returns u' from the conditional prediction the state holds -- by
+  reference -- for the same i, RuntimeError if "cond" has not run forward i); anything else: this part is inert.
+
+  Self-attention, on TaylorSeer's hook points and kernels.  The hooked tensor is every block's attn1 return value
+  y = T(acc + bias); attn2 always computes.  A forward computes iff spatial_attention_block_skip_range is None or there is no
+  plane yet or t is not strictly inside spatial_attention_timestep_skip_range or i % N == 0 or this context did not run its
+  stack at forward i - 1.  A computing forward: ops.taylor_update(y, planes, n, delta=1, n_new=min(n + 1, 2)), so f_0 = y_1 and
+  f_1 = T(y_1 - y_0); a skipping one runs no attn1 branch and adds ops.taylor_predict(planes, n, coef=[1, w]),
+  w = float(attention_weight_callback(attn1 module)), to the residual stream with TaylorSeer's epilogue forms.
+
+  `cache_log` gets `(context, i, t, stack_ran, attention_computed)` per forward and context; the state's lifetime is Pyramid
+  Attention Broadcast's.  Temporal attention, module selection by identifier and `tensor_format` other than "BCFHW" match
+  nothing on this model.
 
 The CogVideoX DiT (`PyramidAttentionBroadcastMixin`) takes Pyramid Attention Broadcast alone, with the same rule and state: its one
 attention layer per block, the joint text + video attn1, is the "spatial" kind, and a call's whole batch is one segment under one
@@ -113,8 +145,41 @@ class TaylorSeerCacheConfig:
     use_lite_mode: bool = False
 
 
+
+@dataclasses.dataclass
+class FasterCacheConfig:
+    """diffusers.FasterCacheConfig: the unconditional CFG branch runs on every `unconditional_batch_skip_range`-th step while the
+    timestep lies strictly inside `unconditional_batch_timestep_skip_range` and is rebuilt in between from the conditional
+    prediction plus the frequency-split difference of the last step that ran both; every block's self-attention recomputes on
+    every `spatial_attention_block_skip_range`-th forward inside `spatial_attention_timestep_skip_range` and is extrapolated
+    from its last two outputs in between.  The temporal fields match no layer of the Wan DiT; the `*_block_identifiers` are
+    accepted and ignored."""
+    spatial_attention_block_skip_range: Optional[int] = 2
+    temporal_attention_block_skip_range: Optional[int] = None
+    spatial_attention_timestep_skip_range: Tuple[int, int] = (-1, 681)
+    temporal_attention_timestep_skip_range: Tuple[int, int] = (-1, 681)
+    low_frequency_weight_update_timestep_range: Tuple[int, int] = (99, 901)
+    high_frequency_weight_update_timestep_range: Tuple[int, int] = (-1, 301)
+    alpha_low_frequency: float = 1.1
+    alpha_high_frequency: float = 1.1
+    unconditional_batch_skip_range: Optional[int] = 5
+    unconditional_batch_timestep_skip_range: Tuple[int, int] = (-1, 641)
+    spatial_attention_block_identifiers: Tuple[str, ...] = ("blocks", "transformer_blocks", "single_transformer_blocks")
+    temporal_attention_block_identifiers: Tuple[str, ...] = ("temporal_transformer_blocks",)
+    attention_weight_callback: Optional[Callable[[Any], float]] = None
+    low_frequency_weight_callback: Optional[Callable[[Any], float]] = None
+    high_frequency_weight_callback: Optional[Callable[[Any], float]] = None
+    tensor_format: str = "BCFHW"
+    is_guidance_distilled: bool = False
+    current_timestep_callback: Optional[Callable[[], Any]] = None
+
+
 # the other configs diffusers' CacheMixin applies: recognised, not implemented here
-_OTHER_DIFFUSERS_CONFIGS = ("FasterCacheConfig", "MagCacheConfig", "TeaCacheConfig")
+_OTHER_DIFFUSERS_CONFIGS = ("MagCacheConfig", "TeaCacheConfig")
+_FASTER_NAME = "FasterCacheConfig"
+_FASTER_REQUIRED = ("spatial_attention_block_skip_range", "unconditional_batch_skip_range", "current_timestep_callback")
+_FASTER_DEFAULTS = {f.name: f.default for f in dataclasses.fields(FasterCacheConfig)}
+FASTER_CONTEXTS = ("cond", "uncond")    # the cache contexts of the denoising loop the unconditional-branch rule pairs
 _TAYLOR_NAME = "TaylorSeerCacheConfig"
 _TAYLOR_REQUIRED = ("cache_interval", "disable_cache_before_step", "max_order")
 TAYLOR_MAX_ORDER = 3                     # ops.TAYLOR_MAX_PLANES - 1
@@ -172,6 +237,95 @@ def taylorseer_decide(s, n_factors, cfg):
     return n_factors == 0 or s < w or (s - (w - 1)) % n == 0 or (after is not None and s >= after)
 
 
+
+def _is_fastercache_config(config):
+    return type(config).__name__ == _FASTER_NAME and all(hasattr(config, a) for a in _FASTER_REQUIRED)
+
+
+def _fc(cfg, name):
+    """a field of a FasterCache config, diffusers' default where a duck-typed object lacks it"""
+    return getattr(cfg, name, _FASTER_DEFAULTS[name])
+
+
+def _fastercache_validate(config):
+    """ValueError for a field outside its range or a missing `current_timestep_callback`"""
+    for name in ("spatial_attention_block_skip_range", "temporal_attention_block_skip_range", "unconditional_batch_skip_range"):
+        v = _fc(config, name)
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
+            raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need an integer of at least 1, or None")
+    for name in ("spatial_attention_timestep_skip_range", "temporal_attention_timestep_skip_range",
+                 "unconditional_batch_timestep_skip_range", "low_frequency_weight_update_timestep_range",
+                 "high_frequency_weight_update_timestep_range"):
+        v = _fc(config, name)
+        ok = isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, (int, float)) and not isinstance(e, bool)
+                                                                  and e == e for e in v)
+        if not ok or not v[0] < v[1]:
+            raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need a pair (lo, hi) of numbers with lo < hi")
+    for name in ("alpha_low_frequency", "alpha_high_frequency"):
+        v = _fc(config, name)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= float(v) < float("inf")):
+            raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need a finite number of at least 0")
+    for name in ("attention_weight_callback", "low_frequency_weight_callback", "high_frequency_weight_callback"):
+        v = _fc(config, name)
+        if v is not None and not callable(v):
+            raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need a callable or None")
+    if _fc(config, "tensor_format") != "BCFHW":
+        raise ValueError(f"FasterCacheConfig.tensor_format = {_fc(config, 'tensor_format')!r}: this model's predictions are "
+                         f'"BCFHW" (the low-pass runs over the (H, W) planes)')
+    if config.current_timestep_callback is None:
+        raise ValueError("The `current_timestep_callback` function must be provided in the configuration to apply FasterCache: "
+                         "it returns the denoising loop's current timestep (`lambda: pipe.current_timestep`).")
+
+
+def _f32(x):
+    """x rounded to fp32 (nearest even), as a Python float"""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def _strictly_inside(t, rng):
+    return rng[0] < t < rng[1]
+
+
+def fastercache_uncond_decide(i, t, has_delta, cfg):
+    """True: forward `i` (0-based, since the last reset) of the "uncond" context at timestep `t` SKIPS its stack and is rebuilt
+    from the conditional prediction.  Skip iff there is a delta, i > 0, t lies strictly inside
+    `unconditional_batch_timestep_skip_range`, i is no multiple of `unconditional_batch_skip_range`, the model is not
+    guidance-distilled and the skip range is not None."""
+    n = _fc(cfg, "unconditional_batch_skip_range")
+    if n is None or bool(_fc(cfg, "is_guidance_distilled")) or not has_delta or i <= 0:
+        return False
+    return _strictly_inside(t, _fc(cfg, "unconditional_batch_timestep_skip_range")) and i % int(n) != 0
+
+
+def fastercache_weights(t, a_low, a_high, cfg, model=None):
+    """(aL, aH) of a skipping step at timestep `t` from the weights so far: aL = f32(aL * wL) with
+    wL = low_frequency_weight_callback(model) if given, else alpha_low_frequency while t lies strictly inside
+    `low_frequency_weight_update_timestep_range`, else 1 (aH likewise): the weights compound over consecutive skips."""
+    out = []
+    for a, cb, alpha, rng in ((a_low, "low_frequency_weight_callback", "alpha_low_frequency",
+                               "low_frequency_weight_update_timestep_range"),
+                              (a_high, "high_frequency_weight_callback", "alpha_high_frequency",
+                               "high_frequency_weight_update_timestep_range")):
+        call = _fc(cfg, cb)
+        if call is not None:
+            w = float(call(model))
+        else:
+            w = float(_fc(cfg, alpha)) if _strictly_inside(t, _fc(cfg, rng)) else 1.0
+        out.append(float(torch.tensor(float(a), dtype=torch.float32) * torch.tensor(w, dtype=torch.float32)))
+    return tuple(out)
+
+
+def fastercache_attention_decide(i, t, n_planes, ran_prev, cfg):
+    """True: forward `i` of a context at timestep `t` COMPUTES its self-attention branches.  Compute iff
+    `spatial_attention_block_skip_range` (N) is None, or no plane is kept yet, or t is not strictly inside
+    `spatial_attention_timestep_skip_range`, or i % N == 0, or the context did not run its stack at forward i - 1 (an "uncond"
+    forward that runs on every fifth step must not extrapolate outputs that old)."""
+    n = _fc(cfg, "spatial_attention_block_skip_range")
+    if n is None or n_planes == 0 or not ran_prev:
+        return True
+    return (not _strictly_inside(t, _fc(cfg, "spatial_attention_timestep_skip_range"))) or i % int(n) == 0
+
+
 def pab_decide(iteration, timestep, has_cache, block_skip_range, timestep_skip_range):
     """True: the attention module computes on this forward; False: it hands out its cached output."""
     lo, hi = timestep_skip_range
@@ -206,7 +360,8 @@ class FirstBlockCacheMixin:
     TaylorSeer: per context a counter, the number of valid factor planes and the last computing forward, per hooked tensor
     a [max_order + 1, rows, D] buffer in the factor dtype, allocated by the first forward that computes; `cache_log` holds
     `(context, step, computed)`, with the same lifetime."""
-    _cache_configs_implemented = "FirstBlockCacheConfig, PyramidAttentionBroadcastConfig and TaylorSeerCacheConfig are"
+    _cache_configs_implemented = ("FirstBlockCacheConfig, PyramidAttentionBroadcastConfig, TaylorSeerCacheConfig and "
+                                  "FasterCacheConfig are")
     _step_cache_config = None
     _step_cache_states = None
     _step_cache_log_fresh = True
@@ -254,6 +409,19 @@ class FirstBlockCacheMixin:
             raise NotImplementedError(f"{name}: this object carries the name but not the `cache_interval`, "
                                       f"`disable_cache_before_step` and `max_order` attributes of diffusers' config, so it "
                                       f"cannot be applied")
+        if _is_fastercache_config(config):
+            _fastercache_validate(config)
+            self._fastercache_refusals(config)
+            if _fc(config, "spatial_attention_block_skip_range") is not None and _fc(config, "attention_weight_callback") is None:
+                warnings.warn("FasterCacheConfig: no `attention_weight_callback` provided; defaulting to 0.5 for every "
+                              "attention module.", stacklevel=2)
+            self._step_cache_config = config
+            self._reset_stateful_cache()
+            return
+        if name == _FASTER_NAME:
+            raise NotImplementedError(f"{name}: this object carries the name but not the `spatial_attention_block_skip_range`, "
+                                      f"`unconditional_batch_skip_range` and `current_timestep_callback` attributes of "
+                                      f"diffusers' FasterCacheConfig, so it cannot be applied")
         if name in _OTHER_DIFFUSERS_CONFIGS or (name.endswith("CacheConfig") and
                                                  type(config).__module__.split(".")[0] == "diffusers"):
             raise NotImplementedError(f"{name} is not implemented on this model; {self._cache_configs_implemented}")
@@ -277,8 +445,8 @@ class FirstBlockCacheMixin:
         """None when no cache is enabled, else [(context, first row, end row)] of the call's [b * n, D] rows: one segment per
         batch element when `contexts` names one context each (the pipeline's CFG-batched call), else one joint segment under
         the current `cache_context`."""
-        if self._step_cache_config is None or self._pab_on or self._taylor_on:
-            return None                       # (Pyramid Attention Broadcast, TaylorSeer: the first-block code stays inert)
+        if self._step_cache_config is None or self._pab_on or self._taylor_on or self._faster_on:
+            return None                       # (Pyramid Attention Broadcast, TaylorSeer, FasterCache: the first-block code stays inert)
         return self._context_segments(b, n, contexts)
 
     def _context_segments(self, b, n, contexts):
@@ -456,6 +624,142 @@ class FirstBlockCacheMixin:
             buf = seg.state.buffers[key] = torch.empty((plan.planes, seg.r1 - seg.r0, d), dtype=plan.factor_dtype, device=device)
         return buf
 
+    # ---------------------------------------------------------------- FasterCache
+    @property
+    def _faster_on(self):
+        return self._step_cache_config is not None and _is_fastercache_config(self._step_cache_config)
+
+    @property
+    def _faster_attention(self):
+        """whether FasterCache hooks the self-attention branches"""
+        return self._faster_on and _fc(self._step_cache_config, "spatial_attention_block_skip_range") is not None
+
+    def _fastercache_refusals(self, config):
+        """what the model cannot combine with FasterCache, raised by `enable_cache` (the model overrides this)"""
+
+    def _faster_state(self, name, key):
+        if self._step_cache_log_fresh or not isinstance(self.cache_log, list):
+            self.cache_log = []
+            self._step_cache_log_fresh = False
+        if self._step_cache_states is None:
+            self._step_cache_states = {}
+        st = self._step_cache_states.get(name)
+        if st is None or st.key != key:          # first use, or another shape / dtype / device: start over
+            st = self._step_cache_states[name] = SimpleNamespace(
+                key=key, steps=0, ran_prev=False, n=0, buffers={},            # the counter; the self-attention planes
+                out=None, out_i=-1,                                           # this context's last prediction, by reference
+                d_low=None, d_high=None, has_delta=False, a_low=1.0, a_high=1.0)      # ("uncond": the delta and its weights)
+        return st
+
+    def _faster_will_skip(self):
+        """whether the NEXT "uncond" forward of the denoising loop skips its stack (nothing is advanced): the loop's two-stream
+        path asks before it forks"""
+        if not self._faster_on:
+            return False
+        cfg = self._step_cache_config
+        st = (self._step_cache_states or {}).get("uncond")
+        if st is None:
+            return False
+        return bool(fastercache_uncond_decide(st.steps, float(cfg.current_timestep_callback()), st.has_delta, cfg))
+
+    def _faster_begin(self, b, shape, dtype, device, contexts=None):
+        """The decisions of one forward under FasterCache, taken before anything is launched: None when it is off, else a
+        plan with `.t` (the timestep callback, read ONCE), `.mode` -- "batched" (batch 2 as ("cond", "uncond")), "cond" /
+        "uncond" (a batch-1 call under that cache context) or None (any other call: the unconditional-branch rule is inert) --,
+        `.skip` (this call's "uncond" does not run the stack) and `.entries` = one per context of the call with `.name`,
+        `.state`, `.i`, `.stack` (whether its stack runs) and `.compute` (whether its self-attention branches compute).
+        Advances every context's counter and appends `(context, i, t, stack_ran, attention_computed)` to `cache_log`."""
+        if not self._faster_on:
+            return None
+        cfg = self._step_cache_config
+        names = tuple(contexts) if contexts is not None else None
+        if names is not None and (len(names) != b or len(set(names)) != b):
+            raise ValueError(f"_cache_contexts {names}: need {b} distinct names, one per batch element")
+        if names is None:
+            if self._ctx_name is None:
+                raise ValueError("No context is set. Please set a context before retrieving the state.")
+            names = (self._ctx_name,)
+        t = float(cfg.current_timestep_callback())
+        mode = None
+        if _fc(cfg, "unconditional_batch_skip_range") is not None and not bool(_fc(cfg, "is_guidance_distilled")):
+            if contexts is not None and names == FASTER_CONTEXTS:
+                mode = "batched"
+            elif contexts is None and b == 1 and names[0] in FASTER_CONTEXTS:
+                mode = names[0]
+        key = (tuple(shape), dtype, str(device), b if contexts is None else 1)
+        plan = SimpleNamespace(t=t, mode=mode, skip=False, entries=[], cfg=cfg)
+        for name in names:
+            st = self._faster_state(name, key)
+            i = st.steps
+            stack = True
+            if name == "uncond" and mode in ("batched", "uncond"):
+                stack = not fastercache_uncond_decide(i, t, st.has_delta, cfg)
+                plan.skip = not stack
+            compute = stack and bool(fastercache_attention_decide(i, t, st.n, st.ran_prev, cfg))
+            self.cache_log.append((name, i, t, stack, compute))
+            st.steps += 1
+            plan.entries.append(SimpleNamespace(name=name, state=st, i=i, stack=stack, compute=compute))
+            st.ran_prev = stack
+        return plan
+
+    def _faster_attention_plan(self, faster, b, n, d, dtype, device):
+        """the self-attention decisions of the forward as a plan of TaylorSeer's shape (`_taylor_begin`), for the contexts whose
+        stack runs: only the "self" kind is hooked, a computing segment updates two planes with delta 1, a skipping one
+        predicts with the coefficients [1, w]; None when the self-attention is not hooked"""
+        if not self._faster_attention:
+            return None
+        entries = [e for e in faster.entries if e.stack]
+        joint = len(entries) == 1 and b > 1                      # a batch under one context: one segment for all rows
+        plan = SimpleNamespace(segs=[], hooked={"self": True, "cross": False}, taylor=faster.cfg, planes=2, factor_dtype=dtype,
+                               lite=False, faster=True)
+        for j, e in enumerate(entries):
+            st = e.state
+            r0, r1 = (0, b * n) if joint else (j * n, (j + 1) * n)
+            n_new = min(st.n + 1, 2) if e.compute else st.n
+            plan.segs.append(SimpleNamespace(name=e.name, r0=r0, r1=r1, state=st, compute={"self": e.compute, "cross": True},
+                                             s=e.i, k=1, n_old=st.n, n_new=n_new))
+            if e.compute:
+                st.n = n_new
+        return plan
+
+    def _faster_weight(self, module):
+        cb = _fc(self._step_cache_config, "attention_weight_callback")
+        return 0.5 if cb is None else float(cb(module))
+
+    def _faster_pair(self, entry, out):
+        """a context of the ("cond", "uncond") pair ran its stack at forward i and returned `out` [C, F, H, W] (kept by
+        reference): once both have, the delta of that step is taken (ops.fastercache_delta) and the weights start at 1"""
+        st = entry.state
+        st.out, st.out_i = out, entry.i
+        if getattr(self, "_faster_defer_delta", False):
+            return
+        self._faster_delta_now()
+
+    def _faster_delta_now(self):
+        states = self._step_cache_states or {}
+        c, u = states.get("cond"), states.get("uncond")
+        if c is None or u is None or c.out is None or u.out is None or c.out_i != u.out_i or getattr(u, "delta_i", -1) == u.out_i:
+            return
+        if c.out.shape != u.out.shape:
+            return
+        planes = c.out.numel() // max(c.out.shape[-1] * c.out.shape[-2], 1)
+        if not self.ops.fastercache_supported(planes, c.out.shape[-2], c.out.shape[-1]):
+            raise NotImplementedError(f"FasterCache: the low-pass kernel takes planes of at most 16384 elements, the model's "
+                                      f"prediction has {tuple(c.out.shape[-2:])} ones (unconditional_batch_skip_range=None "
+                                      f"keeps the unconditional branch on every step)")
+        if u.d_low is None or u.d_low.shape != u.out.shape:
+            u.d_low = torch.empty(u.out.shape, dtype=torch.float32, device=u.out.device)
+            u.d_high = torch.empty_like(u.d_low)
+        self.ops.fastercache_delta(u.out, c.out, u.d_low, u.d_high)
+        u.has_delta, u.a_low, u.a_high, u.delta_i = True, 1.0, 1.0, u.out_i
+        u.out = None                              # (only the conditional prediction is needed again)
+
+    def _faster_rebuild(self, plan, cond_out, out=None):
+        """u' of a skipping step from this step's conditional prediction: the weights move on, one apply launch"""
+        u = self._step_cache_states["uncond"]
+        u.a_low, u.a_high = fastercache_weights(plan.t, u.a_low, u.a_high, plan.cfg, self)
+        return self.ops.fastercache_apply(cond_out, u.d_low, u.d_high, u.a_low, u.a_high, out=out)
+
 
 class PyramidAttentionBroadcastMixin(FirstBlockCacheMixin):
     """The same surface for a model that implements Pyramid Attention Broadcast alone (CogVideoXTransformer3DModel), plus
@@ -480,6 +784,8 @@ class PyramidAttentionBroadcastMixin(FirstBlockCacheMixin):
                                       f"{self._cache_configs_implemented}")
         if not self.is_cache_enabled and type(config).__name__ == _TAYLOR_NAME:       # with or without its attributes
             raise NotImplementedError(f"{_TAYLOR_NAME} is not implemented on this model; {self._cache_configs_implemented}")
+        if not self.is_cache_enabled and type(config).__name__ == _FASTER_NAME:
+            raise NotImplementedError(f"{_FASTER_NAME} is not implemented on this model; {self._cache_configs_implemented}")
         super().enable_cache(config)
         if self._pab_on and config.spatial_attention_block_skip_range is None:
             warnings.warn(f"Pyramid Attention Broadcast: `spatial_attention_block_skip_range` is None and the temporal / cross "

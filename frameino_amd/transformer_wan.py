@@ -16,7 +16,9 @@ What is different by design (results identical):
 `enable_cache(FirstBlockCacheConfig(...))` (diffusers' CacheMixin, reference :28, :353) skips blocks 1 .. N-1 of a step whose
 first-block residual barely changed; `enable_cache(PyramidAttentionBroadcastConfig(...))` re-uses the self- and / or
 cross-attention branch outputs of the previous step on a schedule of the step counter and the timestep
-(frameino_amd/step_cache.py).  One at a time, both off by default.
+(frameino_amd/step_cache.py); `TaylorSeerCacheConfig` extrapolates the attention branches (or the output) along the step axis;
+`FasterCacheConfig` skips the unconditional CFG branch on a schedule and rebuilds its prediction from the conditional one, and
+extrapolates the self-attention branches.  One at a time, all off by default.
 """
 import contextlib
 import math
@@ -137,7 +139,12 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
     mask predicted from the bf16 / fp16 q and k; DESIGN.md section 6m -- any other head_dim is refused); window attention,
     Pyramid Attention Broadcast, TaylorSeer caching, a token-sharded plan and user-installed attention processors are refused.
     Its similarity gate, per-head thresholds and their calibration (frameino_amd/sparse_calibration.py; bf16 / fp16 only):
-    DESIGN.md section 6k."""
+    DESIGN.md section 6k.
+
+    FasterCache (enable_cache(FasterCacheConfig(...))): the unconditional CFG branch runs on a schedule and
+    is rebuilt from the conditional prediction in between (`_faster_forward`); that part works with MX linears, fp8 / window /
+    sparse attention and LoRA.  Its self-attention extrapolation takes TaylorSeer's route through the attention branches and
+    refuses what TaylorSeer's default mode refuses."""
     _window_table_cache = "_rope_cache"
     _loader_name = "load_wan_transformer"
     _keep_in_fp32_modules = ["time_embedder", "scale_shift_table", "norm1", "norm2", "norm3"]   # reference :393
@@ -168,6 +175,9 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._rope_cache = {}
         self._text_cache = {}
         self._ws = {}
+        self._ws_rows_floor = 0           # FasterCache: a batch-1 step of a batch-2 loop binds the batch-2 workspace
+        self._faster_text = None          # ... and the "cond" row of the loop's stacked prompt, sliced once per prompt
+        self._faster_defer_delta = False  # the loop's two-stream CFG path takes the delta itself, after the streams join
         self._ctx_name = None
         self.ops = ops            # kernel front end (tests of the sharding logic inject a CPU stand-in)
         self.parallel = None      # frameino_amd.parallel.TokenShard or None
@@ -238,6 +248,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         self._reset_stateful_cache()
         self._packed = None
         self._text_cache.clear()
+        self._faster_text = None
         self._rope_cache.clear()          # (the window-attention range tables live here too: `_window_table_cache`)
         self._ws.clear()
         return had_fp8
@@ -295,6 +306,10 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                                       f"caching is)")
         if self._taylor_on:
             raise NotImplementedError(f"{what} with TaylorSeer caching: not implemented in this version (first-block caching is)")
+        if self._faster_attention:
+            raise NotImplementedError(f"{what} with FasterCache's self-attention extrapolation: not implemented in this version "
+                                      f"(`spatial_attention_block_skip_range=None` keeps its unconditional-branch part alone, "
+                                      f"which is)")
         if shard is not None and getattr(shard, "active", True):
             raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
         if not default_procs:
@@ -328,6 +343,27 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                                       f"the built-in MI355WanAttnProcessor path only (lite mode, `use_lite_mode=True`, predicts "
                                       f"the model's output and takes any processor)")
 
+    def _fastercache_refusals(self, config):
+        """what FasterCache does not combine with, at `enable_cache`.  Its unconditional-branch part sits around the forward
+        and takes everything the forward supports on one GPU; the self-attention part, when hooked, refuses what TaylorSeer's
+        default mode refuses (the other order: `_window_refusals`, `_sparse_refusals`, `_bind`)"""
+        what = "FasterCache (FasterCacheConfig)"
+        if self.parallel is not None and getattr(self.parallel, "active", True):
+            raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
+        if getattr(config, "spatial_attention_block_skip_range", None) is None:
+            return
+        what = "FasterCache's self-attention extrapolation (FasterCacheConfig.spatial_attention_block_skip_range)"
+        if self._window is not None:
+            raise NotImplementedError(f"{what} with window attention (enable_window_attention): not implemented in this version "
+                                      f"(pass None: the unconditional-branch part alone is)")
+        if self._sparse is not None:
+            raise NotImplementedError(f"{what} with sparse attention (enable_sparse_attention): not implemented in this version "
+                                      f"(pass None: the unconditional-branch part alone is)")
+        if not self._default_processors():
+            raise NotImplementedError(f"{what} with a user-installed attention processor: the attention branches are "
+                                      f"extrapolated on the built-in MI355WanAttnProcessor path only (pass None: the "
+                                      f"unconditional-branch part alone takes any processor)")
+
     def disable_cache(self):
         super().disable_cache()
         for ws in self._ws.values():          # TaylorSeer's [n, D] scratch for a computed branch's y
@@ -336,6 +372,10 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
     def _workspace(self, L, dtype, device):
         # one workspace per (shape, cache_context name): the two CFG branches may run concurrently on two streams
         key = (L, dtype, str(device), self._ctx_name)
+        if L < self._ws_rows_floor:     # FasterCache's batch-1 step of a batch-2 loop: the views of the larger workspace
+            big = self._ws.get((self._ws_rows_floor,) + key[1:])
+            if big is not None:
+                return big
         ws = self._ws.get(key)
         if ws is None:
             d, f = self.inner_dim, self.config.ffn_dim
@@ -440,12 +480,13 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             if not bool(finite):
                 val.w2, val.pbuf, val.rrms = None, None, None
 
-    def _text_kv(self, encoder_hidden_states, pk, lq=0, may_fold=False):
+    def _text_kv(self, encoder_hidden_states, pk, lq=0, may_fold=False, slot=None):
         """text_embedder (:185) + the 30 layers' attn2 K (after norm_k) and V: step-invariant, cached per
         cache_context name for as long as the caller passes the SAME prompt tensor object, unmodified.  `may_fold`: the
         zero-padded tail of the prompt may be folded into one key (`dedup_text_padding`): then only the kept rows are embedded
         and projected (row-wise operations: the kept rows come out bit-identical) and `.tail` carries (key counts, multiplicities)."""
-        hit = self._text_cache.get(self._ctx_name)
+        name = self._ctx_name if slot is None else (self._ctx_name, slot)     # (`slot`: a second entry under one context)
+        hit = self._text_cache.get(name)
         key = (bool(may_fold), int(lq) if may_fold else 0, self._mx_on, self.reassociate_text_out, self.dedup_text_padding)
         if hit is not None and hit[0] is encoder_hidden_states and hit[1] == encoder_hidden_states._version and hit[3] == key:
             return hit[2]
@@ -476,7 +517,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             self._text_out_weights(val, kept.shape[0], lq, pk)
         # the entry holds the prompt tensor itself: identity (`is`) + in-place version, never its address -- a freed
         # prompt's address is handed to the next same-shape prompt by the caching allocator
-        self._text_cache[self._ctx_name] = (encoder_hidden_states, encoder_hidden_states._version, val, key)
+        self._text_cache[name] = (encoder_hidden_states, encoder_hidden_states._version, val, key)
         return val
 
     # ------------------------------------------------------------------ forward
@@ -524,11 +565,67 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         # LoRA scale (:463-476): adapters are merged into the weights, a changed scale re-merges them here (frameino_amd/lora.py)
         self._lora_apply(attention_kwargs.pop("scale", None) if attention_kwargs is not None else None)
         self._mx_requantise_if_pending()
+        args = (attention_kwargs, timestep_rows, shard, live_rows, id_frames)
+        if self._faster_on:
+            out = yield from self._faster_forward(hidden_states, timestep, encoder_hidden_states, _cache_contexts, args)
+        else:
+            out = yield from self._forward_stack(hidden_states, timestep, encoder_hidden_states, _cache_contexts, *args)
+        return (out,) if not return_dict else SimpleNamespace(sample=out)
+
+    def _faster_forward(self, hidden_states, timestep, encoder_hidden_states, contexts, args):
+        """The forward under FasterCache (frameino_amd/step_cache.py): the unconditional-branch rule around the stack.  A
+        computing step runs the stack as without the cache and then takes the delta of the two predictions; a skipping step of
+        the batched call runs the stack for the "cond" element alone -- in the batch-2 workspace, its text K / V under a slot of
+        their own, its prediction written into row 0 of the result -- and rebuilds row 1; the "uncond" call of a skipping step
+        runs nothing but the rebuild.  -> the prediction [b, C, F, H, W]"""
+        b = hidden_states.shape[0]
+        sh = args[2] if args[2] is not None else self.parallel
+        if sh is not None and sh.active:
+            raise NotImplementedError("first-block caching, Pyramid Attention Broadcast, TaylorSeer caching and FasterCache run on "
+                                      "one GPU: a token-sharded forward cannot take the cache")
+        fc = self._faster_begin(b, hidden_states.shape[1:], hidden_states.dtype, hidden_states.device, contexts)
+        entry = {e.name: e for e in fc.entries}
+        if fc.mode == "batched" and fc.skip:
+            cond_kv = getattr(self, "_faster_text", None)
+            if cond_kv is None or cond_kv[0] is not encoder_hidden_states or cond_kv[1] != encoder_hidden_states._version:
+                cond_kv = self._faster_text = (encoder_hidden_states, encoder_hidden_states._version,
+                                               encoder_hidden_states[:1].contiguous())
+            ts = timestep[:1] if (timestep is not None and timestep.ndim >= 1 and timestep.shape[0] == b) else timestep
+            cfg = self.config
+            both = torch.empty((2, cfg.out_channels) + tuple(hidden_states.shape[2:]), dtype=hidden_states.dtype,
+                               device=hidden_states.device)
+            pt, ph, pw = cfg.patch_size
+            self._ws_rows_floor = 2 * (hidden_states.shape[2] // pt) * (hidden_states.shape[3] // ph) * (hidden_states.shape[4] // pw)
+            try:
+                yield from self._forward_stack(hidden_states[:1], ts, cond_kv[2], ("cond",), *args, faster=fc, out_buf=both[0],
+                                               text_slot="fastercache-cond")
+            finally:
+                self._ws_rows_floor = 0
+            entry["cond"].state.out, entry["cond"].state.out_i = both[0], entry["cond"].i
+            self._faster_rebuild(fc, both[0], out=both[1])
+            return both
+        if fc.mode == "uncond" and fc.skip:
+            cond = (self._step_cache_states or {}).get("cond")
+            if cond is None or cond.out is None or cond.out_i != entry["uncond"].i:
+                raise RuntimeError(f"FasterCache: forward {entry['uncond'].i} of the \"uncond\" context skips its stack and is rebuilt "
+                                   f"from the conditional prediction of the same step, but the \"cond\" context has not run "
+                                   f"forward {entry['uncond'].i} (call it first, under cache_context(\"cond\"))")
+            return self._faster_rebuild(fc, cond.out)[None]
+        out = yield from self._forward_stack(hidden_states, timestep, encoder_hidden_states, contexts, *args, faster=fc)
+        if fc.mode == "batched":
+            self._faster_pair(entry["cond"], out[0])
+            self._faster_pair(entry["uncond"], out[1])
+        elif fc.mode is not None:
+            self._faster_pair(entry[fc.mode], out[0])
+        return out
+
+    def _forward_stack(self, hidden_states, timestep, encoder_hidden_states, _cache_contexts, attention_kwargs, timestep_rows,
+                       shard, live_rows, id_frames, faster=None, out_buf=None, text_slot=None):
+        """embedding, blocks and output head of one call (the body of `forward_steps`) -> the prediction [b, C, F, H, W]"""
         c = self._bind(hidden_states, timestep, encoder_hidden_states, attention_kwargs, timestep_rows, shard, live_rows,
-                       _cache_contexts, id_frames)
+                       _cache_contexts, id_frames, faster, out_buf, text_slot)
         if c.lite is not None and not any(seg.compute["self"] for seg in c.lite.segs):
-            out = self._taylor_lite_rows(c, c.ws.po[:c.nr])                       # TaylorSeer, lite mode: the output rows predicted
-            return (out,) if not return_dict else SimpleNamespace(sample=out)
+            return self._taylor_lite_rows(c, c.ws.po[:c.nr])                      # TaylorSeer, lite mode: the output rows predicted
         self._embed(c, hidden_states)
         yield
 
@@ -557,10 +654,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             self._step_cache_finish(c.fbc, computes, c.x, c.h1c)
             if c.live is not None:
                 c.segs = c.live_segs
-        out = self._output_head(c)
-        if not return_dict:
-            return (out,)
-        return SimpleNamespace(sample=out)
+        return self._output_head(c)
 
     # ------------------------------------------------------------------ forward: per-call state
     def _timestep_selector(self, timestep, timestep_rows, b, n, lo, sharded, dev):
@@ -588,7 +682,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         return t_rows, torch.arange(b, device=dev, dtype=torch.int32).repeat_interleave(n), False
 
     def _bind(self, hidden_states, timestep, encoder_hidden_states, attention_kwargs, timestep_rows, shard, live_rows,
-              cache_contexts, id_frames=0):
+              cache_contexts, id_frames=0, faster=None, out_buf=None, text_slot=None):
         """Everything the stages of one call share, as a `_Call`: geometry, this rank's token shard, workspace views, RoPE
         tables, modulation tables + selector, text K/V and the switches that pick a path."""
         o, cfg = self.ops, self.config
@@ -617,8 +711,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             lo, n, lpad = sh.rows(L)              # first row, valid rows, padded shard length (equal on all ranks)
             cos1, sin1 = cos1[lo:lo + n].contiguous(), sin1[lo:lo + n].contiguous()
             if self.is_cache_enabled:
-                raise NotImplementedError("first-block caching, Pyramid Attention Broadcast and TaylorSeer caching run on one "
-                                          "GPU: a token-sharded forward cannot take the cache")
+                raise NotImplementedError("first-block caching, Pyramid Attention Broadcast, TaylorSeer caching and FasterCache run "
+                                          "on one GPU: a token-sharded forward cannot take the cache")
             if sh.gemm_tile_m:
                 tk = {"tile_m": sh.tile_m_for(n)}
         fbc = self._step_cache_segments(b, n, cache_contexts)      # None: no cache (nothing extra allocated or launched)
@@ -637,9 +731,15 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                 if not any(seg.compute["self"] for seg in lite.segs):
                     # every segment predicts: no embedding, no block, no head -- the call needs its geometry and the output rows
                     return _Call(b=b, n=n, nr=b * n, L=L, nf=nf, hh=hh, ww=ww, d=d, dev=dev, dt=dt, sh=None,
-                                 ws=self._workspace(b * lpad, dt, dev), lite=lite, live=None, segs=[(0, b * n)])
+                                 ws=self._workspace(b * lpad, dt, dev), lite=lite, live=None, segs=[(0, b * n)], out_buf=None)
             else:
                 pab = self._taylor_begin(b, n, d, dt, dev, cache_contexts)
+        if faster is not None and self._faster_attention:
+            # FasterCache's self-attention part: TaylorSeer's route through the attention branches, its own decisions
+            if not default_procs:
+                raise NotImplementedError("FasterCache's self-attention extrapolation with a user-installed attention processor: "
+                                          "the attention branches are extrapolated on the built-in MI355WanAttnProcessor path only")
+            pab = self._faster_attention_plan(faster, b, n, d, dt, dev)
         # Batch elements are extra ROWS of the token-major buffers ([B*n, D]): every GEMM / norm is one launch over
         # both CFG branches (twice the tiles per launch, weights read once); attention and RoPE index rows per batch.
         nr = b * n
@@ -656,7 +756,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         # per-layer modulation tables: scale_shift_table + temb.float()  (:317-319)  -> [R, layers, 6, D] fp32
         mod = (pk.sst[None] + tproj.float()[:, None]).contiguous()
         head = (self.scale_shift_table.float() + temb.float()[:, None]).contiguous()     # [R, 2, D]  (:522/:527)
-        text = self._text_kv(encoder_hidden_states, pk, lq=n, may_fold=default_procs)    # (token shards too: n = the shard's rows)
+        text = self._text_kv(encoder_hidden_states, pk, lq=n, may_fold=default_procs, slot=text_slot)   # (token shards too: n = the shard's rows)
 
         # `shared`: the batch elements are the SAME latent (the pipeline's CFG-batched call passes x.expand(2, ...)) under
         # the same timestep rows: everything up to the first text cross-attention is identical for them, so the patch
@@ -687,7 +787,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                      text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
                      afold={"scale": o.SCALE_FOLDED} if fold else {}, fp8=fp8, default_procs=default_procs,
                      shared=shared, fbc=fbc, pab=pab, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
-                     live=live, win=win, sp=sp, lite=lite,
+                     live=live, win=win, sp=sp, lite=lite, out_buf=out_buf,
                      live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
                      rows=(0, n),            # the rows of every batch element that run as queries / per-token rows ...
                      segs=[(0, nr)])         # ... and the global row ranges the per-token operations of a block run on
@@ -997,6 +1097,9 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         r0, r1 = i * c.n, (i + 1) * c.n
         f, x = self._taylor_buffer(c.pab, seg, (kind, li))[:, r0 - seg.r0:r1 - seg.r0], c.x[r0:r1]
         gate, sel = (m[:, 2], _sel_rows(c.sel, r0, r1)) if kind == "self" else (None, None)
+        if getattr(c.pab, "faster", False):      # FasterCache: y_1 + (y_1 - y_0) * w, the weight of this block's attn1
+            self.ops.taylor_predict(f, seg.n_old, 1, x, gate, sel, out=x, coef=[1.0, self._faster_weight(self.blocks[li].attn1)])
+            return
         self.ops.taylor_predict(f, seg.n_old, seg.k, x, gate, sel, out=x)
 
     def _taylor_lite_rows(self, c, po):
@@ -1050,6 +1153,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         o, cfg = self.ops, self.config
         unpatch = lambda rows: o.unpatchify(rows, cfg.out_channels, c.nf, c.hh, c.ww, cfg.patch_size)      # noqa: E731
         if c.b == 1:
+            if c.out_buf is not None:                # (FasterCache: row 0 of the batched call's result)
+                return o.unpatchify(po, cfg.out_channels, c.nf, c.hh, c.ww, cfg.patch_size, out=c.out_buf)[None]
             return unpatch(po)[None]
         po3 = po.view(c.b, c.L, -1)
         return torch.stack([unpatch(po3[i]) for i in range(c.b)])
@@ -1067,7 +1172,7 @@ class _Call:
     __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
                  "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
                  "afold", "fp8", "default_procs", "shared", "fbc", "pab", "keep", "h0", "h1c", "attention_kwargs", "live",
-                 "live_segs", "rows", "segs", "win", "sp", "lite", "elements")
+                 "live_segs", "rows", "segs", "win", "sp", "lite", "out_buf", "elements")
 
     def __init__(self, **fields):
         self.elements = None

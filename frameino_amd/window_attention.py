@@ -428,6 +428,10 @@ class SelfAttentionOptionsMixin:
                                       f"caching is)")
         if getattr(self, "_taylor_on", False):
             raise NotImplementedError(f"{what} with TaylorSeer caching: not implemented in this version (first-block caching is)")
+        if getattr(self, "_faster_attention", False):
+            raise NotImplementedError(f"{what} with FasterCache's self-attention extrapolation: not implemented in this version "
+                                      f"(`spatial_attention_block_skip_range=None` keeps its unconditional-branch part alone, "
+                                      f"which is)")
         if shard is not None and getattr(shard, "active", True):
             raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
         if not default_procs:

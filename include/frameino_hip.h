@@ -764,6 +764,33 @@ int fino_taylor_update(const void* y, int64_t ldy, void* factors, int64_t plane_
 int fino_taylor_predict(const void* factors, int64_t plane_stride, int64_t ldf, int n, const float* coef, const void* x,
                         int64_t ldx, void* out, int64_t ldo, int64_t rows, int64_t dim, const float* gate, int64_t mod_stride,
                         const int32_t* sel, int dtype, int fdtype, void* stream);
+/* FasterCache (diffusers' hooks/faster_cache.py; frameino_amd/step_cache.py): the unconditional CFG prediction of a step is
+ * rebuilt from the conditional one and the frequency-split difference the two had on the last step that ran both.
+ *
+ * LP, the radial low-pass of one [height, width] plane: the 2-D DFT bins whose signed frequencies fy in [-(H/2), (H-1)/2],
+ * fx in [-(W/2), (W-1)/2] satisfy fy^2 + fx^2 <= r^2, r = min(H, W) / 5 (integer division), are kept, every other bin is
+ * zeroed, and the plane is transformed back (real).
+ *
+ * fino_fastercache_delta: uncond, cond [planes, height, width] of dtype T, contiguous; d_low, d_high fp32 of that shape:
+ *   D = float(uncond) - float(cond);   d_low = LP(D) per plane;   d_high = D - d_low        (fp32)
+ * One workgroup per plane with D in LDS, a direct DFT over the half disk of kept bins (the other half by conjugate symmetry)
+ * with twiddles from per-axis cos / sin tables indexed by integer residues, summed in fp64 and rounded to fp32 once; no
+ * atomics, fixed summation order: the same inputs give the same bits.  fino_fastercache_supported says whether a shape qualifies: planes, height, width >= 1 and
+ * height * width <= FINO_FASTERCACHE_MAX_PLANE (one fp32 plane of 64 KiB); FINO_ERR_UNSUPPORTED otherwise.
+ *
+ * fino_fastercache_apply, with the HOST floats a_low, a_high, over n >= 1 contiguous elements:
+ *   out[j] = T((float(cond[j]) + a_low * d_low[j]) + a_high * d_high[j])
+ * Every multiply and every add is one IEEE fp32 operation (no contraction), one rounding to T.  HBM-bound, 16-byte accesses,
+ * any n (the last n % 8 elements one by one).  out may alias cond.
+ *
+ * All: T = dtype FINO_BF16 | FINO_F16, every pointer 16-byte aligned; a null pointer, a misaligned one or another dtype ->
+ * FINO_ERR_ARG, before any launch. */
+enum { FINO_FASTERCACHE_MAX_PLANE = 16384 };
+int fino_fastercache_supported(int64_t planes, int64_t height, int64_t width);
+int fino_fastercache_delta(const void* uncond, const void* cond, float* d_low, float* d_high, int64_t planes, int64_t height,
+                           int64_t width, int dtype, void* stream);
+int fino_fastercache_apply(const void* cond, const float* d_low, const float* d_high, float a_low, float a_high, void* out,
+                           int64_t n, int dtype, void* stream);
 
 /* ---- diagnostics (tools/ only) --------------------------------------------------------------------------------
  * Dense MFMA rate with nothing else running: `iters` x 16 independent 32x32x16 (kind 0) / 32 independent 16x16x32
