@@ -383,7 +383,6 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
         # the call's rows are ONE segment under the current cache_context
         pab = self._pab_begin(b, L, d, dt, dev)
         seg = pab.segs[0] if pab is not None and pab.hooked["self"] else None
-        reuse = seg is not None and not seg.compute["self"]
 
         # 1. time embedding (:477-483): sinusoid fp32 -> T -> MLP in T
         half = d // 2
@@ -452,13 +451,13 @@ class CogVideoXTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin
                     self._lin(li, "ff2", ff, blk.ff.net[2].weight, blk.ff.net[2].bias, ops.EPI_GATED_RESIDUAL_STAGED,
                               residual=xs, gate=t2[:, 2], sel=ss, out=xs)
                 continue
-            if reuse:
+            if seg is not None and not seg.compute["self"]:
                 # Pyramid Attention Broadcast, a re-using forward: nothing of the attention branch runs; the y the last computing
                 # forward kept goes through the arithmetic of the out-projection's staged epilogue
-                ops.gated_residual(x2, self._pab_buffer(seg, "self", li), t1[:, 2], sel, out=x2, staged=True)
+                pab.reuse(ops, seg, "self", li, 0, b * L, x2, t1[:, 2], sel, fused=False, staged=True)
             else:
                 # (... a computing forward: the out-projection also writes y = T(acc + bias) into this layer's buffer)
-                kept = None if seg is None else self._pab_buffer(seg, "self", li, d, dt, dev)
+                kept = None if seg is None else pab.kept(None, seg, "self", li, 0, b * L)
                 self._attention_branch(ops, win, fp8, li, blk, e, x2, t1, sel, b, L, lt, cos, sin, qfold, afold, default_procs,
                                        image_rotary_emb, attention_kwargs, kept)
             xq2 = (self._ln_q(li, "ff1", 2, x2, weight=e.n2w, bias=e.n2b, shift=t2[:, 0], scale=t2[:, 1], sel=sel, eps=c.norm_eps)

@@ -240,9 +240,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         if not getattr(self.transformer, "is_cache_enabled", False):
             return False
         if self.use_hip_graph is True:
-            raise RuntimeError("use_hip_graph=True with Pyramid Attention Broadcast: which steps run the attention branch changes "
-                               "from step to step on the host's schedule, which one captured step cannot contain (the loop runs "
-                               "eagerly; use_hip_graph=None or False)")
+            raise self.transformer._step_cache_policy.capture_refusal()
         return True
 
     def _window_attention_check(self):

@@ -171,34 +171,16 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         any collective: a parallel plan and the cache are configured by the same script on every rank, so every rank raises)"""
         if not getattr(self.transformer, "is_cache_enabled", False):
             return False
-        pab = bool(getattr(self.transformer, "_pab_on", False))
-        taylor = bool(getattr(self.transformer, "_taylor_on", False))
-        faster = bool(getattr(self.transformer, "_faster_on", False))
-        what = ("Pyramid Attention Broadcast" if pab else "TaylorSeer caching" if taylor else "FasterCache" if faster
-                else "first-block caching")
+        policy = self.transformer._step_cache_policy        # (label, batch rule and capture reason: stated once, by the cache)
         if getattr(self, "parallel", None) is not None:
-            raise NotImplementedError(f"{what} runs on one GPU; this pipeline has a parallel plan")
-        if self.use_hip_graph is True and taylor:
-            raise RuntimeError("use_hip_graph=True with TaylorSeer caching: whether a step computes or predicts changes from step "
-                               "to step on the host's schedule, which one captured step cannot contain (the loop runs eagerly; "
-                               "use_hip_graph=None or False)")
-        if self.use_hip_graph is True and faster:
-            raise RuntimeError("use_hip_graph=True with FasterCache: whether a step runs the unconditional branch and its "
-                               "self-attention branches changes from step to step on the host's schedule, which one captured "
-                               "step cannot contain (the loop runs eagerly; use_hip_graph=None or False)")
-        if batch > 1 and not pab and not taylor and not faster:
-            # (Pyramid Attention Broadcast and FasterCache decide from the step counter and the timestep alone, TaylorSeer from the step counter:
-            # the samples of a batch, run one at a time from fresh state, decide as diffusers' joint run does)
-            raise NotImplementedError("first-block caching with a batch (a list of prompts, num_videos_per_prompt > 1): diffusers "
-                                      "decides jointly over the batch, this pipeline runs the samples one at a time")
-        if self.use_hip_graph is True and pab:
-            raise RuntimeError("use_hip_graph=True with Pyramid Attention Broadcast: which attention branches a step runs "
-                               "changes from step to step on the host's schedule, which one captured step cannot contain (the "
-                               "loop runs eagerly; use_hip_graph=None or False)")
+            raise NotImplementedError(f"{policy.label} runs on one GPU; this pipeline has a parallel plan")
+        if batch > 1 and not policy.batched:
+            # (the others decide from the step counter and the timestep alone: the samples of a batch, run one at a time from
+            # fresh state, decide as diffusers' joint run does)
+            raise NotImplementedError(f"{policy.label} with a batch (a list of prompts, num_videos_per_prompt > 1): diffusers "
+                                      f"decides jointly over the batch, this pipeline runs the samples one at a time")
         if self.use_hip_graph is True:
-            raise RuntimeError("use_hip_graph=True with first-block caching: every step decides on the host between block 0 and "
-                               "block 1 whether the other blocks run, which one captured step cannot contain (the loop runs "
-                               "eagerly; use_hip_graph=None or False)")
+            raise policy.capture_refusal()
         return True
 
     def _window_attention_check(self):
@@ -438,26 +420,16 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
                 self._streams = (torch.cuda.Stream(), torch.cuda.Stream())
             main = torch.cuda.current_stream()
             s1, s2 = self._streams
-            faster = bool(getattr(tr, "_faster_on", False))
-            if faster and tr._faster_will_skip():
+            if getattr(tr, "_faster_on", False) and tr._faster_will_skip():
                 # FasterCache, a skipping step: the cond forward alone, then the rebuild that reads its prediction -- one stream
                 pc = fwd("cond", st.pe)
                 pu = fwd("uncond", st.ne)
             else:
-                s1.wait_stream(main)
-                s2.wait_stream(main)
-                tr._faster_defer_delta = faster          # (the delta reads both predictions: taken after the streams join)
-                try:
+                with tr._cfg_two_streams(main, (s1, s2)):     # fork and join (FasterCache: its delta after the join)
                     with torch.cuda.stream(s1):
                         pc = fwd("cond", st.pe)
                     with torch.cuda.stream(s2):
                         pu = fwd("uncond", st.ne)
-                finally:
-                    tr._faster_defer_delta = False
-                main.wait_stream(s1)
-                main.wait_stream(s2)
-                if faster:
-                    tr._faster_delta_now()
         elif st.cfg and self.batch_cfg and st.pe_ne is not None and getattr(tr, "parallel", None) is None:
             # both CFG branches as ONE batch-2 forward (rows of the same GEMMs: identical per-row arithmetic, twice
             # the tiles per launch, weights streamed once).  The reference makes two calls (:862-882); with the first-block

@@ -6,6 +6,17 @@ WanTransformer3DModel inherits (architecture/transformer_wan.py:28, :353) and wh
 `FasterCacheConfig` (diffusers/hooks/faster_cache.py).  One at a
 time: a second `enable_cache` raises, as in diffusers.
 
+Layout.  Every config has ONE policy class below (`_FirstBlockPolicy`, `_PabPolicy`, `_TaylorSeerPolicy`, `_FasterCachePolicy`) that
+states what is particular to it -- the attributes a duck-typed config must carry, its validation, its enable-time warnings and
+defaults, its label in messages, why a captured step cannot contain it, whether a batch may run under it, whether it takes over
+the attention branches -- and the entry points a forward asks (`segments` around the stack's first block, `lite` around the whole
+stack, `branches` for the attention branches).  `StepCacheMixin.enable_cache` is a lookup over the model's `_cache_policies`
+and stores the chosen policy next to the config; the `_pab_on` / `_taylor_on` / ... flags are read-only views of it.  The
+attention branches of a forward run under ONE plan, whichever cache made it: `_BroadcastPlan` (Pyramid Attention Broadcast) or
+`_TaylorPlan` (TaylorSeer's default mode, FasterCache's self-attention part), which say where a computing branch's output is kept,
+what follows it, and which single launch stands for a branch that does not run.  What a cache does not combine with is one
+method of the model, `_cache_refusals`, called from `enable_cache`, from where the other feature is enabled and from the forward.
+
 First-block caching.  The rule, per forward under context c (T = the model dtype; h0 = input of block 0, h1 = its output, hN = the last block's):
 
     r = T(h1 - h0)
@@ -176,55 +187,14 @@ class FasterCacheConfig:
 
 # the other configs diffusers' CacheMixin applies: recognised, not implemented here
 _OTHER_DIFFUSERS_CONFIGS = ("MagCacheConfig", "TeaCacheConfig")
-_FASTER_NAME = "FasterCacheConfig"
-_FASTER_REQUIRED = ("spatial_attention_block_skip_range", "unconditional_batch_skip_range", "current_timestep_callback")
 _FASTER_DEFAULTS = {f.name: f.default for f in dataclasses.fields(FasterCacheConfig)}
 FASTER_CONTEXTS = ("cond", "uncond")    # the cache contexts of the denoising loop the unconditional-branch rule pairs
-_TAYLOR_NAME = "TaylorSeerCacheConfig"
-_TAYLOR_REQUIRED = ("cache_interval", "disable_cache_before_step", "max_order")
 TAYLOR_MAX_ORDER = 3                     # ops.TAYLOR_MAX_PLANES - 1
 
-_PAB_NAME = "PyramidAttentionBroadcastConfig"
 _PAB_RANGES = ("spatial_attention_block_skip_range", "temporal_attention_block_skip_range", "cross_attention_block_skip_range")
 # the attention kinds of the Wan DiT: (key, block-skip field, timestep-range field)
 PAB_KINDS = (("self", "spatial_attention_block_skip_range", "spatial_attention_timestep_skip_range"),
              ("cross", "cross_attention_block_skip_range", "cross_attention_timestep_skip_range"))
-
-
-def _is_fbc_config(config):
-    return type(config).__name__ == "FirstBlockCacheConfig" and hasattr(config, "threshold")
-
-
-def _is_pab_config(config):
-    return type(config).__name__ == _PAB_NAME and all(hasattr(config, a) for a in _PAB_RANGES + ("current_timestep_callback",))
-
-
-def _is_taylorseer_config(config):
-    return type(config).__name__ == _TAYLOR_NAME and all(hasattr(config, a) for a in _TAYLOR_REQUIRED)
-
-
-def _taylorseer_validate(config):
-    """ValueError for a field outside its range, NotImplementedError for the module selection that is not built"""
-    def whole(name, lo, hi=None, optional=False):
-        v = getattr(config, name, None)
-        if v is None and optional:
-            return
-        if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
-            raise ValueError(f"TaylorSeerCacheConfig.{name} = {v!r}: need an integer of at least {lo}"
-                             + (f" and at most {hi}" if hi is not None else "") + (" or None" if optional else ""))
-    whole("cache_interval", 1)
-    whole("disable_cache_before_step", 1)
-    whole("disable_cache_after_step", 0, optional=True)
-    whole("max_order", 0, TAYLOR_MAX_ORDER)
-    fdt = getattr(config, "taylor_factors_dtype", None)
-    if fdt is not None and fdt not in (torch.bfloat16, torch.float16, torch.float32):
-        raise ValueError(f"TaylorSeerCacheConfig.taylor_factors_dtype = {fdt!r}: torch.bfloat16, torch.float16, torch.float32 or "
-                         f"None (the model dtype)")
-    for name in ("skip_predict_identifiers", "cache_identifiers"):
-        if getattr(config, name, None) is not None:
-            raise NotImplementedError(f"TaylorSeerCacheConfig.{name}: selecting modules by identifier is not implemented; the "
-                                      f"hooked tensors are every block's attn1 / attn2 output, or the model's output rows in "
-                                      f"lite mode (pass None)")
 
 
 def taylorseer_decide(s, n_factors, cfg):
@@ -237,44 +207,9 @@ def taylorseer_decide(s, n_factors, cfg):
     return n_factors == 0 or s < w or (s - (w - 1)) % n == 0 or (after is not None and s >= after)
 
 
-
-def _is_fastercache_config(config):
-    return type(config).__name__ == _FASTER_NAME and all(hasattr(config, a) for a in _FASTER_REQUIRED)
-
-
 def _fc(cfg, name):
     """a field of a FasterCache config, diffusers' default where a duck-typed object lacks it"""
     return getattr(cfg, name, _FASTER_DEFAULTS[name])
-
-
-def _fastercache_validate(config):
-    """ValueError for a field outside its range or a missing `current_timestep_callback`"""
-    for name in ("spatial_attention_block_skip_range", "temporal_attention_block_skip_range", "unconditional_batch_skip_range"):
-        v = _fc(config, name)
-        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
-            raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need an integer of at least 1, or None")
-    for name in ("spatial_attention_timestep_skip_range", "temporal_attention_timestep_skip_range",
-                 "unconditional_batch_timestep_skip_range", "low_frequency_weight_update_timestep_range",
-                 "high_frequency_weight_update_timestep_range"):
-        v = _fc(config, name)
-        ok = isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, (int, float)) and not isinstance(e, bool)
-                                                                  and e == e for e in v)
-        if not ok or not v[0] < v[1]:
-            raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need a pair (lo, hi) of numbers with lo < hi")
-    for name in ("alpha_low_frequency", "alpha_high_frequency"):
-        v = _fc(config, name)
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= float(v) < float("inf")):
-            raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need a finite number of at least 0")
-    for name in ("attention_weight_callback", "low_frequency_weight_callback", "high_frequency_weight_callback"):
-        v = _fc(config, name)
-        if v is not None and not callable(v):
-            raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need a callable or None")
-    if _fc(config, "tensor_format") != "BCFHW":
-        raise ValueError(f"FasterCacheConfig.tensor_format = {_fc(config, 'tensor_format')!r}: this model's predictions are "
-                         f'"BCFHW" (the low-pass runs over the (H, W) planes)')
-    if config.current_timestep_callback is None:
-        raise ValueError("The `current_timestep_callback` function must be provided in the configuration to apply FasterCache: "
-                         "it returns the denoising loop's current timestep (`lambda: pipe.current_timestep`).")
 
 
 def _f32(x):
@@ -343,28 +278,326 @@ def decide(sum_abs_diff, sum_abs_prev, numel, dtype, threshold):
     return diff, diff > threshold
 
 
-class FirstBlockCacheMixin:
-    """diffusers' CacheMixin surface (enable_cache / disable_cache / is_cache_enabled / _reset_stateful_cache) for
-    FirstBlockCache, Pyramid Attention Broadcast and TaylorSeer.  For the first the model calls `_step_cache_segments`,
-    `_step_cache_probe` and `_step_cache_finish` from its forward; for the second `_pab_begin` (once per forward) and
-    `_pab_buffer`; for the third `_taylor_begin` and `_taylor_buffer`.
+# ---------------------------------------------------------------------- one policy per config
+class _CachePolicy:
+    """What one cache config states once.  Never instantiated: the class is the policy object a model stores.
+    `name`: the config's class name; `required`: the attributes a duck-typed config must carry; `label`: its name in messages
+    (`attention_label`: of the part that takes over the attention branches, `instead`: what to use where that part is refused);
+    `why_eager`: why one captured step cannot contain it; `batched`: whether the pipeline may run it with a batch > 1."""
+    name = label = attention_label = instead = why_eager = None
+    required = ()
+    batched = True
 
-    State per cache-context name: the head residual (plus a spare buffer the next probe writes into), the tail residual, and a
-    step counter.  `cache_log` holds `(context, step, diff, computed)` for every forward since the last reset (diff None: no
-    previous residual); it survives the reset at the end of a pipeline call, so the call's decisions can be read after it.
+    @classmethod
+    def missing(cls):
+        attrs = ", ".join(f"`{a}`" for a in cls.required)
+        return NotImplementedError(f"{cls.name}: this object carries the name but not the attributes of diffusers' {cls.name} "
+                                   f"that are needed here ({attrs}), so it cannot be applied")
 
-    Pyramid Attention Broadcast: per context and kind a counter, per (kind, layer) a [rows, D] buffer in the model dtype,
-    allocated by the first forward that computes; `cache_log` holds `(context, iteration, float(timestep),
-    self_attention_computed, cross_attention_computed)` for every forward and context, with the same lifetime.
+    @classmethod
+    def capture_refusal(cls):
+        return RuntimeError(f"use_hip_graph=True with {cls.label}: {cls.why_eager}, which one captured step cannot contain (the "
+                            f"loop runs eagerly; use_hip_graph=None or False)")
 
-    TaylorSeer: per context a counter, the number of valid factor planes and the last computing forward, per hooked tensor
-    a [max_order + 1, rows, D] buffer in the factor dtype, allocated by the first forward that computes; `cache_log` holds
-    `(context, step, computed)`, with the same lifetime."""
-    _cache_configs_implemented = ("FirstBlockCacheConfig, PyramidAttentionBroadcastConfig, TaylorSeerCacheConfig and "
-                                  "FasterCacheConfig are")
+    @staticmethod
+    def validate(config, model):
+        """ValueError / NotImplementedError for a config this model cannot apply"""
+
+    @staticmethod
+    def prepare(config):
+        """the enable-time warnings and defaults"""
+
+    @staticmethod
+    def hooks_attention(config):
+        """whether it takes over the attention branches of the forward"""
+        return False
+
+    @classmethod
+    def takes_windows(cls, config):
+        """whether it runs beside window / sparse attention: unless stated otherwise, when it leaves the attention branches alone"""
+        return not cls.hooks_attention(config)
+
+    @classmethod
+    def takes_any_processor(cls, config):
+        """whether it runs with a user-installed attention processor: unless stated otherwise, likewise"""
+        return not cls.hooks_attention(config)
+
+    # the three places of a forward a cache can sit in; None: not there
+    @staticmethod
+    def segments(model, b, n, contexts):
+        """around block 0 and the rest of the stack (`_step_cache_probe` / `_step_cache_finish`): the row segments"""
+
+    @staticmethod
+    def lite(model, b, n, d_out, dtype, device, contexts):
+        """around the whole stack, on the output head's rows: a plan"""
+
+    @staticmethod
+    def branches(model, b, n, d, dtype, device, contexts, faster):
+        """in the attention branches of every block: a `_BranchPlan`"""
+
+
+class _FirstBlockPolicy(_CachePolicy):
+    name, required, label = "FirstBlockCacheConfig", ("threshold",), "first-block caching"
+    why_eager = "every step decides on the host between block 0 and block 1 whether the other blocks run"
+    batched = False             # diffusers decides jointly over a batch; the pipeline runs the samples one at a time
+
+    @staticmethod
+    def validate(config, model):
+        if len(model.blocks) < 2:
+            raise ValueError(f"FirstBlockCache needs a head block and at least one more block; this model has "
+                             f"{len(model.blocks)} block(s), so the head block would also be the tail block")
+
+    @staticmethod
+    def segments(model, b, n, contexts):
+        return model._context_segments(b, n, contexts)
+
+
+class _PabPolicy(_CachePolicy):
+    name, required, label = "PyramidAttentionBroadcastConfig", _PAB_RANGES + ("current_timestep_callback",), "Pyramid Attention Broadcast"
+    instead = "first-block caching is"
+    why_eager = "which attention branches a step runs changes from step to step on the host's schedule"
+
+    @staticmethod
+    def validate(config, model):
+        if config.current_timestep_callback is None:
+            raise ValueError("The `current_timestep_callback` function must be provided in the configuration to apply "
+                             "Pyramid Attention Broadcast: it returns the denoising loop's current timestep "
+                             "(`lambda: pipe.current_timestep`).")
+
+    @staticmethod
+    def prepare(config):
+        if all(getattr(config, a) is None for a in _PAB_RANGES):
+            warnings.warn("Pyramid Attention Broadcast requires one or more of `spatial_attention_block_skip_range`, "
+                          "`temporal_attention_block_skip_range` or `cross_attention_block_skip_range` to be set; "
+                          "defaulting to `spatial_attention_block_skip_range=2`.", stacklevel=3)
+            config.spatial_attention_block_skip_range = 2
+
+    @staticmethod
+    def hooks_attention(config):
+        return True
+
+    @staticmethod
+    def takes_any_processor(config):      # (a processor's return value is what it keeps and hands out)
+        return True
+
+    @staticmethod
+    def branches(model, b, n, d, dtype, device, contexts, faster):
+        return model._pab_begin(b, n, d, dtype, device, contexts)
+
+
+class _TaylorSeerPolicy(_CachePolicy):
+    name, required = "TaylorSeerCacheConfig", ("cache_interval", "disable_cache_before_step", "max_order")
+    label = attention_label = "TaylorSeer caching"
+    instead = "first-block caching is"
+    why_eager = "whether a step computes or predicts changes from step to step on the host's schedule"
+
+    @staticmethod
+    def validate(config, model):
+        """ValueError for a field outside its range, NotImplementedError for the module selection that is not built"""
+        def whole(name, lo, hi=None, optional=False):
+            v = getattr(config, name, None)
+            if v is None and optional:
+                return
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+                raise ValueError(f"TaylorSeerCacheConfig.{name} = {v!r}: need an integer of at least {lo}"
+                                 + (f" and at most {hi}" if hi is not None else "") + (" or None" if optional else ""))
+        whole("cache_interval", 1)
+        whole("disable_cache_before_step", 1)
+        whole("disable_cache_after_step", 0, optional=True)
+        whole("max_order", 0, TAYLOR_MAX_ORDER)
+        fdt = getattr(config, "taylor_factors_dtype", None)
+        if fdt is not None and fdt not in (torch.bfloat16, torch.float16, torch.float32):
+            raise ValueError(f"TaylorSeerCacheConfig.taylor_factors_dtype = {fdt!r}: torch.bfloat16, torch.float16, torch.float32 or "
+                             f"None (the model dtype)")
+        for name in ("skip_predict_identifiers", "cache_identifiers"):
+            if getattr(config, name, None) is not None:
+                raise NotImplementedError(f"TaylorSeerCacheConfig.{name}: selecting modules by identifier is not implemented; the "
+                                          f"hooked tensors are every block's attn1 / attn2 output, or the model's output rows in "
+                                          f"lite mode (pass None)")
+
+    @staticmethod
+    def hooks_attention(config):
+        return not getattr(config, "use_lite_mode", False)
+
+    @staticmethod
+    def takes_windows(config):            # (lite mode too: its predicted output rows have not been measured over windows)
+        return False
+
+    @staticmethod
+    def lite(model, b, n, d_out, dtype, device, contexts):
+        return model._taylor_begin(b, n, d_out, dtype, device, contexts) if model._taylor_lite else None
+
+    @staticmethod
+    def branches(model, b, n, d, dtype, device, contexts, faster):
+        return None if model._taylor_lite else model._taylor_begin(b, n, d, dtype, device, contexts)
+
+
+class _FasterCachePolicy(_CachePolicy):
+    name = "FasterCacheConfig"
+    required = ("spatial_attention_block_skip_range", "unconditional_batch_skip_range", "current_timestep_callback")
+    label, attention_label = "FasterCache", "FasterCache's self-attention extrapolation"
+    instead = "`spatial_attention_block_skip_range=None` keeps its unconditional-branch part alone, which is"
+    why_eager = ("whether a step runs the unconditional branch and its self-attention branches changes from step to step on the "
+                 "host's schedule")
+
+    @staticmethod
+    def validate(config, model):
+        """ValueError for a field outside its range or a missing `current_timestep_callback`"""
+        for name in ("spatial_attention_block_skip_range", "temporal_attention_block_skip_range", "unconditional_batch_skip_range"):
+            v = _fc(config, name)
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
+                raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need an integer of at least 1, or None")
+        for name in ("spatial_attention_timestep_skip_range", "temporal_attention_timestep_skip_range",
+                     "unconditional_batch_timestep_skip_range", "low_frequency_weight_update_timestep_range",
+                     "high_frequency_weight_update_timestep_range"):
+            v = _fc(config, name)
+            ok = isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, (int, float)) and not isinstance(e, bool)
+                                                                      and e == e for e in v)
+            if not ok or not v[0] < v[1]:
+                raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need a pair (lo, hi) of numbers with lo < hi")
+        for name in ("alpha_low_frequency", "alpha_high_frequency"):
+            v = _fc(config, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= float(v) < float("inf")):
+                raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need a finite number of at least 0")
+        for name in ("attention_weight_callback", "low_frequency_weight_callback", "high_frequency_weight_callback"):
+            v = _fc(config, name)
+            if v is not None and not callable(v):
+                raise ValueError(f"FasterCacheConfig.{name} = {v!r}: need a callable or None")
+        if _fc(config, "tensor_format") != "BCFHW":
+            raise ValueError(f"FasterCacheConfig.tensor_format = {_fc(config, 'tensor_format')!r}: this model's predictions are "
+                             f'"BCFHW" (the low-pass runs over the (H, W) planes)')
+        if config.current_timestep_callback is None:
+            raise ValueError("The `current_timestep_callback` function must be provided in the configuration to apply FasterCache: "
+                             "it returns the denoising loop's current timestep (`lambda: pipe.current_timestep`).")
+
+    @staticmethod
+    def prepare(config):
+        if _fc(config, "spatial_attention_block_skip_range") is not None and _fc(config, "attention_weight_callback") is None:
+            warnings.warn("FasterCacheConfig: no `attention_weight_callback` provided; defaulting to 0.5 for every "
+                          "attention module.", stacklevel=3)
+
+    @staticmethod
+    def hooks_attention(config):
+        return _fc(config, "spatial_attention_block_skip_range") is not None
+
+    @staticmethod
+    def branches(model, b, n, d, dtype, device, contexts, faster):
+        return model._faster_attention_plan(faster, b, n, d, dtype, device)
+
+
+_POLICIES = {p.name: p for p in (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy)}
+
+
+# ---------------------------------------------------------------------- one plan for the attention branches of a forward
+def _pab_buffer(seg, kind, layer, d=None, dtype=None, device=None):
+    """the cache of attention module (kind, layer) under the segment's context: [rows, D] in the model dtype, allocated by
+    the first forward that computes (pass d / dtype / device); a reuse step finds it there (KeyError: it never computed)"""
+    buf = seg.state.buffers.get((kind, layer))
+    if buf is None:
+        if d is None:
+            raise KeyError(f"Pyramid Attention Broadcast: no cached output of the {kind}-attention of block {layer} under "
+                           f"context {seg.name!r}")
+        buf = seg.state.buffers[(kind, layer)] = torch.empty((seg.r1 - seg.r0, d), dtype=dtype, device=device)
+    return buf
+
+
+def _taylor_buffer(plan, seg, key, d=None, device=None):
+    """the factor planes of hooked tensor `key` ((kind, layer), or "out" in lite mode) under the segment's context:
+    [max_order + 1, rows, D] in the factor dtype, allocated by the first forward that computes (pass d / device); a
+    predicting step finds them there (KeyError: it never computed)"""
+    buf = seg.state.buffers.get(key)
+    if buf is None:
+        if d is None:
+            raise KeyError(f"TaylorSeer: no factors of {key!r} under context {seg.name!r}")
+        buf = seg.state.buffers[key] = torch.empty((plan.planes, seg.r1 - seg.r0, d), dtype=plan.factor_dtype, device=device)
+    return buf
+
+
+class _BranchPlan:
+    """One forward's decisions for the attention branches a cache has taken over, made before anything is launched: `.hooked[kind]`,
+    and `.segs` = one entry per row segment (a batch element under its own context, or the whole batch under one) with `.name`,
+    `.r0`, `.r1`, `.state` and `.compute[kind]`.  `d`, `dtype`, `device`: of the hooked rows.  For the rows [r0, r1) of the call
+    that one launch of a branch covers (inside one segment) a plan answers: `kept` -- where a computing branch's
+    y = T(acc + bias) is kept (the closing GEMM's `keep=`); `computed` -- what runs after that branch; `reuse` -- the one launch
+    that stands for a branch that does not run, x += gate * y' / x += y' with the closing GEMM's epilogue arithmetic."""
+    taylor, lite = None, False
+
+    def __init__(self, hooked, d, dtype, device, **fields):
+        self.segs, self.hooked, self.d, self.dtype, self.device = [], hooked, d, dtype, device
+        vars(self).update(fields)
+
+    def segment(self, row):
+        """the segment row `row` of the call lies in"""
+        return next(s for s in self.segs if s.r0 <= row < s.r1)
+
+
+class _BroadcastPlan(_BranchPlan):
+    """Pyramid Attention Broadcast: y stays in the segment's [rows, D] buffer of (kind, layer) and is handed out as it is"""
+
+    def kept(self, ws, seg, kind, layer, r0, r1):
+        buf = _pab_buffer(seg, kind, layer, self.d, self.dtype, self.device)
+        return buf if (r0, r1) == (seg.r0, seg.r1) else buf[r0 - seg.r0:r1 - seg.r0]
+
+    def computed(self, ops, seg, kind, layer, r0, r1, y):
+        pass
+
+    def reuse(self, ops, seg, kind, layer, r0, r1, x, gate, sel, module=None, fused=True, **epilogue):
+        """bit for bit what the step that computed y wrote: the fused epilogues multiply-add once (`ops.pab_broadcast`), a
+        custom processor's result (and a staged epilogue's, `staged=True`) went through `ops.gated_residual`"""
+        buf = _pab_buffer(seg, kind, layer)
+        y = buf if (r0, r1) == (seg.r0, seg.r1) else buf[r0 - seg.r0:r1 - seg.r0]
+        (ops.pab_broadcast if fused else ops.gated_residual)(x, y, gate, sel, out=x, **epilogue)
+
+
+class _TaylorPlan(_BranchPlan):
+    """TaylorSeer's default mode and FasterCache's self-attention part: y waits in the workspace's one [n, D] scratch for the
+    update launch that folds it into the factor planes of (kind, layer); a branch that does not run is extrapolated from them.
+    Per segment also `.s` (this forward's number), `.k` (its distance to the last computing forward: the `delta` of an update,
+    the offset of a prediction) and `.n_old` / `.n_new` (the valid planes before and after a computing forward).  `weight`
+    (FasterCache): the prediction is f_0 + w * f_1, w = weight(attention module), instead of the Taylor series in k."""
+    weight = None
+
+    def kept(self, ws, seg, kind, layer, r0, r1):
+        if getattr(ws, "taylor_y", None) is None:
+            ws.taylor_y = torch.empty((r1 - r0, self.d), dtype=self.dtype, device=self.device)
+        return ws.taylor_y
+
+    def computed(self, ops, seg, kind, layer, r0, r1, y):
+        f = _taylor_buffer(self, seg, (kind, layer), self.d, self.device)[:, r0 - seg.r0:r1 - seg.r0]
+        ops.taylor_update(y, f, seg.n_old, seg.k, seg.n_new)
+
+    def reuse(self, ops, seg, kind, layer, r0, r1, x, gate, sel, module=None, fused=True):
+        f = _taylor_buffer(self, seg, (kind, layer))[:, r0 - seg.r0:r1 - seg.r0]
+        coef = {} if self.weight is None else {"coef": [1.0, self.weight(module)]}
+        ops.taylor_predict(f, seg.n_old, seg.k, x, gate, sel, out=x, **coef)
+
+
+class StepCacheMixin:
+    """diffusers' CacheMixin surface (enable_cache / disable_cache / is_cache_enabled / _reset_stateful_cache) over the policies
+    in `_cache_policies`.  `enable_cache` looks the config's policy up, lets it validate, asks the model what it cannot be
+    combined with (`_cache_refusals`) and stores it next to the config; the forward asks the stored policy for its entry points
+    (`segments` / `lite` / `branches`), which lead to `_step_cache_segments` + `_step_cache_probe` + `_step_cache_finish`
+    (first-block caching), `_pab_begin`, `_taylor_begin` and `_faster_begin` + `_faster_attention_plan`.
+
+    State per cache-context name (`_cache_state`: made at first use, and again when the rows, width, dtype or device change);
+    `cache_log` holds one row per forward and context since the last reset; it survives the reset at the end of a pipeline call,
+    so the call's decisions can be read after it.
+    First-block caching: the head residual (plus a spare buffer the next probe writes into), the tail residual and a step
+    counter; log rows `(context, step, diff, computed)` (diff None: no previous residual).
+    Pyramid Attention Broadcast: per kind a counter, per (kind, layer) a [rows, D] buffer in the model dtype, allocated by the
+    first forward that computes; log rows `(context, iteration, float(timestep), self_attention_computed,
+    cross_attention_computed)`.
+    TaylorSeer: a counter, the number of valid factor planes and the last computing forward, per hooked tensor a
+    [max_order + 1, rows, D] buffer in the factor dtype, allocated by the first forward that computes; log rows
+    `(context, step, computed)`.
+    FasterCache: a counter, the self-attention planes, the context's last prediction (by reference) and, for "uncond", the
+    delta and its weights; log rows `(context, i, t, stack_ran, attention_computed)`."""
+    _cache_policies = (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy)
     _step_cache_config = None
+    _step_cache_policy = None
     _step_cache_states = None
     _step_cache_log_fresh = True
+    _faster_defer_delta = False
     cache_log = ()
 
     @property
@@ -376,63 +609,33 @@ class FirstBlockCacheMixin:
             raise ValueError(f"Caching has already been enabled with {type(self._step_cache_config)}. To apply a new caching "
                              f"technique, please disable the existing one first.")
         name = type(config).__name__
-        if _is_fbc_config(config):
-            if len(self.blocks) < 2:
-                raise ValueError(f"FirstBlockCache needs a head block and at least one more block; this model has "
-                                 f"{len(self.blocks)} block(s), so the head block would also be the tail block")
-            self._step_cache_config = config
-            self._reset_stateful_cache()
-            return
-        if _is_pab_config(config):
-            if config.current_timestep_callback is None:
-                raise ValueError("The `current_timestep_callback` function must be provided in the configuration to apply "
-                                 "Pyramid Attention Broadcast: it returns the denoising loop's current timestep "
-                                 "(`lambda: pipe.current_timestep`).")
-            if all(getattr(config, a) is None for a in _PAB_RANGES):
-                warnings.warn("Pyramid Attention Broadcast requires one or more of `spatial_attention_block_skip_range`, "
-                              "`temporal_attention_block_skip_range` or `cross_attention_block_skip_range` to be set; "
-                              "defaulting to `spatial_attention_block_skip_range=2`.", stacklevel=2)
-                config.spatial_attention_block_skip_range = 2
-            self._step_cache_config = config
-            self._reset_stateful_cache()
-            return
-        if name == _PAB_NAME:
-            raise NotImplementedError(f"{name}: this object carries the name but not the `*_block_skip_range` and "
-                                      f"`current_timestep_callback` attributes of diffusers' config, so it cannot be applied")
-        if _is_taylorseer_config(config):
-            _taylorseer_validate(config)
-            self._taylorseer_refusals(config)
-            self._step_cache_config = config
-            self._reset_stateful_cache()
-            return
-        if name == _TAYLOR_NAME:
-            raise NotImplementedError(f"{name}: this object carries the name but not the `cache_interval`, "
-                                      f"`disable_cache_before_step` and `max_order` attributes of diffusers' config, so it "
-                                      f"cannot be applied")
-        if _is_fastercache_config(config):
-            _fastercache_validate(config)
-            self._fastercache_refusals(config)
-            if _fc(config, "spatial_attention_block_skip_range") is not None and _fc(config, "attention_weight_callback") is None:
-                warnings.warn("FasterCacheConfig: no `attention_weight_callback` provided; defaulting to 0.5 for every "
-                              "attention module.", stacklevel=2)
-            self._step_cache_config = config
-            self._reset_stateful_cache()
-            return
-        if name == _FASTER_NAME:
-            raise NotImplementedError(f"{name}: this object carries the name but not the `spatial_attention_block_skip_range`, "
-                                      f"`unconditional_batch_skip_range` and `current_timestep_callback` attributes of "
-                                      f"diffusers' FasterCacheConfig, so it cannot be applied")
-        if name in _OTHER_DIFFUSERS_CONFIGS or (name.endswith("CacheConfig") and
-                                                 type(config).__module__.split(".")[0] == "diffusers"):
-            raise NotImplementedError(f"{name} is not implemented on this model; {self._cache_configs_implemented}")
-        raise ValueError(f"Cache config {type(config)} is not supported.")
+        policy = _POLICIES.get(name)
+        if policy not in self._cache_policies:
+            if policy is not None or name in _OTHER_DIFFUSERS_CONFIGS or (
+                    name.endswith("CacheConfig") and type(config).__module__.split(".")[0] == "diffusers"):
+                *some, last = [p.name for p in self._cache_policies]
+                have = f"{', '.join(some)} and {last} are" if some else f"{last} is"
+                raise NotImplementedError(f"{name} is not implemented on {type(self).__name__}; {have}")
+            raise ValueError(f"Cache config {type(config)} is not supported.")
+        if not all(hasattr(config, a) for a in policy.required):
+            raise policy.missing()
+        policy.validate(config, self)
+        self._cache_refusals(policy, config, enabling=True)
+        policy.prepare(config)
+        self._step_cache_config, self._step_cache_policy = config, policy
+        self._reset_stateful_cache()
 
     def disable_cache(self):
         if self._step_cache_config is None:
             warnings.warn("Caching techniques have not been enabled, so there's nothing to disable.", stacklevel=2)
             return
         self._step_cache_config = None
+        del self._step_cache_policy               # (the class's None again: the model is as it was before `enable_cache`)
         self._reset_stateful_cache()
+
+    def _cache_refusals(self, policy=None, config=None, **where):
+        """NotImplementedError for what this model does not combine with a step cache; a model with such limits states them
+        here, once, for both orders (WanTransformer3DModel)"""
 
     def _reset_stateful_cache(self, recurse=True):
         """drop every context's state (diffusers' maybe_free_model_hooks calls this at the end of a pipeline call); the next
@@ -440,16 +643,17 @@ class FirstBlockCacheMixin:
         self._step_cache_states = {}
         self._step_cache_log_fresh = True
 
-    # ---------------------------------------------------------------- used by the forward
-    def _step_cache_segments(self, b, n, contexts=None):
-        """None when no cache is enabled, else [(context, first row, end row)] of the call's [b * n, D] rows: one segment per
-        batch element when `contexts` names one context each (the pipeline's CFG-batched call), else one joint segment under
-        the current `cache_context`."""
-        if self._step_cache_config is None or self._pab_on or self._taylor_on or self._faster_on:
-            return None                       # (Pyramid Attention Broadcast, TaylorSeer, FasterCache: the first-block code stays inert)
-        return self._context_segments(b, n, contexts)
+    # the flags tests, tools, window_attention.py and the pipelines read: views of the stored policy
+    _pab_on = property(lambda self: self._step_cache_policy is _PabPolicy)
+    _taylor_on = property(lambda self: self._step_cache_policy is _TaylorSeerPolicy)
+    _taylor_lite = property(lambda self: self._taylor_on and not _TaylorSeerPolicy.hooks_attention(self._step_cache_config))
+    _faster_on = property(lambda self: self._step_cache_policy is _FasterCachePolicy)
+    _faster_attention = property(lambda self: self._faster_on and _FasterCachePolicy.hooks_attention(self._step_cache_config))
 
+    # ---------------------------------------------------------------- used by the forward
     def _context_segments(self, b, n, contexts):
+        """[(context, first row, end row)] of the call's [b * n, D] rows: one segment per batch element when `contexts` names one
+        context each (the pipeline's CFG-batched call), else one joint segment under the current `cache_context`."""
         if contexts is not None:
             contexts = tuple(contexts)
             if len(contexts) != b or len(set(contexts)) != b:
@@ -459,23 +663,32 @@ class FirstBlockCacheMixin:
             raise ValueError("No context is set. Please set a context before retrieving the state.")
         return [(self._ctx_name, 0, b * n)]
 
-    def _step_cache_probe(self, segs, h0, h1, h1_copy):
-        """after block 0: probe, one host read, decide.  Returns one bool per segment (True: compute blocks 1 .. N-1)."""
+    def _cache_state(self, name, key, fresh):
+        """the state of context `name`: a step counter plus the fields `fresh()` returns, made at first use and again whenever
+        `key` -- shape, dtype, device -- changes; the first forward after a reset starts a new `cache_log`"""
         if self._step_cache_log_fresh or not isinstance(self.cache_log, list):
             self.cache_log = []
             self._step_cache_log_fresh = False
         if self._step_cache_states is None:
             self._step_cache_states = {}
+        st = self._step_cache_states.get(name)
+        if st is None or st.key != key:
+            st = self._step_cache_states[name] = SimpleNamespace(key=key, steps=0, **fresh())
+        return st
+
+    # ---------------------------------------------------------------- first-block caching
+    def _step_cache_segments(self, b, n, contexts=None):
+        """None unless first-block caching is on (nothing extra is allocated or launched), else `_context_segments`"""
+        return None if self._step_cache_policy is None else self._step_cache_policy.segments(self, b, n, contexts)
+
+    def _step_cache_probe(self, segs, h0, h1, h1_copy):
+        """after block 0: probe, one host read, decide.  Returns one bool per segment (True: compute blocks 1 .. N-1)."""
         d, dt, dev = h1.shape[1], h1.dtype, h1.device
-        sts = []
-        for name, r0, r1 in segs:
-            key = (r1 - r0, d, dt, str(dev))
-            st = self._step_cache_states.get(name)
-            if st is None or st.key != key:          # first use, or another shape / dtype / device: start over
-                st = self._step_cache_states[name] = SimpleNamespace(key=key, head=None, spare=None, tail=None, steps=0)
+        sts = [self._cache_state(name, (r1 - r0, d, dt, str(dev)), lambda: dict(head=None, spare=None, tail=None))
+               for name, r0, r1 in segs]
+        for (name, r0, r1), st in zip(segs, sts):
             if st.spare is None:
                 st.spare = torch.empty((r1 - r0, d), dtype=dt, device=dev)
-            sts.append(st)
         sums = self.ops.step_cache_probe([h0[r0:r1] for _, r0, r1 in segs], [h1[r0:r1] for _, r0, r1 in segs],
                                          [st.head for st in sts], [st.spare for st in sts],
                                          [h1_copy[r0:r1] for _, r0, r1 in segs]).tolist()     # the host read
@@ -507,35 +720,21 @@ class FirstBlockCacheMixin:
                 o.step_cache_residual(st.tail, h1_copy[r0:r1], out=x[r0:r1], subtract=False)
 
     # ---------------------------------------------------------------- Pyramid Attention Broadcast
-    @property
-    def _pab_on(self):
-        return self._step_cache_config is not None and _is_pab_config(self._step_cache_config)
-
     def _pab_begin(self, b, n, d, dtype, device, contexts=None):
         """The decisions of one forward, taken before anything is launched: None when Pyramid Attention Broadcast is off, else
-        `.segs` = one entry per row segment (`_step_cache_segments`' segments) with `.name`, `.r0`, `.r1`, `.state` and
-        `.compute[kind]`, and `.hooked[kind]`.  Reads the timestep callback ONCE (a device tensor costs its one host read here,
-        not one per layer), advances every hooked kind's counter and appends to `cache_log`.  A context whose rows, width,
-        dtype or device changed starts over (the model switches `live_rows` off under this cache, so there is no live-row
-        range to key on)."""
+        a `_BroadcastPlan`.  Reads the timestep callback ONCE (a device tensor costs its one host read here, not one per
+        layer), advances every hooked kind's counter and appends to `cache_log`.  A context whose rows, width, dtype or
+        device changed starts over (the model switches `live_rows` off under this cache, so there is no live-row range to
+        key on)."""
         if not self._pab_on:
             return None
         cfg = self._step_cache_config
         segs = self._context_segments(b, n, contexts)
         t = float(cfg.current_timestep_callback())
-        if self._step_cache_log_fresh or not isinstance(self.cache_log, list):
-            self.cache_log = []
-            self._step_cache_log_fresh = False
-        if self._step_cache_states is None:
-            self._step_cache_states = {}
         hooked = {kind: getattr(cfg, rng) is not None for kind, rng, _ in PAB_KINDS}
-        plan = SimpleNamespace(segs=[], hooked=hooked, timestep=t, taylor=None)
+        plan = _BroadcastPlan(hooked, d, dtype, device, timestep=t)
         for name, r0, r1 in segs:
-            key = (r1 - r0, d, dtype, str(device))
-            st = self._step_cache_states.get(name)
-            if st is None or st.key != key:
-                st = self._step_cache_states[name] = SimpleNamespace(key=key, steps=0, iteration={k: 0 for k in hooked},
-                                                                     buffers={})
+            st = self._cache_state(name, (r1 - r0, d, dtype, str(device)), lambda: dict(iteration={k: 0 for k in hooked}, buffers={}))
             compute = {}
             for kind, rng, tsr in PAB_KINDS:
                 if not hooked[kind]:
@@ -549,57 +748,25 @@ class FirstBlockCacheMixin:
             plan.segs.append(SimpleNamespace(name=name, r0=r0, r1=r1, state=st, compute=compute))
         return plan
 
-    @staticmethod
-    def _pab_buffer(seg, kind, layer, d=None, dtype=None, device=None):
-        """the cache of attention module (kind, layer) under the segment's context: [rows, D] in the model dtype, allocated by
-        the first forward that computes (pass d / dtype / device); a reuse step finds it there (KeyError: it never computed)"""
-        buf = seg.state.buffers.get((kind, layer))
-        if buf is None:
-            if d is None:
-                raise KeyError(f"Pyramid Attention Broadcast: no cached output of the {kind}-attention of block {layer} under "
-                               f"context {seg.name!r}")
-            buf = seg.state.buffers[(kind, layer)] = torch.empty((seg.r1 - seg.r0, d), dtype=dtype, device=device)
-        return buf
+    _pab_buffer = staticmethod(_pab_buffer)
 
     # ---------------------------------------------------------------- TaylorSeer
-    @property
-    def _taylor_on(self):
-        return self._step_cache_config is not None and _is_taylorseer_config(self._step_cache_config)
-
-    @property
-    def _taylor_lite(self):
-        return self._taylor_on and bool(getattr(self._step_cache_config, "use_lite_mode", False))
-
-    def _taylorseer_refusals(self, config):
-        """what the model cannot combine with TaylorSeer, raised by `enable_cache` (the model overrides this)"""
-
     def _taylor_begin(self, b, n, d, dtype, device, contexts=None):
-        """The decisions of one forward under TaylorSeer, taken before anything is launched: None when it is off, else a plan
-        shaped like `_pab_begin`'s -- `.segs` = one entry per row segment with `.name`, `.r0`, `.r1`, `.state`,
-        `.compute[kind]` (both kinds decide alike) -- plus, per segment, `.s` (this forward's number), `.k` (its distance to
-        the last computing forward: the `delta` of an update, the offset of a prediction) and `.n_old` / `.n_new` (the valid
-        factor planes before and after a computing forward; a predicting one reads `.n_old`).  `d` / `dtype`: width and dtype
-        of the hooked rows (lite mode: the output head's).  Advances every context's counter, moves `n` and `s_last` of a
-        computing context on, and appends `(context, s, computed)` to `cache_log`.  A context whose rows, width, dtype or
-        device changed starts over."""
+        """The decisions of one forward under TaylorSeer, taken before anything is launched: None when it is off, else a
+        `_TaylorPlan` (both kinds hooked and decided alike) with `.taylor` (the config), `.planes`, `.factor_dtype` and `.lite`.
+        `d` / `dtype`: width and dtype of the hooked rows (lite mode: the output head's).  Advances every context's counter,
+        moves `n` and `s_last` of a computing context on, and appends `(context, s, computed)` to `cache_log`.  A context
+        whose rows, width, dtype or device changed starts over."""
         if not self._taylor_on:
             return None
         cfg = self._step_cache_config
         segs = self._context_segments(b, n, contexts)
-        if self._step_cache_log_fresh or not isinstance(self.cache_log, list):
-            self.cache_log = []
-            self._step_cache_log_fresh = False
-        if self._step_cache_states is None:
-            self._step_cache_states = {}
         planes = int(cfg.max_order) + 1
         fdt = getattr(cfg, "taylor_factors_dtype", None) or dtype
-        plan = SimpleNamespace(segs=[], hooked={"self": True, "cross": True}, taylor=cfg, planes=planes, factor_dtype=fdt,
-                               lite=self._taylor_lite)
+        plan = _TaylorPlan({"self": True, "cross": True}, d, dtype, device, taylor=cfg, planes=planes, factor_dtype=fdt,
+                           lite=self._taylor_lite)
         for name, r0, r1 in segs:
-            key = (r1 - r0, d, dtype, str(device))
-            st = self._step_cache_states.get(name)
-            if st is None or st.key != key:
-                st = self._step_cache_states[name] = SimpleNamespace(key=key, steps=0, n=0, s_last=None, buffers={})
+            st = self._cache_state(name, (r1 - r0, d, dtype, str(device)), lambda: dict(n=0, s_last=None, buffers={}))
             s = st.steps
             compute = bool(taylorseer_decide(s, st.n, cfg))
             k = 0 if st.s_last is None else s - st.s_last
@@ -612,45 +779,9 @@ class FirstBlockCacheMixin:
             plan.segs.append(seg)
         return plan
 
-    @staticmethod
-    def _taylor_buffer(plan, seg, key, d=None, device=None):
-        """the factor planes of hooked tensor `key` ((kind, layer), or "out" in lite mode) under the segment's context:
-        [max_order + 1, rows, D] in the factor dtype, allocated by the first forward that computes (pass d / device); a
-        predicting step finds them there (KeyError: it never computed)"""
-        buf = seg.state.buffers.get(key)
-        if buf is None:
-            if d is None:
-                raise KeyError(f"TaylorSeer: no factors of {key!r} under context {seg.name!r}")
-            buf = seg.state.buffers[key] = torch.empty((plan.planes, seg.r1 - seg.r0, d), dtype=plan.factor_dtype, device=device)
-        return buf
+    _taylor_buffer = staticmethod(_taylor_buffer)
 
     # ---------------------------------------------------------------- FasterCache
-    @property
-    def _faster_on(self):
-        return self._step_cache_config is not None and _is_fastercache_config(self._step_cache_config)
-
-    @property
-    def _faster_attention(self):
-        """whether FasterCache hooks the self-attention branches"""
-        return self._faster_on and _fc(self._step_cache_config, "spatial_attention_block_skip_range") is not None
-
-    def _fastercache_refusals(self, config):
-        """what the model cannot combine with FasterCache, raised by `enable_cache` (the model overrides this)"""
-
-    def _faster_state(self, name, key):
-        if self._step_cache_log_fresh or not isinstance(self.cache_log, list):
-            self.cache_log = []
-            self._step_cache_log_fresh = False
-        if self._step_cache_states is None:
-            self._step_cache_states = {}
-        st = self._step_cache_states.get(name)
-        if st is None or st.key != key:          # first use, or another shape / dtype / device: start over
-            st = self._step_cache_states[name] = SimpleNamespace(
-                key=key, steps=0, ran_prev=False, n=0, buffers={},            # the counter; the self-attention planes
-                out=None, out_i=-1,                                           # this context's last prediction, by reference
-                d_low=None, d_high=None, has_delta=False, a_low=1.0, a_high=1.0)      # ("uncond": the delta and its weights)
-        return st
-
     def _faster_will_skip(self):
         """whether the NEXT "uncond" forward of the denoising loop skips its stack (nothing is advanced): the loop's two-stream
         path asks before it forks"""
@@ -672,13 +803,7 @@ class FirstBlockCacheMixin:
         if not self._faster_on:
             return None
         cfg = self._step_cache_config
-        names = tuple(contexts) if contexts is not None else None
-        if names is not None and (len(names) != b or len(set(names)) != b):
-            raise ValueError(f"_cache_contexts {names}: need {b} distinct names, one per batch element")
-        if names is None:
-            if self._ctx_name is None:
-                raise ValueError("No context is set. Please set a context before retrieving the state.")
-            names = (self._ctx_name,)
+        names = tuple(name for name, _, _ in self._context_segments(b, 1, contexts))
         t = float(cfg.current_timestep_callback())
         mode = None
         if _fc(cfg, "unconditional_batch_skip_range") is not None and not bool(_fc(cfg, "is_guidance_distilled")):
@@ -689,7 +814,10 @@ class FirstBlockCacheMixin:
         key = (tuple(shape), dtype, str(device), b if contexts is None else 1)
         plan = SimpleNamespace(t=t, mode=mode, skip=False, entries=[], cfg=cfg)
         for name in names:
-            st = self._faster_state(name, key)
+            st = self._cache_state(name, key, lambda: dict(
+                ran_prev=False, n=0, buffers={},                              # the self-attention planes
+                out=None, out_i=-1,                                           # this context's last prediction, by reference
+                d_low=None, d_high=None, has_delta=False, a_low=1.0, a_high=1.0))     # ("uncond": the delta and its weights)
             i = st.steps
             stack = True
             if name == "uncond" and mode in ("batched", "uncond"):
@@ -703,15 +831,15 @@ class FirstBlockCacheMixin:
         return plan
 
     def _faster_attention_plan(self, faster, b, n, d, dtype, device):
-        """the self-attention decisions of the forward as a plan of TaylorSeer's shape (`_taylor_begin`), for the contexts whose
-        stack runs: only the "self" kind is hooked, a computing segment updates two planes with delta 1, a skipping one
-        predicts with the coefficients [1, w]; None when the self-attention is not hooked"""
+        """the self-attention decisions of the forward as a `_TaylorPlan`, for the contexts whose stack runs: only the "self"
+        kind is hooked, a computing segment updates two planes with delta 1, a skipping one predicts with the coefficients
+        [1, w] (`_faster_weight`); None when the self-attention is not hooked"""
         if not self._faster_attention:
             return None
         entries = [e for e in faster.entries if e.stack]
         joint = len(entries) == 1 and b > 1                      # a batch under one context: one segment for all rows
-        plan = SimpleNamespace(segs=[], hooked={"self": True, "cross": False}, taylor=faster.cfg, planes=2, factor_dtype=dtype,
-                               lite=False, faster=True)
+        plan = _TaylorPlan({"self": True, "cross": False}, d, dtype, device, taylor=faster.cfg, planes=2, factor_dtype=dtype,
+                           weight=self._faster_weight)
         for j, e in enumerate(entries):
             st = e.state
             r0, r1 = (0, b * n) if joint else (j * n, (j + 1) * n)
@@ -731,9 +859,25 @@ class FirstBlockCacheMixin:
         reference): once both have, the delta of that step is taken (ops.fastercache_delta) and the weights start at 1"""
         st = entry.state
         st.out, st.out_i = out, entry.i
-        if getattr(self, "_faster_defer_delta", False):
-            return
-        self._faster_delta_now()
+        if not self._faster_defer_delta:
+            self._faster_delta_now()
+
+    @contextlib.contextmanager
+    def _cfg_two_streams(self, main, streams):
+        """One denoising step's CFG branches on two side streams: fork them off `main` at entry, join them at exit.  Under
+        FasterCache the delta of the step reads both predictions: it is deferred while the branches run and taken here, after
+        `main` waits for both."""
+        for s in streams:
+            s.wait_stream(main)
+        self._faster_defer_delta = self._faster_on
+        try:
+            yield
+        finally:
+            self._faster_defer_delta = False
+        for s in streams:
+            main.wait_stream(s)
+        if self._faster_on:
+            self._faster_delta_now()
 
     def _faster_delta_now(self):
         states = self._step_cache_states or {}
@@ -761,13 +905,13 @@ class FirstBlockCacheMixin:
         return self.ops.fastercache_apply(cond_out, u.d_low, u.d_high, u.a_low, u.a_high, out=out)
 
 
-class PyramidAttentionBroadcastMixin(FirstBlockCacheMixin):
+class PyramidAttentionBroadcastMixin(StepCacheMixin):
     """The same surface for a model that implements Pyramid Attention Broadcast alone (CogVideoXTransformer3DModel), plus
-    diffusers' `cache_context(name)`.  `FirstBlockCacheConfig` is refused by name.  The model's only attention layer is each
+    diffusers' `cache_context(name)`: every other config is refused by name.  The model's only attention layer is each
     block's joint text + video `attn1`, the "spatial" kind; `temporal_*` and `cross_*` ranges match no layer: a config that sets
     only those is accepted, hooks nothing and says so once.  `_pab_begin` / `_pab_buffer` and the `cache_log` rows are the Wan
     model's -- the last field, the cross-attention's decision, is always True here."""
-    _cache_configs_implemented = "PyramidAttentionBroadcastConfig is"
+    _cache_policies = (_PabPolicy,)
     _ctx_name = None
 
     @contextlib.contextmanager
@@ -779,15 +923,8 @@ class PyramidAttentionBroadcastMixin(FirstBlockCacheMixin):
             self._ctx_name = prev
 
     def enable_cache(self, config):
-        if not self.is_cache_enabled and _is_fbc_config(config):
-            raise NotImplementedError(f"FirstBlockCacheConfig is not implemented on {type(self).__name__}; "
-                                      f"{self._cache_configs_implemented}")
-        if not self.is_cache_enabled and type(config).__name__ == _TAYLOR_NAME:       # with or without its attributes
-            raise NotImplementedError(f"{_TAYLOR_NAME} is not implemented on this model; {self._cache_configs_implemented}")
-        if not self.is_cache_enabled and type(config).__name__ == _FASTER_NAME:
-            raise NotImplementedError(f"{_FASTER_NAME} is not implemented on this model; {self._cache_configs_implemented}")
         super().enable_cache(config)
-        if self._pab_on and config.spatial_attention_block_skip_range is None:
+        if config.spatial_attention_block_skip_range is None:
             warnings.warn(f"Pyramid Attention Broadcast: `spatial_attention_block_skip_range` is None and the temporal / cross "
                           f"ranges match no attention layer of {type(self).__name__} (its only one is the joint attn1 of every "
                           f"block, the spatial kind): this config hooks nothing and every forward computes.", stacklevel=2)

@@ -33,7 +33,7 @@ from .attention_processor import Attention, MI355WanAttnProcessor
 from .loading import FromPretrainedMixin
 from .lora import LoraModelMixin
 from .mx_linears import MXLinearsMixin
-from .step_cache import FirstBlockCacheMixin
+from .step_cache import StepCacheMixin
 from .window_attention import SelfAttentionOptionsMixin
 
 
@@ -120,7 +120,7 @@ class WanTransformerBlock(nn.Module):
         self.scale_shift_table = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
 
 
-class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, FirstBlockCacheMixin, MXLinearsMixin,
+class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, StepCacheMixin, MXLinearsMixin,
                             SelfAttentionOptionsMixin):
     """MX linears (enable_mxfp8_linears / enable_mxfp6_linears): the six large linears of every block -- QKV, attention out,
     cross-attention q / out, FFN up / down.
@@ -301,68 +301,37 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         if fp8:
             raise NotImplementedError(f"{what} with fp8 attention: the range walk exists in the bf16 / fp16 kernel only; switch "
                                       f"one of them off first (disable_window_attention() / enable_fp8_attention(False))")
-        if self._pab_on:
-            raise NotImplementedError(f"{what} with Pyramid Attention Broadcast: not implemented in this version (first-block "
-                                      f"caching is)")
-        if self._taylor_on:
-            raise NotImplementedError(f"{what} with TaylorSeer caching: not implemented in this version (first-block caching is)")
-        if self._faster_attention:
-            raise NotImplementedError(f"{what} with FasterCache's self-attention extrapolation: not implemented in this version "
-                                      f"(`spatial_attention_block_skip_range=None` keeps its unconditional-branch part alone, "
-                                      f"which is)")
+        self._cache_refusals(window=True)
         if shard is not None and getattr(shard, "active", True):
             raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
         if not default_procs:
             raise NotImplementedError(f"{what} with a user-installed attention processor: the windows are applied by the "
                                       f"built-in MI355WanAttnProcessor path only")
 
-    def enable_cache(self, config):
-        from .step_cache import _is_pab_config
-        if self._sparse is not None and _is_pab_config(config):
-            raise NotImplementedError("Pyramid Attention Broadcast with sparse attention (enable_sparse_attention): not "
-                                      "implemented in this version (first-block caching is)")
-        if self._window is not None and _is_pab_config(config):
-            raise NotImplementedError("Pyramid Attention Broadcast with window attention (enable_window_attention): not "
-                                      "implemented in this version (first-block caching is)")
-        return super().enable_cache(config)
-
-    def _taylorseer_refusals(self, config):
-        """what TaylorSeer does not combine with, at `enable_cache` (the other order is refused where the other feature is
-        enabled, or by the forward before its first launch: `_window_refusals`, `_sparse_refusals`, `_bind`)"""
-        what = "TaylorSeer caching (TaylorSeerCacheConfig)"
-        if self._window is not None:
-            raise NotImplementedError(f"{what} with window attention (enable_window_attention): not implemented in this version "
-                                      f"(first-block caching is)")
-        if self._sparse is not None:
-            raise NotImplementedError(f"{what} with sparse attention (enable_sparse_attention): not implemented in this version "
-                                      f"(first-block caching is)")
-        if self.parallel is not None and getattr(self.parallel, "active", True):
-            raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
-        if not getattr(config, "use_lite_mode", False) and not self._default_processors():
-            raise NotImplementedError(f"{what} with a user-installed attention processor: the attention branches are predicted on "
-                                      f"the built-in MI355WanAttnProcessor path only (lite mode, `use_lite_mode=True`, predicts "
-                                      f"the model's output and takes any processor)")
-
-    def _fastercache_refusals(self, config):
-        """what FasterCache does not combine with, at `enable_cache`.  Its unconditional-branch part sits around the forward
-        and takes everything the forward supports on one GPU; the self-attention part, when hooked, refuses what TaylorSeer's
-        default mode refuses (the other order: `_window_refusals`, `_sparse_refusals`, `_bind`)"""
-        what = "FasterCache (FasterCacheConfig)"
-        if self.parallel is not None and getattr(self.parallel, "active", True):
-            raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
-        if getattr(config, "spatial_attention_block_skip_range", None) is None:
+    def _cache_refusals(self, policy=None, config=None, enabling=False, window=False, sparse=False, shard=None, default_procs=True):
+        """What a step cache does not combine with on this model, in both orders.  `enabling`: `enable_cache` asks about `policy`
+        and `config`, against what the model has on; else the enabled cache is asked about the feature that is being switched
+        on (`window` / `sparse`: `_window_refusals`, `_sparse_refusals`) and about the forward that is about to run (`shard`,
+        `default_procs`: `_bind`, before its first launch).  No cache runs token-sharded.  One that takes over the attention
+        branches (`policy.hooks_attention`) does not run beside window or sparse attention and needs the built-in processors;
+        the policies state the two exceptions (`takes_windows`, `takes_any_processor`)."""
+        policy = policy or self._step_cache_policy
+        if policy is None:
             return
-        what = "FasterCache's self-attention extrapolation (FasterCacheConfig.spatial_attention_block_skip_range)"
-        if self._window is not None:
-            raise NotImplementedError(f"{what} with window attention (enable_window_attention): not implemented in this version "
-                                      f"(pass None: the unconditional-branch part alone is)")
-        if self._sparse is not None:
-            raise NotImplementedError(f"{what} with sparse attention (enable_sparse_attention): not implemented in this version "
-                                      f"(pass None: the unconditional-branch part alone is)")
-        if not self._default_processors():
-            raise NotImplementedError(f"{what} with a user-installed attention processor: the attention branches are "
-                                      f"extrapolated on the built-in MI355WanAttnProcessor path only (pass None: the "
-                                      f"unconditional-branch part alone takes any processor)")
+        config = config if enabling else self._step_cache_config
+        if enabling:
+            window, sparse, shard = self._window is not None, self._sparse is not None, self.parallel
+            default_procs = policy.takes_any_processor(config) or self._default_processors()
+        if shard is not None and getattr(shard, "active", True):
+            raise NotImplementedError(f"{policy.label} with a token-sharded plan: the step caches run on one GPU")
+        what = policy.attention_label or policy.label
+        for on, other in ((window, "window attention (enable_window_attention)"), (sparse, "sparse attention (enable_sparse_attention)")):
+            if on and not policy.takes_windows(config):
+                first, second = (what, other) if enabling else (other, what)
+                raise NotImplementedError(f"{first} with {second}: not implemented in this version ({policy.instead})")
+        if not default_procs and not policy.takes_any_processor(config):
+            raise NotImplementedError(f"{what} with a user-installed attention processor: the attention branches are predicted on "
+                                      f"the built-in MI355WanAttnProcessor path only")
 
     def disable_cache(self):
         super().disable_cache()
@@ -579,10 +548,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         their own, its prediction written into row 0 of the result -- and rebuilds row 1; the "uncond" call of a skipping step
         runs nothing but the rebuild.  -> the prediction [b, C, F, H, W]"""
         b = hidden_states.shape[0]
-        sh = args[2] if args[2] is not None else self.parallel
-        if sh is not None and sh.active:
-            raise NotImplementedError("first-block caching, Pyramid Attention Broadcast, TaylorSeer caching and FasterCache run on "
-                                      "one GPU: a token-sharded forward cannot take the cache")
+        self._cache_refusals(shard=args[2] if args[2] is not None else self.parallel)      # (before the forward counts)
         fc = self._faster_begin(b, hidden_states.shape[1:], hidden_states.dtype, hidden_states.device, contexts)
         entry = {e.name: e for e in fc.entries}
         if fc.mode == "batched" and fc.skip:
@@ -634,7 +600,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             m = c.mod[:, li]                                                      # [R, 6, D] view, row stride = layers*6*D
             if c.live is not None and li == last:
                 c.rows, c.segs = c.live, c.live_segs                              # dead rows: keys and values only
-            if c.pab is not None:
+            if c.branches is not None:
                 self._pab_attention(c, li, blk, e, m)                             # 1. + 2., each computed or re-used
             else:
                 if not self._self_attention(c, li, blk, e, m):                    # 1. self-attention (:334-336)
@@ -703,6 +669,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
             self._window_refusals(self.fp8_attention, default_procs, sh)
         if self._sparse is not None:             # ... and what sparse attention refuses
             self._sparse_refusals(self.fp8_attention, default_procs, sh)
+        self._cache_refusals(shard=sh, default_procs=default_procs)      # ... and what the enabled step cache refuses
         lo, n, lpad = 0, L, L
         tk = {}         # the shard's tile height for its GEMM calls (a per-call argument of the C ABI; {} = the library's planner)
         if sh is not None:
@@ -710,36 +677,21 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                 raise NotImplementedError("token-sharded execution runs one sample per call")
             lo, n, lpad = sh.rows(L)              # first row, valid rows, padded shard length (equal on all ranks)
             cos1, sin1 = cos1[lo:lo + n].contiguous(), sin1[lo:lo + n].contiguous()
-            if self.is_cache_enabled:
-                raise NotImplementedError("first-block caching, Pyramid Attention Broadcast, TaylorSeer caching and FasterCache run "
-                                          "on one GPU: a token-sharded forward cannot take the cache")
             if sh.gemm_tile_m:
                 tk = {"tile_m": sh.tile_m_for(n)}
-        fbc = self._step_cache_segments(b, n, cache_contexts)      # None: no cache (nothing extra allocated or launched)
-        # Pyramid Attention Broadcast: this forward's decisions (the timestep callback is read here, once, before any launch)
-        pab = self._pab_begin(b, n, d, dt, dev, cache_contexts)
-        # TaylorSeer: this forward's decisions, from the step counters alone.  Default mode drives the attention branches through
-        # the same route as Pyramid Attention Broadcast (`pab`); lite mode sits around the block stack (`lite`)
-        lite = None
-        if self._taylor_on:
-            if not self._taylor_lite and not default_procs:
-                raise NotImplementedError("TaylorSeer caching (TaylorSeerCacheConfig) with a user-installed attention processor: "
-                                          "the attention branches are predicted on the built-in MI355WanAttnProcessor path only")
-            po_dim = cfg.out_channels * math.prod(cfg.patch_size)
-            if self._taylor_lite:
-                lite = self._taylor_begin(b, n, po_dim, dt, dev, cache_contexts)
-                if not any(seg.compute["self"] for seg in lite.segs):
-                    # every segment predicts: no embedding, no block, no head -- the call needs its geometry and the output rows
-                    return _Call(b=b, n=n, nr=b * n, L=L, nf=nf, hh=hh, ww=ww, d=d, dev=dev, dt=dt, sh=None,
-                                 ws=self._workspace(b * lpad, dt, dev), lite=lite, live=None, segs=[(0, b * n)], out_buf=None)
-            else:
-                pab = self._taylor_begin(b, n, d, dt, dev, cache_contexts)
-        if faster is not None and self._faster_attention:
-            # FasterCache's self-attention part: TaylorSeer's route through the attention branches, its own decisions
-            if not default_procs:
-                raise NotImplementedError("FasterCache's self-attention extrapolation with a user-installed attention processor: "
-                                          "the attention branches are extrapolated on the built-in MI355WanAttnProcessor path only")
-            pab = self._faster_attention_plan(faster, b, n, d, dt, dev)
+        # the step cache's places in this forward, each None when it does not sit there: `fbc` around block 0 (first-block
+        # caching), `lite` around the whole stack (TaylorSeer's lite mode), `branches` in every block's attention branches.
+        # Their decisions are taken here, before any launch (a timestep callback is read once)
+        policy = self._step_cache_policy
+        fbc = lite = branches = None
+        if policy is not None:
+            fbc = policy.segments(self, b, n, cache_contexts)
+            lite = policy.lite(self, b, n, cfg.out_channels * math.prod(cfg.patch_size), dt, dev, cache_contexts)
+            if lite is not None and not any(seg.compute["self"] for seg in lite.segs):
+                # every segment predicts: no embedding, no block, no head -- the call needs its geometry and the output rows
+                return _Call(b=b, n=n, nr=b * n, L=L, nf=nf, hh=hh, ww=ww, d=d, dev=dev, dt=dt, sh=None,
+                             ws=self._workspace(b * lpad, dt, dev), lite=lite, live=None, segs=[(0, b * n)], out_buf=None)
+            branches = policy.branches(self, b, n, d, dt, dev, cache_contexts, faster)
         # Batch elements are extra ROWS of the token-major buffers ([B*n, D]): every GEMM / norm is one launch over
         # both CFG branches (twice the tiles per launch, weights read once); attention and RoPE index rows per batch.
         nr = b * n
@@ -764,7 +716,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         # would have computed).  A per-sample timestep ([b] or [b, L] values) takes the general path.
         # (Pyramid Attention Broadcast keeps one cache per context and layer: every element runs block 0's branch itself)
         shared = (self.dedup_shared_prefix and b > 1 and sh is None and hidden_states.stride(0) == 0 and default_procs
-                  and same_rows and pab is None)
+                  and same_rows and branches is None)
         fold = self.fold_softmax_scale
         fp8 = self.fp8_attention and sh is None and hasattr(o, "attention_fp8")     # this call's self-attention takes fp8 operands
         # sliding-window self-attention over frames: this forward's decision (the timestep callback is read here, once)
@@ -775,7 +727,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
         live = None
         # (not under Pyramid Attention Broadcast: a cached branch output covers every row, so that any later step may use it)
         if (live_rows is not None and self.skip_dead_rows and default_procs and sh is None and len(self.blocks) > 1
-                and not self._fp8 and not fp8 and pab is None and lite is None):
+                and not self._fp8 and not fp8 and branches is None and lite is None):
             l0, l1 = int(live_rows[0]), int(live_rows[1])
             if 0 <= l0 < l1 <= n and (l1 - l0) < n:
                 live = (l0, l1)
@@ -786,7 +738,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
                      ff=ws.ff[:nr], qkv=ws.qkv[:nr], cos=cos, sin=sin, cos1=cos1, sin1=sin1, sel=sel, mod=mod, head=head,
                      text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
                      afold={"scale": o.SCALE_FOLDED} if fold else {}, fp8=fp8, default_procs=default_procs,
-                     shared=shared, fbc=fbc, pab=pab, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
+                     shared=shared, fbc=fbc, branches=branches, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
                      live=live, win=win, sp=sp, lite=lite, out_buf=out_buf,
                      live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
                      rows=(0, n),            # the rows of every batch element that run as queries / per-token rows ...
@@ -1034,73 +986,39 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Firs
 
     # ------------------------------------------------------------------ forward: Pyramid Attention Broadcast
     def _pab_attention(self, c, li, blk, e, m):
-        """Block li's two attention branches under Pyramid Attention Broadcast (`c.pab`: this forward's decisions per row
-        segment = batch element and kind, frameino_amd/step_cache.py).
+        """Block li's two attention branches under a cache that has taken them over (`c.branches`: this forward's decisions per
+        row segment and kind, a `_BranchPlan` of frameino_amd/step_cache.py -- Pyramid Attention Broadcast, TaylorSeer's default
+        mode or FasterCache's self-attention part; the plan knows which, this loop does not).
         Compute: the launches of `_self_attention` / `_self_attention_out` / `_cross_attention`, the closing GEMM with `keep=`
-        into the segment's buffer of this layer (`c.keep`; a custom processor's return value is copied there).
-        Re-use: none of the branch runs; one launch adds the cached y to the residual stream with the closing GEMM's epilogue
-        arithmetic (`_pab_reuse`).  A kind that is not hooked runs as without the cache.  The elements of a batch (the CFG
-        branches of a batched call: one context and one buffer each, and counters that may differ) take a hooked branch one
-        by one, each on a one-element view of the call: per row the launches compute what the batched ones do.
-        TaylorSeer in default mode (`pab.taylor`: its plan has the same shape, both kinds hooked and decided alike) takes the
-        same route: a computing branch keeps y in the workspace's one [n, D] scratch and `ops.taylor_update` folds it into the
-        factors of (kind, layer); a predicting one is `_taylor_predict`."""
-        pab, n = c.pab, c.n
-        stages = (("self", lambda cc: self._self_attention(cc, li, blk, e, m) or self._self_attention_out(cc, li, blk, m)),
-                  ("cross", lambda cc: self._cross_attention(cc, li, blk)))
-        for kind, run in stages:
-            if not pab.hooked[kind]:
+        into the buffer the plan names (`c.keep`; a custom processor's return value is copied there), then what the plan runs
+        on that y.  Re-use: none of the branch runs; the plan's one launch adds the cached or extrapolated y to the residual
+        stream with the closing GEMM's epilogue arithmetic.  A kind that is not hooked runs as without the cache.  The elements
+        of a batch (the CFG branches of a batched call: one context and one buffer each, and counters that may differ) take a
+        hooked branch one by one, each on a one-element view of the call: per row the launches compute what the batched ones do."""
+        plan, n, o = c.branches, c.n, self.ops
+        stages = (("self", blk.attn1, lambda cc: self._self_attention(cc, li, blk, e, m) or self._self_attention_out(cc, li, blk, m)),
+                  ("cross", blk.attn2, lambda cc: self._cross_attention(cc, li, blk)))
+        for kind, module, run in stages:
+            if not plan.hooked[kind]:
                 run(c)
                 continue
             for i in range(c.b):
                 # the segment element i's rows lie in: its own (one context per element), or the joint one of a batch under one
                 # context -- one decision, one [b * n, D] buffer, of which the element takes its rows
-                seg = next(s_ for s_ in pab.segs if s_.r0 <= i * n < s_.r1)
+                r0, r1 = i * n, (i + 1) * n
+                seg = plan.segment(r0)
                 if not seg.compute[kind]:
-                    (self._pab_reuse if pab.taylor is None else self._taylor_predict)(c, kind, seg, i, li, m)
+                    gate, sel = (m[:, 2], _sel_rows(c.sel, r0, r1)) if kind == "self" else (None, None)
+                    plan.reuse(o, seg, kind, li, r0, r1, c.x[r0:r1], gate, sel, module=module, fused=c.default_procs)
                     continue
                 cc = c if c.b == 1 else c.element(i)
-                if pab.taylor is None:
-                    y = self._pab_buffer(seg, kind, li, c.d, c.dt, c.dev)[i * n - seg.r0:(i + 1) * n - seg.r0]
-                else:
-                    y = self._taylor_scratch(c)
+                y = plan.kept(c.ws, seg, kind, li, r0, r1)
                 cc.keep = {(0, n): y}
                 try:
                     run(cc)
                 finally:
                     cc.keep = None
-                if pab.taylor is not None:                # the branch's y -> the factors of (kind, layer) under the segment
-                    f = self._taylor_buffer(pab, seg, (kind, li), c.d, c.dev)[:, i * n - seg.r0:(i + 1) * n - seg.r0]
-                    self.ops.taylor_update(y, f, seg.n_old, seg.k, seg.n_new)
-
-    def _pab_reuse(self, c, kind, seg, i, li, m):
-        """x += gate * y (self-attention) / x += y (cross-attention) on batch element i from the cached y, bit for bit what
-        the step that computed y wrote: the fused epilogues multiply-add once (`ops.pab_broadcast`), a custom processor's
-        result went through `ops.gated_residual`."""
-        o, r0, r1 = self.ops, i * c.n, (i + 1) * c.n
-        y, x = self._pab_buffer(seg, kind, li)[r0 - seg.r0:r1 - seg.r0], c.x[r0:r1]
-        gate, sel = (m[:, 2], _sel_rows(c.sel, r0, r1)) if kind == "self" else (None, None)
-        (o.pab_broadcast if c.default_procs else o.gated_residual)(x, y, gate, sel, out=x)
-
-    # ------------------------------------------------------------------ forward: TaylorSeer
-    def _taylor_scratch(self, c):
-        """the one [n, D] buffer of the workspace a computed branch's y = T(acc + bias) is kept in (`keep=` of its closing
-        GEMM) until the update launch that follows has read it"""
-        ws = c.ws
-        if getattr(ws, "taylor_y", None) is None:
-            ws.taylor_y = torch.empty((c.n, c.d), dtype=c.dt, device=c.dev)
-        return ws.taylor_y
-
-    def _taylor_predict(self, c, kind, seg, i, li, m):
-        """x += gate * p (self-attention) / x += p (cross-attention) on batch element i, p the Taylor extrapolation of the
-        branch's y from its factors: one launch with the closing GEMM's epilogue arithmetic, none of the branch runs"""
-        r0, r1 = i * c.n, (i + 1) * c.n
-        f, x = self._taylor_buffer(c.pab, seg, (kind, li))[:, r0 - seg.r0:r1 - seg.r0], c.x[r0:r1]
-        gate, sel = (m[:, 2], _sel_rows(c.sel, r0, r1)) if kind == "self" else (None, None)
-        if getattr(c.pab, "faster", False):      # FasterCache: y_1 + (y_1 - y_0) * w, the weight of this block's attn1
-            self.ops.taylor_predict(f, seg.n_old, 1, x, gate, sel, out=x, coef=[1.0, self._faster_weight(self.blocks[li].attn1)])
-            return
-        self.ops.taylor_predict(f, seg.n_old, seg.k, x, gate, sel, out=x)
+                plan.computed(o, seg, kind, li, r0, r1, y)
 
     def _taylor_lite_rows(self, c, po):
         """TaylorSeer in lite mode on the output head's rows `po` [b * n, C_out * prod(patch)]: a computing segment's rows
@@ -1164,14 +1082,15 @@ class _Call:
     """What the stages of one `WanTransformer3DModel.forward_steps` call share (built by `_bind` at the first `next()`): sizes,
     the token shard, views of the workspace, tables and the switches that pick a path.  References and views only: nothing on
     the device the call would not hold anyway.  `rows` / `segs` (set for the last block under `live_rows`), `h0` / `h1c`
-    (the first-block cache's buffers, set by the embedding stage) and `keep` around a branch that Pyramid Attention
-    Broadcast or TaylorSeer computes ({(first row, end row): the buffer that also receives the closing GEMM's y}; `elements`:
-    the one-element views it runs a batch through) are the only fields written after `_bind`.  `pab`: the plan of Pyramid
-    Attention Broadcast or of TaylorSeer's default mode; `lite`: the plan of TaylorSeer's lite mode -- when every segment of it
-    predicts, `_bind` returns a call with the geometry, the workspace and the plan alone."""
+    (the first-block cache's buffers, set by the embedding stage) and `keep` around a branch that a step cache computes
+    ({(first row, end row): the buffer that also receives the closing GEMM's y}; `elements`: the one-element views it runs a
+    batch through) are the only fields written after `_bind`.  `branches`: the plan of the cache that has taken over the
+    attention branches (`_BranchPlan`: Pyramid Attention Broadcast, TaylorSeer's default mode, FasterCache's self-attention
+    part), else None; `lite`: the plan of TaylorSeer's lite mode -- when every segment of it predicts, `_bind` returns a call
+    with the geometry, the workspace and the plan alone."""
     __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
                  "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
-                 "afold", "fp8", "default_procs", "shared", "fbc", "pab", "keep", "h0", "h1c", "attention_kwargs", "live",
+                 "afold", "fp8", "default_procs", "shared", "fbc", "branches", "keep", "h0", "h1c", "attention_kwargs", "live",
                  "live_segs", "rows", "segs", "win", "sp", "lite", "out_buf", "elements")
 
     def __init__(self, **fields):

@@ -423,15 +423,7 @@ class SelfAttentionOptionsMixin:
             raise NotImplementedError(f"{what} with fp8 attention at head_dim {self.config.attention_head_dim}: the fp8 tile walk "
                                       f"(fino_attn_fwd_fp8_tiles) exists for head_dim 128 only; switch one of them off first "
                                       f"(disable_sparse_attention() / enable_fp8_attention(False))")
-        if getattr(self, "_pab_on", False):
-            raise NotImplementedError(f"{what} with Pyramid Attention Broadcast: not implemented in this version (first-block "
-                                      f"caching is)")
-        if getattr(self, "_taylor_on", False):
-            raise NotImplementedError(f"{what} with TaylorSeer caching: not implemented in this version (first-block caching is)")
-        if getattr(self, "_faster_attention", False):
-            raise NotImplementedError(f"{what} with FasterCache's self-attention extrapolation: not implemented in this version "
-                                      f"(`spatial_attention_block_skip_range=None` keeps its unconditional-branch part alone, "
-                                      f"which is)")
+        self._cache_refusals(sparse=True)        # (a step cache that does not run beside it: the model's one statement)
         if shard is not None and getattr(shard, "active", True):
             raise NotImplementedError(f"{what} with a token-sharded plan: it runs on one GPU")
         if not default_procs:
