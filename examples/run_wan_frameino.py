@@ -81,6 +81,20 @@ def main():
                     help="with --fastercache: also recompute every block's self-attention on every M-th step only while the "
                          "timestep is inside (-1, 681), e.g. 2, and extrapolate it from its last two outputs in between (weight "
                          "0.5).  Not together with --window-frames or --sparse-attention")
+    ap.add_argument("--magcache", default=None, metavar="FILE",
+                    help="diffusers' MagCache (approximate; eager loop; quality on real checkpoints unmeasured) with the per-context "
+                         "curves of FILE (written by --magcache-calibrate at the same --steps): a step whose accumulated magnitude "
+                         "error stays within the threshold runs no block at all and adds the block stack's residual of the last "
+                         "computing step.  Not together with the other cache flags")
+    ap.add_argument("--magcache-threshold", type=float, default=0.06, metavar="X", help="with --magcache: the error bound")
+    ap.add_argument("--magcache-max-skip", type=int, default=3, metavar="K",
+                    help="with --magcache: at most K consecutive skipped steps")
+    ap.add_argument("--magcache-retention", type=float, default=0.2, metavar="R",
+                    help="with --magcache: the first R * steps steps always compute")
+    ap.add_argument("--magcache-calibrate", default=None, metavar="OUT.json",
+                    help="run the clip with MagCache in calibrate mode (every step computes; one extra pass over the residual per "
+                         "step and context) and write the measured curves, per cache context, to OUT.json.  Curves depend on "
+                         "the weights, the step count and the scheduler.  Not together with the other cache flags")
     ap.add_argument("--window-frames", type=int, default=None, metavar="N",
                     help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
                          "every query attends its own frame +- N neighbours plus the first frame and the ID frame, e.g. 2.  Not "
@@ -129,6 +143,11 @@ def main():
         ap.error("--mxfp6-rotate needs --mxfp6")
     if a.fastercache_attention is not None and a.fastercache is None:
         ap.error("--fastercache-attention needs --fastercache")
+    if a.magcache is not None or a.magcache_calibrate is not None:
+        if a.magcache is not None and a.magcache_calibrate is not None:
+            ap.error("--magcache FILE applies curves, --magcache-calibrate OUT.json measures them: one at a time")
+        if any(v is not None for v in (a.first_block_cache, a.pab, a.taylorseer, a.fastercache)):
+            ap.error("--magcache / --magcache-calibrate: not together with --first-block-cache, --pab, --taylorseer or --fastercache")
 
     from frameino_amd import _lib
     from frameino_amd.autoencoder_kl_wan import AutoencoderKLWan
@@ -208,6 +227,12 @@ def main():
                                                    spatial_attention_block_skip_range=a.fastercache_attention,
                                                    attention_weight_callback=lambda _module: 0.5,
                                                    current_timestep_callback=lambda: pipe.current_timestep))
+    if a.magcache is not None or a.magcache_calibrate is not None:
+        from frameino_amd.step_cache import MagCacheConfig, load_mag_ratios
+        transformer.enable_cache(MagCacheConfig(
+            threshold=a.magcache_threshold, max_skip_steps=a.magcache_max_skip, retention_ratio=a.magcache_retention,
+            num_inference_steps=a.steps, calibrate=a.magcache is None,
+            mag_ratios=None if a.magcache is None else load_mag_ratios(a.magcache)))
     if a.mxfp6:                                    # after the LoRA merge: the merged weights are what is quantised
         transformer.enable_mxfp6_linears(rotate=a.mxfp6_rotate)
     if a.fp8_attention:
@@ -275,8 +300,18 @@ def main():
               f"{a.scheduler}) {t2 - t1:.2f} s{' (cold)' if rep == 0 and a.repeat > 1 else ''}, "
               f"frames in [{frames.min():.3f}, {frames.max():.3f}], peak device memory "
               f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
+    if a.magcache_calibrate is not None:           # filed when each context finished its steps: one host read per context
+        from frameino_amd.step_cache import save_mag_ratios
+        cal = transformer.magcache_calibration
+        save_mag_ratios(a.magcache_calibrate, cal)
+        for ctx, entry in cal.items():
+            print(f"magcache calibration [{ctx}]: {len(entry['mag_ratios'])} steps, ratios in [{min(entry['mag_ratios']):.4f}, "
+                  f"{max(entry['mag_ratios']):.4f}], largest cosine distance {max(entry['cos_dist']):.2e} -> {a.magcache_calibrate}")
+    elif a.magcache is not None:
+        log = transformer.cache_log
+        print(f"magcache: {sum(not e[2] for e in log)} of {len(log)} forwards re-used the stack's residual")
     from frameino_amd.conditions import crop_unpadded
-    region = crop_unpadded(frames, *pads)                      # app.py:741-748: the original (un-extended) region
+    region = crop_unpadded(frames, *pads)                     # app.py:741-748: the original (un-extended) region
     print(f"cropped region {tuple(region.shape)} uint8")
     if a.out:
         np.save(a.out, frames)

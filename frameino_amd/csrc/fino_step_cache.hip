@@ -27,6 +27,11 @@
 // unconditional prediction a later step rebuilds from its conditional one, T((c + aL * DL) + aH * DH).  The low-pass is a
 // direct DFT over the half disk of kept bins, one workgroup per plane with the plane in LDS (below).
 //
+// fino_magcache_calibrate (MagCache's calibration pass): the residual r_new = T(x_out - x_in) of the whole block stack -- the
+// bits fino_step_cache_residual writes -- and, in the same pass over HBM, the mean over rows of ||r_new|| / (||r_prev|| + 1e-8)
+// and of the cosine distance to r_prev.  Per-row sums in fp32, sums over rows in fp64, one partial per wave and a second
+// launch that adds the partials in a fixed order: no atomics.
+//
 // HBM-bound: 16-byte loads and stores, fp32 arithmetic, no contraction (the file is built with -ffp-contract=off).
 #include "fino_common.h"
 
@@ -169,6 +174,120 @@ __global__ __launch_bounds__(kThreads) void residual_kernel(const void* a, int64
         for (int e = 0; e < E; ++e) fo[e] = subtract ? fa[e] - fb[e] : fa[e] + fb[e];
         *(uint4*)at(out, row, ldo, col, IO::kBytes) = IO::pack(fo);
     }
+}
+
+// ---- MagCache calibration: r_new = T(x_out - x_in) and, per row, ||r_new||, ||r_prev||, <r_new, r_prev> in fp32 from the
+// rounded values.  One wave per row at a time: lane l takes the 16-byte vectors l, l + 64, ... of the row in order (the loads
+// of kMagUnroll of them per plane in flight), then the xor butterfly; the wave with global index g takes the rows g, g + W,
+// ... (W = the launch's wave count, a function of `rows` alone) and adds their ratio and cosine distance in that order, in
+// fp64, into partial[2 g], partial[2 g + 1].  Every r_prev vector of a thread is in registers before the thread's first
+// store of the chunk, and no two threads share an element: r_new may be r_prev.
+constexpr int kMagUnroll = 4;           // (2, 3, 4 and 6 vectors per plane in flight, and a cap of 1024 / 1280 / 2048
+constexpr int kMagWavesPerBlock = kThreads / 64;        // workgroups, measure alike at [24640, 3072]: within the run's spread)
+constexpr int kMagMaxBlocks = 256 * 8;
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void magcache_kernel(const void* x_out, int64_t ld_out, const void* x_in, int64_t ld_in,
+                                                            const void* r_prev, int64_t ld_prev, void* r_new, int64_t ld_new,
+                                                            int64_t rows, uint32_t vpr, double* partial) {
+    using IO = Io<T>;
+    constexpr int E = IO::kElems;
+    const uint32_t lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * kMagWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * kMagWavesPerBlock;
+    double sum_ratio = 0., sum_cos = 0.;
+    for (int64_t row = wave; row < rows; row += nwaves) {               // wave-uniform: every lane reaches the butterfly
+        float nn = 0.f, pp = 0.f, np = 0.f;
+        for (uint32_t v0 = lane; v0 < vpr; v0 += 64 * kMagUnroll) {
+            uint4 vo[kMagUnroll], vi[kMagUnroll], vp[kMagUnroll];
+#pragma unroll
+            for (int u = 0; u < kMagUnroll; ++u) {
+                const uint32_t v = v0 + u * 64;
+                if (v < vpr) {
+                    vo[u] = *at(x_out, row, ld_out, v * E, IO::kBytes);
+                    vi[u] = *at(x_in, row, ld_in, v * E, IO::kBytes);
+                    vp[u] = *at(r_prev, row, ld_prev, v * E, IO::kBytes);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kMagUnroll; ++u) {
+                const uint32_t v = v0 + u * 64;
+                if (v >= vpr) break;
+                float fo[E], fi[E], fp[E], fr[E];
+                IO::unpack(vo[u], fo);
+                IO::unpack(vi[u], fi);
+                IO::unpack(vp[u], fp);
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    fr[e] = IO::rnd(fo[e] - fi[e]);
+                    nn += fr[e] * fr[e];
+                    pp += fp[e] * fp[e];
+                    np += fr[e] * fp[e];
+                }
+                *(uint4*)at(r_new, row, ld_new, v * E, IO::kBytes) = IO::pack(fr);
+            }
+        }
+        nn = wave_sum(nn);
+        pp = wave_sum(pp);
+        np = wave_sum(np);
+        const float norm_new = sqrtf(nn), norm_prev = sqrtf(pp);
+        const float ratio = norm_new / (norm_prev + 1e-8f);
+        const float cos_dist = 1.f - np / fmaxf(norm_new * norm_prev, 1e-8f);
+        sum_ratio += (double)ratio;
+        sum_cos += (double)cos_dist;
+    }
+    if (lane == 0) {
+        partial[2 * wave] = sum_ratio;
+        partial[2 * wave + 1] = sum_cos;
+    }
+}
+
+// stats = (sum of the n wave partials) / rows: thread t adds the partials t, t + 256, ... in order, then the xor butterfly and
+// the waves in index order, all in fp64 -- a fixed order
+__global__ __launch_bounds__(kThreads) void magcache_finish_kernel(const double* partial, int64_t n, double rows, double* stats) {
+    __shared__ double red[2][kThreads / 64];
+    constexpr int kPer = kMagMaxBlocks * kMagWavesPerBlock / kThreads;      // partials per thread at the grid's cap
+    const double2* pairs = (const double2*)partial;
+    double2 p[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {                // every load in flight before the first add: one round trip, not kPer
+        const int64_t j = threadIdx.x + (int64_t)k * kThreads;
+        p[k] = j < n ? pairs[j] : make_double2(0., 0.);
+    }
+    double a = 0., c = 0.;
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+        a += p[k].x;
+        c += p[k].y;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        c += __shfl_xor(c, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = a;
+        red[1][threadIdx.x >> 6] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = red[0][0];
+        c = red[1][0];
+#pragma unroll
+        for (int w = 1; w < kThreads / 64; ++w) {
+            a += red[0][w];
+            c += red[1][w];
+        }
+        stats[0] = a / rows;
+        stats[1] = c / rows;
+    }
+}
+
+// the waves of a fino_magcache_calibrate launch over `rows` rows: one per row up to the grid's cap, whole workgroups
+int64_t magcache_waves(int64_t rows) {
+    int64_t blocks = (rows + kMagWavesPerBlock - 1) / kMagWavesPerBlock;
+    blocks = blocks < 1 ? 1 : blocks > kMagMaxBlocks ? kMagMaxBlocks : blocks;
+    return blocks * kMagWavesPerBlock;
 }
 
 template <typename T>
@@ -557,6 +676,52 @@ extern "C" int fino_step_cache_residual(const void* a, int64_t lda, const void* 
         residual_kernel<F16><<<(int)grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
     else
         residual_kernel<F32><<<(int)grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
+}
+
+extern "C" int64_t fino_magcache_workspace_bytes(int64_t rows) {
+    return rows < 1 ? 0 : magcache_waves(rows) * 2 * (int64_t)sizeof(double);
+}
+
+extern "C" int fino_magcache_calibrate(const void* x_out, int64_t ld_out, const void* x_in, int64_t ld_in, const void* r_prev,
+                                       int64_t ld_prev, void* r_new, int64_t ld_new, int64_t rows, int64_t dim, int dtype,
+                                       double* stats, void* workspace, int64_t workspace_bytes, void* stream) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16 || dtype == FINO_F32, FINO_ERR_ARG, "fino_magcache_calibrate: dtype %d",
+               dtype);
+    const int per16 = 16 / esize_of(dtype);
+    FINO_CHECK(rows >= 1 && rows < (1LL << 31), FINO_ERR_ARG, "fino_magcache_calibrate: rows=%lld (1 .. 2^31 - 1)",
+               (long long)rows);
+    FINO_CHECK(dim > 0 && dim % per16 == 0 && dim / per16 < (1LL << 31), FINO_ERR_ARG,
+               "fino_magcache_calibrate: dim=%lld must be a multiple of %d", (long long)dim, per16);
+    FINO_CHECK(x_out && x_in && r_prev && r_new && stats && workspace, FINO_ERR_ARG, "fino_magcache_calibrate: null pointer");
+    FINO_CHECK(ld_out >= dim && ld_in >= dim && ld_prev >= dim && ld_new >= dim, FINO_ERR_ARG,
+               "fino_magcache_calibrate: a row stride is below dim");
+    FINO_CHECK(rows_ok(x_out, ld_out, dtype) && rows_ok(x_in, ld_in, dtype) && rows_ok(r_prev, ld_prev, dtype) &&
+                   rows_ok(r_new, ld_new, dtype) && fino_aligned16(stats) && fino_aligned16(workspace),
+               FINO_ERR_ARG, "fino_magcache_calibrate: 16-byte alignment required");
+    FINO_CHECK(r_new != r_prev || ld_new == ld_prev, FINO_ERR_ARG,
+               "fino_magcache_calibrate: r_new aliases r_prev with another row stride (%lld / %lld)", (long long)ld_new,
+               (long long)ld_prev);
+    const int64_t nwaves = magcache_waves(rows);
+    FINO_CHECK(workspace_bytes >= fino_magcache_workspace_bytes(rows), FINO_ERR_ARG,
+               "fino_magcache_calibrate: workspace of %lld bytes, need %lld (fino_magcache_workspace_bytes)",
+               (long long)workspace_bytes, (long long)fino_magcache_workspace_bytes(rows));
+    const uint32_t vpr = (uint32_t)(dim / per16);
+    const int grid = (int)(nwaves / kMagWavesPerBlock);
+    hipStream_t st = (hipStream_t)stream;
+    double* partial = (double*)workspace;
+    if (dtype == FINO_BF16)
+        magcache_kernel<BF16><<<grid, kThreads, 0, st>>>(x_out, ld_out, x_in, ld_in, r_prev, ld_prev, r_new, ld_new, rows, vpr,
+                                                         partial);
+    else if (dtype == FINO_F16)
+        magcache_kernel<F16><<<grid, kThreads, 0, st>>>(x_out, ld_out, x_in, ld_in, r_prev, ld_prev, r_new, ld_new, rows, vpr,
+                                                        partial);
+    else
+        magcache_kernel<F32><<<grid, kThreads, 0, st>>>(x_out, ld_out, x_in, ld_in, r_prev, ld_prev, r_new, ld_new, rows, vpr,
+                                                        partial);
+    FINO_LAUNCH_CHECK();
+    magcache_finish_kernel<<<1, kThreads, 0, st>>>(partial, nwaves, (double)rows, stats);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }

@@ -1342,6 +1342,39 @@ def step_cache_residual(a, b, out=None, subtract=True):
     return out
 
 
+_MAGCACHE_WS = {}                          # (device, stream) -> the partials' workspace (bytes)
+
+
+def magcache_calibrate(x_out, x_in, r_prev, r_new, stats):
+    """MagCache's calibration pass (fino_magcache_calibrate): r_new = T(x_out - x_in), bit for bit `step_cache_residual`'s, and in
+    the same pass stats[0] = mean over rows of ||r_new|| / (||r_prev|| + 1e-8), stats[1] = mean over rows of the cosine distance
+    1 - <r_new, r_prev> / max(||r_new|| ||r_prev||, 1e-8) -- norms over the rounded values in fp32, means in fp64.  Row-strided
+    [rows, D] bf16 / fp16 / fp32 operands; r_new may be r_prev; `stats` a caller-owned fp64 device tensor [2].  Nothing is read
+    back: the call adds no host sync.  Deterministic bit for bit.  -> r_new"""
+    dt = x_out.dtype
+    _rows_of(x_out, dt, "magcache_calibrate x_out")
+    for t, what in ((x_in, "x_in"), (r_prev, "r_prev"), (r_new, "r_new")):
+        if _rows_of(t, dt, f"magcache_calibrate {what}").shape != x_out.shape or t.device != x_out.device:
+            raise ValueError(f"magcache_calibrate: {what} is {tuple(t.shape)} on {t.device}, want {tuple(x_out.shape)} on "
+                             f"{x_out.device}")
+    if (not stats.is_cuda or stats.dtype != torch.float64 or tuple(stats.shape) != (2,) or stats.stride(0) != 1
+            or stats.device != x_out.device):
+        raise ValueError(f"magcache_calibrate: stats must be a contiguous fp64 [2] tensor on {x_out.device}, got "
+                         f"{tuple(stats.shape)} {stats.dtype} on {stats.device}")
+    rows, d = x_out.shape
+    if rows < 1:
+        raise ValueError("magcache_calibrate: no rows")
+    need = _lib.lib().fino_magcache_workspace_bytes(rows)
+    key = (str(x_out.device), _stream())    # two CFG branches on two streams never share the partials
+    ws = _MAGCACHE_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _MAGCACHE_WS[key] = torch.empty(need, dtype=torch.uint8, device=x_out.device)
+    _lib.check(_lib.lib().fino_magcache_calibrate(_p(x_out), x_out.stride(0), _p(x_in), x_in.stride(0), _p(r_prev),
+                                                  r_prev.stride(0), _p(r_new), r_new.stride(0), rows, d, _dt3(x_out), _p(stats),
+                                                  _p(ws), ws.numel(), _stream()), "fino_magcache_calibrate")
+    return r_new
+
+
 def pab_broadcast(x, y, gate=None, sel=None, out=None):
     """out = T(fma(float(y), gate[sel], float(x))) (gate None: T(x + y)): the gated-residual epilogue of `gemm` applied to a
     cached y, bit for bit what the GEMM that produced y wrote (fino_pab_broadcast; `gated_residual` rounds y * gate first).

@@ -31,9 +31,15 @@ fresh state, and decide as a joint run would.  Replaying its host-known schedule
 TaylorSeer caching (`enable_cache(TaylorSeerCacheConfig(cache_interval=5, disable_cache_before_step=3, max_order=1))`, with
 `use_lite_mode=True` for the mode that predicts the model's output) follows the same rules: the eager loop, one GPU, fresh state
 per `denoise`, a batch sample by sample; its decisions depend on the step counter alone.
+
+MagCache (`enable_cache(MagCacheConfig(mag_ratios=curves, num_inference_steps=N))`; `calibrate=True` records the curves of a
+call into `transformer.magcache_calibration`) likewise: the eager loop, one GPU, fresh state per `denoise`, a batch sample by
+sample; its decisions depend on the step counter and the curve alone.  A call whose step count differs from the config's
+`num_inference_steps` warns: the curve is indexed by the step counter.
 """
 import html
 import re
+import warnings
 from types import SimpleNamespace
 
 import numpy as np
@@ -167,7 +173,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
             reset()
 
     def _step_cache_check(self, batch):
-        """the limits of the step caches (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache), checked before any work (and before
+        """the limits of the step caches (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache), checked before any work (and before
         any collective: a parallel plan and the cache are configured by the same script on every rank, so every rank raises)"""
         if not getattr(self.transformer, "is_cache_enabled", False):
             return False
@@ -498,7 +504,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         """reference :809-913.  Returns the final latents [B, C, F, h, w] fp32.  The loop state is one sample's (the app
         and the evaluation scripts run batch 1); a batch -- a list of prompts, num_videos_per_prompt > 1 -- runs sample by sample:
         the samples of the reference's batched loop never meet, every one sees the noise row `prepare_latents` drew for it.
-        With a step cache (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache) every call -- every sample -- starts from fresh
+        With a step cache (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache) every call -- every sample -- starts from fresh
         cache state."""
         cached = self._step_cache_check(latents.shape[0])
         win_eager = self._window_attention_check()
@@ -530,6 +536,13 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
             dts = self.scheduler.dts.to(dev)
         ts_dev = timesteps.to(dev).float()
         self._num_timesteps = len(timesteps)
+        if cached and getattr(self.transformer, "_mag_on", False):
+            planned = int(self.transformer._step_cache_config.num_inference_steps)
+            if planned != len(timesteps):       # once per call: the curve is indexed by the step counter
+                warnings.warn(f"MagCache: this call runs {len(timesteps)} steps, the config says num_inference_steps={planned}; "
+                              f"its curve (`mag_ratios`, resampled to {planned} entries) is misaligned with the loop and a "
+                              f"context starts over after {planned} forwards.  Build the config with the call's step count.",
+                              stacklevel=2)
         # FasterCache reads `current_timestep` on the host up to three times per step: a host copy of the schedule, taken once,
         # keeps those reads from waiting for the device
         ts_host = timesteps.cpu() if cached and getattr(self.transformer, "_faster_on", False) else None

@@ -1,16 +1,17 @@
 """Step caching of the Wan DiT: diffusers' `CacheMixin` (diffusers/models/cache_utils.py), which the reference's
 WanTransformer3DModel inherits (architecture/transformer_wan.py:28, :353) and whose state its FrameINO loop keys by
-`cache_context("cond")` / `("uncond")` (pipelines/pipeline_wan_i2v_motion_FrameINO.py:862, :873), with four of its configs:
+`cache_context("cond")` / `("uncond")` (pipelines/pipeline_wan_i2v_motion_FrameINO.py:862, :873), with five of its configs:
 `FirstBlockCacheConfig` (diffusers/hooks/first_block_cache.py), `PyramidAttentionBroadcastConfig`
-(diffusers/hooks/pyramid_attention_broadcast.py), `TaylorSeerCacheConfig` (diffusers/hooks/taylorseer_cache.py) and
-`FasterCacheConfig` (diffusers/hooks/faster_cache.py).  One at a
+(diffusers/hooks/pyramid_attention_broadcast.py), `TaylorSeerCacheConfig` (diffusers/hooks/taylorseer_cache.py),
+`FasterCacheConfig` (diffusers/hooks/faster_cache.py) and `MagCacheConfig` (diffusers/hooks/mag_cache.py).  One at a
 time: a second `enable_cache` raises, as in diffusers.
 
-Layout.  Every config has ONE policy class below (`_FirstBlockPolicy`, `_PabPolicy`, `_TaylorSeerPolicy`, `_FasterCachePolicy`) that
+Layout.  Every config has ONE policy class below (`_FirstBlockPolicy`, `_PabPolicy`, `_TaylorSeerPolicy`, `_FasterCachePolicy`,
+`_MagCachePolicy`) that
 states what is particular to it -- the attributes a duck-typed config must carry, its validation, its enable-time warnings and
 defaults, its label in messages, why a captured step cannot contain it, whether a batch may run under it, whether it takes over
 the attention branches -- and the entry points a forward asks (`segments` around the stack's first block, `lite` around the whole
-stack, `branches` for the attention branches).  `StepCacheMixin.enable_cache` is a lookup over the model's `_cache_policies`
+stack, `branches` for the attention branches, `magcache` around the block stack between the embedding and the output head).  `StepCacheMixin.enable_cache` is a lookup over the model's `_cache_policies`
 and stores the chosen policy next to the config; the `_pab_on` / `_taylor_on` / ... flags are read-only views of it.  The
 attention branches of a forward run under ONE plan, whichever cache made it: `_BroadcastPlan` (Pyramid Attention Broadcast) or
 `_TaylorPlan` (TaylorSeer's default mode, FasterCache's self-attention part), which say where a computing branch's output is kept,
@@ -101,12 +102,36 @@ counts too), t = float(current_timestep_callback()), read once per forward.
   Attention Broadcast's.  Temporal attention, module selection by identifier and `tensor_format` other than "BCFHW" match
   nothing on this model.
 
+MagCache.  This project's restatement with diffusers' names (`MagCacheConfig`; diffusers is not installed where this is built, so
+parity with it is unpinned by construction): the rule below is the contract, and the decision sits in one pure function,
+`magcache_decide`, with no tensor in it.  It skips the WHOLE block stack of a step: with x_in the stack's input (after the patch
+embedding) and r = T(x_out - x_in) of the last computing forward, a skipping forward's stack output is T(x_in + r).  Per context the
+state is (acc_ratio = 1.0, acc_steps = 0, acc_err = 0.0, has_residual); N = num_inference_steps, R = int(retention_ratio * N + 0.5),
+g = ratios[s] (1.0 beyond the curve's end), s = the 0-based count of forwards of the context:
+
+    calibrate: compute.    s < R: compute, the accumulators untouched.    Otherwise:
+    acc_ratio *= g;  acc_steps += 1;  acc_err += |1 - acc_ratio|
+    skip  iff  has_residual and acc_err <= threshold and acc_steps <= max_skip_steps,  else compute and reset the three
+
+A computing forward stores the residual (ops.step_cache_residual) and sets has_residual, a skipping one leaves it untouched.  When a
+context's counter reaches N it starts over -- counter 0, accumulators reset, residual dropped --, as after `_reset_stateful_cache()`.
+`mag_ratios` is the per-model curve, the mean over tokens of ||r_t|| / ||r_{t-1}||: a sequence or tensor, resampled to N by nearest
+index (`magcache_resample`), or a mapping from cache context to a curve (an unnamed context takes the "cond" entry).  In calibrate
+mode every forward computes and one launch (ops.magcache_calibrate) stores the residual and measures, over the rows of the context's
+segment, ratio = mean(||r_t|| / (||r_{t-1}|| + 1e-8)) and cos_dist = mean(1 - <r_t, r_{t-1}> / max(||r_t|| ||r_{t-1}||, 1e-8)) -- norms
+over the residuals as rounded to the model dtype, in fp32; the first forward records (1, 0) -- into row s of a [N, 2] fp64 device
+buffer, which is read ONCE, when the context starts over or the state is reset, and filed as `magcache_calibration[context]`
+(`save_mag_ratios` / `load_mag_ratios`).  cos_dist is report-only.  `cache_log` gets `(context, s, computed, acc_err, acc_steps)`, the
+accumulators after the decision; `(context, s, True, None, None)` in calibrate mode.  The model asks `_magcache_begin` for a forward's
+decisions and `_magcache_finish` after the stack.
+
 The CogVideoX DiT (`PyramidAttentionBroadcastMixin`) takes Pyramid Attention Broadcast alone, with the same rule and state: its one
 attention layer per block, the joint text + video attn1, is the "spatial" kind, and a call's whole batch is one segment under one
 context (diffusers' CogVideoX pipelines run the CFG batch under `cache_context("cond_uncond")`).
 """
 import contextlib
 import dataclasses
+import json
 import warnings
 from types import SimpleNamespace
 from typing import Any, Callable, Optional, Tuple
@@ -185,8 +210,26 @@ class FasterCacheConfig:
     current_timestep_callback: Optional[Callable[[], Any]] = None
 
 
+@dataclasses.dataclass
+class MagCacheConfig:
+    """diffusers.MagCacheConfig: after the first `int(retention_ratio * num_inference_steps + 0.5)` steps the whole block stack
+    of a step is skipped -- its output is its input plus the stack's residual of the last computing step -- while the error
+    accumulated from `mag_ratios` (the per-step mean ratio of the residual's per-token magnitude to the previous step's) stays
+    at or below `threshold` and at most `max_skip_steps` steps were skipped in a row.  `mag_ratios`: a sequence or tensor of
+    floats, resampled by nearest index to `num_inference_steps`, or (this project's extension) a mapping from cache context to
+    such a curve; `calibrate=True` runs every step and records the curve (`model.magcache_calibration`)."""
+    threshold: float = 0.06
+    max_skip_steps: int = 3
+    retention_ratio: float = 0.2
+    num_inference_steps: int = 28
+    mag_ratios: Any = None
+    calibrate: bool = False
+
+
 # the other configs diffusers' CacheMixin applies: recognised, not implemented here
-_OTHER_DIFFUSERS_CONFIGS = ("MagCacheConfig", "TeaCacheConfig")
+_OTHER_DIFFUSERS_CONFIGS = ("TeaCacheConfig",)
+_MAG_DEFAULTS = {f.name: f.default for f in dataclasses.fields(MagCacheConfig)}
+MAG_FORMAT = "frameino_amd.mag_ratios"
 _FASTER_DEFAULTS = {f.name: f.default for f in dataclasses.fields(FasterCacheConfig)}
 FASTER_CONTEXTS = ("cond", "uncond")    # the cache contexts of the denoising loop the unconditional-branch rule pairs
 TAYLOR_MAX_ORDER = 3                     # ops.TAYLOR_MAX_PLANES - 1
@@ -261,6 +304,85 @@ def fastercache_attention_decide(i, t, n_planes, ran_prev, cfg):
     return (not _strictly_inside(t, _fc(cfg, "spatial_attention_timestep_skip_range"))) or i % int(n) == 0
 
 
+def _mc(cfg, name):
+    """a field of a MagCache config, diffusers' default where a duck-typed object lacks it"""
+    return getattr(cfg, name, _MAG_DEFAULTS[name])
+
+
+MAG_FRESH = (1.0, 0, 0.0, False)        # (acc_ratio, acc_steps, acc_err, has_residual) of a context that starts over
+
+
+def magcache_retention(cfg):
+    """R: the first R forwards of a context always compute"""
+    return int(float(_mc(cfg, "retention_ratio")) * int(_mc(cfg, "num_inference_steps")) + 0.5)
+
+
+def magcache_decide(s, state, cfg, ratios):
+    """(compute, state') of forward `s` (0-based, per cache context) from state = (acc_ratio, acc_steps, acc_err, has_residual)
+    and the context's curve `ratios` (1.0 beyond its end).  A function of the step counter and the curve alone: no tensor in
+    it.  In calibrate mode and during the first R forwards: compute, the accumulators untouched.  Otherwise acc_ratio *= g,
+    acc_steps += 1, acc_err += |1 - acc_ratio|; skip iff there is a residual and acc_err <= threshold and
+    acc_steps <= max_skip_steps, else compute and reset the three.  A computing forward leaves has_residual set."""
+    acc_ratio, acc_steps, acc_err, has_residual = state
+    if bool(_mc(cfg, "calibrate")) or s < magcache_retention(cfg):
+        return True, (acc_ratio, acc_steps, acc_err, True)
+    g = float(ratios[s]) if ratios is not None and s < len(ratios) else 1.0
+    acc_ratio, acc_steps = acc_ratio * g, acc_steps + 1
+    acc_err = acc_err + abs(1.0 - acc_ratio)
+    if has_residual and acc_err <= float(_mc(cfg, "threshold")) and acc_steps <= int(_mc(cfg, "max_skip_steps")):
+        return False, (acc_ratio, acc_steps, acc_err, True)
+    return True, MAG_FRESH[:3] + (True,)
+
+
+def magcache_resample(ratios, n):
+    """`ratios` at `n` steps by nearest index: src[round(i * (len - 1) / (n - 1))], for n == 1 the last element; as it is when
+    the length is n already"""
+    src = [float(v) for v in (ratios.tolist() if isinstance(ratios, torch.Tensor) else ratios)]
+    if len(src) == n:
+        return src
+    if n == 1:
+        return [src[-1]]
+    return [src[int(round(i * (len(src) - 1) / (n - 1)))] for i in range(n)]
+
+
+def magcache_curve(cfg, context):
+    """the curve of cache context `context`: `mag_ratios` itself, or its entry of a per-context mapping -- for a context the
+    mapping does not name, its "cond" entry, ValueError if it has none --, resampled to `num_inference_steps`; None in
+    calibrate mode without a curve"""
+    ratios = _mc(cfg, "mag_ratios")
+    if ratios is None:
+        return None
+    if hasattr(ratios, "keys"):
+        if context in ratios:
+            ratios = ratios[context]
+        elif "cond" in ratios:
+            ratios = ratios["cond"]
+        else:
+            raise ValueError(f"MagCacheConfig.mag_ratios names the cache contexts {sorted(ratios.keys())}: no curve for context "
+                             f"{context!r} and no \"cond\" entry to use instead")
+    return magcache_resample(ratios, int(_mc(cfg, "num_inference_steps")))
+
+
+def save_mag_ratios(path, calibration):
+    """the per-context curves of a calibrating run (`model.magcache_calibration`: {context: {"mag_ratios": [...],
+    "cos_dist": [...]}}, or {context: [...]}) as plain JSON"""
+    ctxs = {}
+    for name, entry in calibration.items():
+        entry = entry if hasattr(entry, "keys") else {"mag_ratios": entry}
+        ctxs[str(name)] = {k: [float(v) for v in entry[k]] for k in ("mag_ratios", "cos_dist") if entry.get(k) is not None}
+    with open(path, "w") as f:
+        json.dump({"format": MAG_FORMAT, "version": 1, "contexts": ctxs}, f, indent=1)
+
+
+def load_mag_ratios(path):
+    """-> {context: [ratios]} as `save_mag_ratios` wrote it: what `MagCacheConfig(mag_ratios=...)` takes"""
+    with open(path) as f:
+        d = json.load(f)
+    if not isinstance(d, dict) or d.get("format") != MAG_FORMAT or not isinstance(d.get("contexts"), dict):
+        raise ValueError(f"{path}: not a file of save_mag_ratios")
+    return {name: [float(v) for v in entry["mag_ratios"]] for name, entry in d["contexts"].items()}
+
+
 def pab_decide(iteration, timestep, has_cache, block_skip_range, timestep_skip_range):
     """True: the attention module computes on this forward; False: it hands out its cached output."""
     lo, hi = timestep_skip_range
@@ -322,7 +444,7 @@ class _CachePolicy:
         """whether it runs with a user-installed attention processor: unless stated otherwise, likewise"""
         return not cls.hooks_attention(config)
 
-    # the three places of a forward a cache can sit in; None: not there
+    # the four places of a forward a cache can sit in; None: not there
     @staticmethod
     def segments(model, b, n, contexts):
         """around block 0 and the rest of the stack (`_step_cache_probe` / `_step_cache_finish`): the row segments"""
@@ -334,6 +456,10 @@ class _CachePolicy:
     @staticmethod
     def branches(model, b, n, d, dtype, device, contexts, faster):
         """in the attention branches of every block: a `_BranchPlan`"""
+
+    @staticmethod
+    def magcache(model, b, n, d, dtype, device, contexts):
+        """around the block stack, between the embedding and the output head, on the residual stream's rows: a plan"""
 
 
 class _FirstBlockPolicy(_CachePolicy):
@@ -485,7 +611,50 @@ class _FasterCachePolicy(_CachePolicy):
         return model._faster_attention_plan(faster, b, n, d, dtype, device)
 
 
-_POLICIES = {p.name: p for p in (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy)}
+class _MagCachePolicy(_CachePolicy):
+    name = "MagCacheConfig"
+    required = ("threshold", "max_skip_steps", "retention_ratio", "num_inference_steps", "mag_ratios", "calibrate")
+    label = "MagCache"
+    why_eager = "whether a step runs its block stack or re-uses the last residual changes from step to step on the host's schedule"
+
+    @staticmethod
+    def validate(config, model):
+        """ValueError for a field outside its range, a curve that is no curve, or neither a curve nor `calibrate`"""
+        def number(name, ok, need):
+            v = getattr(config, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(v):
+                raise ValueError(f"MagCacheConfig.{name} = {v!r}: need {need}")
+        number("threshold", lambda v: 0.0 <= v < float("inf"), "a finite number of at least 0")
+        number("retention_ratio", lambda v: 0.0 <= v <= 1.0, "a number between 0 and 1")
+        for name, lo in (("max_skip_steps", 0), ("num_inference_steps", 1)):
+            v = getattr(config, name)
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+                raise ValueError(f"MagCacheConfig.{name} = {v!r}: need an integer of at least {lo}")
+        ratios = config.mag_ratios
+        if ratios is None:
+            if not config.calibrate:
+                raise ValueError("MagCacheConfig.mag_ratios is None and calibrate is False: MagCache needs the model's curve.  "
+                                 "Run the clip once with MagCacheConfig(calibrate=True, num_inference_steps=N), take the curves "
+                                 "from `transformer.magcache_calibration` (save_mag_ratios / load_mag_ratios) and pass them as "
+                                 "`mag_ratios`.")
+            return
+        if hasattr(ratios, "keys") and not len(ratios):
+            raise ValueError("MagCacheConfig.mag_ratios is an empty mapping: need one curve per cache context")
+        for ctx, curve in (ratios.items() if hasattr(ratios, "keys") else ((None, ratios),)):
+            where = "MagCacheConfig.mag_ratios" + ("" if ctx is None else f"[{ctx!r}]")
+            try:
+                values = [float(v) for v in (curve.tolist() if isinstance(curve, torch.Tensor) else curve)]
+            except (TypeError, ValueError):
+                raise ValueError(f"{where} = {curve!r}: need a sequence or tensor of floats") from None
+            if not values or not all(0.0 < v < float("inf") for v in values):
+                raise ValueError(f"{where}: need at least one ratio, every one finite and above 0")
+
+    @staticmethod
+    def magcache(model, b, n, d, dtype, device, contexts):
+        return model._magcache_begin(b, n, d, dtype, device, contexts)
+
+
+_POLICIES = {p.name: p for p in (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy, _MagCachePolicy)}
 
 
 # ---------------------------------------------------------------------- one plan for the attention branches of a forward
@@ -576,8 +745,9 @@ class StepCacheMixin:
     """diffusers' CacheMixin surface (enable_cache / disable_cache / is_cache_enabled / _reset_stateful_cache) over the policies
     in `_cache_policies`.  `enable_cache` looks the config's policy up, lets it validate, asks the model what it cannot be
     combined with (`_cache_refusals`) and stores it next to the config; the forward asks the stored policy for its entry points
-    (`segments` / `lite` / `branches`), which lead to `_step_cache_segments` + `_step_cache_probe` + `_step_cache_finish`
-    (first-block caching), `_pab_begin`, `_taylor_begin` and `_faster_begin` + `_faster_attention_plan`.
+    (`segments` / `lite` / `branches` / `magcache`), which lead to `_step_cache_segments` + `_step_cache_probe` + `_step_cache_finish`
+    (first-block caching), `_pab_begin`, `_taylor_begin`, `_faster_begin` + `_faster_attention_plan` and `_magcache_begin` +
+    `_magcache_finish`.
 
     State per cache-context name (`_cache_state`: made at first use, and again when the rows, width, dtype or device change);
     `cache_log` holds one row per forward and context since the last reset; it survives the reset at the end of a pipeline call,
@@ -591,8 +761,11 @@ class StepCacheMixin:
     [max_order + 1, rows, D] buffer in the factor dtype, allocated by the first forward that computes; log rows
     `(context, step, computed)`.
     FasterCache: a counter, the self-attention planes, the context's last prediction (by reference) and, for "uncond", the
-    delta and its weights; log rows `(context, i, t, stack_ran, attention_computed)`."""
-    _cache_policies = (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy)
+    delta and its weights; log rows `(context, i, t, stack_ran, attention_computed)`.
+    MagCache: a counter, the three accumulators, the stack's residual [rows, D] and, in calibrate mode, the [N, 2] fp64 rows;
+    log rows `(context, s, computed, acc_err, acc_steps)`."""
+    _cache_policies = (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy, _MagCachePolicy)
+    magcache_calibration = None     # {context: {"mag_ratios": [...], "cos_dist": [...]}} once a calibrating context finished
     _step_cache_config = None
     _step_cache_policy = None
     _step_cache_states = None
@@ -639,7 +812,9 @@ class StepCacheMixin:
 
     def _reset_stateful_cache(self, recurse=True):
         """drop every context's state (diffusers' maybe_free_model_hooks calls this at the end of a pipeline call); the next
-        forward starts a new `cache_log`"""
+        forward starts a new `cache_log`.  A calibrating MagCache context files what it has recorded first."""
+        for name, st in (self._step_cache_states or {}).items():
+            self._magcache_file(name, st)
         self._step_cache_states = {}
         self._step_cache_log_fresh = True
 
@@ -649,6 +824,7 @@ class StepCacheMixin:
     _taylor_lite = property(lambda self: self._taylor_on and not _TaylorSeerPolicy.hooks_attention(self._step_cache_config))
     _faster_on = property(lambda self: self._step_cache_policy is _FasterCachePolicy)
     _faster_attention = property(lambda self: self._faster_on and _FasterCachePolicy.hooks_attention(self._step_cache_config))
+    _mag_on = property(lambda self: self._step_cache_policy is _MagCachePolicy)
 
     # ---------------------------------------------------------------- used by the forward
     def _context_segments(self, b, n, contexts):
@@ -903,6 +1079,79 @@ class StepCacheMixin:
         u = self._step_cache_states["uncond"]
         u.a_low, u.a_high = fastercache_weights(plan.t, u.a_low, u.a_high, plan.cfg, self)
         return self.ops.fastercache_apply(cond_out, u.d_low, u.d_high, u.a_low, u.a_high, out=out)
+
+
+    # ---------------------------------------------------------------- MagCache
+    def _magcache_begin(self, b, n, d, dtype, device, contexts=None):
+        """The decisions of one forward under MagCache, taken before anything is launched: None when it is off, else a plan
+        with `.calibrate` and `.segs` = one entry per row segment with `.name`, `.r0`, `.r1`, `.state`, `.s` (this forward's
+        number), `.compute` and `.had_residual` (whether an earlier forward of the context left a residual).  Reads the step
+        counter and the context's curve alone.  Advances every context's counter and accumulators and appends
+        `(context, s, computed, acc_err, acc_steps)` -- the accumulators after the decision; `(context, s, True, None, None)`
+        in calibrate mode -- to `cache_log`.  A context whose rows, width, dtype or device changed starts over, and so does
+        one whose counter has reached `num_inference_steps`."""
+        if not self._mag_on:
+            return None
+        cfg = self._step_cache_config
+        segs = self._context_segments(b, n, contexts)
+        curves = [magcache_curve(cfg, name) for name, _, _ in segs]        # (an unnamed context raises before anything counts)
+        steps, calibrate = int(_mc(cfg, "num_inference_steps")), bool(_mc(cfg, "calibrate"))
+        plan = SimpleNamespace(segs=[], calibrate=calibrate, steps=steps, d=d, dtype=dtype, device=device)
+        for (name, r0, r1), ratios in zip(segs, curves):
+            fresh = lambda: dict(acc=MAG_FRESH, residual=None, stats=None)          # noqa: E731
+            st = self._cache_state(name, (r1 - r0, d, dtype, str(device)), fresh)
+            if st.steps >= steps:
+                self._magcache_start_over(name)
+                st = self._cache_state(name, (r1 - r0, d, dtype, str(device)), fresh)
+            s, had = st.steps, st.acc[3]
+            compute, st.acc = magcache_decide(s, st.acc, cfg, ratios)
+            self.cache_log.append((name, s, True, None, None) if calibrate else (name, s, compute, st.acc[2], st.acc[1]))
+            st.steps += 1
+            plan.segs.append(SimpleNamespace(name=name, r0=r0, r1=r1, state=st, s=s, compute=compute, had_residual=had))
+        return plan
+
+    def _magcache_finish(self, plan, x, x_in):
+        """after the last block (or right after the embedding when every segment skips), x_in = the stack's input [rows, D]:
+        a computing segment stores the stack's residual T(x - x_in) -- in calibrate mode with the one launch that also measures
+        it against the previous one (ops.magcache_calibrate, into row s of the context's [N, 2] fp64 device buffer; nothing is
+        read here) --, a skipping one takes T(x_in + r) as the stack's output, its residual untouched.  A context whose counter
+        has reached `num_inference_steps` starts over."""
+        o = self.ops
+        for seg in plan.segs:
+            st, r0, r1 = seg.state, seg.r0, seg.r1
+            if seg.compute:
+                if st.residual is None:
+                    st.residual = torch.empty((r1 - r0, plan.d), dtype=plan.dtype, device=plan.device)
+                if plan.calibrate and st.stats is None:          # row s = (ratio, cos_dist); a context's first step: (1, 0)
+                    st.stats = torch.zeros((plan.steps, 2), dtype=torch.float64, device=plan.device)
+                    st.stats[:, 0] = 1.0
+                if plan.calibrate and seg.had_residual:
+                    o.magcache_calibrate(x[r0:r1], x_in[r0:r1], st.residual, st.residual, st.stats[seg.s])
+                else:
+                    o.step_cache_residual(x[r0:r1], x_in[r0:r1], out=st.residual, subtract=True)
+            else:
+                if st.residual is None:
+                    raise KeyError(f"MagCache: no residual under context {seg.name!r}")
+                o.step_cache_residual(st.residual, x_in[r0:r1], out=x[r0:r1], subtract=False)
+            if st.steps >= plan.steps and self._step_cache_states.get(seg.name) is st:
+                self._magcache_start_over(seg.name)
+
+    def _magcache_start_over(self, name):
+        """context `name` has run its `num_inference_steps` forwards: counter 0, accumulators reset, residual dropped; a
+        calibrating context files its curve first"""
+        st = self._step_cache_states.pop(name, None)
+        if st is not None:
+            self._magcache_file(name, st)
+
+    def _magcache_file(self, name, st):
+        """`magcache_calibration[name]` from the rows a calibrating context has recorded: the ONE host read of a calibrating
+        call (per context), when the context starts over or the state is reset"""
+        stats = getattr(st, "stats", None)
+        if stats is None or st.steps < 1:
+            return
+        rows = stats[:st.steps].tolist()
+        self.magcache_calibration = dict(self.magcache_calibration or {})
+        self.magcache_calibration[name] = {"mag_ratios": [r[0] for r in rows], "cos_dist": [r[1] for r in rows]}
 
 
 class PyramidAttentionBroadcastMixin(StepCacheMixin):

@@ -18,7 +18,9 @@ first-block residual barely changed; `enable_cache(PyramidAttentionBroadcastConf
 cross-attention branch outputs of the previous step on a schedule of the step counter and the timestep
 (frameino_amd/step_cache.py); `TaylorSeerCacheConfig` extrapolates the attention branches (or the output) along the step axis;
 `FasterCacheConfig` skips the unconditional CFG branch on a schedule and rebuilds its prediction from the conditional one, and
-extrapolates the self-attention branches.  One at a time, all off by default.
+extrapolates the self-attention branches; `MagCacheConfig` skips the whole block stack of a step and adds the stack's residual
+of the last computing step, on a schedule of the step counter and a per-model curve (`calibrate=True` measures it).  One at a
+time, all off by default.
 """
 import contextlib
 import math
@@ -502,7 +504,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         self-attention as keys and values: their q projection's use, attention queries, out-projection, text branch, FFN and
         output head are skipped, and their part of the returned tensor is ZERO.  Every kept row is computed exactly as without it.
         A bare `transformer(...)` call (None) keeps the full output.
-        `_cache_contexts` (private; a step cache enabled -- first-block caching, Pyramid Attention Broadcast or TaylorSeer): one
+        `_cache_contexts` (private; a step cache enabled -- first-block caching, Pyramid Attention Broadcast, TaylorSeer, MagCache): one
         cache-context name per batch element, each element then decided on its own as if called alone under that context -- the
         pipeline's CFG-batched call passes ("cond", "uncond").  Without it a batch-B call under one `cache_context` makes one
         joint decision, as diffusers does (first-block caching: over the means of all its rows; Pyramid Attention Broadcast:
@@ -596,7 +598,10 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         yield
 
         last = len(self.blocks) - 1
-        for li, (blk, e) in enumerate(zip(self.blocks, c.pk.layers)):
+        # MagCache: when every segment re-uses its residual the block stack does not run; when some do, it runs on all rows
+        # (as under first-block caching) and the skipping segments' rows are overwritten afterwards
+        stack = c.mag is None or any(seg.compute for seg in c.mag.segs)
+        for li, (blk, e) in enumerate(zip(self.blocks, c.pk.layers) if stack else ()):
             m = c.mod[:, li]                                                      # [R, 6, D] view, row stride = layers*6*D
             if c.live is not None and li == last:
                 c.rows, c.segs = c.live, c.live_segs                              # dead rows: keys and values only
@@ -618,6 +623,12 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
             # the dead rows at block N-2's output, so a tail residual is meaningful on the live rows only -- the rows the caller
             # reads; the head below runs on those rows alone whether or not the blocks ran.
             self._step_cache_finish(c.fbc, computes, c.x, c.h1c)
+            if c.live is not None:
+                c.segs = c.live_segs
+        if c.mag is not None:
+            # the stack's residual T(x - h0) of the computing segments, T(h0 + r) for the skipping ones; `live_rows` as under
+            # first-block caching: the residual is meaningful on the live rows, which are the rows the head runs on
+            self._magcache_finish(c.mag, c.x, c.h0)
             if c.live is not None:
                 c.segs = c.live_segs
         return self._output_head(c)
@@ -680,12 +691,14 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
             if sh.gemm_tile_m:
                 tk = {"tile_m": sh.tile_m_for(n)}
         # the step cache's places in this forward, each None when it does not sit there: `fbc` around block 0 (first-block
-        # caching), `lite` around the whole stack (TaylorSeer's lite mode), `branches` in every block's attention branches.
+        # caching), `lite` around the whole stack (TaylorSeer's lite mode), `branches` in every block's attention branches,
+        # `mag` around the block stack between the embedding and the output head (MagCache).
         # Their decisions are taken here, before any launch (a timestep callback is read once)
         policy = self._step_cache_policy
-        fbc = lite = branches = None
+        fbc = lite = branches = mag = None
         if policy is not None:
             fbc = policy.segments(self, b, n, cache_contexts)
+            mag = policy.magcache(self, b, n, d, dt, dev, cache_contexts)        # MagCache: around the whole block stack
             lite = policy.lite(self, b, n, cfg.out_channels * math.prod(cfg.patch_size), dt, dev, cache_contexts)
             if lite is not None and not any(seg.compute["self"] for seg in lite.segs):
                 # every segment predicts: no embedding, no block, no head -- the call needs its geometry and the output rows
@@ -727,7 +740,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         live = None
         # (not under Pyramid Attention Broadcast: a cached branch output covers every row, so that any later step may use it)
         if (live_rows is not None and self.skip_dead_rows and default_procs and sh is None and len(self.blocks) > 1
-                and not self._fp8 and not fp8 and branches is None and lite is None):
+                and not self._fp8 and not fp8 and branches is None and lite is None
+                and not (mag is not None and mag.calibrate)):      # (a calibrating MagCache run measures every row's full stack)
             l0, l1 = int(live_rows[0]), int(live_rows[1])
             if 0 <= l0 < l1 <= n and (l1 - l0) < n:
                 live = (l0, l1)
@@ -739,7 +753,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
                      text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
                      afold={"scale": o.SCALE_FOLDED} if fold else {}, fp8=fp8, default_procs=default_procs,
                      shared=shared, fbc=fbc, branches=branches, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
-                     live=live, win=win, sp=sp, lite=lite, out_buf=out_buf,
+                     live=live, win=win, sp=sp, lite=lite, mag=mag, out_buf=out_buf,
                      live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
                      rows=(0, n),            # the rows of every batch element that run as queries / per-token rows ...
                      segs=[(0, nr)])         # ... and the global row ranges the per-token operations of a block run on
@@ -755,11 +769,13 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         else:
             a_rows = torch.cat([o.patchify(hidden_states[i], patch) for i in range(b)])
         o.gemm(a_rows, c.pk.w_patch, self.patch_embedding.bias, out=x[:n] if c.shared else x, **c.tk)
-        if c.fbc is not None:
-            ws = c.ws                        # h0, and a buffer for the probe's copy of h1
+        if c.fbc is not None or c.mag is not None:
+            ws = c.ws                        # h0, and a buffer for the probe's copy of h1 (MagCache keeps h0 alone)
             if getattr(ws, "fbc_h0", None) is None:
-                ws.fbc_h0, ws.fbc_h1 = torch.empty_like(ws.x), torch.empty_like(ws.x)
-            c.h0, c.h1c = ws.fbc_h0[:c.nr], ws.fbc_h1[:c.nr]
+                ws.fbc_h0 = torch.empty_like(ws.x)
+            if c.fbc is not None and getattr(ws, "fbc_h1", None) is None:
+                ws.fbc_h1 = torch.empty_like(ws.x)
+            c.h0, c.h1c = ws.fbc_h0[:c.nr], (ws.fbc_h1[:c.nr] if c.fbc is not None else None)
             if c.shared:                     # (the embedding of the shared latent sits in the first n rows only)
                 for bi in range(b):
                     c.h0[bi * n:(bi + 1) * n].copy_(x[:n])
@@ -1087,11 +1103,12 @@ class _Call:
     batch through) are the only fields written after `_bind`.  `branches`: the plan of the cache that has taken over the
     attention branches (`_BranchPlan`: Pyramid Attention Broadcast, TaylorSeer's default mode, FasterCache's self-attention
     part), else None; `lite`: the plan of TaylorSeer's lite mode -- when every segment of it predicts, `_bind` returns a call
-    with the geometry, the workspace and the plan alone."""
+    with the geometry, the workspace and the plan alone; `mag`: MagCache's plan for the block stack as a whole (`h0` is then
+    the stack's input, kept by the embedding stage)."""
     __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
                  "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
                  "afold", "fp8", "default_procs", "shared", "fbc", "branches", "keep", "h0", "h1c", "attention_kwargs", "live",
-                 "live_segs", "rows", "segs", "win", "sp", "lite", "out_buf", "elements")
+                 "live_segs", "rows", "segs", "win", "sp", "lite", "mag", "out_buf", "elements")
 
     def __init__(self, **fields):
         self.elements = None

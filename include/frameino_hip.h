@@ -726,6 +726,24 @@ int fino_step_cache_probe(const FinoStepCacheSegment* segs, int nseg, int64_t di
                           void* stream);
 int fino_step_cache_residual(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int64_t rows,
                              int64_t dim, int subtract, int dtype, void* stream);
+/* MagCache (diffusers' hooks/mag_cache.py; frameino_amd/step_cache.py), the calibration pass: one pass over HBM that stores the
+ * residual of the whole block stack and measures it against the previous step's.  Row-strided [rows, dim] operands of dtype T:
+ *   r_new = T(x_out - x_in)                       the bits fino_step_cache_residual(subtract) writes
+ *   per row, from the ROUNDED values, in fp32:    nn = sum r_new^2, pp = sum r_prev^2, np = sum r_new * r_prev
+ *     ratio    = sqrt(nn) / (sqrt(pp) + 1e-8)
+ *     cos_dist = 1 - np / max(sqrt(nn) * sqrt(pp), 1e-8)
+ *   stats[0] = mean over rows of ratio,  stats[1] = mean over rows of cos_dist          fp64 DEVICE doubles
+ * One wave sweeps a row with 16-byte loads (lanes sum in sequence, then an xor butterfly); wave g of the launch takes the rows
+ * g, g + W, ... and adds them in that order in fp64 into its partial in `workspace` (fino_magcache_workspace_bytes(rows)
+ * device bytes, 16-byte aligned); a second launch adds the partials in a fixed order and divides by rows.  W depends on rows
+ * alone and there are no atomics: the same inputs give the same bits on every run.  No contraction.  r_new may BE r_prev (same
+ * pointer, same stride: a thread reads its r_prev vectors before it writes); any other overlap of r_new with an input is
+ * undefined.  dtype FINO_BF16 | FINO_F16 | FINO_F32; dim a multiple of 8 (16-bit) or 4 (fp32); every row stride >= dim with
+ * 16-byte aligned rows; rows in 1 .. 2^31 - 1; stats 16-byte aligned.  Every argument error -> FINO_ERR_ARG before any launch. */
+int64_t fino_magcache_workspace_bytes(int64_t rows);
+int fino_magcache_calibrate(const void* x_out, int64_t ld_out, const void* x_in, int64_t ld_in, const void* r_prev,
+                            int64_t ld_prev, void* r_new, int64_t ld_new, int64_t rows, int64_t dim, int dtype, double* stats,
+                            void* workspace, int64_t workspace_bytes, void* stream);
 /* Pyramid Attention Broadcast (diffusers' hooks/pyramid_attention_broadcast.py; frameino_amd/step_cache.py): a step that
  * re-uses an attention branch adds the cached y = T(acc + bias) of its out-projection (kept by fino_gemm_keep) to the residual
  * stream without running the branch:
