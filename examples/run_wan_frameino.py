@@ -95,6 +95,16 @@ def main():
                     help="run the clip with MagCache in calibrate mode (every step computes; one extra pass over the residual per "
                          "step and context) and write the measured curves, per cache context, to OUT.json.  Curves depend on "
                          "the weights, the step count and the scheduler.  Not together with the other cache flags")
+    ap.add_argument("--ras", type=float, default=None, metavar="RATIO",
+                    help="region-adaptive sampling (approximate; eager loop; quality on real checkpoints unmeasured): on most steps "
+                         "only the fraction RATIO of the tokens whose prediction is moving most, e.g. 0.5, runs through the DiT; "
+                         "the others keep their last prediction and serve the self-attention from per-layer K / V planes (two "
+                         "planes per CFG branch and layer: 9.1 GB at 704x1280x81).  Not together with the other cache flags, "
+                         "--window-frames, --sparse-attention or --fp8-attention")
+    ap.add_argument("--ras-interval", type=int, default=5, metavar="N", help="with --ras: every N-th step runs every token")
+    ap.add_argument("--ras-warmup", type=int, default=4, metavar="W", help="with --ras: the first W steps run every token")
+    ap.add_argument("--ras-trajectory-mask", action="store_true",
+                    help="with --ras: the tokens under the painted trajectories are active on every step")
     ap.add_argument("--window-frames", type=int, default=None, metavar="N",
                     help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
                          "every query attends its own frame +- N neighbours plus the first frame and the ID frame, e.g. 2.  Not "
@@ -148,6 +158,12 @@ def main():
             ap.error("--magcache FILE applies curves, --magcache-calibrate OUT.json measures them: one at a time")
         if any(v is not None for v in (a.first_block_cache, a.pab, a.taylorseer, a.fastercache)):
             ap.error("--magcache / --magcache-calibrate: not together with --first-block-cache, --pab, --taylorseer or --fastercache")
+
+    if a.ras is None and (a.ras_trajectory_mask or a.ras_interval != 5 or a.ras_warmup != 4):
+        ap.error("--ras-interval / --ras-warmup / --ras-trajectory-mask need --ras RATIO")
+    if a.ras is not None and any(v is not None for v in (a.first_block_cache, a.pab, a.taylorseer, a.fastercache, a.magcache,
+                                                         a.magcache_calibrate)):
+        ap.error("--ras: not together with --first-block-cache, --pab, --taylorseer, --fastercache or --magcache")
 
     from frameino_amd import _lib
     from frameino_amd.autoencoder_kl_wan import AutoencoderKLWan
@@ -257,6 +273,18 @@ def main():
     t0 = time.perf_counter()
     canvas, tracks, id_tensor, pads = synthetic_conditions(a.frames, a.height, a.width, dev)
     traj = prepare_traj_tensor(tracks, a.height, a.width, 6, a.width, a.height, device=dev)        # [F, 3, H, W]
+    if a.ras is not None:
+        from frameino_amd.conditions import trajectory_token_mask
+        from frameino_amd.step_cache import RegionAdaptiveSamplingConfig
+        pinned = None
+        if a.ras_trajectory_mask:                  # a token = patch x the VAE's spatial stride pixels; the ID frame comes last
+            px = vae.config.scale_factor_spatial * transformer.config.patch_size[1]
+            pinned = trajectory_token_mask(traj, a.height // px, a.width // px, vae.config.scale_factor_temporal,
+                                           extra_frames=0 if id_tensor is None else 1)
+            print(f"ras: {int(pinned.sum())} of {pinned.numel()} tokens lie under the trajectories")
+        transformer.enable_cache(RegionAdaptiveSamplingConfig(sample_ratio=a.ras, full_step_interval=a.ras_interval,
+                                                              warmup_steps=a.ras_warmup, num_inference_steps=a.steps,
+                                                              always_active=pinned))
     kw = {}
     if text_encoder is None:                                   # no text encoder offline: synthetic prompt embeddings
         g = torch.Generator().manual_seed(0)
@@ -310,6 +338,9 @@ def main():
     elif a.magcache is not None:
         log = transformer.cache_log
         print(f"magcache: {sum(not e[2] for e in log)} of {len(log)} forwards re-used the stack's residual")
+    if a.ras is not None:
+        log = [e for e in transformer.cache_log if e[0] == "cond"]
+        print(f"ras: {sum(not e[2] for e in log)} of {len(log)} steps ran {min(e[3] for e in log)} of {max(e[3] for e in log)} tokens")
     from frameino_amd.conditions import crop_unpadded
     region = crop_unpadded(frames, *pads)                     # app.py:741-748: the original (un-extended) region
     print(f"cropped region {tuple(region.shape)} uint8")

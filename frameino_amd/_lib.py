@@ -151,6 +151,12 @@ SIGNATURES = {
     "fino_fastercache_supported": [c_i64, c_i64, c_i64],
     "fino_fastercache_delta": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p],
     "fino_fastercache_apply": [c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_i64, c_int, c_void_p],
+    "fino_token_score": [c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p],
+    "fino_token_select": [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p],
+    "fino_gather_rows": [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p],
+    "fino_scatter_rows": [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p],
+    "fino_qkv_rmsnorm_rope_rows": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_float, c_void_p, c_float, c_void_p, c_void_p, c_int,
+                                   c_float, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p],
 }
 
 

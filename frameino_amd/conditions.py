@@ -166,3 +166,25 @@ def crop_unpadded(frames, top_left_height, top_left_width, bottom_right_height, 
     f = torch.as_tensor(frames)
     y1, x1 = f.shape[1] - bottom_right_height, f.shape[2] - bottom_right_width
     return (f[:, top_left_height:y1, top_left_width:x1] * 255).to(torch.uint8)     # np.uint8(x * 255): truncation
+
+
+def trajectory_token_mask(traj_tensor, tokens_h, tokens_w, temporal_stride=4, extra_frames=0, tolerance=1.0 / 255):
+    """Which DiT tokens lie under the user's trajectories (host side, a handful of torch calls): bool
+    [(latent_frames + extra_frames) * tokens_h * tokens_w] on the CPU, in the DiT's token order (frame, row, column), for
+    `RegionAdaptiveSamplingConfig(always_active=...)`.  `traj_tensor` [F, 3, H, W] in [-1, 1] as `prepare_traj_tensor` returns
+    it (white background): a pixel is painted when any channel is more than `tolerance` below white.  A token is set if any
+    painted pixel falls in its H / tokens_h x W / tokens_w patch on any pixel frame of its latent frame -- latent frame 0 is
+    pixel frame 0, latent frame f > 0 the pixel frames temporal_stride * (f - 1) + 1 .. temporal_stride * f (the causal VAE's
+    grouping).  `extra_frames`: trailing latent frames that carry no trajectory (the ID frame), all False."""
+    t = torch.as_tensor(traj_tensor)
+    if t.dim() != 4 or t.shape[2] % tokens_h or t.shape[3] % tokens_w:
+        raise ValueError(f"trajectory_token_mask: traj_tensor {tuple(t.shape)} does not split into {tokens_h} x {tokens_w} patches")
+    frames = t.shape[0]
+    painted = (t < 1.0 - tolerance).any(dim=1).float()                                            # [F, H, W]
+    per_token = torch.nn.functional.adaptive_max_pool2d(painted[None], (tokens_h, tokens_w))[0] > 0      # [F, th, tw]
+    latent_frames = (frames - 1) // temporal_stride + 1
+    mask = torch.zeros((latent_frames + extra_frames, tokens_h, tokens_w), dtype=torch.bool)
+    mask[0] = per_token[0].cpu()
+    for f in range(1, latent_frames):
+        mask[f] = per_token[temporal_stride * (f - 1) + 1:temporal_stride * f + 1].any(dim=0).cpu()
+    return mask.flatten()

@@ -179,7 +179,8 @@ __device__ __forceinline__ void rmsnorm_rope_row(uint16_t* __restrict__ xrow, in
                                                  const float* __restrict__ cos_t, const float* __restrict__ sin_t,
                                                  int head_dim, float out_scale, uint16_t* __restrict__ out,
                                                  const int64_t* __restrict__ head_off,
-                                                 const int64_t* __restrict__ head_ld, int lane) {
+                                                 const int64_t* __restrict__ head_ld, int lane,
+                                                 uint16_t* __restrict__ copy_to = nullptr) {
     float v[NP][8];
     load_row<T, NP>(xrow, dim, lane, v);
     float rs = 1.f;
@@ -227,7 +228,9 @@ __device__ __forceinline__ void rmsnorm_rope_row(uint16_t* __restrict__ xrow, in
             const int hd = c / head_dim;
             EW_STORE(out + head_off[hd] + row * head_ld[hd] + (c - hd * head_dim), pack8<T>(o));
         } else {
-            EW_STORE(xrow + c, pack8<T>(o));
+            const uint4 packed = pack8<T>(o);
+            EW_STORE(xrow + c, packed);
+            if (copy_to) EW_STORE(copy_to + c, packed);      // fino_qkv_rmsnorm_rope_rows: the same bits into a K plane's row
         }
     }
 }
@@ -256,6 +259,34 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void rmsnorm_rope_kernel(uint1
     rmsnorm_rope_row<T, NP>(x + row * ldx + (int64_t)s * dim, row, dim, pp.w[s], pp.eps[s], rope ? cos_t : nullptr,
                             rope ? sin_t : nullptr, head_dim, pp.out_scale[s], out,
                             head_off ? head_off + (int64_t)s * (dim / head_dim) : nullptr, head_ld, lane);
+}
+
+// fino_qkv_rmsnorm_rope_rows (region-adaptive sampling): rmsnorm_rope_kernel's q and k segments on a compact [rows, 3 dim]
+// projection, in place, and in the same launch row r's k (the bits just written) and v copied to row idx[r] of the K / V planes
+// (idx null: row r).  cos / sin rows belong to the compact rows.  idx[r] is clamped into [0, n).
+template <typename T, int NP>
+__global__ __launch_bounds__(kWavesPerBlock * 64) void qkv_rmsnorm_rope_rows_kernel(
+    uint16_t* __restrict__ x, int64_t rows, int dim, int64_t ldx, const RmsRopeParts pp, const float* __restrict__ cos_t,
+    const float* __restrict__ sin_t, int head_dim, const int32_t* __restrict__ idx, int64_t n, uint16_t* __restrict__ kcache,
+    uint16_t* __restrict__ vcache, int64_t ldc) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int s = blockIdx.y;
+    int64_t t = idx ? (int64_t)idx[row] : row;
+    t = t < 0 ? 0 : (t >= n ? n - 1 : t);
+    if (s == 2) {
+        const uint16_t* __restrict__ v = x + row * ldx + 2 * (int64_t)dim;
+        uint16_t* __restrict__ d = vcache + t * ldc;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int c = (i * 64 + lane) * 8;
+            if (c < dim) EW_STORE(d + c, *reinterpret_cast<const uint4*>(v + c));
+        }
+        return;
+    }
+    rmsnorm_rope_row<T, NP>(x + row * ldx + (int64_t)s * dim, row, dim, pp.w[s], pp.eps[s], cos_t, sin_t, head_dim,
+                            pp.out_scale[s], nullptr, nullptr, nullptr, lane, s == 1 ? kcache + t * ldc : nullptr);
 }
 
 // The statistic of rmsnorm_rope_row alone: rrms[row] = 1 / sqrt(mean(x^2) + eps), the same loads, the same order of summation,
@@ -797,6 +828,43 @@ extern "C" int fino_qkv_rmsnorm_rope(void* qkv, int64_t rows, int dim, int64_t l
     // in place: q and k only (v is left alone); scattered: v travels too, as a copy
     return rmsnorm_rope_impl(qkv, rows, dim, ldx, out ? 3 : 2, pp, cos_t, sin_t, head_dim, out, head_off, head_ld, dtype,
                              stream);
+}
+
+extern "C" int fino_qkv_rmsnorm_rope_rows(void* qkv, int64_t rows, int dim, int64_t ldx, const void* q_weight, float q_eps,
+                                          const void* k_weight, float k_eps, const float* cos_t, const float* sin_t,
+                                          int head_dim, float q_out_scale, const int32_t* idx, int64_t n, void* kcache,
+                                          void* vcache, int64_t ld_cache, int dtype, void* stream) {
+    const char* who = "fino_qkv_rmsnorm_rope_rows";
+    CHECK_ROWS_DIM("fino_qkv_rmsnorm_rope_rows");
+    FINO_CHECK(qkv && q_weight && k_weight && cos_t && sin_t && kcache && vcache, FINO_ERR_ARG, "%s: null pointer", who);
+    FINO_CHECK(q_out_scale > 0.f, FINO_ERR_ARG, "%s: q_out_scale must be > 0", who);
+    FINO_CHECK(head_dim > 0 && head_dim % 8 == 0 && dim % head_dim == 0 && dim % 8 == 0, FINO_ERR_ARG,
+               "%s: head_dim=%d must divide dim=%d and be a multiple of 8", who, head_dim, dim);
+    FINO_CHECK(n >= 1 && n < (1LL << 31) && (idx || rows <= n), FINO_ERR_ARG, "%s: n=%lld planes rows for %lld rows", who,
+               (long long)n, (long long)rows);
+    FINO_CHECK(ldx >= 3 * (int64_t)dim && ld_cache >= dim, FINO_ERR_ARG, "%s: a row stride is below the row", who);
+    FINO_CHECK(ldx % 8 == 0 && ld_cache % 8 == 0 && fino_aligned16(qkv) && fino_aligned16(cos_t) && fino_aligned16(sin_t) &&
+                   fino_aligned16(kcache) && fino_aligned16(vcache) && fino_aligned16(q_weight) && fino_aligned16(k_weight),
+               FINO_ERR_ARG, "%s: 16-byte alignment required", who);
+    RmsRopeParts pp = {};
+    pp.w[0] = (const uint16_t*)q_weight; pp.eps[0] = q_eps; pp.out_scale[0] = q_out_scale; pp.rope[0] = 1;
+    pp.w[1] = (const uint16_t*)k_weight; pp.eps[1] = k_eps; pp.out_scale[1] = 1.0f; pp.rope[1] = 1;
+    const dim3 grid((unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock), 3u), block(kWavesPerBlock * 64);
+    hipStream_t st = (hipStream_t)stream;
+    const bool ok = dispatch_np<kMaxPasses>(dim, [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        if (dtype == FINO_BF16)
+            qkv_rmsnorm_rope_rows_kernel<BF16, NP><<<grid, block, 0, st>>>((uint16_t*)qkv, rows, dim, ldx, pp, cos_t, sin_t,
+                                                                           head_dim, idx, n, (uint16_t*)kcache,
+                                                                           (uint16_t*)vcache, ld_cache);
+        else
+            qkv_rmsnorm_rope_rows_kernel<F16, NP><<<grid, block, 0, st>>>((uint16_t*)qkv, rows, dim, ldx, pp, cos_t, sin_t,
+                                                                          head_dim, idx, n, (uint16_t*)kcache,
+                                                                          (uint16_t*)vcache, ld_cache);
+    });
+    FINO_CHECK(ok, FINO_ERR_UNSUPPORTED, "%s: dim %d > %d unsupported", who, dim, kMaxPasses * 512);
+    FINO_LAUNCH_CHECK();
+    return FINO_OK;
 }
 
 extern "C" int fino_rmsnorm_rope(void* x, int64_t rows, int dim, int64_t ldx, const void* weight, float eps,

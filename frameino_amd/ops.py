@@ -1559,3 +1559,110 @@ def fastercache_apply(cond, d_low, d_high, a_low, a_high, out=None):
                                                  _dt(cond), _stream()), "fino_fastercache_apply")
     _taylor_bytes("fastercache_apply", ev, n * (2 * cond.element_size() + 8))
     return out
+
+
+# ---------------------------------------------------------------------- region-adaptive sampling (fino_token_select.hip)
+TOKEN_SELECT_MAX = 65536                   # FINO_TOKEN_SELECT_MAX
+
+
+def _index_list(idx, what):
+    if not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
+        raise ValueError(f"{what}: the list must be a contiguous int32 [k] device tensor, got {tuple(idx.shape)} {idx.dtype} on "
+                         f"{idx.device}")
+    return idx
+
+
+def token_score(po, batch=1, counters=None, starvation_scale=0.0, eligible=None, out=None):
+    """The score of every token row of a kept prediction (fino_token_score): po row-strided [batch * rows, cols] bf16 / fp16
+    (the batch elements stacked) -> fp32 [rows], the population standard deviation of the row's `cols` values averaged over
+    the batch elements, times exp(starvation_scale * counters[row]) (int32 [rows]; None: no factor).  `eligible` (uint8 [rows]):
+    0 scores -inf, 2 scores +inf.  Deterministic bit for bit."""
+    _rows_of(po, po.dtype, "token_score po")
+    batch = int(batch)
+    if batch < 1 or po.shape[0] % batch or po.shape[0] < batch:
+        raise ValueError(f"token_score: {po.shape[0]} rows for a batch of {batch}")
+    rows, cols = po.shape[0] // batch, po.shape[1]
+    for t, dt, what in ((counters, torch.int32, "counters"), (eligible, torch.uint8, "eligible")):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (rows,) or not t.is_contiguous() or t.device != po.device):
+            raise ValueError(f"token_score: {what} must be a contiguous {dt} [{rows}] tensor on {po.device}")
+    out = torch.empty(rows, dtype=torch.float32, device=po.device) if out is None else out
+    if out.dtype != torch.float32 or tuple(out.shape) != (rows,) or not out.is_contiguous() or out.device != po.device:
+        raise ValueError(f"token_score: out must be a contiguous fp32 [{rows}] tensor on {po.device}")
+    _lib.check(_lib.lib().fino_token_score(_p(po), rows, cols, po.stride(0), batch, _p(counters), float(starvation_scale),
+                                           _p(eligible), _p(out), _dt(po), _stream()), "fino_token_score")
+    return out
+
+
+def token_select(score, k, counters=None, out=None):
+    """The k rows of the largest scores (fino_token_select): fp32 [n] -> int32 [k] in ascending index order, ties to the lower
+    index; `counters` (int32 [n]) are set to 0 for the selected rows and incremented for the others.  n <= TOKEN_SELECT_MAX."""
+    if not score.is_cuda or score.dtype != torch.float32 or score.dim() != 1 or not score.is_contiguous():
+        raise ValueError(f"token_select: score must be a contiguous fp32 [n] device tensor, got {tuple(score.shape)} {score.dtype}")
+    n, k = score.shape[0], int(k)
+    if counters is not None and (counters.dtype != torch.int32 or tuple(counters.shape) != (n,) or not counters.is_contiguous()
+                                 or counters.device != score.device):
+        raise ValueError(f"token_select: counters must be a contiguous int32 [{n}] tensor on {score.device}")
+    out = torch.empty(max(k, 0), dtype=torch.int32, device=score.device) if out is None else _index_list(out, "token_select out")
+    if out.shape[0] != k or out.device != score.device:
+        raise ValueError(f"token_select: out holds {out.shape[0]} entries on {out.device}, want {k} on {score.device}")
+    _lib.check(_lib.lib().fino_token_select(_p(score), n, k, _p(out), _p(counters), _stream()), "fino_token_select")
+    return out
+
+
+def _row_bytes(t, what):
+    if not t.is_cuda:
+        raise RuntimeError("frameino_amd ops need CUDA(HIP) tensors; there is no CPU path")
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{what}: need a row-strided [rows, width] tensor, got {tuple(t.shape)} strides {t.stride()}")
+    return t.shape[1] * t.element_size(), t.stride(0) * t.element_size()
+
+
+def gather_rows(src, idx, out=None):
+    """out[r] = src[idx[r]] (fino_gather_rows): whole rows of a row-strided [n, width] tensor of any dtype by an int32 list;
+    indices are clamped into [0, n)."""
+    _index_list(idx, "gather_rows")
+    rb, lds = _row_bytes(src, "gather_rows src")
+    out = torch.empty((idx.shape[0], src.shape[1]), dtype=src.dtype, device=src.device) if out is None else out
+    rbo, ldo = _row_bytes(out, "gather_rows out")
+    if rbo != rb or out.dtype != src.dtype or out.shape[0] != idx.shape[0] or out.device != src.device or idx.device != src.device:
+        raise ValueError(f"gather_rows: src {tuple(src.shape)} {src.dtype}, {idx.shape[0]} indices, out {tuple(out.shape)} {out.dtype}")
+    _lib.check(_lib.lib().fino_gather_rows(_p(src), lds, src.shape[0], _p(idx), idx.shape[0], rb, _p(out), ldo, _stream()),
+               "fino_gather_rows")
+    return out
+
+
+def scatter_rows(src, idx, out):
+    """out[idx[r]] = src[r] (fino_scatter_rows): the inverse of `gather_rows`; indices are clamped into [0, rows of out)."""
+    _index_list(idx, "scatter_rows")
+    rb, lds = _row_bytes(src, "scatter_rows src")
+    rbo, ldo = _row_bytes(out, "scatter_rows out")
+    if rbo != rb or out.dtype != src.dtype or src.shape[0] != idx.shape[0] or out.device != src.device or idx.device != src.device:
+        raise ValueError(f"scatter_rows: src {tuple(src.shape)} {src.dtype}, {idx.shape[0]} indices, out {tuple(out.shape)} {out.dtype}")
+    _lib.check(_lib.lib().fino_scatter_rows(_p(src), lds, _p(idx), idx.shape[0], rb, _p(out), ldo, out.shape[0], _stream()),
+               "fino_scatter_rows")
+    return out
+
+
+def qkv_rmsnorm_rope_rows_(qkv, dim, q_weight, q_eps, k_weight, k_eps, cos, sin, head_dim, idx, kcache, vcache, q_out_scale=1.0):
+    """`qkv_rmsnorm_rope_` (in place, bit for bit) on a compact projection qkv [rows, 3 dim] whose row r is token idx[r] (int32
+    [rows]; None: token r) and whose cos / sin rows are the compact rows' own; the same launch writes row r's k (as just normed
+    and rotated) to kcache[idx[r]] and its v to vcache[idx[r]] -- row-strided [n, dim] planes with one row stride
+    (fino_qkv_rmsnorm_rope_rows).  Indices are clamped into [0, n)."""
+    x2, rows, width, ldx = _rows2d(qkv)
+    assert width == 3 * dim
+    assert cos.dtype == torch.float32 and cos.is_contiguous() and cos.shape == (rows, head_dim // 2) and sin.shape == cos.shape
+    assert sin.dtype == torch.float32 and sin.is_contiguous()
+    _rows_of(kcache, qkv.dtype, "qkv_rmsnorm_rope_rows_ kcache")
+    _rows_of(vcache, qkv.dtype, "qkv_rmsnorm_rope_rows_ vcache")
+    if kcache.shape != vcache.shape or kcache.shape[1] != dim or kcache.stride(0) != vcache.stride(0):
+        raise ValueError(f"qkv_rmsnorm_rope_rows_: planes {tuple(kcache.shape)} / {tuple(vcache.shape)} strides "
+                         f"{kcache.stride()} / {vcache.stride()}: need two [n, {dim}] planes with one row stride")
+    if idx is not None and _index_list(idx, "qkv_rmsnorm_rope_rows_").shape[0] != rows:
+        raise ValueError(f"qkv_rmsnorm_rope_rows_: {idx.shape[0]} indices for {rows} rows")
+    if idx is None and rows > kcache.shape[0]:
+        raise ValueError(f"qkv_rmsnorm_rope_rows_: {rows} rows for planes of {kcache.shape[0]}")
+    _lib.check(_lib.lib().fino_qkv_rmsnorm_rope_rows(_p(x2), rows, dim, ldx, _p(q_weight), q_eps, _p(k_weight), k_eps, _p(cos),
+                                                     _p(sin), head_dim, float(q_out_scale), _p(idx), kcache.shape[0], _p(kcache),
+                                                     _p(vcache), kcache.stride(0), _dt(qkv), _stream()),
+               "fino_qkv_rmsnorm_rope_rows")
+    return qkv

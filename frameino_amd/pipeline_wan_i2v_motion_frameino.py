@@ -36,6 +36,12 @@ MagCache (`enable_cache(MagCacheConfig(mag_ratios=curves, num_inference_steps=N)
 call into `transformer.magcache_calibration`) likewise: the eager loop, one GPU, fresh state per `denoise`, a batch sample by
 sample; its decisions depend on the step counter and the curve alone.  A call whose step count differs from the config's
 `num_inference_steps` warns: the curve is indexed by the step counter.
+
+Region-adaptive sampling (`enable_cache(RegionAdaptiveSamplingConfig(sample_ratio=0.5, num_inference_steps=N))`) likewise: the
+eager loop, one GPU, fresh state per `denoise`, a batch sample by sample; which steps run every token row depends on the step
+counter alone, which rows a partial step runs on the kept prediction (on the device: no host read).  The batched CFG call shares
+one list of active rows; the loop's `live_rows` keep the first frame and the ID frame off it.  A call whose step count differs
+from the config's warns: the full steps at the end are counted from the config's figure.
 """
 import html
 import re
@@ -173,7 +179,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
             reset()
 
     def _step_cache_check(self, batch):
-        """the limits of the step caches (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache), checked before any work (and before
+        """the limits of the step caches (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache, region-adaptive sampling), checked before any work (and before
         any collective: a parallel plan and the cache are configured by the same script on every rank, so every rank raises)"""
         if not getattr(self.transformer, "is_cache_enabled", False):
             return False
@@ -504,7 +510,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         """reference :809-913.  Returns the final latents [B, C, F, h, w] fp32.  The loop state is one sample's (the app
         and the evaluation scripts run batch 1); a batch -- a list of prompts, num_videos_per_prompt > 1 -- runs sample by sample:
         the samples of the reference's batched loop never meet, every one sees the noise row `prepare_latents` drew for it.
-        With a step cache (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache) every call -- every sample -- starts from fresh
+        With a step cache (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache, region-adaptive sampling) every call -- every sample -- starts from fresh
         cache state."""
         cached = self._step_cache_check(latents.shape[0])
         win_eager = self._window_attention_check()
@@ -543,6 +549,13 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
                               f"its curve (`mag_ratios`, resampled to {planned} entries) is misaligned with the loop and a "
                               f"context starts over after {planned} forwards.  Build the config with the call's step count.",
                               stacklevel=2)
+        if cached and getattr(self.transformer, "_ras_on", False):
+            planned = int(self.transformer._step_cache_config.num_inference_steps)
+            if planned != len(timesteps):       # once per call: the full steps at the end are counted from the config's figure
+                warnings.warn(f"region-adaptive sampling: this call runs {len(timesteps)} steps, the config says "
+                              f"num_inference_steps={planned}; its full steps at the end sit at forwards {planned} - "
+                              f"full_steps_at_end and later, and every forward from {planned} on is full.  Build the config "
+                              f"with the call's step count.", stacklevel=2)
         # FasterCache reads `current_timestep` on the host up to three times per step: a host copy of the schedule, taken once,
         # keeps those reads from waiting for the device
         ts_host = timesteps.cpu() if cached and getattr(self.transformer, "_faster_on", False) else None

@@ -125,6 +125,29 @@ buffer, which is read ONCE, when the context starts over or the state is reset, 
 accumulators after the decision; `(context, s, True, None, None)` in calibrate mode.  The model asks `_magcache_begin` for a forward's
 decisions and `_magcache_finish` after the stack.
 
+Region-adaptive sampling (`RegionAdaptiveSamplingConfig`, a config of this project; after RAS, Liu et al. 2025, "Region-Adaptive
+Sampling for Diffusion Transformers").  The one policy that removes work along the TOKEN axis: a partial forward runs only the La
+active token rows of every batch element through the embedding, the blocks and the head; the other rows keep the prediction of
+the last forward that computed them and serve every layer's self-attention as keys and values from per-layer K / V planes.  Per
+state, s = the 0-based count of forwards since the last reset, W = warmup_steps, N = full_step_interval, E = full_steps_at_end,
+T = num_inference_steps (`ras_decide`, a function of s alone):
+
+    full  if  s < W  or  s >= T - E  or  (s - (W - 1)) % N == 0  or  sample_ratio >= 1  or  there are no K / V planes yet
+
+A full forward is the uncached forward (without the shared CFG prefix) whose norm + RoPE stage also writes every layer's K and V
+into the planes, and whose head rows `po` are kept; the sit-out counters go to 0.  A partial forward first makes its list from the
+kept `po` -- ops.token_score (per row the population standard deviation of its C_out values, averaged over the batch elements
+of the call, times exp(starvation_scale * counter); rows outside `live_rows` score -inf, `always_active` rows +inf) and
+ops.token_select (the La = max(1, round(sample_ratio * n_eligible)) largest, ties to the lower index, ascending; counters 0 for
+the listed rows, + 1 for the others) -- gathers the patch, cos / sin and selector rows, runs every per-token stage on the compact
+[b * La, D] buffers with q at lq = La against the planes just refreshed at the active rows (ops.qkv_rmsnorm_rope_rows_), scatters
+the head's rows into `po` and returns the unpatchified `po`.  One state per CALL: a batch whose elements are named by
+`_cache_contexts` (the pipeline's CFG batch) shares one list, one counter vector and one set of [b * n, D] planes, filed under the
+tuple of the names; a call under one `cache_context` files under that name.  State: per layer two planes K (after norm and RoPE)
+and V [b * n, D], `po` [b * n, C_out], counters int32 [n] -- 2 planes per context and layer, 9.1 GB for the two contexts of the
+30-layer model at 12320 tokens.  Past T forwards every forward is full until the state is reset.  `cache_log` gets
+`(context, s, full, rows_run)` per forward and context.  The model asks `_ras_begin` for a forward's decision.
+
 The CogVideoX DiT (`PyramidAttentionBroadcastMixin`) takes Pyramid Attention Broadcast alone, with the same rule and state: its one
 attention layer per block, the joint text + video attn1, is the "spatial" kind, and a call's whole batch is one segment under one
 context (diffusers' CogVideoX pipelines run the CFG batch under `cache_context("cond_uncond")`).
@@ -226,6 +249,25 @@ class MagCacheConfig:
     calibrate: bool = False
 
 
+@dataclasses.dataclass
+class RegionAdaptiveSamplingConfig:
+    """Region-adaptive sampling (a config of this project, not of diffusers): on most steps only a fixed fraction of the token
+    rows -- those whose prediction is moving most -- run through the model; the rest keep their last prediction and serve the
+    self-attention from per-layer K / V planes.  A partial step runs La = max(1, round(sample_ratio * n_eligible)) rows per batch
+    element.  Full steps: the first `warmup_steps`, the last `full_steps_at_end` of `num_inference_steps`, and every
+    `full_step_interval`-th counted from the last warm-up step.  A row that has sat out k consecutive partial steps has its score
+    multiplied by exp(starvation_scale * k).  `always_active`: a bool [L] mask of rows that are on every list (they count
+    towards La; more of them than La: ValueError at the first forward).  Memory: two [rows, D] planes per cache context and
+    layer (9.1 GB for the two CFG contexts of the 30-layer model at 12320 tokens)."""
+    sample_ratio: float = 0.5
+    full_step_interval: int = 5
+    warmup_steps: int = 4
+    full_steps_at_end: int = 2
+    num_inference_steps: int = 50
+    starvation_scale: float = 0.1
+    always_active: Optional[torch.Tensor] = None
+
+
 # the other configs diffusers' CacheMixin applies: recognised, not implemented here
 _OTHER_DIFFUSERS_CONFIGS = ("TeaCacheConfig",)
 _MAG_DEFAULTS = {f.name: f.default for f in dataclasses.fields(MagCacheConfig)}
@@ -248,6 +290,22 @@ def taylorseer_decide(s, n_factors, cfg):
     w, n = int(cfg.disable_cache_before_step), int(cfg.cache_interval)
     after = getattr(cfg, "disable_cache_after_step", None)
     return n_factors == 0 or s < w or (s - (w - 1)) % n == 0 or (after is not None and s >= after)
+
+
+def ras_decide(s, cfg, has_cache=True):
+    """True: forward `s` (0-based, per state, since the last reset) under region-adaptive sampling is FULL; False: it runs the
+    active rows only.  A function of the step counter alone.  With W = warmup_steps, N = full_step_interval,
+    E = full_steps_at_end and T = num_inference_steps: full during the warm-up (s < W), at the end (s >= T - E), on every N-th
+    forward counted from the last warm-up forward ((s - (W - 1)) % N == 0), whenever sample_ratio >= 1, and while there are no
+    K / V planes yet (`has_cache` False)."""
+    w, n = int(cfg.warmup_steps), int(cfg.full_step_interval)
+    end = int(cfg.num_inference_steps) - int(cfg.full_steps_at_end)
+    return (not has_cache) or float(cfg.sample_ratio) >= 1.0 or s < w or s >= end or (s - (w - 1)) % n == 0
+
+
+def ras_active_count(sample_ratio, n_eligible):
+    """La: the rows a partial forward runs per batch element"""
+    return max(1, int(round(float(sample_ratio) * int(n_eligible))))
 
 
 def _fc(cfg, name):
@@ -444,7 +502,12 @@ class _CachePolicy:
         """whether it runs with a user-installed attention processor: unless stated otherwise, likewise"""
         return not cls.hooks_attention(config)
 
-    # the four places of a forward a cache can sit in; None: not there
+    @staticmethod
+    def takes_fp8_attention(config):
+        """whether it runs with fp8 self-attention"""
+        return True
+
+    # the places of a forward a cache can sit in; None: not there
     @staticmethod
     def segments(model, b, n, contexts):
         """around block 0 and the rest of the stack (`_step_cache_probe` / `_step_cache_finish`): the row segments"""
@@ -460,6 +523,10 @@ class _CachePolicy:
     @staticmethod
     def magcache(model, b, n, d, dtype, device, contexts):
         """around the block stack, between the embedding and the output head, on the residual stream's rows: a plan"""
+
+    @staticmethod
+    def ras(model, b, n, d, d_out, dtype, device, contexts, live, active_rows):
+        """along the token axis of the whole forward (region-adaptive sampling): a plan"""
 
 
 class _FirstBlockPolicy(_CachePolicy):
@@ -654,7 +721,48 @@ class _MagCachePolicy(_CachePolicy):
         return model._magcache_begin(b, n, d, dtype, device, contexts)
 
 
-_POLICIES = {p.name: p for p in (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy, _MagCachePolicy)}
+class _RegionAdaptivePolicy(_CachePolicy):
+    name = "RegionAdaptiveSamplingConfig"
+    required = ("sample_ratio", "full_step_interval", "warmup_steps", "full_steps_at_end", "num_inference_steps",
+                "starvation_scale", "always_active")
+    label = attention_label = "region-adaptive sampling"
+    instead = "first-block caching is"
+    why_eager = "whether a step runs every token row or the active ones alone changes from step to step on the host's schedule"
+    batched = True              # (the list comes from the call's own rows: the samples of a batch run one at a time, as under PAB)
+
+    @staticmethod
+    def validate(config, model):
+        """ValueError for a field outside its range or a mask that is no bool vector"""
+        r = config.sample_ratio
+        if isinstance(r, bool) or not isinstance(r, (int, float)) or not (0.0 < float(r) <= 1.0):
+            raise ValueError(f"RegionAdaptiveSamplingConfig.sample_ratio = {r!r}: need a number in (0, 1]")
+        for name, lo in (("full_step_interval", 1), ("warmup_steps", 1), ("full_steps_at_end", 0), ("num_inference_steps", 1)):
+            v = getattr(config, name)
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+                raise ValueError(f"RegionAdaptiveSamplingConfig.{name} = {v!r}: need an integer of at least {lo}")
+        v = config.starvation_scale
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= float(v) < float("inf")):
+            raise ValueError(f"RegionAdaptiveSamplingConfig.starvation_scale = {v!r}: need a finite number of at least 0")
+        m = config.always_active
+        if m is not None and (not isinstance(m, torch.Tensor) or m.dtype != torch.bool or m.dim() != 1):
+            raise ValueError(f"RegionAdaptiveSamplingConfig.always_active: need a bool [L] tensor or None, got "
+                             f"{type(m).__name__}" + (f" {m.dtype} {tuple(m.shape)}" if isinstance(m, torch.Tensor) else ""))
+
+    @staticmethod
+    def hooks_attention(config):          # (the self-attention reads the planes: no window, no tile mask, no user processor)
+        return True
+
+    @staticmethod
+    def takes_fp8_attention(config):      # (the planes are kept in the model dtype and read by the bf16 / fp16 kernel)
+        return False
+
+    @staticmethod
+    def ras(model, b, n, d, d_out, dtype, device, contexts, live, active_rows):
+        return model._ras_begin(b, n, d, d_out, dtype, device, contexts, live, active_rows)
+
+
+_POLICIES = {p.name: p for p in (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy, _MagCachePolicy,
+                                 _RegionAdaptivePolicy)}
 
 
 # ---------------------------------------------------------------------- one plan for the attention branches of a forward
@@ -764,7 +872,8 @@ class StepCacheMixin:
     delta and its weights; log rows `(context, i, t, stack_ran, attention_computed)`.
     MagCache: a counter, the three accumulators, the stack's residual [rows, D] and, in calibrate mode, the [N, 2] fp64 rows;
     log rows `(context, s, computed, acc_err, acc_steps)`."""
-    _cache_policies = (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy, _MagCachePolicy)
+    _cache_policies = (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy, _MagCachePolicy,
+                       _RegionAdaptivePolicy)
     magcache_calibration = None     # {context: {"mag_ratios": [...], "cos_dist": [...]}} once a calibrating context finished
     _step_cache_config = None
     _step_cache_policy = None
@@ -825,6 +934,7 @@ class StepCacheMixin:
     _faster_on = property(lambda self: self._step_cache_policy is _FasterCachePolicy)
     _faster_attention = property(lambda self: self._faster_on and _FasterCachePolicy.hooks_attention(self._step_cache_config))
     _mag_on = property(lambda self: self._step_cache_policy is _MagCachePolicy)
+    _ras_on = property(lambda self: self._step_cache_policy is _RegionAdaptivePolicy)
 
     # ---------------------------------------------------------------- used by the forward
     def _context_segments(self, b, n, contexts):
@@ -1152,6 +1262,61 @@ class StepCacheMixin:
         rows = stats[:st.steps].tolist()
         self.magcache_calibration = dict(self.magcache_calibration or {})
         self.magcache_calibration[name] = {"mag_ratios": [r[0] for r in rows], "cos_dist": [r[1] for r in rows]}
+
+
+    # ---------------------------------------------------------------- region-adaptive sampling
+    def _ras_begin(self, b, n, d, d_out, dtype, device, contexts=None, live=None, active_rows=None):
+        """The decision of one forward under region-adaptive sampling, taken before anything is launched: None when it is off,
+        else a plan with `.full`, `.state` (ONE per call: filed under the context name, or under the tuple of the names of a
+        batch whose elements are named), `.rows` (La of a partial forward, n of a full one), `.override` (the list a caller
+        passed as `_active_rows`: that forward is partial whatever the schedule says, and the counters stay) and `.cfg`.
+        `live`: the (lo, hi) rows the caller reads -- the others are not eligible.  Advances the counter and appends
+        `(context, s, full, rows_run)` per context of the call to `cache_log`.  A state whose batch, rows, widths, dtype or
+        device changed starts over."""
+        if not self._ras_on:
+            return None
+        cfg = self._step_cache_config
+        names = tuple(name for name, _, _ in self._context_segments(b, n, contexts))
+        st = self._cache_state(names[0] if len(names) == 1 else names, (b, n, d, d_out, dtype, str(device)),
+                               lambda: dict(planes=None, po=None, counters=None, score=None, idx=None, eligible=None,
+                                            eligible_key=None, n_always=0, valid=False))
+        lo, hi = (0, n) if live is None else live
+        key = (lo, hi, id(cfg.always_active))
+        if st.eligible_key != key:           # one host read per state: how many rows the mask pins
+            elig = torch.zeros(n, dtype=torch.uint8, device=device)
+            elig[lo:hi] = 1
+            st.n_always = 0
+            if cfg.always_active is not None:
+                mask = cfg.always_active.to(device)
+                if mask.shape[0] != n:
+                    raise ValueError(f"RegionAdaptiveSamplingConfig.always_active has {mask.shape[0]} entries, the forward "
+                                     f"{n} token rows")
+                pinned = mask & (elig == 1)
+                elig[pinned] = 2
+                st.n_always = int(pinned.sum())
+            st.eligible, st.eligible_key = elig, key
+        la = ras_active_count(cfg.sample_ratio, hi - lo)
+        if st.n_always > la:
+            raise ValueError(f"RegionAdaptiveSamplingConfig.always_active pins {st.n_always} of the {hi - lo} eligible token rows, "
+                             f"a partial step runs La = {la} (sample_ratio = {cfg.sample_ratio}): raise sample_ratio or shrink "
+                             f"the mask")
+        s = st.steps
+        override = None
+        if active_rows is not None:
+            if not st.valid:
+                raise RuntimeError("forward(_active_rows=...): a partial forward needs the K / V planes of a full forward of this "
+                                   "state first")
+            override = active_rows.to(device=device, dtype=torch.int32).contiguous()
+            if override.dim() != 1 or not 1 <= override.shape[0] <= n:
+                raise ValueError(f"_active_rows: need a list of 1 .. {n} row indices, got {tuple(override.shape)}")
+            full, rows = False, int(override.shape[0])
+        else:
+            full = bool(ras_decide(s, cfg, st.valid))
+            rows = n if full else la
+        for name in names:
+            self.cache_log.append((name, s, full, rows))
+        st.steps += 1
+        return SimpleNamespace(full=full, state=st, rows=rows, override=override, cfg=cfg, idx=None, names=names)
 
 
 class PyramidAttentionBroadcastMixin(StepCacheMixin):

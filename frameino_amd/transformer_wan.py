@@ -19,8 +19,9 @@ cross-attention branch outputs of the previous step on a schedule of the step co
 (frameino_amd/step_cache.py); `TaylorSeerCacheConfig` extrapolates the attention branches (or the output) along the step axis;
 `FasterCacheConfig` skips the unconditional CFG branch on a schedule and rebuilds its prediction from the conditional one, and
 extrapolates the self-attention branches; `MagCacheConfig` skips the whole block stack of a step and adds the stack's residual
-of the last computing step, on a schedule of the step counter and a per-model curve (`calibrate=True` measures it).  One at a
-time, all off by default.
+of the last computing step, on a schedule of the step counter and a per-model curve (`calibrate=True` measures it);
+`RegionAdaptiveSamplingConfig` (this project's) runs only the active token rows of most steps, the others serving the self-attention
+from per-layer K / V planes.  One at a time, all off by default.
 """
 import contextlib
 import math
@@ -146,7 +147,11 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
     FasterCache (enable_cache(FasterCacheConfig(...))): the unconditional CFG branch runs on a schedule and
     is rebuilt from the conditional prediction in between (`_faster_forward`); that part works with MX linears, fp8 / window /
     sparse attention and LoRA.  Its self-attention extrapolation takes TaylorSeer's route through the attention branches and
-    refuses what TaylorSeer's default mode refuses."""
+    refuses what TaylorSeer's default mode refuses.
+
+    Region-adaptive sampling (enable_cache(RegionAdaptiveSamplingConfig(...))): a partial forward runs the
+    listed token rows alone (`_ras_partial`), q at lq = La against per-layer K / V planes of all rows; LoRA and MX linears work with
+    it; window, sparse and fp8 attention, a token-sharded plan and user-installed attention processors are refused."""
     _window_table_cache = "_rope_cache"
     _loader_name = "load_wan_transformer"
     _keep_in_fp32_modules = ["time_embedder", "scale_shift_table", "norm1", "norm2", "norm3"]   # reference :393
@@ -310,23 +315,29 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
             raise NotImplementedError(f"{what} with a user-installed attention processor: the windows are applied by the "
                                       f"built-in MI355WanAttnProcessor path only")
 
-    def _cache_refusals(self, policy=None, config=None, enabling=False, window=False, sparse=False, shard=None, default_procs=True):
+    def _cache_refusals(self, policy=None, config=None, enabling=False, window=False, sparse=False, shard=None, default_procs=True,
+                        fp8=False):
         """What a step cache does not combine with on this model, in both orders.  `enabling`: `enable_cache` asks about `policy`
         and `config`, against what the model has on; else the enabled cache is asked about the feature that is being switched
         on (`window` / `sparse`: `_window_refusals`, `_sparse_refusals`) and about the forward that is about to run (`shard`,
         `default_procs`: `_bind`, before its first launch).  No cache runs token-sharded.  One that takes over the attention
         branches (`policy.hooks_attention`) does not run beside window or sparse attention and needs the built-in processors;
-        the policies state the two exceptions (`takes_windows`, `takes_any_processor`)."""
+        the policies state the two exceptions (`takes_windows`, `takes_any_processor`).  `fp8`: fp8 self-attention, for a policy that
+        keeps K / V in the model dtype (`takes_fp8_attention`)."""
         policy = policy or self._step_cache_policy
         if policy is None:
             return
         config = config if enabling else self._step_cache_config
         if enabling:
-            window, sparse, shard = self._window is not None, self._sparse is not None, self.parallel
+            window, sparse, shard, fp8 = self._window is not None, self._sparse is not None, self.parallel, self.fp8_attention
             default_procs = policy.takes_any_processor(config) or self._default_processors()
         if shard is not None and getattr(shard, "active", True):
             raise NotImplementedError(f"{policy.label} with a token-sharded plan: the step caches run on one GPU")
         what = policy.attention_label or policy.label
+        if fp8 and not policy.takes_fp8_attention(config):
+            first, second = (what, "fp8 attention (enable_fp8_attention)") if enabling else ("fp8 attention (enable_fp8_attention)", what)
+            raise NotImplementedError(f"{first} with {second}: the K / V planes are kept in the model dtype and read by the "
+                                      f"bf16 / fp16 kernel; switch one of them off first")
         for on, other in ((window, "window attention (enable_window_attention)"), (sparse, "sparse attention (enable_sparse_attention)")):
             if on and not policy.takes_windows(config):
                 first, second = (what, other) if enabling else (other, what)
@@ -495,7 +506,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
     @torch.no_grad()
     def forward(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None,
                 return_dict=True, attention_kwargs=None, timestep_rows=None, live_rows=None, _cache_contexts=None,
-                id_frames=0):
+                id_frames=0, _active_rows=None):
         """`timestep_rows=(values [R], selector int32 [L])` is the de-duplicated form of a per-token timestep; when a
         2-D `timestep` is given instead it is de-duplicated here (torch.unique: host sync, eager only).
         `live_rows=(lo, hi)` (round 6): the caller will only read the output of token rows [lo, hi) -- the FrameINO loop drops the
@@ -510,10 +521,13 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         joint decision, as diffusers does (first-block caching: over the means of all its rows; Pyramid Attention Broadcast:
         one counter and one [B * L, D] buffer per layer and kind for the whole batch; TaylorSeer likewise, with its factor planes).
         `id_frames` (window and sparse attention only, `enable_window_attention` / `enable_sparse_attention`): the trailing latent frames that are identity-reference
-        frames -- every query sees them, like the configured sink frames."""
+        frames -- every query sees them, like the configured sink frames.
+        `_active_rows` (private, a TEST HOOK of region-adaptive sampling): an integer tensor of token rows that replaces the list
+        the model would derive, for this one forward, which is then partial whatever the schedule says (the sit-out counters
+        stay as they are)."""
         gen = self.forward_steps(hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image,
                                  return_dict, attention_kwargs, timestep_rows, live_rows=live_rows,
-                                 _cache_contexts=_cache_contexts, id_frames=id_frames)
+                                 _cache_contexts=_cache_contexts, id_frames=id_frames, _active_rows=_active_rows)
         while True:
             try:
                 next(gen)
@@ -522,7 +536,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
 
     def forward_steps(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None,
                       return_dict=True, attention_kwargs=None, timestep_rows=None, shard=None, live_rows=None,
-                      _cache_contexts=None, id_frames=0):
+                      _cache_contexts=None, id_frames=0, _active_rows=None):
         """The forward as a generator that yields after the embedding stage and after every block, so that a caller
         can interleave two independent forwards (the CFG branches) kernel-stream by kernel-stream
         (frameino_amd/parallel.py: one branch's K|V all-gather then flies under the other branch's compute).  Every
@@ -537,10 +551,14 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         self._lora_apply(attention_kwargs.pop("scale", None) if attention_kwargs is not None else None)
         self._mx_requantise_if_pending()
         args = (attention_kwargs, timestep_rows, shard, live_rows, id_frames)
+        if _active_rows is not None and not self._ras_on:
+            raise ValueError("forward(_active_rows=...) is a hook of region-adaptive sampling "
+                             "(enable_cache(RegionAdaptiveSamplingConfig(...)) first)")
         if self._faster_on:
             out = yield from self._faster_forward(hidden_states, timestep, encoder_hidden_states, _cache_contexts, args)
         else:
-            out = yield from self._forward_stack(hidden_states, timestep, encoder_hidden_states, _cache_contexts, *args)
+            out = yield from self._forward_stack(hidden_states, timestep, encoder_hidden_states, _cache_contexts, *args,
+                                                 active_rows=_active_rows)
         return (out,) if not return_dict else SimpleNamespace(sample=out)
 
     def _faster_forward(self, hidden_states, timestep, encoder_hidden_states, contexts, args):
@@ -588,10 +606,12 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         return out
 
     def _forward_stack(self, hidden_states, timestep, encoder_hidden_states, _cache_contexts, attention_kwargs, timestep_rows,
-                       shard, live_rows, id_frames, faster=None, out_buf=None, text_slot=None):
+                       shard, live_rows, id_frames, faster=None, out_buf=None, text_slot=None, active_rows=None):
         """embedding, blocks and output head of one call (the body of `forward_steps`) -> the prediction [b, C, F, H, W]"""
         c = self._bind(hidden_states, timestep, encoder_hidden_states, attention_kwargs, timestep_rows, shard, live_rows,
-                       _cache_contexts, id_frames, faster, out_buf, text_slot)
+                       _cache_contexts, id_frames, faster, out_buf, text_slot, active_rows)
+        if c.ras is not None and not c.ras.full:
+            return (yield from self._ras_partial(c, hidden_states))        # region-adaptive sampling: the active rows alone
         if c.lite is not None and not any(seg.compute["self"] for seg in c.lite.segs):
             return self._taylor_lite_rows(c, c.ws.po[:c.nr])                      # TaylorSeer, lite mode: the output rows predicted
         self._embed(c, hidden_states)
@@ -659,7 +679,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         return t_rows, torch.arange(b, device=dev, dtype=torch.int32).repeat_interleave(n), False
 
     def _bind(self, hidden_states, timestep, encoder_hidden_states, attention_kwargs, timestep_rows, shard, live_rows,
-              cache_contexts, id_frames=0, faster=None, out_buf=None, text_slot=None):
+              cache_contexts, id_frames=0, faster=None, out_buf=None, text_slot=None, active_rows=None):
         """Everything the stages of one call share, as a `_Call`: geometry, this rank's token shard, workspace views, RoPE
         tables, modulation tables + selector, text K/V and the switches that pick a path."""
         o, cfg = self.ops, self.config
@@ -680,7 +700,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
             self._window_refusals(self.fp8_attention, default_procs, sh)
         if self._sparse is not None:             # ... and what sparse attention refuses
             self._sparse_refusals(self.fp8_attention, default_procs, sh)
-        self._cache_refusals(shard=sh, default_procs=default_procs)      # ... and what the enabled step cache refuses
+        self._cache_refusals(shard=sh, default_procs=default_procs, fp8=self.fp8_attention)      # ... and what the enabled step cache refuses
         lo, n, lpad = 0, L, L
         tk = {}         # the shard's tile height for its GEMM calls (a per-call argument of the C ABI; {} = the library's planner)
         if sh is not None:
@@ -692,11 +712,14 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
                 tk = {"tile_m": sh.tile_m_for(n)}
         # the step cache's places in this forward, each None when it does not sit there: `fbc` around block 0 (first-block
         # caching), `lite` around the whole stack (TaylorSeer's lite mode), `branches` in every block's attention branches,
-        # `mag` around the block stack between the embedding and the output head (MagCache).
+        # `mag` around the block stack between the embedding and the output head (MagCache), `ras` along the token axis of the
+        # whole forward (region-adaptive sampling).
         # Their decisions are taken here, before any launch (a timestep callback is read once)
         policy = self._step_cache_policy
-        fbc = lite = branches = mag = None
+        fbc = lite = branches = mag = ras = None
         if policy is not None:
+            ras = policy.ras(self, b, n, d, cfg.out_channels * math.prod(cfg.patch_size), dt, dev, cache_contexts,
+                             _live_range(live_rows, n), active_rows)
             fbc = policy.segments(self, b, n, cache_contexts)
             mag = policy.magcache(self, b, n, d, dt, dev, cache_contexts)        # MagCache: around the whole block stack
             lite = policy.lite(self, b, n, cfg.out_channels * math.prod(cfg.patch_size), dt, dev, cache_contexts)
@@ -729,7 +752,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         # would have computed).  A per-sample timestep ([b] or [b, L] values) takes the general path.
         # (Pyramid Attention Broadcast keeps one cache per context and layer: every element runs block 0's branch itself)
         shared = (self.dedup_shared_prefix and b > 1 and sh is None and hidden_states.stride(0) == 0 and default_procs
-                  and same_rows and branches is None)
+                  and same_rows and branches is None and ras is None)
         fold = self.fold_softmax_scale
         fp8 = self.fp8_attention and sh is None and hasattr(o, "attention_fp8")     # this call's self-attention takes fp8 operands
         # sliding-window self-attention over frames: this forward's decision (the timestep callback is read here, once)
@@ -753,7 +776,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
                      text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
                      afold={"scale": o.SCALE_FOLDED} if fold else {}, fp8=fp8, default_procs=default_procs,
                      shared=shared, fbc=fbc, branches=branches, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
-                     live=live, win=win, sp=sp, lite=lite, mag=mag, out_buf=out_buf,
+                     live=live, win=win, sp=sp, lite=lite, mag=mag, ras=ras, out_buf=out_buf,
                      live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
                      rows=(0, n),            # the rows of every batch element that run as queries / per-token rows ...
                      segs=[(0, nr)])         # ... and the global row ranges the per-token operations of a block run on
@@ -790,6 +813,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
             if sh is not None:
                 raise NotImplementedError("token-sharded execution needs the built-in MI355WanAttnProcessor")
             return self._sa_processors(c, blk, m)
+        if c.ras is not None:                         # region-adaptive sampling: K and V kept in / read from the planes
+            return self._sa_ras(c, li, blk, e, m)
         if c.shared and li == 0:                      # CFG batch of one latent: block 0's branch once, copied
             return self._sa_shared_prefix(c, li, blk, e, m)
         if sh is None:                                # one GPU
@@ -1000,6 +1025,82 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
             self._lin(li, "out2", att[r0:r1], a2.to_out[0].weight, a2.to_out[0].bias, o.EPI_RESIDUAL, residual=x[r0:r1],
                       out=x[r0:r1], **c.tk, **_keep_kw(c, r0, r1))
 
+    # ------------------------------------------------------------------ forward: region-adaptive sampling
+    def _ras_buffers(self, c):
+        """the state's device buffers, allocated by its first forward: per layer the planes K | V [2, b * n, D], the kept head
+        rows po [b * n, C_out], the sit-out counters, the scores and the list"""
+        st, nr = c.ras.state, c.nr
+        if st.planes is None:
+            mk = lambda *s, dtype=c.dt: torch.empty(*s, dtype=dtype, device=c.dev)          # noqa: E731
+            st.planes = [mk(2, nr, c.d) for _ in self.blocks]
+            st.po = mk(nr, c.ws.po.shape[1])
+            st.counters = torch.zeros(c.n, dtype=torch.int32, device=c.dev)
+            st.score = mk(c.n, dtype=torch.float32)
+        return st
+
+    def _sa_ras(self, c, li, blk, e, m):
+        """`_sa_single` under region-adaptive sampling.  A full forward: the same launches, the norm + RoPE stage also writing
+        every row's k and v into layer li's planes (q | k | v of the attention still read in place: the bits of the uncached
+        forward).  A partial forward (`c` = the compact call): the projection of the active rows alone, their k and v written
+        over their rows of the planes, and q at lq = La against all n rows of the planes."""
+        o, b, n, d, ras, a = self.ops, c.b, c.n, c.d, c.ras, blk.attn1
+        st = self._ras_buffers(c) if ras.full else ras.state
+        xq = self._ln_q(li, "qkv", 0, c.x, shift=m[:, 0], scale=m[:, 1], sel=c.sel, eps=c.eps)
+        if xq is None:
+            o.adaln_modulate(c.x, m[:, 0], m[:, 1], c.sel, c.eps, out=c.nrm)
+        self._lin(li, "qkv", c.nrm, e.wqkv, e.bqkv, xq=xq, out=c.qkv)
+        kp, vp = st.planes[li][0], st.planes[li][1]
+        o.qkv_rmsnorm_rope_rows_(c.qkv, d, a.norm_q.weight, a.norm_q.eps, a.norm_k.weight, a.norm_k.eps, c.cos, c.sin, c.dh,
+                                 ras.idx, kp, vp, q_out_scale=c.qfold.get("out_scale", 1.0))
+        q3 = c.qkv.view(b, n, 3 * d)
+        if ras.full:
+            s0, s1 = c.rows
+            o.attention(q3[:, s0:s1, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], c.heads, out=c.att.view(b, n, d)[:, s0:s1], **c.afold)
+        else:
+            o.attention(q3[:, :, :d], kp.view(b, -1, d), vp.view(b, -1, d), c.heads, out=c.att.view(b, n, d), **c.afold)
+        return False
+
+    def _ras_partial(self, c, hidden_states):
+        """A partial forward of region-adaptive sampling (`c`: the call as `_bind` made it, over all rows).  The list -- from the
+        kept head rows (ops.token_score + ops.token_select; one list per call, from the batch-averaged score) or the caller's
+        `_active_rows` --, then patches, cos / sin and selector rows gathered by it, every stage on the compact [b * La, D]
+        buffers (the first rows of the workspace), the head's rows scattered into the kept `po`, and the whole `po` unpatchified:
+        a row that did not run returns the prediction of the last forward that computed it."""
+        o, ras, st, b, n, d = self.ops, c.ras, c.ras.state, c.b, c.n, c.d
+        la = ras.rows
+        if ras.override is not None:
+            idx1 = ras.override
+        else:
+            if st.idx is None or st.idx.shape[0] != la:
+                st.idx = torch.empty(la, dtype=torch.int32, device=c.dev)
+            o.token_score(st.po, batch=b, counters=st.counters, starvation_scale=float(ras.cfg.starvation_scale),
+                          eligible=st.eligible, out=st.score)
+            idx1 = o.token_select(st.score, la, counters=st.counters, out=st.idx)
+        ras.idx = idx = idx1 if b == 1 else torch.cat([idx1 + i * n for i in range(b)])       # rows of the [b * n, .] buffers
+        nra, ws, patch = b * la, c.ws, self.config.patch_size
+        patches = (o.patchify(hidden_states[0], patch) if b == 1 else
+                   torch.cat([o.patchify(hidden_states[i], patch) for i in range(b)]))
+        x = ws.x[:nra]
+        o.gemm(o.gather_rows(patches, idx, out=ws.a[:nra]), c.pk.w_patch, self.patch_embedding.bias, out=x)
+        fields = {k: getattr(c, k) for k in c.__slots__ if k != "elements"}
+        fields.update(n=la, nr=nra, L=la, x=x, nrm=ws.n[:nra], att=ws.att[:nra], q2=ws.q2[:nra], ff=ws.ff[:nra], qkv=ws.qkv[:nra],
+                      cos=o.gather_rows(c.cos, idx), sin=o.gather_rows(c.sin, idx), cos1=None, sin1=None,
+                      sel=None if c.sel is None else o.gather_rows(c.sel.view(-1, 1), idx).view(-1),
+                      shared=False, live=None, live_segs=None, rows=(0, la), segs=[(0, nra)])
+        cc = _Call(**fields)
+        yield
+        for li, (blk, e) in enumerate(zip(self.blocks, c.pk.layers)):
+            m = c.mod[:, li]
+            self._sa_ras(cc, li, blk, e, m)
+            self._self_attention_out(cc, li, blk, m)
+            self._cross_attention(cc, li, blk)
+            self._ffn(cc, li, blk, m)
+            yield
+        o.adaln_modulate(x, c.head[:, 0], c.head[:, 1], cc.sel, c.eps, out=cc.nrm)
+        rows = o.gemm(cc.nrm, self.proj_out.weight, self.proj_out.bias, out=ws.po[:nra])
+        o.scatter_rows(rows, idx, st.po)
+        return self._unpatchify(c, st.po)
+
     # ------------------------------------------------------------------ forward: Pyramid Attention Broadcast
     def _pab_attention(self, c, li, blk, e, m):
         """Block li's two attention branches under a cache that has taken them over (`c.branches`: this forward's decisions per
@@ -1081,6 +1182,11 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
             po = sh.all_gather_out(po_loc)[:c.L]
         if c.lite is not None:
             return self._taylor_lite_rows(c, po)
+        if c.ras is not None:                # a full forward under region-adaptive sampling keeps the head's rows
+            st = c.ras.state
+            st.po.copy_(po)
+            st.counters.zero_()
+            st.valid = True
         return self._unpatchify(c, po)
 
     def _unpatchify(self, c, po):
@@ -1104,14 +1210,16 @@ class _Call:
     attention branches (`_BranchPlan`: Pyramid Attention Broadcast, TaylorSeer's default mode, FasterCache's self-attention
     part), else None; `lite`: the plan of TaylorSeer's lite mode -- when every segment of it predicts, `_bind` returns a call
     with the geometry, the workspace and the plan alone; `mag`: MagCache's plan for the block stack as a whole (`h0` is then
-    the stack's input, kept by the embedding stage)."""
+    the stack's input, kept by the embedding stage); `ras`: the plan of region-adaptive sampling -- a partial forward runs on
+    a second `_Call` over the compact rows (`_ras_partial`)."""
     __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
                  "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
                  "afold", "fp8", "default_procs", "shared", "fbc", "branches", "keep", "h0", "h1c", "attention_kwargs", "live",
-                 "live_segs", "rows", "segs", "win", "sp", "lite", "mag", "out_buf", "elements")
+                 "live_segs", "rows", "segs", "win", "sp", "lite", "mag", "ras", "out_buf", "elements")
 
     def __init__(self, **fields):
         self.elements = None
+        self.ras = None
         for k, v in fields.items():
             setattr(self, k, v)
 
@@ -1130,6 +1238,14 @@ class _Call:
                  text=_text_element(self.text, i, self.b, self.n, self.d), keep=None)
         self.elements[i] = _Call(**f)
         return self.elements[i]
+
+
+def _live_range(live_rows, n):
+    """`forward(live_rows=(lo, hi))` as a checked row range of a sequence of n rows, or None (no range, or not a proper one)"""
+    if live_rows is None:
+        return None
+    lo, hi = int(live_rows[0]), int(live_rows[1])
+    return (lo, hi) if 0 <= lo < hi <= n else None
 
 
 def _sel_rows(sel, r0, r1):

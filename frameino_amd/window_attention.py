@@ -326,6 +326,8 @@ class SelfAttentionOptionsMixin:
         to the normalised output in fp32 (fino_attn_fwd_fp8_smoothed): exact, the softmax weights sum to one, and an offset that
         all keys of a channel share (attn1.to_v.bias, a DC component of the modulated input: V has no norm and no RoPE) stops
         taking the mantissa bits.  Off by default."""
+        if enabled and getattr(self, "_step_cache_policy", None) is not None:
+            self._cache_refusals(fp8=True)           # (a step cache that keeps K / V in the model dtype says so, once)
         if enabled and self._sparse is not None:
             self._sparse_refusals(True, self._default_processors(), getattr(self, "parallel", None))
         if enabled and self._window is not None and not self._fp8_window_walk:

@@ -810,6 +810,46 @@ int fino_fastercache_delta(const void* uncond, const void* cond, float* d_low, f
 int fino_fastercache_apply(const void* cond, const float* d_low, const float* d_high, float a_low, float a_high, void* out,
                            int64_t n, int dtype, void* stream);
 
+/* ---- region-adaptive sampling (frameino_amd/step_cache.py: RegionAdaptiveSamplingConfig) ---------------------------------
+ * The list of ACTIVE token rows of a partial forward, and whole rows moved by it.  No atomics, every sum in a fixed order:
+ * the same inputs give the same bits on every launch.  Every index read from a list is clamped into [0, n) before it is
+ * used: a bad list gives a wrong answer, never an access outside the indexed buffer (as the range and tile kernels clamp
+ * their tables).  Plain vector stores only.
+ *
+ * fino_token_score: po holds `batch` stacked [rows, cols] matrices of T (row r of element bi at po + (bi * rows + r) * ld
+ * elements).  One wave per token row r:
+ *   sd_bi = sqrt(mean_c (po[bi, r, c] - mean_c po[bi, r, c])^2)      (population standard deviation, fp32, two passes)
+ *   score[r] = ((sd_0 + sd_1 + ...) / batch) * expf(starvation_scale * counters[r])       (counters null: no factor)
+ * eligible (uint8 [rows], null: all 1): 0 -> score -inf, 2 -> score +inf, anything else the value above.
+ *
+ * fino_token_select: the k indices of the largest of score[0 .. n) -- ties go to the lower index; -0 counts as +0, a NaN as
+ * -inf -- written in ascending index order to idx_out[0 .. k); counters (int32 [n], may be null): 0 for a selected row,
+ * counter + 1 for every other.  One workgroup: a radix select (4 bits per pass) of the threshold on the ordered fp32 bit
+ * pattern, then an ordered compaction by prefix sum.  1 <= k <= n (FINO_ERR_ARG otherwise), n <= FINO_TOKEN_SELECT_MAX
+ * (FINO_ERR_UNSUPPORTED otherwise).
+ *
+ * fino_gather_rows: dst row r = src row idx[r] for r < k (src has n rows).  fino_scatter_rows: dst row idx[r] = src row r
+ * (dst has n rows; a list that names a row twice leaves either source there).  Rows of row_bytes bytes (a multiple of 4),
+ * strides in BYTES; 16-byte copies when row_bytes, both strides and both pointers are multiples of 16, else 4-byte ones.
+ *
+ * fino_qkv_rmsnorm_rope_rows: the arithmetic of fino_qkv_rmsnorm_rope (in place), bit for bit, on a COMPACT projection
+ * qkv [rows, 3 dim] whose row r is token idx[r] (idx null: token r) and whose cos_t / sin_t rows are already those of the
+ * compact rows: q and k are normed and rotated in place, and in the same launch the k bits just written go to
+ * kcache + idx[r] * ld_cache and row r's v to vcache + idx[r] * ld_cache (elements; planes of n rows).  T = dtype
+ * FINO_BF16 | FINO_F16; alignment as fino_qkv_rmsnorm_rope, the planes 16-byte aligned with ld_cache % 8 == 0. */
+enum { FINO_TOKEN_SELECT_MAX = 65536 };
+int fino_token_score(const void* po, int64_t rows, int cols, int64_t ld, int batch, const int32_t* counters,
+                     float starvation_scale, const uint8_t* eligible, float* score_out, int dtype, void* stream);
+int fino_token_select(const float* score, int64_t n, int64_t k, int32_t* idx_out, int32_t* counters, void* stream);
+int fino_gather_rows(const void* src, int64_t ld_src, int64_t n, const int32_t* idx, int64_t k, int64_t row_bytes, void* dst,
+                     int64_t ld_dst, void* stream);
+int fino_scatter_rows(const void* src, int64_t ld_src, const int32_t* idx, int64_t k, int64_t row_bytes, void* dst,
+                      int64_t ld_dst, int64_t n, void* stream);
+int fino_qkv_rmsnorm_rope_rows(void* qkv, int64_t rows, int dim, int64_t ldx, const void* q_weight, float q_eps,
+                               const void* k_weight, float k_eps, const float* cos_t, const float* sin_t, int head_dim,
+                               float q_out_scale, const int32_t* idx, int64_t n, void* kcache, void* vcache, int64_t ld_cache,
+                               int dtype, void* stream);
+
 /* ---- diagnostics (tools/ only) --------------------------------------------------------------------------------
  * Dense MFMA rate with nothing else running: `iters` x 16 independent 32x32x16 (kind 0) / 32 independent 16x16x32
  * (kind 1) bf16 MFMAs per wave from registers -- or (kind 2) 16 block-scaled fp8 MFMAs 32x32x64 on e4m3 operands with unit scales,
