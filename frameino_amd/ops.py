@@ -1148,9 +1148,10 @@ def rmsnorm_silu_cl_f32(x, gamma, c_valid, silu=True, split=None, nplanes=3):
 
 
 def conv3d_split_cl(xp, w6, bias, kernel, nplanes, stride=(1, 1, 1), pad=(0, 0, 0), out_thw=None, upsample2x=False,
-                    residual=None):
+                    residual=None, out=None):
     """conv3d_cl on split operands: xp bf16 [T, H, W, nplanes * Cin_pad] (split_bf16 layout "planes"), w6 bf16 [Cout_pad,
-    taps * products * Cin_pad] (W planes of the products per tap), bias fp32 [Cout_pad], residual fp32 -> fp32 [To, Ho, Wo, Cout_pad]"""
+    taps * products * Cin_pad] (W planes of the products per tap), bias fp32 [Cout_pad], residual fp32 -> fp32 [To, Ho, Wo, Cout_pad]
+    (into `out` if given: contiguous fp32 of that shape)"""
     assert xp.dim() == 4 and xp.is_contiguous() and w6.is_contiguous() and xp.dtype == torch.bfloat16 and w6.dtype == torch.bfloat16
     t, h, w, cw = xp.shape
     cin = cw // nplanes
@@ -1164,7 +1165,9 @@ def conv3d_split_cl(xp, w6, bias, kernel, nplanes, stride=(1, 1, 1), pad=(0, 0, 
         out_thw = ((t + pad[0] - kt) // stride[0] + 1, (h * up + 2 * pad[1] - kh) // stride[1] + 1,
                    (w * up + 2 * pad[2] - kw) // stride[2] + 1)
     to, ho, wo = out_thw
-    out = torch.empty((to, ho, wo, cout), dtype=torch.float32, device=xp.device)
+    if out is None:
+        out = torch.empty((to, ho, wo, cout), dtype=torch.float32, device=xp.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (to, ho, wo, cout)
     if residual is not None:
         assert residual.dtype == torch.float32 and residual.is_contiguous() and residual.shape == out.shape
     ev = _timed("conv3d")
