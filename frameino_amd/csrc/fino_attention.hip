@@ -37,7 +37,7 @@ extern "C" int fino_attn_debug_read(unsigned long long* out) {
 #define ASTAMP(V_)
 #endif
 
-#include "fino_attention_common.h"
+#include "fino_attention_host.h"
 using namespace fino_attn_ns;
 
 namespace {
@@ -107,14 +107,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParam
 
     // ---- Q fragments (B operand of S^T = K.Q^T): lane holds Q[q0 + r][16*ks + 8h .. +7] ----
     const int qrow = qb * kQBlock + wave * kQRowsPerWave + r;
-    const int qrow_c = qrow < p.lq ? qrow : p.lq - 1;
-    vec8 qf[kKS];
-#pragma unroll
-    for (int ks = 0; ks < kKS; ++ks) {
-        uint4 u = *reinterpret_cast<const uint4*>(qp + (int64_t)qrow_c * p.q_rs + 16 * ks + 8 * h);
-        if (qrow >= p.lq) u = make_uint4(0, 0, 0, 0);      // rows past Lq are never stored: zero operands draw the least power
-        qf[ks] = __builtin_bit_cast(vec8, u);
-    }
+    ATTN_LOAD_Q()
 
 #ifdef FINO_ATTN_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -216,15 +209,6 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParam
             if (key_ + 32 >= lk) sc1[j_] = -INFINITY;                                                       \
         }                                                                                                   \
     }
-    // row max of 8 accumulator registers (one of four independent chains).  v_max3_f32 through asm: fmaxf on MFMA
-    // results makes the compiler canonicalise every input first (32 extra v_max_f32 per tile).
-#define MAX8(S_, O_) vmax2(vmax3(vmax3(S_[O_], S_[O_ + 1], S_[O_ + 2]), vmax3(S_[O_ + 3], S_[O_ + 4], S_[O_ + 5]), \
-                                 S_[O_ + 6]), S_[O_ + 7])
-#define MAX_FINISH1(MX_, OUT_)                                                                              \
-    {                                                                                                       \
-        const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(MX_), __float_as_uint(MX_), false, false); \
-        OUT_ = vmax2(__uint_as_float(sw_[0]), __uint_as_float(sw_[1]));                                     \
-    }
     float mx_next;
     {
         MASK_RAGGED(0)
@@ -244,7 +228,6 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParam
     uint32_t ka0 = 1 * kTileBytes + k_lds_off<D>(r, h);
     uint32_t vl0 = 2 * kTileBytes + lds_off<D>(4 * h + tq, 2 * g1 + (tp >> 1)) + 8 * (tp & 1);
     uint32_t vh0 = 2 * kTileBytes + lds_off<D>(4 * h + tq + 8, 2 * g1 + (tp >> 1)) + 8 * (tp & 1);
-#define LDS_PTR(TYPE_, ADDR_) ((FINO_LDS TYPE_*)(uintptr_t)(uint32_t)(ADDR_))
 
     // Ping-pong: per key tile every wave alternates a SOFTMAX phase (VALU: max, exp2, sums, bf16 packing; plus its
     // share of the K/V staging) with a MATRIX phase (32 MFMAs: S(t+1) = K(t+1).Q^T and O^T += V(t)^T.P(t)^T, LDS
@@ -260,20 +243,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParam
         const int w = t + grp;                      // tile whose V (and K of the next) this group stages now
         if (w >= 1) { PP_WRITE(w) }
         ASTAMP(tsa)
-        {
-            // deferred rescale (threshold rescale_thr<T>()): O, l and m move together, between tiles.  mx_next = row max of
-            // this tile's S, computed in the shadow of the previous matrix phase's P.V MFMAs.
-            const float m_cand = fmaxf(m_run, mx_next * c2);
-            if (__any((m_cand - m_run) > rescale_thr<T>())) {
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_cand);
-                m_run = m_cand;
-                l_run *= alpha;
-#pragma unroll
-                for (int i = 0; i < kDT; ++i)
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) o[i][j] *= alpha;
-            }
-        }
+        // mx_next = row max of this tile's S, computed in the shadow of the previous matrix phase's P.V MFMAs
+        ATTN_RESCALE()
         ASTAMP(tsb)
         // p = exp2(c.s - m).  Scalar fp32 on purpose: v_pk_fma_f32 / v_pk_add_f32 measured ~2x SLOWER per element here.
 #pragma unroll
@@ -283,32 +254,10 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParam
         }
         ASTAMP(tsc)
         PP_LOAD(w + 1)                               // spaced from the ds_writes above by the exp block
-        {
-            float psum0 = 0.f, psum1 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                psum0 += sc0[j];
-                psum1 += sc1[j];
-            }
-            l_run += psum0 + psum1;
-        }
+        ATTN_ROWSUM()
         vec8 pb[4];                                  // P(t) packed: pb[2*kt + s2]
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            pb[0][j] = (typename T::scalar)sc0[j];
-            pb[1][j] = (typename T::scalar)sc0[8 + j];
-            pb[2][j] = (typename T::scalar)sc1[j];
-            pb[3][j] = (typename T::scalar)sc1[8 + j];
-        }
-        // the whole softmax belongs to THIS phase: pin its results in registers here (pure arithmetic would otherwise
-        // be sunk past the barrier into the matrix phase, next to its first use)
-        {
-            u32x4_t p0 = __builtin_bit_cast(u32x4_t, pb[0]), p1 = __builtin_bit_cast(u32x4_t, pb[1]);
-            u32x4_t p2 = __builtin_bit_cast(u32x4_t, pb[2]), p3 = __builtin_bit_cast(u32x4_t, pb[3]);
-            asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3), "+v"(l_run));
-            pb[0] = __builtin_bit_cast(vec8, p0); pb[1] = __builtin_bit_cast(vec8, p1);
-            pb[2] = __builtin_bit_cast(vec8, p2); pb[3] = __builtin_bit_cast(vec8, p3);
-        }
+        ATTN_PACK_P()
+        ATTN_PIN_P()
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         ASTAMP(ts1)
@@ -319,9 +268,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParam
         // 12 stages: 8 k-steps of S(t+1) (2 K row reads + 2 MFMAs each), then 4 key groups of P.V (8 transposed V reads
         // + 4 MFMAs each).  A stage's LDS reads are issued two (K) / one (V) stages ahead of its MFMAs, pinned by
         // sched_barrier, so every MFMA finds its operands in registers.
-#ifndef FINO_ATTN_NOPRIO
         __builtin_amdgcn_s_setprio(1);               // the matrix-phase wave wins issue arbitration on its SIMD
-#endif
         u32x4_t ka[3][2];
         s16x4_t vlo[2][kDT], vhi[2][kDT];
 #define LOADK(KS_, B_)                                                                                      \
@@ -373,9 +320,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParam
         ka0 ^= kTileBytes;
         vl0 ^= kTileBytes;
         vh0 ^= kTileBytes;
-#ifndef FINO_ATTN_NOPRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         ASTAMP(ts3)
@@ -401,10 +346,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParam
 #undef QK_TILE
 #undef PP_LOAD
 #undef PP_WRITE
-#undef LDS_PTR
 #undef MASK_RAGGED
-#undef MAX8
-#undef MAX_FINISH1
 
     // ---------------- epilogue: normalise, store O[q][d] ----------------
     {
@@ -423,21 +365,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParam
         continue;
     }
     const float inv = 1.0f / l_run;
-    if (qrow < p.lq) {
-        uint16_t* orow = op + (int64_t)qrow * p.o_rs;
-#pragma unroll
-        for (int dt = 0; dt < kDT; ++dt) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d0 = dt * 32 + 8 * g + 4 * h;
-                uint32_t w0 = (uint32_t)T::from_f32(o[dt][4 * g + 0] * inv) |
-                              ((uint32_t)T::from_f32(o[dt][4 * g + 1] * inv) << 16);
-                uint32_t w1 = (uint32_t)T::from_f32(o[dt][4 * g + 2] * inv) |
-                              ((uint32_t)T::from_f32(o[dt][4 * g + 3] * inv) << 16);
-                *reinterpret_cast<uint2*>(orow + d0) = make_uint2(w0, w1);
-            }
-        }
-    }
+    ATTN_STORE_O()
 #ifdef FINO_ATTN_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ASTAMP(wg_ts[5])
@@ -457,26 +385,61 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_pp_kernel(const AttnParam
 //   K(j) is last read by group 1's matrix(j-1) (global phase 2j), V(j) by its matrix(j) (phase 2j+2); group g issues, in its
 //   softmax(t) (phase 2t+g), K(t+g+3) into the slot of K(t+g-1) and V(t+g+2) into the slot of V(t+g-2): both dead by then;
 //   every wave ends a softmax phase with vmcnt(4) -- everything it issued before this phase (4 DMAs per phase) has landed --
-//   so a tile is published a whole phase before its first reader, whose first K fragments are fetched across the barrier
-//   (PD_PREK; vmcnt(8) without it).  In the matrix phase the LDS reads are issued BETWEEN the MFMAs that shadow them: an
-//   in-order wave issues nothing while its MFMA waits for the pipe, so reads queued behind a run of MFMAs would start late.
-//   The row maxima of S(t) open softmax(t) (out of the P.V shadow, where they delayed MFMAs), waves 4-7 run at static
-//   priority 1, and the output rows leave through LDS as whole 256-byte rows (attn_rows_through_lds).
+//   so a tile is published a whole phase before its first reader, whose first K fragments are fetched across the barrier.
+//   In the matrix phase the LDS reads are issued BETWEEN the MFMAs that shadow them: an in-order wave issues nothing while
+//   its MFMA waits for the pipe, so reads queued behind a run of MFMAs would start late.  The row maxima of S(t) open
+//   softmax(t) (out of the P.V shadow, where they delayed MFMAs), waves 4-7 run at static priority 1 (the A/B of these
+//   three choices: profiles/r04_attn_ppd_variants.txt), and the output rows leave through LDS as whole 256-byte rows
+//   (attn_rows_through_lds).
 // Every LDS read of the loop is inline asm with hand-counted lgkmcnt waits (the compiler would put vmcnt(0) in front of any
 // LDS read it can see while a DMA is in flight, see attn_fr_kernel).  Block map, tail split, partial layout and arithmetic
 // are attn_pp_kernel's: results are bit-identical (tests/test_kernels_gpu.py).
 constexpr int kPdSlots = 4;
 
-// A/B knobs of attn_ppd_kernel (make variant VFLAGS=-DPD_...=x; results are the same bits for every setting):
-#ifndef PD_PREK
-#define PD_PREK 1          /* 1: the first two k-steps' K fragments are fetched BEFORE the barrier that opens the matrix phase */
-#endif
-#ifndef PD_PRIO
-#define PD_PRIO 1          /* 0: s_setprio 1 around every matrix phase; 1: static priority for waves 4-7, no flips; 2: none */
-#endif
-#ifndef PD_MAX_SOFTMAX
-#define PD_MAX_SOFTMAX 1   /* 1: the row maxima of S(t) open softmax(t) instead of riding in the P.V shadow of matrix(t-1) */
-#endif
+// The pieces of attn_ppd_kernel's and attn_ppw_kernel's matrix phase.  Both kernels name what these read and write the same:
+// ka0 / vl0 / vh0 (LDS fragment addresses), ka, vlo / vhi (fragments), qf, pb, sc0 / sc1, o, zero16.
+#define PD_KISSUE(KS_, B_)                                                                                   \
+    {                                                                                                        \
+        const uint32_t a_ = ka0 ^ ((KS_) << 5);                                                              \
+        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:%3"                                  \
+                     : "=&v"(ka[B_][0]), "=&v"(ka[B_][1]) : "v"(a_), "n"(32 * D * 2));                       \
+        __builtin_amdgcn_sched_barrier(0);                                                                   \
+    }
+#define PD_KWAIT(N_, B_) asm volatile("s_waitcnt lgkmcnt(" #N_ ")" : "+v"(ka[B_][0]), "+v"(ka[B_][1]));
+// one MFMA, then the reads its 32 cycles shadow -- an in-order wave issues nothing while its MFMA waits for the
+// pipe, so reads queued behind a run of MFMAs start late and the next run waits for them
+#define PD_A_S(KS_, B_, H_) __builtin_bit_cast(vec8, ka[B_][H_])
+#define PD_A_V(STEP_, B_, DT_) __builtin_bit_cast(vec8, __builtin_shufflevector(vlo[B_][DT_], vhi[B_][DT_], 0, 1, 2, 3, 4, 5, 6, 7))
+#define PD_MF0(KS_, B_, FIRST_)                                                                              \
+    sc0 = T::mfma32(PD_A_S(KS_, B_, 0), qf[KS_], (FIRST_) ? zero16 : sc0);                                   \
+    __builtin_amdgcn_sched_barrier(0);
+#define PD_MF1(KS_, B_, FIRST_)                                                                              \
+    sc1 = T::mfma32(PD_A_S(KS_, B_, 1), qf[KS_], (FIRST_) ? zero16 : sc1);                                   \
+    __builtin_amdgcn_sched_barrier(0);
+#define PD_VPAIR(STEP_, B_, DT_)                                                                             \
+    {                                                                                                        \
+        const uint32_t l_ = vl0 ^ ((DT_) << 6), h_ = vh0 ^ ((DT_) << 6);                                     \
+        asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4"            \
+                     : "=&v"(vlo[B_][DT_]), "=&v"(vhi[B_][DT_]) : "v"(l_), "v"(h_), "n"((STEP_) * 16 * D * 2)); \
+        __builtin_amdgcn_sched_barrier(0);                                                                   \
+    }
+#define PD_VW(N_, B_, DT_) asm volatile("s_waitcnt lgkmcnt(" #N_ ")" : "+v"(vlo[B_][DT_]), "+v"(vhi[B_][DT_]));
+#define PD_MFV(STEP_, B_, DT_)                                                                               \
+    {                                                                                                        \
+        o[DT_] = T::mfma32(PD_A_V(STEP_, B_, DT_), pb[STEP_], o[DT_]);                                       \
+        __builtin_amdgcn_sched_barrier(0);                                                                   \
+    }
+// one key step of P.V: d-tile DT_'s MFMA, then the next step's fragments for the same d-tile
+#define PD_PVSTEP(STEP_, B_, NB_, NSTEP_)                                                                    \
+    PD_VW(6, B_, 0) PD_MFV(STEP_, B_, 0) PD_VPAIR(NSTEP_, NB_, 0)                                            \
+    PD_VW(6, B_, 1) PD_MFV(STEP_, B_, 1) PD_VPAIR(NSTEP_, NB_, 1)                                            \
+    PD_VW(6, B_, 2) PD_MFV(STEP_, B_, 2) PD_VPAIR(NSTEP_, NB_, 2)                                            \
+    PD_VW(6, B_, 3) PD_MFV(STEP_, B_, 3) PD_VPAIR(NSTEP_, NB_, 3)
+// head_dim 64: two d-tiles per key step (4 reads in flight per step instead of 8)
+#define PD_PVSTEP64(STEP_, B_, NB_, NSTEP_)                                                                  \
+    PD_VW(2, B_, 0) PD_MFV(STEP_, B_, 0) PD_VPAIR(NSTEP_, NB_, 0)                                            \
+    PD_VW(2, B_, 1) PD_MFV(STEP_, B_, 1) PD_VPAIR(NSTEP_, NB_, 1)
+
 template <typename T, int D, int VAR>
 __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnParams p, const AttnTileMask tm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -666,14 +629,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
 
     // ---- Q fragments (B operand of S^T = K.Q^T): lane holds Q[q0 + r][16*ks + 8h .. +7] ----
     const int qrow = qb * kQBlock + wave * kQRowsPerWave + r;
-    const int qrow_c = qrow < p.lq ? qrow : p.lq - 1;
-    vec8 qf[kKS];
-#pragma unroll
-    for (int ks = 0; ks < kKS; ++ks) {
-        uint4 u = *reinterpret_cast<const uint4*>(qp + (int64_t)qrow_c * p.q_rs + 16 * ks + 8 * h);
-        if (qrow >= p.lq) u = make_uint4(0, 0, 0, 0);      // rows past Lq are never stored: zero operands draw the least power
-        qf[ks] = __builtin_bit_cast(vec8, u);
-    }
+    ATTN_LOAD_Q()
 
     const int tq = (lane & 15) >> 2;
     const int tp = lane & 3;
@@ -712,25 +668,9 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
             if (key_ + 32 >= lk) sc1[j_] = -INFINITY;                                                       \
         }                                                                                                   \
     }
-#define MAX8(S_, O_) vmax2(vmax3(vmax3(S_[O_], S_[O_ + 1], S_[O_ + 2]), vmax3(S_[O_ + 3], S_[O_ + 4], S_[O_ + 5]), \
-                                 S_[O_ + 6]), S_[O_ + 7])
-#define MAX_FINISH1(MX_, OUT_)                                                                              \
-    {                                                                                                       \
-        const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(MX_), __float_as_uint(MX_), false, false); \
-        OUT_ = vmax2(__uint_as_float(sw_[0]), __uint_as_float(sw_[1]));                                     \
-    }
     float mx_next = 0.f;
-#if !PD_MAX_SOFTMAX
-    {
-        MASK_RAGGED(0)
-        const float m0 = vmax2(vmax3(MAX8(sc0, 0), MAX8(sc0, 8), MAX8(sc1, 0)), MAX8(sc1, 8));
-        MAX_FINISH1(m0, mx_next)
-    }
-#endif
     if (grp == 1) __builtin_amdgcn_s_barrier();       // group 1 runs one phase behind group 0 from here on
-#if PD_PRIO == 1
     if (grp == 1) __builtin_amdgcn_s_setprio(1);      // the second-dispatched half loses every age arbitration otherwise
-#endif
 
     // LDS fragment addresses of the matrix phase: k-step / d-tile flip address bits (one v_xor next to the read), the
     // +32 / +16-row operands are instruction offsets, the ring slot (K: (t+1) & 3, V: t & 3) advances once per tile.
@@ -741,52 +681,6 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
 
     u32x4_t ka[3][2];
     s16x4_t vlo[2][kDT], vhi[2][kDT];
-#define PD_KISSUE(KS_, B_)                                                                                   \
-    {                                                                                                        \
-        const uint32_t a_ = ka0 ^ ((KS_) << 5);                                                              \
-        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:%3"                                  \
-                     : "=&v"(ka[B_][0]), "=&v"(ka[B_][1]) : "v"(a_), "n"(32 * D * 2));                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-    }
-#define PD_KWAIT(N_, B_) asm volatile("s_waitcnt lgkmcnt(" #N_ ")" : "+v"(ka[B_][0]), "+v"(ka[B_][1]));
-    // one MFMA, then the reads its 32 cycles shadow -- an in-order wave issues nothing while its MFMA waits for the
-    // pipe, so reads queued behind a run of MFMAs start late and the next run waits for them
-#define PD_A_S(KS_, B_, H_) __builtin_bit_cast(vec8, ka[B_][H_])
-#define PD_A_V(STEP_, B_, DT_) __builtin_bit_cast(vec8, __builtin_shufflevector(vlo[B_][DT_], vhi[B_][DT_], 0, 1, 2, 3, 4, 5, 6, 7))
-#define PD_MF0(KS_, B_, FIRST_)                                                                              \
-    sc0 = T::mfma32(PD_A_S(KS_, B_, 0), qf[KS_], (FIRST_) ? zero16 : sc0);                                   \
-    __builtin_amdgcn_sched_barrier(0);
-#define PD_MF1(KS_, B_, FIRST_)                                                                              \
-    sc1 = T::mfma32(PD_A_S(KS_, B_, 1), qf[KS_], (FIRST_) ? zero16 : sc1);                                   \
-    __builtin_amdgcn_sched_barrier(0);
-#define PD_VPAIR(STEP_, B_, DT_)                                                                             \
-    {                                                                                                        \
-        const uint32_t l_ = vl0 ^ ((DT_) << 6), h_ = vh0 ^ ((DT_) << 6);                                     \
-        asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4"            \
-                     : "=&v"(vlo[B_][DT_]), "=&v"(vhi[B_][DT_]) : "v"(l_), "v"(h_), "n"((STEP_) * 16 * D * 2)); \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-    }
-#define PD_VW(N_, B_, DT_) asm volatile("s_waitcnt lgkmcnt(" #N_ ")" : "+v"(vlo[B_][DT_]), "+v"(vhi[B_][DT_]));
-#define PD_MFV(STEP_, B_, DT_)                                                                               \
-    {                                                                                                        \
-        o[DT_] = T::mfma32(PD_A_V(STEP_, B_, DT_), pb[STEP_], o[DT_]);                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-    }
-    // one key step of P.V: d-tile DT_'s MFMA, then the next step's fragments for the same d-tile
-#define PD_PVSTEP(STEP_, B_, NB_, NSTEP_)                                                                    \
-    PD_VW(6, B_, 0) PD_MFV(STEP_, B_, 0) PD_VPAIR(NSTEP_, NB_, 0)                                            \
-    PD_VW(6, B_, 1) PD_MFV(STEP_, B_, 1) PD_VPAIR(NSTEP_, NB_, 1)                                            \
-    PD_VW(6, B_, 2) PD_MFV(STEP_, B_, 2) PD_VPAIR(NSTEP_, NB_, 2)                                            \
-    PD_VW(6, B_, 3) PD_MFV(STEP_, B_, 3) PD_VPAIR(NSTEP_, NB_, 3)
-    // head_dim 64: two d-tiles per key step (4 reads in flight per step instead of 8)
-#define PD_PVSTEP64(STEP_, B_, NB_, NSTEP_)                                                                  \
-    PD_VW(2, B_, 0) PD_MFV(STEP_, B_, 0) PD_VPAIR(NSTEP_, NB_, 0)                                            \
-    PD_VW(2, B_, 1) PD_MFV(STEP_, B_, 1) PD_VPAIR(NSTEP_, NB_, 1)
-#if PD_MAX_SOFTMAX
-#define PD_SHADOW_MAX(MAXEXPR_)
-#else
-#define PD_SHADOW_MAX(MAXEXPR_) mxa = vmax2(mxa, MAXEXPR_);
-#endif
 
 #ifdef FINO_ATTN_STAMP
     unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, tsm = 0, tse = 0, sa0 = 0, sa1 = 0, sa2 = 0, sa3 = 0, sa5 = 0, sa6 = 0;
@@ -798,61 +692,27 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
         const int w = t + grp;
         PD_DMA_K(w + 3)
         PD_DMA_V(w + 2)
-#if PD_MAX_SOFTMAX
         {
             MASK_RAGGED(t)
             const float m0 = vmax2(vmax3(MAX8(sc0, 0), MAX8(sc0, 8), MAX8(sc1, 0)), MAX8(sc1, 8));
             MAX_FINISH1(m0, mx_next)
         }
-#endif
-        {
-            const float m_cand = fmaxf(m_run, mx_next * c2);
-            if (__any((m_cand - m_run) > rescale_thr<T>())) {
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_cand);
-                m_run = m_cand;
-                l_run *= alpha;
-#pragma unroll
-                for (int i = 0; i < kDT; ++i)
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) o[i][j] *= alpha;
-            }
-        }
+        ATTN_RESCALE()
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             sc0[j] = __builtin_amdgcn_exp2f(sc0[j] * c2 - m_run);
             sc1[j] = __builtin_amdgcn_exp2f(sc1[j] * c2 - m_run);
         }
-        {
-            float psum0 = 0.f, psum1 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                psum0 += sc0[j];
-                psum1 += sc1[j];
-            }
-            l_run += psum0 + psum1;
-        }
+        ATTN_ROWSUM()
         vec8 pb[4];                                  // P(t) packed: pb[2*kt + s2]
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            pb[0][j] = (typename T::scalar)sc0[j];
-            pb[1][j] = (typename T::scalar)sc0[8 + j];
-            pb[2][j] = (typename T::scalar)sc1[j];
-            pb[3][j] = (typename T::scalar)sc1[8 + j];
-        }
-        {
-            u32x4_t p0 = __builtin_bit_cast(u32x4_t, pb[0]), p1 = __builtin_bit_cast(u32x4_t, pb[1]);
-            u32x4_t p2 = __builtin_bit_cast(u32x4_t, pb[2]), p3 = __builtin_bit_cast(u32x4_t, pb[3]);
-            asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3), "+v"(l_run));
-            pb[0] = __builtin_bit_cast(vec8, p0); pb[1] = __builtin_bit_cast(vec8, p1);
-            pb[2] = __builtin_bit_cast(vec8, p2); pb[3] = __builtin_bit_cast(vec8, p3);
-        }
+        ATTN_PACK_P()
+        ATTN_PIN_P()
         __builtin_amdgcn_sched_barrier(0);
         ASTAMP(tse)
         if constexpr (VAR == 3) {                    // g(w + 4) has had the whole softmax phase to arrive
             g3_v = g3_k;
             PD_LIST_WAIT(g3_k)
         }
-#if PD_PREK
         // K(t+1) was published a phase ago (vmcnt(4) below): the first two k-steps' fragments travel across the barrier
         if (t + 1 < nt) {
             PD_KISSUE(0, 0)
@@ -861,26 +721,14 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
         // all DMAs this wave issued before this phase (4 per phase) have landed
         if constexpr (kPW == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-#else
-        // all but this wave's last two phases' DMAs (4 per phase) have landed: its pieces of K(t+1) and V(t), at the latest
-        if constexpr (kPW == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-#endif
         ASTAMP(ts1)
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         ASTAMP(ts2)
         // ================= matrix phase =================
-#if PD_PRIO == 0
-        __builtin_amdgcn_s_setprio(1);
-#endif
         const f32x16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       if constexpr (D == 128) {
         if (t + 1 < nt) {
-#if !PD_PREK
-            PD_KISSUE(0, 0)
-            PD_KISSUE(1, 1)
-#endif
             PD_KWAIT(2, 0) PD_MF0(0, 0, true) PD_KISSUE(2, 2) PD_MF1(0, 0, true)
             PD_KWAIT(2, 1) PD_MF0(1, 1, false) PD_KISSUE(3, 0) PD_MF1(1, 1, false)
             PD_KWAIT(2, 2) PD_MF0(2, 2, false) PD_KISSUE(4, 1) PD_MF1(2, 2, false)
@@ -893,27 +741,15 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
             PD_VPAIR(0, 0, 0) PD_VPAIR(0, 0, 1) PD_VPAIR(0, 0, 2) PD_VPAIR(0, 0, 3)
         }
         ASTAMP(tsm)
-#if !PD_MAX_SOFTMAX
-        MASK_RAGGED(t + 1)
-        float mxa = -INFINITY;
-#endif
         PD_PVSTEP(0, 0, 1, 1)
-        PD_SHADOW_MAX(MAX8(sc0, 0))
         PD_PVSTEP(1, 1, 0, 2)
-        PD_SHADOW_MAX(MAX8(sc0, 8))
         PD_PVSTEP(2, 0, 1, 3)
-        PD_SHADOW_MAX(MAX8(sc1, 0))
         PD_VW(6, 1, 0) PD_MFV(3, 1, 0)
         PD_VW(4, 1, 1) PD_MFV(3, 1, 1)
         PD_VW(2, 1, 2) PD_MFV(3, 1, 2)
         PD_VW(0, 1, 3) PD_MFV(3, 1, 3)
-        PD_SHADOW_MAX(MAX8(sc1, 8))
       } else {                                     // head_dim 64: 4 k-steps of S, 4 key steps x 2 d-tiles of P.V
         if (t + 1 < nt) {
-#if !PD_PREK
-            PD_KISSUE(0, 0)
-            PD_KISSUE(1, 1)
-#endif
             PD_KWAIT(2, 0) PD_MF0(0, 0, true) PD_KISSUE(2, 2) PD_MF1(0, 0, true)
             PD_KWAIT(2, 1) PD_MF0(1, 1, false) PD_KISSUE(3, 0) PD_MF1(1, 1, false)
             PD_KWAIT(2, 2) PD_MF0(2, 2, false) PD_VPAIR(0, 0, 0) PD_VPAIR(0, 0, 1) PD_MF1(2, 2, false)
@@ -922,32 +758,15 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
             PD_VPAIR(0, 0, 0) PD_VPAIR(0, 0, 1)
         }
         ASTAMP(tsm)
-#if !PD_MAX_SOFTMAX
-        MASK_RAGGED(t + 1)
-        float mxa = -INFINITY;
-#endif
         PD_PVSTEP64(0, 0, 1, 1)
-        PD_SHADOW_MAX(MAX8(sc0, 0))
         PD_PVSTEP64(1, 1, 0, 2)
-        PD_SHADOW_MAX(MAX8(sc0, 8))
         PD_PVSTEP64(2, 0, 1, 3)
-        PD_SHADOW_MAX(MAX8(sc1, 0))
         PD_VW(2, 1, 0) PD_MFV(3, 1, 0)
         PD_VW(0, 1, 1) PD_MFV(3, 1, 1)
-        PD_SHADOW_MAX(MAX8(sc1, 8))
-#if !PD_MAX_SOFTMAX
-        MAX_FINISH1(mxa, mx_next)
-#endif
       }
-#if !PD_MAX_SOFTMAX
-        MAX_FINISH1(mxa, mx_next)
-#endif
         ka0 = (ka0 + kTileBytes) & kRingMask;
         vl0 = ((vl0 + kTileBytes) & kRingMask) | kVBase;
         vh0 = ((vh0 + kTileBytes) & kRingMask) | kVBase;
-#if PD_PRIO == 0
-        __builtin_amdgcn_s_setprio(0);
-#endif
         __builtin_amdgcn_sched_barrier(0);
         ASTAMP(ts3)
         __builtin_amdgcn_s_barrier();
@@ -964,9 +783,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
         fino_attn_dbg[wave * 8 + 5] = sa5; fino_attn_dbg[wave * 8 + 6] = sa6; fino_attn_dbg[wave * 8 + 7] = 0;
     }
 #endif
-#if PD_PRIO == 1
     __builtin_amdgcn_s_setprio(0);
-#endif
     if (grp == 0) __builtin_amdgcn_s_barrier();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the look-ahead DMAs past the last tile (zeros) have landed too ...
     __builtin_amdgcn_s_barrier();                      // ... for EVERY wave: the epilogue stages its output rows in the rings
@@ -977,21 +794,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppd_kernel(const AttnPara
 #undef PD_LIST_ISSUE
 #undef PD_LIST_WAIT
 #undef PD_GTILE
-#undef PD_KISSUE
-#undef PD_KWAIT
-#undef PD_SHADOW_MAX
-#undef PD_MF0
-#undef PD_A_S
-#undef PD_A_V
-#undef PD_MF1
-#undef PD_VPAIR
-#undef PD_VW
-#undef PD_MFV
-#undef PD_PVSTEP
-#undef PD_PVSTEP64
 #undef MASK_RAGGED
-#undef MAX8
-#undef MAX_FINISH1
 
     // ---------------- epilogue: normalise, store O[q][d] (as attn_pp_kernel) ----------------
     {
@@ -1202,8 +1005,6 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppw_kernel(const AttnPara
             sc1 = T::mfma32(__builtin_bit_cast(vec8, a1), qf[ks], sc1);
         }
     }
-#define MAX8(S_, O_) vmax2(vmax3(vmax3(S_[O_], S_[O_ + 1], S_[O_ + 2]), vmax3(S_[O_ + 3], S_[O_ + 4], S_[O_ + 5]), \
-                                 S_[O_ + 6]), S_[O_ + 7])
     float mx_next = 0.f;
     if (grp == 1) __builtin_amdgcn_s_barrier();       // group 1 runs one phase behind group 0 from here on
     if (grp == 1) __builtin_amdgcn_s_setprio(1);      // the second-dispatched half loses every age arbitration otherwise
@@ -1215,39 +1016,6 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppw_kernel(const AttnPara
 
     u32x4_t ka[3][2];
     s16x4_t vlo[2][kDT], vhi[2][kDT];
-#define PD_KISSUE(KS_, B_)                                                                                   \
-    {                                                                                                        \
-        const uint32_t a_ = ka0 ^ ((KS_) << 5);                                                              \
-        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:%3"                                  \
-                     : "=&v"(ka[B_][0]), "=&v"(ka[B_][1]) : "v"(a_), "n"(32 * D * 2));                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-    }
-#define PD_KWAIT(N_, B_) asm volatile("s_waitcnt lgkmcnt(" #N_ ")" : "+v"(ka[B_][0]), "+v"(ka[B_][1]));
-#define PD_MF0(KS_, B_, FIRST_)                                                                              \
-    sc0 = T::mfma32(__builtin_bit_cast(vec8, ka[B_][0]), qf[KS_], (FIRST_) ? zero16 : sc0);                  \
-    __builtin_amdgcn_sched_barrier(0);
-#define PD_MF1(KS_, B_, FIRST_)                                                                              \
-    sc1 = T::mfma32(__builtin_bit_cast(vec8, ka[B_][1]), qf[KS_], (FIRST_) ? zero16 : sc1);                  \
-    __builtin_amdgcn_sched_barrier(0);
-#define PD_VPAIR(STEP_, B_, DT_)                                                                             \
-    {                                                                                                        \
-        const uint32_t l_ = vl0 ^ ((DT_) << 6), h_ = vh0 ^ ((DT_) << 6);                                     \
-        asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4"            \
-                     : "=&v"(vlo[B_][DT_]), "=&v"(vhi[B_][DT_]) : "v"(l_), "v"(h_), "n"((STEP_) * 16 * D * 2)); \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-    }
-#define PD_VW(N_, B_, DT_) asm volatile("s_waitcnt lgkmcnt(" #N_ ")" : "+v"(vlo[B_][DT_]), "+v"(vhi[B_][DT_]));
-#define PD_MFV(STEP_, B_, DT_)                                                                               \
-    {                                                                                                        \
-        o[DT_] = T::mfma32(__builtin_bit_cast(vec8, __builtin_shufflevector(vlo[B_][DT_], vhi[B_][DT_], 0, 1, 2, 3, 4, 5, 6, 7)), \
-                           pb[STEP_], o[DT_]);                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                                   \
-    }
-#define PD_PVSTEP(STEP_, B_, NB_, NSTEP_)                                                                    \
-    PD_VW(6, B_, 0) PD_MFV(STEP_, B_, 0) PD_VPAIR(NSTEP_, NB_, 0)                                            \
-    PD_VW(6, B_, 1) PD_MFV(STEP_, B_, 1) PD_VPAIR(NSTEP_, NB_, 1)                                            \
-    PD_VW(6, B_, 2) PD_MFV(STEP_, B_, 2) PD_VPAIR(NSTEP_, NB_, 2)                                            \
-    PD_VW(6, B_, 3) PD_MFV(STEP_, B_, 3) PD_VPAIR(NSTEP_, NB_, 3)
 
     Pos np = cp;                                       // the block whose Q rows are in qn
     for (int t = 0; t < TT; ++t) {
@@ -1282,50 +1050,18 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppw_kernel(const AttnPara
                 }
             }
             const float m0 = vmax2(vmax3(MAX8(sc0, 0), MAX8(sc0, 8), MAX8(sc1, 0)), MAX8(sc1, 8));
-            const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(m0), __float_as_uint(m0), false, false);
-            mx_next = vmax2(__uint_as_float(sw_[0]), __uint_as_float(sw_[1]));
+            MAX_FINISH1(m0, mx_next)
         }
-        {
-            const float m_cand = fmaxf(m_run, mx_next * c2);
-            if (__any((m_cand - m_run) > rescale_thr<T>())) {
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_cand);
-                m_run = m_cand;
-                l_run *= alpha;
-#pragma unroll
-                for (int i = 0; i < kDT; ++i)
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) o[i][j] *= alpha;
-            }
-        }
+        ATTN_RESCALE()
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             sc0[j] = __builtin_amdgcn_exp2f(sc0[j] * c2 - m_run);
             sc1[j] = __builtin_amdgcn_exp2f(sc1[j] * c2 - m_run);
         }
-        {
-            float psum0 = 0.f, psum1 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                psum0 += sc0[j];
-                psum1 += sc1[j];
-            }
-            l_run += psum0 + psum1;
-        }
+        ATTN_ROWSUM()
         vec8 pb[4];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            pb[0][j] = (typename T::scalar)sc0[j];
-            pb[1][j] = (typename T::scalar)sc0[8 + j];
-            pb[2][j] = (typename T::scalar)sc1[j];
-            pb[3][j] = (typename T::scalar)sc1[8 + j];
-        }
-        {
-            u32x4_t p0 = __builtin_bit_cast(u32x4_t, pb[0]), p1 = __builtin_bit_cast(u32x4_t, pb[1]);
-            u32x4_t p2 = __builtin_bit_cast(u32x4_t, pb[2]), p3 = __builtin_bit_cast(u32x4_t, pb[3]);
-            asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3), "+v"(l_run));
-            pb[0] = __builtin_bit_cast(vec8, p0); pb[1] = __builtin_bit_cast(vec8, p1);
-            pb[2] = __builtin_bit_cast(vec8, p2); pb[3] = __builtin_bit_cast(vec8, p3);
-        }
+        ATTN_PACK_P()
+        ATTN_PIN_P()
         __builtin_amdgcn_sched_barrier(0);
         // Everything this wave issued before the PREVIOUS softmax phase has landed (a block's output stores get two tiles to be
         // acknowledged: all CUs reach their block boundaries together, 16 MB of stores at once); before a block's last matrix
@@ -1407,16 +1143,18 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_ppw_kernel(const AttnPara
 #undef PW_DMA_V
 #undef PW_LOAD_Q
 #undef PW_TAKE_Q
+}
 #undef PD_KISSUE
 #undef PD_KWAIT
 #undef PD_MF0
+#undef PD_A_S
+#undef PD_A_V
 #undef PD_MF1
 #undef PD_VPAIR
 #undef PD_VW
 #undef PD_MFV
 #undef PD_PVSTEP
-#undef MAX8
-}
+#undef PD_PVSTEP64
 
 // Merge the key-range partials of each tail block: m = max m_s, O = sum O_s 2^(m_s-m), l likewise; store bf16.
 // grid = (8 * rem_x, D / 32): one workgroup per (tail block, 32-column d-tile) -- a block's 64 KB of fp32 partials per
@@ -1629,14 +1367,7 @@ __global__ __launch_bounds__(kFrWaves * 64, D == 64 ? 3 : 2) void attn_fr_kernel
 
     // ---- Q fragments (B operand of S^T = K.Q^T): lane holds Q[q0 + r][16*ks + 8h .. +7] ----
     const int qrow = qb * kFrQBlock + wave * kQRowsPerWave + r;
-    const int qrow_c = qrow < p.lq ? qrow : p.lq - 1;
-    vec8 qf[kKS];
-#pragma unroll
-    for (int ks = 0; ks < kKS; ++ks) {
-        uint4 u = *reinterpret_cast<const uint4*>(qp + (int64_t)qrow_c * p.q_rs + 16 * ks + 8 * h);
-        if (qrow >= p.lq) u = make_uint4(0, 0, 0, 0);
-        qf[ks] = __builtin_bit_cast(vec8, u);
-    }
+    ATTN_LOAD_Q()
 
     const int tq = (lane & 15) >> 2;
     const int tp = lane & 3;
@@ -1651,7 +1382,6 @@ __global__ __launch_bounds__(kFrWaves * 64, D == 64 ? 3 : 2) void attn_fr_kernel
     const float c2 = p.scale_log2;
 
     if ((uint32_t)(uintptr_t)(FINO_LDS char*)smem != 0u) __builtin_trap();
-#define LDS_PTR(TYPE_, ADDR_) ((FINO_LDS TYPE_*)(uintptr_t)(uint32_t)(ADDR_))
     uint32_t ka0 = k_lds_off<D>(r, h);                                       // K ring slot 0 first (S(0)), then toggled
     uint32_t vl0 = 2 * kTileBytes + lds_off<D>(4 * h + tq, 2 * g1 + (tp >> 1)) + 8 * (tp & 1);
     uint32_t vh0 = 2 * kTileBytes + lds_off<D>(4 * h + tq + 8, 2 * g1 + (tp >> 1)) + 8 * (tp & 1);
@@ -1734,40 +1464,15 @@ __global__ __launch_bounds__(kFrWaves * 64, D == 64 ? 3 : 2) void attn_fr_kernel
         // K(t+2) into the slot K(t) left, V(t+1) into the slot V(t-1) left: a whole tile of compute to land under
         FR_DMA_K(t + 2, t & 1)
         FR_DMA_V(t + 1, (t + 1) & 1)
-        {
-            const float m_cand = fmaxf(m_run, mx_next * c2);
-            if (__any((m_cand - m_run) > rescale_thr<T>())) {
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_cand);
-                m_run = m_cand;
-                l_run *= alpha;
-#pragma unroll
-                for (int i = 0; i < kDT; ++i)
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) o[i][j] *= alpha;
-            }
-        }
+        ATTN_RESCALE()
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             sc0[j] = __builtin_amdgcn_exp2f(sc0[j] * c2 - m_run);
             sc1[j] = __builtin_amdgcn_exp2f(sc1[j] * c2 - m_run);
         }
-        {
-            float psum0 = 0.f, psum1 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                psum0 += sc0[j];
-                psum1 += sc1[j];
-            }
-            l_run += psum0 + psum1;
-        }
+        ATTN_ROWSUM()
         vec8 pb[4];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            pb[0][j] = (typename T::scalar)sc0[j];
-            pb[1][j] = (typename T::scalar)sc0[8 + j];
-            pb[2][j] = (typename T::scalar)sc1[j];
-            pb[3][j] = (typename T::scalar)sc1[8 + j];
-        }
+        ATTN_PACK_P()
         // S(t+1) for every t: past the last tile the K slot holds the zeros of an out-of-range DMA and the result is dropped
         FR_QK()
         FR_MASK(t + 1)
@@ -1816,28 +1521,13 @@ __global__ __launch_bounds__(kFrWaves * 64, D == 64 ? 3 : 2) void attn_fr_kernel
 #undef FR_QK
 #undef FR_MASK
 #undef FR_ROWMAX
-#undef LDS_PTR
 
     {
         const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
         l_run = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
     }
     const float inv = 1.0f / l_run;
-    if (qrow < p.lq) {
-        uint16_t* orow = op + (int64_t)qrow * p.o_rs;
-#pragma unroll
-        for (int dt = 0; dt < kDT; ++dt) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d0 = dt * 32 + 8 * g + 4 * h;
-                uint32_t w0 = (uint32_t)T::from_f32(o[dt][4 * g + 0] * inv) |
-                              ((uint32_t)T::from_f32(o[dt][4 * g + 1] * inv) << 16);
-                uint32_t w1 = (uint32_t)T::from_f32(o[dt][4 * g + 2] * inv) |
-                              ((uint32_t)T::from_f32(o[dt][4 * g + 3] * inv) << 16);
-                *reinterpret_cast<uint2*>(orow + d0) = make_uint2(w0, w1);
-            }
-        }
-    }
+    ATTN_STORE_O()
 }
 
 template <typename T, int D>
@@ -1847,10 +1537,7 @@ int launch_attn_fr(AttnParams p, hipStream_t st) {
     if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&attn_fr_kernel<T, D>), smem, "fino_attn_fwd")) return rc;
     p.nqb = (p.lq + kFrQBlock - 1) / kFrQBlock;
     p.ws = nullptr; p.all_partial = 0;
-    attn_virtual_heads(p.batch, p.heads, p.nqb, p.vsplit, p.nqb_v);
-    const int groups = (p.batch * p.heads * p.vsplit + 7) / 8;
-    p.full_x = groups * p.nqb_v; p.rem_x = 0; p.nwg = 0; p.per = 1;
-    attn_fr_kernel<T, D><<<dim3((unsigned)(8 * p.full_x)), kFrWaves * 64, smem, st>>>(p);
+    attn_fr_kernel<T, D><<<dim3(attn_whole_blocks(p)), kFrWaves * 64, smem, st>>>(p);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }
@@ -1881,11 +1568,7 @@ int launch_attn_v(AttnParams p, int64_t ws_bytes, hipStream_t st) {
         if constexpr (D == 128) {
             const int nt = (p.lk + kKV - 1) / kKV;
             const int64_t blocks = (int64_t)p.batch * p.heads * p.nqb;
-            auto span = [&](int64_t bs, int64_t hs, int64_t rs, int64_t rows) {
-                return (((int64_t)p.batch - 1) * bs + ((int64_t)p.heads - 1) * hs + (rows - 1 + 2 * kKV) * rs + 128) * 2;
-            };
-            const bool can = !p.all_partial && nt >= 2 && blocks < (1 << 24) && span(p.k_bs, p.k_hs, p.k_rs, p.lk) < (1ll << 31) &&
-                             span(p.v_bs, p.v_hs, p.v_rs, p.lk) < (1ll << 31) && span(p.o_bs, p.o_hs, p.o_rs, p.lq) < (1ll << 31);
+            const bool can = !p.all_partial && nt >= 2 && blocks < (1 << 24) && attn_spans_fit(p);
             if (can && (tk == 6 || (tk == 0 && VAR == 1 && blocks >= 2 * device_cus()))) return launch_attn_ppw<T>(p, st);
         }
         // the free-running kernel exists for head_dim 128 only (at head_dim 64 it lost to the 4-wave kernel and left in round 5)
@@ -1895,9 +1578,8 @@ int launch_attn_v(AttnParams p, int64_t ws_bytes, hipStream_t st) {
     static FinoPerDeviceOnce once_b;
     if (int rc = fino_max_smem_once(once_b, reinterpret_cast<const void*>(&attn_pp_kernel<T, D, VAR>), smem, "fino_attn_fwd"))
         return rc;
-    attn_virtual_heads(p.batch, p.heads, p.nqb, p.vsplit, p.nqb_v);
-    const int groups = (p.batch * p.heads * p.vsplit + 7) / 8;
-    SplitPlan sp{groups * p.nqb_v, 0, 0, 1};
+    attn_whole_blocks(p);                              // every block whole -- all_partial: every block is a partial anyway --
+    SplitPlan sp{p.full_x, 0, 0, 1};                   // unless there is a workspace for the tail split's
     if (p.ws && !p.all_partial) {
         sp = plan_split(p.batch, p.heads, p.nqb, (p.lk + kKV - 1) / kKV);
         const int64_t need = (int64_t)8 * sp.nwg * 2 * partial_floats<D>() * 4;
@@ -1906,7 +1588,6 @@ int launch_attn_v(AttnParams p, int64_t ws_bytes, hipStream_t st) {
             return FINO_ERR_ARG;
         }
     }
-    if (p.all_partial) sp = SplitPlan{groups * p.nqb_v, 0, 0, 1};     // no tail split: every block is a partial anyway
     p.full_x = sp.full_x; p.rem_x = sp.rem_x; p.nwg = sp.nwg; p.per = sp.per;
     const dim3 grid((unsigned)(8 * (sp.full_x + sp.nwg)));
     // head_dim 128, long key sequences: the LDS-DMA-staged ping-pong kernel (round 4; same bits as the register-staged one,
@@ -1948,11 +1629,8 @@ int launch_attn_ranges(AttnParams p, hipStream_t st) {
     static FinoPerDeviceOnce once;
     if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&attn_ppd_kernel<T, D, 2>), smem_d, "fino_attn_fwd_ranges"))
         return rc;
-    attn_virtual_heads(p.batch, p.heads, p.nqb, p.vsplit, p.nqb_v);
-    const int groups = (p.batch * p.heads * p.vsplit + 7) / 8;
-    p.full_x = groups * p.nqb_v; p.rem_x = 0; p.nwg = 0; p.per = 1;
     p.ws = nullptr; p.all_partial = 0;
-    attn_ppd_kernel<T, D, 2><<<dim3((unsigned)(8 * p.full_x)), kWaves * 64, smem_d, st>>>(p, AttnTileMask{});
+    attn_ppd_kernel<T, D, 2><<<dim3(attn_whole_blocks(p)), kWaves * 64, smem_d, st>>>(p, AttnTileMask{});
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }
@@ -1964,11 +1642,8 @@ int launch_attn_tiles(AttnParams p, const AttnTileMask& tm, hipStream_t st) {
     static FinoPerDeviceOnce once;
     if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(&attn_ppd_kernel<T, D, 3>), smem_d, "fino_attn_fwd_tiles"))
         return rc;
-    attn_virtual_heads(p.batch, p.heads, p.nqb, p.vsplit, p.nqb_v);
-    const int groups = (p.batch * p.heads * p.vsplit + 7) / 8;
-    p.full_x = groups * p.nqb_v; p.rem_x = 0; p.nwg = 0; p.per = 1;
     p.ws = nullptr; p.all_partial = 0;
-    attn_ppd_kernel<T, D, 3><<<dim3((unsigned)(8 * p.full_x)), kWaves * 64, smem_d, st>>>(p, tm);
+    attn_ppd_kernel<T, D, 3><<<dim3(attn_whole_blocks(p)), kWaves * 64, smem_d, st>>>(p, tm);
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }
@@ -1990,6 +1665,7 @@ void fino_attn_plan_split(int batch, int heads, int nqb, int nt, int& full_x, in
 int fino_attn_launch_combine(const AttnParams& p, int dtype, int head_dim, hipStream_t st) {
     if (p.rem_x <= 0) return FINO_OK;
     const dim3 grid((unsigned)(8 * p.rem_x), (unsigned)(head_dim / 32));
+    // (written out, head_dim first: these four come first in the device code, in this order, and attn_dispatch's is dtype first)
     if (head_dim == 128) {
         if (dtype == FINO_BF16) attn_combine_kernel<BF16, 128><<<grid, kWaves * 64, 0, st>>>(p);
         else attn_combine_kernel<F16, 128><<<grid, kWaves * 64, 0, st>>>(p);
@@ -2013,69 +1689,59 @@ static int64_t attn_partial_bytes(int batch, int heads, int64_t lq, int head_dim
     return (int64_t)batch * heads * ((lq + kQBlock - 1) / kQBlock) * pf * 4;
 }
 
-static int attn_common(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                       int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs,
-                       int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs,
-                       int64_t o_rs, int64_t o_hs, float scale, int dtype, void* workspace,
-                       int64_t workspace_bytes, int all_partial, void* stream, const int* ranges = nullptr,
-                       const uint32_t* mask = nullptr, int64_t mask_bs = 0, int64_t mask_hs = 0, int mask_words = 0) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_attn_fwd: dtype %d", dtype);
+// fino_attn_fwd's parameters up to dtype, which its siblings repeat, and the AttnOperands they make
+#define ATTN_LEAD_PARAMS                                                                                                       \
+    const void *q, const void *k, const void *v, void *o, int batch, int heads, int64_t lq, int64_t lk, int head_dim, int64_t q_bs, \
+        int64_t q_rs, int64_t q_hs, int64_t k_bs, int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs,       \
+        int64_t o_bs, int64_t o_rs, int64_t o_hs, float scale, int dtype
+#define ATTN_LEAD_OPERANDS \
+    AttnOperands { q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs, v_hs, o_bs, o_rs, o_hs, scale }
+
+static int attn_common(const char* fn, AttnOperands a, int dtype, void* workspace, int64_t workspace_bytes, int all_partial,
+                       void* stream, const int* ranges = nullptr, const AttnTileMask& tm = AttnTileMask{}) {
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "%s: dtype %d", fn, dtype);
     if (all_partial) {
         static const uint16_t dummy_o[8] __attribute__((aligned(16))) = {0};
-        o = (void*)dummy_o;                                    // never written in this mode
-        o_bs = o_rs = o_hs = 0;
-        FINO_CHECK(head_dim == 128 || head_dim == 64, FINO_ERR_UNSUPPORTED, "fino_attn_partial: head_dim %d", head_dim);
-        FINO_CHECK(workspace && workspace_bytes >= attn_partial_bytes(batch, heads, lq, head_dim), FINO_ERR_ARG,
-                   "fino_attn_partial: workspace of %lld bytes needed",
-                   (long long)attn_partial_bytes(batch, heads, lq, head_dim));
+        a.o = (void*)dummy_o;                                  // never written in this mode
+        a.o_bs = a.o_rs = a.o_hs = 0;
+        FINO_CHECK(a.head_dim == 128 || a.head_dim == 64, FINO_ERR_UNSUPPORTED, "%s: head_dim %d", fn, a.head_dim);
+        FINO_CHECK(workspace && workspace_bytes >= attn_partial_bytes(a.batch, a.heads, a.lq, a.head_dim), FINO_ERR_ARG,
+                   "%s: workspace of %lld bytes needed", fn, (long long)attn_partial_bytes(a.batch, a.heads, a.lq, a.head_dim));
     }
-    FINO_CHECK(q && k && v && o, FINO_ERR_ARG, "fino_attn_fwd: null pointer");
-    FINO_CHECK(batch > 0 && heads > 0 && lq >= 0 && lk > 0, FINO_ERR_ARG,
-               "fino_attn_fwd: bad shape B=%d H=%d Lq=%lld Lk=%lld", batch, heads, (long long)lq, (long long)lk);
-    FINO_CHECK(head_dim == 128 || head_dim == 64, FINO_ERR_UNSUPPORTED,
-               "fino_attn_fwd: head_dim %d not in {64,128}", head_dim);
-    FINO_CHECK(lq < (1ll << 31) - 256 && lk < (1ll << 31) - 64, FINO_ERR_ARG, "fino_attn_fwd: sequence too long");
-    FINO_CHECK(fino_aligned16(q) && fino_aligned16(k) && fino_aligned16(v) && fino_aligned16(o) && q_rs % 8 == 0 &&
-                   k_rs % 8 == 0 && v_rs % 8 == 0 && o_rs % 8 == 0 && q_hs % 8 == 0 && k_hs % 8 == 0 &&
-                   v_hs % 8 == 0 && o_hs % 8 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0 && o_bs % 8 == 0,
-               FINO_ERR_ARG, "fino_attn_fwd: pointers and strides must be 16-byte aligned");
-    FINO_CHECK(scale > 0.f || scale == FINO_ATTN_SCALE_FOLDED, FINO_ERR_ARG,
-               "fino_attn_fwd: scale must be > 0 (or FINO_ATTN_SCALE_FOLDED)");
+    if (int rc = attn_check_operands(fn, a, true, nullptr, "scale must be > 0 (or FINO_ATTN_SCALE_FOLDED)", [&]() -> int {
+            FINO_CHECK(a.batch > 0 && a.heads > 0 && a.lq >= 0 && a.lk > 0, FINO_ERR_ARG, "%s: bad shape B=%d H=%d Lq=%lld Lk=%lld", fn,
+                       a.batch, a.heads, (long long)a.lq, (long long)a.lk);
+            FINO_CHECK(a.head_dim == 128 || a.head_dim == 64, FINO_ERR_UNSUPPORTED, "%s: head_dim %d not in {64,128}", fn, a.head_dim);
+            FINO_CHECK(a.lq < (1ll << 31) - 256 && a.lk < (1ll << 31) - 64, FINO_ERR_ARG, "%s: sequence too long", fn);
+            return FINO_OK;
+        }))
+        return rc;
     // the kernels address the K/V rows of one (batch, head) through a buffer resource: 32-bit byte count and offsets
     {
-        const int64_t kmax = k_rs > v_rs ? k_rs : v_rs;
-        FINO_CHECK(((lk - 1) * kmax + head_dim) * 2 < (1ll << 31), FINO_ERR_UNSUPPORTED,
-                   "fino_attn_fwd: Lk=%lld keys x row stride %lld exceed the 2 GiB one (batch, head) K/V slice may span",
-                   (long long)lk, (long long)kmax);
+        const int64_t kmax = a.k_rs > a.v_rs ? a.k_rs : a.v_rs;
+        FINO_CHECK(((a.lk - 1) * kmax + a.head_dim) * 2 < (1ll << 31), FINO_ERR_UNSUPPORTED,
+                   "%s: Lk=%lld keys x row stride %lld exceed the 2 GiB one (batch, head) K/V slice may span", fn, (long long)a.lk,
+                   (long long)kmax);
     }
-    if (lq == 0) return FINO_OK;
+    if (a.lq == 0) return FINO_OK;
     AttnParams p;
-    p.q = (const uint16_t*)q; p.k = (const uint16_t*)k; p.v = (const uint16_t*)v; p.o = (uint16_t*)o;
-    p.batch = batch; p.heads = heads; p.lq = (int)lq; p.lk = (int)lk;
-    p.q_bs = q_bs; p.q_rs = q_rs; p.q_hs = q_hs; p.k_bs = k_bs; p.k_rs = k_rs; p.k_hs = k_hs;
-    p.v_bs = v_bs; p.v_rs = v_rs; p.v_hs = v_hs; p.o_bs = o_bs; p.o_rs = o_rs; p.o_hs = o_hs;
-    p.scale_log2 = scale == FINO_ATTN_SCALE_FOLDED ? 1.0f : scale * 1.4426950408889634f;
-    p.nqb = (int)((lq + kQBlock - 1) / kQBlock);
+    attn_fill_params(p, a);
     p.ws = (workspace && workspace_bytes > 0) ? (float*)workspace : nullptr;
     p.all_partial = all_partial;
-    p.tail_n = 0;
-    p.ranges = ranges; p.vmean = nullptr;
-    const AttnTileMask tm{mask, mask_bs, mask_hs, mask_words};
-    FINO_CHECK(((uintptr_t)workspace & 15) == 0, FINO_ERR_ARG, "fino_attn_fwd_ws: workspace must be 16-byte aligned");
+    p.ranges = ranges;
+    FINO_CHECK(((uintptr_t)workspace & 15) == 0, FINO_ERR_ARG, "%s: workspace must be 16-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t wb = workspace_bytes;
-    if (dtype == FINO_BF16)
-        return head_dim == 128 ? launch_attn<BF16, 128>(p, tm, wb, st) : launch_attn<BF16, 64>(p, tm, wb, st);
-    return head_dim == 128 ? launch_attn<F16, 128>(p, tm, wb, st) : launch_attn<F16, 64>(p, tm, wb, st);
+    return attn_dispatch(dtype, a.head_dim, [&](auto t, auto d) {
+        return launch_attn<decltype(t), decltype(d)::value>(p, tm, workspace_bytes, st);
+    });
 }
 
-extern "C" int fino_attn_fwd_ws(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                                int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs,
-                                int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs,
-                                int64_t o_rs, int64_t o_hs, float scale, int dtype, void* workspace,
-                                int64_t workspace_bytes, void* stream) {
-    return attn_common(q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs, v_hs,
-                       o_bs, o_rs, o_hs, scale, dtype, workspace, workspace_bytes, 0, stream);
+extern "C" int fino_attn_fwd_ws(ATTN_LEAD_PARAMS, void* workspace, int64_t workspace_bytes, void* stream) {
+    return attn_common("fino_attn_fwd_ws", ATTN_LEAD_OPERANDS, dtype, workspace, workspace_bytes, 0, stream);
+}
+
+extern "C" int fino_attn_fwd(ATTN_LEAD_PARAMS, void* stream) {
+    return attn_common("fino_attn_fwd", ATTN_LEAD_OPERANDS, dtype, nullptr, 0, 0, stream);
 }
 
 extern "C" int64_t fino_attn_partial_bytes(int batch, int heads, int64_t lq, int head_dim) {
@@ -2087,8 +1753,9 @@ extern "C" int fino_attn_partial(const void* q, const void* k, const void* v, in
                                  int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs, int64_t k_rs,
                                  int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, float scale, int dtype,
                                  void* partial, int64_t partial_bytes, void* stream) {
-    return attn_common(q, k, v, nullptr, batch, heads, lq, lk, head_dim, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs,
-                       v_hs, 0, 0, 0, scale, dtype, partial, partial_bytes, 1, stream);
+    const AttnOperands a{q, k, v, nullptr, batch, heads, lq, lk, head_dim, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs, v_hs,
+                         0, 0, 0, scale};
+    return attn_common("fino_attn_partial", a, dtype, partial, partial_bytes, 1, stream);
 }
 
 extern "C" int fino_attn_merge(void* o, int batch, int heads, int64_t lq, int head_dim, int64_t o_bs, int64_t o_rs,
@@ -2108,63 +1775,35 @@ extern "C" int fino_attn_merge(void* o, int batch, int heads, int64_t lq, int he
     mp.o_bs = o_bs; mp.o_rs = o_rs; mp.o_hs = o_hs;
     const dim3 grid((unsigned)(batch * heads * mp.nqb), (unsigned)(head_dim / 32));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16) {
-        if (head_dim == 128) attn_merge_kernel<BF16, 128><<<grid, kWaves * 64, 0, st>>>(mp);
-        else attn_merge_kernel<BF16, 64><<<grid, kWaves * 64, 0, st>>>(mp);
-    } else {
-        if (head_dim == 128) attn_merge_kernel<F16, 128><<<grid, kWaves * 64, 0, st>>>(mp);
-        else attn_merge_kernel<F16, 64><<<grid, kWaves * 64, 0, st>>>(mp);
-    }
+    attn_dispatch(dtype, head_dim, [&](auto t, auto d) {
+        attn_merge_kernel<decltype(t), decltype(d)::value><<<grid, kWaves * 64, 0, st>>>(mp);
+        return 0;
+    });
     FINO_LAUNCH_CHECK();
     return FINO_OK;
-}
-
-extern "C" int fino_attn_fwd(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                             int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs,
-                             int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs,
-                             int64_t o_rs, int64_t o_hs, float scale, int dtype, void* stream) {
-    return fino_attn_fwd_ws(q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs,
-                            v_hs, o_bs, o_rs, o_hs, scale, dtype, nullptr, 0, stream);
 }
 
 // Attention over up to three ranges of key tiles per 256-row q-block (include/frameino_hip.h): fino_attn_fwd's arguments and
 // checks + the device table; always attn_ppd_kernel<T, D, 2>.
 extern "C" int fino_attn_ranges_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim) {
-    return (head_dim == 128 || head_dim == 64) && batch > 0 && heads > 0 && lq > 0 && lk > 0 && lq < (1ll << 31) - 256 &&
-           lk < (1ll << 31) - 64;
+    return attn_shape_supported(batch, heads, lq, lk, head_dim, 64 | 128, false);
 }
 
-extern "C" int fino_attn_fwd_ranges(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                                    int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs,
-                                    int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs,
-                                    int64_t o_rs, int64_t o_hs, float scale, int dtype, const int* ranges, void* stream) {
-    FINO_CHECK(ranges, FINO_ERR_ARG, "fino_attn_fwd_ranges: null ranges table");
-    FINO_CHECK(((uintptr_t)ranges & 3) == 0, FINO_ERR_ARG, "fino_attn_fwd_ranges: the ranges table must be 4-byte aligned");
-    return attn_common(q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs, v_hs,
-                       o_bs, o_rs, o_hs, scale, dtype, nullptr, 0, 0, stream, ranges);
+extern "C" int fino_attn_fwd_ranges(ATTN_LEAD_PARAMS, const int* ranges, void* stream) {
+    if (int rc = attn_check_ranges("fino_attn_fwd_ranges", ranges)) return rc;
+    return attn_common("fino_attn_fwd_ranges", ATTN_LEAD_OPERANDS, dtype, nullptr, 0, 0, stream, ranges);
 }
 
 // Attention over the key tiles a bitmask names per (batch element, head, 256-row q-block) (include/frameino_hip.h):
 // fino_attn_fwd's arguments and checks + the device mask; always attn_ppd_kernel<T, D, 3>.
 extern "C" int fino_attn_tiles_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim) {
-    return fino_attn_ranges_supported(batch, heads, lq, lk, head_dim) && (lk + kKV - 1) / kKV <= kAttnMaxTiles;
+    return attn_shape_supported(batch, heads, lq, lk, head_dim, 64 | 128, true);
 }
 
-extern "C" int fino_attn_fwd_tiles(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                                   int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs,
-                                   int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs,
-                                   int64_t o_rs, int64_t o_hs, float scale, int dtype, const uint32_t* mask,
-                                   int64_t mask_bs, int64_t mask_hs, int words, void* stream) {
-    FINO_CHECK(mask, FINO_ERR_ARG, "fino_attn_fwd_tiles: null mask");
-    FINO_CHECK(((uintptr_t)mask & 3) == 0, FINO_ERR_ARG, "fino_attn_fwd_tiles: the mask must be 4-byte aligned");
-    FINO_CHECK(lk > 0 && (lk + kKV - 1) / kKV <= kAttnMaxTiles, FINO_ERR_UNSUPPORTED,
-               "fino_attn_fwd_tiles: Lk=%lld is more than %d key tiles", (long long)lk, kAttnMaxTiles);
-    FINO_CHECK(words > 0 && (int64_t)words * 32 >= (lk + kKV - 1) / kKV, FINO_ERR_ARG,
-               "fino_attn_fwd_tiles: %d mask words per q-block do not hold %lld key tiles", words,
-               (long long)((lk + kKV - 1) / kKV));
-    FINO_CHECK(mask_bs >= 0 && mask_hs >= 0, FINO_ERR_ARG, "fino_attn_fwd_tiles: negative mask stride");
-    return attn_common(q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs, v_hs,
-                       o_bs, o_rs, o_hs, scale, dtype, nullptr, 0, 0, stream, nullptr, mask, mask_bs, mask_hs, words);
+extern "C" int fino_attn_fwd_tiles(ATTN_LEAD_PARAMS, const uint32_t* mask, int64_t mask_bs, int64_t mask_hs, int words, void* stream) {
+    if (int rc = attn_check_tile_mask("fino_attn_fwd_tiles", mask, mask_bs, mask_hs, words, lk)) return rc;
+    return attn_common("fino_attn_fwd_tiles", ATTN_LEAD_OPERANDS, dtype, nullptr, 0, 0, stream, nullptr,
+                       AttnTileMask{mask, mask_bs, mask_hs, words});
 }
 
 // Cross-attention over key sequences whose TAIL is one row repeated (a zero-padded prompt: every padding token yields the same
@@ -2179,42 +1818,26 @@ extern "C" int fino_attn_tail_supported(int batch, int heads, int64_t lq, int64_
            (int64_t)batch * heads * ((lq + kQBlock - 1) / kQBlock) < (1 << 24);
 }
 
-extern "C" int fino_attn_fwd_tail(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                                  int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t q_hs, int64_t k_bs,
-                                  int64_t k_rs, int64_t k_hs, int64_t v_bs, int64_t v_rs, int64_t v_hs, int64_t o_bs,
-                                  int64_t o_rs, int64_t o_hs, float scale, int dtype, const int* lk_b,
-                                  const float* tail_mult, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_attn_fwd_tail: dtype %d", dtype);
-    FINO_CHECK(q && k && v && o && lk_b && tail_mult, FINO_ERR_ARG, "fino_attn_fwd_tail: null pointer");
-    FINO_CHECK(fino_attn_tail_supported(batch, heads, lq, lk, head_dim), FINO_ERR_UNSUPPORTED,
-               "fino_attn_fwd_tail: needs head_dim 128, batch <= 4, lk > 64 (got head_dim %d, batch %d, lk %lld)", head_dim,
-               batch, (long long)lk);
-    FINO_CHECK(fino_aligned16(q) && fino_aligned16(k) && fino_aligned16(v) && fino_aligned16(o) && q_rs % 8 == 0 &&
-                   k_rs % 8 == 0 && v_rs % 8 == 0 && o_rs % 8 == 0 && q_hs % 8 == 0 && k_hs % 8 == 0 &&
-                   v_hs % 8 == 0 && o_hs % 8 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0 && o_bs % 8 == 0,
-               FINO_ERR_ARG, "fino_attn_fwd_tail: pointers and strides must be 16-byte aligned");
-    FINO_CHECK(scale > 0.f || scale == FINO_ATTN_SCALE_FOLDED, FINO_ERR_ARG, "fino_attn_fwd_tail: scale");
+extern "C" int fino_attn_fwd_tail(ATTN_LEAD_PARAMS, const int* lk_b, const float* tail_mult, void* stream) {
+    const char* fn = "fino_attn_fwd_tail";
+    const AttnOperands a = ATTN_LEAD_OPERANDS;
+    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "%s: dtype %d", fn, dtype);
+    if (int rc = attn_check_operands(fn, a, lk_b && tail_mult, nullptr, "scale", [&]() -> int {
+            FINO_CHECK(fino_attn_tail_supported(batch, heads, lq, lk, head_dim), FINO_ERR_UNSUPPORTED,
+                       "%s: needs head_dim 128, batch <= 4, lk > 64 (got head_dim %d, batch %d, lk %lld)", fn, head_dim, batch,
+                       (long long)lk);
+            return FINO_OK;
+        }))
+        return rc;
     AttnParams p;
-    p.q = (const uint16_t*)q; p.k = (const uint16_t*)k; p.v = (const uint16_t*)v; p.o = (uint16_t*)o;
-    p.batch = batch; p.heads = heads; p.lq = (int)lq; p.lk = (int)lk;
-    p.q_bs = q_bs; p.q_rs = q_rs; p.q_hs = q_hs; p.k_bs = k_bs; p.k_rs = k_rs; p.k_hs = k_hs;
-    p.v_bs = v_bs; p.v_rs = v_rs; p.v_hs = v_hs; p.o_bs = o_bs; p.o_rs = o_rs; p.o_hs = o_hs;
-    p.scale_log2 = scale == FINO_ATTN_SCALE_FOLDED ? 1.0f : scale * 1.4426950408889634f;
-    p.nqb = (int)((lq + kQBlock - 1) / kQBlock);
-    p.vsplit = 1; p.nqb_v = p.nqb; p.full_x = 0; p.rem_x = 0; p.nwg = 0; p.per = 1;
-    p.ws = nullptr; p.all_partial = 0; p.ranges = nullptr; p.vmean = nullptr;
+    attn_fill_params(p, a);
     // the walking kernel addresses each operand through ONE buffer resource over the whole tensor
-    auto span = [&](int64_t bs, int64_t hs, int64_t rs, int64_t rows) {
-        return (((int64_t)batch - 1) * bs + ((int64_t)heads - 1) * hs + (rows - 1 + 2 * kKV) * rs + 128) * 2;
-    };
-    FINO_CHECK(span(k_bs, k_hs, k_rs, lk) < (1ll << 31) && span(v_bs, v_hs, v_rs, lk) < (1ll << 31) &&
-                   span(o_bs, o_hs, o_rs, lq) < (1ll << 31),
-               FINO_ERR_UNSUPPORTED, "fino_attn_fwd_tail: an operand spans more than 2 GiB");
+    FINO_CHECK(attn_spans_fit(a), FINO_ERR_UNSUPPORTED, "%s: an operand spans more than 2 GiB", fn);
     p.tail_n = batch;
     for (int b = 0; b < 4; ++b) {
         const int bb = b < batch ? b : batch - 1;
-        FINO_CHECK(lk_b[bb] >= 1 && lk_b[bb] <= lk && tail_mult[bb] >= 1.0f, FINO_ERR_ARG,
-                   "fino_attn_fwd_tail: lk_b[%d] = %d (of %lld), tail_mult %g", bb, lk_b[bb], (long long)lk, (double)tail_mult[bb]);
+        FINO_CHECK(lk_b[bb] >= 1 && lk_b[bb] <= lk && tail_mult[bb] >= 1.0f, FINO_ERR_ARG, "%s: lk_b[%d] = %d (of %lld), tail_mult %g",
+                   fn, bb, lk_b[bb], (long long)lk, (double)tail_mult[bb]);
         p.tail_lk[b] = lk_b[bb];
         p.tail_bias[b] = log2f(tail_mult[bb]) / p.scale_log2;
     }
@@ -2222,3 +1845,5 @@ extern "C" int fino_attn_fwd_tail(const void* q, const void* k, const void* v, v
     hipStream_t st = (hipStream_t)stream;
     return dtype == FINO_BF16 ? launch_attn_ppw<BF16, true>(p, st) : launch_attn_ppw<F16, true>(p, st);
 }
+#undef ATTN_LEAD_PARAMS
+#undef ATTN_LEAD_OPERANDS

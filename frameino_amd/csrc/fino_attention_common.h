@@ -15,6 +15,87 @@ __device__ __forceinline__ float vmax2(float a, float b) {
     asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
     return d;
 }
+// a raw LDS address as a pointer (the dynamic segment is each kernel's only LDS, so it starts at 0: the kernels check)
+#define LDS_PTR(TYPE_, ADDR_) ((FINO_LDS TYPE_*)(uintptr_t)(uint32_t)(ADDR_))
+// row max of 8 accumulator registers (one of four independent chains).  v_max3_f32 through asm: fmaxf on MFMA results makes
+// the compiler canonicalise every input first (32 extra v_max_f32 per tile).  Macros, not functions: as __forceinline__
+// functions they changed attn_ppd_kernel's register allocation.
+#define MAX8(S_, O_) vmax2(vmax3(vmax3(S_[O_], S_[O_ + 1], S_[O_ + 2]), vmax3(S_[O_ + 3], S_[O_ + 4], S_[O_ + 5]), \
+                                 S_[O_ + 6]), S_[O_ + 7])
+// ... and the finish: OUT_ = the maximum of MX_ over the two half-waves (the two lanes that share a query row)
+#define MAX_FINISH1(MX_, OUT_)                                                                              \
+    {                                                                                                       \
+        const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(MX_), __float_as_uint(MX_), false, false); \
+        OUT_ = vmax2(__uint_as_float(sw_[0]), __uint_as_float(sw_[1]));                                     \
+    }
+
+// The softmax phase's pieces, one copy for the four loops of fino_attention.hip, which name what these read and write the same:
+// sc0 / sc1 (S, then P, of the tile), m_run, l_run, mx_next, c2, o, pb.  Deferred rescale (threshold rescale_thr<T>()): O, l and m
+// move together, between tiles.
+#define ATTN_RESCALE()                                                                                      \
+    {                                                                                                       \
+        const float m_cand = fmaxf(m_run, mx_next * c2);                                                    \
+        if (__any((m_cand - m_run) > rescale_thr<T>())) {                                                   \
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_cand);                                     \
+            m_run = m_cand;                                                                                 \
+            l_run *= alpha;                                                                                 \
+            _Pragma("unroll") for (int i = 0; i < kDT; ++i)                                                 \
+                _Pragma("unroll") for (int j = 0; j < 16; ++j) o[i][j] *= alpha;                            \
+        }                                                                                                   \
+    }
+// l += the lane's share of the row sum of P
+#define ATTN_ROWSUM()                                                                                       \
+    {                                                                                                       \
+        float psum0 = 0.f, psum1 = 0.f;                                                                     \
+        _Pragma("unroll") for (int j = 0; j < 16; ++j) {                                                    \
+            psum0 += sc0[j];                                                                                \
+            psum1 += sc1[j];                                                                                \
+        }                                                                                                   \
+        l_run += psum0 + psum1;                                                                             \
+    }
+// P(t) packed to the operand type: pb[2 * kt + s2]
+#define ATTN_PACK_P()                                                                                       \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                         \
+        pb[0][j] = (typename T::scalar)sc0[j];                                                              \
+        pb[1][j] = (typename T::scalar)sc0[8 + j];                                                          \
+        pb[2][j] = (typename T::scalar)sc1[j];                                                              \
+        pb[3][j] = (typename T::scalar)sc1[8 + j];                                                          \
+    }
+// the whole softmax belongs to ITS phase: pin its results in registers (pure arithmetic would otherwise be sunk past the
+// barrier into the matrix phase, next to its first use)
+#define ATTN_PIN_P()                                                                                        \
+    {                                                                                                       \
+        u32x4_t p0 = __builtin_bit_cast(u32x4_t, pb[0]), p1 = __builtin_bit_cast(u32x4_t, pb[1]);           \
+        u32x4_t p2 = __builtin_bit_cast(u32x4_t, pb[2]), p3 = __builtin_bit_cast(u32x4_t, pb[3]);           \
+        asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3), "+v"(l_run));                             \
+        pb[0] = __builtin_bit_cast(vec8, p0); pb[1] = __builtin_bit_cast(vec8, p1);                         \
+        pb[2] = __builtin_bit_cast(vec8, p2); pb[3] = __builtin_bit_cast(vec8, p3);                         \
+    }
+// Q fragments (B operand of S^T = K.Q^T) of query row `qrow` at `qp`: lane holds Q[qrow][16 * ks + 8 * h .. + 7].  Rows past Lq are
+// never stored: zero operands draw the least power.
+#define ATTN_LOAD_Q()                                                                                       \
+    const int qrow_c = qrow < p.lq ? qrow : p.lq - 1;                                                       \
+    vec8 qf[kKS];                                                                                           \
+    _Pragma("unroll") for (int ks = 0; ks < kKS; ++ks) {                                                    \
+        uint4 u = *reinterpret_cast<const uint4*>(qp + (int64_t)qrow_c * p.q_rs + 16 * ks + 8 * h);         \
+        if (qrow >= p.lq) u = make_uint4(0, 0, 0, 0);                                                       \
+        qf[ks] = __builtin_bit_cast(vec8, u);                                                               \
+    }
+// O[qrow][..] = o * inv, straight from the accumulators: 8 bytes per store
+#define ATTN_STORE_O()                                                                                      \
+    if (qrow < p.lq) {                                                                                      \
+        uint16_t* orow = op + (int64_t)qrow * p.o_rs;                                                       \
+        _Pragma("unroll") for (int dt = 0; dt < kDT; ++dt) {                                                \
+            _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                 \
+                const int d0 = dt * 32 + 8 * g + 4 * h;                                                     \
+                uint32_t w0 = (uint32_t)T::from_f32(o[dt][4 * g + 0] * inv) |                               \
+                              ((uint32_t)T::from_f32(o[dt][4 * g + 1] * inv) << 16);                        \
+                uint32_t w1 = (uint32_t)T::from_f32(o[dt][4 * g + 2] * inv) |                               \
+                              ((uint32_t)T::from_f32(o[dt][4 * g + 3] * inv) << 16);                        \
+                *reinterpret_cast<uint2*>(orow + d0) = make_uint2(w0, w1);                                  \
+            }                                                                                               \
+        }                                                                                                   \
+    }
 
 namespace fino_attn_ns {
 

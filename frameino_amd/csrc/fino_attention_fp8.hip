@@ -30,7 +30,7 @@
 //     Measurements: DESIGN.md section 4.2, profiles/r03_attn_fp8_*.
 #include <stdlib.h>
 
-#include "fino_attention_common.h"
+#include "fino_attention_host.h"
 using namespace fino_attn_ns;
 
 namespace {
@@ -528,13 +528,6 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_kernel(const Fp8AttnP
             if (key_ + 32 >= rem_) S1_[j_] = -INFINITY;                                                      \
         }                                                                                                    \
     }
-#define F8_MAX8(S_, O_) vmax2(vmax3(vmax3(S_[O_], S_[O_ + 1], S_[O_ + 2]), vmax3(S_[O_ + 3], S_[O_ + 4], S_[O_ + 5]), \
-                                    S_[O_ + 6]), S_[O_ + 7])
-#define F8_SWAPMAX(MX_, OUT_)                                                                                \
-    {                                                                                                        \
-        const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(MX_), __float_as_uint(MX_), false, false); \
-        OUT_ = vmax2(__uint_as_float(sw_[0]), __uint_as_float(sw_[1]));                                      \
-    }
 
     // ---- S(0) unpipelined; m_run = the value SUBTRACTED from s (running maximum minus kPShift, T-representable) ----
     f32x16_t s0, s1;
@@ -543,13 +536,13 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_kernel(const Fp8AttnP
     F8_MASK(0, s0, s1)
     float m_run;
     {
-        // fmaxf here, not the asm v_max3 of F8_MAX8: the compiler places the MFMA -> VALU wait states for what it can see;
+        // fmaxf here, not the asm v_max3 of MAX8: the compiler places the MFMA -> VALU wait states for what it can see;
         // an asm reading an accumulator right behind its MFMA gets none (and reads the register before the write-back)
         float mx = fmaxf(s0[0], s1[0]);
 #pragma unroll
         for (int j = 1; j < 16; ++j) mx = fmaxf(mx, fmaxf(s0[j], s1[j]));
         float mxx;
-        F8_SWAPMAX(mx, mxx)
+        MAX_FINISH1(mx, mxx)
         m_run = px_first_m<T, PX>(mxx);
         const float off0 = px_first_off<PX>(m_run);
 #pragma unroll
@@ -648,7 +641,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_kernel(const Fp8AttnP
         const float mxb = max16_behind(s1, o[1][0]);    // behind P.V (d-tile 1)
         lacc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ones8, pf, lacc, 0, 0, 0, kOne, 0, kPs);
         mxa = vmax2(mxa, mxb);
-        F8_SWAPMAX(mxa, ex_next)
+        MAX_FINISH1(mxa, ex_next)
 #undef F8_PV
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
@@ -665,8 +658,6 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_kernel(const Fp8AttnP
 #undef F8_KREAD
 #undef F8_BARRIER
 #undef F8_MASK
-#undef F8_MAX8
-#undef F8_SWAPMAX
 
     // ---- epilogue: every register of lacc holds l of this lane's query (all rows of the ones tile are equal) ----
     float l_run = lacc[0];
@@ -859,11 +850,6 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
             if (key_ + 32 >= rem_) S1_[j_] = -INFINITY;                                                      \
         }                                                                                                    \
     }
-#define FR_SWAPMAX(MX_, OUT_)                                                                                \
-    {                                                                                                        \
-        const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(MX_), __float_as_uint(MX_), false, false); \
-        OUT_ = vmax2(__uint_as_float(sw_[0]), __uint_as_float(sw_[1]));                                      \
-    }
 
     // ---- S(0) unpipelined ----
     f32x16_t s0, s1;
@@ -876,7 +862,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
 #pragma unroll
         for (int j = 1; j < 16; ++j) mx = fmaxf(mx, fmaxf(s0[j], s1[j]));
         float mxx;
-        FR_SWAPMAX(mx, mxx)
+        MAX_FINISH1(mx, mxx)
         m_run = px_first_m<T, PX>(mxx);
         const float off0 = px_first_off<PX>(m_run);
 #pragma unroll
@@ -949,7 +935,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
         const float mxb = FRX_MAX(SO1_, o[1][0]);                                                            \
         FRX_LACC()                                                                                           \
         mxa = vmax2(mxa, mxb);                                                                               \
-        FR_SWAPMAX(mxa, ex_next)                                                                             \
+        MAX_FINISH1(mxa, ex_next)                                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
         asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");     /* tile t + 2 has landed (t + 3 may be in flight) */ \
         FRX_BARRIER();                                                                                       \
@@ -978,7 +964,6 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
 #undef FR_KREAD
 #undef FR_QK
 #undef FR_MASK
-#undef FR_SWAPMAX
 
     // (direct 8-byte stores: the staged whole-row form of the other kernels -- attn_rows_through_lds -- pushed this kernel, which
     // lives at the 168-register limit of three workgroups per CU, into scratch spills inside its loop)
@@ -1225,11 +1210,6 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
             if (key_ + 32 >= rem_) S1_[j_] = -INFINITY;                                                      \
         }                                                                                                    \
     }
-#define D8_SWAPMAX(MX_, OUT_)                                                                                \
-    {                                                                                                        \
-        const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(MX_), __float_as_uint(MX_), false, false); \
-        OUT_ = vmax2(__uint_as_float(sw_[0]), __uint_as_float(sw_[1]));                                      \
-    }
 
     f32x16_t s0, s1;
     D8_KREAD(0)
@@ -1241,7 +1221,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
 #pragma unroll
         for (int j = 1; j < 16; ++j) mx = fmaxf(mx, fmaxf(s0[j], s1[j]));
         float mxx;
-        D8_SWAPMAX(mx, mxx)
+        MAX_FINISH1(mx, mxx)
         m_run = px_first_m<T, PX>(mxx);
         const float off0 = px_first_off<PX>(m_run);
 #pragma unroll
@@ -1315,7 +1295,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
         const float mxb = max16_behind(s1, o[3][0]);
         lacc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ones8, pf, lacc, 0, 0, 0, kOne, 0, kPs);
         mxa = vmax2(mxa, mxb);
-        D8_SWAPMAX(mxa, ex_next)
+        MAX_FINISH1(mxa, ex_next)
 #undef D8_PV
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
@@ -1331,7 +1311,6 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
 #undef D8_KREAD
 #undef D8_QK
 #undef D8_MASK
-#undef D8_SWAPMAX
 
     if (part >= 0) {
         // partial in the bf16 kernels' layout (attn_combine_kernel finishes): m, O and l share the 2^kPShift offset, which
@@ -1401,11 +1380,46 @@ extern "C" int64_t fino_attn_fp8_smoothed_kv_bytes(int batch, int heads, int64_t
 // `ranges` (fino_attn_fwd_fp8_ranges): head_dim 64 only, always attn_fp8_fr_kernel<T, PX, true>, whatever the tuning knob says.
 // `tiles` (fino_attn_fwd_fp8_tiles): head_dim 128 only, always attn_fp8_d128_kernel<T, PX, true> over whole blocks (no tail split,
 // no partials, no combine launch).
-static int attn_fwd_fp8_impl(const char* fn, int smooth, const void* q, const void* k, const void* v, void* o, int batch, int heads,
-                             int64_t lq, int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
-                             int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode,
-                             void* kv_workspace, int64_t kv_workspace_bytes, void* stream, const int* ranges = nullptr,
+// kernel families of the main launch: Family::kernel<T, PX>() is the __global__ function for (operand type, p_mode)
+struct KFr     { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_fr_kernel<T, PX>; } };
+struct KFrRg   { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_fr_kernel<T, PX, true>; } };
+struct KD128   { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_d128_kernel<T, PX>; } };
+struct KD128Tl { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_d128_kernel<T, PX, true>; } };
+struct KPp     { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_kernel<T, 0, PX>; } };
+
+template <class Family, typename T, int PX, class... Args>
+static int fp8_launch_as(const char* fn, dim3 grid, int threads, int smem, hipStream_t st, const Args&... args) {
+    constexpr auto kernel = Family::template kernel<T, PX>();
+    if (smem > 64 * 1024) {                       // more dynamic LDS than a kernel gets without asking
+        static FinoPerDeviceOnce once;
+        if (int rc = fino_max_smem_once(once, reinterpret_cast<const void*>(kernel), smem, fn)) return rc;
+    }
+    kernel<<<grid, threads, smem, st>>>(args...);
+    return FINO_OK;
+}
+// the Family's kernel for (dtype, p_mode); the caller checks the launch
+template <class Family, class... Args>
+static int fp8_launch(const char* fn, int dtype, bool ramp, dim3 grid, int threads, int smem, hipStream_t st, const Args&... args) {
+    if (dtype == FINO_BF16)
+        return ramp ? fp8_launch_as<Family, BF16, 1>(fn, grid, threads, smem, st, args...)
+                    : fp8_launch_as<Family, BF16, 0>(fn, grid, threads, smem, st, args...);
+    return ramp ? fp8_launch_as<Family, F16, 1>(fn, grid, threads, smem, st, args...)
+                : fp8_launch_as<Family, F16, 0>(fn, grid, threads, smem, st, args...);
+}
+
+// fino_attn_fwd_fp8's parameters up to kv_workspace_bytes, which its siblings repeat, and the AttnOperands they make
+#define FP8_LEAD_PARAMS                                                                                                        \
+    const void *q, const void *k, const void *v, void *o, int batch, int heads, int64_t lq, int64_t lk, int head_dim, int64_t q_bs, \
+        int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype, \
+        int p_mode, void *kv_workspace, int64_t kv_workspace_bytes
+#define FP8_LEAD_OPERANDS \
+    AttnOperands { q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, head_dim, k_bs, k_rs, 0, v_bs, v_rs, 0, o_bs, o_rs, head_dim, scale }
+
+static int attn_fwd_fp8_impl(const char* fn, int smooth, const AttnOperands& a, int dtype, int p_mode, void* kv_workspace,
+                             int64_t kv_workspace_bytes, void* stream, const int* ranges = nullptr,
                              const AttnTileMask* tiles = nullptr) {
+    const int batch = a.batch, heads = a.heads, head_dim = a.head_dim;
+    const int64_t lq = a.lq, lk = a.lk, k_bs = a.k_bs, k_rs = a.k_rs, v_bs = a.v_bs, v_rs = a.v_rs;
     FINO_CHECK(smooth >= 0 && smooth <= (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V), FINO_ERR_ARG, "%s: smooth flags %d not in 0 .. 3", fn,
                smooth);
     FINO_CHECK(p_mode == FINO_FP8_P_EXP2 || p_mode == FINO_FP8_P_RAMP, FINO_ERR_ARG, "%s: p_mode %d", fn, p_mode);
@@ -1415,13 +1429,11 @@ static int attn_fwd_fp8_impl(const char* fn, int smooth, const void* q, const vo
                head_dim);
     FINO_CHECK(!tiles || head_dim == 128, FINO_ERR_UNSUPPORTED, "%s: head_dim %d: the fp8 tile walk exists for head_dim 128 only", fn,
                head_dim);
-    FINO_CHECK(q && k && v && o && kv_workspace, FINO_ERR_ARG, "%s: null pointer", fn);
-    FINO_CHECK(batch > 0 && heads > 0 && lq >= 0 && lk > 0, FINO_ERR_ARG, "%s: bad shape", fn);
-    FINO_CHECK(fino_aligned16(q) && fino_aligned16(k) && fino_aligned16(v) && fino_aligned16(o) &&
-                   fino_aligned16(kv_workspace) && q_rs % 8 == 0 && k_rs % 8 == 0 && v_rs % 8 == 0 && o_rs % 8 == 0 &&
-                   q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0 && o_bs % 8 == 0,
-               FINO_ERR_ARG, "%s: pointers and strides must be 16-byte aligned", fn);
-    FINO_CHECK(scale > 0.f || scale == FINO_ATTN_SCALE_FOLDED, FINO_ERR_ARG, "%s: scale", fn);
+    if (int rc = attn_check_operands(fn, a, kv_workspace != nullptr, kv_workspace, "scale", [&]() -> int {
+            FINO_CHECK(batch > 0 && heads > 0 && lq >= 0 && lk > 0, FINO_ERR_ARG, "%s: bad shape", fn);
+            return FINO_OK;
+        }))
+        return rc;
     const int64_t need = fino_attn_fp8_smoothed_kv_bytes(batch, heads, lk, head_dim, smooth);
     FINO_CHECK(kv_workspace_bytes >= need, FINO_ERR_ARG, "%s: workspace %lld B < %lld B", fn,
                (long long)kv_workspace_bytes, (long long)need);
@@ -1432,7 +1444,7 @@ static int attn_fwd_fp8_impl(const char* fn, int smooth, const void* q, const vo
     const int64_t bh = (int64_t)batch * heads * sub;
     uint8_t* w8 = (uint8_t*)kv_workspace;
     QuantParamsT<true> qp;                                    // (.mean: the smoothing quantiser alone reads it)
-    qp.k = (const uint16_t*)k; qp.v = (const uint16_t*)v;
+    qp.k = (const uint16_t*)a.k; qp.v = (const uint16_t*)a.v;
     qp.k8 = w8; qp.v8t = w8 + bh * nt * kTileK8; qp.ks = w8 + 2 * bh * nt * kTileK8; qp.vs = qp.ks + bh * nt * 128;
     qp.batch = batch; qp.heads = heads * sub; qp.lk = (int)lk; qp.nt = nt;
     qp.k_bs = k_bs; qp.k_rs = k_rs; qp.k_hs = 64; qp.v_bs = v_bs; qp.v_rs = v_rs; qp.v_hs = 64;
@@ -1482,59 +1494,23 @@ static int attn_fwd_fp8_impl(const char* fn, int smooth, const void* q, const vo
 
     Fp8AttnParams fp;
     AttnParams& p = fp.a;
-    p.q = (const uint16_t*)q; p.k = nullptr; p.v = nullptr; p.o = (uint16_t*)o;
-    p.batch = batch; p.heads = heads; p.lq = (int)lq; p.lk = (int)lk;
-    p.q_bs = q_bs; p.q_rs = q_rs; p.q_hs = head_dim; p.k_bs = p.k_rs = p.k_hs = p.v_bs = p.v_rs = p.v_hs = 0;
-    p.o_bs = o_bs; p.o_rs = o_rs; p.o_hs = head_dim;
-    p.scale_log2 = scale == FINO_ATTN_SCALE_FOLDED ? 1.0f : scale * 1.4426950408889634f;
     const bool ramp = p_mode == FINO_FP8_P_RAMP;
-    if (ramp) p.scale_log2 *= 8.0f;          // logits in eighths of an octave: an exact shift of q's e8m0 block scales
     const bool free_running = head_dim == 64 && (ranges || fino_tune_get(FINO_TUNE_ATTN_FP8_KERNEL) != 1);   // default at head_dim 64
-    const int qblock = free_running ? kFrQBlock : kQBlock;
-    p.nqb = (int)((lq + qblock - 1) / qblock);
-    p.ws = nullptr; p.all_partial = 0; p.tail_n = 0; p.ranges = ranges; p.vmean = qp.vmean;
-    attn_virtual_heads(p.batch, p.heads, p.nqb, p.vsplit, p.nqb_v);
-    const int groups = (p.batch * p.heads * p.vsplit + 7) / 8;
-    p.full_x = groups * p.nqb_v; p.rem_x = 0; p.nwg = 0; p.per = 1;
+    attn_fill_params(p, a, free_running ? kFrQBlock : kQBlock);
+    p.k = p.v = nullptr;                     // the main kernels read the quantised images, not K / V
+    p.k_bs = p.k_rs = p.k_hs = p.v_bs = p.v_rs = p.v_hs = 0;
+    if (ramp) p.scale_log2 *= 8.0f;          // logits in eighths of an octave: an exact shift of q's e8m0 block scales
+    p.ranges = ranges; p.vmean = qp.vmean;
     fp.k8 = qp.k8; fp.ks = qp.ks; fp.v8t = qp.v8t; fp.vs = qp.vs; fp.nt = nt;
-    const dim3 grid((unsigned)(8 * p.full_x));
+    const dim3 grid(attn_whole_blocks(p));
     if (free_running) {
-#define F8_LAUNCH(KERNEL_, GRID_, THREADS_, SMEM_)                                                                        \
-    {                                                                                                                     \
-        if (dtype == FINO_BF16) { if (ramp) KERNEL_(BF16, 1)<<<GRID_, THREADS_, SMEM_, st>>>(fp); else KERNEL_(BF16, 0)<<<GRID_, THREADS_, SMEM_, st>>>(fp); } \
-        else { if (ramp) KERNEL_(F16, 1)<<<GRID_, THREADS_, SMEM_, st>>>(fp); else KERNEL_(F16, 0)<<<GRID_, THREADS_, SMEM_, st>>>(fp); } \
-    }
-#define F8_LAUNCH_TM(KERNEL_, GRID_, THREADS_, SMEM_, TM_)                                                                \
-    {                                                                                                                     \
-        if (dtype == FINO_BF16) { if (ramp) KERNEL_(BF16, 1)<<<GRID_, THREADS_, SMEM_, st>>>(fp, TM_); else KERNEL_(BF16, 0)<<<GRID_, THREADS_, SMEM_, st>>>(fp, TM_); } \
-        else { if (ramp) KERNEL_(F16, 1)<<<GRID_, THREADS_, SMEM_, st>>>(fp, TM_); else KERNEL_(F16, 0)<<<GRID_, THREADS_, SMEM_, st>>>(fp, TM_); } \
-    }
-#define F8_SMEM_ONCE(KERNEL_, SMEM_)                                                                                      \
-    {                                                                                                                     \
-        static FinoPerDeviceOnce once_[4];                                                                                \
-        const void* fn_ = dtype == FINO_BF16 ? (ramp ? (const void*)KERNEL_(BF16, 1) : (const void*)KERNEL_(BF16, 0))     \
-                                             : (ramp ? (const void*)KERNEL_(F16, 1) : (const void*)KERNEL_(F16, 0));      \
-        const int rc_ = fino_max_smem_once(once_[(dtype == FINO_BF16 ? 0 : 2) + (ramp ? 1 : 0)], fn_, SMEM_, fn); \
-        if (rc_ != FINO_OK) return rc_;                                                                                   \
-    }
-#define K_FR(T_, PX_) attn_fp8_fr_kernel<T_, PX_>
-#define K_FR_RG(T_, PX_) attn_fp8_fr_kernel<T_, PX_, true>
-#define K_D128(T_, PX_) attn_fp8_d128_kernel<T_, PX_>
-#define K_D128_TL(T_, PX_) attn_fp8_d128_kernel<T_, PX_, true>
-#define K_PP(T_, PX_) attn_fp8_kernel<T_, 0, PX_>
-        if (ranges) F8_LAUNCH(K_FR_RG, grid, kFrWaves * 64, kFrSmem + kMuSlot)
-        else F8_LAUNCH(K_FR, grid, kFrWaves * 64, kFrSmem + kMuSlot)
-        FINO_LAUNCH_CHECK();
-        return FINO_OK;
-    }
-    if (tiles) {
-        // whole blocks only (full_x covers every block, rem_x = 0 as set above); the tile list sits behind the rings and the mean slot
-        F8_SMEM_ONCE(K_D128_TL, kSmem128Tiles)
-        F8_LAUNCH_TM(K_D128_TL, grid, kWaves * 64, kSmem128Tiles, *tiles)
-        FINO_LAUNCH_CHECK();
-        return FINO_OK;
-    }
-    if (head_dim == 128) {
+        if (int rc = ranges ? fp8_launch<KFrRg>(fn, dtype, ramp, grid, kFrWaves * 64, kFrSmem + kMuSlot, st, fp)
+                            : fp8_launch<KFr>(fn, dtype, ramp, grid, kFrWaves * 64, kFrSmem + kMuSlot, st, fp))
+            return rc;
+    } else if (tiles) {
+        // whole blocks only; the tile list sits behind the rings and the mean slot
+        if (int rc = fp8_launch<KD128Tl>(fn, dtype, ramp, grid, kWaves * 64, kSmem128Tiles, st, fp, *tiles)) return rc;
+    } else if (head_dim == 128) {
         // tail split: the last, partial round of (head, q-block) workgroups is cut over the keys (fino_attention.hip's plan)
         int full_x, rem_x, nwg, per;
         fino_attn_plan_split(p.batch, p.heads, p.nqb, nt, full_x, rem_x, nwg, per);
@@ -1544,86 +1520,60 @@ static int attn_fwd_fp8_impl(const char* fn, int smooth, const void* q, const vo
             p.full_x = full_x; p.rem_x = rem_x; p.nwg = nwg; p.per = per;
         }
         const dim3 grid128((unsigned)(8 * (p.full_x + p.nwg)));
-        F8_SMEM_ONCE(K_D128, kSmem128 + kMuSlot)
-        F8_LAUNCH_TM(K_D128, grid128, kWaves * 64, kSmem128 + kMuSlot, AttnTileMask{})
+        if (int rc = fp8_launch<KD128>(fn, dtype, ramp, grid128, kWaves * 64, kSmem128 + kMuSlot, st, fp, AttnTileMask{})) return rc;
         FINO_LAUNCH_CHECK();
         return fino_attn_launch_combine(p, dtype, 128, st);
+    } else {
+        // 66 KiB of dynamic LDS
+        if (int rc = fp8_launch<KPp>(fn, dtype, ramp, grid, kWaves * 64, kSmem8 + kMuSlot, st, fp)) return rc;
     }
-    constexpr int smem = kSmem8 + kMuSlot;
-    F8_SMEM_ONCE(K_PP, smem)        // 66 KiB of dynamic LDS: above the 64 KiB a kernel gets without asking
-    F8_LAUNCH(K_PP, grid, kWaves * 64, smem)
     FINO_LAUNCH_CHECK();
     return FINO_OK;
 }
 
-extern "C" int fino_attn_fwd_fp8(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                                 int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
-                                 int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode,
-                                 void* kv_workspace, int64_t kv_workspace_bytes, void* stream) {
-    return attn_fwd_fp8_impl("fino_attn_fwd_fp8", 0, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs,
-                             o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream);
+extern "C" int fino_attn_fwd_fp8(FP8_LEAD_PARAMS, void* stream) {
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8", 0, FP8_LEAD_OPERANDS, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream);
 }
 
-extern "C" int fino_attn_fwd_fp8_smooth(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                                        int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
-                                        int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype,
-                                        int p_mode, void* kv_workspace, int64_t kv_workspace_bytes, void* stream) {
-    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smooth", FINO_FP8_SMOOTH_K, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs,
-                             k_rs, v_bs, v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream);
+extern "C" int fino_attn_fwd_fp8_smooth(FP8_LEAD_PARAMS, void* stream) {
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smooth", FINO_FP8_SMOOTH_K, FP8_LEAD_OPERANDS, dtype, p_mode, kv_workspace,
+                             kv_workspace_bytes, stream);
 }
 
 // the flag word form: smooth = 0 is fino_attn_fwd_fp8, FINO_FP8_SMOOTH_K is fino_attn_fwd_fp8_smooth, bit FINO_FP8_SMOOTH_V adds smooth V
-extern "C" int fino_attn_fwd_fp8_smoothed(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                                          int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
-                                          int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype,
-                                          int p_mode, void* kv_workspace, int64_t kv_workspace_bytes, void* stream, int smooth) {
-    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smoothed", smooth, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs, v_bs,
-                             v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream);
+extern "C" int fino_attn_fwd_fp8_smoothed(FP8_LEAD_PARAMS, void* stream, int smooth) {
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smoothed", smooth, FP8_LEAD_OPERANDS, dtype, p_mode, kv_workspace, kv_workspace_bytes,
+                             stream);
 }
 
 // fp8 attention over up to three ranges of key tiles per 256 query rows (include/frameino_hip.h): fino_attn_fwd_fp8's
 // arguments and checks + smooth_k + the device table; head_dim 64 only, always the free-running kernel's range walk.
 extern "C" int fino_attn_fp8_ranges_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim) {
-    return head_dim == 64 && batch > 0 && heads > 0 && lq > 0 && lk > 0 && lq < (1ll << 31) - 256 && lk < (1ll << 31) - 64;
+    return attn_shape_supported(batch, heads, lq, lk, head_dim, 64, false);
 }
 
-extern "C" int fino_attn_fwd_fp8_ranges(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                                        int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
-                                        int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype,
-                                        int p_mode, void* kv_workspace, int64_t kv_workspace_bytes, int smooth_k,
-                                        const int* ranges, void* stream) {
-    FINO_CHECK(ranges, FINO_ERR_ARG, "fino_attn_fwd_fp8_ranges: null ranges table");
-    FINO_CHECK(((uintptr_t)ranges & 3) == 0, FINO_ERR_ARG, "fino_attn_fwd_fp8_ranges: the ranges table must be 4-byte aligned");
+extern "C" int fino_attn_fwd_fp8_ranges(FP8_LEAD_PARAMS, int smooth_k, const int* ranges, void* stream) {
+    if (int rc = attn_check_ranges("fino_attn_fwd_fp8_ranges", ranges)) return rc;
     // smooth_k: 0 / 1 as ever; 2 and 3 = the flag word of fino_attn_fwd_fp8_smoothed.  Any other non-zero value keeps meaning 1.
     const int smooth = (smooth_k == 2 || smooth_k == 3) ? smooth_k : (smooth_k != 0 ? FINO_FP8_SMOOTH_K : 0);
-    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_ranges", smooth, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs,
-                             k_rs, v_bs, v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream, ranges);
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_ranges", smooth, FP8_LEAD_OPERANDS, dtype, p_mode, kv_workspace, kv_workspace_bytes,
+                             stream, ranges);
 }
 
 // fp8 attention over the key tiles a bitmask names per (batch element, head, 256-row q-block) (include/frameino_hip.h):
 // fino_attn_fwd_fp8_smoothed's arguments and checks + the device mask of fino_attn_fwd_tiles; head_dim 128 only, always
 // attn_fp8_d128_kernel<T, PX, true>.
 extern "C" int fino_attn_fp8_tiles_supported(int batch, int heads, int64_t lq, int64_t lk, int head_dim) {
-    return head_dim == 128 && batch > 0 && heads > 0 && lq > 0 && lk > 0 && lq < (1ll << 31) - 256 && lk < (1ll << 31) - 64 &&
-           (lk + kKV - 1) / kKV <= kAttnMaxTiles;
+    return attn_shape_supported(batch, heads, lq, lk, head_dim, 128, true);
 }
 
-extern "C" int fino_attn_fwd_fp8_tiles(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq,
-                                       int64_t lk, int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs,
-                                       int64_t v_bs, int64_t v_rs, int64_t o_bs, int64_t o_rs, float scale, int dtype,
-                                       int p_mode, void* kv_workspace, int64_t kv_workspace_bytes, int smooth,
-                                       const uint32_t* mask, int64_t mask_bs, int64_t mask_hs, int words, void* stream) {
-    FINO_CHECK(head_dim == 128, FINO_ERR_UNSUPPORTED,
-               "fino_attn_fwd_fp8_tiles: head_dim %d: the fp8 tile walk exists for head_dim 128 only", head_dim);
-    FINO_CHECK(mask, FINO_ERR_ARG, "fino_attn_fwd_fp8_tiles: null mask");
-    FINO_CHECK(((uintptr_t)mask & 3) == 0, FINO_ERR_ARG, "fino_attn_fwd_fp8_tiles: the mask must be 4-byte aligned");
-    FINO_CHECK(lk > 0 && (lk + kKV - 1) / kKV <= kAttnMaxTiles, FINO_ERR_UNSUPPORTED,
-               "fino_attn_fwd_fp8_tiles: Lk=%lld is more than %d key tiles", (long long)lk, kAttnMaxTiles);
-    FINO_CHECK(words > 0 && (int64_t)words * 32 >= (lk + kKV - 1) / kKV, FINO_ERR_ARG,
-               "fino_attn_fwd_fp8_tiles: %d mask words per q-block do not hold %lld key tiles", words,
-               (long long)((lk + kKV - 1) / kKV));
-    FINO_CHECK(mask_bs >= 0 && mask_hs >= 0, FINO_ERR_ARG, "fino_attn_fwd_fp8_tiles: negative mask stride");
+extern "C" int fino_attn_fwd_fp8_tiles(FP8_LEAD_PARAMS, int smooth, const uint32_t* mask, int64_t mask_bs, int64_t mask_hs, int words,
+                                       void* stream) {
+    const char* fn = "fino_attn_fwd_fp8_tiles";
+    FINO_CHECK(head_dim == 128, FINO_ERR_UNSUPPORTED, "%s: head_dim %d: the fp8 tile walk exists for head_dim 128 only", fn, head_dim);
+    if (int rc = attn_check_tile_mask(fn, mask, mask_bs, mask_hs, words, lk)) return rc;
     const AttnTileMask tm{mask, mask_bs, mask_hs, words};
-    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_tiles", smooth, q, k, v, o, batch, heads, lq, lk, head_dim, q_bs, q_rs, k_bs, k_rs,
-                             v_bs, v_rs, o_bs, o_rs, scale, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream, nullptr, &tm);
+    return attn_fwd_fp8_impl(fn, smooth, FP8_LEAD_OPERANDS, dtype, p_mode, kv_workspace, kv_workspace_bytes, stream, nullptr, &tm);
 }
+#undef FP8_LEAD_PARAMS
+#undef FP8_LEAD_OPERANDS

@@ -45,7 +45,6 @@ constexpr int w4_lo(int s, int n) { return s <= 0 ? 0 : (s >= n ? 32 : (32 * s +
 #ifndef W4_SEP
 #define W4_SEP        /* measured: s_setprio 0 there 1266 TFLOP/s, the recogniser's s_nop 1277 -- left to the s_nop */
 #endif
-#define W4_LDS_PTR(TYPE_, ADDR_) ((FINO_LDS TYPE_*)(uintptr_t)(uint32_t)(ADDR_))
 
 // The MFMAs go through inline asm so that the register FILE of every operand is this file's decision: O^T (128
 // registers) and the Q fragments (64) live in AGPRs for the whole kernel, S / P / the LDS fragments in VGPRs.  Left to
@@ -257,8 +256,8 @@ void attn_w4_kernel(const AttnParams p) {
 #pragma unroll
     for (int ks = 0; ks < kKS; ++ks) {
         const uint32_t a = ka_base ^ (ks << 5);
-        const u32x4_t a0 = *W4_LDS_PTR(const u32x4_t, a);
-        const u32x4_t a1 = *W4_LDS_PTR(const u32x4_t, a + 32 * D * 2);
+        const u32x4_t a0 = *LDS_PTR(const u32x4_t, a);
+        const u32x4_t a1 = *LDS_PTR(const u32x4_t, a + 32 * D * 2);
 #pragma unroll
         for (int qs = 0; qs < 2; ++qs) {
             if (ks == 0) {

@@ -255,19 +255,31 @@ def _attention_workspace(b, heads, lq, lk, dh, device):
     return ws, need
 
 
-def _attn_args(q, k, v, heads, out, scale):
+def _attn_args(q, k, v, heads, out, scale, make_out=True):
     """what the attention front ends share before the launch: q [B, Lq, H*Dh], k / v [B, Lk, H*Dh] (row-strided views) checked,
-    `out` and `scale` defaulted -> (b, lq, lk, hd, dh, out, scale)"""
+    `out` (unless the front end makes its own) and `scale` defaulted -> (b, lq, lk, hd, dh, out, scale)"""
     assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
     b, lq, hd = q.shape
     lk = k.shape[1]
     dh = hd // heads
     for t in (q, k, v):
         assert t.stride(2) == 1 and t.is_cuda
-    if out is None:
+    if out is None and make_out:
         out = torch.empty((b, lq, hd), dtype=q.dtype, device=q.device)
     scale = dh ** -0.5 if scale is None else scale
     return b, lq, lk, hd, dh, out, scale
+
+
+def _attn_lead(q, k, v, out, b, heads, lq, lk, dh, scale):
+    """fino_attn_fwd's arguments up to dtype, which its siblings repeat (head stride dh: a row holds its heads side by side)"""
+    return (_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1), dh, k.stride(0), k.stride(1), dh,
+            v.stride(0), v.stride(1), dh, out.stride(0), out.stride(1), dh, float(scale), _dt(q))
+
+
+def _attn_fp8_lead(q, k, v, out, b, heads, lq, lk, dh, scale, p_mode, ws, need):
+    """fino_attn_fwd_fp8's arguments up to kv_workspace_bytes, which its siblings repeat"""
+    return (_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+            v.stride(0), v.stride(1), out.stride(0), out.stride(1), float(scale), _dt(q), int(p_mode), _p(ws), need)
 
 
 def _check_ranges(ranges, lq):
@@ -301,10 +313,8 @@ def attention(q, k, v, heads, out=None, scale=None):
     b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
     done = _timed_attn(b, lq, lk, hd, nbytes=True)
     ws, ws_bytes = _attention_workspace(b, heads, lq, lk, dh, q.device) if SPLIT_ATTENTION_TAIL else (None, 0)
-    _lib.check(_lib.lib().fino_attn_fwd_ws(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh,
-                                          q.stride(0), q.stride(1), dh, k.stride(0), k.stride(1), dh,
-                                          v.stride(0), v.stride(1), dh, out.stride(0), out.stride(1), dh,
-                                          float(scale), _dt(q), _p(ws), ws_bytes, _stream()), "fino_attn_fwd_ws")
+    _lib.check(_lib.lib().fino_attn_fwd_ws(*_attn_lead(q, k, v, out, b, heads, lq, lk, dh, scale), _p(ws), ws_bytes, _stream()),
+               "fino_attn_fwd_ws")
     if done is not None:
         done()
     return out
@@ -332,10 +342,8 @@ def attention_ranges(q, k, v, heads, ranges, out=None, scale=None):
     b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
     _check_ranges(ranges, lq)
     done = _timed_attn(b, lq, lk, hd, ranges, nbytes=True)
-    _lib.check(_lib.lib().fino_attn_fwd_ranges(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh,
-                                              q.stride(0), q.stride(1), dh, k.stride(0), k.stride(1), dh,
-                                              v.stride(0), v.stride(1), dh, out.stride(0), out.stride(1), dh,
-                                              float(scale), _dt(q), _p(ranges), _stream()), "fino_attn_fwd_ranges")
+    _lib.check(_lib.lib().fino_attn_fwd_ranges(*_attn_lead(q, k, v, out, b, heads, lq, lk, dh, scale), _p(ranges), _stream()),
+               "fino_attn_fwd_ranges")
     if done is not None:
         done()
     return out
@@ -480,11 +488,8 @@ def attention_tiles(q, k, v, heads, mask, out=None, scale=None):
     b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
     words, mask_bs, mask_hs = _check_tile_mask(mask, b, heads, lq, lk)
     ev = _timed("attn_self")
-    _lib.check(_lib.lib().fino_attn_fwd_tiles(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh,
-                                             q.stride(0), q.stride(1), dh, k.stride(0), k.stride(1), dh,
-                                             v.stride(0), v.stride(1), dh, out.stride(0), out.stride(1), dh,
-                                             float(scale), _dt(q), _p(mask), mask_bs, mask_hs, words, _stream()),
-               "fino_attn_fwd_tiles")
+    _lib.check(_lib.lib().fino_attn_fwd_tiles(*_attn_lead(q, k, v, out, b, heads, lq, lk, dh, scale), _p(mask), mask_bs, mask_hs,
+                                             words, _stream()), "fino_attn_fwd_tiles")
     if ev is not None:
         _timed_tiles_done(ev, mask, b, heads, lq, lk, hd, dh)
     return out
@@ -505,11 +510,9 @@ def attention_tail(q, k, v, heads, lk_b, tail_mult, out=None, scale=None):
     lk_arr = (ctypes.c_int * b)(*[int(x) for x in lk_b])
     mult_arr = (ctypes.c_float * b)(*[float(x) for x in tail_mult])
     ev = _timed("attn_cross")
-    _lib.check(_lib.lib().fino_attn_fwd_tail(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh,
-                                            q.stride(0), q.stride(1), dh, k.stride(0), k.stride(1), dh,
-                                            v.stride(0), v.stride(1), dh, out.stride(0), out.stride(1), dh,
-                                            float(scale), _dt(q), ctypes.cast(lk_arr, ctypes.c_void_p),
-                                            ctypes.cast(mult_arr, ctypes.c_void_p), _stream()), "fino_attn_fwd_tail")
+    _lib.check(_lib.lib().fino_attn_fwd_tail(*_attn_lead(q, k, v, out, b, heads, lq, lk, dh, scale),
+                                            ctypes.cast(lk_arr, ctypes.c_void_p), ctypes.cast(mult_arr, ctypes.c_void_p), _stream()),
+               "fino_attn_fwd_tail")
     if ev is not None:
         ev.record()
         kt_ = KernelTimer.active
@@ -592,6 +595,15 @@ def _fp8_smooth_flags(smooth_k, smooth_v):
     return (1 if smooth_k else 0) | (2 if smooth_v else 0)
 
 
+def _attn_fp8_prepare(p_mode, smooth_k, smooth_v, b, heads, lk, dh, device):
+    """what the fp8 front ends share before the launch -> (p_mode as its FP8_P_* integer, the smooth flag word, bytes of the
+    quantised K / V images for these flags -- <= 0: no kernel for this head_dim --, their workspace)"""
+    p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
+    flags = _fp8_smooth_flags(smooth_k, smooth_v)
+    need = _lib.lib().fino_attn_fp8_smoothed_kv_bytes(b, heads, lk, dh, flags)      # flags 0 / 1: the plain / smooth-K sizes
+    return p_mode, flags, need, _attn_fp8_workspace(max(need, 0), device)
+
+
 def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=False, smooth_v=False):
     """attention() with fp8 (e4m3) matrix operands, head_dim 64 or 128: K / V quantised per call (block-scaled, V transposed), Q
     and P in registers, both products on the block-scaled fp8 MFMA, softmax and accumulation in fp32 (fino_attn_fwd_fp8).
@@ -601,18 +613,13 @@ def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=Fa
     smooth_v: subtract the mean of V over the keys before V is quantised and add it back to the normalised output in fp32
     (fino_attn_fwd_fp8_smoothed): exact, because the softmax weights sum to one; V has one scale per (channel, 32 keys), so an
     offset all keys of a channel share (a to_v bias, a DC component) stops costing mantissa bits."""
-    p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
     b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
-    flags = _fp8_smooth_flags(smooth_k, smooth_v)
-    fwd = "fino_attn_fwd_fp8_smoothed" if smooth_v else ("fino_attn_fwd_fp8_smooth" if smooth_k else "fino_attn_fwd_fp8")
-    need = _lib.lib().fino_attn_fp8_smoothed_kv_bytes(b, heads, lk, dh, flags)      # flags 0 / 1: the plain / smooth-K sizes
+    p_mode, flags, need, ws = _attn_fp8_prepare(p_mode, smooth_k, smooth_v, b, heads, lk, dh, q.device)
     if need <= 0:
         raise RuntimeError(f"attention_fp8: head_dim {dh} is not supported (64 or 128)")
-    ws = _attn_fp8_workspace(need, q.device)
+    fwd = "fino_attn_fwd_fp8_smoothed" if smooth_v else ("fino_attn_fwd_fp8_smooth" if smooth_k else "fino_attn_fwd_fp8")
     done = _timed_attn(b, lq, lk, hd)
-    _lib.check(getattr(_lib.lib(), fwd)(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
-                                        k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
-                                        float(scale), _dt(q), int(p_mode), _p(ws), need, _stream(),
+    _lib.check(getattr(_lib.lib(), fwd)(*_attn_fp8_lead(q, k, v, out, b, heads, lq, lk, dh, scale, p_mode, ws, need), _stream(),
                                         *((flags,) if smooth_v else ())), fwd)
     if done is not None:
         done()
@@ -628,18 +635,13 @@ def attention_fp8_ranges(q, k, v, heads, ranges, out=None, scale=None, p_mode=No
     per 256 query rows (fino_attn_fwd_fp8_ranges; head_dim 64 only).  K / V are quantised whole, and `smooth_k` subtracts the mean
     over ALL keys: the softmax over any subset of them cannot see it either.  `smooth_v` likewise subtracts (and adds back) the
     mean of V over ALL keys: the weights of any subset still sum to one.  A q-block without tiles gets zeros, not that mean."""
-    p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
     b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
     _check_ranges(ranges, lq)
     if dh != 64:
         raise RuntimeError(f"attention_fp8_ranges: head_dim {dh} is not supported (64 only)")
-    flags = _fp8_smooth_flags(smooth_k, smooth_v)
-    need = _lib.lib().fino_attn_fp8_smoothed_kv_bytes(b, heads, lk, dh, flags)
-    ws = _attn_fp8_workspace(need, q.device)
+    p_mode, flags, need, ws = _attn_fp8_prepare(p_mode, smooth_k, smooth_v, b, heads, lk, dh, q.device)
     done = _timed_attn(b, lq, lk, hd, ranges)
-    _lib.check(_lib.lib().fino_attn_fwd_fp8_ranges(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
-                                                  k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0),
-                                                  out.stride(1), float(scale), _dt(q), int(p_mode), _p(ws), need,
+    _lib.check(_lib.lib().fino_attn_fwd_fp8_ranges(*_attn_fp8_lead(q, k, v, out, b, heads, lq, lk, dh, scale, p_mode, ws, need),
                                                   flags, _p(ranges), _stream()), "fino_attn_fwd_fp8_ranges")
     if done is not None:
         done()
@@ -656,19 +658,14 @@ def attention_fp8_tiles(q, k, v, heads, mask, out=None, scale=None, p_mode=None,
     `smooth_k` / `smooth_v` take their means over ALL keys: exact for any subset (every logit of a query moves by the same amount;
     the weights of the walked tiles sum to one).  Bits at or beyond ceil(Lk / 64) are ignored; an empty row gives zeros, not the
     value mean."""
-    p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
     b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
     words, mask_bs, mask_hs = _check_tile_mask(mask, b, heads, lq, lk)
     if dh != 128:
         raise RuntimeError(f"attention_fp8_tiles: head_dim {dh} is not supported (the fp8 tile walk exists for head_dim 128 only)")
-    flags = _fp8_smooth_flags(smooth_k, smooth_v)
-    need = _lib.lib().fino_attn_fp8_smoothed_kv_bytes(b, heads, lk, dh, flags)
-    ws = _attn_fp8_workspace(need, q.device)
+    p_mode, flags, need, ws = _attn_fp8_prepare(p_mode, smooth_k, smooth_v, b, heads, lk, dh, q.device)
     ev = _timed("attn_self")
-    _lib.check(_lib.lib().fino_attn_fwd_fp8_tiles(_p(q), _p(k), _p(v), _p(out), b, heads, lq, lk, dh, q.stride(0), q.stride(1),
-                                                 k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0),
-                                                 out.stride(1), float(scale), _dt(q), int(p_mode), _p(ws), need, flags,
-                                                 _p(mask), mask_bs, mask_hs, words, _stream()), "fino_attn_fwd_fp8_tiles")
+    _lib.check(_lib.lib().fino_attn_fwd_fp8_tiles(*_attn_fp8_lead(q, k, v, out, b, heads, lq, lk, dh, scale, p_mode, ws, need),
+                                                 flags, _p(mask), mask_bs, mask_hs, words, _stream()), "fino_attn_fwd_fp8_tiles")
     if ev is not None:
         _timed_tiles_done(ev, mask, b, heads, lq, lk, hd, dh)
     return out
@@ -681,16 +678,10 @@ def attention_partial_floats(batch, heads, lq, head_dim):
 def attention_partial(q, k, v, heads, out=None, scale=None):
     """Attention of q [B, Lq, H*Dh] over ONE key range k/v [B, Lk, H*Dh]: -> fp32 partial buffer (unnormalised O, m, l per
     (head, q-block)) for `attention_merge`."""
-    assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3
-    b, lq, hd = q.shape
-    lk = k.shape[1]
-    dh = hd // heads
-    for t in (q, k, v):
-        assert t.stride(2) == 1 and t.is_cuda
+    b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale, make_out=False)
     need = _lib.lib().fino_attn_partial_bytes(b, heads, lq, dh)
     if out is None or out.numel() * 4 < need:
         out = torch.empty(need // 4, dtype=torch.float32, device=q.device)
-    scale = dh ** -0.5 if scale is None else scale
     _lib.check(_lib.lib().fino_attn_partial(_p(q), _p(k), _p(v), b, heads, lq, lk, dh, q.stride(0), q.stride(1), dh,
                                            k.stride(0), k.stride(1), dh, v.stride(0), v.stride(1), dh, float(scale),
                                            _dt(q), _p(out), need, _stream()), "fino_attn_partial")
