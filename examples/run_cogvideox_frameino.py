@@ -89,7 +89,10 @@ def main():
     ap.add_argument("--lora", default=None, metavar="PATH",
                     help="a LoRA adapter (local folder or .safetensors file), merged into the transformer's weights")
     ap.add_argument("--lora-scale", type=float, default=1.0, help="the adapter's scale (attention_kwargs['scale'])")
+    from frameino_amd.guiders import add_guider_arguments, guider_from_arguments
+    add_guider_arguments(ap)
     a = ap.parse_args()
+    guider = guider_from_arguments(ap, a)
     if a.mxfp6 and a.mxfp8:
         ap.error("--mxfp6 and --mxfp8: one reduced precision of the linears at a time")
     if a.mxfp6_rotate and not a.mxfp6:
@@ -138,6 +141,8 @@ def main():
             vae.enable_tiling()
         text_dim = cfg["text_embed_dim"]
         pipe = CogVideoXImageToVideoPipeline(vae=vae, transformer=transformer, scheduler=sched)
+    if guider is not None:                         # how the two CFG predictions are combined (frameino_amd/guiders.py)
+        pipe.set_guider(guider)
     if a.lora:                                     # merged before the first step: the denoise step itself is unchanged
         pipe.load_lora_weights(a.lora, adapter_name="lora")
     if a.mxfp8:

@@ -148,7 +148,10 @@ def main():
     ap.add_argument("--vae-fp32", type=int, nargs="?", const=3, default=0, metavar="PLANES",
                     help="run the VAE like the reference app does (app.py:157 loads it in fp32): fp32-compute mode on split-bf16 "
                          "products, 3 (default) or 2 bf16 planes per fp32 operand -- `vae.set_compute_dtype(torch.float32)`")
+    from frameino_amd.guiders import add_guider_arguments, guider_from_arguments
+    add_guider_arguments(ap)
     a = ap.parse_args()
+    guider = guider_from_arguments(ap, a)
     if a.mxfp6_rotate and not a.mxfp6:
         ap.error("--mxfp6-rotate needs --mxfp6")
     if a.fastercache_attention is not None and a.fastercache is None:
@@ -221,6 +224,8 @@ def main():
         vae.set_compute_dtype(torch.float32, planes=a.vae_fp32)
     pipe = WanImageToVideoPipeline(tokenizer=tokenizer, text_encoder=text_encoder, vae=vae, scheduler=sched,
                                    transformer=transformer, expand_timesteps=True)
+    if guider is not None:                         # how the two CFG predictions are combined (frameino_amd/guiders.py)
+        pipe.set_guider(guider)
     if a.lora:                                     # merged before the first step: the denoise step itself is unchanged
         pipe.load_lora_weights(a.lora, adapter_name="lora")
     if a.first_block_cache is not None:

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("FINO_LIB_PATH") or os.path.join(_HERE, "lib", "libfra
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "frameino_hip.h")
 
 c_void_p, c_int, c_i64, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+c_double = ctypes.c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPES)
 SIGNATURES = {
@@ -124,6 +125,13 @@ SIGNATURES = {
     "fino_cfg_unipc_step": [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_int, c_void_p],
     "fino_cfg_vpred_step": [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_int, c_int, c_void_p],
     "fino_cfg_dpm_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_int, c_int, c_void_p],
+    "fino_guider_workspace_bytes": [c_i64],
+    "fino_guider_coefs": [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_double, c_double, c_double, c_void_p, c_void_p,
+                          c_void_p, c_i64, c_void_p, c_int, c_void_p],
+    "fino_guided_euler_step": [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "fino_guided_unipc_step": [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p],
+    "fino_guided_vpred_step": [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p],
+    "fino_guided_dpm_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p],
     "fino_conv3d": [c_void_p] * 4 + [c_int] * 19 + [c_void_p, c_void_p, c_int, c_void_p],
     "fino_rmsnorm_silu_cl": [c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p, c_int, c_int, c_void_p],
     "fino_split_bf16": [c_void_p, c_void_p, c_i64, c_int, c_i64, c_i64, c_int, ctypes.c_uint, c_void_p],
@@ -169,7 +177,8 @@ _RESTYPES = {"fino_last_error": ctypes.c_char_p, "fino_attn_workspace_bytes": c_
              "fino_attn_partial_bytes": c_i64, "fino_attn_fp8_kv_bytes": c_i64, "fino_attn_fp8_smooth_kv_bytes": c_i64,
              "fino_attn_fp8_smoothed_kv_bytes": c_i64, "fino_mxfp6_bytes": c_i64,
              "fino_mxfp6_scale_bytes": c_i64, "fino_attn_tile_plan_bytes": c_i64,
-             "fino_attn_tile_plan_gated_bytes": c_i64, "fino_magcache_workspace_bytes": c_i64}
+             "fino_attn_tile_plan_gated_bytes": c_i64, "fino_magcache_workspace_bytes": c_i64,
+             "fino_guider_workspace_bytes": c_i64}
 
 
 # the FINO_VERSION this table (argument lists, tune-knob meanings) was written for: a stale library found through

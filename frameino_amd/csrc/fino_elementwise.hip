@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "fino_common.h"
+#include "fino_sampler_step.h"
 #include "fino_gemm_common.h"      // mx_quant8 / mx_scale_index: the MXFP8 activation layout fino_gemm_mxfp8 consumes
 
 namespace {
@@ -452,6 +453,8 @@ __global__ __launch_bounds__(256) void wan_model_input_kernel(const float* __res
     }
 }
 
+// The arithmetic of the four sampler steps lives in fino_sampler_step.h (its comments state each step), shared with the
+// guided steps of fino_guidance.hip; these kernels form v as plain CFG.
 template <typename T>
 __global__ __launch_bounds__(256) void cfg_euler_kernel(const uint16_t* __restrict__ pc,
                                                         const uint16_t* __restrict__ pu, float* __restrict__ lat,
@@ -460,100 +463,25 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(const uint16_t* __restri
     const float dt = *dt_dev;
     const int64_t total = (int64_t)C * Fg * HW;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int s = (int)(i % HW);
-        const int f = (int)((i / HW) % Fg);
-        const int c = (int)(i / ((int64_t)HW * Fg));
-        const int64_t pi = ((int64_t)c * Ft + f) * HW + s;
-        float n = T::to_f32(pc[pi]);
-        if (pu) {
-            const float u = T::to_f32(pu[pi]);
-            n = round_to<T>(u + round_to<T>(g * round_to<T>(n - u)));
-        }
-        float v = lat[i] + dt * n;
-        if (round_out) v = round_to<T>(v);
-        lat[i] = v;
-    }
+         i += (int64_t)gridDim.x * blockDim.x)
+        euler_step_elem<T>(i, pc, pu, lat, Fg, Ft, HW, CfgRounded<T>{g}, dt, round_out);
 }
 
-// CogVideoX sampler step (pipeline_cogvideox_i2v_motion_FrameINO.py:893-927 with a v-prediction DDIM step):
-//   v = u + g*(c - u) in fp32 (the reference upcasts noise_pred, :896);  x0 = T(sa*x) - sb*v;  x' = T(T(ca*x) + cb*x0)
-//   (x is the T-typed latent; products of x with the scheduler's 0-dim coefficients stay in T under torch promotion).
-// coef = {sa, sb, ca, cb, g} on the device.  pred: [2, Ft, C*HW] (uncond, cond), lat: [Fg, C*HW] in place.
 template <typename T>
 __global__ __launch_bounds__(256) void cfg_vpred_step_kernel(const uint16_t* __restrict__ pred,
                                                              uint16_t* __restrict__ lat, int64_t n_lat,
                                                              int64_t batch_stride, const float* __restrict__ coef,
                                                              int has_uncond) {
-    const float sa = coef[0], sb = coef[1], ca = coef[2], cb = coef[3], g = coef[4];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lat; i += (int64_t)gridDim.x * blockDim.x) {
-        float v;
-        if (has_uncond) {
-            const float u = T::to_f32(pred[i]);
-            const float c = T::to_f32(pred[batch_stride + i]);
-            v = u + g * (c - u);
-        } else {
-            v = T::to_f32(pred[i]);
-        }
-        const float x = T::to_f32(lat[i]);
-        const float x0 = round_to<T>(sa * x) - sb * v;
-        lat[i] = T::from_f32(round_to<T>(ca * x) + cb * x0);
-    }
+    vpred_step_body<T>(pred, lat, n_lat, batch_stride, coef[0], coef[1], coef[2], coef[3], CfgF32{coef[4]}, has_uncond,
+                       FINO_GRID_STRIDE());
 }
 
-// CogVideoXDPMScheduler.step (diffusers, third-party; the sampler the CogVideoX-5B-I2V repo ships and the reference's
-// training-time validation builds, train_code/train_cogvideox_motion_FrameINO.py:692; pipeline call site :915-926):
-// SDE-DPM-Solver++ (2M) on v-prediction, fused with CFG.  Linear in {x, v, x0_old, noise}; the host folds the step's
-// scalars into coef = {sa, sb, m1, m2, m3, m4, mn, g, use_old}:
-//   v  = u + g*(c-u) (fp32: the pipeline takes noise_pred.float(), :897);  x0 = T(sa*x) - sb*v            (fp32)
-//   d  = use_old ? m3*x0 - m4*x0_old : x0;   x' = T( T(m1*x) - m2*d + T(mn*noise) );   x0_old <- x0
-// (products of the T-typed latent / noise with the scheduler's 0-dim coefficients stay in T under torch promotion.)
 template <typename T>
 __global__ __launch_bounds__(256) void cfg_dpm_step_kernel(const uint16_t* __restrict__ pred, uint16_t* __restrict__ lat,
                                                            float* __restrict__ x0_old, const uint16_t* __restrict__ noise,
                                                            int64_t n_lat, int64_t batch_stride,
                                                            const float* __restrict__ coef, int has_uncond) {
-    const float sa = coef[0], sb = coef[1], m1 = coef[2], m2 = coef[3], m3 = coef[4], m4 = coef[5], mn = coef[6];
-    const float g = coef[7];
-    const bool use_old = coef[8] != 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_lat; i += (int64_t)gridDim.x * blockDim.x) {
-        float v;
-        if (has_uncond) {
-            const float u = T::to_f32(pred[i]);
-            const float c = T::to_f32(pred[batch_stride + i]);
-            v = u + g * (c - u);
-        } else {
-            v = T::to_f32(pred[i]);
-        }
-        const float x = T::to_f32(lat[i]);
-        const float x0 = round_to<T>(sa * x) - sb * v;
-        const float d = use_old ? m3 * x0 - m4 * x0_old[i] : x0;
-        const float nz = round_to<T>(mn * T::to_f32(noise[i]));
-        lat[i] = T::from_f32(round_to<T>(m1 * x) - m2 * d + nz);
-        x0_old[i] = x0;
-    }
-}
-
-// UniPC (bh2, predict-x0, flow sigmas) multistep update fused with CFG, one pass over the latents
-// (diffusers UniPCMultistepScheduler.step as Wan2.2-TI2V-5B-Diffusers configures it; pipeline :882-891).
-// Every tensor op of the published algorithm is linear in {x, last_sample, m0, m1, v}; the host folds the step's
-// scalars into coef = {g, sigma, use_corr, Cx, C0, C1, Ct, Px, P0, P1}:
-//   v   = T(u + T(g*T(c-u)));  m_t = x - T(sigma*v)                         (convert_model_output, flow prediction)
-//   x_c = use_corr ? Cx*last + C0*m0 + C1*m1 + Ct*m_t : x                    (multistep_uni_c_bh_update)
-//   x'  = Px*x_c + P0*m_t + P1*m0                                            (multistep_uni_p_bh_update)
-//   last <- x_c;  m1 <- m0;  m0 <- m_t;  x <- x'
-// `sigma_t * model_output` as torch evaluates it on this device: the exact product rounded ONCE to T.  For fp16 torch's
-// compiled elementwise product is one v_fma_mixlo_f16 (no fp32 rounding in between; tests/test_kernels_gpu.py::test_cfg_unipc_step),
-// for bf16 the fp32 product rounded to bf16.
-template <typename T>
-__device__ __forceinline__ float round_product(float a, float b) {
-    if constexpr (std::is_same<T, F16>::value) {
-        uint32_t r = 0;
-        asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "+v"(r) : "v"(a), "v"(b));
-        return F16::to_f32((uint16_t)r);
-    } else {
-        return round_to<T>(a * b);
-    }
+    dpm_step_body<T, CfgF32>(pred, lat, x0_old, noise, n_lat, batch_stride, coef, coef + 7, has_uncond, FINO_GRID_STRIDE());
 }
 
 template <typename T>
@@ -565,24 +493,9 @@ __global__ __launch_bounds__(256) void cfg_unipc_kernel(const uint16_t* __restri
     const float Cx = coef[3], C0 = coef[4], C1 = coef[5], Ct = coef[6], Px = coef[7], P0 = coef[8], P1 = coef[9];
     const int64_t total = (int64_t)C * Fg * HW;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int s = (int)(i % HW);
-        const int f = (int)((i / HW) % Fg);
-        const int c = (int)(i / ((int64_t)HW * Fg));
-        const int64_t pi = ((int64_t)c * Ft + f) * HW + s;
-        float v = T::to_f32(pc[pi]);
-        if (pu) {
-            const float u = T::to_f32(pu[pi]);
-            v = round_to<T>(u + round_to<T>(g * round_to<T>(v - u)));
-        }
-        const float xv = x[i], a0 = m0[i];
-        const float mt = xv - round_product<T>(sigma, v);
-        const float xc = use_corr != 0.f ? Cx * last[i] + C0 * a0 + C1 * m1[i] + Ct * mt : xv;
-        x[i] = Px * xc + P0 * mt + P1 * a0;
-        last[i] = xc;
-        m1[i] = a0;
-        m0[i] = mt;
-    }
+         i += (int64_t)gridDim.x * blockDim.x)
+        unipc_step_elem<T>(i, pc, pu, x, last, m0, m1, Fg, Ft, HW, sigma, use_corr, Cx, C0, C1, Ct, Px, P0, P1,
+                           CfgRounded<T>{g});
 }
 
 template <int NPmax, typename F>

@@ -1001,6 +1001,86 @@ def cfg_dpm_step_(lat, pred, x0_old, noise, coef_dev, has_uncond=True):
     return lat
 
 
+# ---- guiders (frameino_amd/guiders.py): {A, B} of v = A c + B u on the device, and the guided siblings of the four steps
+def guider_workspace_bytes(n):
+    """bytes of the caller-owned workspace of guider_coefs over a sample of n elements"""
+    return int(_lib.lib().fino_guider_workspace_bytes(int(n)))
+
+
+def _guider_launch(cond, uncond, rows, row_len, row_stride, args, g_dev, zero_dev, workspace, ab):
+    kind, norm_threshold, eta, rescale = args
+    assert ab.dtype == torch.float32 and ab.numel() >= 2 and ab.is_contiguous() and workspace.is_contiguous()
+    assert g_dev.dtype == torch.float32 and g_dev.numel() >= 1 and (zero_dev is None or zero_dev.dtype == torch.float32)
+    assert g_dev.device == ab.device == workspace.device == cond.device
+    _lib.check(_lib.lib().fino_guider_coefs(_p(cond), _p(uncond), rows, row_len, row_stride, int(kind), float(norm_threshold),
+                                           float(eta), float(rescale), _p(g_dev), _p(zero_dev), _p(workspace),
+                                           workspace.numel() * workspace.element_size(), _p(ab), _dt(cond), _stream()),
+               "fino_guider_coefs")
+    return ab
+
+
+def guider_coefs(cond_pred, uncond_pred, gen_frames, args, g_dev, zero_dev, workspace, ab):
+    """Wan layout: preds [C, Ft, H, W] of T, the first gen_frames frames of every channel are the sample (ID frames excluded).
+    args = guiders.kernel_args(config); g_dev / zero_dev: one fp32 each on the device (zero_dev may be None); writes ab[0:2]."""
+    c, ft, h, w = cond_pred.shape
+    assert cond_pred.is_contiguous() and uncond_pred.is_contiguous() and uncond_pred.shape == cond_pred.shape
+    assert cond_pred.dtype == uncond_pred.dtype and 1 <= gen_frames <= ft
+    return _guider_launch(cond_pred, uncond_pred, c, gen_frames * h * w, ft * h * w, args, g_dev, zero_dev, workspace, ab)
+
+
+def guider_coefs_rows(pred, n_lat, args, g_dev, zero_dev, workspace, ab):
+    """CogVideoX layout: pred [2, ...] of T (uncond, cond), the first n_lat elements of each row are the sample."""
+    assert pred.is_contiguous() and pred.shape[0] == 2 and 1 <= n_lat <= pred[0].numel()
+    return _guider_launch(pred[1], pred[0], 1, int(n_lat), pred[0].numel(), args, g_dev, zero_dev, workspace, ab)
+
+
+def guided_euler_step_(lat, cond_pred, uncond_pred, ab, dt_dev, round_out=True):
+    """cfg_euler_step_ with v = T(A c + B u) from ab = {A, B} (device fp32[2])."""
+    c, fg, h, w = lat.shape
+    ft = cond_pred.shape[1]
+    assert lat.dtype == torch.float32 and lat.is_contiguous() and cond_pred.is_contiguous() and uncond_pred.is_contiguous()
+    assert cond_pred.shape == uncond_pred.shape == (c, ft, h, w) and ft >= fg
+    assert dt_dev.dtype == torch.float32 and dt_dev.is_cuda and ab.dtype == torch.float32 and ab.numel() >= 2
+    _lib.check(_lib.lib().fino_guided_euler_step(_p(cond_pred), _p(uncond_pred), _p(lat), c, fg, ft, h, w, _p(ab), _p(dt_dev),
+                                                int(round_out), _dt(cond_pred), _stream()), "fino_guided_euler_step")
+    return lat
+
+
+def guided_unipc_step_(x, last, m0, m1, cond_pred, uncond_pred, coef_dev, ab):
+    """cfg_unipc_step_ with v = T(A c + B u) from ab = {A, B} (device fp32[2]); coef_dev[0] (g) is not read."""
+    c, fg, h, w = x.shape
+    ft = cond_pred.shape[1]
+    for t in (x, last, m0, m1):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape
+    assert coef_dev.dtype == torch.float32 and coef_dev.numel() >= 10 and cond_pred.is_contiguous()
+    assert uncond_pred.is_contiguous() and cond_pred.shape == uncond_pred.shape == (c, ft, h, w) and ft >= fg
+    assert ab.dtype == torch.float32 and ab.numel() >= 2
+    _lib.check(_lib.lib().fino_guided_unipc_step(_p(cond_pred), _p(uncond_pred), _p(x), _p(last), _p(m0), _p(m1), c, fg, ft, h,
+                                                w, _p(coef_dev), _p(ab), _dt(cond_pred), _stream()), "fino_guided_unipc_step")
+    return x
+
+
+def guided_vpred_step_(lat, pred, coef_dev, ab):
+    """cfg_vpred_step_ with v = A c + B u (fp32) from ab = {A, B} (device fp32[2]); coef_dev[4] (g) is not read."""
+    assert lat.is_contiguous() and pred.is_contiguous() and coef_dev.dtype == torch.float32 and lat.dtype == pred.dtype
+    assert pred.shape[0] == 2 and pred[0].numel() >= lat.numel() and coef_dev.numel() >= 4
+    assert ab.dtype == torch.float32 and ab.numel() >= 2
+    _lib.check(_lib.lib().fino_guided_vpred_step(_p(pred), _p(lat), lat.numel(), pred[0].numel(), _p(coef_dev), _p(ab),
+                                                _dt(lat), _stream()), "fino_guided_vpred_step")
+    return lat
+
+
+def guided_dpm_step_(lat, pred, x0_old, noise, coef_dev, ab):
+    """cfg_dpm_step_ with v = A c + B u (fp32) from ab = {A, B} (device fp32[2]); coef_dev[7] (g) is not read."""
+    assert lat.is_contiguous() and pred.is_contiguous() and noise.is_contiguous() and x0_old.is_contiguous()
+    assert coef_dev.dtype == torch.float32 and coef_dev.numel() >= 9 and lat.dtype == pred.dtype == noise.dtype
+    assert x0_old.dtype == torch.float32 and x0_old.numel() == lat.numel() == noise.numel()
+    assert pred.shape[0] == 2 and pred[0].numel() >= lat.numel() and ab.dtype == torch.float32 and ab.numel() >= 2
+    _lib.check(_lib.lib().fino_guided_dpm_step(_p(pred), _p(lat), _p(x0_old), _p(noise), lat.numel(), pred[0].numel(),
+                                              _p(coef_dev), _p(ab), _dt(lat), _stream()), "fino_guided_dpm_step")
+    return lat
+
+
 # ------------------------------------------------------------------------------------------------ Wan VAE (channels-last)
 _ZERO_PAGE = {}
 

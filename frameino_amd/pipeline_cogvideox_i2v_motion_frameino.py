@@ -18,6 +18,11 @@ current_timestep_callback=lambda: pipe.current_timestep))`, frameino_amd/step_ca
 runs eagerly (`use_hip_graph = True` raises; graph replay returns after `disable_cache()`).  The cache state starts fresh in every
 single-video loop and is dropped at its end and by `maybe_free_model_hooks()`; `transformer.cache_log` keeps the last loop's
 decisions.
+
+Guiders (`pipe.set_guider(CFGZeroStarConfig() | AdaptiveProjectedGuidanceConfig() | GuidanceRescaleConfig())`,
+frameino_amd/guiders.py) replace the CFG combine of a guided call: `fino_guider_coefs` (two small launches, no host read; the
+guidance scale is the coefficient row's, `use_dynamic_cfg` included) and the `fino_guided_vpred_step` / `fino_guided_dpm_step`
+sibling of the step kernel; the loop is captured as before.
 """
 import contextlib
 import math
@@ -26,6 +31,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
+from .guiders import GuiderPipelineMixin
 from .lora import LoraPipelineMixin, lora_denoise_loop
 from .window_attention import window_attention_runs_eagerly
 from .schedulers import CogVideoXDDIMScheduler  # noqa: F401  (re-export)
@@ -91,7 +97,7 @@ def _one_generator(generator, batch_size=1):
     return generator
 
 
-class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
+class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
     extend_rope_by_first_frame = True             # :834-839 (the ID frame reuses the first frame's RoPE rows)
 
@@ -272,6 +278,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         dev, dt = latents.device, tr.dtype
         win_eager = self._window_attention_check()
         cached = self._step_cache_check()
+        guider = self._guider_check()
         if latents.shape[0] != 1:
             # A batch (a list of prompts, batched `prompt_embeds` / `latents`) runs video by video: the loop state -- the static
             # model-input buffer, the sampler history, the captured graph -- is one video's.  The videos of a batched loop never
@@ -335,6 +342,10 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         st.coef = torch.zeros(coefs.shape[1], dtype=torch.float32, device=dev)
         st.x0_old = torch.zeros(lat.shape, dtype=torch.float32, device=dev) if dpm else None
         st.noise = torch.zeros_like(lat) if dpm else None
+        # a guider (frameino_amd/guiders.py) reads the step's guidance scale where the coefficient row carries it
+        g_slot = 7 if dpm else 4
+        st.guider = self._guider_state(ops, guider, lat.numel(), st.coef[g_slot:g_slot + 1], len(ts), dev) \
+            if guider is not None and cfg_on else None
         from .graph_step import StepGraph
         from .pipeline_wan_i2v_motion_frameino import tr_default_procs
         stepper = StepGraph(lambda: self._step(st), self.use_hip_graph,
@@ -348,6 +359,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
             st.coef.copy_(coefs[i])
             if dpm:
                 st.noise.copy_(self.scheduler.noise(i, lat.shape, generator, dev, dt))
+            self._guider_begin_step(st.guider, i)
             stepper.step()
             if callback_on_step_end is not None:
                 out = callback_on_step_end(self, i, t, {"latents": lat[None]})
@@ -373,7 +385,16 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         with ctx:
             pred = self.transformer(hidden_states=st.x, encoder_hidden_states=st.prompt, timestep=st.t,
                                     image_rotary_emb=st.rot, attention_kwargs=st.attention_kwargs, return_dict=False, **live)[0]
-        if st.dpm:
+        gs = getattr(st, "guider", None)
+        if gs is not None:
+            # {A, B} of v = A c + B u from the moments of the generated frames, on the device, then the step's guided sibling
+            pred = pred.contiguous()
+            ops.guider_coefs_rows(pred, st.lat.numel(), gs.args, gs.g, gs.zero, gs.workspace, gs.ab)
+            if st.dpm:
+                ops.guided_dpm_step_(st.lat, pred, st.x0_old, st.noise, st.coef, gs.ab)
+            else:
+                ops.guided_vpred_step_(st.lat, pred, st.coef, gs.ab)
+        elif st.dpm:
             ops.cfg_dpm_step_(st.lat, pred.contiguous(), st.x0_old, st.noise, st.coef, has_uncond=st.cfg_on)
         else:
             ops.cfg_vpred_step_(st.lat, pred.contiguous(), st.coef, has_uncond=st.cfg_on)       # :896-927
@@ -459,6 +480,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin):
         self.check_inputs(image, prompt, height, width, negative_prompt, callback_on_step_end_tensor_inputs, latents,
                           prompt_embeds, negative_prompt_embeds)
         self._step_cache_check()
+        self._guider_check()
         # The reference overwrites `num_videos_per_prompt` with 1 (:723) and its loop breaks on more than one prompt (the
         # trajectory / identity latents are batch 1, :803-826 against torch.cat at :872-880); here a list of B prompts (or
         # B rows of `prompt_embeds`) makes B videos, run video by video in `denoise` (the Wan mirror does the same).

@@ -42,6 +42,12 @@ eager loop, one GPU, fresh state per `denoise`, a batch sample by sample; which 
 counter alone, which rows a partial step runs on the kept prediction (on the device: no host read).  The batched CFG call shares
 one list of active rows; the loop's `live_rows` keep the first frame and the ID frame off it.  A call whose step count differs
 from the config's warns: the full steps at the end are counted from the config's figure.
+
+Guiders (`pipe.set_guider(CFGZeroStarConfig() | AdaptiveProjectedGuidanceConfig() | GuidanceRescaleConfig())`,
+frameino_amd/guiders.py) replace the CFG combine of a guided call: `fino_guider_coefs` (two small launches, no host read) and the
+`fino_guided_euler_step` / `fino_guided_unipc_step` sibling of the step kernel; the loop is captured as before, and every option
+above composes with it.  The moments cover all generated frames, the first one included: under a guider `live_rows` keeps only
+the ID frames off the last block.  One GPU (a parallel plan raises NotImplementedError).
 """
 import html
 import re
@@ -52,6 +58,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .guiders import GuiderPipelineMixin
 from .lora import LoraPipelineMixin, lora_denoise_loop
 from .window_attention import window_attention_runs_eagerly
 
@@ -114,7 +121,7 @@ def tr_default_procs(transformer):
     return bool(f()) if callable(f) else True
 
 
-class WanImageToVideoPipeline(LoraPipelineMixin):
+class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
     model_cpu_offload_seq = "text_encoder->image_encoder->transformer->transformer_2->vae"
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
 
@@ -454,7 +461,17 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         else:
             pc = fwd("cond", st.pe)
             pu = fwd("uncond", st.ne) if st.cfg else None
-        if st.unipc is not None:
+        gs = getattr(st, "guider", None)
+        if gs is not None:
+            # a guider (frameino_amd/guiders.py): {A, B} of v = A c + B u from the moments of the generated frames, on the device,
+            # then the step's guided sibling
+            o.guider_coefs(pc, pu, st.lat.shape[1], gs.args, gs.g, gs.zero, gs.workspace, gs.ab)
+            if st.unipc is not None:
+                o.guided_unipc_step_(st.lat, *st.unipc, pc, pu, st.coef, gs.ab)
+            else:
+                o.guided_euler_step_(st.lat, pc, pu, gs.ab, st.dt,
+                                     round_out=getattr(self.scheduler, "cast_output_to_model_dtype", True))
+        elif st.unipc is not None:
             # the sampler the released Wan2.2 folder ships: corrector + predictor + CFG in one pass
             o.cfg_unipc_step_(st.lat, *st.unipc, pc, pu, st.coef)
         else:
@@ -503,6 +520,23 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         st.attention_kwargs = attention_kwargs
         return st
 
+    def _attach_guider(self, st, guider, num_steps):
+        """The guider's part of the loop state `st` (None: none, or the call does not guide).  A guider takes its moments over
+        ALL Fg generated frames, the first one included -- so with a guider the first frame's prediction is read, and
+        `live_rows` may only keep the ID frames off the last block: what the guider sees, and with it the video, does not
+        depend on whether the transformer honours `live_rows` (skip_dead_rows, a callback, a cache or a precision that does
+        not)."""
+        st.guider = None
+        if guider is None or not st.cfg:
+            return
+        dev = st.lat.device
+        # the step's guidance scale in device memory: the UniPC row carries it, the Euler loop gets a slot of its own
+        g_dev = st.coef[0:1] if st.unipc is not None else torch.full((1,), st.guidance, dtype=torch.float32, device=dev)
+        st.guider = self._guider_state(self.transformer.ops, guider, st.lat.numel(), g_dev, num_steps, dev)
+        if st.live_rows is not None:
+            hi = st.live_rows[1]
+            st.live_rows = (0, hi) if hi < st.sel.numel() else None
+
     @lora_denoise_loop
     def denoise(self, latents, condition, traj_latents, id_latent, first_frame_mask, prompt_embeds,
                 negative_prompt_embeds, guidance_scale, num_inference_steps, attention_kwargs=None,
@@ -514,6 +548,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         cache state."""
         cached = self._step_cache_check(latents.shape[0])
         win_eager = self._window_attention_check()
+        guider = self._guider_check()
         if cached:
             self.transformer._reset_stateful_cache()
         if latents.shape[0] > 1:
@@ -542,6 +577,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
             dts = self.scheduler.dts.to(dev)
         ts_dev = timesteps.to(dev).float()
         self._num_timesteps = len(timesteps)
+        self._attach_guider(st, guider, len(timesteps))
         if cached and getattr(self.transformer, "_mag_on", False):
             planned = int(self.transformer._step_cache_config.num_inference_steps)
             if planned != len(timesteps):       # once per call: the curve is indexed by the step counter
@@ -575,6 +611,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
                 st.coef.copy_(coefs[i])
             else:
                 st.dt.copy_(dts[i:i + 1])
+            self._guider_begin_step(st.guider, i)
             stepper.step()
             if callback_on_step_end is not None:
                 latents = st.lat[None]
@@ -614,6 +651,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin):
         else:
             batch_size = prompt_embeds.shape[0]
         self._step_cache_check(batch_size * num_videos_per_prompt)
+        self._guider_check()
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(
             prompt, negative_prompt, self.do_classifier_free_guidance, num_videos_per_prompt, prompt_embeds,
             negative_prompt_embeds, max_sequence_length, device)

@@ -487,6 +487,51 @@ int fino_cfg_vpred_step(const void* pred, void* lat, int64_t n_lat, int64_t batc
 int fino_cfg_dpm_step(const void* pred, void* lat, float* x0_old, const void* noise, int64_t n_lat, int64_t batch_stride,
                       const float* coef_dev, int has_uncond, int dtype, void* stream);
 
+/* ---- guiders: CFG-Zero*, adaptive projected guidance, guidance rescale (frameino_amd/guiders.py) -------------------
+ * A guider combines the two predictions of one sample as v = A c + B u.  {A, B} depend on five global moments of (c, u)
+ * over exactly the n elements the step kernel updates -- Sc, Su, Scc, Suu, Scu; elements of T read as fp32, sums in fp64 --
+ * on the step's guidance scale g and on the guider:
+ *   FINO_GUIDER_RESCALE    A0 = g, B0 = 1 - g                                                        (plain CFG)
+ *   FINO_GUIDER_ZERO_STAR  s = Scu / (Suu + 1e-8);  A0 = g, B0 = (1 - g) s       [*zero_init_dev != 0: A = B = 0, no rescale]
+ *   FINO_GUIDER_APG        dd = Scc - 2 Scu + Suu;  s = norm_threshold <= 0 or dd <= 0 ? 1 : min(1, norm_threshold / sqrt(dd));
+ *                          p = Scc > 0 ? s (Scc - Scu) / Scc : 0;  A0 = g (s + (eta - 1) p), B0 = 1 - g s
+ * and, with guidance_rescale = phi > 0, on the unbiased variances var_c = (Scc - Sc^2 / n) / (n - 1), var_u, cov (variances
+ * clamped at 0):  var_p = A0^2 var_c + B0^2 var_u + 2 A0 B0 cov;  f = n < 2 or var_p <= 0 ? 1 : sqrt(var_c / var_p);
+ * m = phi f + 1 - phi;  A = m A0, B = m B0.  All of it in fp64, {A, B} stored as fp32 in ab_dev[0..1].
+ *
+ * The sample is `rows` runs of `row_len` contiguous elements of T, `row_stride` elements apart, at the same offsets in
+ * cond_pred and uncond_pred:
+ *   Wan        preds [C, Fg + n_id, H, W], ID frames excluded: rows = C, row_len = Fg H W, row_stride = (Fg + n_id) H W
+ *   CogVideoX  pred [2, batch_stride] (uncond, cond): uncond_pred = pred, cond_pred = pred + batch_stride, rows = 1,
+ *              row_len = n_lat
+ * g_dev (one float) and zero_init_dev (one float, or NULL: never) are read on the device: a captured step replays the call
+ * and the loop refreshes them by device copies.  Two launches (per-workgroup partial moments into `workspace`, then one
+ * workgroup that adds them in a fixed order and evaluates the formulas); no atomics: the same input gives the same bits.
+ * workspace: fino_guider_workspace_bytes(rows * row_len) bytes, 8-byte aligned, caller-owned (0: n out of range). */
+#define FINO_GUIDER_RESCALE 0
+#define FINO_GUIDER_ZERO_STAR 1
+#define FINO_GUIDER_APG 2
+int64_t fino_guider_workspace_bytes(int64_t n);
+int fino_guider_coefs(const void* cond_pred, const void* uncond_pred, int64_t rows, int64_t row_len, int64_t row_stride,
+                      int kind, double norm_threshold, double eta, double guidance_rescale, const float* g_dev,
+                      const float* zero_init_dev, void* workspace, int64_t workspace_bytes, float* ab_dev, int dtype,
+                      void* stream);
+
+/* The four sampler steps with v = fl(fl(A c) + fl(B u)) in fp32 from ab_dev = {A, B} (device) in the place of the CFG value:
+ * rounded to T first where that value is a T value (Euler, UniPC), in fp32 where it is fp32 (the two CogVideoX steps).
+ * Everything else is the sibling fino_cfg_*_step's arithmetic and arguments; the guidance value of the sibling (the
+ * `guidance` argument, the g entry of coef_dev) is not read, and both predictions are required. */
+int fino_guided_euler_step(const void* cond_pred, const void* uncond_pred, float* lat, int channels, int gen_frames,
+                           int total_frames, int height, int width, const float* ab_dev, const float* dt_dev, int round_out,
+                           int dtype, void* stream);
+int fino_guided_unipc_step(const void* cond_pred, const void* uncond_pred, float* x, float* last, float* m0, float* m1,
+                           int channels, int gen_frames, int total_frames, int height, int width, const float* coef_dev,
+                           const float* ab_dev, int dtype, void* stream);
+int fino_guided_vpred_step(const void* pred, void* lat, int64_t n_lat, int64_t batch_stride, const float* coef_dev,
+                           const float* ab_dev, int dtype, void* stream);
+int fino_guided_dpm_step(const void* pred, void* lat, float* x0_old, const void* noise, int64_t n_lat, int64_t batch_stride,
+                         const float* coef_dev, const float* ab_dev, int dtype, void* stream);
+
 /* ---- Wan 3D causal VAE (architecture/autoencoder_kl_wan.py) ------------------------------------------------------
  * Activations are channels-last [T, H, W, Cpad] of `dtype`, Cpad = channels zero-padded to a multiple of 64.
  * fino_conv3d: implicit-GEMM convolution (MFMA-bound) -- WanCausalConv3d (:134-176), the Conv2d of WanResample
