@@ -76,53 +76,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
             pos_w[j] = rem - pos_h[j] * p.wo;
         }
     }
-    auto stage = [&](int buf, int kt) {
-        char* ab = smem + buf * kStageBytes;
-        char* wb = ab + kTileBytes;
-        const int64_t k0 = (int64_t)kt * BK;
-        if constexpr (CONV) {
-            const int tap = kt / p.cin_chunks;
-            const int c0 = (kt - tap * p.cin_chunks) * BK;
-            const int dw = tap % p.kw;
-            const int dh = (tap / p.kw) % p.kh;
-            const int dt = tap / (p.kw * p.kh);
-            const int hlim = p.up ? 2 * p.hi : p.hi, wlim = p.up ? 2 * p.wi : p.wi;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int ti = pos_t[j] * p.st + dt - p.pt;
-                int hi = pos_h[j] * p.sh + dh - p.ph;
-                int wi = pos_w[j] * p.sw + dw - p.pw;
-                const bool ok = a_ok[j] && ti >= 0 && ti < p.ti && hi >= 0 && hi < hlim && wi >= 0 && wi < wlim;
-                if (p.up) { hi >>= 1; wi >>= 1; }
-                const uint16_t* src = ok ? p.a + (((int64_t)ti * p.hi + hi) * p.wi + wi) * p.lda + c0 + sk[j]
-                                         : p.zero_page + sk[j];
-                __builtin_amdgcn_global_load_lds((const FINO_GLB void*)src,
-                                                 (FINO_LDS void*)(ab + j * 8192 + wave * 1024), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((const FINO_GLB void*)(w_src[j] + k0),
-                                                 (FINO_LDS void*)(wb + j * 8192 + wave * 1024), 16, 0, 0);
-            }
-        } else if constexpr (!GENERIC) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                __builtin_amdgcn_global_load_lds((const FINO_GLB void*)(a_src[j] + k0),
-                                                 (FINO_LDS void*)(ab + j * 8192 + wave * 1024), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((const FINO_GLB void*)(w_src[j] + k0),
-                                                 (FINO_LDS void*)(wb + j * 8192 + wave * 1024), 16, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool kin = k0 + sk[j] < p.k;
-                uint4 va = make_uint4(0, 0, 0, 0), vw = make_uint4(0, 0, 0, 0);
-                if (kin && a_ok[j]) va = *reinterpret_cast<const uint4*>(a_src[j] + k0);
-                if (kin && w_ok[j]) vw = *reinterpret_cast<const uint4*>(w_src[j] + k0);
-                *reinterpret_cast<uint4*>(ab + j * 8192 + tid * 16) = va;
-                *reinterpret_cast<uint4*>(wb + j * 8192 + tid * 16) = vw;
-            }
-        }
-    };
-
     // one LDS-DMA piece (one wave-instruction = 8 tile rows) of K-tile `kt`: pieces 0..3 = A rounds, 4..7 = W rounds
+    // (the three DMA forms of this kernel: W rows, the CONV gather of A with its tap decode, plain A rows)
     auto stage_piece = [&](int buf, int kt, int piece) {
         char* ab = smem + buf * kStageBytes;
         char* wb = ab + kTileBytes;
@@ -152,6 +107,30 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
                                              (FINO_LDS void*)(ab + j * 8192 + wave * 1024), 16, 0, 0);
         }
     };
+    // a whole K-tile: GENERIC through registers (predicated, zero-filled), the DMA variants as their eight pieces, A and W
+    // round by round
+    auto stage = [&](int buf, int kt) {
+        if constexpr (GENERIC) {
+            char* ab = smem + buf * kStageBytes;
+            char* wb = ab + kTileBytes;
+            const int64_t k0 = (int64_t)kt * BK;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool kin = k0 + sk[j] < p.k;
+                uint4 va = make_uint4(0, 0, 0, 0), vw = make_uint4(0, 0, 0, 0);
+                if (kin && a_ok[j]) va = *reinterpret_cast<const uint4*>(a_src[j] + k0);
+                if (kin && w_ok[j]) vw = *reinterpret_cast<const uint4*>(w_src[j] + k0);
+                *reinterpret_cast<uint4*>(ab + j * 8192 + tid * 16) = va;
+                *reinterpret_cast<uint4*>(wb + j * 8192 + tid * 16) = vw;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                stage_piece(buf, kt, j);
+                stage_piece(buf, kt, 4 + j);
+            }
+        }
+    };
 
     // ---- fragment read addressing: row = base + 16*tile + (lane&15), chunk = (4*kk + (lane>>4)) ^ swz(row) ----
     const int frow = lane & 15;
@@ -166,18 +145,16 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const int nk = (int)((p.k + BK - 1) / BK);
-#define LOAD_FRAGS(SB_, KK_, WF_, AF_)                                                                           \
-    {                                                                                                            \
-        const int pch_ = (pch0 ^ ((KK_) << 2)) << 4;                                                             \
-        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                         \
-            WF_[j_] = *reinterpret_cast<const u32x4_t*>((SB_) + w_base + j_ * 2048 + pch_);                      \
-        _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_)                                                         \
-            AF_[i_] = *reinterpret_cast<const u32x4_t*>((SB_) + a_base + i_ * 2048 + pch_);                      \
-    }
-#define MFMA_BLOCK(WF_, AF_)                                                                                     \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_)                                                             \
-        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                         \
-            acc[i_][j_] = T::mfma16(__builtin_bit_cast(vec8, WF_[j_]), __builtin_bit_cast(vec8, AF_[i_]), acc[i_][j_]);
+    // The pieces both loops are made of: the byte offset of k-step KK_'s chunk in a fragment row, the fragment reads at that
+    // offset of the stage at SB_ (the four W fragments; A fragment I_), and the four MFMAs of A fragment AF_[I_].
+#define FRAG_OFF(KK_) ((pch0 ^ ((KK_) << 2)) << 4)
+#define LD_W(SB_, OFF_, WF_)                                                                                      \
+    _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                              \
+        WF_[j_] = *reinterpret_cast<const u32x4_t*>((SB_) + w_base + j_ * 2048 + (OFF_));
+#define LD_A(SB_, OFF_, I_) (*reinterpret_cast<const u32x4_t*>((SB_) + a_base + (I_) * 2048 + (OFF_)))
+#define MFMA_ROW(WF_, AF_, I_)                                                                                    \
+    _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                              \
+        acc[I_][j_] = T::mfma16(__builtin_bit_cast(vec8, WF_[j_]), __builtin_bit_cast(vec8, AF_[I_]), acc[I_][j_]);
 
     if constexpr (GENERIC) {
         // simple loop (register-staged, predicated): ragged K / tiny shapes
@@ -190,8 +167,12 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 u32x4_t wf[4], af[8];
-                LOAD_FRAGS(sb, kk, wf, af)
-                MFMA_BLOCK(wf, af)
+                const int off = FRAG_OFF(kk);
+                LD_W(sb, off, wf)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) af[i] = LD_A(sb, off, i);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) MFMA_ROW(wf, af, i)
             }
             __syncthreads();
         }
@@ -203,23 +184,15 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
         // K-tile t+1 (LDS-DMA issued one iteration earlier, so the vmcnt(0) in front of it is free) and (2) retires
         // every wave's reads of K-tile t, so the DMA of K-tile t+2 may overwrite that buffer.
         u32x4_t wfa[4], wfb[4], af[8], an;   // an: the A fragment in flight for the next k-step
-#define LD_W(SB_, KK_, WF_)                                                                                       \
-    _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                              \
-        WF_[j_] = *reinterpret_cast<const u32x4_t*>((SB_) + w_base + j_ * 2048 + ((pch0 ^ ((KK_) << 2)) << 4));
-#define LD_A(SB_, KK_, I_) (*reinterpret_cast<const u32x4_t*>((SB_) + a_base + (I_) * 2048 + ((pch0 ^ ((KK_) << 2)) << 4)))
         // one k-step: 8 groups of {4 MFMAs on af[i]; af[i] <- fragment i of the next k-step (loaded one group early)}
-#define K_STEP(WF_, SBN_, KKN_, HAS_NEXT_, DMA_)                                                                  \
+#define K_STEP(WF_, SBN_, KKN_, DMA_)                                                                             \
     {                                                                                                             \
-        if (HAS_NEXT_) an = LD_A(SBN_, KKN_, 0);                                                                  \
+        an = LD_A(SBN_, FRAG_OFF(KKN_), 0);                                                                       \
         _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                        \
             if (DMA_) stage_piece(cur, kt + 2, i_); /* LDS-DMA issue spread over the MFMA groups */                \
-            _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                      \
-                acc[i_][j_] = T::mfma16(__builtin_bit_cast(vec8, WF_[j_]), __builtin_bit_cast(vec8, af[i_]),      \
-                                        acc[i_][j_]);                                                             \
-            if (HAS_NEXT_) {                                                                                      \
-                af[i_] = an;                                                                                      \
-                if (i_ < 7) an = LD_A(SBN_, KKN_, i_ + 1);                                                        \
-            }                                                                                                     \
+            MFMA_ROW(WF_, af, i_)                                                                                 \
+            af[i_] = an;                                                                                          \
+            if (i_ < 7) an = LD_A(SBN_, FRAG_OFF(KKN_), i_ + 1);                                                  \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
         }                                                                                                         \
     }
@@ -227,9 +200,9 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
         if (nk > 1) stage(1, 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        LD_W(smem, 0, wfa)
+        LD_W(smem, FRAG_OFF(0), wfa)
 #pragma unroll
-        for (int i = 0; i < 8; ++i) af[i] = LD_A(smem, 0, i);
+        for (int i = 0; i < 8; ++i) af[i] = LD_A(smem, FRAG_OFF(0), i);
 #ifdef FINO_GEMM_STAMP
         unsigned long long t0, t1, t2, t3, t4, acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
 #endif
@@ -240,8 +213,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
 #ifdef FINO_GEMM_STAMP
             __builtin_amdgcn_sched_barrier(0); STAMP(t0) __builtin_amdgcn_sched_barrier(0);
 #endif
-            LD_W(sb, 1, wfb)
-            K_STEP(wfa, sb, 1, true, false)
+            LD_W(sb, FRAG_OFF(1), wfb)
+            K_STEP(wfa, sb, 1, false)
 #ifdef FINO_GEMM_STAMP
             __builtin_amdgcn_sched_barrier(0); STAMP(t1) __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -254,9 +227,9 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
 #endif
             __builtin_amdgcn_sched_barrier(0);
             // (on the last K-tile these fragment loads read the stale other buffer: valid LDS, values never used)
-            LD_W(sbn, 0, wfa)
+            LD_W(sbn, FRAG_OFF(0), wfa)
             const bool dma = kt + 2 < nk;          // wave-uniform: a scalar branch around each DMA piece
-            K_STEP(wfb, sbn, 0, true, dma)
+            K_STEP(wfb, sbn, 0, dma)
 #ifdef FINO_GEMM_STAMP
             __builtin_amdgcn_sched_barrier(0); STAMP(t4) __builtin_amdgcn_sched_barrier(0);
             acc0 += t1 - t0; acc1 += t2 - t1; acc2 += t3 - t2; acc3 += t4 - t3;
@@ -271,11 +244,11 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
 #endif
         __syncthreads();
     }
+#undef FRAG_OFF
 #undef LD_W
 #undef LD_A
+#undef MFMA_ROW
 #undef K_STEP
-#undef LOAD_FRAGS
-#undef MFMA_BLOCK
 
     gemm_epilogue<T, EPI, false, 8, KEEP>(acc, p, smem, m0, n0, tid, lane, wm, wn);
 }
@@ -301,7 +274,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_kernel(const GemmParams p) {
 // writes zeros into LDS (no zero page, no branch).  The resource is re-based per workgroup to the first input frame
 // its rows can touch, so the offsets fit 32 bits on tensors of any size (fino_conv3d checks the per-tile span).
 // The main loop of one output tile over K-tiles [kb, kb + nk): everything between the tile coordinates and the
-// accumulators (the whole-tile kernel passes kb = 0, nk = K / 64; the stream-K kernel a key... a K range).
+// accumulators (gemm_pp_kernel, its only caller, passes kb = 0, nk = K / 64).
 // MI = 16-row fragments per wave: the tile is BM_ = 32 * MI rows high, group g (waves 4g .. 4g+3) owns rows [16 MI g,
 // 16 MI (g + 1)); 8 = the 256 x 256 tile.  Lower tiles exist for ROW COUNTS, not for speed per FLOP: 3080 rows (a 4-way
 // token shard) are 13 x 12 = 156 tiles of 256 x 256 on 256 CUs -- 100 CUs idle for the whole GEMM -- but 20 x 12 = 240
@@ -748,49 +721,19 @@ inline bool use_pingpong() {
     return v == 1;
 }
 
-template <typename T, int EPI, bool KEEP = false>
-int launch_gemm_pp_mi(const GemmParams& p, int mi, hipStream_t st) {
-    if constexpr (KEEP) {  // fino_gemm_keep: y = T(acc + bias) also goes to p.c2 (the residual epilogues, every tile height)
-        switch (mi) {
-            case 2: return launch_gemm_pp<T, EPI, false, 2, false, true>(p, st);
-            case 3: return launch_gemm_pp<T, EPI, false, 3, false, true>(p, st);
-            case 4: return launch_gemm_pp<T, EPI, false, 4, false, true>(p, st);
-            case 5: return launch_gemm_pp<T, EPI, false, 5, false, true>(p, st);
-            case 6: return launch_gemm_pp<T, EPI, false, 6, false, true>(p, st);
-            case 7: return launch_gemm_pp<T, EPI, false, 7, false, true>(p, st);
-            default: return launch_gemm_pp<T, EPI, false, 8, false, true>(p, st);
-        }
-    }
-    if (p.a_tpb > 0) {     // K-blocked A: built for the out-projection's epilogue only (fino_gemm_blocked_a checks)
-        if constexpr (EPI == FINO_EPI_GATED_RESIDUAL) {
-            switch (mi) {
-                case 2: return launch_gemm_pp<T, EPI, false, 2, true>(p, st);
-                case 3: return launch_gemm_pp<T, EPI, false, 3, true>(p, st);
-                case 4: return launch_gemm_pp<T, EPI, false, 4, true>(p, st);
-                case 5: return launch_gemm_pp<T, EPI, false, 5, true>(p, st);
-                case 6: return launch_gemm_pp<T, EPI, false, 6, true>(p, st);
-                case 7: return launch_gemm_pp<T, EPI, false, 7, true>(p, st);
-                default: return launch_gemm_pp<T, EPI, false, 8, true>(p, st);
-            }
-        } else {
-            fino_set_error("fino_gemm_blocked_a: epilogue must be FINO_EPI_GATED_RESIDUAL");
-            return FINO_ERR_UNSUPPORTED;
-        }
-    }
-    switch (mi) {
-        case 2: return launch_gemm_pp<T, EPI, false, 2>(p, st);
-        case 3: return launch_gemm_pp<T, EPI, false, 3>(p, st);
-        case 4: return launch_gemm_pp<T, EPI, false, 4>(p, st);
-        case 5: return launch_gemm_pp<T, EPI, false, 5>(p, st);
-        case 6: return launch_gemm_pp<T, EPI, false, 6>(p, st);
-        case 7: return launch_gemm_pp<T, EPI, false, 7>(p, st);
-        default: return launch_gemm_pp<T, EPI, false, 8>(p, st);
-    }
+// ---- the host launch path --------------------------------------------------------------------------------------------
+// What is instantiated, and nothing else: KEEP for the three residual epilogues; ABLK for GATED_RESIDUAL; the fp32 epilogues
+// at MI = 8 on the ping-pong loop only; CONV with NONE / RESIDUAL (and F32 / F32_RESIDUAL for the split products).
+constexpr bool epi_is_f32(int epi) { return epi == FINO_EPI_F32 || epi == FINO_EPI_F32_RESIDUAL; }
+constexpr bool epi_keeps(int epi) {
+    return epi == FINO_EPI_RESIDUAL || epi == FINO_EPI_GATED_RESIDUAL || epi == FINO_EPI_GATED_RESIDUAL_STAGED;
 }
 
-// rows [r0, r0 + rows) of the GEMM as one launch of 32 * mi-row tiles
-template <typename T, bool KEEP = false>
-int launch_gemm_rows(GemmParams p, int64_t r0, int64_t rows, int mi, int epi, hipStream_t st) {
+// rows [r0, r0 + rows) of the GEMM as one launch of 32 * mi-row tiles on the ping-pong loop
+template <typename T, int EPI, bool KEEP, bool ABLK>
+int launch_gemm_rows(GemmParams p, int64_t r0, int64_t rows, int mi, hipStream_t st) {
+    static_assert(!epi_is_f32(EPI) && (!KEEP || epi_keeps(EPI)) && (!ABLK || (EPI == FINO_EPI_GATED_RESIDUAL && !KEEP)),
+                  "not a kernel of this file");
     p.a += r0 * p.lda;
     p.c += r0 * p.ldc;
     if (p.c2) p.c2 += r0 * p.ldc2;
@@ -798,55 +741,36 @@ int launch_gemm_rows(GemmParams p, int64_t r0, int64_t rows, int mi, int epi, hi
     if (p.sel) p.sel += r0;
     p.m = rows;
     p.tiles_m = (int)((rows + 32 * mi - 1) / (32 * mi));
-    if constexpr (KEEP) {
-        switch (epi) {
-            case FINO_EPI_RESIDUAL: return launch_gemm_pp_mi<T, FINO_EPI_RESIDUAL, true>(p, mi, st);
-            case FINO_EPI_GATED_RESIDUAL_STAGED: return launch_gemm_pp_mi<T, FINO_EPI_GATED_RESIDUAL_STAGED, true>(p, mi, st);
-            default: return launch_gemm_pp_mi<T, FINO_EPI_GATED_RESIDUAL, true>(p, mi, st);
-        }
-    }
-    switch (epi) {
-        case FINO_EPI_NONE: return launch_gemm_pp_mi<T, FINO_EPI_NONE>(p, mi, st);
-        case FINO_EPI_GELU_TANH: return launch_gemm_pp_mi<T, FINO_EPI_GELU_TANH>(p, mi, st);
-        case FINO_EPI_RESIDUAL: return launch_gemm_pp_mi<T, FINO_EPI_RESIDUAL>(p, mi, st);
-        case FINO_EPI_GATED_RESIDUAL_STAGED: return launch_gemm_pp_mi<T, FINO_EPI_GATED_RESIDUAL_STAGED>(p, mi, st);
-        default: return launch_gemm_pp_mi<T, FINO_EPI_GATED_RESIDUAL>(p, mi, st);
-    }
+    return gemm_dispatch_mi(mi, [&](auto h) { return launch_gemm_pp<T, EPI, false, decltype(h)::value, ABLK, KEEP>(p, st); });
 }
 
-template <typename T, bool GENERIC, bool KEEP = false>
-int launch_gemm_e(const GemmParams& p, int epi, int tile_m, hipStream_t st) {
+// the planned launch: plan_tiles' leading rows as 256-row tiles, the rest as one more launch of lower ones
+template <typename T, int EPI, bool KEEP, bool ABLK>
+int launch_gemm_planned(const GemmParams& p, int tile_m, hipStream_t st) {
+    const TilePlan tp = plan_tiles(p.m, p.tiles_n, gemm_device_cus(), tile_m);
+    if (tp.rows1 > 0)
+        if (int rc = launch_gemm_rows<T, EPI, KEEP, ABLK>(p, 0, tp.rows1, 8, st)) return rc;
+    if (tp.rows1 < p.m) return launch_gemm_rows<T, EPI, KEEP, ABLK>(p, tp.rows1, p.m - tp.rows1, tp.mi2, st);
+    return FINO_OK;
+}
+
+// The route of a fino_gemm / fino_gemm_split_n / fino_gemm_keep call, chosen here and nowhere else: the fp32-output form,
+// the planned ping-pong launches, or the one-barrier kernel (ragged K -> GENERIC; FINO_GEMM_PP=0; operands of 2 GiB or more).
+template <typename T, int EPI, bool KEEP>
+int launch_gemm_route(const GemmParams& p, int tile_m, hipStream_t st) {
+    const bool generic = (p.k % BK) != 0;
     const bool fits32 = ((p.m - 1) * p.lda + p.k) * 2 < (1ll << 31) && ((p.n - 1) * p.ldw + p.k) * 2 < (1ll << 31);
-    if (epi == FINO_EPI_F32 || epi == FINO_EPI_F32_RESIDUAL) {
+    if constexpr (epi_is_f32(EPI)) {
         // fp32 output (the split-bf16 products of the Wan VAE's mid-block attention): one launch of 256-row tiles on the
         // ping-pong loop -- the row-offset arithmetic of the planned two-launch form counts T elements
-        if (GENERIC || !fits32) {
+        if (generic || !fits32) {
             fino_set_error("fino_gemm: the fp32-output epilogues need K %% 64 == 0, 16-byte aligned operands and operands < 2 GiB");
             return FINO_ERR_UNSUPPORTED;
         }
-        return epi == FINO_EPI_F32 ? launch_gemm_pp<T, FINO_EPI_F32, false, 8>(p, st)
-                                   : launch_gemm_pp<T, FINO_EPI_F32_RESIDUAL, false, 8>(p, st);
-    }
-    if (!GENERIC && use_pingpong() && fits32) {
-        const TilePlan tp = plan_tiles(p.m, p.tiles_n, gemm_device_cus(), tile_m);
-        if (tp.rows1 > 0)
-            if (int rc = launch_gemm_rows<T, KEEP>(p, 0, tp.rows1, 8, epi, st)) return rc;
-        if (tp.rows1 < p.m) return launch_gemm_rows<T, KEEP>(p, tp.rows1, p.m - tp.rows1, tp.mi2, epi, st);
-        return FINO_OK;
-    }
-    if constexpr (KEEP) {
-        switch (epi) {
-            case FINO_EPI_RESIDUAL: return launch_gemm_t<T, FINO_EPI_RESIDUAL, GENERIC, false, true>(p, st);
-            case FINO_EPI_GATED_RESIDUAL_STAGED: return launch_gemm_t<T, FINO_EPI_GATED_RESIDUAL_STAGED, GENERIC, false, true>(p, st);
-            default: return launch_gemm_t<T, FINO_EPI_GATED_RESIDUAL, GENERIC, false, true>(p, st);
-        }
-    }
-    switch (epi) {
-        case FINO_EPI_NONE: return launch_gemm_t<T, FINO_EPI_NONE, GENERIC>(p, st);
-        case FINO_EPI_GELU_TANH: return launch_gemm_t<T, FINO_EPI_GELU_TANH, GENERIC>(p, st);
-        case FINO_EPI_RESIDUAL: return launch_gemm_t<T, FINO_EPI_RESIDUAL, GENERIC>(p, st);
-        case FINO_EPI_GATED_RESIDUAL_STAGED: return launch_gemm_t<T, FINO_EPI_GATED_RESIDUAL_STAGED, GENERIC>(p, st);
-        default: return launch_gemm_t<T, FINO_EPI_GATED_RESIDUAL, GENERIC>(p, st);
+        return launch_gemm_pp<T, EPI, false, 8>(p, st);
+    } else {
+        if (!generic && use_pingpong() && fits32) return launch_gemm_planned<T, EPI, KEEP, false>(p, tile_m, st);
+        return generic ? launch_gemm_t<T, EPI, true, false, KEEP>(p, st) : launch_gemm_t<T, EPI, false, false, KEEP>(p, st);
     }
 }
 
@@ -944,15 +868,10 @@ static int gemm_impl(const void* a, const void* w, const void* bias, void* c, in
     GemmParams p = {};
     p.c2 = (uint16_t*)c2; p.ldc2 = ldc2; p.n_split = n_split;
     if (keep) { p.c2 = (uint16_t*)keep; p.ldc2 = ldk; p.n_split = 0; }
-    p.a = (const uint16_t*)a; p.w = (const uint16_t*)w; p.bias = (const uint16_t*)bias; p.c = (uint16_t*)c;
-    p.r = (const uint16_t*)r; p.gate = gate; p.sel = sel;
-    p.m = m; p.n = n; p.k = k; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.mod_stride = mod_stride;
-    p.tiles_m = (int)((m + BM - 1) / BM);
-    p.tiles_n = (int)((n + BN - 1) / BN);
-    p.group_m = fino_tune_get(FINO_TUNE_GEMM_GROUP_M);
+    // (the raster group falls back to gemm_default_group_m here and in fino_gemm_blocked_a only; the raster bit below is
+    // this function's alone)
+    gemm_fill_params(p, a, w, bias, c, r, gate, sel, m, n, k, lda, ldw, ldc, ldr, mod_stride, true);
     hipStream_t st = (hipStream_t)stream;
-    const bool generic = (k % BK) != 0;
-    if (p.group_m <= 0) p.group_m = gemm_default_group_m(p.tiles_n, k);
     // Long-K GEMMs (FFN-down: K = 14336, a 706 MB A operand written by the launch before it) walk their tile rows LAST TO FIRST: the
     // rows the producer wrote last are the ones still in the 256 MiB Infinity Cache, and a first-to-last walk evicts them before it gets
     // there.  Same bits; FFN-up + FFN-down 3373.8 -> 3340.4 us per pair at M = 24640 (tools/ffn_pair_ab.py, profiles/r06_ffn_pair_ab.txt).
@@ -961,16 +880,15 @@ static int gemm_impl(const void* a, const void* w, const void* bias, void* c, in
         const int rk = fino_tune_get(FINO_TUNE_GEMM_RASTER);
         if (rk == 1 || (rk == 3 && (k >= 8192 || n >= 8192)) || (rk != 2 && rk != 3 && k >= 8192)) p.group_m |= 0x100;
     }
-    if (keep) {
-        if (dtype == FINO_BF16)
-            return generic ? launch_gemm_e<BF16, true, true>(p, epilogue, tile_m, st)
-                           : launch_gemm_e<BF16, false, true>(p, epilogue, tile_m, st);
-        return generic ? launch_gemm_e<F16, true, true>(p, epilogue, tile_m, st)
-                       : launch_gemm_e<F16, false, true>(p, epilogue, tile_m, st);
-    }
-    if (dtype == FINO_BF16)
-        return generic ? launch_gemm_e<BF16, true>(p, epilogue, tile_m, st) : launch_gemm_e<BF16, false>(p, epilogue, tile_m, st);
-    return generic ? launch_gemm_e<F16, true>(p, epilogue, tile_m, st) : launch_gemm_e<F16, false>(p, epilogue, tile_m, st);
+    return gemm_dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (keep)
+            return gemm_dispatch_keep_epilogue(
+                epilogue, [&](auto e) { return launch_gemm_route<T, decltype(e)::value, true>(p, tile_m, st); });
+        return gemm_dispatch_among<FINO_EPI_NONE, FINO_EPI_GELU_TANH, FINO_EPI_RESIDUAL, FINO_EPI_GATED_RESIDUAL,
+                                   FINO_EPI_GATED_RESIDUAL_STAGED, FINO_EPI_F32, FINO_EPI_F32_RESIDUAL>(
+            epilogue, [&](auto e) { return launch_gemm_route<T, decltype(e)::value, false>(p, tile_m, st); });
+    });
 }
 
 extern "C" int fino_gemm_split_n(const void* a, const void* w, const void* bias, void* c, int64_t m, int64_t n, int64_t k,
@@ -1023,9 +941,7 @@ extern "C" int fino_gemm_blocked_a(const void* a, const void* w, const void* bia
                "fino_gemm_blocked_a: operands must span < 2 GiB");
     if (m == 0) return FINO_OK;
     GemmParams p = {};
-    p.a = (const uint16_t*)a; p.w = (const uint16_t*)w; p.bias = (const uint16_t*)bias; p.c = (uint16_t*)c;
-    p.r = (const uint16_t*)r; p.gate = gate; p.sel = sel;
-    p.m = m; p.n = n; p.k = k; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.mod_stride = mod_stride;
+    gemm_fill_params(p, a, w, bias, c, r, gate, sel, m, n, k, lda, ldw, ldc, ldr, mod_stride, true);   // (as fino_gemm: default group)
     p.a_tpb = (int)(a_block_k / BK); p.a_inv = (65536 + p.a_tpb - 1) / p.a_tpb; p.a_blk_elems = a_block_stride;
     p.a_groups = a_groups; p.a_ginv = (65536 + a_groups - 1) / a_groups; p.a_grp_elems = a_group_stride;
     // (x * ceil(65536 / d)) >> 16 == x / d holds while x * (d * ceil(65536 / d) - 65536) < 65536: check it for the largest
@@ -1035,20 +951,10 @@ extern "C" int fino_gemm_blocked_a(const void* a, const void* w, const void* bia
                FINO_ERR_UNSUPPORTED,
                "fino_gemm_blocked_a: a_block_k=%lld / a_groups=%d with K=%lld is beyond the exact range of the kernel's "
                "reciprocal index arithmetic", (long long)a_block_k, a_groups, (long long)k);
-    p.tiles_m = (int)((m + BM - 1) / BM);
-    p.tiles_n = (int)((n + BN - 1) / BN);
-    p.group_m = fino_tune_get(FINO_TUNE_GEMM_GROUP_M);
-    if (p.group_m <= 0) p.group_m = gemm_default_group_m(p.tiles_n, k);
-    hipStream_t st = (hipStream_t)stream;
-    const TilePlan tp = plan_tiles(p.m, p.tiles_n, gemm_device_cus(), tile_m);
-    auto rows = [&](int64_t r0, int64_t nr, int mi) {
-        return dtype == FINO_BF16 ? launch_gemm_rows<BF16>(p, r0, nr, mi, FINO_EPI_GATED_RESIDUAL, st)
-                                  : launch_gemm_rows<F16>(p, r0, nr, mi, FINO_EPI_GATED_RESIDUAL, st);
-    };
-    if (tp.rows1 > 0)
-        if (int rc = rows(0, tp.rows1, 8)) return rc;
-    if (tp.rows1 < p.m) return rows(tp.rows1, p.m - tp.rows1, tp.mi2);
-    return FINO_OK;
+    // always the ping-pong loop (the only one that knows the K-blocked A): FINO_GEMM_PP is not consulted
+    return gemm_dispatch_dtype(dtype, [&](auto t) {
+        return launch_gemm_planned<decltype(t), FINO_EPI_GATED_RESIDUAL, false, true>(p, tile_m, (hipStream_t)stream);
+    });
 }
 
 // fino_conv3d and fino_conv3d_split (planes = 0 / 2 / 3): one body.  With planes > 0, c_in_pad is the width of ONE plane,
@@ -1096,14 +1002,12 @@ static int conv3d_impl(const void* x, const void* w, const void* bias, void* y, 
     FINO_CHECK(planes == 0 || fino_aligned16(bias), FINO_ERR_ARG, "fino_conv3d_split: bias must be 16-byte aligned");
     const int products = planes == 0 ? 1 : (planes == 2 ? 3 : 6);
     const int64_t a_width = (int64_t)(planes == 0 ? 1 : planes) * c_in_pad;         // elements of one A row
+    const int64_t k_all = (int64_t)kt * kh * kw * c_in_pad * products;
     GemmParams p = {};
-    p.a = (const uint16_t*)x; p.w = (const uint16_t*)w; p.bias = (const uint16_t*)bias; p.c = (uint16_t*)y;
-    p.r = (const uint16_t*)r; p.gate = nullptr; p.sel = nullptr;
-    p.m = (int64_t)t_out * h_out * w_out; p.n = c_out_pad; p.k = (int64_t)kt * kh * kw * c_in_pad * products;
-    p.lda = a_width; p.ldw = p.k; p.ldc = c_out_pad; p.ldr = c_out_pad; p.mod_stride = 0;
+    // (the raster group is the tune value as it is, like the MX GEMMs: 0 means 4 in tile_raster)
+    gemm_fill_params(p, x, w, bias, y, r, nullptr, nullptr, (int64_t)t_out * h_out * w_out, c_out_pad, k_all, a_width, k_all,
+                     c_out_pad, c_out_pad, 0, false);
     p.a_cc = planes == 0 ? 0 : c_in_pad / BK; p.a_nplanes = planes;
-    p.tiles_m = (int)((p.m + BM - 1) / BM); p.tiles_n = (int)((p.n + BN - 1) / BN);
-    p.group_m = fino_tune_get(FINO_TUNE_GEMM_GROUP_M);
     p.to = t_out; p.ho = h_out; p.wo = w_out; p.ti = t_in; p.hi = h_in; p.wi = w_in;
     p.kt = kt; p.kh = kh; p.kw = kw; p.st = st; p.sh = sh; p.sw = sw; p.pt = pt; p.ph = ph; p.pw = pw;
     p.up = upsample2x; p.cin_chunks = c_in_pad / BK * products; p.zero_page = (const uint16_t*)zero_page;
@@ -1123,21 +1027,16 @@ static int conv3d_impl(const void* x, const void* w, const void* bias, void* y, 
                            "or c_out_pad %% 32 != 0 -- run the layer in chunks of fewer frames", (long long)in_span_bytes);
             return FINO_ERR_UNSUPPORTED;
         }
-        return epilogue == FINO_EPI_NONE ? launch_gemm_pp<BF16, FINO_EPI_F32, true>(p, s)
-                                         : launch_gemm_pp<BF16, FINO_EPI_F32_RESIDUAL, true>(p, s);
+        return gemm_dispatch_among<FINO_EPI_NONE, FINO_EPI_RESIDUAL>(epilogue, [&](auto e) {      // -> their fp32 forms
+            return launch_gemm_pp<BF16, decltype(e)::value == FINO_EPI_NONE ? FINO_EPI_F32 : FINO_EPI_F32_RESIDUAL, true>(p, s);
+        });
     }
-    if (pp) {
-        if (dtype == FINO_BF16)
-            return epilogue == FINO_EPI_NONE ? launch_gemm_pp<BF16, FINO_EPI_NONE, true>(p, s)
-                                             : launch_gemm_pp<BF16, FINO_EPI_RESIDUAL, true>(p, s);
-        return epilogue == FINO_EPI_NONE ? launch_gemm_pp<F16, FINO_EPI_NONE, true>(p, s)
-                                         : launch_gemm_pp<F16, FINO_EPI_RESIDUAL, true>(p, s);
-    }
-    if (dtype == FINO_BF16)
-        return epilogue == FINO_EPI_NONE ? launch_gemm_t<BF16, FINO_EPI_NONE, false, true>(p, s)
-                                         : launch_gemm_t<BF16, FINO_EPI_RESIDUAL, false, true>(p, s);
-    return epilogue == FINO_EPI_NONE ? launch_gemm_t<F16, FINO_EPI_NONE, false, true>(p, s)
-                                     : launch_gemm_t<F16, FINO_EPI_RESIDUAL, false, true>(p, s);
+    return gemm_dispatch_dtype(dtype, [&](auto t) {
+        return gemm_dispatch_among<FINO_EPI_NONE, FINO_EPI_RESIDUAL>(epilogue, [&](auto e) {
+            return pp ? launch_gemm_pp<decltype(t), decltype(e)::value, true>(p, s)
+                      : launch_gemm_t<decltype(t), decltype(e)::value, false, true>(p, s);
+        });
+    });
 }
 
 extern "C" int fino_skinny_linear(const float* x, const void* w, const void* b, float* y, int m, int64_t n,

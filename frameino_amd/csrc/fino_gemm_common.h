@@ -1,4 +1,4 @@
-// Shared definitions of the MFMA GEMM / implicit-GEMM conv kernels (fino_gemm.hip).
+// Shared definitions of the MFMA GEMM / implicit-GEMM conv kernels (fino_gemm.hip) and the MX GEMMs.
 #pragma once
 #include <type_traits>
 
@@ -344,6 +344,66 @@ __device__ __forceinline__ void gemm_epilogue(f32x4_t (&acc)[MI][4], const GemmP
         gemm_epilogue_t<T, EPI, QOUT, MI, KEEP>(acc, p, smem, m0, n0, tid, lane, wm, wn);
 }
 
+// ================= host side shared by the whole family (fino_gemm.hip, fino_gemm_fp8.hip, fino_gemm_fp6.hip) =================
+// Run-time choices become template arguments in ONE way: a dispatcher calls `launch` with the choice as a tag value (an
+// integral constant, or the element type itself), and `launch` is a generic lambda that names the instantiation.  A lambda
+// is instantiated for every tag its dispatcher can pass, so the set of kernels of a call site is the product of the lists
+// it dispatches over: what must not exist is kept out with a narrower list or `if constexpr`, never with a run-time test.
+template <int V>
+using gemm_tag = std::integral_constant<int, V>;
+
+// the epilogue, among the ones listed (the caller has validated `epi`: the last one listed is the default of the switch)
+template <int E, int... REST, typename F>
+int gemm_dispatch_among(int epi, F&& launch) {
+    if constexpr (sizeof...(REST) == 0)
+        return launch(gemm_tag<E>{});
+    else
+        return epi == E ? launch(gemm_tag<E>{}) : gemm_dispatch_among<REST...>(epi, launch);
+}
+// ... among the five that write T, and among the three of them the KEEP kernels are instantiated for
+template <typename F>
+int gemm_dispatch_epilogue(int epi, F&& launch) {
+    return gemm_dispatch_among<FINO_EPI_NONE, FINO_EPI_GELU_TANH, FINO_EPI_RESIDUAL, FINO_EPI_GATED_RESIDUAL_STAGED,
+                               FINO_EPI_GATED_RESIDUAL>(epi, launch);
+}
+template <typename F>
+int gemm_dispatch_keep_epilogue(int epi, F&& launch) {
+    return gemm_dispatch_among<FINO_EPI_RESIDUAL, FINO_EPI_GATED_RESIDUAL_STAGED, FINO_EPI_GATED_RESIDUAL>(epi, launch);
+}
+// the element type: launch(BF16{}) or launch(F16{}) (the caller has validated `dtype`)
+template <typename F>
+int gemm_dispatch_dtype(int dtype, F&& launch) {
+    return dtype == FINO_BF16 ? launch(BF16{}) : launch(F16{});
+}
+// the tile height in 32-row units, 2 .. 8 (plan_tiles and the tile_m checks produce nothing else)
+template <typename F>
+int gemm_dispatch_mi(int mi, F&& launch) {
+    switch (mi) {
+        case 2: return launch(gemm_tag<2>{});
+        case 3: return launch(gemm_tag<3>{});
+        case 4: return launch(gemm_tag<4>{});
+        case 5: return launch(gemm_tag<5>{});
+        case 6: return launch(gemm_tag<6>{});
+        case 7: return launch(gemm_tag<7>{});
+        default: return launch(gemm_tag<8>{});
+    }
+}
+
+// Pointers, shape, leading dimensions, tile counts (of 256 x 256 tiles) and the raster group of `p`; every other field is
+// the caller's.  group_m is the FINO_TUNE_GEMM_GROUP_M value as it is (0 means 4 in tile_raster), or with
+// `default_group_m` gemm_default_group_m's choice where the knob is unset.
+inline void gemm_fill_params(GemmParams& p, const void* a, const void* w, const void* bias, void* c, const void* r,
+                             const float* gate, const int32_t* sel, int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldw,
+                             int64_t ldc, int64_t ldr, int64_t mod_stride, bool default_group_m) {
+    p.a = (const uint16_t*)a; p.w = (const uint16_t*)w; p.bias = (const uint16_t*)bias; p.c = (uint16_t*)c;
+    p.r = (const uint16_t*)r; p.gate = gate; p.sel = sel;
+    p.m = m; p.n = n; p.k = k; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.mod_stride = mod_stride;
+    p.tiles_m = (int)((m + BM - 1) / BM);
+    p.tiles_n = (int)((n + BN - 1) / BN);
+    p.group_m = fino_tune_get(FINO_TUNE_GEMM_GROUP_M);
+    if (default_group_m && p.group_m <= 0) p.group_m = gemm_default_group_m(p.tiles_n, k);
+}
+
 // ================= host side shared by the MX GEMMs (fino_gemm_fp8.hip, fino_gemm_fp6.hip) =================
 struct MxGemmParams {
     GemmParams g;                  // a / w = the quantiser's element images (e4m3 bytes; e2m3 fragments); k in elements
@@ -374,28 +434,11 @@ inline int mx_gemm_params(MxGemmParams& fp, const char* who, bool qout, const vo
     if (epilogue == FINO_EPI_GATED_RESIDUAL || epilogue == FINO_EPI_GATED_RESIDUAL_STAGED)
         FINO_CHECK(gate && fino_aligned16(gate) && mod_stride % 4 == 0, FINO_ERR_ARG, "%s: gate operand", who);
     fp = {};
-    GemmParams& p = fp.g;
-    p.a = (const uint16_t*)aq; p.w = (const uint16_t*)wq; p.bias = (const uint16_t*)bias; p.c = (uint16_t*)c;
-    p.r = (const uint16_t*)r; p.gate = gate; p.sel = sel;
-    p.m = m; p.n = n; p.k = k; p.lda = k; p.ldw = k; p.ldc = ldc; p.ldr = ldr; p.mod_stride = mod_stride;
-    p.tiles_m = (int)((m + BM - 1) / BM);
-    p.tiles_n = (int)((n + BN - 1) / BN);
-    p.group_m = fino_tune_get(FINO_TUNE_GEMM_GROUP_M);
+    // (the raster group is the tune value as it is: the MX kernels never took gemm_default_group_m's choice)
+    gemm_fill_params(fp.g, aq, wq, bias, c, r, gate, sel, m, n, k, k, k, ldc, ldr, mod_stride, false);
     fp.sa = (const uint8_t*)a_scales; fp.sw = (const uint8_t*)w_scales;
     fp.m_pad = (m + 255) / 256 * 256; fp.n_pad = (n + 255) / 256 * 256;
     return FINO_OK;
-}
-
-// the epilogues an MX GEMM is instantiated for: `launch` is called with the epilogue as an integral constant
-template <typename F>
-int mx_dispatch_epilogue(int epi, F&& launch) {
-    switch (epi) {
-        case FINO_EPI_NONE: return launch(std::integral_constant<int, FINO_EPI_NONE>{});
-        case FINO_EPI_GELU_TANH: return launch(std::integral_constant<int, FINO_EPI_GELU_TANH>{});
-        case FINO_EPI_RESIDUAL: return launch(std::integral_constant<int, FINO_EPI_RESIDUAL>{});
-        case FINO_EPI_GATED_RESIDUAL_STAGED: return launch(std::integral_constant<int, FINO_EPI_GATED_RESIDUAL_STAGED>{});
-        default: return launch(std::integral_constant<int, FINO_EPI_GATED_RESIDUAL>{});
-    }
 }
 
 // the keep buffer of fino_gemm_mxfp8_keep / fino_gemm_mxfp6_keep (after mx_gemm_params): the residual epilogues only; the
@@ -409,16 +452,6 @@ inline int mx_gemm_keep_params(MxGemmParams& fp, const char* who, int epilogue, 
                "%s: needs a 16-byte aligned keep buffer with ldk >= N a multiple of 8", who);
     fp.g.c2 = (uint16_t*)keep; fp.g.ldc2 = ldk; fp.g.n_split = 0;
     return FINO_OK;
-}
-
-// ... and the three epilogues the KEEP kernels are instantiated for (the caller has checked `epi`)
-template <typename F>
-int mx_dispatch_keep_epilogue(int epi, F&& launch) {
-    switch (epi) {
-        case FINO_EPI_RESIDUAL: return launch(std::integral_constant<int, FINO_EPI_RESIDUAL>{});
-        case FINO_EPI_GATED_RESIDUAL_STAGED: return launch(std::integral_constant<int, FINO_EPI_GATED_RESIDUAL_STAGED>{});
-        default: return launch(std::integral_constant<int, FINO_EPI_GATED_RESIDUAL>{});
-    }
 }
 
 }  // namespace fino_gemm_ns

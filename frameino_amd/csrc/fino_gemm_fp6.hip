@@ -328,16 +328,6 @@ int launch_mxfp6(const MxGemmParams& fp, hipStream_t st) {
     return FINO_OK;
 }
 
-template <typename T>
-int launch_mxfp6_e(const MxGemmParams& fp, int epi, hipStream_t st) {
-    return mx_dispatch_epilogue(epi, [&](auto e) { return launch_mxfp6<T, decltype(e)::value>(fp, st); });
-}
-
-template <typename T>
-int launch_mxfp6_keep(const MxGemmParams& fp, int epi, hipStream_t st) {
-    return mx_dispatch_keep_epilogue(epi, [&](auto e) { return launch_mxfp6<T, decltype(e)::value, true>(fp, st); });
-}
-
 }  // namespace
 
 extern "C" int64_t fino_mxfp6_bytes(int64_t rows, int64_t cols) {
@@ -406,7 +396,9 @@ extern "C" int fino_gemm_mxfp6(const void* aq, const void* a_scales, const void*
     FINO_CHECK(fp.m_pad * k < (1ll << 31) && fp.n_pad * k < (1ll << 31), FINO_ERR_UNSUPPORTED,
                "fino_gemm_mxfp6: operand > 2 GiB");
     hipStream_t st = (hipStream_t)stream;
-    return out_dtype == FINO_BF16 ? launch_mxfp6_e<BF16>(fp, epilogue, st) : launch_mxfp6_e<F16>(fp, epilogue, st);
+    return gemm_dispatch_dtype(out_dtype, [&](auto t) {
+        return gemm_dispatch_epilogue(epilogue, [&](auto e) { return launch_mxfp6<decltype(t), decltype(e)::value>(fp, st); });
+    });
 }
 
 extern "C" int fino_gemm_mxfp6_keep(const void* aq, const void* a_scales, const void* wq, const void* w_scales,
@@ -422,5 +414,8 @@ extern "C" int fino_gemm_mxfp6_keep(const void* aq, const void* a_scales, const 
     FINO_CHECK(fp.m_pad * k < (1ll << 31) && fp.n_pad * k < (1ll << 31), FINO_ERR_UNSUPPORTED,
                "fino_gemm_mxfp6_keep: operand > 2 GiB");
     hipStream_t st = (hipStream_t)stream;
-    return out_dtype == FINO_BF16 ? launch_mxfp6_keep<BF16>(fp, epilogue, st) : launch_mxfp6_keep<F16>(fp, epilogue, st);
+    return gemm_dispatch_dtype(out_dtype, [&](auto t) {
+        return gemm_dispatch_keep_epilogue(
+            epilogue, [&](auto e) { return launch_mxfp6<decltype(t), decltype(e)::value, true>(fp, st); });
+    });
 }

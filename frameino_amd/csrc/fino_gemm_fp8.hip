@@ -225,16 +225,6 @@ int launch_mxfp8(const MxGemmParams& fp, hipStream_t st) {
     return FINO_OK;
 }
 
-template <typename T>
-int launch_mxfp8_e(const MxGemmParams& fp, int epi, hipStream_t st) {
-    return mx_dispatch_epilogue(epi, [&](auto e) { return launch_mxfp8<T, decltype(e)::value>(fp, st); });
-}
-
-template <typename T>
-int launch_mxfp8_keep(const MxGemmParams& fp, int epi, hipStream_t st) {
-    return mx_dispatch_keep_epilogue(epi, [&](auto e) { return launch_mxfp8<T, decltype(e)::value, false, true>(fp, st); });
-}
-
 }  // namespace
 
 extern "C" int64_t fino_mxfp8_scale_bytes(int64_t rows, int64_t cols) {
@@ -282,11 +272,10 @@ extern "C" int fino_gemm_mxfp8_q(const void* aq, const void* a_scales, const voi
     if (m == 0) return FINO_OK;
     fp.g.cq = (uint8_t*)cq; fp.g.cs = (uint8_t*)c_scales; fp.g.cs_rows_pad = fp.m_pad;
     hipStream_t st = (hipStream_t)stream;
-    if (bias_dtype == FINO_BF16)
-        return epilogue == FINO_EPI_NONE ? launch_mxfp8<BF16, FINO_EPI_NONE, true>(fp, st)
-                                         : launch_mxfp8<BF16, FINO_EPI_GELU_TANH, true>(fp, st);
-    return epilogue == FINO_EPI_NONE ? launch_mxfp8<F16, FINO_EPI_NONE, true>(fp, st)
-                                     : launch_mxfp8<F16, FINO_EPI_GELU_TANH, true>(fp, st);
+    return gemm_dispatch_dtype(bias_dtype, [&](auto t) {      // QOUT exists for these two epilogues only
+        return gemm_dispatch_among<FINO_EPI_NONE, FINO_EPI_GELU_TANH>(
+            epilogue, [&](auto e) { return launch_mxfp8<decltype(t), decltype(e)::value, true>(fp, st); });
+    });
 }
 
 extern "C" int fino_gemm_mxfp8(const void* aq, const void* a_scales, const void* wq, const void* w_scales,
@@ -300,7 +289,9 @@ extern "C" int fino_gemm_mxfp8(const void* aq, const void* a_scales, const void*
     FINO_CHECK(m * k < (1ll << 31) && n * k < (1ll << 31), FINO_ERR_UNSUPPORTED, "fino_gemm_mxfp8: operand > 2 GiB");
     if (m == 0) return FINO_OK;
     hipStream_t st = (hipStream_t)stream;
-    return out_dtype == FINO_BF16 ? launch_mxfp8_e<BF16>(fp, epilogue, st) : launch_mxfp8_e<F16>(fp, epilogue, st);
+    return gemm_dispatch_dtype(out_dtype, [&](auto t) {
+        return gemm_dispatch_epilogue(epilogue, [&](auto e) { return launch_mxfp8<decltype(t), decltype(e)::value>(fp, st); });
+    });
 }
 
 extern "C" int fino_gemm_mxfp8_keep(const void* aq, const void* a_scales, const void* wq, const void* w_scales,
@@ -315,5 +306,8 @@ extern "C" int fino_gemm_mxfp8_keep(const void* aq, const void* a_scales, const 
     FINO_CHECK(m * k < (1ll << 31) && n * k < (1ll << 31), FINO_ERR_UNSUPPORTED, "fino_gemm_mxfp8_keep: operand > 2 GiB");
     if (m == 0) return FINO_OK;
     hipStream_t st = (hipStream_t)stream;
-    return out_dtype == FINO_BF16 ? launch_mxfp8_keep<BF16>(fp, epilogue, st) : launch_mxfp8_keep<F16>(fp, epilogue, st);
+    return gemm_dispatch_dtype(out_dtype, [&](auto t) {
+        return gemm_dispatch_keep_epilogue(
+            epilogue, [&](auto e) { return launch_mxfp8<decltype(t), decltype(e)::value, false, true>(fp, st); });
+    });
 }
