@@ -67,6 +67,9 @@ def main():
     ap.add_argument("--smooth-v", action="store_true",
                     help="with --fp8-attention: subtract the value mean before V is quantised and add it back to the output (exact: "
                          "the softmax weights sum to one)")
+    ap.add_argument("--smooth-q", action="store_true",
+                    help="with --fp8-attention: subtract each 256-row q-block's mean before Q is quantised and add its share of the "
+                         "logits back in fp32 (exact; the dense attention only: not with window or sparse attention)")
     ap.add_argument("--window-frames", type=int, default=None, metavar="N",
                     help="sliding-window self-attention over latent frames (approximate; quality on real checkpoints unmeasured): "
                          "a video query sees the text, its own latent frame +- N, the first frame and the identity frame; "
@@ -150,7 +153,7 @@ def main():
     if a.mxfp6:
         transformer.enable_mxfp6_linears(rotate=a.mxfp6_rotate)
     if a.fp8_attention:
-        transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v)
+        transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v, smooth_q=a.smooth_q)
     if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)
         from frameino_amd.window_attention import WindowAttentionConfig
         transformer.enable_window_attention(WindowAttentionConfig(window_frames=a.window_frames, sink_frames=(0,)))
@@ -184,7 +187,7 @@ def main():
         assert frames.shape == (a.frames, a.height, a.width, 3) and frames.dtype == np.uint8
         cond_s = f"conditions {tc - t0:.2f} s, " if rep == 0 else ""
         lin = "mxfp8" if a.mxfp8 else ("mxfp6, rotated blocks" if a.mxfp6_rotate else "mxfp6") if a.mxfp6 else a.dtype
-        mode = f"{lin} linears" + ((" + fp8 attention" + (" (smooth K)" if a.smooth_k else "") + (" (smooth V)" if a.smooth_v else "")) if a.fp8_attention else "")
+        mode = f"{lin} linears" + ((" + fp8 attention" + (" (smooth K)" if a.smooth_k else "") + (" (smooth V)" if a.smooth_v else "") + (" (smooth Q)" if a.smooth_q else "")) if a.fp8_attention else "")
         if a.window_frames is not None:
             mode += f" + window attention (+- {a.window_frames} frames)"
         if a.pab is not None:

@@ -137,6 +137,9 @@ def main():
     ap.add_argument("--smooth-v", action="store_true",
                     help="with --fp8-attention: subtract the value mean before V is quantised and add it back to the output (exact: "
                          "the softmax weights sum to one)")
+    ap.add_argument("--smooth-q", action="store_true",
+                    help="with --fp8-attention: subtract each 256-row q-block's mean before Q is quantised and add its share of the "
+                         "logits back in fp32 (exact; the dense attention only: not with window or sparse attention)")
     ap.add_argument("--mxfp6", action="store_true", help="MXFP6 (e2m3) linears in the DiT (reduced precision, opt-in)")
     ap.add_argument("--mxfp6-rotate", action="store_true",
                     help="with --mxfp6: rotate every 32-element block of weights and activations by the Walsh-Hadamard matrix "
@@ -257,7 +260,7 @@ def main():
     if a.mxfp6:                                    # after the LoRA merge: the merged weights are what is quantised
         transformer.enable_mxfp6_linears(rotate=a.mxfp6_rotate)
     if a.fp8_attention:
-        transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v)
+        transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v, smooth_q=a.smooth_q)
     if a.window_frames is not None:                # sinks: the first frame (config) and the ID frame (the loop's id_frames)
         from frameino_amd.window_attention import WindowAttentionConfig
         transformer.enable_window_attention(WindowAttentionConfig(window_frames=a.window_frames, sink_frames=(0,)))
@@ -316,7 +319,7 @@ def main():
               f"{sum(t for t in flat if t < 1.0) / max(1, sum(t < 1.0 for t in flat)):.3f}")
         transformer.enable_sparse_attention(sparse_cfg)
         if a.fp8_attention:
-            transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v)
+            transformer.enable_fp8_attention(smooth_k=a.smooth_k, smooth_v=a.smooth_v, smooth_q=a.smooth_q)
     torch.cuda.synchronize()
     tc = time.perf_counter()
     for rep in range(a.repeat):

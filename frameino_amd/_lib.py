@@ -77,6 +77,9 @@ SIGNATURES = {
     "fino_attn_fp8_smoothed_kv_bytes": [c_int, c_int, c_i64, c_int, c_int],
     "fino_attn_fwd_fp8_smoothed": [c_void_p] * 4 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 8 + [c_float, c_int, c_int,
                                                                                                     c_void_p, c_i64, c_void_p, c_int],
+    "fino_attn_fp8_smooth_q_kv_bytes": [c_int, c_int, c_i64, c_i64, c_int, c_int],
+    "fino_attn_fwd_fp8_smooth_q": [c_void_p] * 4 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 8 + [c_float, c_int, c_int,
+                                                                                                    c_void_p, c_i64, c_void_p, c_int],
     "fino_attn_fp8_tiles_supported": [c_int, c_int, c_i64, c_i64, c_int],
     "fino_attn_fwd_fp8_tiles": [c_void_p] * 4 + [c_int, c_int, c_i64, c_i64, c_int] + [c_i64] * 8 + [c_float, c_int, c_int,
                                                                                                  c_void_p, c_i64, c_int, c_void_p,
@@ -175,7 +178,7 @@ class StepCacheSegment(ctypes.Structure):
 _RESTYPES = {"fino_last_error": ctypes.c_char_p, "fino_attn_workspace_bytes": c_i64, "fino_mxfp8_scale_bytes": c_i64,
              "fino_groupnorm_workspace_bytes": c_i64,
              "fino_attn_partial_bytes": c_i64, "fino_attn_fp8_kv_bytes": c_i64, "fino_attn_fp8_smooth_kv_bytes": c_i64,
-             "fino_attn_fp8_smoothed_kv_bytes": c_i64, "fino_mxfp6_bytes": c_i64,
+             "fino_attn_fp8_smoothed_kv_bytes": c_i64, "fino_attn_fp8_smooth_q_kv_bytes": c_i64, "fino_mxfp6_bytes": c_i64,
              "fino_mxfp6_scale_bytes": c_i64, "fino_attn_tile_plan_bytes": c_i64,
              "fino_attn_tile_plan_gated_bytes": c_i64, "fino_magcache_workspace_bytes": c_i64,
              "fino_guider_workspace_bytes": c_i64}

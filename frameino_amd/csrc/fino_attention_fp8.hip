@@ -215,6 +215,76 @@ __global__ __launch_bounds__(256) void attn_kmean_finish_kernel(const MeanParams
     (op ? p.mean[1] : p.mean[0])[(int64_t)bi * p.channels + c] = s / (float)p.lk;
 }
 
+// ---- SMOOTH Q (fino_attn_fwd_fp8_smooth_q): the pre-pass.  For a block of 256 consecutive query rows, qbar = the mean of q over
+// the block's rows, s_ij = (q_i - qbar) . k_j + qbar . k_j: the first term goes through e4m3 as ever (load_q_fp8<T, true>), the
+// second is one fp32 number per (block, key), the same for every row of the block, taken from the UNQUANTISED keys here and added
+// to the logits by the main kernels.  Exact in real arithmetic.  Unlike K's mean the softmax sees it (it differs from key to key).
+//   1. sums per (batch element, 256-row block, channel): attn_kmean_partial_kernel on q as it is (its chunk IS the block);
+//   2. attn_qmean_finish_kernel: / the block's real row count, in place -> qmean [batch][block][heads * head_dim];
+//   3. attn_qbias_kernel: bias[batch * heads + head][block][key] = pre * qbar . (k_key - mu_K if smooth K), pre = the main kernels'
+//      scale_log2 (x 8 under the ramp p_mode), as a pair of T: hi = T(bias), lo = T(bias - hi), one 32-bit word hi | lo << 16.
+//      hi + lo carries >= 16 significant bits (bf16: 8 + 8, fp16: 11 + 11) and 1 x hi + 1 x lo is exact in the fold MFMA's fp32
+//      accumulator.  fp16: |bias| shares the range of the running maximum -m, which rides the same operand (logits beyond 65504
+//      S units = 8188 octaves under the ramp are out of the plain kernel's reach already); lo >= 2^-11 |hi| leaves fp16's normal
+//      range below |bias| = 2^-3, where what a subnormal lo drops is < 2^-25 S units.
+//      Rows of nt * 64 words: the keys in [lk, nt * 64) get zero words (their logits are masked by the main kernels).
+// A fixed partition and a fixed order, no atomics: the same inputs give the same bits.
+__global__ __launch_bounds__(256) void attn_qmean_finish_kernel(float* qmean, int lq, int nqb, int channels) {
+    const int c = blockIdx.x * 256 + threadIdx.x, qb = blockIdx.y, bi = blockIdx.z;
+    if (c >= channels) return;
+    const int rows = lq - qb * kMeanRows < kMeanRows ? lq - qb * kMeanRows : kMeanRows;
+    float* x = qmean + ((int64_t)bi * nqb + qb) * channels + c;
+    *x = *x / (float)rows;
+}
+
+struct QBiasParams {
+    const uint16_t* k;
+    const float* kmean;    // [batch][heads * head_dim] (smooth K) or null
+    const float* qmean;    // [batch][nqb][heads * head_dim]
+    uint32_t* bias;        // [batch * heads][nqb][nt * 64]
+    int heads, lk, nqb, nt;
+    int64_t k_bs, k_rs;
+    float pre;
+};
+// thread = key: its row of K (minus the key mean) stays in registers, the q-blocks go by with their means at uniform addresses;
+// K is read once, the table written once in rows along the keys
+template <typename T, int HD>
+__global__ __launch_bounds__(256) void attn_qbias_kernel(const QBiasParams p) {
+    const int key = blockIdx.x * 256 + threadIdx.x, head = blockIdx.y, bi = blockIdx.z;
+    const int lkp = p.nt * kKV;
+    if (key >= lkp) return;
+    const int channels = p.heads * HD;
+    float kr[HD];
+#pragma unroll
+    for (int d = 0; d < HD; ++d) kr[d] = 0.f;
+    if (key < p.lk) {
+        const uint16_t* kp = p.k + bi * p.k_bs + (int64_t)key * p.k_rs + head * HD;
+#pragma unroll
+        for (int c8 = 0; c8 < HD / 8; ++c8) {
+            float f[8];
+            unpack8<T>(*reinterpret_cast<const uint4*>(kp + 8 * c8), f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) kr[8 * c8 + e] = f[e];
+        }
+        if (p.kmean) {
+            const float* mu = p.kmean + (int64_t)bi * channels + head * HD;
+#pragma unroll
+            for (int d = 0; d < HD; ++d) kr[d] -= mu[d];
+        }
+    }
+    const float* qm = p.qmean + (int64_t)bi * p.nqb * channels + head * HD;
+    uint32_t* dst = p.bias + ((int64_t)bi * p.heads + head) * p.nqb * lkp + key;
+    for (int qb = 0; qb < p.nqb; ++qb) {
+        const float* m = qm + (int64_t)qb * channels;
+        float acc = 0.f;
+#pragma unroll
+        for (int d = 0; d < HD; ++d) acc = fmaf(m[d], kr[d], acc);
+        const float bias = acc * p.pre;
+        const uint16_t hi = T::from_f32(bias), lo = T::from_f32(bias - T::to_f32(hi));
+        dst[(int64_t)qb * lkp] = key < p.lk ? ((uint32_t)hi | ((uint32_t)lo << 16)) : 0u;
+    }
+}
+
 // one workgroup per (batch * head, key tile): 256 threads; threads 0..127 own (key, channel block) of K, 128..255
 // (channel, key block) of V
 template <typename T, int SM>               // SM: FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V
@@ -312,6 +382,14 @@ struct Fp8AttnParams {
     const uint8_t* vs;
     int nt;
 };
+// SMOOTH Q (fino_attn_fwd_fp8_smooth_q; template parameter SQ of the free-running and the head_dim 128 kernel): a derived struct,
+// so the kernels without it keep the argument block they had.
+struct Fp8AttnParamsQ : Fp8AttnParams {
+    const float* qmean;        // fp32 [batch][ceil(lq / 256)][heads * head_dim]: the mean of q over the rows of its 256-row block
+    const uint32_t* qbias;     // [batch * heads][ceil(lq / 256)][nt * 64] words: T(hi) | T(lo) << 16 of qbar . k_key in S units
+};
+template <bool SQ> struct Fp8ParamsSel { typedef Fp8AttnParams type; };
+template <> struct Fp8ParamsSel<true> { typedef Fp8AttnParamsQ type; };
 
 // LDS: K8 ring (8 x 4 KiB) | V8T ring (8 x 4 KiB) | K scale ring (8 x 128 B) | V scale ring (8 x 128 B)
 constexpr int kRing8 = 8;
@@ -324,9 +402,12 @@ constexpr int kSmem8 = kLdsVS + kRing8 * 128;
 // Q row -> e4m3 B operand: lane (row r, group g) holds channels 16 g .. 16 g + 15 and 32 + 16 g .. + 15, pre-scaled, with
 // one scale per 32-channel block (block b = channels [32 b, 32 b + 32): half of it sits in the partner lane); q_scale =
 // the scale byte of block g (the operand this lane group supplies).  Rows past lq: zeros.
-template <typename T>
+// SQ (smooth Q): qm = the 64 fp32 means of the row's 256-row block for these channels; q - qm in fp32 (exact for operands whose
+// difference is representable), THEN the pre-scale, so the amax / e8m0 / convert sequence sees what differs from row to row.
+// Rows past lq stay zeros.
+template <typename T, bool SQ = false>
 __device__ __forceinline__ void load_q_fp8(const AttnParams& p, const uint16_t* qp, int qrow, int g, i32x8_t& qf,
-                                           int& q_scale) {
+                                           int& q_scale, const float* qm = nullptr) {
     const int qrow_c = qrow < p.lq ? qrow : p.lq - 1;
     {
         float x[2][16];
@@ -339,6 +420,14 @@ __device__ __forceinline__ void load_q_fp8(const AttnParams& p, const uint16_t* 
                 if (qrow >= p.lq) u = make_uint4(0, 0, 0, 0);
                 float f[8];
                 unpack8<T>(u, f);
+                if constexpr (SQ) {
+                    if (qrow < p.lq) {
+                        const float4 m0 = *reinterpret_cast<const float4*>(qm + 16 * ch + 8 * hlf);
+                        const float4 m1 = *reinterpret_cast<const float4*>(qm + 16 * ch + 8 * hlf + 4);
+                        f[0] -= m0.x; f[1] -= m0.y; f[2] -= m0.z; f[3] -= m0.w;
+                        f[4] -= m1.x; f[5] -= m1.y; f[6] -= m1.z; f[7] -= m1.w;
+                    }
+                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) x[c][8 * hlf + e] = f[e] * p.scale_log2;
             }
@@ -711,8 +800,17 @@ constexpr int kFrSmem = kFrLdsVS + kFrRing * 128;       // 33 KiB
 // only the DMA's tile offset and the ragged mask see the global one.  The six integers are read once, clipped to [0, ntall]
 // and made wave-uniform, so g is scalar arithmetic; the buffer resources span the head's whole images either way (a bad table
 // can give a wrong answer, never a read outside them).  RG = false is the code it was.
-template <typename T, int PX, bool RG = false>
-__global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8AttnParams fp) {
+//
+// SQ (fino_attn_fwd_fp8_smooth_q; dense walk only): the mean of q over the rows of its 256-row block (row qb >> 1 of fp.qmean: two
+// of this kernel's blocks share one) leaves q before it is quantised, and what it contributed to the logits, qbar . k_key -- one fp32
+// per (256-row block, key), computed from the unquantised keys by attn_qbias_kernel and stored as a hi | lo pair of T -- comes back
+// through the MFMA that already carries -m: key row r's pair sits in k-slots 2 / 3 of the A operand ("ones" in slots 0 / 1), ones in
+// slots 2 / 3 of B (-m and the ramp's constant in 0 / 1).  One fold per 32-key half (their keys differ), two dwords per lane and
+// tile, loaded at the top of the tile in front of its DMAs (so the hand-counted vmcnt waits mean what they meant).  All lanes load
+// (lane group 1 the words of group 0: finite numbers), and B's slots are zero in group 1.  SQ = false is the code it was.
+template <typename T, int PX, bool RG = false, bool SQ = false>
+__global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const typename Fp8ParamsSel<SQ>::type fp) {
+    static_assert(!(RG && SQ), "smooth Q exists on the dense walk only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const AttnParams& p = fp.a;
     constexpr int kDT = kD8 / 32;
@@ -772,7 +870,24 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
     }
     i32x8_t qf;
     int q_scale;
-    load_q_fp8<T>(p, qp, qrow, g, qf, q_scale);
+    const uint32_t* sq_row = nullptr;        // SQ: this lane's word of key tile 0, first half (second half: + 32 words)
+    if constexpr (SQ) {
+        const int nqb256 = (p.lq + 255) >> 8;
+        load_q_fp8<T, true>(p, qp, qrow, g, qf, q_scale,
+                            fp.qmean + ((int64_t)bi * nqb256 + (qb >> 1)) * ((int64_t)p.heads * kD8) + head * kD8);
+        sq_row = fp.qbias + ((int64_t)hb * nqb256 + (qb >> 1)) * ((int64_t)ntall * kKV) + r;
+    } else {
+        load_q_fp8<T>(p, qp, qrow, g, qf, q_scale);
+    }
+    // SQ: the bias words of tile U_ (past the last tile: that tile's again, like the DMA)
+    uint32_t sq_w0 = 0, sq_w1 = 0;
+#define FR_SQLOAD(U_)                                                                                        \
+    if constexpr (SQ) {                                                                                      \
+        const uint32_t* b_ = sq_row + ((U_) < nt ? (U_) : nt - 1) * kKV;                                     \
+        sq_w0 = b_[0];                                                                                       \
+        sq_w1 = b_[32];                                                                                      \
+    }
+    FR_SQLOAD(0)
 
     // ---- staging: wave w moves LDS positions 64 w .. 64 w + 63 (16-byte slots) of the K8 and of the V8T image, and (lanes
     //      0..31) the K scales (waves 0, 2) or the V scales (waves 1, 3): three vector-memory operations per wave and tile ----
@@ -816,6 +931,16 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
     const f32x16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     uint4 ones_u = make_uint4(g == 0 ? px_ones_word<T, PX>() : 0u, 0u, 0u, 0u);
     asm volatile("" : "+v"(ones_u.x));
+    // SQ: k-slots 2 / 3 of the fold's B operand -- ones in lane group 0 (the ramp's "ones" word is that already), zeros in group 1
+    uint32_t sq_b = 0;
+    if constexpr (SQ) {
+        if constexpr (PX) {
+            sq_b = ones_u.x;
+        } else {
+            sq_b = g == 0 ? px_ones_word<T, 1>() : 0u;
+            asm volatile("" : "+v"(sq_b));
+        }
+    }
 
     // per-lane byte offsets of the two 16-byte chunks of row r inside a tile image (rows 32 + r: + 2048)
     const int la0 = r * 64 + 16 * (chunk0(g) ^ swz8(r));
@@ -854,7 +979,15 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
     // ---- S(0) unpipelined ----
     f32x16_t s0, s1;
     FR_KREAD(0)
-    FR_QK(zero16, zero16, s0, s1)
+    if constexpr (SQ) {
+        // S(0) = bias + K(0) . Q^T: the fold with nothing in the -m slots
+        const vec8 b_ = __builtin_bit_cast(vec8, make_uint4(0u, sq_b, 0u, 0u));
+        const f32x16_t c0 = T::mfma32(__builtin_bit_cast(vec8, make_uint4(ones_u.x, sq_w0, 0u, 0u)), b_, zero16);
+        const f32x16_t c1 = T::mfma32(__builtin_bit_cast(vec8, make_uint4(ones_u.x, sq_w1, 0u, 0u)), b_, zero16);
+        FR_QK(c0, c1, s0, s1)
+    } else {
+        FR_QK(zero16, zero16, s0, s1)
+    }
     FR_MASK(0, s0, s1)
     float m_run;
     {
@@ -888,6 +1021,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
 #define FR_TILE(T_, SI0_, SI1_, SO0_, SO1_)                                                                  \
     {                                                                                                        \
         const int t = (T_);                                                                                  \
+        FR_SQLOAD(t + 1)                                      /* SQ: the bias words of S(t+1), in front of the DMAs */ \
         /* tile t + 3 into the slot tile t - 1 left (its last reads ended before the previous barrier) */     \
         FRX_DMA(t + 3)                                                                                       \
         /* K fragments of S(t+1): they land under the exp2 work */                                           \
@@ -910,9 +1044,17 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
         }                                                                                                    \
         {                                                                                                    \
             uint4 mn_u = make_uint4(g == 0 ? px_mneg_word<T, PX>(m_run) : 0u, 0u, 0u, 0u);                \
-            const vec8 onesv = __builtin_bit_cast(vec8, ones_u), mnegv = __builtin_bit_cast(vec8, mn_u);     \
-            const f32x16_t c0 = FRX_FOLD(onesv, mnegv);                                                      \
-            FR_QK(c0, c0, SO0_, SO1_)                                                                        \
+            if constexpr (SQ) {                                                                              \
+                mn_u.y = sq_b;                                                                               \
+                const vec8 mnegv = __builtin_bit_cast(vec8, mn_u);                                           \
+                const f32x16_t c0 = FRX_FOLD(__builtin_bit_cast(vec8, make_uint4(ones_u.x, sq_w0, 0u, 0u)), mnegv); \
+                const f32x16_t c1 = FRX_FOLD(__builtin_bit_cast(vec8, make_uint4(ones_u.x, sq_w1, 0u, 0u)), mnegv); \
+                FR_QK(c0, c1, SO0_, SO1_)                                                                    \
+            } else {                                                                                         \
+                const vec8 onesv = __builtin_bit_cast(vec8, ones_u), mnegv = __builtin_bit_cast(vec8, mn_u); \
+                const f32x16_t c0 = FRX_FOLD(onesv, mnegv);                                                  \
+                FR_QK(c0, c0, SO0_, SO1_)                                                                    \
+            }                                                                                                \
         }                                                                                                    \
         /* V fragments only now: they take the registers the K fragments leave (168 registers per wave is the whole  \
            budget of three waves per SIMD) and land under the two S MFMAs and the other waves' work */       \
@@ -964,6 +1106,7 @@ __global__ __launch_bounds__(kFrWaves * 64, 3) void attn_fp8_fr_kernel(const Fp8
 #undef FR_KREAD
 #undef FR_QK
 #undef FR_MASK
+#undef FR_SQLOAD
 
     // (direct 8-byte stores: the staged whole-row form of the other kernels -- attn_rows_through_lds -- pushed this kernel, which
     // lives at the 168-register limit of three workgroups per CU, into scratch spills inside its loop)
@@ -1031,8 +1174,13 @@ constexpr int kL128List = kSmem128 + kMuSlot;                // uint32 list, VAR
 constexpr int kSmem128Tiles = kL128List + (kAttnMaxTiles + kAttnTileListPad) * 4;
 static_assert(kSmem128Tiles <= 160 * 1024, "rings + mean slot + tile list must fit the CU's 160 KiB of LDS");
 
-template <typename T, int PX, bool TL = false>
-__global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8AttnParams fp, const AttnTileMask tm) {
+// SQ (fino_attn_fwd_fp8_smooth_q; dense walk, tail split included: the launch plan of the plain call): attn_fp8_fr_kernel's smooth Q.
+// This kernel's block IS the 256-row block of the means; each sub-head's half of q loses its half of them; the bias is one number
+// per key for the whole head, so the fold carries it once.  The two words of S(t+1) are loaded at the top of the softmax phase of
+// tile t, in front of its DMAs, and used behind the barrier.  SQ = false is the code it was.
+template <typename T, int PX, bool TL = false, bool SQ = false>
+__global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const typename Fp8ParamsSel<SQ>::type fp, const AttnTileMask tm) {
+    static_assert(!(TL && SQ), "smooth Q exists on the dense walk only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const AttnParams& p = fp.a;
     typedef typename T::vec8 vec8;
@@ -1112,8 +1260,26 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
     const int qrow = qb * kQBlock + wave * kQRowsPerWave + r;
     i32x8_t qf[2];
     int q_scale[2];
-    load_q_fp8<T>(p, qp, qrow, g, qf[0], q_scale[0]);
-    load_q_fp8<T>(p, qp + 64, qrow, g, qf[1], q_scale[1]);
+    const uint32_t* sq_row = nullptr;        // SQ: this lane's word of key tile 0, first half (second half: + 32 words)
+    if constexpr (SQ) {
+        const float* qm = fp.qmean + ((int64_t)bi * p.nqb + qb) * ((int64_t)p.heads * 128) + head * 128;
+        load_q_fp8<T, true>(p, qp, qrow, g, qf[0], q_scale[0], qm);
+        load_q_fp8<T, true>(p, qp + 64, qrow, g, qf[1], q_scale[1], qm + 64);
+        sq_row = fp.qbias + ((int64_t)hb * p.nqb + qb) * ((int64_t)ntall * kKV) + r;
+    } else {
+        load_q_fp8<T>(p, qp, qrow, g, qf[0], q_scale[0]);
+        load_q_fp8<T>(p, qp + 64, qrow, g, qf[1], q_scale[1]);
+    }
+    // SQ: the bias words of tile U_ of this range (a table row is indexed by the head's global key tile; past the last tile:
+    // that tile's again, like the DMA)
+    uint32_t sq_w0 = 0, sq_w1 = 0;
+#define D8_SQLOAD(U_)                                                                                        \
+    if constexpr (SQ) {                                                                                      \
+        const uint32_t* b_ = sq_row + (t_begin + ((U_) < nt ? (U_) : nt - 1)) * kKV;                         \
+        sq_w0 = b_[0];                                                                                       \
+        sq_w1 = b_[32];                                                                                      \
+    }
+    D8_SQLOAD(0)
 
     // ---- staging (LDS-DMA): waves 0 / 1 of a group move the group's half of BOTH K8 images of a tile, 2 / 3 of both V8T
     //      images; lanes 0..15 also the group's half of their scale blocks: four vector-memory operations per wave and tile ----
@@ -1171,6 +1337,16 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
     const f32x16_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     uint4 ones_u = make_uint4(g == 0 ? px_ones_word<T, PX>() : 0u, 0u, 0u, 0u);
     asm volatile("" : "+v"(ones_u.x));
+    // SQ: k-slots 2 / 3 of the fold's B operand -- ones in lane group 0 (the ramp's "ones" word is that already), zeros in group 1
+    uint32_t sq_b = 0;
+    if constexpr (SQ) {
+        if constexpr (PX) {
+            sq_b = ones_u.x;
+        } else {
+            sq_b = g == 0 ? px_ones_word<T, 1>() : 0u;
+            asm volatile("" : "+v"(sq_b));
+        }
+    }
     const int la0 = r * 64 + 16 * (chunk0(g) ^ swz8(r));
     const int la1 = r * 64 + 16 * (chunk1(g) ^ swz8(r));
     const int ls0 = r * 2 + g;
@@ -1189,12 +1365,12 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
         kS[sb_][0] = *reinterpret_cast<const uint8_t*>(sb__ + ls0);                                          \
         kS[sb_][1] = *reinterpret_cast<const uint8_t*>(sb__ + 64 + ls0);                                     \
     }
-#define D8_QK(C_, S0_, S1_)                                                                                  \
+#define D8_QK(C0_, C1_, S0_, S1_)                                                                                  \
     {                                                                                                        \
         S0_ = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(                                               \
-            __builtin_shufflevector(kA[0][0][0], kA[0][0][1], 0, 1, 2, 3, 4, 5, 6, 7), qf[0], C_, 0, 0, 0, kS[0][0], 0, q_scale[0]); \
+            __builtin_shufflevector(kA[0][0][0], kA[0][0][1], 0, 1, 2, 3, 4, 5, 6, 7), qf[0], C0_, 0, 0, 0, kS[0][0], 0, q_scale[0]); \
         S1_ = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(                                               \
-            __builtin_shufflevector(kA[0][1][0], kA[0][1][1], 0, 1, 2, 3, 4, 5, 6, 7), qf[0], C_, 0, 0, 0, kS[0][1], 0, q_scale[0]); \
+            __builtin_shufflevector(kA[0][1][0], kA[0][1][1], 0, 1, 2, 3, 4, 5, 6, 7), qf[0], C1_, 0, 0, 0, kS[0][1], 0, q_scale[0]); \
         S0_ = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(                                               \
             __builtin_shufflevector(kA[1][0][0], kA[1][0][1], 0, 1, 2, 3, 4, 5, 6, 7), qf[1], S0_, 0, 0, 0, kS[1][0], 0, q_scale[1]); \
         S1_ = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(                                               \
@@ -1213,7 +1389,15 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
 
     f32x16_t s0, s1;
     D8_KREAD(0)
-    D8_QK(zero16, s0, s1)
+    if constexpr (SQ) {
+        // S(0) = bias + K(0) . Q^T: the fold with nothing in the -m slots
+        const vec8 b_ = __builtin_bit_cast(vec8, make_uint4(0u, sq_b, 0u, 0u));
+        const f32x16_t c0 = T::mfma32(__builtin_bit_cast(vec8, make_uint4(ones_u.x, sq_w0, 0u, 0u)), b_, zero16);
+        const f32x16_t c1 = T::mfma32(__builtin_bit_cast(vec8, make_uint4(ones_u.x, sq_w1, 0u, 0u)), b_, zero16);
+        D8_QK(c0, c1, s0, s1)
+    } else {
+        D8_QK(zero16, zero16, s0, s1)
+    }
     D8_MASK(0, s0, s1)
     float m_run;
     {
@@ -1249,6 +1433,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
             pf[i] = (int)p_bytes4<PX>(s0[4 * i], s0[4 * i + 1], s0[4 * i + 2], s0[4 * i + 3]);
             pf[4 + i] = (int)p_bytes4<PX>(s1[4 * i], s1[4 * i + 1], s1[4 * i + 2], s1[4 * i + 3]);
         }
+        D8_SQLOAD(t + 1)                                      // SQ: the bias words of S(t+1), in front of the DMAs
         uint32_t tl_gv = 0;
         if constexpr (TL) {
             D8_DMA_T(t + 4, tl_g)
@@ -1279,9 +1464,17 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
         }
         {
             uint4 mn_u = make_uint4(g == 0 ? px_mneg_word<T, PX>(m_run) : 0u, 0u, 0u, 0u);
-            const vec8 onesv = __builtin_bit_cast(vec8, ones_u), mnegv = __builtin_bit_cast(vec8, mn_u);
-            const f32x16_t c0 = T::mfma32(onesv, mnegv, zero16);
-            D8_QK(c0, s0, s1)
+            if constexpr (SQ) {
+                mn_u.y = sq_b;
+                const vec8 mnegv = __builtin_bit_cast(vec8, mn_u);
+                const f32x16_t c0 = T::mfma32(__builtin_bit_cast(vec8, make_uint4(ones_u.x, sq_w0, 0u, 0u)), mnegv, zero16);
+                const f32x16_t c1 = T::mfma32(__builtin_bit_cast(vec8, make_uint4(ones_u.x, sq_w1, 0u, 0u)), mnegv, zero16);
+                D8_QK(c0, c1, s0, s1)
+            } else {
+                const vec8 onesv = __builtin_bit_cast(vec8, ones_u), mnegv = __builtin_bit_cast(vec8, mn_u);
+                const f32x16_t c0 = T::mfma32(onesv, mnegv, zero16);
+                D8_QK(c0, c0, s0, s1)
+            }
         }
 #define D8_PV(D4_)                                                                                           \
         o[D4_] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(                                            \
@@ -1311,6 +1504,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void attn_fp8_d128_kernel(const Fp8
 #undef D8_KREAD
 #undef D8_QK
 #undef D8_MASK
+#undef D8_SQLOAD
 
     if (part >= 0) {
         // partial in the bf16 kernels' layout (attn_combine_kernel finishes): m, O and l share the 2^kPShift offset, which
@@ -1375,6 +1569,18 @@ extern "C" int64_t fino_attn_fp8_smoothed_kv_bytes(int batch, int heads, int64_t
     return b;
 }
 
+// fino_attn_fp8_smoothed_kv_bytes(smooth & 3) | pad to 16 | with FINO_FP8_SMOOTH_Q: qmean fp32 [batch][ceil(lq / 256)][heads *
+// head_dim] | pad to 16 | bias words [batch * heads][ceil(lq / 256)][ceil(lk / 64) * 64]
+static int64_t sq_blocks(int64_t lq) { return (lq + kMeanRows - 1) / kMeanRows; }
+extern "C" int64_t fino_attn_fp8_smooth_q_kv_bytes(int batch, int heads, int64_t lq, int64_t lk, int head_dim, int smooth) {
+    if (smooth < 0 || smooth > (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V | FINO_FP8_SMOOTH_Q) || lq < 0) return 0;
+    int64_t b = fino_attn_fp8_smoothed_kv_bytes(batch, heads, lk, head_dim, smooth & (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V));
+    if (b <= 0 || !(smooth & FINO_FP8_SMOOTH_Q)) return b;
+    const int64_t nqb = sq_blocks(lq), nt = (lk + kKV - 1) / kKV;
+    b = ((b + 15) & ~(int64_t)15) + (int64_t)batch * nqb * heads * head_dim * 4;
+    return ((b + 15) & ~(int64_t)15) + (int64_t)batch * heads * nqb * nt * kKV * 4;
+}
+
 // every entry point: `smooth` (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V) != 0 = means -> smoothing quantiser, otherwise the plain
 // quantiser; the main-kernel launch is the same, and with FINO_FP8_SMOOTH_V it gets the mean of V to add back (AttnParams::vmean).
 // `ranges` (fino_attn_fwd_fp8_ranges): head_dim 64 only, always attn_fp8_fr_kernel<T, PX, true>, whatever the tuning knob says.
@@ -1385,6 +1591,8 @@ struct KFr     { template <typename T, int PX> static constexpr auto kernel() { 
 struct KFrRg   { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_fr_kernel<T, PX, true>; } };
 struct KD128   { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_d128_kernel<T, PX>; } };
 struct KD128Tl { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_d128_kernel<T, PX, true>; } };
+struct KFrSq   { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_fr_kernel<T, PX, false, true>; } };
+struct KD128Sq { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_d128_kernel<T, PX, false, true>; } };
 struct KPp     { template <typename T, int PX> static constexpr auto kernel() { return &attn_fp8_kernel<T, 0, PX>; } };
 
 template <class Family, typename T, int PX, class... Args>
@@ -1417,11 +1625,14 @@ static int fp8_launch(const char* fn, int dtype, bool ramp, dim3 grid, int threa
 
 static int attn_fwd_fp8_impl(const char* fn, int smooth, const AttnOperands& a, int dtype, int p_mode, void* kv_workspace,
                              int64_t kv_workspace_bytes, void* stream, const int* ranges = nullptr,
-                             const AttnTileMask* tiles = nullptr) {
+                             const AttnTileMask* tiles = nullptr, bool allow_q = false) {
     const int batch = a.batch, heads = a.heads, head_dim = a.head_dim;
     const int64_t lq = a.lq, lk = a.lk, k_bs = a.k_bs, k_rs = a.k_rs, v_bs = a.v_bs, v_rs = a.v_rs;
-    FINO_CHECK(smooth >= 0 && smooth <= (FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V), FINO_ERR_ARG, "%s: smooth flags %d not in 0 .. 3", fn,
-               smooth);
+    // bit FINO_FP8_SMOOTH_Q: fino_attn_fwd_fp8_smooth_q alone (the dense walk); `smooth` below is the K | V part, as ever
+    const int smooth_kvq = smooth, smooth_max = allow_q ? 7 : 3;
+    FINO_CHECK(smooth >= 0 && smooth <= smooth_max, FINO_ERR_ARG, "%s: smooth flags %d not in 0 .. %d", fn, smooth, smooth_max);
+    const bool sq = (smooth & FINO_FP8_SMOOTH_Q) != 0;
+    smooth &= FINO_FP8_SMOOTH_K | FINO_FP8_SMOOTH_V;
     FINO_CHECK(p_mode == FINO_FP8_P_EXP2 || p_mode == FINO_FP8_P_RAMP, FINO_ERR_ARG, "%s: p_mode %d", fn, p_mode);
     FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "%s: dtype %d", fn, dtype);
     FINO_CHECK(head_dim == 64 || head_dim == 128, FINO_ERR_UNSUPPORTED, "%s: head_dim %d not in {64, 128}", fn, head_dim);
@@ -1434,7 +1645,8 @@ static int attn_fwd_fp8_impl(const char* fn, int smooth, const AttnOperands& a, 
             return FINO_OK;
         }))
         return rc;
-    const int64_t need = fino_attn_fp8_smoothed_kv_bytes(batch, heads, lk, head_dim, smooth);
+    const int64_t need = sq ? fino_attn_fp8_smooth_q_kv_bytes(batch, heads, lq, lk, head_dim, smooth_kvq)
+                            : fino_attn_fp8_smoothed_kv_bytes(batch, heads, lk, head_dim, smooth);
     FINO_CHECK(kv_workspace_bytes >= need, FINO_ERR_ARG, "%s: workspace %lld B < %lld B", fn,
                (long long)kv_workspace_bytes, (long long)need);
     if (lq == 0) return FINO_OK;
@@ -1492,24 +1704,66 @@ static int attn_fwd_fp8_impl(const char* fn, int smooth, const AttnOperands& a, 
     }
     FINO_LAUNCH_CHECK();
 
-    Fp8AttnParams fp;
+    Fp8AttnParamsQ fp;                       // (the kernels without smooth Q take its base)
     AttnParams& p = fp.a;
     const bool ramp = p_mode == FINO_FP8_P_RAMP;
-    const bool free_running = head_dim == 64 && (ranges || fino_tune_get(FINO_TUNE_ATTN_FP8_KERNEL) != 1);   // default at head_dim 64
+    // default at head_dim 64; the range walk and smooth Q exist in it alone
+    const bool free_running = head_dim == 64 && (ranges || sq || fino_tune_get(FINO_TUNE_ATTN_FP8_KERNEL) != 1);
     attn_fill_params(p, a, free_running ? kFrQBlock : kQBlock);
     p.k = p.v = nullptr;                     // the main kernels read the quantised images, not K / V
     p.k_bs = p.k_rs = p.k_hs = p.v_bs = p.v_rs = p.v_hs = 0;
     if (ramp) p.scale_log2 *= 8.0f;          // logits in eighths of an octave: an exact shift of q's e8m0 block scales
     p.ranges = ranges; p.vmean = qp.vmean;
     fp.k8 = qp.k8; fp.ks = qp.ks; fp.v8t = qp.v8t; fp.vs = qp.vs; fp.nt = nt;
+    fp.qmean = nullptr; fp.qbias = nullptr;
+    const Fp8AttnParams& fpl = fp;           // what the kernels without smooth Q get: the struct they always got
     const dim3 grid(attn_whole_blocks(p));
-    if (free_running) {
-        if (int rc = ranges ? fp8_launch<KFrRg>(fn, dtype, ramp, grid, kFrWaves * 64, kFrSmem + kMuSlot, st, fp)
-                            : fp8_launch<KFr>(fn, dtype, ramp, grid, kFrWaves * 64, kFrSmem + kMuSlot, st, fp))
+    if (sq) {
+        // smooth Q's pre-pass (three launches, see attn_qbias_kernel); the main launch below takes the SQ instantiation
+        const int nqb = (int)sq_blocks(lq), channels = heads * head_dim;
+        int64_t off = (fino_attn_fp8_smoothed_kv_bytes(batch, heads, lk, head_dim, smooth) + 15) & ~(int64_t)15;
+        float* qmean = (float*)(w8 + off);
+        off = (off + (int64_t)batch * nqb * channels * 4 + 15) & ~(int64_t)15;
+        uint32_t* qbias = (uint32_t*)(w8 + off);
+        MeanParams mq;
+        mq.lk = (int)lq; mq.chunks = nqb; mq.channels = channels; mq.nsrc = 1;
+        for (int s = 0; s < 2; ++s) {
+            mq.k[s] = (const uint16_t*)a.q; mq.k_bs[s] = a.q_bs; mq.k_rs[s] = a.q_rs; mq.part[s] = qmean; mq.mean[s] = qmean;
+        }
+        const int nkb = (nt * kKV + 255) / 256;
+        FINO_CHECK(nqb <= 65535 && batch <= 65535 && channels / kD8 <= 65535 && heads <= 65535, FINO_ERR_UNSUPPORTED,
+                   "%s: lq %lld / batch %d / %d channels beyond the smooth-Q pre-pass's grid", fn, (long long)lq, batch, channels);
+        const dim3 gpart((unsigned)nqb, (unsigned)(channels / kD8), (unsigned)batch);
+        if (dtype == FINO_BF16) attn_kmean_partial_kernel<BF16><<<gpart, 256, 0, st>>>(mq);
+        else attn_kmean_partial_kernel<F16><<<gpart, 256, 0, st>>>(mq);
+        FINO_LAUNCH_CHECK();
+        attn_qmean_finish_kernel<<<dim3((unsigned)((channels + 255) / 256), (unsigned)nqb, (unsigned)batch), 256, 0, st>>>(
+            qmean, (int)lq, nqb, channels);
+        FINO_LAUNCH_CHECK();
+        QBiasParams bp;
+        bp.k = qp.k; bp.kmean = qp.mean; bp.qmean = qmean; bp.bias = qbias;
+        bp.heads = heads; bp.lk = (int)lk; bp.nqb = nqb; bp.nt = nt; bp.k_bs = k_bs; bp.k_rs = k_rs; bp.pre = p.scale_log2;
+        const dim3 gb((unsigned)nkb, (unsigned)heads, (unsigned)batch);
+        if (head_dim == 64) {
+            if (dtype == FINO_BF16) attn_qbias_kernel<BF16, 64><<<gb, 256, 0, st>>>(bp);
+            else attn_qbias_kernel<F16, 64><<<gb, 256, 0, st>>>(bp);
+        } else {
+            if (dtype == FINO_BF16) attn_qbias_kernel<BF16, 128><<<gb, 256, 0, st>>>(bp);
+            else attn_qbias_kernel<F16, 128><<<gb, 256, 0, st>>>(bp);
+        }
+        FINO_LAUNCH_CHECK();
+        fp.qmean = qmean; fp.qbias = qbias;
+        if (fino_tune_get(FINO_TUNE_ATTN_FP8_SQ_PREPASS) == 1) return FINO_OK;       // timing: the pre-pass alone
+    }
+    if (sq && free_running) {
+        if (int rc = fp8_launch<KFrSq>(fn, dtype, ramp, grid, kFrWaves * 64, kFrSmem + kMuSlot, st, fp)) return rc;
+    } else if (free_running) {
+        if (int rc = ranges ? fp8_launch<KFrRg>(fn, dtype, ramp, grid, kFrWaves * 64, kFrSmem + kMuSlot, st, fpl)
+                            : fp8_launch<KFr>(fn, dtype, ramp, grid, kFrWaves * 64, kFrSmem + kMuSlot, st, fpl))
             return rc;
     } else if (tiles) {
         // whole blocks only; the tile list sits behind the rings and the mean slot
-        if (int rc = fp8_launch<KD128Tl>(fn, dtype, ramp, grid, kWaves * 64, kSmem128Tiles, st, fp, *tiles)) return rc;
+        if (int rc = fp8_launch<KD128Tl>(fn, dtype, ramp, grid, kWaves * 64, kSmem128Tiles, st, fpl, *tiles)) return rc;
     } else if (head_dim == 128) {
         // tail split: the last, partial round of (head, q-block) workgroups is cut over the keys (fino_attention.hip's plan)
         int full_x, rem_x, nwg, per;
@@ -1520,12 +1774,14 @@ static int attn_fwd_fp8_impl(const char* fn, int smooth, const AttnOperands& a, 
             p.full_x = full_x; p.rem_x = rem_x; p.nwg = nwg; p.per = per;
         }
         const dim3 grid128((unsigned)(8 * (p.full_x + p.nwg)));
-        if (int rc = fp8_launch<KD128>(fn, dtype, ramp, grid128, kWaves * 64, kSmem128 + kMuSlot, st, fp, AttnTileMask{})) return rc;
+        if (int rc = sq ? fp8_launch<KD128Sq>(fn, dtype, ramp, grid128, kWaves * 64, kSmem128 + kMuSlot, st, fp, AttnTileMask{})
+                        : fp8_launch<KD128>(fn, dtype, ramp, grid128, kWaves * 64, kSmem128 + kMuSlot, st, fpl, AttnTileMask{}))
+            return rc;
         FINO_LAUNCH_CHECK();
         return fino_attn_launch_combine(p, dtype, 128, st);
     } else {
         // 66 KiB of dynamic LDS
-        if (int rc = fp8_launch<KPp>(fn, dtype, ramp, grid, kWaves * 64, kSmem8 + kMuSlot, st, fp)) return rc;
+        if (int rc = fp8_launch<KPp>(fn, dtype, ramp, grid, kWaves * 64, kSmem8 + kMuSlot, st, fpl)) return rc;
     }
     FINO_LAUNCH_CHECK();
     return FINO_OK;
@@ -1544,6 +1800,13 @@ extern "C" int fino_attn_fwd_fp8_smooth(FP8_LEAD_PARAMS, void* stream) {
 extern "C" int fino_attn_fwd_fp8_smoothed(FP8_LEAD_PARAMS, void* stream, int smooth) {
     return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smoothed", smooth, FP8_LEAD_OPERANDS, dtype, p_mode, kv_workspace, kv_workspace_bytes,
                              stream);
+}
+
+// smooth Q (include/frameino_hip.h): any combination of the three bits; without FINO_FP8_SMOOTH_Q the launches of
+// fino_attn_fwd_fp8_smoothed
+extern "C" int fino_attn_fwd_fp8_smooth_q(FP8_LEAD_PARAMS, void* stream, int smooth) {
+    return attn_fwd_fp8_impl("fino_attn_fwd_fp8_smooth_q", smooth, FP8_LEAD_OPERANDS, dtype, p_mode, kv_workspace, kv_workspace_bytes,
+                             stream, nullptr, nullptr, true);
 }
 
 // fp8 attention over up to three ranges of key tiles per 256 query rows (include/frameino_hip.h): fino_attn_fwd_fp8's

@@ -604,7 +604,7 @@ def _attn_fp8_prepare(p_mode, smooth_k, smooth_v, b, heads, lk, dh, device):
     return p_mode, flags, need, _attn_fp8_workspace(max(need, 0), device)
 
 
-def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=False, smooth_v=False):
+def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=False, smooth_v=False, smooth_q=False):
     """attention() with fp8 (e4m3) matrix operands, head_dim 64 or 128: K / V quantised per call (block-scaled, V transposed), Q
     and P in registers, both products on the block-scaled fp8 MFMA, softmax and accumulation in fp32 (fino_attn_fwd_fp8).
     p_mode: "exp2" | "ramp" (or the FP8_P_* integers); None = FP8_P_DEFAULT.
@@ -612,8 +612,15 @@ def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=Fa
     (fino_attn_fwd_fp8_smooth): the softmax cannot see it, and a channel offset all keys share stops costing mantissa bits.
     smooth_v: subtract the mean of V over the keys before V is quantised and add it back to the normalised output in fp32
     (fino_attn_fwd_fp8_smoothed): exact, because the softmax weights sum to one; V has one scale per (channel, 32 keys), so an
-    offset all keys of a channel share (a to_v bias, a DC component) stops costing mantissa bits."""
+    offset all keys of a channel share (a to_v bias, a DC component) stops costing mantissa bits.
+    smooth_q: subtract from every block of 256 consecutive query rows its mean (per batch element, head and channel) before q is
+    quantised, and add what the mean contributed to the logits -- qbar . k_key, one fp32 per (q-block, key), from the unquantised
+    keys -- back on the matrix pipe (fino_attn_fwd_fp8_smooth_q): exact, and an offset neighbouring query rows share (norm_q
+    weights, low-frequency RoPE channels) stops costing mantissa bits.  Three more small launches and a table of
+    B * heads * ceil(Lq / 256) * Lk words per call; the dense call only.  With smooth_q=False the call is what it was."""
     b, lq, lk, hd, dh, out, scale = _attn_args(q, k, v, heads, out, scale)
+    if smooth_q:
+        return _attention_fp8_smooth_q(q, k, v, out, b, heads, lq, lk, hd, dh, scale, p_mode, smooth_k, smooth_v)
     p_mode, flags, need, ws = _attn_fp8_prepare(p_mode, smooth_k, smooth_v, b, heads, lk, dh, q.device)
     if need <= 0:
         raise RuntimeError(f"attention_fp8: head_dim {dh} is not supported (64 or 128)")
@@ -621,6 +628,22 @@ def attention_fp8(q, k, v, heads, out=None, scale=None, p_mode=None, smooth_k=Fa
     done = _timed_attn(b, lq, lk, hd)
     _lib.check(getattr(_lib.lib(), fwd)(*_attn_fp8_lead(q, k, v, out, b, heads, lq, lk, dh, scale, p_mode, ws, need), _stream(),
                                         *((flags,) if smooth_v else ())), fwd)
+    if done is not None:
+        done()
+    return out
+
+
+def _attention_fp8_smooth_q(q, k, v, out, b, heads, lq, lk, hd, dh, scale, p_mode, smooth_k, smooth_v):
+    """attention_fp8(smooth_q=True): the flag word with FINO_FP8_SMOOTH_Q = 4 and the workspace that holds the means and the table"""
+    p_mode = FP8_P_DEFAULT if p_mode is None else FP8_P_MODES.get(p_mode, p_mode)
+    flags = _fp8_smooth_flags(smooth_k, smooth_v) | 4
+    need = _lib.lib().fino_attn_fp8_smooth_q_kv_bytes(b, heads, lq, lk, dh, flags)
+    if need <= 0:
+        raise RuntimeError(f"attention_fp8: head_dim {dh} is not supported (64 or 128)")
+    ws = _attn_fp8_workspace(need, q.device)
+    done = _timed_attn(b, lq, lk, hd)
+    _lib.check(_lib.lib().fino_attn_fwd_fp8_smooth_q(*_attn_fp8_lead(q, k, v, out, b, heads, lq, lk, dh, scale, p_mode, ws, need),
+                                                    _stream(), flags), "fino_attn_fwd_fp8_smooth_q")
     if done is not None:
         done()
     return out

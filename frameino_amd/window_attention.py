@@ -306,6 +306,7 @@ class SelfAttentionOptionsMixin:
         self.fp8_p_mode = None
         self.fp8_smooth_k = False
         self.fp8_smooth_v = False
+        self.fp8_smooth_q = False
         self._window = None               # WindowAttentionConfig or None: see enable_window_attention
         self._window_forwards = 0
         self.window_attention_log = []    # (forward index, timestep or None, windowed) since enable_window_attention
@@ -315,7 +316,18 @@ class SelfAttentionOptionsMixin:
         self._sparse_sims = {}            # layer -> (sim_q | sim_k of the last call (device), (b, heads, nqb, ntall)), gate + `keep_masks`
         self._sparse_calib = None         # a running calibration (frameino_amd/sparse_calibration.py), else None
 
-    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False, smooth_v=False):
+    def _smooth_q_refusals(self, smooth_q, window, sparse):
+        """smooth Q exists on the dense fp8 call alone: not on the fp8 range walk (window attention), not on the fp8 tile walk
+        (sparse attention)"""
+        if not smooth_q:
+            return
+        for on, what, walk in ((window, "window attention (enable_window_attention)", "fp8 range walk (fino_attn_fwd_fp8_ranges)"),
+                               (sparse, "sparse attention (enable_sparse_attention)", "fp8 tile walk (fino_attn_fwd_fp8_tiles)")):
+            if on:
+                raise NotImplementedError(f"fp8 attention with smooth_q and {what}: the {walk} has no smooth Q; switch one of "
+                                          f"them off first (enable_fp8_attention(smooth_q=False))")
+
+    def enable_fp8_attention(self, enabled=True, p_mode=None, smooth_k=False, smooth_v=False, smooth_q=False):
         """The self-attention with fp8 (e4m3) matrix operands -- q, k, v and P on the block-scaled fp8 MFMA, softmax and
         accumulation fp32 (`ops.attention_fp8`; the model's class docstring says where it applies).  Opt-in, no reference counterpart.
         p_mode: "exp2" | "ramp" -- how a softmax weight becomes its e4m3 byte (ops.FP8_P_*; None = ops.FP8_P_DEFAULT).
@@ -325,7 +337,14 @@ class SelfAttentionOptionsMixin:
         smooth_v: subtract the per-(batch element, head, channel) mean of V over the keys before V is quantised and add it back
         to the normalised output in fp32 (fino_attn_fwd_fp8_smoothed): exact, the softmax weights sum to one, and an offset that
         all keys of a channel share (attn1.to_v.bias, a DC component of the modulated input: V has no norm and no RoPE) stops
-        taking the mantissa bits.  Off by default."""
+        taking the mantissa bits.  Off by default.
+        smooth_q: subtract from every block of 256 consecutive query rows its per-(batch element, head, channel) mean before q is
+        quantised and add qbar . k_key back to the logits in fp32 (fino_attn_fwd_fp8_smooth_q): exact, and an
+        offset that neighbouring query rows share (norm_q weights, low-frequency RoPE channels) stops taking the mantissa bits.
+        The dense call only: refused with window attention and with sparse attention, in either order.  The token-sharded forward
+        keeps its bf16 attention.  Off by default."""
+        if enabled:
+            self._smooth_q_refusals(smooth_q, self._window is not None, self._sparse is not None)
         if enabled and getattr(self, "_step_cache_policy", None) is not None:
             self._cache_refusals(fp8=True)           # (a step cache that keeps K / V in the model dtype says so, once)
         if enabled and self._sparse is not None:
@@ -337,6 +356,7 @@ class SelfAttentionOptionsMixin:
         self.fp8_p_mode = p_mode
         self.fp8_smooth_k = bool(smooth_k)
         self.fp8_smooth_v = bool(smooth_v)
+        self.fp8_smooth_q = bool(smooth_q)
         return self
 
     def enable_window_attention(self, config):
@@ -356,6 +376,7 @@ class SelfAttentionOptionsMixin:
             raise NotImplementedError("window attention (enable_window_attention) with sparse attention "
                                       "(enable_sparse_attention): switch one of them off first; the sparse attention's "
                                       "`window_frames` keeps a window of frames always")
+        self._smooth_q_refusals(self.fp8_attention and self.fp8_smooth_q, True, False)
         self._window_refusals(self.fp8_attention, self._default_processors(), getattr(self, "parallel", None))
         self._window = config
         self._window_forwards = 0
@@ -449,6 +470,7 @@ class SelfAttentionOptionsMixin:
         if not isinstance(config, SparseAttentionConfig):
             raise TypeError(f"enable_sparse_attention takes a SparseAttentionConfig, got {type(config)}")
         config.check_model(self.config.num_layers, self.config.num_attention_heads)
+        self._smooth_q_refusals(self.fp8_attention and self.fp8_smooth_q, False, True)
         self._sparse_refusals(self.fp8_attention, self._default_processors(), getattr(self, "parallel", None))
         self._sparse = config
         self.sparse_attention_masks, self._sparse_mask_keys, self._sparse_sims = {}, {}, {}
@@ -597,10 +619,15 @@ class SelfAttentionOptionsMixin:
     def _attend(self, ops, q, k, v, heads, *, fp8, ranges=None, tiles=None, **kw):
         """one self-attention call: dense or over `ranges`, bf16 / fp16 or -- `fp8` -- with the model's fp8 options; `kw`: out=,
         scale=.  `tiles` (`_sparse_tiles`): the dynamic tile walk instead (with `fp8`: head_dim 128 only, `_sparse_refusals`)."""
+        if fp8 and self.fp8_smooth_q:
+            # (the enable_* calls have refused these; a walk reached some other way is refused before it launches)
+            self._smooth_q_refusals(True, ranges is not None, tiles is not None)
         if tiles is not None:
             return self._attend_tiles(ops, q, k, v, heads, tiles, fp8=fp8, **kw)
         if fp8:
             kw.update(p_mode=self.fp8_p_mode, smooth_k=self.fp8_smooth_k, smooth_v=self.fp8_smooth_v)
+            if self.fp8_smooth_q:
+                kw.update(smooth_q=True)             # the dense route alone (ranges is None here)
         if ranges is None:
             return (ops.attention_fp8 if fp8 else ops.attention)(q, k, v, heads, **kw)
         return (ops.attention_fp8_ranges if fp8 else ops.attention_ranges)(q, k, v, heads, ranges, **kw)

@@ -58,9 +58,12 @@ const char* fino_last_error(void);
  * tiles, whole blocks; by policy it serves Lk <= 1024 when there are at least two q-blocks per CU, the free-running kernel the
  * rest; 7 = the policy without the walking kernel.  FINO_TUNE_ATTN_WALK_GRID: workgroups of the walking kernel (0 = one per CU; tests use small counts to make runs of
  * blocks cross heads and batches on small shapes).
- * FINO_TUNE_ATTN_FP8_KERNEL (fino_attn_fwd_fp8): 1 = the 8-wave ping-pong kernel instead of the free-running 4-wave one. */
+ * FINO_TUNE_ATTN_FP8_KERNEL (fino_attn_fwd_fp8): 1 = the 8-wave ping-pong kernel instead of the free-running 4-wave one.
+ * FINO_TUNE_ATTN_FP8_SQ_PREPASS (fino_attn_fwd_fp8_smooth_q with FINO_FP8_SMOOTH_Q; timing only): 1 = stop behind smooth Q's
+ * pre-pass, before the main launch (the output is not written), so a timer sees the pre-pass alone. */
 enum { FINO_TUNE_GEMM_GROUP_M = 0, FINO_TUNE_GEMM_RASTER = 1, FINO_TUNE_CONV_LOOP = 2, FINO_TUNE_GEMM_TILE_M = 3,
-       FINO_TUNE_ATTN_KERNEL = 4, FINO_TUNE_ATTN_FP8_KERNEL = 5, FINO_TUNE_ATTN_WALK_GRID = 6, FINO_TUNE_COUNT = 8 };
+       FINO_TUNE_ATTN_KERNEL = 4, FINO_TUNE_ATTN_FP8_KERNEL = 5, FINO_TUNE_ATTN_WALK_GRID = 6, FINO_TUNE_ATTN_FP8_SQ_PREPASS = 7,
+       FINO_TUNE_COUNT = 8 };
 int fino_tune_set(int key, int value);
 int fino_tune_get(int key);
 
@@ -209,6 +212,31 @@ int fino_attn_fwd_fp8_smooth(const void* q, const void* k, const void* v, void* 
 #define FINO_FP8_SMOOTH_V 2
 int64_t fino_attn_fp8_smoothed_kv_bytes(int batch, int heads, int64_t lk, int head_dim, int smooth);
 int fino_attn_fwd_fp8_smoothed(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq, int64_t lk,
+                               int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs,
+                               int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode, void* kv_workspace,
+                               int64_t kv_workspace_bytes, void* stream, int smooth);
+/* SMOOTH Q: the third operand.  For every block of 256 consecutive query rows (the row / 256 block of the range tables and tile
+ * masks; a ragged last block averages over the rows it has), per (batch element, head), qbar = the mean of q over the block's rows
+ * leaves q before it is quantised to e4m3, and
+ *     s_ij = (q_i - qbar) . k_j + qbar . k_j
+ * gets its second term back in fp32: one number per (q-block, key), the same for all rows of the block, computed from the
+ * UNQUANTISED keys (k_j - mu_K with FINO_FP8_SMOOTH_K: qbar . mu_K is constant over the keys of a block, so the result is the same
+ * and the bias stays small) by a pre-pass, stored as a hi | lo pair of the operand type (>= 16 significant bits) and added to the
+ * logits on the matrix pipe, beside the running maximum.  Exact in real arithmetic.  What it buys: a per-channel offset that
+ * neighbouring query rows share (norm_q weights, low-frequency RoPE channels) no longer takes the three mantissa bits of its
+ * 32-channel block.  Means and table are computed in a fixed partition and order, no atomics: the same inputs give the same bits.
+ * `smooth` takes any combination of the three bits; without FINO_FP8_SMOOTH_Q the call is fino_attn_fwd_fp8_smoothed (the same
+ * launches, sizes and bits).  With it: three more launches in front of the main one; head_dim 64 always runs the free-running
+ * kernel, whatever FINO_TUNE_ATTN_FP8_KERNEL says; head_dim 128 keeps the launch plan of the plain call (tail split and combine
+ * included).  The dense walk only: fino_attn_fwd_fp8_ranges / _tiles and the two calls above keep refusing the bit.  Workspace
+ * (fino_attn_fp8_smooth_q_kv_bytes; 0 for unsupported arguments or flags outside 0 .. 7; for smooth < 4 it IS
+ * fino_attn_fp8_smoothed_kv_bytes):
+ *     [ fino_attn_fp8_smoothed_kv_bytes(smooth & 3) | with FINO_FP8_SMOOTH_Q: pad to 16 B |
+ *       q-block means fp32 [batch][ceil(lq / 256)][heads * head_dim] | pad to 16 B |
+ *       bias words uint32 [batch][heads][ceil(lq / 256)][ceil(lk / 64) * 64] ] */
+#define FINO_FP8_SMOOTH_Q 4
+int64_t fino_attn_fp8_smooth_q_kv_bytes(int batch, int heads, int64_t lq, int64_t lk, int head_dim, int smooth);
+int fino_attn_fwd_fp8_smooth_q(const void* q, const void* k, const void* v, void* o, int batch, int heads, int64_t lq, int64_t lk,
                                int head_dim, int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs,
                                int64_t o_bs, int64_t o_rs, float scale, int dtype, int p_mode, void* kv_workspace,
                                int64_t kv_workspace_bytes, void* stream, int smooth);
