@@ -173,5 +173,7 @@ class StepGraph:
         """Drop the captured graph (call when the loop ends).  A graph that holds a captured all-to-all must die BEFORE the process
         group does: `destroy_process_group()` never returns while such a graph is alive (profiles/r06_rccl_capture_probe.txt)."""
         if self.graph is not None:
-            self.graph = None
-            torch.cuda.synchronize()
+            try:
+                torch.cuda.synchronize()         # first: nothing of a replay may be in flight when the graph goes
+            finally:
+                self.graph = None

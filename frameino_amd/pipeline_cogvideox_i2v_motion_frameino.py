@@ -23,17 +23,17 @@ Guiders (`pipe.set_guider(CFGZeroStarConfig() | AdaptiveProjectedGuidanceConfig(
 frameino_amd/guiders.py) replace the CFG combine of a guided call: `fino_guider_coefs` (two small launches, no host read; the
 guidance scale is the coefficient row's, `use_dynamic_cfg` included) and the `fino_guided_vpred_step` / `fino_guided_dpm_step`
 sibling of the step kernel; the loop is captured as before.
+
+The loop itself (the captured step, the checks before any launch, a batch video by video) is frameino_amd/pipeline_base.py's.
 """
-import contextlib
 import math
 from types import SimpleNamespace
 
 import torch
 
 from . import ops
-from .guiders import GuiderPipelineMixin
-from .lora import LoraPipelineMixin, lora_denoise_loop
-from .window_attention import window_attention_runs_eagerly
+from .lora import lora_denoise_loop
+from .pipeline_base import DenoisePipelineBase, VideoProcessor, nullcontext
 from .schedulers import CogVideoXDDIMScheduler  # noqa: F401  (re-export)
 
 
@@ -97,8 +97,9 @@ def _one_generator(generator, batch_size=1):
     return generator
 
 
-class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
-    _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
+class CogVideoXImageToVideoPipeline(DenoisePipelineBase):
+    _negative_batch_message = ("`negative_prompt`: {negative_prompt} has batch size {n}, but `prompt`: {prompt} has batch size "
+                               "{bsz}. Please make sure that passed `negative_prompt` matches the batch size of `prompt`.")
     extend_rope_by_first_frame = True             # :834-839 (the ID frame reuses the first frame's RoPE rows)
 
     def __init__(self, tokenizer=None, text_encoder=None, vae=None, transformer=None, scheduler=None):
@@ -107,19 +108,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
         self.vae_scale_factor_spatial = 8
         self.vae_scale_factor_temporal = 4
         self.vae_scaling_factor_image = getattr(getattr(vae, "config", None), "scaling_factor", 0.7)
-        self._interrupt = False
-        self._current_timestep = None
-        self.use_hip_graph = None            # None: replay the step from a captured hipGraph whenever the loop is
-        #                                      capturable (no per-step callback); False: eager; True: capture or raise
-
-    def enable_model_cpu_offload(self, *a, **k):
-        return self
-
-    def to(self, device):
-        for m in (self.transformer, self.vae, self.text_encoder):
-            if m is not None and hasattr(m, "to"):
-                m.to(device)
-        return self
+        self.video_processor = VideoProcessor(vae_scale_factor=self.vae_scale_factor_spatial)
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, torch_dtype=None, **kwargs):
@@ -139,14 +128,6 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
             raise TypeError(f"{cls.__name__}.from_pretrained: unexpected keyword arguments {sorted(rest)}")
         return cls(tokenizer=parts["tokenizer"], text_encoder=parts["text_encoder"], vae=parts["vae"],
                    transformer=parts["transformer"], scheduler=parts["scheduler"])
-
-    @property
-    def interrupt(self):
-        return self._interrupt
-
-    @property
-    def _execution_device(self):
-        return self.transformer.device
 
     # ---- text (once per clip; HF transformers T5, not on the kernel path) ----
     def _get_t5_prompt_embeds(self, prompt=None, num_videos_per_prompt=1, max_sequence_length=226, device=None,
@@ -173,28 +154,6 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
         emb = self.text_encoder(ids.to(device))[0].to(dtype=dtype, device=device)
         _, seq_len, _ = emb.shape
         return emb.repeat(1, num_videos_per_prompt, 1).view(bsz * num_videos_per_prompt, seq_len, -1)
-
-    def encode_prompt(self, prompt, negative_prompt=None, do_classifier_free_guidance=True, num_videos_per_prompt=1,
-                      prompt_embeds=None, negative_prompt_embeds=None, max_sequence_length=226, device=None, dtype=None):
-        """reference :269-348"""
-        device = device or self._execution_device
-        prompt = [prompt] if isinstance(prompt, str) else prompt
-        bsz = len(prompt) if prompt is not None else prompt_embeds.shape[0]
-        if prompt_embeds is None:
-            prompt_embeds = self._get_t5_prompt_embeds(prompt, num_videos_per_prompt, max_sequence_length, device, dtype)
-        if do_classifier_free_guidance and negative_prompt_embeds is None:
-            negative_prompt = negative_prompt or ""
-            negative_prompt = bsz * [negative_prompt] if isinstance(negative_prompt, str) else negative_prompt
-            if prompt is not None and type(prompt) is not type(negative_prompt):
-                raise TypeError(f"`negative_prompt` should be the same type to `prompt`, but got "
-                                f"{type(negative_prompt)} != {type(prompt)}.")
-            elif bsz != len(negative_prompt):
-                raise ValueError(f"`negative_prompt`: {negative_prompt} has batch size {len(negative_prompt)}, but "
-                                 f"`prompt`: {prompt} has batch size {bsz}. Please make sure that passed "
-                                 f"`negative_prompt` matches the batch size of `prompt`.")
-            negative_prompt_embeds = self._get_t5_prompt_embeds(negative_prompt, num_videos_per_prompt,
-                                                                max_sequence_length, device, dtype)
-        return prompt_embeds, negative_prompt_embeds
 
     def check_inputs(self, image, prompt, height, width, negative_prompt, callback_on_step_end_tensor_inputs,
                      latents=None, prompt_embeds=None, negative_prompt_embeds=None):
@@ -230,30 +189,6 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
                              f"directly, but got: `prompt_embeds` {prompt_embeds.shape} != `negative_prompt_embeds` "
                              f"{negative_prompt_embeds.shape}.")
 
-    @property
-    def current_timestep(self):
-        return self._current_timestep
-
-    def maybe_free_model_hooks(self):
-        # diffusers resets every component's stateful cache here, at the end of each call
-        reset = getattr(self.transformer, "_reset_stateful_cache", None)
-        if callable(reset):
-            reset()
-
-    def _step_cache_check(self):
-        """the limits of Pyramid Attention Broadcast (CogVideoXTransformer3DModel.enable_cache), checked before any work.  ->
-        whether a step cache is enabled: the loop then runs eagerly."""
-        if not getattr(self.transformer, "is_cache_enabled", False):
-            return False
-        if self.use_hip_graph is True:
-            raise self.transformer._step_cache_policy.capture_refusal()
-        return True
-
-    def _window_attention_check(self):
-        """the limits of window attention (CogVideoXTransformer3DModel.enable_window_attention), checked before any work.  ->
-        whether the loop must run eagerly: with a timestep range the host decides per step whether the windows apply."""
-        return window_attention_runs_eagerly(self.transformer, self.use_hip_graph)
-
     def _prepare_rotary_positional_embeddings(self, height, width, num_frames, device):
         """reference :540-584 (patch_size_t None) + the FrameIn first-frame extension :834-839."""
         c = self.transformer.config
@@ -274,31 +209,29 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
                 attention_kwargs=None, callback_on_step_end=None, generator=None):
         """reference :848-944.  latents / image_latents / traj_latents [1, F, C, h, w], id_latent [1, 1, C, h, w] or
         None; returns the final latents [1, F, C, h, w] in the transformer dtype."""
+        cached, win_eager, guider = self._loop_checks(latents.shape[0])
+        if latents.shape[0] != 1:
+            # (the loop state -- the static model-input buffer, the sampler history, the captured graph -- is one video's;
+            # conditions given with batch 1, like the reference's traj / ID latents :803-826, are shared)
+            return self._sample_by_sample(
+                lambda i, lat, rows, g: self.denoise(lat, *rows, guidance_scale, num_inference_steps, use_dynamic_cfg,
+                                                     image_rotary_emb, attention_kwargs, callback_on_step_end, g),
+                latents, (image_latents, traj_latents, id_latent, prompt_embeds, negative_prompt_embeds), generator)
+        st = self.make_state(latents, image_latents, traj_latents, id_latent, prompt_embeds, negative_prompt_embeds,
+                             guidance_scale, num_inference_steps, use_dynamic_cfg, image_rotary_emb, attention_kwargs,
+                             _one_generator(generator), guider)
+        self._run_steps(st, st.ts, cached, win_eager, callback=callback_on_step_end)
+        if cached:
+            self.transformer._reset_stateful_cache()        # (the buffers go; `cache_log` stays readable until the next forward)
+        return st.lat[None]
+
+    def make_state(self, latents, image_latents, traj_latents, id_latent, prompt_embeds, negative_prompt_embeds, guidance_scale,
+                   num_inference_steps, use_dynamic_cfg=False, image_rotary_emb=None, attention_kwargs=None, generator=None,
+                   guider=None):
+        """Sets the schedule; -> the static device buffers of one video's loop (what a captured step reads and writes) and the
+        schedule's rows that `_refresh_slots` copies into them."""
         tr = self.transformer
         dev, dt = latents.device, tr.dtype
-        win_eager = self._window_attention_check()
-        cached = self._step_cache_check()
-        guider = self._guider_check()
-        if latents.shape[0] != 1:
-            # A batch (a list of prompts, batched `prompt_embeds` / `latents`) runs video by video: the loop state -- the static
-            # model-input buffer, the sampler history, the captured graph -- is one video's.  The videos of a batched loop never
-            # meet (per-sample attention, per-sample guidance), so every row equals the single call on that row's noise, prompt
-            # and conditions; conditions given with batch 1 (the reference's traj / ID latents are batch 1, :803-826) are shared.
-            nb_ = latents.shape[0]
-
-            def row(t, i):
-                return t if t is None or t.shape[0] == 1 else t[i:i + 1]
-            outs = []
-            for i in range(nb_):
-                gi = generator[i] if isinstance(generator, (list, tuple)) else generator
-                outs.append(self.denoise(latents[i:i + 1], row(image_latents, i), row(traj_latents, i), row(id_latent, i),
-                                         row(prompt_embeds, i), row(negative_prompt_embeds, i), guidance_scale,
-                                         num_inference_steps, use_dynamic_cfg, image_rotary_emb, attention_kwargs,
-                                         callback_on_step_end, gi))
-            return torch.cat(outs, dim=0)
-        generator = _one_generator(generator)
-        if cached:
-            tr._reset_stateful_cache()        # every video starts from fresh cache state
         cfg_on = guidance_scale > 1.0 and negative_prompt_embeds is not None
         self.scheduler.set_timesteps(num_inference_steps, device=dev)
         ts = self.scheduler.timesteps
@@ -324,14 +257,13 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
         sc = self.scheduler.coefs.to(dev)
         coefs = torch.cat([sc[:, :7], gcol, sc[:, 7:8]], 1) if dpm else torch.cat([sc, gcol], 1)
 
-        # Static buffers of the loop (what a captured step reads and writes).  The model input [nb, F(+1), 3C, h, w] =
-        # [noisy | first frame + 0 | trajectory + 0] on the channel axis, identity frame appended on the frame axis
-        # (:866-880): only the noisy C channels of the generated frames change from step to step, so everything else is
-        # written once here and each step copies `lat` into its slot (the reference re-concatenates all of it).
+        # The model input [nb, F(+1), 3C, h, w] = [noisy | first frame + 0 | trajectory + 0] on the channel axis, identity frame
+        # appended on the frame axis (:866-880): only the noisy C channels of the generated frames change from step to step, so
+        # everything else is written once here and each step copies `lat` into its slot (the reference re-concatenates all of it).
         C = lat.shape[1]
         nf_in = nlf + (0 if id_latent is None else id_latent.shape[1])
         st = SimpleNamespace(lat=lat, nlf=nlf, C=C, cfg_on=cfg_on, dpm=dpm, prompt=prompt, rot=image_rotary_emb,
-                             attention_kwargs=attention_kwargs)
+                             attention_kwargs=attention_kwargs, ts=ts, coefs=coefs, generator=generator)
         st.id_frames = nf_in - nlf            # window attention: the identity-reference frame is a sink (FrameOut: none)
         st.x = torch.zeros((nb, nf_in, 3 * C) + tuple(lat.shape[2:]), dtype=dt, device=dev)
         if id_latent is not None:
@@ -346,30 +278,18 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
         g_slot = 7 if dpm else 4
         st.guider = self._guider_state(ops, guider, lat.numel(), st.coef[g_slot:g_slot + 1], len(ts), dev) \
             if guider is not None and cfg_on else None
-        from .graph_step import StepGraph
-        from .pipeline_wan_i2v_motion_frameino import tr_default_procs
-        stepper = StepGraph(lambda: self._step(st), self.use_hip_graph,
-                            callback_on_step_end is None and lat.is_cuda and not win_eager and not cached
-                            and (self.use_hip_graph is True or tr_default_procs(tr)), len(ts))
-        for i, t in enumerate(ts):
-            if self._interrupt:
-                continue
-            self._current_timestep = t
-            st.t.copy_(t.expand(nb))                          # device-to-device: no host sync
-            st.coef.copy_(coefs[i])
-            if dpm:
-                st.noise.copy_(self.scheduler.noise(i, lat.shape, generator, dev, dt))
-            self._guider_begin_step(st.guider, i)
-            stepper.step()
-            if callback_on_step_end is not None:
-                out = callback_on_step_end(self, i, t, {"latents": lat[None]})
-                if "latents" in out and out["latents"] is not None:
-                    lat.copy_(out["latents"][0])
-        self._current_timestep = None
-        stepper.close()
-        if cached:
-            tr._reset_stateful_cache()        # (the buffers go; `cache_log` stays readable until the next forward)
-        return lat[None]
+        return st
+
+    def _refresh_slots(self, st, i):
+        st.t.copy_(st.ts[i].expand(st.t.shape[0]))            # device-to-device: no host sync
+        st.coef.copy_(st.coefs[i])
+        if st.dpm:
+            st.noise.copy_(self.scheduler.noise(i, st.lat.shape, st.generator, st.lat.device, st.lat.dtype))
+
+    def _after_step(self, st, i, t, callback, tensor_inputs):
+        out = callback(self, i, t, {"latents": st.lat[None]})
+        if "latents" in out and out["latents"] is not None:
+            st.lat.copy_(out["latents"][0])
 
     def _step(self, st):
         """One denoise step on the static buffers `st` (no host sync, no data-dependent shapes: hipGraph-capturable)."""
@@ -380,8 +300,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
         if getattr(self.transformer, "is_window_attention_enabled", False):      # (this package's transformer only, as above)
             live["id_frames"] = st.id_frames
         # one cache context for the CFG batch, as diffusers' CogVideoX pipelines set it
-        ctx = self.transformer.cache_context("cond_uncond") if hasattr(self.transformer, "cache_context") \
-            else contextlib.nullcontext()
+        ctx = self.transformer.cache_context("cond_uncond") if hasattr(self.transformer, "cache_context") else nullcontext()
         with ctx:
             pred = self.transformer(hidden_states=st.x, encoder_hidden_states=st.prompt, timestep=st.t,
                                     image_rotary_emb=st.rot, attention_kwargs=st.attention_kwargs, return_dict=False, **live)[0]
@@ -497,15 +416,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
             dev)                                                                                # :757-766
         prompt_embeds = prompt_embeds.to(dev)
         self._interrupt = False
-        if isinstance(image, torch.Tensor):
-            img = image if image.ndim == 4 else image[None]
-            img = img if img.min() < 0 else 2.0 * img - 1.0
-        else:
-            import numpy as np
-            import PIL.Image
-            pil = image if isinstance(image, list) else [image]
-            arrs = [np.asarray(im.resize((width, height), resample=PIL.Image.LANCZOS)).astype("float32") / 255.0 for im in pil]
-            img = 2.0 * torch.from_numpy(np.stack(arrs).transpose(0, 3, 1, 2).copy()) - 1.0
+        img = self.video_processor.preprocess(image, height=height, width=width)
         img = img.to(dev, dtype=dt)
         if img.shape[0] not in (1, batch_size):
             raise ValueError(f"`image` holds {img.shape[0]} images for {batch_size} prompts: pass one image, or one per prompt")
@@ -547,17 +458,7 @@ class CogVideoXImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
             video = out
         else:
             frames = torch.cat([self.decode_latents(out[i:i + 1]) for i in range(out.shape[0])])   # [B, C, F, H, W]
-            v = (frames.float() / 2 + 0.5).clamp(0, 1).permute(0, 2, 1, 3, 4)                      # [B, F, C, H, W]
-            if output_type == "pt":
-                video = v
-            elif output_type == "np":
-                video = v.permute(0, 1, 3, 4, 2).cpu().numpy()
-            elif output_type == "pil":
-                import PIL.Image
-                arr = (v.permute(0, 1, 3, 4, 2).cpu().numpy() * 255).round().astype("uint8")
-                video = [[PIL.Image.fromarray(f) for f in vid] for vid in arr]
-            else:
-                raise ValueError(f"unsupported output_type {output_type}")
+            video = self.video_processor.postprocess_video(frames, output_type=output_type)
         if not return_dict:
             return (video,)
         return CogVideoXPipelineOutput(frames=video)

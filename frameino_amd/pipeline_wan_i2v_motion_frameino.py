@@ -11,11 +11,10 @@ The 50-step loop (:809-908) runs on HIP kernels only:
     WanTransformer3DModel x2  cond / uncond forward with the de-duplicated per-token timestep {0, t} (:832-843)
     fino_cfg_euler_step       CFG combine, ID-frame drop, flow-match Euler update (:882-891)
 
-The loop replays ONE captured step from a hipGraph (frameino_amd/graph_step.py: step 0 eager, step 1 captured, the rest
-replays; timestep and dt live in device buffers that a device-to-device copy refreshes between replays, no host sync
-inside the loop) whenever the call has no per-step callback: on one GPU always, on token shards for the call patterns this
-image's runtime captures (graph_step.py lists them).  `use_hip_graph = False` keeps the eager loop, `True` makes a loop
-that cannot be captured an error.
+The loop is frameino_amd/pipeline_base.py's: ONE captured step replayed from a hipGraph whenever the call has no per-step
+callback -- on one GPU always, on token shards for the call patterns this image's runtime captures (graph_step.py lists them).
+Here: the state (`make_state`), the step (`_step`: model input, the two predictions by one of four CFG execution forms or one
+after the other, the step kernel) and the slots a step reads (`t_rows`, `dt` or the UniPC coefficient row).
 
 With first-block caching enabled on the transformer (`pipe.transformer.enable_cache(FirstBlockCacheConfig(threshold))`,
 frameino_amd/step_cache.py) the loop runs eagerly: every step decides on the host, between block 0 and block 1, whether the
@@ -51,16 +50,12 @@ the ID frames off the last block.  One GPU (a parallel plan raises NotImplemente
 """
 import html
 import re
-import warnings
 from types import SimpleNamespace
 
-import numpy as np
 import torch
 
-from . import ops
-from .guiders import GuiderPipelineMixin
-from .lora import LoraPipelineMixin, lora_denoise_loop
-from .window_attention import window_attention_runs_eagerly
+from .lora import lora_denoise_loop
+from .pipeline_base import DenoisePipelineBase, VideoProcessor, nullcontext, tr_default_procs  # noqa: F401  (re-exports)
 
 
 def _basic_clean(text):
@@ -77,53 +72,13 @@ def prompt_clean(text):
     return re.sub(r"\s+", " ", _basic_clean(text)).strip()
 
 
-class VideoProcessor:
-    """The two diffusers VideoProcessor calls the pipeline makes (:767, :927); host-side pre/post-processing."""
-
-    def __init__(self, vae_scale_factor=16):
-        self.vae_scale_factor = vae_scale_factor
-
-    def preprocess(self, image, height, width):
-        import PIL.Image
-        if isinstance(image, PIL.Image.Image):
-            image = image.resize((width, height), resample=PIL.Image.LANCZOS)
-            arr = np.asarray(image).astype(np.float32) / 255.0
-            if arr.ndim == 2:
-                arr = arr[..., None]
-            return 2.0 * torch.from_numpy(arr.transpose(2, 0, 1).copy())[None] - 1.0
-        if isinstance(image, torch.Tensor):
-            t = image if image.ndim == 4 else image[None]
-            return t if t.min() < 0 else 2.0 * t - 1.0
-        raise ValueError(f"`image` has to be of type `torch.Tensor` or `PIL.Image.Image` but is {type(image)}")
-
-    def postprocess_video(self, video, output_type="np"):
-        v = (video.float() / 2 + 0.5).clamp(0, 1).permute(0, 2, 1, 3, 4)       # [B, F, C, H, W]
-        if output_type == "pt":
-            return v
-        if output_type == "np":
-            return v.permute(0, 1, 3, 4, 2).cpu().numpy()
-        raise ValueError(f"unsupported output_type {output_type}")
-
-
-import contextlib as _contextlib
-
-_null_ctx = _contextlib.nullcontext
-
-
 class WanPipelineOutput(SimpleNamespace):
     pass
 
 
-def tr_default_procs(transformer):
-    """the built-in processors run only this library's kernels: capturable.  A user-installed processor may do anything
-    (host syncs included), so its loop stays eager unless `use_hip_graph = True` asks for the capture"""
-    f = getattr(transformer, "_default_processors", None)
-    return bool(f()) if callable(f) else True
-
-
-class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
+class WanImageToVideoPipeline(DenoisePipelineBase):
     model_cpu_offload_seq = "text_encoder->image_encoder->transformer->transformer_2->vae"
-    _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
+    _negative_batch_message = "`negative_prompt` has batch size {n}, but `prompt` has batch size {bsz}."
 
     def __init__(self, tokenizer=None, text_encoder=None, vae=None, scheduler=None, image_processor=None,
                  image_encoder=None, transformer=None, transformer_2=None, boundary_ratio=None,
@@ -138,22 +93,11 @@ class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
         self.vae_scale_factor_temporal = vae.config.scale_factor_temporal if vae is not None else 4
         self.vae_scale_factor_spatial = vae.config.scale_factor_spatial if vae is not None else 8
         self.video_processor = VideoProcessor(vae_scale_factor=self.vae_scale_factor_spatial)
-        self.use_hip_graph = None        # None: graph replay whenever the loop is capturable (graph_step.StepGraph)
         self.batch_cfg = True            # run cond+uncond as one batch-2 forward when not CFG-parallel
         self.shard_vae_decode = True     # under a multi-rank plan: every rank decodes a slab of the frame (parallel.sharded_vae_decode)
         self.shard_vae_encode = True     # ... and encodes a slab of the trajectory video (parallel.sharded_vae_encode)
         self.cfg_streams = False         # ... or as two B=1 forwards on two concurrent streams (takes precedence)
         self._streams = None
-        self._interrupt = False
-        self._graph = None
-
-    # ---- diffusers-style conveniences ----
-    @property
-    def _execution_device(self):
-        return self.transformer.device
-
-    def enable_model_cpu_offload(self, *a, **k):      # reference app.py:163 -- unnecessary with 288 GB of HBM
-        return self
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, torch_dtype=None, **kwargs):
@@ -179,44 +123,6 @@ class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
                    scheduler=parts["scheduler"], transformer=parts["transformer"],
                    expand_timesteps=bool(index.get("expand_timesteps", True)))
 
-    def maybe_free_model_hooks(self):
-        # diffusers resets every component's stateful cache here, at the end of each call
-        reset = getattr(self.transformer, "_reset_stateful_cache", None)
-        if callable(reset):
-            reset()
-
-    def _step_cache_check(self, batch):
-        """the limits of the step caches (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache, region-adaptive sampling), checked before any work (and before
-        any collective: a parallel plan and the cache are configured by the same script on every rank, so every rank raises)"""
-        if not getattr(self.transformer, "is_cache_enabled", False):
-            return False
-        policy = self.transformer._step_cache_policy        # (label, batch rule and capture reason: stated once, by the cache)
-        if getattr(self, "parallel", None) is not None:
-            raise NotImplementedError(f"{policy.label} runs on one GPU; this pipeline has a parallel plan")
-        if batch > 1 and not policy.batched:
-            # (the others decide from the step counter and the timestep alone: the samples of a batch, run one at a time from
-            # fresh state, decide as diffusers' joint run does)
-            raise NotImplementedError(f"{policy.label} with a batch (a list of prompts, num_videos_per_prompt > 1): diffusers "
-                                      f"decides jointly over the batch, this pipeline runs the samples one at a time")
-        if self.use_hip_graph is True:
-            raise policy.capture_refusal()
-        return True
-
-    def _window_attention_check(self):
-        """the limits of window attention (WanTransformer3DModel.enable_window_attention), checked before any work.  -> whether
-        the loop must run eagerly: with a timestep range the host decides per step whether the windows apply."""
-        if getattr(self.transformer, "is_window_attention_enabled", False) and getattr(self, "parallel", None) is not None:
-            raise NotImplementedError("window attention runs on one GPU; this pipeline has a parallel plan")
-        if getattr(self.transformer, "is_sparse_attention_enabled", False) and getattr(self, "parallel", None) is not None:
-            raise NotImplementedError("sparse attention runs on one GPU; this pipeline has a parallel plan")
-        return window_attention_runs_eagerly(self.transformer, self.use_hip_graph)
-
-    def to(self, device):
-        for m in (self.transformer, self.vae, self.text_encoder):
-            if m is not None and hasattr(m, "to"):
-                m.to(device)
-        return self
-
     @property
     def guidance_scale(self):
         return self._guidance_scale
@@ -228,14 +134,6 @@ class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
     @property
     def num_timesteps(self):
         return self._num_timesteps
-
-    @property
-    def current_timestep(self):
-        return self._current_timestep
-
-    @property
-    def interrupt(self):
-        return self._interrupt
 
     # ---- text (once per clip; HF transformers model, not on the kernel path) ----
     def _get_t5_prompt_embeds(self, prompt, num_videos_per_prompt=1, max_sequence_length=512, device=None, dtype=None):
@@ -254,28 +152,6 @@ class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
         emb = torch.stack([torch.cat([u, u.new_zeros(max_sequence_length - u.size(0), u.size(1))]) for u in emb])
         _, seq_len, _ = emb.shape
         return emb.repeat(1, num_videos_per_prompt, 1).view(bsz * num_videos_per_prompt, seq_len, -1)
-
-    def encode_prompt(self, prompt, negative_prompt=None, do_classifier_free_guidance=True, num_videos_per_prompt=1,
-                      prompt_embeds=None, negative_prompt_embeds=None, max_sequence_length=226, device=None,
-                      dtype=None):
-        """reference :258-337"""
-        device = device or self._execution_device
-        prompt = [prompt] if isinstance(prompt, str) else prompt
-        bsz = len(prompt) if prompt is not None else prompt_embeds.shape[0]
-        if prompt_embeds is None:
-            prompt_embeds = self._get_t5_prompt_embeds(prompt, num_videos_per_prompt, max_sequence_length, device, dtype)
-        if do_classifier_free_guidance and negative_prompt_embeds is None:
-            negative_prompt = negative_prompt or ""
-            negative_prompt = bsz * [negative_prompt] if isinstance(negative_prompt, str) else negative_prompt
-            if prompt is not None and type(prompt) is not type(negative_prompt):
-                raise TypeError(f"`negative_prompt` should be the same type to `prompt`, but got "
-                                f"{type(negative_prompt)} != {type(prompt)}.")
-            if bsz != len(negative_prompt):
-                raise ValueError(f"`negative_prompt` has batch size {len(negative_prompt)}, but `prompt` has batch "
-                                 f"size {bsz}.")
-            negative_prompt_embeds = self._get_t5_prompt_embeds(negative_prompt, num_videos_per_prompt,
-                                                                max_sequence_length, device, dtype)
-        return prompt_embeds, negative_prompt_embeds
 
     def check_inputs(self, prompt, negative_prompt, image, height, width, prompt_embeds=None,
                      negative_prompt_embeds=None, image_embeds=None, callback_on_step_end_tensor_inputs=None,
@@ -314,11 +190,20 @@ class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
                              f"{self.vae_scale_factor_spatial * ps[1]} for this model (e.g. 704x1280, not 720x1280).")
 
     # ---- conditions (reference :400-553) ----
-    def _norm_latents(self, z, dtype):
+    def _latent_constants(self, device, dtype):
+        """(mean, 1 / std) of the VAE's latent channels, [1, z, 1, 1, 1]"""
         cfgv = self.vae.config
-        mean = torch.tensor(cfgv.latents_mean).view(1, cfgv.z_dim, 1, 1, 1).to(z.device, dtype)
-        inv_std = 1.0 / torch.tensor(cfgv.latents_std).view(1, cfgv.z_dim, 1, 1, 1).to(z.device, dtype)
+        mean = torch.tensor(cfgv.latents_mean).view(1, cfgv.z_dim, 1, 1, 1).to(device, dtype)
+        inv_std = 1.0 / torch.tensor(cfgv.latents_std).view(1, cfgv.z_dim, 1, 1, 1).to(device, dtype)
+        return mean, inv_std
+
+    def _norm_latents(self, z, dtype):
+        mean, inv_std = self._latent_constants(z.device, dtype)
         return (z.to(dtype) - mean) * inv_std
+
+    def _denorm_latents(self, lat):
+        mean, inv_std = self._latent_constants(lat.device, lat.dtype)
+        return lat / inv_std + mean                                                   # :917-925
 
     def prepare_latents(self, image, traj_tensor, ID_tensor, batch_size, num_channels_latents=16, height=480,
                         width=832, num_frames=81, dtype=None, device=None, generator=None, latents=None,
@@ -370,98 +255,122 @@ class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
 
     # ---- the hot loop ----
     def _step(self, st):
-        """One denoise step on static buffers `st` (graph-capturable: no host sync, no allocation-dependent shapes)."""
-        tr, o = self.transformer, self.transformer.ops
-        x = o.wan_model_input(st.lat, st.cond, st.idl, st.traj, tr.dtype, out=st.x)[None]
-        rows = (st.t_rows, st.sel)
-
+        """One denoise step on static buffers `st` (graph-capturable: no host sync, no allocation-dependent shapes): the model
+        input, the two predictions by the call's CFG execution form, the step kernel."""
+        tr = self.transformer
+        x = tr.ops.wan_model_input(st.lat, st.cond, st.idl, st.traj, tr.dtype, out=st.x)[None]
         live = {"live_rows": st.live_rows} if getattr(st, "live_rows", None) is not None else {}
         if getattr(tr, "is_window_attention_enabled", False) or getattr(tr, "is_sparse_attention_enabled", False):
             # (this package's transformer only, like live_rows)
             live["id_frames"] = st.id_frames
+        pc, pu = self._cfg_route(st)(st, x, live)
+        self._advance(st, pc, pu)
 
-        cached = bool(getattr(tr, "is_cache_enabled", False))
-
-        def fwd(name, emb):
-            with tr.cache_context(name):
-                return tr(hidden_states=x, timestep=None, encoder_hidden_states=emb, return_dict=False,
-                          attention_kwargs=st.attention_kwargs, timestep_rows=rows, **live)[0][0]
-
+    def _cfg_route(self, st):
+        """How this call runs its two CFG branches."""
         plan = getattr(self, "parallel", None)
-        if plan is not None and plan.interleave and st.cfg:
-            # both branches on this rank's token shard, advanced alternately block by block on two streams: the K|V
-            # all-gather of one branch overlaps the other branch's compute (frameino_amd/parallel.py)
-            if self._streams is None:
-                self._streams = (torch.cuda.Stream(), torch.cuda.Stream()) if x.is_cuda else (None, None)
-            main = torch.cuda.current_stream() if x.is_cuda else None
-            gens, outs = [], [None, None]
-            # the branches' kernels run on the two side streams.  Inside a hipGraph capture their collectives are issued on the
-            # step's own stream (TokenShard.issue_stream: the only call pattern a capture of this step survives on this image);
-            # an eager step issues them from the branch's stream, which keeps the two branches independent of each other
-            capturing = bool(x.is_cuda and torch.cuda.is_current_stream_capturing())
-            try:
-                for shard in plan.shards:
-                    shard.issue_stream = main if capturing else None
-                for name, emb, shard in (("cond", st.pe, plan.shards[0]), ("uncond", st.ne, plan.shards[1])):
-                    gens.append((name, tr.forward_steps(hidden_states=x, timestep=None, encoder_hidden_states=emb,
-                                                         return_dict=False, attention_kwargs=st.attention_kwargs,
-                                                         timestep_rows=rows, shard=shard)))
-                for s_ in self._streams:
-                    if s_ is not None:
-                        s_.wait_stream(main)
-                alive = [True, True]
-                while any(alive):
-                    for i, (name, g) in enumerate(gens):
-                        if not alive[i]:
-                            continue
-                        ctx_stream = torch.cuda.stream(self._streams[i]) if self._streams[i] is not None else _null_ctx()
-                        with ctx_stream, tr.cache_context(name):
-                            try:
-                                next(g)
-                            except StopIteration as done:
-                                outs[i], alive[i] = done.value[0][0], False
-                for s_ in self._streams:
-                    if s_ is not None:
-                        main.wait_stream(s_)
-            finally:
-                for shard in plan.shards:
-                    shard.issue_stream = None
-            pc, pu = outs
-        elif plan is not None and plan.cfg_ways == 2 and st.cfg:
-            # CFG branches on two rank groups; one exchange of noise_pred per step (frameino_amd/parallel.py)
-            mine = fwd("cond", st.pe) if plan.cfg_idx == 0 else fwd("uncond", st.ne)
-            pc, pu = plan.exchange_cfg(mine)
-        elif st.cfg and self.cfg_streams and getattr(tr, "parallel", None) is None:
-            # the two CFG branches as two concurrent kernel streams: each branch's launches are 2.3-10.7 "rounds" of
-            # workgroups over the 256 CUs, and the CUs that one branch's last partial round leaves idle take the
-            # other branch's workgroups (same for the synchronized epilogue bursts)
-            if self._streams is None:
-                self._streams = (torch.cuda.Stream(), torch.cuda.Stream())
-            main = torch.cuda.current_stream()
-            s1, s2 = self._streams
-            if getattr(tr, "_faster_on", False) and tr._faster_will_skip():
-                # FasterCache, a skipping step: the cond forward alone, then the rebuild that reads its prediction -- one stream
-                pc = fwd("cond", st.pe)
-                pu = fwd("uncond", st.ne)
-            else:
-                with tr._cfg_two_streams(main, (s1, s2)):     # fork and join (FasterCache: its delta after the join)
-                    with torch.cuda.stream(s1):
-                        pc = fwd("cond", st.pe)
-                    with torch.cuda.stream(s2):
-                        pu = fwd("uncond", st.ne)
-        elif st.cfg and self.batch_cfg and st.pe_ne is not None and getattr(tr, "parallel", None) is None:
-            # both CFG branches as ONE batch-2 forward (rows of the same GEMMs: identical per-row arithmetic, twice
-            # the tiles per launch, weights streamed once).  The reference makes two calls (:862-882); with the first-block
-            # cache each row block keeps the context of the call it stands for, and is decided as that call would be.
-            ctxs = {"_cache_contexts": ("cond", "uncond")} if cached else {}
-            with tr.cache_context("cfg"):
-                both = tr(hidden_states=x.expand(2, -1, -1, -1, -1), timestep=None, encoder_hidden_states=st.pe_ne,
-                          return_dict=False, attention_kwargs=st.attention_kwargs, timestep_rows=rows, **live, **ctxs)[0]
-            pc, pu = both[0], both[1]
-        else:
-            pc = fwd("cond", st.pe)
-            pu = fwd("uncond", st.ne) if st.cfg else None
-        gs = getattr(st, "guider", None)
+        if st.cfg and plan is not None and plan.interleave:
+            return self._cfg_interleaved
+        if st.cfg and plan is not None and plan.cfg_ways == 2:
+            return self._cfg_rank_groups
+        if st.cfg and getattr(self.transformer, "parallel", None) is None:
+            if self.cfg_streams:
+                return self._cfg_two_streams
+            if self.batch_cfg and st.pe_ne is not None:
+                return self._cfg_batched
+        return self._cfg_sequential
+
+    def _fwd(self, st, x, live, name, emb):
+        tr = self.transformer
+        with tr.cache_context(name):
+            return tr(hidden_states=x, timestep=None, encoder_hidden_states=emb, return_dict=False,
+                      attention_kwargs=st.attention_kwargs, timestep_rows=(st.t_rows, st.sel), **live)[0][0]
+
+    def _cfg_sequential(self, st, x, live):
+        """one forward after the other, as the reference makes them (:862-882); without CFG the conditional one alone"""
+        pc = self._fwd(st, x, live, "cond", st.pe)
+        return pc, (self._fwd(st, x, live, "uncond", st.ne) if st.cfg else None)
+
+    def _cfg_interleaved(self, st, x, live):
+        """both branches on this rank's token shard, advanced alternately block by block on two streams: the K|V all-gather of
+        one branch overlaps the other branch's compute (frameino_amd/parallel.py)"""
+        tr, plan = self.transformer, self.parallel
+        if self._streams is None:
+            self._streams = (torch.cuda.Stream(), torch.cuda.Stream()) if x.is_cuda else (None, None)
+        main = torch.cuda.current_stream() if x.is_cuda else None
+        gens, outs = [], [None, None]
+        # the branches' kernels run on the two side streams.  Inside a hipGraph capture their collectives are issued on the
+        # step's own stream (TokenShard.issue_stream: the only call pattern a capture of this step survives on this image);
+        # an eager step issues them from the branch's stream, which keeps the two branches independent of each other
+        capturing = bool(x.is_cuda and torch.cuda.is_current_stream_capturing())
+        try:
+            for shard in plan.shards:
+                shard.issue_stream = main if capturing else None
+            for name, emb, shard in (("cond", st.pe, plan.shards[0]), ("uncond", st.ne, plan.shards[1])):
+                gens.append((name, tr.forward_steps(hidden_states=x, timestep=None, encoder_hidden_states=emb,
+                                                     return_dict=False, attention_kwargs=st.attention_kwargs,
+                                                     timestep_rows=(st.t_rows, st.sel), shard=shard)))
+            for s_ in self._streams:
+                if s_ is not None:
+                    s_.wait_stream(main)
+            alive = [True, True]
+            while any(alive):
+                for i, (name, g) in enumerate(gens):
+                    if not alive[i]:
+                        continue
+                    ctx_stream = torch.cuda.stream(self._streams[i]) if self._streams[i] is not None else nullcontext()
+                    with ctx_stream, tr.cache_context(name):
+                        try:
+                            next(g)
+                        except StopIteration as done:
+                            outs[i], alive[i] = done.value[0][0], False
+            for s_ in self._streams:
+                if s_ is not None:
+                    main.wait_stream(s_)
+        finally:
+            for shard in plan.shards:
+                shard.issue_stream = None
+        return outs
+
+    def _cfg_rank_groups(self, st, x, live):
+        """CFG branches on two rank groups; one exchange of noise_pred per step (frameino_amd/parallel.py)"""
+        plan = self.parallel
+        mine = self._fwd(st, x, live, "cond", st.pe) if plan.cfg_idx == 0 else self._fwd(st, x, live, "uncond", st.ne)
+        return plan.exchange_cfg(mine)
+
+    def _cfg_two_streams(self, st, x, live):
+        """the two CFG branches as two concurrent kernel streams: each branch's launches are 2.3-10.7 "rounds" of workgroups over
+        the 256 CUs, and the CUs that one branch's last partial round leaves idle take the other branch's workgroups (same for
+        the synchronized epilogue bursts)"""
+        tr = self.transformer
+        if self._streams is None:
+            self._streams = (torch.cuda.Stream(), torch.cuda.Stream())
+        if getattr(tr, "_faster_on", False) and tr._faster_will_skip():
+            # FasterCache, a skipping step: the cond forward alone, then the rebuild that reads its prediction -- one stream
+            return self._cfg_sequential(st, x, live)
+        s1, s2 = self._streams
+        with tr._cfg_two_streams(torch.cuda.current_stream(), (s1, s2)):     # fork and join (FasterCache: its delta after the join)
+            with torch.cuda.stream(s1):
+                pc = self._fwd(st, x, live, "cond", st.pe)
+            with torch.cuda.stream(s2):
+                pu = self._fwd(st, x, live, "uncond", st.ne)
+        return pc, pu
+
+    def _cfg_batched(self, st, x, live):
+        """both CFG branches as ONE batch-2 forward (rows of the same GEMMs: identical per-row arithmetic, twice the tiles per
+        launch, weights streamed once).  The reference makes two calls (:862-882); with a step cache each row block keeps the
+        context of the call it stands for, and is decided as that call would be."""
+        tr = self.transformer
+        ctxs = {"_cache_contexts": ("cond", "uncond")} if getattr(tr, "is_cache_enabled", False) else {}
+        with tr.cache_context("cfg"):
+            both = tr(hidden_states=x.expand(2, -1, -1, -1, -1), timestep=None, encoder_hidden_states=st.pe_ne,
+                      return_dict=False, attention_kwargs=st.attention_kwargs, timestep_rows=(st.t_rows, st.sel), **live, **ctxs)[0]
+        return both[0], both[1]
+
+    def _advance(self, st, pc, pu):
+        """CFG combine, ID-frame drop and the sampler's update in one kernel: Euler or UniPC, plain or guided"""
+        o, gs = self.transformer.ops, getattr(st, "guider", None)
+        round_out = getattr(self.scheduler, "cast_output_to_model_dtype", True)
         if gs is not None:
             # a guider (frameino_amd/guiders.py): {A, B} of v = A c + B u from the moments of the generated frames, on the device,
             # then the step's guided sibling
@@ -469,14 +378,12 @@ class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
             if st.unipc is not None:
                 o.guided_unipc_step_(st.lat, *st.unipc, pc, pu, st.coef, gs.ab)
             else:
-                o.guided_euler_step_(st.lat, pc, pu, gs.ab, st.dt,
-                                     round_out=getattr(self.scheduler, "cast_output_to_model_dtype", True))
+                o.guided_euler_step_(st.lat, pc, pu, gs.ab, st.dt, round_out=round_out)
         elif st.unipc is not None:
             # the sampler the released Wan2.2 folder ships: corrector + predictor + CFG in one pass
             o.cfg_unipc_step_(st.lat, *st.unipc, pc, pu, st.coef)
         else:
-            o.cfg_euler_step_(st.lat, pc, pu, st.guidance, st.dt,
-                              round_out=getattr(self.scheduler, "cast_output_to_model_dtype", True))
+            o.cfg_euler_step_(st.lat, pc, pu, st.guidance, st.dt, round_out=round_out)
 
     def make_state(self, latents, condition, traj_latents, id_latent, first_frame_mask, prompt_embeds,
                    negative_prompt_embeds, guidance_scale, attention_kwargs=None):
@@ -546,22 +453,13 @@ class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
         the samples of the reference's batched loop never meet, every one sees the noise row `prepare_latents` drew for it.
         With a step cache (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache, region-adaptive sampling) every call -- every sample -- starts from fresh
         cache state."""
-        cached = self._step_cache_check(latents.shape[0])
-        win_eager = self._window_attention_check()
-        guider = self._guider_check()
-        if cached:
-            self.transformer._reset_stateful_cache()
+        cached, win_eager, guider = self._loop_checks(latents.shape[0])
         if latents.shape[0] > 1:
-            def row(t, i):
-                return t if t is None or t.shape[0] == 1 else t[i:i + 1]
-            outs = []
-            for i in range(latents.shape[0]):
-                cb = callback_on_step_end
-                outs.append(self.denoise(latents[i:i + 1], row(condition, i), row(traj_latents, i), row(id_latent, i),
-                                         row(first_frame_mask, i), row(prompt_embeds, i), row(negative_prompt_embeds, i),
-                                         guidance_scale, num_inference_steps, attention_kwargs, cb,
-                                         callback_on_step_end_tensor_inputs, timesteps_set=True if timesteps_set or i > 0 else False))
-            return torch.cat(outs, dim=0)
+            return self._sample_by_sample(
+                lambda i, lat, rows, g: self.denoise(lat, *rows, guidance_scale, num_inference_steps, attention_kwargs,
+                                                     callback_on_step_end, callback_on_step_end_tensor_inputs,
+                                                     timesteps_set=timesteps_set or i > 0),       # one schedule for the batch
+                latents, (condition, traj_latents, id_latent, first_frame_mask, prompt_embeds, negative_prompt_embeds))
         dev = latents.device
         if not timesteps_set:
             self.scheduler.set_timesteps(num_inference_steps, device=dev)
@@ -570,62 +468,37 @@ class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
                              negative_prompt_embeds, guidance_scale, attention_kwargs)
         if callback_on_step_end is not None:
             st.live_rows = None          # a callback sees the latents after every step, the first frame's Euler update included
+        # the schedule's rows, on the device: (timesteps, UniPC coefficient rows | Euler dts)
         if st.unipc is not None:
-            coefs = self.scheduler.coefs.to(dev).clone()
-            coefs[:, 0] = st.guidance
+            rows = self.scheduler.coefs.to(dev).clone()
+            rows[:, 0] = st.guidance
         else:
-            dts = self.scheduler.dts.to(dev)
-        ts_dev = timesteps.to(dev).float()
+            rows = self.scheduler.dts.to(dev)
+        st.schedule = (timesteps.to(dev).float(), rows)
         self._num_timesteps = len(timesteps)
         self._attach_guider(st, guider, len(timesteps))
-        if cached and getattr(self.transformer, "_mag_on", False):
-            planned = int(self.transformer._step_cache_config.num_inference_steps)
-            if planned != len(timesteps):       # once per call: the curve is indexed by the step counter
-                warnings.warn(f"MagCache: this call runs {len(timesteps)} steps, the config says num_inference_steps={planned}; "
-                              f"its curve (`mag_ratios`, resampled to {planned} entries) is misaligned with the loop and a "
-                              f"context starts over after {planned} forwards.  Build the config with the call's step count.",
-                              stacklevel=2)
-        if cached and getattr(self.transformer, "_ras_on", False):
-            planned = int(self.transformer._step_cache_config.num_inference_steps)
-            if planned != len(timesteps):       # once per call: the full steps at the end are counted from the config's figure
-                warnings.warn(f"region-adaptive sampling: this call runs {len(timesteps)} steps, the config says "
-                              f"num_inference_steps={planned}; its full steps at the end sit at forwards {planned} - "
-                              f"full_steps_at_end and later, and every forward from {planned} on is full.  Build the config "
-                              f"with the call's step count.", stacklevel=2)
-        # FasterCache reads `current_timestep` on the host up to three times per step: a host copy of the schedule, taken once,
-        # keeps those reads from waiting for the device
-        ts_host = timesteps.cpu() if cached and getattr(self.transformer, "_faster_on", False) else None
-
-        from .graph_step import StepGraph, capture_error_mode, groups_capturable
-        stepper = StepGraph(lambda: self._step(st), self.use_hip_graph,
-                            callback_on_step_end is None and st.lat.is_cuda and not cached and not win_eager
-                            and (self.use_hip_graph is True or tr_default_procs(self.transformer))
-                            and groups_capturable(getattr(self, "parallel", None), self.use_hip_graph is True),
-                            len(timesteps), capture_error_mode(getattr(self, "parallel", None)))
-        for i in range(len(timesteps)):
-            if self._interrupt:
-                continue
-            self._current_timestep = timesteps[i] if ts_host is None else ts_host[i]
-            st.t_rows[1:2].copy_(ts_dev[i:i + 1])          # device-to-device: no host sync
-            if st.unipc is not None:
-                st.coef.copy_(coefs[i])
-            else:
-                st.dt.copy_(dts[i:i + 1])
-            self._guider_begin_step(st.guider, i)
-            stepper.step()
-            if callback_on_step_end is not None:
-                latents = st.lat[None]
-                loc = {"latents": latents, "prompt_embeds": st.pe, "negative_prompt_embeds": st.ne}
-                out = callback_on_step_end(self, i, timesteps[i], {k: loc[k] for k in callback_on_step_end_tensor_inputs})
-                if "latents" in out and out["latents"] is not latents:
-                    st.lat.copy_(out["latents"][0])
-                pe, ne = out.pop("prompt_embeds", st.pe), out.pop("negative_prompt_embeds", st.ne)
-                if pe is not st.pe or ne is not st.ne:
-                    st.pe, st.ne = pe, ne
-                    st.pe_ne = torch.cat([pe, ne], dim=0).contiguous() if st.cfg and pe.shape == ne.shape else None
-        self._current_timestep = None
-        stepper.close()
+        self._run_steps(st, timesteps, cached, win_eager, getattr(self, "parallel", None), callback_on_step_end,
+                        callback_on_step_end_tensor_inputs)
         return (1 - first_frame_mask) * condition + first_frame_mask * st.lat[None]          # :913
+
+    def _refresh_slots(self, st, i):
+        ts_dev, rows = st.schedule
+        st.t_rows[1:2].copy_(ts_dev[i:i + 1])          # device-to-device: no host sync
+        if st.unipc is not None:
+            st.coef.copy_(rows[i])
+        else:
+            st.dt.copy_(rows[i:i + 1])
+
+    def _after_step(self, st, i, t, callback, tensor_inputs):
+        latents = st.lat[None]
+        loc = {"latents": latents, "prompt_embeds": st.pe, "negative_prompt_embeds": st.ne}
+        out = callback(self, i, t, {k: loc[k] for k in tensor_inputs})
+        if "latents" in out and out["latents"] is not latents:
+            st.lat.copy_(out["latents"][0])
+        pe, ne = out.pop("prompt_embeds", st.pe), out.pop("negative_prompt_embeds", st.ne)
+        if pe is not st.pe or ne is not st.ne:
+            st.pe, st.ne = pe, ne
+            st.pe_ne = torch.cat([pe, ne], dim=0).contiguous() if st.cfg and pe.shape == ne.shape else None
 
     @torch.no_grad()
     def __call__(self, image, prompt=None, negative_prompt=None, traj_tensor=None, ID_tensor=None, height=480,
@@ -668,11 +541,7 @@ class WanImageToVideoPipeline(LoraPipelineMixin, GuiderPipelineMixin):
                                guidance_scale, num_inference_steps, attention_kwargs, callback_on_step_end,
                                callback_on_step_end_tensor_inputs, timesteps_set=True)
         if output_type != "latent":
-            cfgv = self.vae.config
-            lat = latents.to(self.vae.dtype)
-            mean = torch.tensor(cfgv.latents_mean).view(1, cfgv.z_dim, 1, 1, 1).to(lat.device, lat.dtype)
-            inv_std = 1.0 / torch.tensor(cfgv.latents_std).view(1, cfgv.z_dim, 1, 1, 1).to(lat.device, lat.dtype)
-            lat = lat / inv_std + mean                                                # :917-925
+            lat = self._denorm_latents(latents.to(self.vae.dtype))
             plan = getattr(self, "parallel", None)
             if (plan is not None and plan.world > 1 and self.shard_vae_decode and hasattr(self.vae, "decode_slab")
                     and lat.shape[0] == 1):

@@ -463,10 +463,13 @@ class _CachePolicy:
     """What one cache config states once.  Never instantiated: the class is the policy object a model stores.
     `name`: the config's class name; `required`: the attributes a duck-typed config must carry; `label`: its name in messages
     (`attention_label`: of the part that takes over the attention branches, `instead`: what to use where that part is refused);
-    `why_eager`: why one captured step cannot contain it; `batched`: whether the pipeline may run it with a batch > 1."""
+    `why_eager`: why one captured step cannot contain it; `batched`: whether the pipeline may run it with a batch > 1;
+    `reads_timestep_on_host`: whether it reads the timestep callback several times per step (the loop then keeps a host copy of
+    the schedule, so that those reads do not wait for the device)."""
     name = label = attention_label = instead = why_eager = None
     required = ()
     batched = True
+    reads_timestep_on_host = False
 
     @classmethod
     def missing(cls):
@@ -486,6 +489,10 @@ class _CachePolicy:
     @staticmethod
     def prepare(config):
         """the enable-time warnings and defaults"""
+
+    @staticmethod
+    def loop_begins(config, num_steps):
+        """what the sampler loop has to hear once per `denoise`, given the call's step count (a warning, mostly)"""
 
     @staticmethod
     def hooks_attention(config):
@@ -632,6 +639,7 @@ class _FasterCachePolicy(_CachePolicy):
     instead = "`spatial_attention_block_skip_range=None` keeps its unconditional-branch part alone, which is"
     why_eager = ("whether a step runs the unconditional branch and its self-attention branches changes from step to step on the "
                  "host's schedule")
+    reads_timestep_on_host = True       # up to three times per step
 
     @staticmethod
     def validate(config, model):
@@ -717,6 +725,15 @@ class _MagCachePolicy(_CachePolicy):
                 raise ValueError(f"{where}: need at least one ratio, every one finite and above 0")
 
     @staticmethod
+    def loop_begins(config, num_steps):
+        planned = int(config.num_inference_steps)
+        if planned != num_steps:            # once per call: the curve is indexed by the step counter
+            warnings.warn(f"MagCache: this call runs {num_steps} steps, the config says num_inference_steps={planned}; "
+                          f"its curve (`mag_ratios`, resampled to {planned} entries) is misaligned with the loop and a "
+                          f"context starts over after {planned} forwards.  Build the config with the call's step count.",
+                          stacklevel=4)
+
+    @staticmethod
     def magcache(model, b, n, d, dtype, device, contexts):
         return model._magcache_begin(b, n, d, dtype, device, contexts)
 
@@ -747,6 +764,15 @@ class _RegionAdaptivePolicy(_CachePolicy):
         if m is not None and (not isinstance(m, torch.Tensor) or m.dtype != torch.bool or m.dim() != 1):
             raise ValueError(f"RegionAdaptiveSamplingConfig.always_active: need a bool [L] tensor or None, got "
                              f"{type(m).__name__}" + (f" {m.dtype} {tuple(m.shape)}" if isinstance(m, torch.Tensor) else ""))
+
+    @staticmethod
+    def loop_begins(config, num_steps):
+        planned = int(config.num_inference_steps)
+        if planned != num_steps:            # once per call: the full steps at the end are counted from the config's figure
+            warnings.warn(f"region-adaptive sampling: this call runs {num_steps} steps, the config says "
+                          f"num_inference_steps={planned}; its full steps at the end sit at forwards {planned} - "
+                          f"full_steps_at_end and later, and every forward from {planned} on is full.  Build the config "
+                          f"with the call's step count.", stacklevel=4)
 
     @staticmethod
     def hooks_attention(config):          # (the self-attention reads the planes: no window, no tile mask, no user processor)
