@@ -3,13 +3,9 @@
 // instead of numpy + OpenCV on the host: coloured squares on a white canvas per frame, a 45x45 isotropic Gaussian blur
 // (cv2.filter2D, BORDER_REFLECT_101), truncation to uint8 and the x/255*2-1 transform.  HBM-bound, trivially small.
 #include "fino_common.h"
+#include "fino_host.h"
 
 namespace {
-
-inline unsigned grid_1d(int64_t total, int block = 256) {
-    int64_t g = (total + block - 1) / block;
-    return (unsigned)(g > 262144 ? 262144 : g);
-}
 
 // canvas[f, c, y, x] (fp32, 0..255): white, then every point of frame f in order paints the square
 // [y-r, y+r) x [x-r, x+r) clipped to the canvas (:153-160); points outside the canvas are skipped (:149-150).
@@ -130,6 +126,7 @@ __global__ __launch_bounds__(256) void u8_hwc_to_chw_unit_kernel(const uint8_t* 
 
 }  // namespace
 
+// (every total below is positive by its entry point's checks: the grids take no floor)
 extern "C" int fino_resize_area_pad_u8(const void* src, void* dst, int src_h, int src_w, int region_h, int region_w,
                                        int out_h, int out_w, int off_y, int off_x, int fill, void* stream) {
     FINO_CHECK(src && dst, FINO_ERR_ARG, "fino_resize_area_pad_u8: null pointer");
@@ -137,18 +134,16 @@ extern "C" int fino_resize_area_pad_u8(const void* src, void* dst, int src_h, in
                    off_x >= 0 && off_y + region_h <= out_h && off_x + region_w <= out_w && fill >= 0 && fill <= 255,
                FINO_ERR_ARG, "fino_resize_area_pad_u8: the resized region must lie inside the canvas");
     const int64_t total = (int64_t)out_h * out_w;
-    resize_area_pad_u8_kernel<<<grid_1d(total), 256, 0, (hipStream_t)stream>>>(
+    resize_area_pad_u8_kernel<<<fino_grid_1d(total, kFinoGridCapWide, false), 256, 0, (hipStream_t)stream>>>(
         (const uint8_t*)src, (uint8_t*)dst, src_h, src_w, region_h, region_w, out_h, out_w, off_y, off_x, fill);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    return fino_launch_check("fino_resize_area_pad_u8");
 }
 
 extern "C" int fino_u8_hwc_to_chw_unit(const void* src, float* dst, int height, int width, void* stream) {
     FINO_CHECK(src && dst && height > 0 && width > 0, FINO_ERR_ARG, "fino_u8_hwc_to_chw_unit: bad arguments");
-    u8_hwc_to_chw_unit_kernel<<<grid_1d((int64_t)height * width), 256, 0, (hipStream_t)stream>>>(
+    u8_hwc_to_chw_unit_kernel<<<fino_grid_1d((int64_t)height * width, kFinoGridCapWide, false), 256, 0, (hipStream_t)stream>>>(
         (const uint8_t*)src, dst, height, width);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    return fino_launch_check("fino_u8_hwc_to_chw_unit");
 }
 
 extern "C" int fino_traj_paint(const int32_t* points, const int32_t* frame_offsets, float* canvas, int frames, int height,
@@ -156,22 +151,21 @@ extern "C" int fino_traj_paint(const int32_t* points, const int32_t* frame_offse
     FINO_CHECK(points && frame_offsets && canvas, FINO_ERR_ARG, "fino_traj_paint: null pointer");
     FINO_CHECK(frames > 0 && height > 0 && width > 0 && radius >= 0, FINO_ERR_ARG, "fino_traj_paint: bad shape");
     const int64_t total = (int64_t)frames * height * width;
-    traj_paint_kernel<<<grid_1d(total), 256, 0, (hipStream_t)stream>>>(points, frame_offsets, canvas, frames, height,
-                                                                        width, radius);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    traj_paint_kernel<<<fino_grid_1d(total, kFinoGridCapWide, false), 256, 0, (hipStream_t)stream>>>(
+        points, frame_offsets, canvas, frames, height, width, radius);
+    return fino_launch_check("fino_traj_paint");
 }
 
 extern "C" int fino_traj_blur_quantize(const float* canvas, float* scratch, float* out, const float* taps_dev, int taps,
                                        int planes, int height, int width, void* stream) {
-    FINO_CHECK(canvas && scratch && out && taps_dev, FINO_ERR_ARG, "fino_traj_blur_quantize: null pointer");
+    const char* who = "fino_traj_blur_quantize";
+    FINO_CHECK(canvas && scratch && out && taps_dev, FINO_ERR_ARG, "%s: null pointer", who);
     FINO_CHECK(taps > 0 && (taps & 1) && planes > 0 && height > 0 && width > 0, FINO_ERR_ARG,
                "fino_traj_blur_quantize: taps must be odd, shapes positive");
-    const int64_t total = (int64_t)planes * height * width;
+    const unsigned grid = fino_grid_1d((int64_t)planes * height * width, kFinoGridCapWide, false);
     hipStream_t st = (hipStream_t)stream;
-    blur_pass_kernel<0, false><<<grid_1d(total), 256, 0, st>>>(canvas, scratch, taps_dev, taps, planes, height, width);
-    FINO_LAUNCH_CHECK();
-    blur_pass_kernel<1, true><<<grid_1d(total), 256, 0, st>>>(scratch, out, taps_dev, taps, planes, height, width);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    blur_pass_kernel<0, false><<<grid, 256, 0, st>>>(canvas, scratch, taps_dev, taps, planes, height, width);
+    FINO_TRY(fino_launch_check(who));
+    blur_pass_kernel<1, true><<<grid, 256, 0, st>>>(scratch, out, taps_dev, taps, planes, height, width);
+    return fino_launch_check(who);
 }

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "fino_common.h"
+#include "fino_host.h"
 #include "fino_sampler_step.h"
 #include "fino_gemm_common.h"      // mx_quant8 / mx_scale_index: the MXFP8 activation layout fino_gemm_mxfp8 consumes
 
@@ -498,86 +499,43 @@ __global__ __launch_bounds__(256) void cfg_unipc_kernel(const uint16_t* __restri
                            CfgRounded<T>{g});
 }
 
-template <int NPmax, typename F>
-inline bool dispatch_np(int dim, F&& f) {
-    const int np = (dim + 511) / 512;
-    switch (np) {
-        case 1: f(std::integral_constant<int, 1>{}); return true;
-        case 2: f(std::integral_constant<int, 2>{}); return true;
-        case 3: f(std::integral_constant<int, 3>{}); return true;
-        case 4: f(std::integral_constant<int, 4>{}); return true;
-        case 5: f(std::integral_constant<int, 5>{}); return true;
-        case 6: f(std::integral_constant<int, 6>{}); return true;
-        case 7: f(std::integral_constant<int, 7>{}); return true;
-        case 8: f(std::integral_constant<int, 8>{}); return true;
-        default: return false;
-    }
-}
-
-inline int grid_1d(int64_t total, int block = 256) {
-    int64_t g = (total + block - 1) / block;
-    const int64_t cap = 256 * 8;  // ~8 blocks per CU, grid-stride the rest
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
+// the LayerNorm family: one wave per row (fino_launch_rows); `who` is the entry point, for a failed launch
 template <int MODE>
-int launch_ln_q(const void* x, void* q, void* qs, int64_t rows, int dim, int64_t ldx, const float* w, const float* b,
-                const float* shift, const float* scale, int64_t mod_stride, const int32_t* sel, float eps, int dtype,
-                hipStream_t st) {
-    const dim3 grid((unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock)), block(kWavesPerBlock * 64);
+int launch_ln_q(const char* who, const void* x, void* q, void* qs, int64_t rows, int dim, int64_t ldx, const float* w,
+                const float* b, const float* shift, const float* scale, int64_t mod_stride, const int32_t* sel, float eps,
+                int dtype, hipStream_t st) {
     const int64_t rows_pad = (rows + 255) / 256 * 256;
-    const bool ok = dispatch_np<kMaxPasses>(dim, [&](auto np) {
-        constexpr int NP = decltype(np)::value;
-        if (dtype == FINO_BF16)
-            ln_modulate_kernel<BF16, NP, MODE, true><<<grid, block, 0, st>>>((const uint16_t*)x, nullptr, rows, dim, ldx, 0, w,
-                                                                           b, shift, scale, mod_stride, sel, eps,
-                                                                           (uint8_t*)q, (uint8_t*)qs, rows_pad);
-        else
-            ln_modulate_kernel<F16, NP, MODE, true><<<grid, block, 0, st>>>((const uint16_t*)x, nullptr, rows, dim, ldx, 0, w,
-                                                                          b, shift, scale, mod_stride, sel, eps,
-                                                                          (uint8_t*)q, (uint8_t*)qs, rows_pad);
+    return fino_launch_rows<kMaxPasses>(who, "layernorm", rows, 1, kWavesPerBlock, dim, dtype,
+                                        [&](auto t, auto np, dim3 grid, dim3 block) {
+        ln_modulate_kernel<decltype(t), decltype(np)::value, MODE, true><<<grid, block, 0, st>>>(
+            (const uint16_t*)x, nullptr, rows, dim, ldx, 0, w, b, shift, scale, mod_stride, sel, eps, (uint8_t*)q, (uint8_t*)qs,
+            rows_pad);
     });
-    FINO_CHECK(ok, FINO_ERR_UNSUPPORTED, "layernorm: dim %d > %d unsupported", dim, kMaxPasses * 512);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
 }
 
 template <int MODE>
-int launch_ln(const void* x, void* y, int64_t rows, int dim, int64_t ldx, int64_t ldy, const float* w, const float* b,
-              const float* shift, const float* scale, int64_t mod_stride, const int32_t* sel, float eps, int dtype,
-              hipStream_t st) {
-    const dim3 grid((unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock)), block(kWavesPerBlock * 64);
-    const bool ok = dispatch_np<kMaxPasses>(dim, [&](auto np) {
-        constexpr int NP = decltype(np)::value;
-        if (dtype == FINO_BF16)
-            ln_modulate_kernel<BF16, NP, MODE><<<grid, block, 0, st>>>((const uint16_t*)x, (uint16_t*)y, rows, dim,
-                                                                     ldx, ldy, w, b, shift, scale, mod_stride, sel, eps);
-        else
-            ln_modulate_kernel<F16, NP, MODE><<<grid, block, 0, st>>>((const uint16_t*)x, (uint16_t*)y, rows, dim,
-                                                                    ldx, ldy, w, b, shift, scale, mod_stride, sel, eps);
+int launch_ln(const char* who, const void* x, void* y, int64_t rows, int dim, int64_t ldx, int64_t ldy, const float* w,
+              const float* b, const float* shift, const float* scale, int64_t mod_stride, const int32_t* sel, float eps,
+              int dtype, hipStream_t st) {
+    return fino_launch_rows<kMaxPasses>(who, "layernorm", rows, 1, kWavesPerBlock, dim, dtype,
+                                        [&](auto t, auto np, dim3 grid, dim3 block) {
+        ln_modulate_kernel<decltype(t), decltype(np)::value, MODE><<<grid, block, 0, st>>>(
+            (const uint16_t*)x, (uint16_t*)y, rows, dim, ldx, ldy, w, b, shift, scale, mod_stride, sel, eps);
     });
-    FINO_CHECK(ok, FINO_ERR_UNSUPPORTED, "layernorm: dim %d > %d unsupported", dim, kMaxPasses * 512);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
 }
 
 }  // namespace
 
-#define CHECK_ROWS_DIM(fn)                                                                                    \
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, fn ": dtype %d", dtype);                \
-    FINO_CHECK(rows >= 0 && dim > 0 && dim % 8 == 0, FINO_ERR_ARG, fn ": rows=%lld dim=%d (dim %% 8 != 0)",   \
-               (long long)rows, dim);                                                                         \
-    if (rows == 0) return FINO_OK;
-
 extern "C" int fino_adaln_modulate(const void* x, void* y, int64_t rows, int dim, int64_t ldx, int64_t ldy,
                                    const float* shift, const float* scale, int64_t mod_stride, const int32_t* sel,
                                    float eps, int dtype, void* stream) {
-    CHECK_ROWS_DIM("fino_adaln_modulate");
-    FINO_CHECK(x && y && shift && scale, FINO_ERR_ARG, "fino_adaln_modulate: null pointer");
-    FINO_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && mod_stride % 4 == 0 && fino_aligned16(x) && fino_aligned16(y) &&
-                   fino_aligned16(shift) && fino_aligned16(scale),
-               FINO_ERR_ARG, "fino_adaln_modulate: 16-byte alignment required");
-    return launch_ln<0>(x, y, rows, dim, ldx, ldy, nullptr, nullptr, shift, scale, mod_stride, sel, eps, dtype,
+    const char* who = "fino_adaln_modulate";
+    FINO_TRY(fino_check_rows_dim(who, rows, dim, dtype));
+    if (rows == 0) return FINO_OK;
+    FINO_CHECK(x && y && shift && scale, FINO_ERR_ARG, "%s: null pointer", who);
+    const bool mod_rows_ok = mod_stride % 4 == 0;          // the fp32 modulation rows are read 16 bytes at a time too
+    FINO_TRY(fino_check_aligned16(who, 8, {{x, ldx}, {y, ldy}, {shift, 0}, {scale, 0}}, mod_rows_ok));
+    return launch_ln<0>(who, x, y, rows, dim, ldx, ldy, nullptr, nullptr, shift, scale, mod_stride, sel, eps, dtype,
                         (hipStream_t)stream);
 }
 
@@ -585,7 +543,9 @@ extern "C" int fino_adaln_modulate(const void* x, void* y, int64_t rows, int dim
 extern "C" int fino_ln_mxfp8(int mode, const void* x, void* q, void* scales, int64_t rows, int dim, int64_t ldx,
                              const float* w, const float* b, const float* shift, const float* scale, int64_t mod_stride,
                              const int32_t* sel, float eps, int dtype, void* stream) {
-    CHECK_ROWS_DIM("fino_ln_mxfp8");
+    const char* who = "fino_ln_mxfp8";
+    FINO_TRY(fino_check_rows_dim(who, rows, dim, dtype));
+    if (rows == 0) return FINO_OK;
     FINO_CHECK(mode >= 0 && mode <= 2 && x && q && scales, FINO_ERR_ARG, "fino_ln_mxfp8: mode %d / null pointer", mode);
     FINO_CHECK(mode == 1 || (shift && scale), FINO_ERR_ARG, "fino_ln_mxfp8: modulation rows missing");
     FINO_CHECK(dim % 128 == 0, FINO_ERR_ARG, "fino_ln_mxfp8: dim=%d must be a multiple of 128", dim);
@@ -593,118 +553,107 @@ extern "C" int fino_ln_mxfp8(int mode, const void* x, void* q, void* scales, int
                    fino_aligned16(w) && fino_aligned16(b) && ((uintptr_t)q & 7) == 0,
                FINO_ERR_ARG, "fino_ln_mxfp8: alignment");
     hipStream_t st = (hipStream_t)stream;
-    if (mode == 0) return launch_ln_q<0>(x, q, scales, rows, dim, ldx, nullptr, nullptr, shift, scale, mod_stride, sel, eps, dtype, st);
-    if (mode == 1) return launch_ln_q<1>(x, q, scales, rows, dim, ldx, w, b, nullptr, nullptr, 0, nullptr, eps, dtype, st);
-    return launch_ln_q<2>(x, q, scales, rows, dim, ldx, w, b, shift, scale, mod_stride, sel, eps, dtype, st);
+    if (mode == 0)
+        return launch_ln_q<0>(who, x, q, scales, rows, dim, ldx, nullptr, nullptr, shift, scale, mod_stride, sel, eps, dtype, st);
+    if (mode == 1) return launch_ln_q<1>(who, x, q, scales, rows, dim, ldx, w, b, nullptr, nullptr, 0, nullptr, eps, dtype, st);
+    return launch_ln_q<2>(who, x, q, scales, rows, dim, ldx, w, b, shift, scale, mod_stride, sel, eps, dtype, st);
 }
 
 extern "C" int fino_layernorm(const void* x, void* y, int64_t rows, int dim, int64_t ldx, int64_t ldy,
                               const float* w, const float* b, float eps, int dtype, void* stream) {
-    CHECK_ROWS_DIM("fino_layernorm");
-    FINO_CHECK(x && y, FINO_ERR_ARG, "fino_layernorm: null pointer");
-    FINO_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && fino_aligned16(x) && fino_aligned16(y) && fino_aligned16(w) &&
-                   fino_aligned16(b),
-               FINO_ERR_ARG, "fino_layernorm: 16-byte alignment required");
-    return launch_ln<1>(x, y, rows, dim, ldx, ldy, w, b, nullptr, nullptr, 0, nullptr, eps, dtype, (hipStream_t)stream);
+    const char* who = "fino_layernorm";
+    FINO_TRY(fino_check_rows_dim(who, rows, dim, dtype));
+    if (rows == 0) return FINO_OK;
+    FINO_CHECK(x && y, FINO_ERR_ARG, "%s: null pointer", who);
+    FINO_TRY(fino_check_aligned16(who, 8, {{x, ldx}, {y, ldy}, {w, 0}, {b, 0}}));
+    return launch_ln<1>(who, x, y, rows, dim, ldx, ldy, w, b, nullptr, nullptr, 0, nullptr, eps, dtype, (hipStream_t)stream);
 }
 
 extern "C" int fino_layernorm_zero(const void* x, void* y, int64_t rows, int dim, int64_t ldx, int64_t ldy,
                                    const float* w, const float* b, const float* shift, const float* scale,
                                    int64_t mod_stride, const int32_t* sel, float eps, int dtype, void* stream) {
-    CHECK_ROWS_DIM("fino_layernorm_zero");
-    FINO_CHECK(x && y && shift && scale, FINO_ERR_ARG, "fino_layernorm_zero: null pointer");
-    FINO_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && mod_stride % 4 == 0 && fino_aligned16(x) && fino_aligned16(y) &&
-                   fino_aligned16(shift) && fino_aligned16(scale) && fino_aligned16(w) && fino_aligned16(b),
-               FINO_ERR_ARG, "fino_layernorm_zero: 16-byte alignment required");
-    return launch_ln<2>(x, y, rows, dim, ldx, ldy, w, b, shift, scale, mod_stride, sel, eps, dtype, (hipStream_t)stream);
+    const char* who = "fino_layernorm_zero";
+    FINO_TRY(fino_check_rows_dim(who, rows, dim, dtype));
+    if (rows == 0) return FINO_OK;
+    FINO_CHECK(x && y && shift && scale, FINO_ERR_ARG, "%s: null pointer", who);
+    const bool mod_rows_ok = mod_stride % 4 == 0;
+    FINO_TRY(fino_check_aligned16(who, 8, {{x, ldx}, {y, ldy}, {shift, 0}, {scale, 0}, {w, 0}, {b, 0}}, mod_rows_ok));
+    return launch_ln<2>(who, x, y, rows, dim, ldx, ldy, w, b, shift, scale, mod_stride, sel, eps, dtype, (hipStream_t)stream);
 }
 
-static int gated_residual_impl(const void* x, const void* y, void* out, int64_t rows, int dim, int64_t ldx, int64_t ldy,
-                               int64_t ldo, const float* gate, int64_t mod_stride, const int32_t* sel, int staged,
-                               int dtype, void* stream);
+// both gated residuals; every refusal says fino_gated_residual, a failed launch says `who`
+static int gated_residual_impl(const char* who, const void* x, const void* y, void* out, int64_t rows, int dim, int64_t ldx,
+                               int64_t ldy, int64_t ldo, const float* gate, int64_t mod_stride, const int32_t* sel, int staged,
+                               int dtype, void* stream) {
+    const char* fam = "fino_gated_residual";
+    FINO_TRY(fino_check_rows_dim(fam, rows, dim, dtype));
+    if (rows == 0) return FINO_OK;
+    FINO_CHECK(x && y && out, FINO_ERR_ARG, "%s: null pointer", fam);
+    const bool gate_rows_ok = mod_stride % 4 == 0;
+    FINO_TRY(fino_check_aligned16(fam, 8, {{x, ldx}, {y, ldy}, {out, ldo}, {gate, 0}}, gate_rows_ok));
+    const unsigned grid = fino_grid_1d(rows * (dim / 8), kFinoGridCap8, true);
+    hipStream_t st = (hipStream_t)stream;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        gated_residual_kernel<decltype(t)><<<grid, 256, 0, st>>>((const uint16_t*)x, (const uint16_t*)y, (uint16_t*)out, rows,
+                                                                 dim, ldx, ldy, ldo, gate, mod_stride, sel, staged);
+    });
+    return fino_launch_check(who);
+}
 
 extern "C" int fino_gated_residual(const void* x, const void* y, void* out, int64_t rows, int dim, int64_t ldx,
                                    int64_t ldy, int64_t ldo, const float* gate, int64_t mod_stride,
                                    const int32_t* sel, int dtype, void* stream) {
-    return gated_residual_impl(x, y, out, rows, dim, ldx, ldy, ldo, gate, mod_stride, sel, 0, dtype, stream);
+    return gated_residual_impl("fino_gated_residual", x, y, out, rows, dim, ldx, ldy, ldo, gate, mod_stride, sel, 0, dtype,
+                               stream);
 }
 
 extern "C" int fino_gated_residual_staged(const void* x, const void* y, void* out, int64_t rows, int dim, int64_t ldx,
                                           int64_t ldy, int64_t ldo, const float* gate, int64_t mod_stride,
                                           const int32_t* sel, int dtype, void* stream) {
-    return gated_residual_impl(x, y, out, rows, dim, ldx, ldy, ldo, gate, mod_stride, sel, 1, dtype, stream);
+    return gated_residual_impl("fino_gated_residual_staged", x, y, out, rows, dim, ldx, ldy, ldo, gate, mod_stride, sel, 1,
+                               dtype, stream);
 }
 
-static int gated_residual_impl(const void* x, const void* y, void* out, int64_t rows, int dim, int64_t ldx, int64_t ldy,
-                               int64_t ldo, const float* gate, int64_t mod_stride, const int32_t* sel, int staged,
-                               int dtype, void* stream) {
-    CHECK_ROWS_DIM("fino_gated_residual");
-    FINO_CHECK(x && y && out, FINO_ERR_ARG, "fino_gated_residual: null pointer");
-    FINO_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && ldo % 8 == 0 && mod_stride % 4 == 0 && fino_aligned16(x) &&
-                   fino_aligned16(y) && fino_aligned16(out) && fino_aligned16(gate),
-               FINO_ERR_ARG, "fino_gated_residual: 16-byte alignment required");
-    const int grid = grid_1d(rows * (dim / 8));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        gated_residual_kernel<BF16><<<grid, 256, 0, st>>>((const uint16_t*)x, (const uint16_t*)y, (uint16_t*)out,
-                                                          rows, dim, ldx, ldy, ldo, gate, mod_stride, sel, staged);
-    else
-        gated_residual_kernel<F16><<<grid, 256, 0, st>>>((const uint16_t*)x, (const uint16_t*)y, (uint16_t*)out,
-                                                         rows, dim, ldx, ldy, ldo, gate, mod_stride, sel, staged);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
-}
-
-static int rmsnorm_rope_impl(void* x, int64_t rows, int dim, int64_t ldx, int parts, const RmsRopeParts& pp,
+// the RMSNorm + RoPE family; every refusal says fino_rmsnorm_rope (one: fino_rmsnorm_rope_scaled), a failed launch `who`
+static int rmsnorm_rope_impl(const char* who, void* x, int64_t rows, int dim, int64_t ldx, int parts, const RmsRopeParts& pp,
                              const float* cos_t, const float* sin_t, int head_dim, void* out, const int64_t* head_off,
                              const int64_t* head_ld, int dtype, void* stream) {
-    CHECK_ROWS_DIM("fino_rmsnorm_rope");
+    const char* fam = "fino_rmsnorm_rope";
+    FINO_TRY(fino_check_rows_dim(fam, rows, dim, dtype));
+    if (rows == 0) return FINO_OK;
     FINO_CHECK(x, FINO_ERR_ARG, "fino_rmsnorm_rope: null pointer");
     FINO_CHECK(parts >= 1 && parts <= 3, FINO_ERR_ARG, "fino_rmsnorm_rope: parts %d", parts);
     bool any_rope = false;
     for (int i = 0; i < parts; ++i) {
         FINO_CHECK(pp.out_scale[i] > 0.f, FINO_ERR_ARG, "fino_rmsnorm_rope_scaled: out_scale must be > 0");
-        FINO_CHECK(fino_aligned16(pp.w[i]), FINO_ERR_ARG, "fino_rmsnorm_rope: 16-byte alignment required");
+        FINO_TRY(fino_check_aligned16(fam, 8, {{pp.w[i], 0}}));
         any_rope = any_rope || pp.rope[i];
     }
     FINO_CHECK((cos_t == nullptr) == (sin_t == nullptr), FINO_ERR_ARG, "fino_rmsnorm_rope: cos/sin must both be set");
     FINO_CHECK(!any_rope || cos_t, FINO_ERR_ARG, "fino_rmsnorm_rope: a segment asks for RoPE without tables");
     FINO_CHECK((!cos_t && !out) || (head_dim > 0 && head_dim % 8 == 0 && dim % head_dim == 0), FINO_ERR_ARG,
                "fino_rmsnorm_rope: head_dim=%d must divide dim=%d and be a multiple of 8", head_dim, dim);
-    FINO_CHECK(ldx % 8 == 0 && fino_aligned16(x) && fino_aligned16(cos_t) && fino_aligned16(sin_t) && fino_aligned16(out),
-               FINO_ERR_ARG, "fino_rmsnorm_rope: 16-byte alignment required");
+    FINO_TRY(fino_check_aligned16(fam, 8, {{x, ldx}, {cos_t, 0}, {sin_t, 0}, {out, 0}}));
     FINO_CHECK(parts == 1 || dim % 8 == 0, FINO_ERR_ARG, "fino_rmsnorm_rope: segments need dim % 8 == 0");
-    const dim3 grid((unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock), (unsigned)parts), block(kWavesPerBlock * 64);
     hipStream_t st = (hipStream_t)stream;
-    const bool ok = dispatch_np<kMaxPasses>(dim, [&](auto np) {
-        constexpr int NP = decltype(np)::value;
-        if (dtype == FINO_BF16)
-            rmsnorm_rope_kernel<BF16, NP><<<grid, block, 0, st>>>((uint16_t*)x, rows, dim, ldx, pp, cos_t, sin_t, head_dim,
-                                                                  (uint16_t*)out, head_off, head_ld);
-        else
-            rmsnorm_rope_kernel<F16, NP><<<grid, block, 0, st>>>((uint16_t*)x, rows, dim, ldx, pp, cos_t, sin_t, head_dim,
-                                                                 (uint16_t*)out, head_off, head_ld);
+    return fino_launch_rows<kMaxPasses>(who, fam, rows, (unsigned)parts, kWavesPerBlock, dim, dtype,
+                                        [&](auto t, auto np, dim3 grid, dim3 block) {
+        rmsnorm_rope_kernel<decltype(t), decltype(np)::value><<<grid, block, 0, st>>>(
+            (uint16_t*)x, rows, dim, ldx, pp, cos_t, sin_t, head_dim, (uint16_t*)out, head_off, head_ld);
     });
-    FINO_CHECK(ok, FINO_ERR_UNSUPPORTED, "fino_rmsnorm_rope: dim %d > %d unsupported", dim, kMaxPasses * 512);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
 }
 
 extern "C" int fino_row_rrms(const void* x, int64_t rows, int dim, int64_t ldx, float eps, float* rrms, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_row_rrms: dtype %d", dtype);
+    const char* who = "fino_row_rrms";
+    FINO_TRY(fino_check_dtype(who, dtype));
     FINO_CHECK(x && rrms && rows >= 0 && dim > 0 && dim % 8 == 0 && ldx % 8 == 0 && fino_aligned16(x), FINO_ERR_ARG,
                "fino_row_rrms: bad arguments");
     if (rows == 0) return FINO_OK;
-    const dim3 grid((unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock)), block(kWavesPerBlock * 64);
     hipStream_t st = (hipStream_t)stream;
-    const bool ok = dispatch_np<kMaxPasses>(dim, [&](auto np) {
-        constexpr int NP = decltype(np)::value;
-        if (dtype == FINO_BF16) row_rrms_kernel<BF16, NP><<<grid, block, 0, st>>>((const uint16_t*)x, rows, dim, ldx, eps, rrms);
-        else row_rrms_kernel<F16, NP><<<grid, block, 0, st>>>((const uint16_t*)x, rows, dim, ldx, eps, rrms);
+    return fino_launch_rows<kMaxPasses>(who, who, rows, 1, kWavesPerBlock, dim, dtype,
+                                        [&](auto t, auto np, dim3 grid, dim3 block) {
+        row_rrms_kernel<decltype(t), decltype(np)::value><<<grid, block, 0, st>>>((const uint16_t*)x, rows, dim, ldx, eps, rrms);
     });
-    FINO_CHECK(ok, FINO_ERR_UNSUPPORTED, "fino_row_rrms: dim %d > %d unsupported", dim, kMaxPasses * 512);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
 }
 
 static RmsRopeParts one_part(const void* weight, float eps, float out_scale, bool rope) {
@@ -716,16 +665,17 @@ static RmsRopeParts one_part(const void* weight, float eps, float out_scale, boo
 extern "C" int fino_rmsnorm_rope_scaled(void* x, int64_t rows, int dim, int64_t ldx, const void* weight, float eps,
                                         const float* cos_t, const float* sin_t, int head_dim, float out_scale, int dtype,
                                         void* stream) {
-    return rmsnorm_rope_impl(x, rows, dim, ldx, 1, one_part(weight, eps, out_scale, cos_t != nullptr), cos_t, sin_t,
-                             head_dim, nullptr, nullptr, nullptr, dtype, stream);
+    return rmsnorm_rope_impl("fino_rmsnorm_rope_scaled", x, rows, dim, ldx, 1, one_part(weight, eps, out_scale, cos_t != nullptr),
+                             cos_t, sin_t, head_dim, nullptr, nullptr, nullptr, dtype, stream);
 }
 
 extern "C" int fino_rmsnorm_rope_scatter(const void* x, int64_t rows, int dim, int64_t ldx, const void* weight, float eps,
                                          const float* cos_t, const float* sin_t, int head_dim, float out_scale, void* out,
                                          const int64_t* head_off, const int64_t* head_ld, int dtype, void* stream) {
     FINO_CHECK(out && head_off && head_ld, FINO_ERR_ARG, "fino_rmsnorm_rope_scatter: null destination / table");
-    return rmsnorm_rope_impl(const_cast<void*>(x), rows, dim, ldx, 1, one_part(weight, eps, out_scale, cos_t != nullptr),
-                             cos_t, sin_t, head_dim, out, head_off, head_ld, dtype, stream);
+    return rmsnorm_rope_impl("fino_rmsnorm_rope_scatter", const_cast<void*>(x), rows, dim, ldx, 1,
+                             one_part(weight, eps, out_scale, cos_t != nullptr), cos_t, sin_t, head_dim, out, head_off, head_ld,
+                             dtype, stream);
 }
 
 extern "C" int fino_qkv_rmsnorm_rope(void* qkv, int64_t rows, int dim, int64_t ldx, const void* q_weight, float q_eps,
@@ -739,8 +689,8 @@ extern "C" int fino_qkv_rmsnorm_rope(void* qkv, int64_t rows, int dim, int64_t l
     pp.w[1] = (const uint16_t*)k_weight; pp.eps[1] = k_eps; pp.out_scale[1] = 1.0f; pp.rope[1] = cos_t ? 1 : 0;
     pp.w[2] = nullptr; pp.eps[2] = 0.f; pp.out_scale[2] = 1.0f; pp.rope[2] = 0;
     // in place: q and k only (v is left alone); scattered: v travels too, as a copy
-    return rmsnorm_rope_impl(qkv, rows, dim, ldx, out ? 3 : 2, pp, cos_t, sin_t, head_dim, out, head_off, head_ld, dtype,
-                             stream);
+    return rmsnorm_rope_impl("fino_qkv_rmsnorm_rope", qkv, rows, dim, ldx, out ? 3 : 2, pp, cos_t, sin_t, head_dim, out, head_off,
+                             head_ld, dtype, stream);
 }
 
 extern "C" int fino_qkv_rmsnorm_rope_rows(void* qkv, int64_t rows, int dim, int64_t ldx, const void* q_weight, float q_eps,
@@ -748,7 +698,8 @@ extern "C" int fino_qkv_rmsnorm_rope_rows(void* qkv, int64_t rows, int dim, int6
                                           int head_dim, float q_out_scale, const int32_t* idx, int64_t n, void* kcache,
                                           void* vcache, int64_t ld_cache, int dtype, void* stream) {
     const char* who = "fino_qkv_rmsnorm_rope_rows";
-    CHECK_ROWS_DIM("fino_qkv_rmsnorm_rope_rows");
+    FINO_TRY(fino_check_rows_dim(who, rows, dim, dtype));
+    if (rows == 0) return FINO_OK;
     FINO_CHECK(qkv && q_weight && k_weight && cos_t && sin_t && kcache && vcache, FINO_ERR_ARG, "%s: null pointer", who);
     FINO_CHECK(q_out_scale > 0.f, FINO_ERR_ARG, "%s: q_out_scale must be > 0", who);
     FINO_CHECK(head_dim > 0 && head_dim % 8 == 0 && dim % head_dim == 0 && dim % 8 == 0, FINO_ERR_ARG,
@@ -756,62 +707,49 @@ extern "C" int fino_qkv_rmsnorm_rope_rows(void* qkv, int64_t rows, int dim, int6
     FINO_CHECK(n >= 1 && n < (1LL << 31) && (idx || rows <= n), FINO_ERR_ARG, "%s: n=%lld planes rows for %lld rows", who,
                (long long)n, (long long)rows);
     FINO_CHECK(ldx >= 3 * (int64_t)dim && ld_cache >= dim, FINO_ERR_ARG, "%s: a row stride is below the row", who);
-    FINO_CHECK(ldx % 8 == 0 && ld_cache % 8 == 0 && fino_aligned16(qkv) && fino_aligned16(cos_t) && fino_aligned16(sin_t) &&
-                   fino_aligned16(kcache) && fino_aligned16(vcache) && fino_aligned16(q_weight) && fino_aligned16(k_weight),
-               FINO_ERR_ARG, "%s: 16-byte alignment required", who);
+    FINO_TRY(fino_check_aligned16(who, 8, {{qkv, ldx}, {kcache, ld_cache}, {vcache, ld_cache}, {cos_t, 0}, {sin_t, 0},
+                                           {q_weight, 0}, {k_weight, 0}}));
     RmsRopeParts pp = {};
     pp.w[0] = (const uint16_t*)q_weight; pp.eps[0] = q_eps; pp.out_scale[0] = q_out_scale; pp.rope[0] = 1;
     pp.w[1] = (const uint16_t*)k_weight; pp.eps[1] = k_eps; pp.out_scale[1] = 1.0f; pp.rope[1] = 1;
-    const dim3 grid((unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock), 3u), block(kWavesPerBlock * 64);
     hipStream_t st = (hipStream_t)stream;
-    const bool ok = dispatch_np<kMaxPasses>(dim, [&](auto np) {
-        constexpr int NP = decltype(np)::value;
-        if (dtype == FINO_BF16)
-            qkv_rmsnorm_rope_rows_kernel<BF16, NP><<<grid, block, 0, st>>>((uint16_t*)qkv, rows, dim, ldx, pp, cos_t, sin_t,
-                                                                           head_dim, idx, n, (uint16_t*)kcache,
-                                                                           (uint16_t*)vcache, ld_cache);
-        else
-            qkv_rmsnorm_rope_rows_kernel<F16, NP><<<grid, block, 0, st>>>((uint16_t*)qkv, rows, dim, ldx, pp, cos_t, sin_t,
-                                                                          head_dim, idx, n, (uint16_t*)kcache,
-                                                                          (uint16_t*)vcache, ld_cache);
+    return fino_launch_rows<kMaxPasses>(who, who, rows, 3u, kWavesPerBlock, dim, dtype,
+                                        [&](auto t, auto np, dim3 grid, dim3 block) {
+        qkv_rmsnorm_rope_rows_kernel<decltype(t), decltype(np)::value><<<grid, block, 0, st>>>(
+            (uint16_t*)qkv, rows, dim, ldx, pp, cos_t, sin_t, head_dim, idx, n, (uint16_t*)kcache, (uint16_t*)vcache, ld_cache);
     });
-    FINO_CHECK(ok, FINO_ERR_UNSUPPORTED, "%s: dim %d > %d unsupported", who, dim, kMaxPasses * 512);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
 }
 
 extern "C" int fino_rmsnorm_rope(void* x, int64_t rows, int dim, int64_t ldx, const void* weight, float eps,
                                  const float* cos_t, const float* sin_t, int head_dim, int dtype, void* stream) {
-    return fino_rmsnorm_rope_scaled(x, rows, dim, ldx, weight, eps, cos_t, sin_t, head_dim, 1.0f, dtype, stream);
+    return rmsnorm_rope_impl("fino_rmsnorm_rope", x, rows, dim, ldx, 1, one_part(weight, eps, 1.0f, cos_t != nullptr), cos_t,
+                             sin_t, head_dim, nullptr, nullptr, nullptr, dtype, stream);
 }
 
+// (every refusal says fino_headnorm_rope: the unscaled entry point is this one with out_scale = 1)
 extern "C" int fino_headnorm_rope_scaled(void* x, int batch, int64_t rows, int heads, int head_dim, int64_t ldx,
                                          int64_t batch_stride, const void* w, const void* b, float eps,
                                          const float* cos_t, const float* sin_t, int64_t rope_row0, float out_scale,
                                          int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_headnorm_rope: dtype %d", dtype);
+    const char* fam = "fino_headnorm_rope";
+    FINO_TRY(fino_check_dtype(fam, dtype));
     FINO_CHECK(x && batch >= 0 && rows >= 0 && heads > 0 && out_scale > 0.f, FINO_ERR_ARG, "fino_headnorm_rope: bad shape");
     FINO_CHECK(head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128, FINO_ERR_UNSUPPORTED,
                "fino_headnorm_rope: head_dim %d not in {16,32,64,128}", head_dim);
     FINO_CHECK((w == nullptr) == (b == nullptr) && (cos_t == nullptr) == (sin_t == nullptr), FINO_ERR_ARG,
                "fino_headnorm_rope: w/b and cos/sin come in pairs");
-    FINO_CHECK(ldx % 8 == 0 && batch_stride % 8 == 0 && fino_aligned16(x) && fino_aligned16(w) && fino_aligned16(b) &&
-                   fino_aligned16(cos_t) && fino_aligned16(sin_t),
-               FINO_ERR_ARG, "fino_headnorm_rope: 16-byte alignment required");
+    const bool batches_ok = batch_stride % 8 == 0;          // every batch element starts on a 16-byte boundary
+    FINO_TRY(fino_check_aligned16(fam, 8, {{x, ldx}, {w, 0}, {b, 0}, {cos_t, 0}, {sin_t, 0}}, batches_ok));
     const int64_t total = (int64_t)batch * rows * heads * (head_dim / 8);
     if (total == 0) return FINO_OK;
     const unsigned grid = (unsigned)((total + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        headnorm_rope_kernel<BF16><<<grid, 256, 0, st>>>((uint16_t*)x, batch, rows, heads, head_dim, ldx, batch_stride,
-                                                         (const uint16_t*)w, (const uint16_t*)b, eps, cos_t, sin_t,
-                                                         rope_row0, out_scale);
-    else
-        headnorm_rope_kernel<F16><<<grid, 256, 0, st>>>((uint16_t*)x, batch, rows, heads, head_dim, ldx, batch_stride,
-                                                        (const uint16_t*)w, (const uint16_t*)b, eps, cos_t, sin_t,
-                                                        rope_row0, out_scale);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        headnorm_rope_kernel<decltype(t)><<<grid, 256, 0, st>>>((uint16_t*)x, batch, rows, heads, head_dim, ldx, batch_stride,
+                                                                (const uint16_t*)w, (const uint16_t*)b, eps, cos_t, sin_t,
+                                                                rope_row0, out_scale);
+    });
+    return fino_launch_check("fino_headnorm_rope_scaled");
 }
 
 extern "C" int fino_headnorm_rope(void* x, int batch, int64_t rows, int heads, int head_dim, int64_t ldx,
@@ -823,127 +761,101 @@ extern "C" int fino_headnorm_rope(void* x, int batch, int64_t rows, int heads, i
 
 extern "C" int fino_patchify(const void* x, void* a, int channels, int frames, int height, int width, int pt, int ph,
                              int pw, int64_t lda, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_patchify: dtype %d", dtype);
+    FINO_TRY(fino_check_dtype("fino_patchify", dtype));
     FINO_CHECK(x && a && channels > 0 && pt > 0 && ph > 0 && pw > 0, FINO_ERR_ARG, "fino_patchify: bad arguments");
     FINO_CHECK(frames % pt == 0 && height % ph == 0 && width % pw == 0, FINO_ERR_ARG,
                "fino_patchify: (%d,%d,%d) not divisible by patch (%d,%d,%d)", frames, height, width, pt, ph, pw);
     FINO_CHECK(lda >= (int64_t)channels * pt * ph * pw, FINO_ERR_ARG, "fino_patchify: lda too small");
     const int64_t total = (int64_t)channels * frames * height * width / pw;
     if (total == 0) return FINO_OK;
-    patchify_kernel<<<grid_1d(total), 256, 0, (hipStream_t)stream>>>((const uint16_t*)x, (uint16_t*)a, channels,
-                                                                     frames, height, width, pt, ph, pw, lda);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    patchify_kernel<<<fino_grid_1d(total, kFinoGridCap8, true), 256, 0, (hipStream_t)stream>>>(
+        (const uint16_t*)x, (uint16_t*)a, channels, frames, height, width, pt, ph, pw, lda);
+    return fino_launch_check("fino_patchify");
 }
 
 extern "C" int fino_unpatchify(const void* y, void* out, int cout, int frames, int height, int width, int pt, int ph,
                                int pw, int64_t ldy, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_unpatchify: dtype %d", dtype);
+    FINO_TRY(fino_check_dtype("fino_unpatchify", dtype));
     FINO_CHECK(y && out && cout > 0 && pt > 0 && ph > 0 && pw > 0, FINO_ERR_ARG, "fino_unpatchify: bad arguments");
     FINO_CHECK(frames % pt == 0 && height % ph == 0 && width % pw == 0, FINO_ERR_ARG,
                "fino_unpatchify: (%d,%d,%d) not divisible by patch (%d,%d,%d)", frames, height, width, pt, ph, pw);
     FINO_CHECK(ldy >= (int64_t)cout * pt * ph * pw, FINO_ERR_ARG, "fino_unpatchify: ldy too small");
     const int64_t total = (int64_t)cout * frames * height * width;
     if (total == 0) return FINO_OK;
-    unpatchify_kernel<<<grid_1d(total), 256, 0, (hipStream_t)stream>>>((const uint16_t*)y, (uint16_t*)out, cout,
-                                                                       frames, height, width, pt, ph, pw, ldy);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    unpatchify_kernel<<<fino_grid_1d(total, kFinoGridCap8, true), 256, 0, (hipStream_t)stream>>>(
+        (const uint16_t*)y, (uint16_t*)out, cout, frames, height, width, pt, ph, pw, ldy);
+    return fino_launch_check("fino_unpatchify");
 }
 
 extern "C" int fino_wan_model_input(const float* lat, const float* cond, const float* id_lat, const float* traj,
                                     void* out, int channels, int gen_frames, int id_frames, int height, int width,
                                     int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_wan_model_input: dtype %d", dtype);
+    FINO_TRY(fino_check_dtype("fino_wan_model_input", dtype));
     FINO_CHECK(lat && cond && traj && out && (id_frames == 0 || id_lat), FINO_ERR_ARG,
                "fino_wan_model_input: null pointer");
     FINO_CHECK(channels > 0 && gen_frames > 0 && id_frames >= 0 && height > 0 && width > 0, FINO_ERR_ARG,
                "fino_wan_model_input: bad shape");
     const int64_t total = (int64_t)2 * channels * (gen_frames + id_frames) * height * width;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        wan_model_input_kernel<BF16><<<grid_1d(total), 256, 0, st>>>(lat, cond, id_lat, traj, (uint16_t*)out, channels,
-                                                                     gen_frames, id_frames, height * width);
-    else
-        wan_model_input_kernel<F16><<<grid_1d(total), 256, 0, st>>>(lat, cond, id_lat, traj, (uint16_t*)out, channels,
-                                                                    gen_frames, id_frames, height * width);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        wan_model_input_kernel<decltype(t)><<<fino_grid_1d(total, kFinoGridCap8, true), 256, 0, st>>>(
+            lat, cond, id_lat, traj, (uint16_t*)out, channels, gen_frames, id_frames, height * width);
+    });
+    return fino_launch_check("fino_wan_model_input");
 }
 
+// The sampler steps: fino_check_flat_step / fino_check_frames_step and the grid are the guided steps' too (fino_guidance.hip)
 extern "C" int fino_cfg_vpred_step(const void* pred, void* lat, int64_t n_lat, int64_t batch_stride, const float* coef_dev,
                                    int has_uncond, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_cfg_vpred_step: dtype %d", dtype);
-    FINO_CHECK(pred && lat && coef_dev && n_lat > 0 && (!has_uncond || batch_stride >= n_lat), FINO_ERR_ARG,
-               "fino_cfg_vpred_step: bad arguments");
+    const char* who = "fino_cfg_vpred_step";
+    FINO_TRY(fino_check_flat_step(who, dtype, pred && lat && coef_dev, n_lat, has_uncond != 0, batch_stride));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        cfg_vpred_step_kernel<BF16><<<grid_1d(n_lat), 256, 0, st>>>((const uint16_t*)pred, (uint16_t*)lat, n_lat,
-                                                                   batch_stride, coef_dev, has_uncond);
-    else
-        cfg_vpred_step_kernel<F16><<<grid_1d(n_lat), 256, 0, st>>>((const uint16_t*)pred, (uint16_t*)lat, n_lat,
-                                                                  batch_stride, coef_dev, has_uncond);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        cfg_vpred_step_kernel<decltype(t)><<<fino_grid_1d(n_lat, kFinoGridCap8, true), 256, 0, st>>>(
+            (const uint16_t*)pred, (uint16_t*)lat, n_lat, batch_stride, coef_dev, has_uncond);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_cfg_dpm_step(const void* pred, void* lat, float* x0_old, const void* noise, int64_t n_lat,
                                  int64_t batch_stride, const float* coef_dev, int has_uncond, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_cfg_dpm_step: dtype %d", dtype);
-    FINO_CHECK(pred && lat && x0_old && noise && coef_dev && n_lat > 0 && (!has_uncond || batch_stride >= n_lat),
-               FINO_ERR_ARG, "fino_cfg_dpm_step: bad arguments");
+    const char* who = "fino_cfg_dpm_step";
+    FINO_TRY(fino_check_flat_step(who, dtype, pred && lat && x0_old && noise && coef_dev, n_lat, has_uncond != 0, batch_stride));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        cfg_dpm_step_kernel<BF16><<<grid_1d(n_lat), 256, 0, st>>>((const uint16_t*)pred, (uint16_t*)lat, x0_old,
-                                                                 (const uint16_t*)noise, n_lat, batch_stride, coef_dev,
-                                                                 has_uncond);
-    else
-        cfg_dpm_step_kernel<F16><<<grid_1d(n_lat), 256, 0, st>>>((const uint16_t*)pred, (uint16_t*)lat, x0_old,
-                                                                (const uint16_t*)noise, n_lat, batch_stride, coef_dev,
-                                                                has_uncond);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        cfg_dpm_step_kernel<decltype(t)><<<fino_grid_1d(n_lat, kFinoGridCap8, true), 256, 0, st>>>(
+            (const uint16_t*)pred, (uint16_t*)lat, x0_old, (const uint16_t*)noise, n_lat, batch_stride, coef_dev, has_uncond);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_cfg_unipc_step(const void* cond_pred, const void* uncond_pred, float* x, float* last, float* m0,
                                    float* m1, int channels, int gen_frames, int total_frames, int height, int width,
                                    const float* coef_dev, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_cfg_unipc_step: dtype %d", dtype);
-    FINO_CHECK(cond_pred && x && last && m0 && m1 && coef_dev, FINO_ERR_ARG, "fino_cfg_unipc_step: null pointer");
-    FINO_CHECK(channels > 0 && gen_frames > 0 && total_frames >= gen_frames && height > 0 && width > 0, FINO_ERR_ARG,
-               "fino_cfg_unipc_step: bad shape");
+    const char* who = "fino_cfg_unipc_step";
+    FINO_TRY(fino_check_frames_step(who, dtype, cond_pred && x && last && m0 && m1 && coef_dev, channels, gen_frames,
+                                    total_frames, height, width));
     const int64_t total = (int64_t)channels * gen_frames * height * width;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        cfg_unipc_kernel<BF16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)cond_pred, (const uint16_t*)uncond_pred,
-                                                               x, last, m0, m1, channels, gen_frames, total_frames,
-                                                               height * width, coef_dev);
-    else
-        cfg_unipc_kernel<F16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)cond_pred, (const uint16_t*)uncond_pred,
-                                                              x, last, m0, m1, channels, gen_frames, total_frames,
-                                                              height * width, coef_dev);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        cfg_unipc_kernel<decltype(t)><<<fino_grid_1d(total, kFinoGridCap8, true), 256, 0, st>>>(
+            (const uint16_t*)cond_pred, (const uint16_t*)uncond_pred, x, last, m0, m1, channels, gen_frames, total_frames,
+            height * width, coef_dev);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_cfg_euler_step(const void* cond_pred, const void* uncond_pred, float* lat, int channels,
                                    int gen_frames, int total_frames, int height, int width, float guidance,
                                    const float* dt_dev, int round_out, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_cfg_euler_step: dtype %d", dtype);
-    FINO_CHECK(cond_pred && lat && dt_dev, FINO_ERR_ARG, "fino_cfg_euler_step: null pointer");
-    FINO_CHECK(channels > 0 && gen_frames > 0 && total_frames >= gen_frames && height > 0 && width > 0, FINO_ERR_ARG,
-               "fino_cfg_euler_step: bad shape");
+    const char* who = "fino_cfg_euler_step";
+    FINO_TRY(fino_check_frames_step(who, dtype, cond_pred && lat && dt_dev, channels, gen_frames, total_frames, height, width));
     const int64_t total = (int64_t)channels * gen_frames * height * width;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        cfg_euler_kernel<BF16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)cond_pred,
-                                                               (const uint16_t*)uncond_pred, lat, channels, gen_frames,
-                                                               total_frames, height * width, guidance, dt_dev,
-                                                               round_out);
-    else
-        cfg_euler_kernel<F16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)cond_pred, (const uint16_t*)uncond_pred,
-                                                              lat, channels, gen_frames, total_frames, height * width,
-                                                              guidance, dt_dev, round_out);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        cfg_euler_kernel<decltype(t)><<<fino_grid_1d(total, kFinoGridCap8, true), 256, 0, st>>>(
+            (const uint16_t*)cond_pred, (const uint16_t*)uncond_pred, lat, channels, gen_frames, total_frames, height * width,
+            guidance, dt_dev, round_out);
+    });
+    return fino_launch_check(who);
 }

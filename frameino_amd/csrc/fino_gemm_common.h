@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include "fino_common.h"
+#include "fino_host.h"
 
 #ifdef FINO_GEMM_STAMP
 // diagnostic build only (make stamp): per-wave s_memtime deltas of workgroup 17: [wave][0..3] main-loop segments, [4] K-tiles,
@@ -373,7 +374,7 @@ int gemm_dispatch_keep_epilogue(int epi, F&& launch) {
 // the element type: launch(BF16{}) or launch(F16{}) (the caller has validated `dtype`)
 template <typename F>
 int gemm_dispatch_dtype(int dtype, F&& launch) {
-    return dtype == FINO_BF16 ? launch(BF16{}) : launch(F16{});
+    return fino_dispatch_dtype(dtype, launch);
 }
 // the tile height in 32-row units, 2 .. 8 (plan_tiles and the tile_m checks produce nothing else)
 template <typename F>

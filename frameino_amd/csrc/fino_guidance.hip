@@ -20,6 +20,7 @@
 // 1-2 M elements (9 MB read per step), so the cost is the two launches, not the bytes.
 //
 // The fino_guided_*_step kernels are the fino_cfg_*_step bodies (fino_sampler_step.h) with v formed from {A, B}.
+#include "fino_host.h"
 #include "fino_sampler_step.h"
 
 namespace {
@@ -219,13 +220,6 @@ __global__ __launch_bounds__(256) void guided_dpm_kernel(const uint16_t* __restr
     dpm_step_body<T, GuidedF32>(pred, lat, x0_old, noise, n_lat, batch_stride, coef, ab, 1, FINO_GRID_STRIDE());
 }
 
-// the launch shape of the fino_cfg_*_step kernels
-inline int grid_1d(int64_t total, int block = 256) {
-    int64_t g = (total + block - 1) / block;
-    const int64_t cap = 256 * 8;  // ~8 blocks per CU, grid-stride the rest
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 constexpr int64_t kMaxElems = (int64_t)1 << 40;      // keeps the workgroup count of the moments launch below 2^31
 
 }  // namespace
@@ -238,7 +232,8 @@ extern "C" int fino_guider_coefs(const void* cond_pred, const void* uncond_pred,
                                  int64_t row_stride, int kind, double norm_threshold, double eta, double guidance_rescale,
                                  const float* g_dev, const float* zero_init_dev, void* workspace, int64_t workspace_bytes,
                                  float* ab_dev, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_guider_coefs: dtype %d", dtype);
+    const char* who = "fino_guider_coefs";
+    FINO_TRY(fino_check_dtype(who, dtype));
     FINO_CHECK(kind == FINO_GUIDER_RESCALE || kind == FINO_GUIDER_ZERO_STAR || kind == FINO_GUIDER_APG, FINO_ERR_ARG,
                "fino_guider_coefs: kind %d", kind);
     FINO_CHECK(cond_pred && uncond_pred && g_dev && workspace && ab_dev, FINO_ERR_ARG, "fino_guider_coefs: null pointer");
@@ -261,98 +256,74 @@ extern "C" int fino_guider_coefs(const void* cond_pred, const void* uncond_pred,
     const uint16_t* pu = (const uint16_t*)uncond_pred;
     double* partial = (double*)workspace;
     const unsigned grid = (unsigned)nblocks;
-    if (dtype == FINO_BF16) {
-        if (vec)
-            guider_moments_kernel<BF16, true><<<grid, kThreads, 0, st>>>(pc, pu, n, row_len, row_stride, partial);
-        else
-            guider_moments_kernel<BF16, false><<<grid, kThreads, 0, st>>>(pc, pu, n, row_len, row_stride, partial);
-    } else {
-        if (vec)
-            guider_moments_kernel<F16, true><<<grid, kThreads, 0, st>>>(pc, pu, n, row_len, row_stride, partial);
-        else
-            guider_moments_kernel<F16, false><<<grid, kThreads, 0, st>>>(pc, pu, n, row_len, row_stride, partial);
-    }
-    FINO_LAUNCH_CHECK();
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        auto launch = [&](auto v) {
+            guider_moments_kernel<decltype(t), decltype(v)::value><<<grid, kThreads, 0, st>>>(pc, pu, n, row_len, row_stride,
+                                                                                             partial);
+        };
+        vec ? launch(std::true_type{}) : launch(std::false_type{});
+    });
+    FINO_TRY(fino_launch_check(who));
     const GuiderParams p = {kind, norm_threshold, eta, guidance_rescale};
     guider_finish_kernel<<<1, kThreads, 0, st>>>(partial, nblocks, (double)n, g_dev, zero_init_dev, p, ab_dev);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    return fino_launch_check(who);
 }
 
+// The guided steps: the checks and the launch shape of the fino_cfg_*_step entry points (fino_host.h), with the pointers
+// these kernels read
 extern "C" int fino_guided_euler_step(const void* cond_pred, const void* uncond_pred, float* lat, int channels,
                                       int gen_frames, int total_frames, int height, int width, const float* ab_dev,
                                       const float* dt_dev, int round_out, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_guided_euler_step: dtype %d", dtype);
-    FINO_CHECK(cond_pred && uncond_pred && lat && ab_dev && dt_dev, FINO_ERR_ARG, "fino_guided_euler_step: null pointer");
-    FINO_CHECK(channels > 0 && gen_frames > 0 && total_frames >= gen_frames && height > 0 && width > 0, FINO_ERR_ARG,
-               "fino_guided_euler_step: bad shape");
+    const char* who = "fino_guided_euler_step";
+    FINO_TRY(fino_check_frames_step(who, dtype, cond_pred && uncond_pred && lat && ab_dev && dt_dev, channels, gen_frames,
+                                    total_frames, height, width));
     const int64_t total = (int64_t)channels * gen_frames * height * width;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        guided_euler_kernel<BF16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)cond_pred, (const uint16_t*)uncond_pred,
-                                                                  lat, channels, gen_frames, total_frames, height * width,
-                                                                  ab_dev, dt_dev, round_out);
-    else
-        guided_euler_kernel<F16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)cond_pred, (const uint16_t*)uncond_pred,
-                                                                 lat, channels, gen_frames, total_frames, height * width,
-                                                                 ab_dev, dt_dev, round_out);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        guided_euler_kernel<decltype(t)><<<fino_grid_1d(total, kFinoGridCap8, true), 256, 0, st>>>(
+            (const uint16_t*)cond_pred, (const uint16_t*)uncond_pred, lat, channels, gen_frames, total_frames, height * width,
+            ab_dev, dt_dev, round_out);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_guided_unipc_step(const void* cond_pred, const void* uncond_pred, float* x, float* last, float* m0,
                                       float* m1, int channels, int gen_frames, int total_frames, int height, int width,
                                       const float* coef_dev, const float* ab_dev, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_guided_unipc_step: dtype %d", dtype);
-    FINO_CHECK(cond_pred && uncond_pred && x && last && m0 && m1 && coef_dev && ab_dev, FINO_ERR_ARG,
-               "fino_guided_unipc_step: null pointer");
-    FINO_CHECK(channels > 0 && gen_frames > 0 && total_frames >= gen_frames && height > 0 && width > 0, FINO_ERR_ARG,
-               "fino_guided_unipc_step: bad shape");
+    const char* who = "fino_guided_unipc_step";
+    FINO_TRY(fino_check_frames_step(who, dtype, cond_pred && uncond_pred && x && last && m0 && m1 && coef_dev && ab_dev, channels,
+                                    gen_frames, total_frames, height, width));
     const int64_t total = (int64_t)channels * gen_frames * height * width;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        guided_unipc_kernel<BF16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)cond_pred, (const uint16_t*)uncond_pred,
-                                                                  x, last, m0, m1, channels, gen_frames, total_frames,
-                                                                  height * width, coef_dev, ab_dev);
-    else
-        guided_unipc_kernel<F16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)cond_pred, (const uint16_t*)uncond_pred,
-                                                                 x, last, m0, m1, channels, gen_frames, total_frames,
-                                                                 height * width, coef_dev, ab_dev);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        guided_unipc_kernel<decltype(t)><<<fino_grid_1d(total, kFinoGridCap8, true), 256, 0, st>>>(
+            (const uint16_t*)cond_pred, (const uint16_t*)uncond_pred, x, last, m0, m1, channels, gen_frames, total_frames,
+            height * width, coef_dev, ab_dev);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_guided_vpred_step(const void* pred, void* lat, int64_t n_lat, int64_t batch_stride,
                                       const float* coef_dev, const float* ab_dev, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_guided_vpred_step: dtype %d", dtype);
-    FINO_CHECK(pred && lat && coef_dev && ab_dev && n_lat > 0 && batch_stride >= n_lat, FINO_ERR_ARG,
-               "fino_guided_vpred_step: bad arguments");
+    const char* who = "fino_guided_vpred_step";
+    FINO_TRY(fino_check_flat_step(who, dtype, pred && lat && coef_dev && ab_dev, n_lat, true, batch_stride));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        guided_vpred_kernel<BF16><<<grid_1d(n_lat), 256, 0, st>>>((const uint16_t*)pred, (uint16_t*)lat, n_lat, batch_stride,
-                                                                  coef_dev, ab_dev);
-    else
-        guided_vpred_kernel<F16><<<grid_1d(n_lat), 256, 0, st>>>((const uint16_t*)pred, (uint16_t*)lat, n_lat, batch_stride,
-                                                                 coef_dev, ab_dev);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        guided_vpred_kernel<decltype(t)><<<fino_grid_1d(n_lat, kFinoGridCap8, true), 256, 0, st>>>(
+            (const uint16_t*)pred, (uint16_t*)lat, n_lat, batch_stride, coef_dev, ab_dev);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_guided_dpm_step(const void* pred, void* lat, float* x0_old, const void* noise, int64_t n_lat,
                                     int64_t batch_stride, const float* coef_dev, const float* ab_dev, int dtype,
                                     void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_guided_dpm_step: dtype %d", dtype);
-    FINO_CHECK(pred && lat && x0_old && noise && coef_dev && ab_dev && n_lat > 0 && batch_stride >= n_lat, FINO_ERR_ARG,
-               "fino_guided_dpm_step: bad arguments");
+    const char* who = "fino_guided_dpm_step";
+    FINO_TRY(fino_check_flat_step(who, dtype, pred && lat && x0_old && noise && coef_dev && ab_dev, n_lat, true, batch_stride));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        guided_dpm_kernel<BF16><<<grid_1d(n_lat), 256, 0, st>>>((const uint16_t*)pred, (uint16_t*)lat, x0_old,
-                                                                (const uint16_t*)noise, n_lat, batch_stride, coef_dev,
-                                                                ab_dev);
-    else
-        guided_dpm_kernel<F16><<<grid_1d(n_lat), 256, 0, st>>>((const uint16_t*)pred, (uint16_t*)lat, x0_old,
-                                                               (const uint16_t*)noise, n_lat, batch_stride, coef_dev,
-                                                               ab_dev);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        guided_dpm_kernel<decltype(t)><<<fino_grid_1d(n_lat, kFinoGridCap8, true), 256, 0, st>>>(
+            (const uint16_t*)pred, (uint16_t*)lat, x0_old, (const uint16_t*)noise, n_lat, batch_stride, coef_dev, ab_dev);
+    });
+    return fino_launch_check(who);
 }

@@ -12,6 +12,7 @@
 // Grid: x = 64-column strips of K, y = segments of N-tiles.  A workgroup (4 waves) stages A^T of its strip, every adapter,
 // in LDS once ([chunk][k 0..63][16 ranks], zero outside the rank / K) and walks its N-tiles of 128 rows (32 per wave).
 #include "fino_common.h"
+#include "fino_host.h"
 
 namespace {
 
@@ -182,6 +183,7 @@ __global__ __launch_bounds__(256) void lora_merge_f32(const float* wb, int64_t l
 extern "C" int fino_lora_merge(const void* w_base, int64_t ldw_base, void* w_out, int64_t ldw_out, int64_t n, int64_t k,
                                int n_adapters, const void* const* a, const int64_t* lda, const void* const* b,
                                const int64_t* ldb, const int* rank, const float* scale, int dtype, void* stream) {
+    const char* who = "fino_lora_merge";
     FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16 || dtype == FINO_F32, FINO_ERR_ARG,
                "fino_lora_merge: dtype %d is not FINO_BF16 / FINO_F16 / FINO_F32", dtype);
     FINO_CHECK(n >= 0 && k >= 0, FINO_ERR_ARG, "fino_lora_merge: negative shape n=%lld k=%lld", (long long)n, (long long)k);
@@ -220,10 +222,8 @@ extern "C" int fino_lora_merge(const void* w_base, int64_t ldw_base, void* w_out
         const int64_t blocks = (threads + 255) / 256;
         FINO_CHECK(blocks <= 0x7fffffff, FINO_ERR_UNSUPPORTED, "fino_lora_merge: fp32 weight too large (%lld x %lld)",
                    (long long)n, (long long)k);
-        hipLaunchKernelGGL(lora_merge_f32, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)w_base, ldw_base,
-                           (float*)w_out, ldw_out, n, k, args, w_vec);
-        FINO_LAUNCH_CHECK();
-        return FINO_OK;
+        lora_merge_f32<<<(unsigned)blocks, 256, 0, st>>>((const float*)w_base, ldw_base, (float*)w_out, ldw_out, n, k, args, w_vec);
+        return fino_launch_check(who);
     }
     FINO_CHECK(chunks * 16 <= FINO_LORA_MAX_TOTAL_RANK, FINO_ERR_UNSUPPORTED,
                "fino_lora_merge: total rank %d of one call exceeds %d (ranks are padded to 16)", chunks * 16,
@@ -240,21 +240,12 @@ extern "C" int fino_lora_merge(const void* w_base, int64_t ldw_base, void* w_out
     FINO_CHECK(segs <= 65535, FINO_ERR_UNSUPPORTED, "fino_lora_merge: n = %lld too large", (long long)n);
     const size_t lds = (size_t)chunks * kTK * 16 * sizeof(uint16_t);
     const dim3 grid((unsigned)strips, (unsigned)segs);
-    if (dtype == FINO_BF16) {
-        static FinoPerDeviceOnce once;
-        if (int rc = fino_max_smem_once(once, (const void*)lora_merge_mfma<BF16>, FINO_LORA_MAX_TOTAL_RANK * kTK * 2,
-                                        "fino_lora_merge"))
-            return rc;
-        hipLaunchKernelGGL(lora_merge_mfma<BF16>, grid, dim3(256), lds, st, (const uint16_t*)w_base, ldw_base,
-                           (uint16_t*)w_out, ldw_out, n, k, args, (int)tiles_per_seg, w_vec);
-    } else {
-        static FinoPerDeviceOnce once;
-        if (int rc = fino_max_smem_once(once, (const void*)lora_merge_mfma<F16>, FINO_LORA_MAX_TOTAL_RANK * kTK * 2,
-                                        "fino_lora_merge"))
-            return rc;
-        hipLaunchKernelGGL(lora_merge_mfma<F16>, grid, dim3(256), lds, st, (const uint16_t*)w_base, ldw_base,
-                           (uint16_t*)w_out, ldw_out, n, k, args, (int)tiles_per_seg, w_vec);
-    }
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    return fino_dispatch_dtype(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        static FinoPerDeviceOnce once;        // one per instantiation: the LDS limit is raised per kernel (and per device)
+        FINO_TRY(fino_max_smem_once(once, (const void*)lora_merge_mfma<T>, FINO_LORA_MAX_TOTAL_RANK * kTK * 2, who));
+        lora_merge_mfma<T><<<grid, 256, lds, st>>>((const uint16_t*)w_base, ldw_base, (uint16_t*)w_out, ldw_out, n, k, args,
+                                                   (int)tiles_per_seg, w_vec);
+        return fino_launch_check(who);
+    });
 }

@@ -34,6 +34,7 @@
 //
 // HBM-bound: 16-byte loads and stores, fp32 arithmetic, no contraction (the file is built with -ffp-contract=off).
 #include "fino_common.h"
+#include "fino_host.h"
 
 namespace {
 
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void residual_kernel(const void* a, int64
 // store of the chunk, and no two threads share an element: r_new may be r_prev.
 constexpr int kMagUnroll = 4;           // (2, 3, 4 and 6 vectors per plane in flight, and a cap of 1024 / 1280 / 2048
 constexpr int kMagWavesPerBlock = kThreads / 64;        // workgroups, measure alike at [24640, 3072]: within the run's spread)
-constexpr int kMagMaxBlocks = 256 * 8;
+constexpr int kMagMaxBlocks = (int)kFinoGridCap8;
 
 template <typename T>
 __global__ __launch_bounds__(kThreads) void magcache_kernel(const void* x_out, int64_t ld_out, const void* x_in, int64_t ld_in,
@@ -285,9 +286,7 @@ __global__ __launch_bounds__(kThreads) void magcache_finish_kernel(const double*
 
 // the waves of a fino_magcache_calibrate launch over `rows` rows: one per row up to the grid's cap, whole workgroups
 int64_t magcache_waves(int64_t rows) {
-    int64_t blocks = (rows + kMagWavesPerBlock - 1) / kMagWavesPerBlock;
-    blocks = blocks < 1 ? 1 : blocks > kMagMaxBlocks ? kMagMaxBlocks : blocks;
-    return blocks * kMagWavesPerBlock;
+    return (int64_t)fino_grid_1d(rows, kMagMaxBlocks, true, kMagWavesPerBlock) * kMagWavesPerBlock;
 }
 
 template <typename T>
@@ -593,36 +592,37 @@ int fc_disk(int r, FcDisk& disk) {
     return n;
 }
 
-int esize_of(int dtype) { return dtype == FINO_F32 ? 4 : 2; }
-
 // the factor planes of a TaylorSeer call: [n planes][rows][dim] of dtype fdtype, 16-byte aligned rows, planes that do not overlap
 bool planes_ok(const void* fac, int64_t plane, int64_t ldf, int fdtype, int n, int64_t rows, int64_t dim) {
-    const int per16 = 16 / esize_of(fdtype);
+    const int per16 = fino_per16(fdtype);
     if (!fac || !fino_aligned16(fac) || ldf < dim || ldf % per16 != 0) return false;
     return n <= 1 || (plane % per16 == 0 && (rows == 0 || plane >= (rows - 1) * ldf + dim));
 }
 
-int taylor_grid(uint32_t nvec) {
-    const int64_t grid = ((int64_t)nvec + kThreads - 1) / kThreads;
-    return (int)(grid > 256 * 8 ? 256 * 8 : grid);
+// rows x dim walked in 16-byte vectors of per16 elements, fewer than 2^31 of them
+int check_rows_dim(const char* who, int64_t rows, int64_t dim, int per16) {
+    FINO_CHECK(rows >= 0 && dim > 0 && dim % per16 == 0 && rows * (dim / per16) < (1LL << 31), FINO_ERR_ARG,
+               "%s: rows=%lld dim=%lld", who, (long long)rows, (long long)dim);
+    return FINO_OK;
 }
 
-bool rows_ok(const void* p, int64_t ld, int dtype) {
-    const int per16 = 16 / esize_of(dtype);
-    return fino_aligned16(p) && ld % per16 == 0;
+// the element dtype (two) and, inside it, the factor dtype (three): launch(T{}, F{})
+template <typename L>
+void taylor_dispatch(int dtype, int fdtype, L&& launch) {
+    fino_dispatch_dtype(dtype, [&](auto t) { fino_dispatch_dtype3<F32>(fdtype, [&](auto f) { launch(t, f); }); });
 }
 
 }  // namespace
 
 extern "C" int fino_step_cache_probe(const FinoStepCacheSegment* segs, int nseg, int64_t dim, float* sums, float* workspace,
                                      int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16 || dtype == FINO_F32, FINO_ERR_ARG, "fino_step_cache_probe: dtype %d",
-               dtype);
+    const char* who = "fino_step_cache_probe";
+    FINO_TRY(fino_check_dtype3(who, dtype));
     FINO_CHECK(segs && nseg >= 1 && nseg <= FINO_STEP_CACHE_MAX_SEGMENTS, FINO_ERR_ARG,
                "fino_step_cache_probe: %d segments (1 .. %d)", nseg, FINO_STEP_CACHE_MAX_SEGMENTS);
     FINO_CHECK(sums && workspace && fino_aligned16(sums) && fino_aligned16(workspace), FINO_ERR_ARG,
                "fino_step_cache_probe: sums / workspace missing or not 16-byte aligned");
-    const int per16 = 16 / esize_of(dtype);
+    const int per16 = fino_per16(dtype);
     FINO_CHECK(dim > 0 && dim % per16 == 0, FINO_ERR_ARG, "fino_step_cache_probe: dim=%lld must be a multiple of %d",
                (long long)dim, per16);
     ProbeArgs args = {};
@@ -635,49 +635,36 @@ extern "C" int fino_step_cache_probe(const FinoStepCacheSegment* segs, int nseg,
         FINO_CHECK(g.ld_h0 >= dim && g.ld_h1 >= dim && g.ld_r >= dim && (!g.p || g.ld_p >= dim) &&
                        (!g.h1_copy || g.ld_h1_copy >= dim),
                    FINO_ERR_ARG, "fino_step_cache_probe: segment %d: a row stride is below dim", s);
-        FINO_CHECK(rows_ok(g.h0, g.ld_h0, dtype) && rows_ok(g.h1, g.ld_h1, dtype) && rows_ok(g.r, g.ld_r, dtype) &&
-                       (!g.p || rows_ok(g.p, g.ld_p, dtype)) && (!g.h1_copy || rows_ok(g.h1_copy, g.ld_h1_copy, dtype)),
+        FINO_CHECK(fino_rows_ok(g.h0, g.ld_h0, per16) && fino_rows_ok(g.h1, g.ld_h1, per16) && fino_rows_ok(g.r, g.ld_r, per16) &&
+                       (!g.p || fino_rows_ok(g.p, g.ld_p, per16)) && (!g.h1_copy || fino_rows_ok(g.h1_copy, g.ld_h1_copy, per16)),
                    FINO_ERR_ARG, "fino_step_cache_probe: segment %d: 16-byte alignment required", s);
         args.seg[s] = g;
     }
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(FINO_STEP_CACHE_BLOCKS, nseg);
-    if (dtype == FINO_BF16)
-        probe_kernel<BF16><<<grid, kThreads, 0, st>>>(args, workspace);
-    else if (dtype == FINO_F16)
-        probe_kernel<F16><<<grid, kThreads, 0, st>>>(args, workspace);
-    else
-        probe_kernel<F32><<<grid, kThreads, 0, st>>>(args, workspace);
-    FINO_LAUNCH_CHECK();
+    fino_dispatch_dtype3<F32>(dtype, [&](auto t) { probe_kernel<decltype(t)><<<grid, kThreads, 0, st>>>(args, workspace); });
+    FINO_TRY(fino_launch_check(who));
     probe_finish_kernel<<<nseg, kThreads, 0, st>>>(workspace, sums);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_step_cache_residual(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo,
                                         int64_t rows, int64_t dim, int subtract, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16 || dtype == FINO_F32, FINO_ERR_ARG,
-               "fino_step_cache_residual: dtype %d", dtype);
-    const int per16 = 16 / esize_of(dtype);
-    FINO_CHECK(rows >= 0 && dim > 0 && dim % per16 == 0 && rows * (dim / per16) < (1LL << 31), FINO_ERR_ARG,
-               "fino_step_cache_residual: rows=%lld dim=%lld", (long long)rows, (long long)dim);
-    FINO_CHECK(a && b && out, FINO_ERR_ARG, "fino_step_cache_residual: null pointer");
-    FINO_CHECK(lda >= dim && ldb >= dim && ldo >= dim, FINO_ERR_ARG, "fino_step_cache_residual: a row stride is below dim");
-    FINO_CHECK(rows_ok(a, lda, dtype) && rows_ok(b, ldb, dtype) && rows_ok(out, ldo, dtype), FINO_ERR_ARG,
-               "fino_step_cache_residual: 16-byte alignment required");
+    const char* who = "fino_step_cache_residual";
+    FINO_TRY(fino_check_dtype3(who, dtype));
+    const int per16 = fino_per16(dtype);
+    FINO_TRY(check_rows_dim(who, rows, dim, per16));
+    FINO_CHECK(a && b && out, FINO_ERR_ARG, "%s: null pointer", who);
+    FINO_TRY(fino_check_strides(who, dim, {lda, ldb, ldo}));
+    FINO_TRY(fino_check_aligned16(who, per16, {{a, lda}, {b, ldb}, {out, ldo}}));
     if (rows == 0) return FINO_OK;
     const uint32_t vpr = (uint32_t)(dim / per16), nvec = (uint32_t)(rows * vpr);
-    int64_t grid = (nvec + kThreads - 1) / kThreads;
-    if (grid > 256 * 8) grid = 256 * 8;
+    const unsigned grid = fino_grid_1d(nvec, kFinoGridCap8, false, kThreads);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        residual_kernel<BF16><<<(int)grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
-    else if (dtype == FINO_F16)
-        residual_kernel<F16><<<(int)grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
-    else
-        residual_kernel<F32><<<(int)grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype3<F32>(dtype, [&](auto t) {
+        residual_kernel<decltype(t)><<<grid, kThreads, 0, st>>>(a, lda, b, ldb, out, ldo, vpr, nvec, subtract);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int64_t fino_magcache_workspace_bytes(int64_t rows) {
@@ -687,19 +674,17 @@ extern "C" int64_t fino_magcache_workspace_bytes(int64_t rows) {
 extern "C" int fino_magcache_calibrate(const void* x_out, int64_t ld_out, const void* x_in, int64_t ld_in, const void* r_prev,
                                        int64_t ld_prev, void* r_new, int64_t ld_new, int64_t rows, int64_t dim, int dtype,
                                        double* stats, void* workspace, int64_t workspace_bytes, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16 || dtype == FINO_F32, FINO_ERR_ARG, "fino_magcache_calibrate: dtype %d",
-               dtype);
-    const int per16 = 16 / esize_of(dtype);
+    const char* who = "fino_magcache_calibrate";
+    FINO_TRY(fino_check_dtype3(who, dtype));
+    const int per16 = fino_per16(dtype);
     FINO_CHECK(rows >= 1 && rows < (1LL << 31), FINO_ERR_ARG, "fino_magcache_calibrate: rows=%lld (1 .. 2^31 - 1)",
                (long long)rows);
     FINO_CHECK(dim > 0 && dim % per16 == 0 && dim / per16 < (1LL << 31), FINO_ERR_ARG,
                "fino_magcache_calibrate: dim=%lld must be a multiple of %d", (long long)dim, per16);
     FINO_CHECK(x_out && x_in && r_prev && r_new && stats && workspace, FINO_ERR_ARG, "fino_magcache_calibrate: null pointer");
-    FINO_CHECK(ld_out >= dim && ld_in >= dim && ld_prev >= dim && ld_new >= dim, FINO_ERR_ARG,
-               "fino_magcache_calibrate: a row stride is below dim");
-    FINO_CHECK(rows_ok(x_out, ld_out, dtype) && rows_ok(x_in, ld_in, dtype) && rows_ok(r_prev, ld_prev, dtype) &&
-                   rows_ok(r_new, ld_new, dtype) && fino_aligned16(stats) && fino_aligned16(workspace),
-               FINO_ERR_ARG, "fino_magcache_calibrate: 16-byte alignment required");
+    FINO_TRY(fino_check_strides(who, dim, {ld_out, ld_in, ld_prev, ld_new}));
+    FINO_TRY(fino_check_aligned16(who, per16, {{x_out, ld_out}, {x_in, ld_in}, {r_prev, ld_prev}, {r_new, ld_new}, {stats, 0},
+                                               {workspace, 0}}));
     FINO_CHECK(r_new != r_prev || ld_new == ld_prev, FINO_ERR_ARG,
                "fino_magcache_calibrate: r_new aliases r_prev with another row stride (%lld / %lld)", (long long)ld_new,
                (long long)ld_prev);
@@ -711,109 +696,87 @@ extern "C" int fino_magcache_calibrate(const void* x_out, int64_t ld_out, const 
     const int grid = (int)(nwaves / kMagWavesPerBlock);
     hipStream_t st = (hipStream_t)stream;
     double* partial = (double*)workspace;
-    if (dtype == FINO_BF16)
-        magcache_kernel<BF16><<<grid, kThreads, 0, st>>>(x_out, ld_out, x_in, ld_in, r_prev, ld_prev, r_new, ld_new, rows, vpr,
-                                                         partial);
-    else if (dtype == FINO_F16)
-        magcache_kernel<F16><<<grid, kThreads, 0, st>>>(x_out, ld_out, x_in, ld_in, r_prev, ld_prev, r_new, ld_new, rows, vpr,
-                                                        partial);
-    else
-        magcache_kernel<F32><<<grid, kThreads, 0, st>>>(x_out, ld_out, x_in, ld_in, r_prev, ld_prev, r_new, ld_new, rows, vpr,
-                                                        partial);
-    FINO_LAUNCH_CHECK();
+    fino_dispatch_dtype3<F32>(dtype, [&](auto t) {
+        magcache_kernel<decltype(t)><<<grid, kThreads, 0, st>>>(x_out, ld_out, x_in, ld_in, r_prev, ld_prev, r_new, ld_new, rows,
+                                                                vpr, partial);
+    });
+    FINO_TRY(fino_launch_check(who));
     magcache_finish_kernel<<<1, kThreads, 0, st>>>(partial, nwaves, (double)rows, stats);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_pab_broadcast(const void* x, int64_t ldx, const void* y, int64_t ldy, void* out, int64_t ldo, int64_t rows,
                                   int64_t dim, const float* gate, int64_t mod_stride, const int32_t* sel, int dtype,
                                   void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_pab_broadcast: dtype %d", dtype);
-    FINO_CHECK(rows >= 0 && dim > 0 && dim % 8 == 0 && rows * (dim / 8) < (1LL << 31), FINO_ERR_ARG,
-               "fino_pab_broadcast: rows=%lld dim=%lld", (long long)rows, (long long)dim);
-    FINO_CHECK(x && y && out, FINO_ERR_ARG, "fino_pab_broadcast: null pointer");
-    FINO_CHECK(ldx >= dim && ldy >= dim && ldo >= dim, FINO_ERR_ARG, "fino_pab_broadcast: a row stride is below dim");
-    FINO_CHECK(rows_ok(x, ldx, dtype) && rows_ok(y, ldy, dtype) && rows_ok(out, ldo, dtype) &&
-                   (!gate || (fino_aligned16(gate) && mod_stride % 4 == 0)),
-               FINO_ERR_ARG, "fino_pab_broadcast: 16-byte alignment required");
+    const char* who = "fino_pab_broadcast";
+    FINO_TRY(fino_check_dtype(who, dtype));
+    FINO_TRY(check_rows_dim(who, rows, dim, 8));
+    FINO_CHECK(x && y && out, FINO_ERR_ARG, "%s: null pointer", who);
+    FINO_TRY(fino_check_strides(who, dim, {ldx, ldy, ldo}));
+    const bool gate_ok = !gate || (fino_aligned16(gate) && mod_stride % 4 == 0);      // (a gate row stride counts only with a gate)
+    FINO_TRY(fino_check_aligned16(who, 8, {{x, ldx}, {y, ldy}, {out, ldo}}, gate_ok));
     if (rows == 0) return FINO_OK;
     const uint32_t vpr = (uint32_t)(dim / 8), nvec = (uint32_t)(rows * vpr);
-    int64_t grid = (nvec + kThreads - 1) / kThreads;
-    if (grid > 256 * 8) grid = 256 * 8;
+    const unsigned grid = fino_grid_1d(nvec, kFinoGridCap8, false, kThreads);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        pab_broadcast_kernel<BF16><<<(int)grid, kThreads, 0, st>>>(x, ldx, y, ldy, out, ldo, vpr, nvec, gate, mod_stride, sel);
-    else
-        pab_broadcast_kernel<F16><<<(int)grid, kThreads, 0, st>>>(x, ldx, y, ldy, out, ldo, vpr, nvec, gate, mod_stride, sel);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        pab_broadcast_kernel<decltype(t)><<<grid, kThreads, 0, st>>>(x, ldx, y, ldy, out, ldo, vpr, nvec, gate, mod_stride, sel);
+    });
+    return fino_launch_check(who);
 }
-
-#define FINO_TAYLOR_DISPATCH(KERNEL, ...)                                                          \
-    do {                                                                                           \
-        if (dtype == FINO_BF16 && fdtype == FINO_BF16)                                             \
-            KERNEL<BF16, BF16><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                            \
-        else if (dtype == FINO_BF16 && fdtype == FINO_F16)                                         \
-            KERNEL<BF16, F16><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                             \
-        else if (dtype == FINO_BF16)                                                               \
-            KERNEL<BF16, F32><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                             \
-        else if (fdtype == FINO_BF16)                                                              \
-            KERNEL<F16, BF16><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                             \
-        else if (fdtype == FINO_F16)                                                               \
-            KERNEL<F16, F16><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                              \
-        else                                                                                       \
-            KERNEL<F16, F32><<<grid, kThreads, 0, st>>>(__VA_ARGS__);                              \
-    } while (0)
 
 extern "C" int fino_taylor_update(const void* y, int64_t ldy, void* factors, int64_t plane_stride, int64_t ldf, int64_t rows,
                                   int64_t dim, int n_old, int n_new, int delta, int dtype, int fdtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_taylor_update: dtype %d", dtype);
+    const char* who = "fino_taylor_update";
+    FINO_TRY(fino_check_dtype(who, dtype));
     FINO_CHECK(fdtype == FINO_BF16 || fdtype == FINO_F16 || fdtype == FINO_F32, FINO_ERR_ARG, "fino_taylor_update: factor dtype %d",
                fdtype);
-    FINO_CHECK(rows >= 0 && dim > 0 && dim % 8 == 0 && rows * (dim / 8) < (1LL << 31), FINO_ERR_ARG,
-               "fino_taylor_update: rows=%lld dim=%lld", (long long)rows, (long long)dim);
+    FINO_TRY(check_rows_dim(who, rows, dim, 8));
     FINO_CHECK(n_old >= 0 && n_old <= FINO_TAYLOR_MAX_PLANES && n_new >= 1 && n_new <= FINO_TAYLOR_MAX_PLANES && n_new <= n_old + 1,
                FINO_ERR_ARG, "fino_taylor_update: n_old=%d n_new=%d (n_new in 1 .. %d, at most n_old + 1)", n_old, n_new,
                FINO_TAYLOR_MAX_PLANES);
     FINO_CHECK(delta >= 1 || n_new == 1, FINO_ERR_ARG, "fino_taylor_update: delta=%d must be at least 1", delta);
     FINO_CHECK(y && ldy >= dim, FINO_ERR_ARG, "fino_taylor_update: y missing or its row stride below dim");
-    FINO_CHECK(rows_ok(y, ldy, dtype) && planes_ok(factors, plane_stride, ldf, fdtype, n_new, rows, dim), FINO_ERR_ARG,
+    FINO_CHECK(fino_rows_ok(y, ldy, 8) && planes_ok(factors, plane_stride, ldf, fdtype, n_new, rows, dim), FINO_ERR_ARG,
                "fino_taylor_update: 16-byte aligned rows, row strides of at least dim and planes that do not overlap required");
     if (rows == 0) return FINO_OK;
     const uint32_t vpr = (uint32_t)(dim / 8), nvec = (uint32_t)(rows * vpr);
-    const int grid = taylor_grid(nvec);
+    const unsigned grid = fino_grid_1d(nvec, kFinoGridCap8, false, kThreads);
     hipStream_t st = (hipStream_t)stream;
-    FINO_TAYLOR_DISPATCH(taylor_update_kernel, y, ldy, factors, plane_stride, ldf, vpr, nvec, n_new, (float)delta);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    taylor_dispatch(dtype, fdtype, [&](auto t, auto f) {
+        taylor_update_kernel<decltype(t), decltype(f)><<<grid, kThreads, 0, st>>>(y, ldy, factors, plane_stride, ldf, vpr, nvec,
+                                                                                  n_new, (float)delta);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_taylor_predict(const void* factors, int64_t plane_stride, int64_t ldf, int n, const float* coef, const void* x,
                                    int64_t ldx, void* out, int64_t ldo, int64_t rows, int64_t dim, const float* gate,
                                    int64_t mod_stride, const int32_t* sel, int dtype, int fdtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_taylor_predict: dtype %d", dtype);
+    const char* who = "fino_taylor_predict";
+    FINO_TRY(fino_check_dtype(who, dtype));
     FINO_CHECK(fdtype == FINO_BF16 || fdtype == FINO_F16 || fdtype == FINO_F32, FINO_ERR_ARG, "fino_taylor_predict: factor dtype %d",
                fdtype);
-    FINO_CHECK(rows >= 0 && dim > 0 && dim % 8 == 0 && rows * (dim / 8) < (1LL << 31), FINO_ERR_ARG,
-               "fino_taylor_predict: rows=%lld dim=%lld", (long long)rows, (long long)dim);
+    FINO_TRY(check_rows_dim(who, rows, dim, 8));
     FINO_CHECK(n >= 1 && n <= FINO_TAYLOR_MAX_PLANES && coef, FINO_ERR_ARG, "fino_taylor_predict: n=%d planes (1 .. %d) with n "
                "host coefficients", n, FINO_TAYLOR_MAX_PLANES);
     FINO_CHECK(out && ldo >= dim && (!x || ldx >= dim), FINO_ERR_ARG, "fino_taylor_predict: out missing or a row stride below dim");
     FINO_CHECK(x || !gate, FINO_ERR_ARG, "fino_taylor_predict: a gate needs x");
-    FINO_CHECK(planes_ok(factors, plane_stride, ldf, fdtype, n, rows, dim) && rows_ok(out, ldo, dtype) &&
-                   (!x || rows_ok(x, ldx, dtype)) && (!gate || (fino_aligned16(gate) && mod_stride % 4 == 0)),
+    FINO_CHECK(planes_ok(factors, plane_stride, ldf, fdtype, n, rows, dim) && fino_rows_ok(out, ldo, 8) &&
+                   (!x || fino_rows_ok(x, ldx, 8)) && (!gate || (fino_aligned16(gate) && mod_stride % 4 == 0)),
                FINO_ERR_ARG,
                "fino_taylor_predict: 16-byte aligned rows, row strides of at least dim and planes that do not overlap required");
     if (rows == 0) return FINO_OK;
     TaylorCoef c = {};
     for (int i = 0; i < n; ++i) c.c[i] = coef[i];
     const uint32_t vpr = (uint32_t)(dim / 8), nvec = (uint32_t)(rows * vpr);
-    const int grid = taylor_grid(nvec);
+    const unsigned grid = fino_grid_1d(nvec, kFinoGridCap8, false, kThreads);
     hipStream_t st = (hipStream_t)stream;
-    FINO_TAYLOR_DISPATCH(taylor_predict_kernel, factors, plane_stride, ldf, n, c, x, ldx, out, ldo, vpr, nvec, gate, mod_stride, sel);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    taylor_dispatch(dtype, fdtype, [&](auto t, auto f) {
+        taylor_predict_kernel<decltype(t), decltype(f)><<<grid, kThreads, 0, st>>>(factors, plane_stride, ldf, n, c, x, ldx, out, ldo,
+                                                                                   vpr, nvec, gate, mod_stride, sel);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_fastercache_supported(int64_t planes, int64_t height, int64_t width) {
@@ -823,10 +786,10 @@ extern "C" int fino_fastercache_supported(int64_t planes, int64_t height, int64_
 
 extern "C" int fino_fastercache_delta(const void* uncond, const void* cond, float* d_low, float* d_high, int64_t planes,
                                       int64_t height, int64_t width, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_fastercache_delta: dtype %d", dtype);
-    FINO_CHECK(uncond && cond && d_low && d_high, FINO_ERR_ARG, "fino_fastercache_delta: null pointer");
-    FINO_CHECK(fino_aligned16(uncond) && fino_aligned16(cond) && fino_aligned16(d_low) && fino_aligned16(d_high), FINO_ERR_ARG,
-               "fino_fastercache_delta: 16-byte alignment required");
+    const char* who = "fino_fastercache_delta";
+    FINO_TRY(fino_check_dtype(who, dtype));
+    FINO_CHECK(uncond && cond && d_low && d_high, FINO_ERR_ARG, "%s: null pointer", who);
+    FINO_TRY(fino_check_aligned16(who, 8, {{uncond, 0}, {cond, 0}, {d_low, 0}, {d_high, 0}}));
     FINO_CHECK(fino_fastercache_supported(planes, height, width) && planes < (1LL << 31), FINO_ERR_UNSUPPORTED,
                "fino_fastercache_delta: planes=%lld height=%lld width=%lld (each at least 1, height * width at most %d)",
                (long long)planes, (long long)height, (long long)width, (int)FINO_FASTERCACHE_MAX_PLANE);
@@ -838,39 +801,29 @@ extern "C" int fino_fastercache_delta(const void* uncond, const void* cond, floa
     constexpr int kMaxSmem = 144 * 1024;        // (the largest supported plane: 64 KiB of D, 53 KiB of tables, 17 KiB of bins)
     FINO_CHECK(r + 1 <= kFcMaxRows && smem <= (size_t)kMaxSmem, FINO_ERR_UNSUPPORTED,
                "fino_fastercache_delta: height=%d width=%d needs %zu bytes of LDS", H, W, smem);
-    static FinoPerDeviceOnce once_bf16, once_f16;
     hipStream_t st = (hipStream_t)stream;
     const uint16_t* u = (const uint16_t*)uncond;
     const uint16_t* c = (const uint16_t*)cond;
-    if (dtype == FINO_BF16) {
-        const int rc = fino_max_smem_once(once_bf16, (const void*)fastercache_delta_kernel<BF16>, kMaxSmem, "fino_fastercache_delta");
-        if (rc != FINO_OK) return rc;
-        fastercache_delta_kernel<BF16><<<(int)planes, kFcThreads, smem, st>>>(u, c, d_low, d_high, H, W, r, nbins, disk);
-    } else {
-        const int rc = fino_max_smem_once(once_f16, (const void*)fastercache_delta_kernel<F16>, kMaxSmem, "fino_fastercache_delta");
-        if (rc != FINO_OK) return rc;
-        fastercache_delta_kernel<F16><<<(int)planes, kFcThreads, smem, st>>>(u, c, d_low, d_high, H, W, r, nbins, disk);
-    }
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    return fino_dispatch_dtype(dtype, [&](auto t) -> int {
+        static FinoPerDeviceOnce once;        // one per instantiation: the LDS limit is raised per kernel (and per device)
+        FINO_TRY(fino_max_smem_once(once, (const void*)fastercache_delta_kernel<decltype(t)>, kMaxSmem, who));
+        fastercache_delta_kernel<decltype(t)><<<(int)planes, kFcThreads, smem, st>>>(u, c, d_low, d_high, H, W, r, nbins, disk);
+        return fino_launch_check(who);
+    });
 }
 
 extern "C" int fino_fastercache_apply(const void* cond, const float* d_low, const float* d_high, float a_low, float a_high,
                                       void* out, int64_t n, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_fastercache_apply: dtype %d", dtype);
-    FINO_CHECK(cond && d_low && d_high && out, FINO_ERR_ARG, "fino_fastercache_apply: null pointer");
-    FINO_CHECK(fino_aligned16(cond) && fino_aligned16(d_low) && fino_aligned16(d_high) && fino_aligned16(out), FINO_ERR_ARG,
-               "fino_fastercache_apply: 16-byte alignment required");
+    const char* who = "fino_fastercache_apply";
+    FINO_TRY(fino_check_dtype(who, dtype));
+    FINO_CHECK(cond && d_low && d_high && out, FINO_ERR_ARG, "%s: null pointer", who);
+    FINO_TRY(fino_check_aligned16(who, 8, {{cond, 0}, {d_low, 0}, {d_high, 0}, {out, 0}}));
     FINO_CHECK(n >= 1, FINO_ERR_ARG, "fino_fastercache_apply: n=%lld must be at least 1", (long long)n);
-    int64_t grid = (n / 8 + kThreads - 1) / kThreads;
-    grid = grid < 1 ? 1 : grid > 256 * 8 ? 256 * 8 : grid;
+    const unsigned grid = fino_grid_1d(n / 8, kFinoGridCap8, true, kThreads);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        fastercache_apply_kernel<BF16><<<(int)grid, kThreads, 0, st>>>((const uint16_t*)cond, d_low, d_high, a_low, a_high,
-                                                                       (uint16_t*)out, n);
-    else
-        fastercache_apply_kernel<F16><<<(int)grid, kThreads, 0, st>>>((const uint16_t*)cond, d_low, d_high, a_low, a_high,
-                                                                      (uint16_t*)out, n);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        fastercache_apply_kernel<decltype(t)><<<grid, kThreads, 0, st>>>((const uint16_t*)cond, d_low, d_high, a_low, a_high,
+                                                                         (uint16_t*)out, n);
+    });
+    return fino_launch_check(who);
 }

@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "fino_common.h"
+#include "fino_host.h"
 
 namespace {
 
@@ -185,6 +186,7 @@ __global__ __launch_bounds__(256) void move_rows_kernel(const char* __restrict__
     }
 }
 
+// fino_gather_rows / fino_scatter_rows (`who`); the copy unit and the direction reach the kernel as tags
 int move_rows(const char* who, bool gather, const void* src, int64_t ld_src, const int32_t* idx, int64_t k, int64_t n,
               int64_t row_bytes, void* dst, int64_t ld_dst, void* stream) {
     FINO_CHECK(src && idx && dst, FINO_ERR_ARG, "%s: null pointer", who);
@@ -199,39 +201,32 @@ int move_rows(const char* who, bool gather, const void* src, int64_t ld_src, con
     const bool v16 = row_bytes % 16 == 0 && ld_src % 16 == 0 && ld_dst % 16 == 0 && fino_aligned16(src) && fino_aligned16(dst);
     const unsigned grid = (unsigned)(k < 65536 ? k : 65536);
     hipStream_t st = (hipStream_t)stream;
-    const char* s = (const char*)src;
-    char* d = (char*)dst;
-    if (v16) {
-        const int units = (int)(row_bytes / 16);
-        if (gather) move_rows_kernel<uint4, true><<<grid, 256, 0, st>>>(s, ld_src, idx, k, n, units, d, ld_dst);
-        else move_rows_kernel<uint4, false><<<grid, 256, 0, st>>>(s, ld_src, idx, k, n, units, d, ld_dst);
-    } else {
-        const int units = (int)(row_bytes / 4);
-        if (gather) move_rows_kernel<uint32_t, true><<<grid, 256, 0, st>>>(s, ld_src, idx, k, n, units, d, ld_dst);
-        else move_rows_kernel<uint32_t, false><<<grid, 256, 0, st>>>(s, ld_src, idx, k, n, units, d, ld_dst);
-    }
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    auto launch = [&](auto unit, auto dir) {
+        using U = decltype(unit);
+        move_rows_kernel<U, decltype(dir)::value><<<grid, 256, 0, st>>>((const char*)src, ld_src, idx, k, n,
+                                                                        (int)(row_bytes / (int64_t)sizeof(U)), (char*)dst, ld_dst);
+    };
+    auto by_direction = [&](auto unit) { gather ? launch(unit, std::true_type{}) : launch(unit, std::false_type{}); };
+    v16 ? by_direction(uint4{}) : by_direction(uint32_t{});
+    return fino_launch_check(who);
 }
 
 }  // namespace
 
 extern "C" int fino_token_score(const void* po, int64_t rows, int cols, int64_t ld, int batch, const int32_t* counters,
                                 float starvation_scale, const uint8_t* eligible, float* score_out, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_token_score: dtype %d", dtype);
-    FINO_CHECK(po && score_out, FINO_ERR_ARG, "fino_token_score: null pointer");
+    const char* who = "fino_token_score";
+    FINO_TRY(fino_check_dtype(who, dtype));
+    FINO_CHECK(po && score_out, FINO_ERR_ARG, "%s: null pointer", who);
     FINO_CHECK(rows >= 1 && rows < (1LL << 31) && cols >= 1 && ld >= cols && batch >= 1 && batch <= 64, FINO_ERR_ARG,
                "fino_token_score: rows=%lld cols=%d ld=%lld batch=%d", (long long)rows, cols, (long long)ld, batch);
     const dim3 grid((unsigned)((rows + kScoreWaves - 1) / kScoreWaves)), block(kScoreWaves * 64);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        token_score_kernel<BF16><<<grid, block, 0, st>>>((const uint16_t*)po, rows, cols, ld, batch, counters, starvation_scale,
-                                                         eligible, score_out);
-    else
-        token_score_kernel<F16><<<grid, block, 0, st>>>((const uint16_t*)po, rows, cols, ld, batch, counters, starvation_scale,
-                                                        eligible, score_out);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto t) {
+        token_score_kernel<decltype(t)><<<grid, block, 0, st>>>((const uint16_t*)po, rows, cols, ld, batch, counters,
+                                                                starvation_scale, eligible, score_out);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_token_select(const float* score, int64_t n, int64_t k, int32_t* idx_out, int32_t* counters, void* stream) {
@@ -241,8 +236,7 @@ extern "C" int fino_token_select(const float* score, int64_t n, int64_t k, int32
     FINO_CHECK(n <= kSelMaxN, FINO_ERR_UNSUPPORTED, "fino_token_select: n=%lld above %d (one workgroup selects)", (long long)n,
                kSelMaxN);
     token_select_kernel<<<1, kSelThreads, 0, (hipStream_t)stream>>>(score, (int)n, (int)k, idx_out, counters);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    return fino_launch_check("fino_token_select");
 }
 
 extern "C" int fino_gather_rows(const void* src, int64_t ld_src, int64_t n, const int32_t* idx, int64_t k, int64_t row_bytes,

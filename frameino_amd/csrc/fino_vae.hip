@@ -3,6 +3,7 @@
 // implicit GEMM over 128-byte channel chunks, see fino_gemm.hip CONV).  Padding channels stay exactly zero through
 // every kernel here (gamma/bias pads are zero).
 #include "fino_common.h"
+#include "fino_host.h"
 
 namespace {
 
@@ -305,70 +306,58 @@ __global__ __launch_bounds__(256) void vae_patchify_kernel(const float* __restri
     }
 }
 
-inline int grid_1d(int64_t total, int block = 256) {
-    int64_t g = (total + block - 1) / block;
-    const int64_t cap = 256 * 16;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+// lanes per row of rmsnorm_silu_cl_kernel: launch(tag) for 64, 32, 16 or 8 (rows that are not a power-of-two number of
+// 16-byte chunks: one row per wave)
+template <typename F>
+void dispatch_lanes(int lpr, F&& launch) {
+    if (lpr == 32) launch(std::integral_constant<int, 32>{});
+    else if (lpr == 16) launch(std::integral_constant<int, 16>{});
+    else if (lpr == 8) launch(std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 64>{});
 }
 
 }  // namespace
 
-// PTR(type, p): the pointer argument cast to the storage type of the dispatched dtype (uint16_t or float)
-#define VAE_DISPATCH3(KERNEL, GRID, ARGS_BF16, ARGS_F16, ARGS_F32)                              \
-    do {                                                                                        \
-        hipStream_t st_ = (hipStream_t)stream;                                                  \
-        if (dtype == FINO_BF16) KERNEL<BF16><<<(GRID), 256, 0, st_>>> ARGS_BF16;                \
-        else if (dtype == FINO_F16) KERNEL<F16><<<(GRID), 256, 0, st_>>> ARGS_F16;              \
-        else KERNEL<F32><<<(GRID), 256, 0, st_>>> ARGS_F32;                                     \
-        FINO_LAUNCH_CHECK();                                                                    \
-    } while (0)
-#define VAE_CHECK_DT(fn) FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, fn ": dtype %d", dtype)
-#define VAE_CHECK_DT3(fn) \
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16 || dtype == FINO_F32, FINO_ERR_ARG, fn ": dtype %d", dtype)
-
 extern "C" int fino_rmsnorm_silu_cl(const void* x, void* y, int64_t rows, int c_valid, int c_pad, const float* gamma,
                                     int silu, int dtype, void* stream) {
-    VAE_CHECK_DT("fino_rmsnorm_silu_cl");
+    const char* who = "fino_rmsnorm_silu_cl";
+    FINO_TRY(fino_check_dtype(who, dtype));
     FINO_CHECK(x && y && gamma && rows >= 0 && c_valid > 0 && c_pad >= c_valid && c_pad % 8 == 0, FINO_ERR_ARG,
                "fino_rmsnorm_silu_cl: bad arguments (c_valid=%d c_pad=%d)", c_valid, c_pad);
-    FINO_CHECK(fino_aligned16(x) && fino_aligned16(y) && fino_aligned16(gamma), FINO_ERR_ARG,
-               "fino_rmsnorm_silu_cl: 16-byte alignment required");
+    FINO_TRY(fino_check_aligned16(who, 8, {{x, 0}, {y, 0}, {gamma, 0}}));
     if (rows == 0) return FINO_OK;
-    hipStream_t st_ = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)stream;
     const int lpr = c_pad / 8 >= 64 ? 64 : c_pad / 8;
     const float sc = sqrtf((float)c_valid);
-#define RMS_LAUNCH(L_)                                                                                              \
-    {                                                                                                               \
-        const unsigned grid = (unsigned)((rows + 4 * (64 / L_) - 1) / (4 * (64 / L_)));                             \
-        if (dtype == FINO_BF16)                                                                                     \
-            rmsnorm_silu_cl_kernel<BF16, L_><<<grid, 256, 0, st_>>>((const uint16_t*)x, (uint16_t*)y, rows, c_pad, sc, gamma, silu); \
-        else                                                                                                        \
-            rmsnorm_silu_cl_kernel<F16, L_><<<grid, 256, 0, st_>>>((const uint16_t*)x, (uint16_t*)y, rows, c_pad, sc, gamma, silu);  \
-    }
-    if (lpr == 64) RMS_LAUNCH(64)
-    else if (lpr == 32) RMS_LAUNCH(32)
-    else if (lpr == 16) RMS_LAUNCH(16)
-    else if (lpr == 8) RMS_LAUNCH(8)
-    else RMS_LAUNCH(64)                    /* rows that are not a power-of-two number of chunks: one row per wave */
-#undef RMS_LAUNCH
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    dispatch_lanes(lpr, [&](auto lanes) {
+        constexpr int L = decltype(lanes)::value;
+        const unsigned grid = (unsigned)((rows + 4 * (64 / L) - 1) / (4 * (64 / L)));
+        fino_dispatch_dtype(dtype, [&](auto t) {
+            rmsnorm_silu_cl_kernel<decltype(t), L><<<grid, 256, 0, st>>>((const uint16_t*)x, (uint16_t*)y, rows, c_pad, sc, gamma,
+                                                                         silu);
+        });
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_softmax_rows(void* s, int64_t rows, int n, int64_t ld, float scale, int dtype, void* stream) {
-    VAE_CHECK_DT3("fino_softmax_rows");
+    const char* who = "fino_softmax_rows";
+    FINO_TRY(fino_check_dtype3(who, dtype));
     FINO_CHECK(s && rows >= 0 && n > 0 && ld >= n, FINO_ERR_ARG, "fino_softmax_rows: bad arguments");
     if (rows == 0) return FINO_OK;
     const unsigned grid = (unsigned)((rows + 3) / 4);
-    VAE_DISPATCH3(softmax_rows_kernel, grid, ((uint16_t*)s, rows, n, ld, scale), ((uint16_t*)s, rows, n, ld, scale),
-                  ((float*)s, rows, n, ld, scale));
-    return FINO_OK;
+    fino_dispatch_dtype3<F32>(dtype, [&](auto t) {
+        using E = typename Elem<decltype(t)>::type;
+        softmax_rows_kernel<decltype(t)><<<grid, 256, 0, (hipStream_t)stream>>>((E*)s, rows, n, ld, scale);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_dup_up3d_add(const void* main_in, const void* x, void* out, int t_in, int h_in, int w_in, int c_in,
                                  int c_in_pad, int c_out, int c_out_pad, int factor_t, int factor_s, int dtype,
                                  void* stream) {
-    VAE_CHECK_DT3("fino_dup_up3d_add");
+    const char* who = "fino_dup_up3d_add";
+    FINO_TRY(fino_check_dtype3(who, dtype));
     FINO_CHECK(main_in && x && out && t_in > 0 && factor_t >= 1 && factor_s >= 1, FINO_ERR_ARG,
                "fino_dup_up3d_add: bad arguments");
     const int factor = factor_t * factor_s * factor_s;
@@ -376,17 +365,20 @@ extern "C" int fino_dup_up3d_add(const void* main_in, const void* x, void* out, 
     const int t_out = 1 + (t_in - 1) * factor_t;
     FINO_CHECK(c_out_pad % 8 == 0 && c_in_pad % 8 == 0, FINO_ERR_ARG, "fino_dup_up3d_add: padded widths %% 8");
     const int64_t total = (int64_t)t_out * h_in * factor_s * w_in * factor_s * (c_out_pad / 8);
-#define DUP_ARGS(TY) ((const TY*)main_in, (const TY*)x, (TY*)out, t_out, h_in * factor_s, w_in * factor_s, c_out, c_out_pad, h_in, \
-                      w_in, c_in_pad, factor_t, factor_s, c_out * factor / c_in)
-    VAE_DISPATCH3(dup_up3d_add_kernel, grid_1d(total), DUP_ARGS(uint16_t), DUP_ARGS(uint16_t), DUP_ARGS(float));
-#undef DUP_ARGS
-    return FINO_OK;
+    fino_dispatch_dtype3<F32>(dtype, [&](auto t) {
+        using E = typename Elem<decltype(t)>::type;
+        dup_up3d_add_kernel<decltype(t)><<<fino_grid_1d(total, kFinoGridCap16, true), 256, 0, (hipStream_t)stream>>>(
+            (const E*)main_in, (const E*)x, (E*)out, t_out, h_in * factor_s, w_in * factor_s, c_out, c_out_pad, h_in, w_in,
+            c_in_pad, factor_t, factor_s, c_out * factor / c_in);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_avg_down3d_add(const void* main_in, const void* x, void* out, int t_in, int h_in, int w_in,
                                    int c_in, int c_in_pad, int c_out, int c_out_pad, int factor_t, int factor_s,
                                    int dtype, void* stream) {
-    VAE_CHECK_DT3("fino_avg_down3d_add");
+    const char* who = "fino_avg_down3d_add";
+    FINO_TRY(fino_check_dtype3(who, dtype));
     FINO_CHECK(main_in && x && out && t_in > 0 && factor_t >= 1 && factor_s >= 1, FINO_ERR_ARG,
                "fino_avg_down3d_add: bad arguments");
     const int factor = factor_t * factor_s * factor_s;
@@ -395,33 +387,43 @@ extern "C" int fino_avg_down3d_add(const void* main_in, const void* x, void* out
     const int pad_t = (factor_t - t_in % factor_t) % factor_t;
     const int t_out = (t_in + pad_t) / factor_t;
     const int64_t total = (int64_t)t_out * (h_in / factor_s) * (w_in / factor_s) * c_out_pad;
-#define AVG_ARGS(TY) ((const TY*)main_in, (const TY*)x, (TY*)out, t_out, h_in / factor_s, w_in / factor_s, c_out, c_out_pad, t_in, \
-                      h_in, w_in, c_in_pad, factor_t, factor_s, c_in * factor / c_out, pad_t)
-    VAE_DISPATCH3(avg_down3d_add_kernel, grid_1d(total), AVG_ARGS(uint16_t), AVG_ARGS(uint16_t), AVG_ARGS(float));
-#undef AVG_ARGS
-    return FINO_OK;
+    fino_dispatch_dtype3<F32>(dtype, [&](auto t) {
+        using E = typename Elem<decltype(t)>::type;
+        avg_down3d_add_kernel<decltype(t)><<<fino_grid_1d(total, kFinoGridCap16, true), 256, 0, (hipStream_t)stream>>>(
+            (const E*)main_in, (const E*)x, (E*)out, t_out, h_in / factor_s, w_in / factor_s, c_out, c_out_pad, t_in, h_in, w_in,
+            c_in_pad, factor_t, factor_s, c_in * factor / c_out, pad_t);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_vae_unpatchify_clamp(const void* y, float* out, int t, int h, int w, int c_pad, int channels,
                                          int patch, int dtype, void* stream) {
-    VAE_CHECK_DT3("fino_vae_unpatchify_clamp");
+    const char* who = "fino_vae_unpatchify_clamp";
+    FINO_TRY(fino_check_dtype3(who, dtype));
     FINO_CHECK(y && out && t > 0 && h > 0 && w > 0 && patch >= 1 && channels * patch * patch <= c_pad, FINO_ERR_ARG,
                "fino_vae_unpatchify_clamp: bad arguments");
     const int64_t total = (int64_t)channels * t * h * patch * w * patch;
-    VAE_DISPATCH3(vae_unpatchify_clamp_kernel, grid_1d(total), ((const uint16_t*)y, out, t, h, w, c_pad, channels, patch),
-                  ((const uint16_t*)y, out, t, h, w, c_pad, channels, patch), ((const float*)y, out, t, h, w, c_pad, channels, patch));
-    return FINO_OK;
+    fino_dispatch_dtype3<F32>(dtype, [&](auto t_) {
+        using E = typename Elem<decltype(t_)>::type;
+        vae_unpatchify_clamp_kernel<decltype(t_)><<<fino_grid_1d(total, kFinoGridCap16, true), 256, 0, (hipStream_t)stream>>>(
+            (const E*)y, out, t, h, w, c_pad, channels, patch);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_vae_patchify(const float* x, void* y, int t, int h, int w, int c_pad, int channels, int patch,
                                  int dtype, void* stream) {
-    VAE_CHECK_DT3("fino_vae_patchify");
+    const char* who = "fino_vae_patchify";
+    FINO_TRY(fino_check_dtype3(who, dtype));
     FINO_CHECK(x && y && t > 0 && h > 0 && w > 0 && patch >= 1 && channels * patch * patch <= c_pad, FINO_ERR_ARG,
                "fino_vae_patchify: bad arguments");
     const int64_t total = (int64_t)t * h * w * c_pad;
-    VAE_DISPATCH3(vae_patchify_kernel, grid_1d(total), (x, (uint16_t*)y, t, h, w, c_pad, channels, patch),
-                  (x, (uint16_t*)y, t, h, w, c_pad, channels, patch), (x, (float*)y, t, h, w, c_pad, channels, patch));
-    return FINO_OK;
+    fino_dispatch_dtype3<F32>(dtype, [&](auto t_) {
+        using E = typename Elem<decltype(t_)>::type;
+        vae_patchify_kernel<decltype(t_)><<<fino_grid_1d(total, kFinoGridCap16, true), 256, 0, (hipStream_t)stream>>>(
+            x, (E*)y, t, h, w, c_pad, channels, patch);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_split_bf16(const float* x, void* out, int64_t rows, int cols, int64_t ldx, int64_t ldo, int nseg,
@@ -432,24 +434,22 @@ extern "C" int fino_split_bf16(const float* x, void* out, int64_t rows, int cols
                "fino_split_bf16: nseg=%d (1 .. 6), ldo must cover nseg * cols", nseg);
     for (int s_ = 0; s_ < nseg; ++s_)
         FINO_CHECK(((planes_packed >> (2 * s_)) & 3u) <= 2u, FINO_ERR_ARG, "fino_split_bf16: plane index 3 in segment %d", s_);
-    FINO_CHECK(fino_aligned16(x) && fino_aligned16(out), FINO_ERR_ARG, "fino_split_bf16: 16-byte alignment required");
+    FINO_TRY(fino_check_aligned16("fino_split_bf16", 8, {{x, 0}, {out, 0}}));
     if (rows == 0) return FINO_OK;
-    split_bf16_kernel<<<grid_1d(rows * (cols / 8)), 256, 0, (hipStream_t)stream>>>(x, (uint16_t*)out, rows, cols, ldx, ldo, nseg,
-                                                                                   planes_packed);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    split_bf16_kernel<<<fino_grid_1d(rows * (cols / 8), kFinoGridCap16, true), 256, 0, (hipStream_t)stream>>>(
+        x, (uint16_t*)out, rows, cols, ldx, ldo, nseg, planes_packed);
+    return fino_launch_check("fino_split_bf16");
 }
 
 extern "C" int fino_rmsnorm_silu_cl_f32(const float* x, void* y, int64_t rows, int c_valid, int c_pad, const float* gamma,
                                         int silu, int nseg, unsigned planes_packed, void* stream) {
+    const char* who = "fino_rmsnorm_silu_cl_f32";
     FINO_CHECK(x && y && gamma && rows >= 0 && c_valid > 0 && c_pad >= c_valid && c_pad % 8 == 0, FINO_ERR_ARG,
                "fino_rmsnorm_silu_cl_f32: bad arguments (c_valid=%d c_pad=%d)", c_valid, c_pad);
     FINO_CHECK(nseg >= 0 && nseg <= 6, FINO_ERR_ARG, "fino_rmsnorm_silu_cl_f32: nseg=%d (0 = fp32 output, 1 .. 6 planes)", nseg);
-    FINO_CHECK(fino_aligned16(x) && fino_aligned16(y) && fino_aligned16(gamma), FINO_ERR_ARG,
-               "fino_rmsnorm_silu_cl_f32: 16-byte alignment required");
+    FINO_TRY(fino_check_aligned16(who, 8, {{x, 0}, {y, 0}, {gamma, 0}}));
     if (rows == 0) return FINO_OK;
     rmsnorm_silu_cl_f32_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(
         x, (float*)y, (uint16_t*)y, rows, c_pad, sqrtf((float)c_valid), gamma, silu, nseg, planes_packed);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    return fino_launch_check(who);
 }

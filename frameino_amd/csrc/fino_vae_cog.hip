@@ -11,6 +11,7 @@
 //   through the nearest-neighbour index map of F.interpolate (first frame of an odd-length batch mapped separately),
 //   instead of interpolating the latent to full resolution and running two 1x1x1 convolutions there.
 #include "fino_common.h"
+#include "fino_host.h"
 
 namespace {
 
@@ -188,11 +189,6 @@ __global__ __launch_bounds__(256) void blend_tiles_kernel(const uint16_t* __rest
     }
 }
 
-inline unsigned grid_1d(int64_t total, int block = 256) {
-    int64_t g = (total + block - 1) / block;
-    return (unsigned)(g > 262144 ? 262144 : (g < 1 ? 1 : g));
-}
-
 }  // namespace
 
 extern "C" int64_t fino_groupnorm_workspace_bytes(int c_pad) {
@@ -203,8 +199,9 @@ extern "C" int fino_groupnorm_cl(const void* x, void* y, int t, int h, int w, in
                                  const float* gamma, const float* beta, float eps, const void* mod_scale,
                                  const void* mod_shift, int tz, int hz, int wz, int silu, void* workspace,
                                  int64_t workspace_bytes, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_groupnorm_cl: dtype %d", dtype);
-    FINO_CHECK(x && y && gamma && beta && workspace, FINO_ERR_ARG, "fino_groupnorm_cl: null pointer");
+    const char* who = "fino_groupnorm_cl";
+    FINO_TRY(fino_check_dtype(who, dtype));
+    FINO_CHECK(x && y && gamma && beta && workspace, FINO_ERR_ARG, "%s: null pointer", who);
     FINO_CHECK(t > 0 && h > 0 && w > 0 && channels > 0 && c_pad >= channels && c_pad % 64 == 0 && c_pad <= 2048 &&
                    (c_pad & (c_pad - 1)) == 0 && groups > 0 && channels % groups == 0,
                FINO_ERR_ARG, "fino_groupnorm_cl: need c_pad a power of two in [64, 2048] and groups | channels");
@@ -220,45 +217,38 @@ extern "C" int fino_groupnorm_cl(const void* x, void* y, int t, int h, int w, in
     float* ab = partial + (int64_t)kGnBlocks * 2 * c_pad;
     const int nblocks = rows < kGnBlocks ? (int)rows : kGnBlocks;
     const int64_t total = rows * (c_pad / 8);
-    if (dtype == FINO_BF16) {
-        gn_partial_kernel<BF16><<<nblocks, 256, 0, st>>>((const uint16_t*)x, partial, rows, c_pad);
-        FINO_LAUNCH_CHECK();
+    return fino_dispatch_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        gn_partial_kernel<T><<<nblocks, 256, 0, st>>>((const uint16_t*)x, partial, rows, c_pad);
+        FINO_TRY(fino_launch_check(who));
         gn_finalize_kernel<<<1, 1024, 0, st>>>(partial, ab, gamma, beta, nblocks, c_pad, channels, groups, (double)rows, eps);
-        FINO_LAUNCH_CHECK();
-        gn_apply_kernel<BF16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)x, (uint16_t*)y, ab,
-                                                               (const uint16_t*)mod_scale, (const uint16_t*)mod_shift, t, h,
-                                                               w, c_pad, tz, hz, wz, silu);
-    } else {
-        gn_partial_kernel<F16><<<nblocks, 256, 0, st>>>((const uint16_t*)x, partial, rows, c_pad);
-        FINO_LAUNCH_CHECK();
-        gn_finalize_kernel<<<1, 1024, 0, st>>>(partial, ab, gamma, beta, nblocks, c_pad, channels, groups, (double)rows, eps);
-        FINO_LAUNCH_CHECK();
-        gn_apply_kernel<F16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)x, (uint16_t*)y, ab,
-                                                              (const uint16_t*)mod_scale, (const uint16_t*)mod_shift, t, h,
-                                                              w, c_pad, tz, hz, wz, silu);
-    }
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+        FINO_TRY(fino_launch_check(who));
+        gn_apply_kernel<T><<<fino_grid_1d(total, kFinoGridCapWide, true), 256, 0, st>>>(
+            (const uint16_t*)x, (uint16_t*)y, ab, (const uint16_t*)mod_scale, (const uint16_t*)mod_shift, t, h, w, c_pad, tz, hz,
+            wz, silu);
+        return fino_launch_check(who);
+    });
 }
 
 extern "C" int fino_avg_pool_time2(const void* x, void* y, int t_in, int h, int w, int c_pad, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_avg_pool_time2: dtype %d", dtype);
+    const char* who = "fino_avg_pool_time2";
+    FINO_TRY(fino_check_dtype(who, dtype));
     FINO_CHECK(x && y && t_in > 1 && h > 0 && w > 0 && c_pad > 0 && c_pad % 8 == 0, FINO_ERR_ARG,
                "fino_avg_pool_time2: bad arguments (t_in must be > 1)");
     const int64_t fc = (int64_t)h * w * (c_pad / 8);
     const int t_out = (t_in & 1) + (t_in - (t_in & 1)) / 2;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        avg_pool_time2_kernel<BF16><<<grid_1d(t_out * fc), 256, 0, st>>>((const uint16_t*)x, (uint16_t*)y, t_in, fc);
-    else
-        avg_pool_time2_kernel<F16><<<grid_1d(t_out * fc), 256, 0, st>>>((const uint16_t*)x, (uint16_t*)y, t_in, fc);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto tag) {
+        avg_pool_time2_kernel<decltype(tag)><<<fino_grid_1d(t_out * fc, kFinoGridCapWide, true), 256, 0, st>>>(
+            (const uint16_t*)x, (uint16_t*)y, t_in, fc);
+    });
+    return fino_launch_check(who);
 }
 
 extern "C" int fino_vae_blend_tiles(const void* a, void* b, int t, int h_a, int w_a, int h_b, int w_b, int c_pad, int extent,
                                     int axis, int dtype, void* stream) {
-    FINO_CHECK(dtype == FINO_BF16 || dtype == FINO_F16, FINO_ERR_ARG, "fino_vae_blend_tiles: dtype %d", dtype);
+    const char* who = "fino_vae_blend_tiles";
+    FINO_TRY(fino_check_dtype(who, dtype));
     FINO_CHECK(a && b && t > 0 && h_a > 0 && w_a > 0 && h_b > 0 && w_b > 0 && c_pad > 0 && c_pad % 8 == 0 &&
                    (axis == 0 || axis == 1) && fino_aligned16(a) && fino_aligned16(b),
                FINO_ERR_ARG, "fino_vae_blend_tiles: bad arguments");
@@ -271,12 +261,9 @@ extern "C" int fino_vae_blend_tiles(const void* a, void* b, int t, int h_a, int 
     if (ext <= 0) return FINO_OK;
     const int64_t total = (int64_t)t * (axis == 0 ? ext : h_b) * (axis == 0 ? w_b : ext) * (c_pad / 8);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == FINO_BF16)
-        blend_tiles_kernel<BF16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)a, (uint16_t*)b, t, h_a, w_a, h_b, w_b,
-                                                                 c_pad / 8, ext, axis);
-    else
-        blend_tiles_kernel<F16><<<grid_1d(total), 256, 0, st>>>((const uint16_t*)a, (uint16_t*)b, t, h_a, w_a, h_b, w_b, c_pad / 8,
-                                                                ext, axis);
-    FINO_LAUNCH_CHECK();
-    return FINO_OK;
+    fino_dispatch_dtype(dtype, [&](auto tag) {
+        blend_tiles_kernel<decltype(tag)><<<fino_grid_1d(total, kFinoGridCapWide, true), 256, 0, st>>>(
+            (const uint16_t*)a, (uint16_t*)b, t, h_a, w_a, h_b, w_b, c_pad / 8, ext, axis);
+    });
+    return fino_launch_check(who);
 }
