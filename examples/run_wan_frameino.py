@@ -95,6 +95,20 @@ def main():
                     help="run the clip with MagCache in calibrate mode (every step computes; one extra pass over the residual per "
                          "step and context) and write the measured curves, per cache context, to OUT.json.  Curves depend on "
                          "the weights, the step count and the scheduler.  Not together with the other cache flags")
+    ap.add_argument("--teacache", default=None, metavar="FILE",
+                    help="TeaCache (approximate; eager loop; quality on real checkpoints unmeasured) with the per-context "
+                         "polynomials of FILE (written by --teacache-calibrate): before block 0 a step measures how far its "
+                         "timestep-modulated input has moved since the previous step, and while the accumulated polynomial of that "
+                         "distance stays below the threshold it re-uses the block stack's residual.  Not together with the other "
+                         "cache flags")
+    ap.add_argument("--teacache-threshold", type=float, default=0.2, metavar="X", help="with --teacache: the accumulated bound")
+    ap.add_argument("--teacache-max-skip", type=int, default=None, metavar="K",
+                    help="with --teacache: at most K consecutive skipped steps (default: no cap)")
+    ap.add_argument("--teacache-calibrate", default=None, metavar="OUT.json",
+                    help="run the clip with TeaCache in calibrate mode (every step computes; one probe of block 0's input and one "
+                         "of the output rows per step and context), fit a quartic per cache context and write it, with the "
+                         "measurements, to OUT.json.  The polynomial depends on the weights.  Not together with the other cache "
+                         "flags")
     ap.add_argument("--ras", type=float, default=None, metavar="RATIO",
                     help="region-adaptive sampling (approximate; eager loop; quality on real checkpoints unmeasured): on most steps "
                          "only the fraction RATIO of the tokens whose prediction is moving most, e.g. 0.5, runs through the DiT; "
@@ -164,6 +178,15 @@ def main():
             ap.error("--magcache FILE applies curves, --magcache-calibrate OUT.json measures them: one at a time")
         if any(v is not None for v in (a.first_block_cache, a.pab, a.taylorseer, a.fastercache)):
             ap.error("--magcache / --magcache-calibrate: not together with --first-block-cache, --pab, --taylorseer or --fastercache")
+    if a.teacache is not None or a.teacache_calibrate is not None:
+        if a.teacache is not None and a.teacache_calibrate is not None:
+            ap.error("--teacache FILE applies polynomials, --teacache-calibrate OUT.json measures them: one at a time")
+        if any(v is not None for v in (a.first_block_cache, a.pab, a.taylorseer, a.fastercache, a.magcache, a.magcache_calibrate,
+                                       a.ras)):
+            ap.error("--teacache / --teacache-calibrate: not together with --first-block-cache, --pab, --taylorseer, --fastercache, "
+                     "--magcache or --ras")
+    elif a.teacache_threshold != 0.2 or a.teacache_max_skip is not None:
+        ap.error("--teacache-threshold / --teacache-max-skip need --teacache FILE")
 
     if a.ras is None and (a.ras_trajectory_mask or a.ras_interval != 5 or a.ras_warmup != 4):
         ap.error("--ras-interval / --ras-warmup / --ras-trajectory-mask need --ras RATIO")
@@ -257,6 +280,11 @@ def main():
             threshold=a.magcache_threshold, max_skip_steps=a.magcache_max_skip, retention_ratio=a.magcache_retention,
             num_inference_steps=a.steps, calibrate=a.magcache is None,
             mag_ratios=None if a.magcache is None else load_mag_ratios(a.magcache)))
+    if a.teacache is not None or a.teacache_calibrate is not None:
+        from frameino_amd.step_cache import TeaCacheConfig, load_teacache
+        transformer.enable_cache(TeaCacheConfig(
+            rel_l1_thresh=a.teacache_threshold, max_skip_steps=a.teacache_max_skip, num_inference_steps=a.steps,
+            calibrate=a.teacache is None, coefficients=None if a.teacache is None else load_teacache(a.teacache)))
     if a.mxfp6:                                    # after the LoRA merge: the merged weights are what is quantised
         transformer.enable_mxfp6_linears(rotate=a.mxfp6_rotate)
     if a.fp8_attention:
@@ -346,6 +374,18 @@ def main():
     elif a.magcache is not None:
         log = transformer.cache_log
         print(f"magcache: {sum(not e[2] for e in log)} of {len(log)} forwards re-used the stack's residual")
+    if a.teacache_calibrate is not None:           # filed when each context finished its steps: one host read per context
+        from frameino_amd.step_cache import fit_teacache_coefficients, save_teacache
+        cal = transformer.teacache_calibration
+        coef = fit_teacache_coefficients(cal, degree=4)
+        save_teacache(a.teacache_calibrate, coef, cal)
+        for ctx, entry in cal.items():
+            ds = [v for v in entry["rel_l1_in"] if v is not None]
+            print(f"teacache calibration [{ctx}]: {len(entry['rel_l1_in'])} steps, input distances in [{min(ds):.4f}, {max(ds):.4f}], "
+                  f"coefficients {[round(c, 6) for c in coef[ctx]]} -> {a.teacache_calibrate}")
+    elif a.teacache is not None:
+        log = transformer.cache_log
+        print(f"teacache: {sum(not e[2] for e in log)} of {len(log)} forwards re-used the stack's residual")
     if a.ras is not None:
         log = [e for e in transformer.cache_log if e[0] == "cond"]
         print(f"ras: {sum(not e[2] for e in log)} of {len(log)} steps ran {min(e[3] for e in log)} of {max(e[3] for e in log)} tokens")

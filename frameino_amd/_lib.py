@@ -154,6 +154,9 @@ SIGNATURES = {
     "fino_magcache_workspace_bytes": [c_i64],
     "fino_magcache_calibrate": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p,
                                 c_void_p, c_i64, c_void_p],
+    "fino_teacache_workspace_bytes": [c_i64],
+    "fino_teacache_probe": [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_int,
+                            c_int, c_void_p, c_void_p, c_i64, c_void_p],
     "fino_pab_broadcast": [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_int,
                            c_void_p],
     "fino_taylor_update": [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p],
@@ -181,7 +184,7 @@ _RESTYPES = {"fino_last_error": ctypes.c_char_p, "fino_attn_workspace_bytes": c_
              "fino_attn_fp8_smoothed_kv_bytes": c_i64, "fino_attn_fp8_smooth_q_kv_bytes": c_i64, "fino_mxfp6_bytes": c_i64,
              "fino_mxfp6_scale_bytes": c_i64, "fino_attn_tile_plan_bytes": c_i64,
              "fino_attn_tile_plan_gated_bytes": c_i64, "fino_magcache_workspace_bytes": c_i64,
-             "fino_guider_workspace_bytes": c_i64}
+             "fino_teacache_workspace_bytes": c_i64, "fino_guider_workspace_bytes": c_i64}
 
 
 # the FINO_VERSION this table (argument lists, tune-knob meanings) was written for: a stale library found through

@@ -9,6 +9,7 @@
 
 #include "fino_common.h"
 #include "fino_host.h"
+#include "fino_row_ln.h"
 #include "fino_sampler_step.h"
 #include "fino_gemm_common.h"      // mx_quant8 / mx_scale_index: the MXFP8 activation layout fino_gemm_mxfp8 consumes
 
@@ -34,51 +35,7 @@ struct RowRegs {
     }
 #define EW_STORE(PTR_, VAL_) (*reinterpret_cast<uint4*>(PTR_) = (VAL_))
 
-template <typename T, int NP, bool NT = false>
-__device__ __forceinline__ void load_row(const uint16_t* __restrict__ p, int dim, int lane, float (&v)[NP][8]) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int c = (i * 64 + lane) * 8;
-        if (c < dim) {
-            uint4 u;
-            if constexpr (NT) {
-                const u32x4_t t4 = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p + c));
-                u = make_uint4(t4[0], t4[1], t4[2], t4[3]);
-            } else {
-                u = *reinterpret_cast<const uint4*>(p + c);
-            }
-            unpack8<T>(u, v[i]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
-        }
-    }
-}
-
-template <int NP>
-__device__ __forceinline__ void ln_stats(const float (&v)[NP][8], int dim, int lane, float eps, float& mean,
-                                         float& rstd) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NP; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s += v[i][j];
-    mean = wave_sum(s) / (float)dim;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int c = (i * 64 + lane) * 8;
-        if (c < dim) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float d = v[i][j] - mean;
-                q += d * d;
-            }
-        }
-    }
-    const float var = wave_sum(q) / (float)dim;
-    rstd = 1.0f / sqrtf(var + eps);
-}
+// load_row / ln_stats / ln_adaln_value: fino_row_ln.h (shared with the TeaCache probe, which writes MODE 0's bits)
 
 // ---------------------------------------------------------------------------------------------------------
 // MODE 0: y = T(LN(x)*(1+scale)+shift)                        (Wan AdaLN-zero: fp32 math, one rounding)
@@ -116,11 +73,10 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void ln_modulate_kernel(
         if (MODE != 1) { ld8(p_scale + moff + c, sc); ld8(p_shift + moff + c, sh); }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float n = (v[i][j] - mean) * rstd;
             if (MODE == 0) {
-                o[j] = n * (1.0f + sc[j]) + sh[j];
+                o[j] = ln_adaln_value(v[i][j], mean, rstd, sc[j], sh[j]);
             } else {
-                float t = n;
+                float t = (v[i][j] - mean) * rstd;
                 if (p_w) t = t * w[j];
                 if (p_b) t = t + b[j];
                 if (MODE == 2) t = round_to<T>(round_to<T>(t) * round_to<T>(1.0f + sc[j])) + sh[j];

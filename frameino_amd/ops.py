@@ -1472,6 +1472,55 @@ def magcache_calibrate(x_out, x_in, r_prev, r_new, stats):
     return r_new
 
 
+_TEACACHE_WS = {}                          # (device, stream) -> the partials' workspace (bytes)
+
+
+def teacache_probe(x, plane, stats, shift=None, scale=None, sel=None, eps=1e-6, compare=True):
+    """TeaCache's probe (fino_teacache_probe): m = T(LN(x) * (1 + scale[sel]) + shift[sel]), bit for bit `adaln_modulate`'s
+    (shift and scale None: the plain mode, m = x); with `compare` stats[0] = sum |m - p| and stats[1] = sum |p| against the
+    p that `plane` held -- row sums over the rounded values in fp32, sums over rows in fp64 --, without it (0, 0) and the plane is
+    not read; then plane = m, in place.  Row-strided [rows, D] bf16 / fp16 operands; shift / scale fp32 [R, D] views of one
+    table, as `adaln_modulate` takes them; `stats` a caller-owned fp64 device tensor [2].  Nothing is read back: the call adds
+    no host sync.  Deterministic bit for bit.  -> plane"""
+    dt = x.dtype
+    _dt(x)
+    _rows_of(x, dt, "teacache_probe x")
+    if _rows_of(plane, dt, "teacache_probe plane").shape != x.shape or plane.device != x.device:
+        raise ValueError(f"teacache_probe: plane is {tuple(plane.shape)} on {plane.device}, want {tuple(x.shape)} on {x.device}")
+    if (not stats.is_cuda or stats.dtype != torch.float64 or tuple(stats.shape) != (2,) or stats.stride(0) != 1
+            or stats.device != x.device):
+        raise ValueError(f"teacache_probe: stats must be a contiguous fp64 [2] tensor on {x.device}, got "
+                         f"{tuple(stats.shape)} {stats.dtype} on {stats.device}")
+    if (shift is None) != (scale is None):
+        raise ValueError("teacache_probe: shift and scale come together (both None: the plain mode)")
+    if shift is None and sel is not None:
+        raise ValueError("teacache_probe: a selector needs shift and scale")
+    rows, d = x.shape
+    if rows < 1:
+        raise ValueError("teacache_probe: no rows")
+    ms = 0
+    if shift is not None:
+        for t, what in ((shift, "shift"), (scale, "scale")):
+            if t.dtype != torch.float32 or t.device != x.device or t.shape[-1] != d or t.stride(-1) != 1 or t.dim() > 2:
+                raise ValueError(f"teacache_probe: {what} must be fp32 [R, {d}] rows on {x.device}, got {tuple(t.shape)} {t.dtype} "
+                                 f"on {t.device}")
+        ms = shift.stride(0) if shift.dim() == 2 else 0
+        if scale.dim() == 2 and scale.stride(0) != ms:
+            raise ValueError("teacache_probe: shift and scale must be views of one table (the same row stride)")
+        if sel is not None and (sel.dtype != torch.int32 or sel.dim() != 1 or sel.shape[0] != rows or sel.stride(0) != 1
+                                or sel.device != x.device):
+            raise ValueError(f"teacache_probe: sel must be a contiguous int32 [{rows}] tensor on {x.device}")
+    need = _lib.lib().fino_teacache_workspace_bytes(rows)
+    key = (str(x.device), _stream())        # two CFG branches on two streams never share the partials
+    ws = _TEACACHE_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _TEACACHE_WS[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().fino_teacache_probe(_p(x), x.stride(0), _p(plane), plane.stride(0), rows, d, _p(shift), _p(scale), ms,
+                                              _p(sel), eps, int(bool(compare)), _dt(x), _p(stats), _p(ws), ws.numel(), _stream()),
+               "fino_teacache_probe")
+    return plane
+
+
 def pab_broadcast(x, y, gate=None, sel=None, out=None):
     """out = T(fma(float(y), gate[sel], float(x))) (gate None: T(x + y)): the gated-residual epilogue of `gemm` applied to a
     cached y, bit for bit what the GEMM that produced y wrote (fino_pab_broadcast; `gated_residual` rounds y * gate first).

@@ -126,7 +126,7 @@ class DenoisePipelineBase(LoraPipelineMixin, GuiderPipelineMixin):
     # ---- the checks before any launch ----
     def _step_cache_check(self, batch=1):
         """the limits of the step caches (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache,
-        region-adaptive sampling), checked before any work (and before any collective: a parallel plan and the cache are
+        TeaCache, region-adaptive sampling), checked before any work (and before any collective: a parallel plan and the cache are
         configured by the same script on every rank, so every rank raises).  -> whether one is enabled: the loop then runs eagerly"""
         if not getattr(self.transformer, "is_cache_enabled", False):
             return False

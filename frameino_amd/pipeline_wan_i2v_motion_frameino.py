@@ -36,6 +36,11 @@ call into `transformer.magcache_calibration`) likewise: the eager loop, one GPU,
 sample; its decisions depend on the step counter and the curve alone.  A call whose step count differs from the config's
 `num_inference_steps` warns: the curve is indexed by the step counter.
 
+TeaCache (`enable_cache(TeaCacheConfig(coefficients=poly, num_inference_steps=N))`; `calibrate=True` records what the polynomial
+is fitted to into `transformer.teacache_calibration`) likewise: the eager loop, one GPU, fresh state per `denoise`, a batch sample
+by sample; its decisions depend on what each step's probe measures, read on the host once per forward.  A call whose step count
+differs from the config's `num_inference_steps` warns: the last step, which always computes, is counted from the config's figure.
+
 Region-adaptive sampling (`enable_cache(RegionAdaptiveSamplingConfig(sample_ratio=0.5, num_inference_steps=N))`) likewise: the
 eager loop, one GPU, fresh state per `denoise`, a batch sample by sample; which steps run every token row depends on the step
 counter alone, which rows a partial step runs on the kept prediction (on the device: no host read).  The batched CFG call shares
@@ -451,7 +456,7 @@ class WanImageToVideoPipeline(DenoisePipelineBase):
         """reference :809-913.  Returns the final latents [B, C, F, h, w] fp32.  The loop state is one sample's (the app
         and the evaluation scripts run batch 1); a batch -- a list of prompts, num_videos_per_prompt > 1 -- runs sample by sample:
         the samples of the reference's batched loop never meet, every one sees the noise row `prepare_latents` drew for it.
-        With a step cache (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache, region-adaptive sampling) every call -- every sample -- starts from fresh
+        With a step cache (first-block caching, Pyramid Attention Broadcast, TaylorSeer, FasterCache, MagCache, TeaCache, region-adaptive sampling) every call -- every sample -- starts from fresh
         cache state."""
         cached, win_eager, guider = self._loop_checks(latents.shape[0])
         if latents.shape[0] > 1:

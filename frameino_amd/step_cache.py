@@ -1,13 +1,13 @@
 """Step caching of the Wan DiT: diffusers' `CacheMixin` (diffusers/models/cache_utils.py), which the reference's
 WanTransformer3DModel inherits (architecture/transformer_wan.py:28, :353) and whose state its FrameINO loop keys by
-`cache_context("cond")` / `("uncond")` (pipelines/pipeline_wan_i2v_motion_FrameINO.py:862, :873), with five of its configs:
+`cache_context("cond")` / `("uncond")` (pipelines/pipeline_wan_i2v_motion_FrameINO.py:862, :873), with six of its configs:
 `FirstBlockCacheConfig` (diffusers/hooks/first_block_cache.py), `PyramidAttentionBroadcastConfig`
 (diffusers/hooks/pyramid_attention_broadcast.py), `TaylorSeerCacheConfig` (diffusers/hooks/taylorseer_cache.py),
-`FasterCacheConfig` (diffusers/hooks/faster_cache.py) and `MagCacheConfig` (diffusers/hooks/mag_cache.py).  One at a
-time: a second `enable_cache` raises, as in diffusers.
+`FasterCacheConfig` (diffusers/hooks/faster_cache.py), `MagCacheConfig` (diffusers/hooks/mag_cache.py) and `TeaCacheConfig`.
+One at a time: a second `enable_cache` raises, as in diffusers.
 
 Layout.  Every config has ONE policy class below (`_FirstBlockPolicy`, `_PabPolicy`, `_TaylorSeerPolicy`, `_FasterCachePolicy`,
-`_MagCachePolicy`) that
+`_MagCachePolicy`, `_TeaCachePolicy`) that
 states what is particular to it -- the attributes a duck-typed config must carry, its validation, its enable-time warnings and
 defaults, its label in messages, why a captured step cannot contain it, whether a batch may run under it, whether it takes over
 the attention branches -- and the entry points a forward asks (`segments` around the stack's first block, `lite` around the whole
@@ -124,6 +124,30 @@ buffer, which is read ONCE, when the context starts over or the state is reset, 
 (`save_mag_ratios` / `load_mag_ratios`).  cos_dist is report-only.  `cache_log` gets `(context, s, computed, acc_err, acc_steps)`, the
 accumulators after the decision; `(context, s, True, None, None)` in calibrate mode.  The model asks `_magcache_begin` for a forward's
 decisions and `_magcache_finish` after the stack.
+
+TeaCache (`TeaCacheConfig`).  This project's restatement (diffusers is not installed where this is built, so parity with it is
+unpinned by construction, as for MagCache): the rule below is the contract, and the decision sits in one pure function,
+`teacache_decide`, with no tensor in it.  Like MagCache it skips the WHOLE block stack of a step and re-uses the stack's residual
+r = T(x_out - h0) of the last computing forward, T(h0 + r); unlike MagCache it decides from the data, and unlike first-block
+caching BEFORE block 0 runs.  Per context, N = num_inference_steps, s = the 0-based count of forwards, h0 = the stack's input:
+
+    m = T(LN(h0) * (1 + scale[sel]) + shift[sel])    block 0's norm1 modulation, bit for bit ops.adaln_modulate's
+    d = sum|float(m) - float(p)| / sum|float(p)|     p = the context's plane of its previous forward; two fp64 sums, the quotient
+                                                     in Python float; the plane becomes m on EVERY forward
+    compute  if  calibrate  or  no plane / residual yet  or  s < ret_steps  or  s >= cutoff_steps (None: N - 1)       acc = 0
+    otherwise acc += P(d)  (Horner in Python float, `coefficients` highest power first, as numpy.poly1d)
+    skip  iff  acc < rel_l1_thresh and fewer than max_skip_steps (None: no cap) forwards were skipped in a row,
+    else compute and acc = 0         (a NaN or inf d computes)
+
+One launch per segment (ops.teacache_probe) forms m, measures it against the plane and stores it over the plane; the host reads
+the sums of all segments of the call ONCE, and not at all when every segment computes unconditionally.  `coefficients`: 1 to 8
+finite floats, or a mapping from cache context to such a sequence (an unnamed context takes the "cond" entry).  When s reaches N
+the context starts over.  In calibrate mode every forward computes, the input sums and the same two sums over the head's output
+rows (the probe's plain mode) go into row s of a [N, 4] fp64 device buffer, which is read ONCE, when the context starts over or
+the state is reset, and filed as `teacache_calibration[context] = {"rel_l1_in", "rel_l1_out"}` (`fit_teacache_coefficients`,
+`save_teacache` / `load_teacache`).  `cache_log` gets `(context, s, computed, d, acc)`: d None where nothing was compared, acc the
+value after the decision.  The model asks `_teacache_begin` before the embedding, `_teacache_probe` after it, `_teacache_finish`
+after the stack and `_teacache_head` after the output head.
 
 Region-adaptive sampling (`RegionAdaptiveSamplingConfig`, a config of this project; after RAS, Liu et al. 2025, "Region-Adaptive
 Sampling for Diffusion Transformers").  The one policy that removes work along the TOKEN axis: a partial forward runs only the La
@@ -250,6 +274,25 @@ class MagCacheConfig:
 
 
 @dataclasses.dataclass
+class TeaCacheConfig:
+    """TeaCache (Liu et al. 2024, "Timestep Embedding Tells: It's Time to Cache for Video Diffusion Model"): the whole block
+    stack of a step is skipped -- its output is its input plus the stack's residual of the last computing step -- while the
+    accumulated estimate of the output's change stays below `rel_l1_thresh`.  The estimate of one step is a polynomial
+    (`coefficients`, highest power first, as numpy.poly1d; a sequence of 1 to 8 floats or a mapping from cache context to one)
+    of the relative L1 distance between this step's timestep-modulated input of block 0 and the previous step's.  The first
+    `ret_steps` forwards and those from `cutoff_steps` on (None: the last of `num_inference_steps`) always compute;
+    `max_skip_steps` caps the skips in a row (None: no cap).  `calibrate=True` runs every step and records the pairs the
+    polynomial is fitted to (`model.teacache_calibration`, `fit_teacache_coefficients`)."""
+    rel_l1_thresh: float = 0.2
+    coefficients: Any = None
+    num_inference_steps: int = 50
+    ret_steps: int = 1
+    cutoff_steps: Optional[int] = None
+    max_skip_steps: Optional[int] = None
+    calibrate: bool = False
+
+
+@dataclasses.dataclass
 class RegionAdaptiveSamplingConfig:
     """Region-adaptive sampling (a config of this project, not of diffusers): on most steps only a fixed fraction of the token
     rows -- those whose prediction is moving most -- run through the model; the rest keep their last prediction and serve the
@@ -268,8 +311,11 @@ class RegionAdaptiveSamplingConfig:
     always_active: Optional[torch.Tensor] = None
 
 
-# the other configs diffusers' CacheMixin applies: recognised, not implemented here
-_OTHER_DIFFUSERS_CONFIGS = ("TeaCacheConfig",)
+# the other configs diffusers' CacheMixin applies: recognised, not implemented here (none is left)
+_OTHER_DIFFUSERS_CONFIGS = ()
+_TEA_DEFAULTS = {f.name: f.default for f in dataclasses.fields(TeaCacheConfig)}
+TEA_FORMAT = "frameino_amd.teacache"
+TEA_MAX_COEFFICIENTS = 8
 _MAG_DEFAULTS = {f.name: f.default for f in dataclasses.fields(MagCacheConfig)}
 MAG_FORMAT = "frameino_amd.mag_ratios"
 _FASTER_DEFAULTS = {f.name: f.default for f in dataclasses.fields(FasterCacheConfig)}
@@ -441,6 +487,132 @@ def load_mag_ratios(path):
     return {name: [float(v) for v in entry["mag_ratios"]] for name, entry in d["contexts"].items()}
 
 
+def _tc(cfg, name):
+    """a field of a TeaCache config, the default where a duck-typed object lacks it"""
+    return getattr(cfg, name, _TEA_DEFAULTS[name])
+
+
+TEA_FRESH = (0.0, 0, False)             # (acc, skipped in a row, ready) of a context that starts over
+
+
+def teacache_coefficients(cfg, context="cond"):
+    """the polynomial of cache context `context`, highest power first: `coefficients` itself, or its entry of a per-context
+    mapping -- for a context the mapping does not name, its "cond" entry, ValueError if it has none; None in calibrate mode
+    without coefficients"""
+    coef = _tc(cfg, "coefficients")
+    if coef is None:
+        return None
+    if hasattr(coef, "keys"):
+        if context in coef:
+            coef = coef[context]
+        elif "cond" in coef:
+            coef = coef["cond"]
+        else:
+            raise ValueError(f"TeaCacheConfig.coefficients names the cache contexts {sorted(coef.keys())}: no polynomial for "
+                             f"context {context!r} and no \"cond\" entry to use instead")
+    return [float(v) for v in (coef.tolist() if isinstance(coef, torch.Tensor) else coef)]
+
+
+def teacache_poly(coefficients, d):
+    """P(d) by Horner's scheme in Python float, `coefficients` highest power first (numpy.poly1d's order)"""
+    p = 0.0
+    for c in coefficients:
+        p = p * d + c
+    return p
+
+
+def teacache_cutoff(cfg):
+    """forwards from this one on always compute: `cutoff_steps`, None = num_inference_steps - 1 (the last step)"""
+    cut = _tc(cfg, "cutoff_steps")
+    return int(_tc(cfg, "num_inference_steps")) - 1 if cut is None else int(cut)
+
+
+def teacache_unconditional(s, state, cfg):
+    """True: forward `s` computes whatever the data say -- in calibrate mode, without a plane or a residual, during the first
+    `ret_steps` forwards and from `cutoff_steps` on.  Such a forward compares nothing, so nothing is read on the host."""
+    return bool(_tc(cfg, "calibrate")) or not state[2] or s < int(_tc(cfg, "ret_steps")) or s >= teacache_cutoff(cfg)
+
+
+def teacache_decide(s, state, cfg, d, context="cond"):
+    """(compute, state') of forward `s` (0-based, per cache context) from state = (acc, skipped in a row, ready) and the
+    relative L1 distance `d` of this forward's modulated input to the previous one's (None: nothing was compared).  A function
+    of numbers alone: no tensor in it.  An unconditional compute (`teacache_unconditional`) sets acc = 0.  Otherwise
+    acc += P(d) with the context's polynomial; skip iff acc < rel_l1_thresh and fewer than `max_skip_steps` forwards were
+    skipped in a row (None: no cap), else compute and acc = 0.  A NaN or inf d computes: a skip needs acc < thresh to be true.
+    Every forward leaves `ready` set: it stores the plane, and the first one of a context computes and stores the residual."""
+    acc, skipped, _ = state
+    if teacache_unconditional(s, state, cfg) or d is None:
+        return True, (0.0, 0, True)
+    acc = acc + teacache_poly(teacache_coefficients(cfg, context), float(d))
+    cap = _tc(cfg, "max_skip_steps")
+    if acc < float(_tc(cfg, "rel_l1_thresh")) and (cap is None or skipped < int(cap)):
+        return False, (acc, skipped + 1, True)
+    return True, (0.0, 0, True)
+
+
+def fit_teacache_coefficients(calibrations, degree=4):
+    """{context: [degree + 1 coefficients, highest power first]} from one or more calibrating runs
+    (`model.teacache_calibration`: {context: {"rel_l1_in": [...], "rel_l1_out": [...]}}; a list of such dicts pools the runs per
+    context): numpy.polyfit of the output's relative L1 change over the modulated input's, over every step that has both
+    (a context's first step compares nothing and is left out)."""
+    import numpy as np
+    runs = [calibrations] if hasattr(calibrations, "keys") else list(calibrations)
+    pairs = {}
+    for run in runs:
+        for name, entry in run.items():
+            xs, ys = entry["rel_l1_in"], entry["rel_l1_out"]
+            if len(xs) != len(ys):
+                raise ValueError(f"fit_teacache_coefficients: context {name!r}: {len(xs)} input and {len(ys)} output distances")
+            for x, y in zip(xs, ys):
+                if x is not None and y is not None and x == x and y == y and abs(x) != float("inf") and abs(y) != float("inf"):
+                    pairs.setdefault(str(name), []).append((float(x), float(y)))
+    degree = int(degree)
+    if not 0 <= degree < TEA_MAX_COEFFICIENTS:
+        raise ValueError(f"fit_teacache_coefficients: degree = {degree}: 0 .. {TEA_MAX_COEFFICIENTS - 1}")
+    out = {}
+    for name, pts in pairs.items():
+        if len(pts) <= degree:
+            raise ValueError(f"fit_teacache_coefficients: context {name!r} has {len(pts)} measured steps, a polynomial of degree "
+                             f"{degree} needs more than {degree}")
+        x, y = np.asarray(pts, dtype=np.float64).T
+        out[name] = [float(c) for c in np.polyfit(x, y, degree)]
+    if not out:
+        raise ValueError("fit_teacache_coefficients: no measured step in the calibration")
+    return out
+
+
+def save_teacache(path, coefficients=None, calibration=None):
+    """per-context polynomials ({context: [...]}, or one sequence, filed under "cond") and / or the measurements of a calibrating
+    run (`model.teacache_calibration`) as plain JSON"""
+    ctxs = {}
+    if coefficients is not None:
+        coefficients = coefficients if hasattr(coefficients, "keys") else {"cond": coefficients}
+        for name, coef in coefficients.items():
+            ctxs.setdefault(str(name), {})["coefficients"] = [float(v) for v in coef]
+    for name, entry in (calibration or {}).items():
+        for k in ("rel_l1_in", "rel_l1_out"):
+            ctxs.setdefault(str(name), {})[k] = [None if v is None else float(v) for v in entry[k]]
+    with open(path, "w") as f:
+        json.dump({"format": TEA_FORMAT, "version": 1, "contexts": ctxs}, f, indent=1)
+
+
+def load_teacache(path):
+    """-> {context: [coefficients]} as `save_teacache` wrote it: what `TeaCacheConfig(coefficients=...)` takes.  A file that
+    holds measurements alone is fitted first (`fit_teacache_coefficients`, degree 4)."""
+    with open(path) as f:
+        d = json.load(f)
+    if not isinstance(d, dict) or d.get("format") != TEA_FORMAT or not isinstance(d.get("contexts"), dict):
+        raise ValueError(f"{path}: not a file of save_teacache")
+    ctxs = d["contexts"]
+    out = {name: [float(v) for v in entry["coefficients"]] for name, entry in ctxs.items() if "coefficients" in entry}
+    rest = {name: entry for name, entry in ctxs.items() if name not in out and "rel_l1_in" in entry}
+    if rest:
+        out.update(fit_teacache_coefficients(rest))
+    if not out:
+        raise ValueError(f"{path}: neither coefficients nor measurements in it")
+    return out
+
+
 def pab_decide(iteration, timestep, has_cache, block_skip_range, timestep_skip_range):
     """True: the attention module computes on this forward; False: it hands out its cached output."""
     lo, hi = timestep_skip_range
@@ -534,6 +706,10 @@ class _CachePolicy:
     @staticmethod
     def ras(model, b, n, d, d_out, dtype, device, contexts, live, active_rows):
         """along the token axis of the whole forward (region-adaptive sampling): a plan"""
+
+    @staticmethod
+    def teacache(model, b, n, d, dtype, device, contexts):
+        """around the block stack like `magcache`, decided after the embedding from a probe of block 0's input: a plan"""
 
 
 class _FirstBlockPolicy(_CachePolicy):
@@ -738,6 +914,60 @@ class _MagCachePolicy(_CachePolicy):
         return model._magcache_begin(b, n, d, dtype, device, contexts)
 
 
+class _TeaCachePolicy(_CachePolicy):
+    name = "TeaCacheConfig"
+    required = ("rel_l1_thresh", "coefficients", "num_inference_steps")
+    label = "TeaCache"
+    why_eager = ("whether a step runs its block stack or re-uses the last residual is decided on the host from what the step's "
+                 "probe measured")
+
+    @staticmethod
+    def validate(config, model):
+        """ValueError for a field outside its range, coefficients that are no polynomial, or neither coefficients nor
+        `calibrate`"""
+        v = config.rel_l1_thresh
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= v < float("inf")):
+            raise ValueError(f"TeaCacheConfig.rel_l1_thresh = {v!r}: need a finite number of at least 0")
+        for name, lo, optional in (("num_inference_steps", 1, False), ("ret_steps", 0, False), ("cutoff_steps", 0, True),
+                                   ("max_skip_steps", 0, True)):
+            v = _tc(config, name)
+            if v is None and optional:
+                continue
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+                raise ValueError(f"TeaCacheConfig.{name} = {v!r}: need an integer of at least {lo}" + (" or None" if optional else ""))
+        coef = config.coefficients
+        if coef is None:
+            if not _tc(config, "calibrate"):
+                raise ValueError("TeaCacheConfig.coefficients is None and calibrate is False: TeaCache needs the model's polynomial.  "
+                                 "Run the clip once with TeaCacheConfig(calibrate=True, num_inference_steps=N), fit "
+                                 "`transformer.teacache_calibration` (fit_teacache_coefficients; save_teacache / load_teacache) and "
+                                 "pass the result as `coefficients`.")
+            return
+        if hasattr(coef, "keys") and not len(coef):
+            raise ValueError("TeaCacheConfig.coefficients is an empty mapping: need one polynomial per cache context")
+        for ctx, poly in (coef.items() if hasattr(coef, "keys") else ((None, coef),)):
+            where = "TeaCacheConfig.coefficients" + ("" if ctx is None else f"[{ctx!r}]")
+            try:
+                values = [float(c) for c in (poly.tolist() if isinstance(poly, torch.Tensor) else poly)]
+            except (TypeError, ValueError):
+                raise ValueError(f"{where} = {poly!r}: need a sequence of floats, highest power first") from None
+            if not 1 <= len(values) <= TEA_MAX_COEFFICIENTS or not all(abs(c) < float("inf") for c in values):
+                raise ValueError(f"{where}: need 1 to {TEA_MAX_COEFFICIENTS} coefficients, every one finite")
+
+    @staticmethod
+    def loop_begins(config, num_steps):
+        planned = int(config.num_inference_steps)
+        if planned != num_steps:            # once per call: the last step and the start-over are counted from the config's figure
+            warnings.warn(f"TeaCache: this call runs {num_steps} steps, the config says num_inference_steps={planned}; the "
+                          f"forwards that always compute (`cutoff_steps`, None = {planned} - 1) are misaligned with the loop and "
+                          f"a context starts over after {planned} forwards.  Build the config with the call's step count.",
+                          stacklevel=4)
+
+    @staticmethod
+    def teacache(model, b, n, d, dtype, device, contexts):
+        return model._teacache_begin(b, n, d, dtype, device, contexts)
+
+
 class _RegionAdaptivePolicy(_CachePolicy):
     name = "RegionAdaptiveSamplingConfig"
     required = ("sample_ratio", "full_step_interval", "warmup_steps", "full_steps_at_end", "num_inference_steps",
@@ -788,7 +1018,7 @@ class _RegionAdaptivePolicy(_CachePolicy):
 
 
 _POLICIES = {p.name: p for p in (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy, _MagCachePolicy,
-                                 _RegionAdaptivePolicy)}
+                                 _TeaCachePolicy, _RegionAdaptivePolicy)}
 
 
 # ---------------------------------------------------------------------- one plan for the attention branches of a forward
@@ -897,10 +1127,13 @@ class StepCacheMixin:
     FasterCache: a counter, the self-attention planes, the context's last prediction (by reference) and, for "uncond", the
     delta and its weights; log rows `(context, i, t, stack_ran, attention_computed)`.
     MagCache: a counter, the three accumulators, the stack's residual [rows, D] and, in calibrate mode, the [N, 2] fp64 rows;
-    log rows `(context, s, computed, acc_err, acc_steps)`."""
+    log rows `(context, s, computed, acc_err, acc_steps)`.
+    TeaCache: a counter, (acc, skips in a row, ready), the modulated-input plane [rows, D], the stack's residual [rows, D] and,
+    in calibrate mode, the head-row plane and the [N, 4] fp64 rows; log rows `(context, s, computed, d, acc)`."""
     _cache_policies = (_FirstBlockPolicy, _PabPolicy, _TaylorSeerPolicy, _FasterCachePolicy, _MagCachePolicy,
-                       _RegionAdaptivePolicy)
+                       _TeaCachePolicy, _RegionAdaptivePolicy)
     magcache_calibration = None     # {context: {"mag_ratios": [...], "cos_dist": [...]}} once a calibrating context finished
+    teacache_calibration = None     # {context: {"rel_l1_in": [...], "rel_l1_out": [...]}} likewise
     _step_cache_config = None
     _step_cache_policy = None
     _step_cache_states = None
@@ -950,6 +1183,7 @@ class StepCacheMixin:
         forward starts a new `cache_log`.  A calibrating MagCache context files what it has recorded first."""
         for name, st in (self._step_cache_states or {}).items():
             self._magcache_file(name, st)
+            self._teacache_file(name, st)
         self._step_cache_states = {}
         self._step_cache_log_fresh = True
 
@@ -960,6 +1194,7 @@ class StepCacheMixin:
     _faster_on = property(lambda self: self._step_cache_policy is _FasterCachePolicy)
     _faster_attention = property(lambda self: self._faster_on and _FasterCachePolicy.hooks_attention(self._step_cache_config))
     _mag_on = property(lambda self: self._step_cache_policy is _MagCachePolicy)
+    _tea_on = property(lambda self: self._step_cache_policy is _TeaCachePolicy)
     _ras_on = property(lambda self: self._step_cache_policy is _RegionAdaptivePolicy)
 
     # ---------------------------------------------------------------- used by the forward
@@ -1288,6 +1523,113 @@ class StepCacheMixin:
         rows = stats[:st.steps].tolist()
         self.magcache_calibration = dict(self.magcache_calibration or {})
         self.magcache_calibration[name] = {"mag_ratios": [r[0] for r in rows], "cos_dist": [r[1] for r in rows]}
+
+    # ---------------------------------------------------------------- TeaCache
+    def _teacache_begin(self, b, n, d, dtype, device, contexts=None):
+        """One forward under TeaCache, before anything is launched: None when it is off, else a plan with `.calibrate` and
+        `.segs` = one entry per row segment with `.name`, `.r0`, `.r1`, `.state`, `.s` (this forward's number),
+        `.unconditional` (it computes whatever the probe measures: `teacache_unconditional`) and `.compute` -- None here: the
+        decision needs the embedding (`_teacache_probe`).  Advances every context's counter.  A context whose rows, width,
+        dtype or device changed starts over, and so does one whose counter has reached `num_inference_steps`."""
+        if not self._tea_on:
+            return None
+        cfg = self._step_cache_config
+        segs = self._context_segments(b, n, contexts)
+        for name, _, _ in segs:                 # (an unnamed context raises before anything counts)
+            teacache_coefficients(cfg, name)
+        steps, calibrate = int(_tc(cfg, "num_inference_steps")), bool(_tc(cfg, "calibrate"))
+        plan = SimpleNamespace(segs=[], calibrate=calibrate, steps=steps, d=d, dtype=dtype, device=device)
+        for name, r0, r1 in segs:
+            fresh = lambda: dict(acc=TEA_FRESH, plane=None, residual=None, tea_stats=None, out_plane=None)      # noqa: E731
+            st = self._cache_state(name, (r1 - r0, d, dtype, str(device)), fresh)
+            if st.steps >= steps:
+                self._teacache_start_over(name)
+                st = self._cache_state(name, (r1 - r0, d, dtype, str(device)), fresh)
+            s = st.steps
+            st.steps += 1
+            plan.segs.append(SimpleNamespace(name=name, r0=r0, r1=r1, state=st, s=s, compute=None,
+                                             unconditional=teacache_unconditional(s, st.acc, cfg)))
+        return plan
+
+    def _teacache_probe(self, plan, h0, shift, scale, sel, eps):
+        """after the embedding, h0 = the stack's input [rows, D]; shift / scale / sel / eps: block 0's `norm1` modulation as
+        `ops.adaln_modulate` takes it.  One probe launch per segment (ops.teacache_probe) leaves the modulated input in the
+        context's plane and the two sums of its distance to the previous one on the device; ONE host read covers every
+        segment of the call -- none when every segment computes unconditionally --, then `teacache_decide` per segment and
+        `(context, s, computed, d, acc)` to `cache_log`.  In calibrate mode the sums go straight into row s of the context's
+        [N, 4] fp64 device buffer and nothing is read."""
+        o, cfg = self.ops, self._step_cache_config
+        sums = torch.empty((len(plan.segs), 2), dtype=torch.float64, device=plan.device)      # (every launch writes its row)
+        for i, seg in enumerate(plan.segs):
+            st, r0, r1 = seg.state, seg.r0, seg.r1
+            had = st.plane is not None
+            if not had:
+                st.plane = torch.empty((r1 - r0, plan.d), dtype=plan.dtype, device=plan.device)
+            stats = sums[i]
+            if plan.calibrate:              # row s = (sum |m - p|, sum |p|, the same two over the head's rows); step 0: zeros
+                if st.tea_stats is None:
+                    st.tea_stats = torch.zeros((plan.steps, 4), dtype=torch.float64, device=plan.device)
+                stats = st.tea_stats[seg.s, 0:2]
+            o.teacache_probe(h0[r0:r1], st.plane, stats, shift, scale, None if sel is None else sel[r0:r1], eps,
+                             compare=had and (plan.calibrate or not seg.unconditional))
+        host = None if all(seg.unconditional for seg in plan.segs) else sums.tolist()        # the host read
+        for i, seg in enumerate(plan.segs):
+            st, dist = seg.state, None
+            if not seg.unconditional:
+                sa, sq = host[i]
+                dist = sa / sq if sq else (float("inf") if sa else float("nan"))
+            seg.compute, st.acc = teacache_decide(seg.s, st.acc, cfg, dist, seg.name)
+            self.cache_log.append((seg.name, seg.s, seg.compute, dist, st.acc[0]))
+
+    def _teacache_finish(self, plan, x, x_in):
+        """after the last block (or right after the probe when every segment skips), x_in = the stack's input [rows, D]: a
+        computing segment stores the stack's residual T(x - x_in), a skipping one takes T(x_in + r) as the stack's output, its
+        residual untouched"""
+        o = self.ops
+        for seg in plan.segs:
+            st, r0, r1 = seg.state, seg.r0, seg.r1
+            if seg.compute:
+                if st.residual is None:
+                    st.residual = torch.empty((r1 - r0, plan.d), dtype=plan.dtype, device=plan.device)
+                o.step_cache_residual(x[r0:r1], x_in[r0:r1], out=st.residual, subtract=True)
+            else:
+                if st.residual is None:
+                    raise KeyError(f"TeaCache: no residual under context {seg.name!r}")
+                o.step_cache_residual(st.residual, x_in[r0:r1], out=x[r0:r1], subtract=False)
+
+    def _teacache_head(self, plan, po):
+        """after the output head, po = its rows [rows, C_out * prod(patch)]: a calibrating run measures them against the previous
+        forward's (the probe's plain mode, into columns 2 and 3 of row s; nothing is read here).  A context whose counter has
+        reached `num_inference_steps` starts over."""
+        for seg in plan.segs:
+            st = seg.state
+            if plan.calibrate:
+                had = st.out_plane is not None
+                if not had:
+                    st.out_plane = torch.empty((seg.r1 - seg.r0, po.shape[1]), dtype=po.dtype, device=po.device)
+                self.ops.teacache_probe(po[seg.r0:seg.r1], st.out_plane, st.tea_stats[seg.s, 2:4], compare=had)
+            if st.steps >= plan.steps and self._step_cache_states.get(seg.name) is st:
+                self._teacache_start_over(seg.name)
+
+    def _teacache_start_over(self, name):
+        """context `name` has run its `num_inference_steps` forwards: counter 0, accumulator reset, plane and residual dropped;
+        a calibrating context files its measurements first"""
+        st = self._step_cache_states.pop(name, None)
+        if st is not None:
+            self._teacache_file(name, st)
+
+    def _teacache_file(self, name, st):
+        """`teacache_calibration[name]` from the rows a calibrating context has recorded: the ONE host read of a calibrating
+        call (per context), when the context starts over or the state is reset.  Entry s is the relative L1 distance of forward
+        s to forward s - 1, of the modulated input and of the head's output rows; None where nothing was compared (s = 0)."""
+        stats = getattr(st, "tea_stats", None)
+        if stats is None or st.steps < 1:
+            return
+        rows = stats[:st.steps].tolist()
+        quot = lambda a, q: a / q if q else None        # noqa: E731
+        self.teacache_calibration = dict(self.teacache_calibration or {})
+        self.teacache_calibration[name] = {"rel_l1_in": [quot(r[0], r[1]) for r in rows],
+                                           "rel_l1_out": [quot(r[2], r[3]) for r in rows]}
 
 
     # ---------------------------------------------------------------- region-adaptive sampling

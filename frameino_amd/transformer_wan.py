@@ -615,12 +615,16 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         if c.lite is not None and not any(seg.compute["self"] for seg in c.lite.segs):
             return self._taylor_lite_rows(c, c.ws.po[:c.nr])                      # TaylorSeer, lite mode: the output rows predicted
         self._embed(c, hidden_states)
+        if c.tea is not None:
+            # TeaCache: block 0's norm1 modulation of h0 against the previous forward's, one host read, the decisions
+            self._teacache_probe(c.tea, c.h0, c.mod[:, 0, 0], c.mod[:, 0, 1], c.sel, c.eps)
         yield
 
         last = len(self.blocks) - 1
-        # MagCache: when every segment re-uses its residual the block stack does not run; when some do, it runs on all rows
-        # (as under first-block caching) and the skipping segments' rows are overwritten afterwards
-        stack = c.mag is None or any(seg.compute for seg in c.mag.segs)
+        # MagCache / TeaCache: when every segment re-uses its residual the block stack does not run; when some do, it runs on
+        # all rows (as under first-block caching) and the skipping segments' rows are overwritten afterwards
+        whole = c.mag if c.mag is not None else c.tea
+        stack = whole is None or any(seg.compute for seg in whole.segs)
         for li, (blk, e) in enumerate(zip(self.blocks, c.pk.layers) if stack else ()):
             m = c.mod[:, li]                                                      # [R, 6, D] view, row stride = layers*6*D
             if c.live is not None and li == last:
@@ -649,6 +653,10 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
             # the stack's residual T(x - h0) of the computing segments, T(h0 + r) for the skipping ones; `live_rows` as under
             # first-block caching: the residual is meaningful on the live rows, which are the rows the head runs on
             self._magcache_finish(c.mag, c.x, c.h0)
+            if c.live is not None:
+                c.segs = c.live_segs
+        if c.tea is not None:               # (likewise)
+            self._teacache_finish(c.tea, c.x, c.h0)
             if c.live is not None:
                 c.segs = c.live_segs
         return self._output_head(c)
@@ -716,12 +724,13 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         # whole forward (region-adaptive sampling).
         # Their decisions are taken here, before any launch (a timestep callback is read once)
         policy = self._step_cache_policy
-        fbc = lite = branches = mag = ras = None
+        fbc = lite = branches = mag = tea = ras = None
         if policy is not None:
             ras = policy.ras(self, b, n, d, cfg.out_channels * math.prod(cfg.patch_size), dt, dev, cache_contexts,
                              _live_range(live_rows, n), active_rows)
             fbc = policy.segments(self, b, n, cache_contexts)
             mag = policy.magcache(self, b, n, d, dt, dev, cache_contexts)        # MagCache: around the whole block stack
+            tea = policy.teacache(self, b, n, d, dt, dev, cache_contexts)        # TeaCache: likewise, decided after the embedding
             lite = policy.lite(self, b, n, cfg.out_channels * math.prod(cfg.patch_size), dt, dev, cache_contexts)
             if lite is not None and not any(seg.compute["self"] for seg in lite.segs):
                 # every segment predicts: no embedding, no block, no head -- the call needs its geometry and the output rows
@@ -764,7 +773,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         # (not under Pyramid Attention Broadcast: a cached branch output covers every row, so that any later step may use it)
         if (live_rows is not None and self.skip_dead_rows and default_procs and sh is None and len(self.blocks) > 1
                 and not self._fp8 and not fp8 and branches is None and lite is None
-                and not (mag is not None and mag.calibrate)):      # (a calibrating MagCache run measures every row's full stack)
+                and not (mag is not None and mag.calibrate)        # (a calibrating MagCache run measures every row's full stack)
+                and not (tea is not None and tea.calibrate)):      # (... and a calibrating TeaCache run every row of the head)
             l0, l1 = int(live_rows[0]), int(live_rows[1])
             if 0 <= l0 < l1 <= n and (l1 - l0) < n:
                 live = (l0, l1)
@@ -776,7 +786,7 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
                      text=text, qfold={"out_scale": dh ** -0.5 * o.LOG2E} if fold else {},
                      afold={"scale": o.SCALE_FOLDED} if fold else {}, fp8=fp8, default_procs=default_procs,
                      shared=shared, fbc=fbc, branches=branches, keep=None, h0=None, h1c=None, attention_kwargs=attention_kwargs,
-                     live=live, win=win, sp=sp, lite=lite, mag=mag, ras=ras, out_buf=out_buf,
+                     live=live, win=win, sp=sp, lite=lite, mag=mag, tea=tea, ras=ras, out_buf=out_buf,
                      live_segs=live and [(bi * n + live[0], bi * n + live[1]) for bi in range(b)],
                      rows=(0, n),            # the rows of every batch element that run as queries / per-token rows ...
                      segs=[(0, nr)])         # ... and the global row ranges the per-token operations of a block run on
@@ -792,8 +802,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
         else:
             a_rows = torch.cat([o.patchify(hidden_states[i], patch) for i in range(b)])
         o.gemm(a_rows, c.pk.w_patch, self.patch_embedding.bias, out=x[:n] if c.shared else x, **c.tk)
-        if c.fbc is not None or c.mag is not None:
-            ws = c.ws                        # h0, and a buffer for the probe's copy of h1 (MagCache keeps h0 alone)
+        if c.fbc is not None or c.mag is not None or c.tea is not None:
+            ws = c.ws                        # h0, and a buffer for the probe's copy of h1 (MagCache and TeaCache keep h0 alone)
             if getattr(ws, "fbc_h0", None) is None:
                 ws.fbc_h0 = torch.empty_like(ws.x)
             if c.fbc is not None and getattr(ws, "fbc_h1", None) is None:
@@ -1182,6 +1192,8 @@ class WanTransformer3DModel(nn.Module, FromPretrainedMixin, LoraModelMixin, Step
             po = sh.all_gather_out(po_loc)[:c.L]
         if c.lite is not None:
             return self._taylor_lite_rows(c, po)
+        if c.tea is not None:                # TeaCache: a calibrating run measures the head's rows; a finished context starts over
+            self._teacache_head(c.tea, po)
         if c.ras is not None:                # a full forward under region-adaptive sampling keeps the head's rows
             st = c.ras.state
             st.po.copy_(po)
@@ -1210,16 +1222,17 @@ class _Call:
     attention branches (`_BranchPlan`: Pyramid Attention Broadcast, TaylorSeer's default mode, FasterCache's self-attention
     part), else None; `lite`: the plan of TaylorSeer's lite mode -- when every segment of it predicts, `_bind` returns a call
     with the geometry, the workspace and the plan alone; `mag`: MagCache's plan for the block stack as a whole (`h0` is then
-    the stack's input, kept by the embedding stage); `ras`: the plan of region-adaptive sampling -- a partial forward runs on
+    the stack's input, kept by the embedding stage); `tea`: TeaCache's, whose decisions are taken after the embedding stage; `ras`: the plan of region-adaptive sampling -- a partial forward runs on
     a second `_Call` over the compact rows (`_ras_partial`)."""
     __slots__ = ("b", "n", "nr", "lo", "lpad", "L", "nf", "hh", "ww", "d", "heads", "dh", "dev", "dt", "eps", "sh", "tk", "pk",
                  "ws", "x", "nrm", "att", "q2", "ff", "qkv", "cos", "sin", "cos1", "sin1", "sel", "mod", "head", "text", "qfold",
                  "afold", "fp8", "default_procs", "shared", "fbc", "branches", "keep", "h0", "h1c", "attention_kwargs", "live",
-                 "live_segs", "rows", "segs", "win", "sp", "lite", "mag", "ras", "out_buf", "elements")
+                 "live_segs", "rows", "segs", "win", "sp", "lite", "mag", "tea", "ras", "out_buf", "elements")
 
     def __init__(self, **fields):
         self.elements = None
         self.ras = None
+        self.tea = None
         for k, v in fields.items():
             setattr(self, k, v)
 

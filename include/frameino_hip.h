@@ -817,6 +817,26 @@ int64_t fino_magcache_workspace_bytes(int64_t rows);
 int fino_magcache_calibrate(const void* x_out, int64_t ld_out, const void* x_in, int64_t ld_in, const void* r_prev,
                             int64_t ld_prev, void* r_new, int64_t ld_new, int64_t rows, int64_t dim, int dtype, double* stats,
                             void* workspace, int64_t workspace_bytes, void* stream);
+/* TeaCache (frameino_amd/step_cache.py), the probe in front of block 0: one pass over HBM that forms the timestep-modulated
+ * input of the first block, measures it against the plane the previous forward left and leaves it there for the next one.
+ * Row-strided [rows, dim] operands of dtype T, modulation rows and selector as in fino_adaln_modulate:
+ *   m = T(LN_fp32(x) * (1 + scale[sel[row]]) + shift[sel[row]])     bit for bit what fino_adaln_modulate writes
+ *   m = x                                                            shift == scale == NULL: the plain mode (sel NULL, eps unused)
+ *   compare != 0:  stats[0] = sum |float(m) - float(p)|,  stats[1] = sum |float(p)|,  p = what `plane` held      fp64 DEVICE doubles
+ *   compare == 0:  stats[0] = stats[1] = 0, the plane is not read
+ *   plane = m                                                        in place: a lane reads and writes the same elements
+ * The sums, not their quotient: the host divides.  One wave holds a row in registers (the row loading and statistics of
+ * fino_adaln_modulate's kernel), forms the row's two sums in fp32 from the rounded values (a lane in sequence, then an xor
+ * butterfly); wave g of the launch takes the rows g, g + W, ... and adds them in that order in fp64 into its partial in
+ * `workspace` (fino_teacache_workspace_bytes(rows) device bytes, 16-byte aligned); a second launch adds the partials in a fixed
+ * order.  W depends on rows alone and there are no atomics: the same inputs give the same bits on every run.  No contraction.
+ * dtype FINO_BF16 | FINO_F16; dim a multiple of 8, at most 4096 (beyond: FINO_ERR_UNSUPPORTED); every row stride >= dim with
+ * 16-byte aligned rows; rows in 1 .. 2^31 - 1; plane must not be x; stats 16-byte aligned.  Every argument error ->
+ * FINO_ERR_ARG before any launch. */
+int64_t fino_teacache_workspace_bytes(int64_t rows);
+int fino_teacache_probe(const void* x, int64_t ldx, void* plane, int64_t ld_plane, int64_t rows, int dim, const float* shift,
+                        const float* scale, int64_t mod_stride, const int32_t* sel, float eps, int compare, int dtype,
+                        double* stats, void* workspace, int64_t workspace_bytes, void* stream);
 /* Pyramid Attention Broadcast (diffusers' hooks/pyramid_attention_broadcast.py; frameino_amd/step_cache.py): a step that
  * re-uses an attention branch adds the cached y = T(acc + bias) of its out-projection (kept by fino_gemm_keep) to the residual
  * stream without running the branch:
